@@ -2,7 +2,7 @@
 """bench.py -- conv-layer forward images/s of the direct-sparse-convolution path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload resnet50|alexnet|googlenet|lenet]
-                    [--global-batch B]
+                    [--global-batch B] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path (escoin_forward, the Forward_gpu drop-in) over one batch
 of synthetic input for every conv layer of the workload.  Default workload = BASELINE.json's
@@ -17,9 +17,22 @@ dimension is sharded, the sparse weights are broadcast once from rank 0 over RCC
 collective sits in the timed region.  Default = weak scaling (256 images per GPU);
 `--global-batch 2048` = BASELINE.json's configs[3] as strong scaling (2048 / N images per GPU).
 
-After the timed region every rank checks images of every distinct layer shape against the CPU
-oracle (`parity_max_rel_err`, the checker only), and for N > 1 rank 0 recomputes two images of
-every other rank and compares them with that rank's per-image checksums.
+A plain run does only what its headline figure needs: set-up (WeightAlign, broadcast, inputs), W
+warm-up steps, the settle loop (--settle-ms), ONE timed region of exactly K steps (`ms_per_step` =
+its wall time / K, `value` = images/s from it), the outputs if --dump-outputs is given, and the
+result line.  `--dump-outputs DIR` writes rank 0's top blob of every layer after the last timed step
+as DIR/top<layer id>_<layer name>.npy (float32; a fixed, seeded sample where the blob is larger
+than its share of 48 MB).  The inputs depend on the arguments only, so two builds can be compared
+output for output.
+
+`--full` adds everything else the benchmark measures or checks, after (never inside) the headline
+region unless said otherwise: K cold steps before the settle loop (`ms_per_step_cold`), R timed
+regions of K steps (--repeats, `value` from the median one) with per-launch events in a sample of
+the steps (`roofline`), a throw-away plan that prices the process's first WeightAlign
+(`first_load_ms`), every rank's images of every distinct layer shape against the CPU oracle
+(`parity_max_rel_err`, the checker only), for N > 1 rank 0's recomputation of two images of every
+other rank against that rank's per-image checksums, the other single-GPU configurations and the
+sparsity sweep (default ResNet run), and the CPU baselines.
 
 Rank 0 prints ONE JSON line on stdout (everything else goes to stderr).
 """
@@ -151,7 +164,7 @@ def _build_layers(be, pkg, synth, shapes, rank, world, args=None, dist_on=None):
     # --force-dist on ONE rank: the process group, the broadcast and the receiver's import all run (rank 0 is its own
     # receiver: it imports the blob it broadcast into a second plan, and THAT plan is the one the step times)
     loopback = dist_on and world == 1
-    if rank == 0 and hasattr(pkg, "Plan") and not test_be(be):
+    if rank == 0 and hasattr(pkg, "Plan") and not test_be(be) and getattr(args, "full", True):
         # The process's first WeightAlign of a generated-code plan also assembles the code object template (once per
         # process, jit_module.cpp) and loads the process's first HIP module: ~90-120 ms that belong to the process,
         # not to a layer.  A throw-away plan of the first layer's shape pays them here, timed on its own line.
@@ -701,6 +714,29 @@ def measure_extras(be, pkg, synth, oracle, budget_s):
     return other, sweep, skipped, round(time.perf_counter() - t0, 1)
 
 
+DUMP_BUDGET_BYTES = 48 << 20      # --dump-outputs: all files together, headers aside (the option promises <= 64 MB)
+
+
+def dump_outputs(be, layers, tops, out_dir):
+    """--dump-outputs: what a caller of the timed path receives -- the top blob of every layer after the last timed
+    step -- as <out_dir>/top<layer id>_<layer name>.npy, float32.  A blob larger than its share of DUMP_BUDGET_BYTES is
+    written as a fixed sample: that many flat indices drawn without replacement by a generator seeded with the layer
+    id, in ascending order -- the same elements in every run with the same arguments.  Returns the file names."""
+    torch = be.torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // max(1, len(layers))
+    names = []
+    for li, (s, plan, bias, si, lid) in enumerate(layers):
+        top = tops[li]
+        if top.numel() > share:
+            idx = np.sort(np.random.default_rng(4099 + lid).choice(top.numel(), share, replace=False))
+            top = top.reshape(-1)[torch.from_numpy(idx).to(top.device)]
+        name = "top%02d_%s.npy" % (lid, s.name)
+        np.save(os.path.join(out_dir, name), top.float().cpu().numpy())
+        names.append(name)
+    return names
+
+
 def test_be(be):
     return be.name != "hip"
 
@@ -773,16 +809,17 @@ def run(args, be, pkg, synth, oracle_loader, dist=None):
             if events is not None:
                 events[li + 1].record()
 
-    # Order of the run: W warm-up steps, then K steps timed COLD (`ms_per_step_cold`: what a caller gets who does exactly
-    # what the command line says -- W untimed steps, K timed ones, nothing else), then the settle loop, then the R timed
-    # regions `value` is computed from.  The chip's clocks take tens of milliseconds of load to settle (the first 100
-    # launches of a layer run 10-15 % slower than the next hundred): with `--warmup 5` the cold region is over before
-    # that.  The settle loop runs the same step untimed for a fixed wall-clock time, outside the W + K steps the command
-    # asks for and declared in the JSON line (`settle_ms`); both numbers are printed so a caller sees both.
+    # Order of the run: W warm-up steps, then (--full only) K steps timed COLD (`ms_per_step_cold`: what a caller gets who
+    # does exactly what the command line says -- W untimed steps, K timed ones, nothing else), then the settle loop, then
+    # the timed region(s) `value` is computed from.  The chip's clocks take tens of milliseconds of load to settle (the
+    # first 100 launches of a layer run 10-15 % slower than the next hundred): with `--warmup 5` the cold region is over
+    # before that.  The settle loop runs the same step untimed for a fixed wall-clock time, outside the W + K steps the
+    # command asks for and declared in the JSON line (`settle_ms`); under --full both numbers are printed.
+    full = bool(getattr(args, "full", True))
     for _ in range(args.warmup):
         step()
     cold_ms = None
-    if not test_be(be):
+    if full and not test_be(be):
         e0, e1 = be.event(), be.event()
         be.synchronize()
         e0.record()
@@ -806,23 +843,25 @@ def run(args, be, pkg, synth, oracle_loader, dist=None):
     n_sampled = min(10, max(2, args.steps // 10)) if args.steps >= 4 else 1
     stride = max(1, args.steps // n_sampled)
     sampled = [k for k in range(args.steps) if k % stride == 0][:n_sampled]
-    if side_streams is not None:
-        sampled = []          # (overlapping launches have no per-launch duration)
-    # R timed regions (--repeats, SURVEY 8d: median of >= 5 repeats), each EXACTLY K steps bracketed by a
-    # barrier + device synchronisation on both sides and reduced with MAX over the ranks; `value` is
-    # computed from the median region, the line also carries the fastest and the slowest one.
+    if side_streams is not None or not full:
+        sampled = []          # (overlapping launches have no per-launch duration; a plain run records no events)
+    # R timed regions (--full: --repeats, SURVEY 8d: median of >= 5 repeats; a plain run: one), each EXACTLY K steps
+    # bracketed by a barrier + device synchronisation on both sides and reduced with MAX over the ranks; `value` is
+    # computed from the median region, under --full the line also carries the fastest and the slowest one.
     regions = []          # (elapsed seconds, step events, per-launch events of the sampled steps)
-    for rep in range(max(1, args.repeats)):
-        step_ev = [be.event() for _ in range(args.steps + 1)]
+    for rep in range(max(1, args.repeats) if full else 1):
+        step_ev = [be.event() for _ in range(args.steps + 1)] if full else None
         ev = {k: [step_ev[k]] + [be.event() for _ in range(len(layers))] for k in sampled}
         if dist_on:
             dist.barrier()
         be.synchronize()
         t0 = time.perf_counter()
         for k in range(args.steps):
-            step_ev[k].record()
+            if step_ev is not None:
+                step_ev[k].record()
             step(ev.get(k))
-        step_ev[args.steps].record()
+        if step_ev is not None:
+            step_ev[args.steps].record()
         be.synchronize()
         elapsed = time.perf_counter() - t0
         if dist_on:
@@ -836,14 +875,22 @@ def run(args, be, pkg, synth, oracle_loader, dist=None):
     elapsed, step_ev, ev = regions[median_region]
     region_ms = [r[0] / args.steps * 1e3 for r in regions]
 
-    # ---- self-check of what was just computed (outside the timed region) ----------------------
-    oracle = oracle_loader()
-    parity = parity_check(be, oracle, synth, layers, bottoms, tops)
-    if dist_on:
-        t = torch.tensor([parity], device=be.device, dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        parity = float(t.item())
-    cross = cross_rank_check(be, dist, synth, layers, shapes, tops, rank, world, g0_of_rank, per_rank)
+    # ---- what the last timed step computed, for a comparison of two builds output for output ----
+    dumped = None
+    if getattr(args, "dump_outputs", None) and rank == 0:
+        dumped = dump_outputs(be, layers, tops, args.dump_outputs)
+        log("bench.py: %d output files in %s" % (len(dumped), args.dump_outputs))
+
+    # ---- self-check of what was just computed (--full; outside the timed region) -------------
+    oracle, parity, cross = None, None, None
+    if full:
+        oracle = oracle_loader()
+        parity = parity_check(be, oracle, synth, layers, bottoms, tops)
+        if dist_on:
+            t = torch.tensor([parity], device=be.device, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            parity = float(t.item())
+        cross = cross_rank_check(be, dist, synth, layers, shapes, tops, rank, world, g0_of_rank, per_rank)
     receive = None
     if dist_on:
         # the slowest receiver's set_csr total and its slowest layer (rank 0 has none: it aligned -- unless it is its
@@ -862,106 +909,108 @@ def run(args, be, pkg, synth, oracle_loader, dist=None):
     if rank != 0:
         return None
 
-    # ---- per-kernel accounting from the events recorded inside the timed region ---------------
-    per_kernel, layer_ms = {}, []
-    step_ms = [step_ev[k].elapsed_time(step_ev[k + 1]) for k in range(args.steps)]
-    plain = [step_ms[k] for k in range(args.steps) if k not in ev]
-    ms_plain = float(np.mean(plain)) if plain else float(np.mean(step_ms))
-    ms_sampled = float(np.mean([step_ms[k] for k in sampled])) if sampled else ms_plain
-    # what one event between two launches costs the launches of a sampled step: their durations, event to
-    # event, add up to this much more than a step without them takes (so the corrected ones add up to it)
-    ms_launches = float(np.mean([ev[k][0].elapsed_time(ev[k][len(layers)]) for k in sampled])) if sampled else ms_plain
-    event_ms = max(0.0, (ms_launches - ms_plain) / len(layers)) if plain and sampled else 0.0
-    # (several streams: launches overlap -- every launch is booked at its algorithmic-byte share of the step, which
-    #  keeps the step's totals right and says nothing about single layers: per_layer is dropped below)
-    total_alg = float(sum(synth.algorithmic_bytes(l[0], per_gpu_batch) for l in layers))
-    layer_ms_raw = []
-    for li, (s, plan, bias, si, lid) in enumerate(layers):
-        ms = [ev[k][li].elapsed_time(ev[k][li + 1]) for k in sampled] if sampled else \
-             [ms_plain * synth.algorithmic_bytes(s, per_gpu_batch) / total_alg]
-        layer_ms_raw.append(float(np.mean(ms)))
-        m = max(float(np.mean(ms)) - event_ms, 1e-6)
-        layer_ms.append(m)
-        # the tiled kernel has a second instantiation for layers whose plane DMA can be issued from
-        # inside the stream walk (escoin_sconv_tiled_dma_kernel<3, 1>): one kernel family, two rows
-        # in a rocprofv3 summary -- "instantiations" below has each row's launches and average
-        fam = plan.kernel_name.replace("_tiled_dma_kernel", "_tiled_kernel")
-        d = per_kernel.setdefault(fam, {"ms": 0.0, "bytes": 0, "flops": 0, "launches": 0, "inst": {}})
-        d["ms"] += m
-        d["bytes"] += synth.algorithmic_bytes(s, per_gpu_batch)
-        d["flops"] += synth.flops(s, per_gpu_batch)
-        d["launches"] += 1
-        i = d["inst"].setdefault(plan.kernel_name, {"ms": 0.0, "launches": 0})
-        i["ms"] += m
-        i["launches"] += 1
-    per_layer, seen = [], {}
+    # ---- per-kernel accounting from the events recorded inside the timed region (--full) --------
     sparsity_pct = round(100 * shapes[0].sparsity)
-    layer_traffic = traffic_per_layer(args.workload, per_gpu_batch, sparsity_pct)
-    seen_raw = {}
-    for li, (s, plan, bias, si, lid) in enumerate(layers):
-        seen.setdefault(si, []).append(layer_ms[li])
-        seen_raw.setdefault(si, []).append(layer_ms_raw[li])
-    for si, s in enumerate(shapes):
-        m = float(np.mean(seen[si]))
-        name = layers[last_layer_of_shape(layers)[si]][1].kernel_name
-        byt, flo = synth.algorithmic_bytes(s, per_gpu_batch), synth.flops(s, per_gpu_batch)
-        t_hbm, t_fma = byt / (HBM_PEAK_GBS * 1e9), flo / (FP32_VECTOR_TFLOPS * 1e12)
-        per_layer.append({"layer": s.name, "count": s.count, "us": round(m * 1e3, 1),
-                          # event to event, nothing taken off (one event between two launches costs `event_us`)
-                          "us_raw": round(float(np.mean(seen_raw[si])) * 1e3, 1),
-                          "alg_GBps": round(byt / m / 1e6, 1), "sparse_TFLOPs": round(flo / m / 1e9, 2),
-                          "hbm_frac": round(t_hbm / (m * 1e-3), 4), "fma_frac": round(t_fma / (m * 1e-3), 4),
-                          "binding_frac": round(max(t_hbm, t_fma) / (m * 1e-3), 4),
-                          "alg_bytes": int(byt),
-                          # PMC (separate run, profiles/traffic_<workload>.json): HBM bytes of this layer's launch
-                          "hbm_traffic": layer_traffic.get(s.name),
-                          "traffic_over_alg": round(layer_traffic[s.name] / byt, 3) if s.name in layer_traffic else None})
-        log("  gpu %-16s %-44s %8.1f us  %7.1f GB/s alg  %6.2f TFLOP/s  binding %.3f  x%d" %
-            (s.name, name, m * 1e3, byt / m / 1e6, flo / m / 1e9, per_layer[-1]["binding_frac"], s.count))
-    dom_name, dom = max(per_kernel.items(), key=lambda kv: kv[1]["ms"])
-    achieved = dom["bytes"] / (dom["ms"] * 1e-3) / 1e9
-    # HBM traffic per launch: the instantiations' PMC figures weighted by their launches
-    traffic, provenance, tw = None, None, 0
-    for iname, iv in dom["inst"].items():
-        tv, pv = traffic_with_provenance(args.workload, iname, per_gpu_batch, sparsity_pct)
-        if tv is None:
-            traffic = None
-            break
-        traffic = (traffic or 0) + tv * iv["launches"]
-        tw += iv["launches"]
-        provenance = pv
-    if traffic is not None and tw:
-        traffic = int(traffic / tw)
-    t_bind = sum(max(synth.algorithmic_bytes(s, per_gpu_batch) / (HBM_PEAK_GBS * 1e9),
-                     synth.flops(s, per_gpu_batch) / (FP32_VECTOR_TFLOPS * 1e12)) * s.count for s in shapes)
-    # (one name per rocprofv3 row: the family's instantiations, most launches first)
-    dom_label = " + ".join(sorted(dom["inst"], key=lambda k: -dom["inst"][k]["launches"]))
-    roofline = {"bound": "hbm", "kernel": dom_label, "achieved": round(achieved, 1),
-                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
-                "traffic": traffic, "traffic_provenance": provenance,
-                # PMC bytes (FETCH_SIZE x 2 + WRITE_SIZE, the fabric side of the L2s: Infinity-Cache hits included) over
-                # the algorithmic bytes, per launch of the dominant kernel over the step: > 1 = re-reads (halo, several
-                # workgroup columns, XCD grouping) and generated code; profiles/r05_mall_share.md says which of it is HBM
-                "traffic_over_alg": round(traffic / (dom["bytes"] / dom["launches"]), 3) if traffic else None,
-                "avg_launch_us": round(dom["ms"] / dom["launches"] * 1e3, 2),
-                "launches_per_step": dom["launches"],
-                # per-launch events in `sampled_steps` of the timed steps; one event costs `event_us`
-                # (sampled minus other steps, per launch), already taken off every duration here
-                # (the corrected per-launch durations must add up to a step without events: a check of the
-                #  correction, not a tunable -- bench lines seen so far sit within 2 % of 1)
-                "launch_sum_over_step": round(sum(layer_ms) / max(1e-9, ms_plain), 4),
-                "events": {"sampled_steps": len(sampled), "of": args.steps, "event_us": round(event_ms * 1e3, 2),
-                           "ms_per_step_sampled": round(ms_sampled, 4), "ms_per_step_other": round(ms_plain, 4)},
-                "instantiations": {k: {"launches_per_step": v["launches"],
-                                       "avg_launch_us": round(v["ms"] / v["launches"] * 1e3, 2)}
-                                   for k, v in dom["inst"].items()},
-                "algorithmic_bytes_per_launch": int(dom["bytes"] / dom["launches"]),
-                "sparse_tflops": round(dom["flops"] / (dom["ms"] * 1e-3) / 1e12, 2),
-                # max(bytes / 8 TB/s, flops / 157.3 TF) summed over the step / measured step time:
-                # the fraction of whichever roofline binds each layer
-                "binding_frac": round(t_bind / (sum(layer_ms) * 1e-3), 4),
-                "per_layer": per_layer if sampled else None,
-                "streams": n_streams}
+    roofline = None
+    if full:
+        per_kernel, layer_ms = {}, []
+        step_ms = [step_ev[k].elapsed_time(step_ev[k + 1]) for k in range(args.steps)]
+        plain = [step_ms[k] for k in range(args.steps) if k not in ev]
+        ms_plain = float(np.mean(plain)) if plain else float(np.mean(step_ms))
+        ms_sampled = float(np.mean([step_ms[k] for k in sampled])) if sampled else ms_plain
+        # what one event between two launches costs the launches of a sampled step: their durations, event to
+        # event, add up to this much more than a step without them takes (so the corrected ones add up to it)
+        ms_launches = float(np.mean([ev[k][0].elapsed_time(ev[k][len(layers)]) for k in sampled])) if sampled else ms_plain
+        event_ms = max(0.0, (ms_launches - ms_plain) / len(layers)) if plain and sampled else 0.0
+        # (several streams: launches overlap -- every launch is booked at its algorithmic-byte share of the step, which
+        #  keeps the step's totals right and says nothing about single layers: per_layer is dropped below)
+        total_alg = float(sum(synth.algorithmic_bytes(l[0], per_gpu_batch) for l in layers))
+        layer_ms_raw = []
+        for li, (s, plan, bias, si, lid) in enumerate(layers):
+            ms = [ev[k][li].elapsed_time(ev[k][li + 1]) for k in sampled] if sampled else \
+                 [ms_plain * synth.algorithmic_bytes(s, per_gpu_batch) / total_alg]
+            layer_ms_raw.append(float(np.mean(ms)))
+            m = max(float(np.mean(ms)) - event_ms, 1e-6)
+            layer_ms.append(m)
+            # the tiled kernel has a second instantiation for layers whose plane DMA can be issued from
+            # inside the stream walk (escoin_sconv_tiled_dma_kernel<3, 1>): one kernel family, two rows
+            # in a rocprofv3 summary -- "instantiations" below has each row's launches and average
+            fam = plan.kernel_name.replace("_tiled_dma_kernel", "_tiled_kernel")
+            d = per_kernel.setdefault(fam, {"ms": 0.0, "bytes": 0, "flops": 0, "launches": 0, "inst": {}})
+            d["ms"] += m
+            d["bytes"] += synth.algorithmic_bytes(s, per_gpu_batch)
+            d["flops"] += synth.flops(s, per_gpu_batch)
+            d["launches"] += 1
+            i = d["inst"].setdefault(plan.kernel_name, {"ms": 0.0, "launches": 0})
+            i["ms"] += m
+            i["launches"] += 1
+        per_layer, seen = [], {}
+        layer_traffic = traffic_per_layer(args.workload, per_gpu_batch, sparsity_pct)
+        seen_raw = {}
+        for li, (s, plan, bias, si, lid) in enumerate(layers):
+            seen.setdefault(si, []).append(layer_ms[li])
+            seen_raw.setdefault(si, []).append(layer_ms_raw[li])
+        for si, s in enumerate(shapes):
+            m = float(np.mean(seen[si]))
+            name = layers[last_layer_of_shape(layers)[si]][1].kernel_name
+            byt, flo = synth.algorithmic_bytes(s, per_gpu_batch), synth.flops(s, per_gpu_batch)
+            t_hbm, t_fma = byt / (HBM_PEAK_GBS * 1e9), flo / (FP32_VECTOR_TFLOPS * 1e12)
+            per_layer.append({"layer": s.name, "count": s.count, "us": round(m * 1e3, 1),
+                              # event to event, nothing taken off (one event between two launches costs `event_us`)
+                              "us_raw": round(float(np.mean(seen_raw[si])) * 1e3, 1),
+                              "alg_GBps": round(byt / m / 1e6, 1), "sparse_TFLOPs": round(flo / m / 1e9, 2),
+                              "hbm_frac": round(t_hbm / (m * 1e-3), 4), "fma_frac": round(t_fma / (m * 1e-3), 4),
+                              "binding_frac": round(max(t_hbm, t_fma) / (m * 1e-3), 4),
+                              "alg_bytes": int(byt),
+                              # PMC (separate run, profiles/traffic_<workload>.json): HBM bytes of this layer's launch
+                              "hbm_traffic": layer_traffic.get(s.name),
+                              "traffic_over_alg": round(layer_traffic[s.name] / byt, 3) if s.name in layer_traffic else None})
+            log("  gpu %-16s %-44s %8.1f us  %7.1f GB/s alg  %6.2f TFLOP/s  binding %.3f  x%d" %
+                (s.name, name, m * 1e3, byt / m / 1e6, flo / m / 1e9, per_layer[-1]["binding_frac"], s.count))
+        dom_name, dom = max(per_kernel.items(), key=lambda kv: kv[1]["ms"])
+        achieved = dom["bytes"] / (dom["ms"] * 1e-3) / 1e9
+        # HBM traffic per launch: the instantiations' PMC figures weighted by their launches
+        traffic, provenance, tw = None, None, 0
+        for iname, iv in dom["inst"].items():
+            tv, pv = traffic_with_provenance(args.workload, iname, per_gpu_batch, sparsity_pct)
+            if tv is None:
+                traffic = None
+                break
+            traffic = (traffic or 0) + tv * iv["launches"]
+            tw += iv["launches"]
+            provenance = pv
+        if traffic is not None and tw:
+            traffic = int(traffic / tw)
+        t_bind = sum(max(synth.algorithmic_bytes(s, per_gpu_batch) / (HBM_PEAK_GBS * 1e9),
+                         synth.flops(s, per_gpu_batch) / (FP32_VECTOR_TFLOPS * 1e12)) * s.count for s in shapes)
+        # (one name per rocprofv3 row: the family's instantiations, most launches first)
+        dom_label = " + ".join(sorted(dom["inst"], key=lambda k: -dom["inst"][k]["launches"]))
+        roofline = {"bound": "hbm", "kernel": dom_label, "achieved": round(achieved, 1),
+                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
+                    "traffic": traffic, "traffic_provenance": provenance,
+                    # PMC bytes (FETCH_SIZE x 2 + WRITE_SIZE, the fabric side of the L2s: Infinity-Cache hits included) over
+                    # the algorithmic bytes, per launch of the dominant kernel over the step: > 1 = re-reads (halo, several
+                    # workgroup columns, XCD grouping) and generated code; profiles/r05_mall_share.md says which of it is HBM
+                    "traffic_over_alg": round(traffic / (dom["bytes"] / dom["launches"]), 3) if traffic else None,
+                    "avg_launch_us": round(dom["ms"] / dom["launches"] * 1e3, 2),
+                    "launches_per_step": dom["launches"],
+                    # per-launch events in `sampled_steps` of the timed steps; one event costs `event_us`
+                    # (sampled minus other steps, per launch), already taken off every duration here
+                    # (the corrected per-launch durations must add up to a step without events: a check of the
+                    #  correction, not a tunable -- bench lines seen so far sit within 2 % of 1)
+                    "launch_sum_over_step": round(sum(layer_ms) / max(1e-9, ms_plain), 4),
+                    "events": {"sampled_steps": len(sampled), "of": args.steps, "event_us": round(event_ms * 1e3, 2),
+                               "ms_per_step_sampled": round(ms_sampled, 4), "ms_per_step_other": round(ms_plain, 4)},
+                    "instantiations": {k: {"launches_per_step": v["launches"],
+                                           "avg_launch_us": round(v["ms"] / v["launches"] * 1e3, 2)}
+                                       for k, v in dom["inst"].items()},
+                    "algorithmic_bytes_per_launch": int(dom["bytes"] / dom["launches"]),
+                    "sparse_tflops": round(dom["flops"] / (dom["ms"] * 1e-3) / 1e12, 2),
+                    # max(bytes / 8 TB/s, flops / 157.3 TF) summed over the step / measured step time:
+                    # the fraction of whichever roofline binds each layer
+                    "binding_frac": round(t_bind / (sum(layer_ms) * 1e-3), 4),
+                    "per_layer": per_layer if sampled else None,
+                    "streams": n_streams}
 
     ms_per_step = elapsed / args.steps * 1e3
     value = global_batch / (ms_per_step * 1e-3)
@@ -969,13 +1018,7 @@ def run(args, be, pkg, synth, oracle_loader, dist=None):
         "metric": "conv-layer fwd images/sec", "value": round(value, 1), "unit": "images/s",
         "n_gpus": world, "n_ranks_seen": dist.get_world_size() if dist is not None else 1,
         "steps": args.steps, "warmup": args.warmup, "settle_ms": args.settle_ms,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-        # the K steps right after the W warm-up steps, BEFORE the settle loop (clocks not yet settled)
-        "ms_per_step_cold": None if cold_ms is None else round(cold_ms, 4),
-        # R timed regions of K steps each; value / ms_per_step are the MEDIAN region's
-        "repeats": len(regions), "ms_per_step_min": round(min(region_ms), 4),
-        "ms_per_step_max": round(max(region_ms), 4),
-        "ms_per_step_regions": [round(v, 4) for v in region_ms],
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "full": full,
         "scaling": "strong" if strong else "weak",
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "%s @%d%% sparsity, batch %d/GPU, fp32" %
@@ -1008,10 +1051,21 @@ def run(args, be, pkg, synth, oracle_loader, dist=None):
         "weight_receive_ms": receive,
         "backend": be.name, "dist_backend": (be.dist_backend if test_be(be) else args.dist_backend) if dist_on else None,
         "buffers": "one bottom/top pair per layer (no launch re-reads the previous launch's input)",
+        "outputs_dumped": None if dumped is None else {"dir": args.dump_outputs, "files": len(dumped)},
+    }
+    if not full:
+        return out
+    out.update({
+        # the K steps right after the W warm-up steps, BEFORE the settle loop (clocks not yet settled)
+        "ms_per_step_cold": None if cold_ms is None else round(cold_ms, 4),
+        # R timed regions of K steps each; value / ms_per_step are the MEDIAN region's
+        "repeats": len(regions), "ms_per_step_min": round(min(region_ms), 4),
+        "ms_per_step_max": round(max(region_ms), 4),
+        "ms_per_step_regions": [round(v, 4) for v in region_ms],
         "parity_max_rel_err": float("%.3g" % parity),
         "cross_rank_checksum_rel_diff": None if cross is None else float("%.3g" % cross),
         "roofline": roofline,
-    }
+    })
     if parity > 1e-4 or (cross is not None and cross > 1e-5):
         out["parity_failed"] = True
         log("PARITY FAILURE: parity_max_rel_err=%g cross_rank=%r" % (parity, cross))
@@ -1054,9 +1108,11 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: per workload, see DEFAULT_STEPS)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed warm-up steps (default: per workload)")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps steps each; value = the median region (SURVEY 8d)")
+                    help="--full: timed regions of --steps steps each; value = the median region (SURVEY 8d).  A plain "
+                         "run times one region")
     ap.add_argument("--settle-ms", type=float, default=300.0,
-                    help="run the step untimed for this long before the warm-up steps (clock settling; 0: not at all)")
+                    help="run the step untimed for this long after the warm-up steps, before the timed region (clock settling; "
+                         "0: not at all)")
     ap.add_argument("--workload", default="resnet50")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (weak scaling)")
     ap.add_argument("--global-batch", type=int, default=None,
@@ -1070,12 +1126,19 @@ def parse_args(argv=None):
                          "model looks like (the reference's nets are SkimCaffe-pruned, run.sh:14)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "generic", "tiled", "jit"],
                     help="auto = generated code (jit) where available; tiled = the LDS-staged stream kernel")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds for the cpu_baseline leg")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: cold steps, --repeats regions "
+                         "with per-launch events (roofline), parity against the CPU oracle, the cross-rank check, the other "
+                         "configurations and the sparsity sweep, the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the top blob of every layer as DIR/<name>.npy (float32; a fixed, "
+                         "seeded sample of a larger blob; at most 48 MB in all)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds for the cpu_baseline leg")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: no cpu_baseline leg")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the other single-GPU configurations and the sparsity sweep that the default 1-GPU ResNet run "
+                    help="--full: skip the other single-GPU configurations and the sparsity sweep that the default 1-GPU ResNet run "
                          "times after its headline region (profiling runs: the kernel averages then are the headline's)")
-    ap.add_argument("--extras-budget", type=float, default=55.0, help="seconds for other_configs + sparsity_sweep")
+    ap.add_argument("--extras-budget", type=float, default=55.0, help="--full: seconds for other_configs + sparsity_sweep")
     ap.add_argument("--stream-stores", action="store_true",
                     help="plan option stream_stores = 1: pointwise layers write their top blob with non-temporal "
                          "stores (the layers of a step have no consumer here; a net's next layer reads the blob, "

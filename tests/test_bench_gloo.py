@@ -50,7 +50,7 @@ def _run(tmp_path, argv):
 
 def test_bench_weak_scaling_two_ranks(tmp_path):
     out = _run(tmp_path, ["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "lenet",
-                          "--batch", "3", "--no-cpu"])
+                          "--batch", "3", "--no-cpu", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "weak"
     assert out["config"]["global_batch"] == 6 and out["config"]["weight_broadcast_ms"] is not None
     assert out["value"] > 0 and out["ms_per_step"] > 0
@@ -63,7 +63,7 @@ def test_bench_weak_scaling_two_ranks(tmp_path):
 def test_bench_strong_scaling_uneven_shards(tmp_path):
     """--global-batch 5 over 2 ranks: 3 + 2 images; value counts all 5."""
     out = _run(tmp_path, ["--gpus", "2", "--steps", "2", "--warmup", "1", "--workload", "alexnet",
-                          "--global-batch", "5", "--no-cpu"])
+                          "--global-batch", "5", "--no-cpu", "--full"])
     assert out["scaling"] == "strong" and out["config"]["global_batch"] == 5
     assert abs(out["value"] - 5 / (out["ms_per_step"] * 1e-3)) <= 0.06 + 1e-3 * out["value"]   # (value is rounded to 0.1)
     assert out["parity_max_rel_err"] <= 1e-4 and out["cross_rank_checksum_rel_diff"] <= 1e-5

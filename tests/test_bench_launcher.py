@@ -26,7 +26,7 @@ def _run_one_command(extra, env_extra=None, timeout=300):
 
 def test_one_command_starts_two_ranks_and_prints_one_json_line():
     rc, lines, err = _run_one_command(["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "lenet",
-                                       "--batch", "3", "--no-cpu"])
+                                       "--batch", "3", "--no-cpu", "--full"])
     assert rc == 0, err[-2000:]
     assert len(lines) == 1, lines                 # ONE line on stdout, everything else on stderr
     out = json.loads(lines[0])
@@ -40,7 +40,7 @@ def test_one_command_starts_two_ranks_and_prints_one_json_line():
 
 def test_one_command_strong_scaling_global_batch():
     rc, lines, err = _run_one_command(["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "lenet",
-                                       "--global-batch", "5", "--no-cpu"])
+                                       "--global-batch", "5", "--no-cpu", "--full"])
     assert rc == 0, err[-2000:]
     out = json.loads(lines[-1])
     assert out["scaling"] == "strong" and out["config"]["global_batch"] == 5 and out["n_ranks_seen"] == 2
@@ -59,7 +59,7 @@ def test_scale_command_line_eight_ranks_global_batch_2048():
     configs[3] -- end to end as one command: eight gloo ranks, 8 x 256-image shards of the ResNet-50 set,
     one JSON line, n_ranks_seen 8 (the stub computes only the images the two checks read)."""
     rc, lines, err = _run_one_command(["--gpus", "8", "--global-batch", "2048", "--steps", "1", "--warmup", "0",
-                                       "--repeats", "1", "--settle-ms", "0", "--no-cpu"],
+                                       "--repeats", "1", "--settle-ms", "0", "--no-cpu", "--full"],
                                       env_extra={"ESCOIN_STUB_CHECKED_IMAGES_ONLY": "1", "OMP_NUM_THREADS": "1"},
                                       timeout=900)
     assert rc == 0, err[-3000:]
@@ -71,6 +71,34 @@ def test_scale_command_line_eight_ranks_global_batch_2048():
     assert out["parity_max_rel_err"] <= 1e-4 and out["cross_rank_checksum_rel_diff"] <= 1e-5
     assert out["weight_broadcast_ms"] is not None and out["weight_receive_ms"]["total"] >= 0
     assert out["repeats"] == 1 and out["ms_per_step_min"] <= out["ms_per_step"] <= out["ms_per_step_max"]
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full the line has the headline figure and nothing that takes runs of its own; --dump-outputs writes
+    every layer's top blob of the last timed step, and a second run with the same arguments writes the same arrays."""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("out%d" % k))
+        rc, lines, err = _run_one_command(["--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "alexnet",
+                                           "--batch", "2", "--settle-ms", "0", "--dump-outputs", d])
+        assert rc == 0, err[-2000:]
+        assert len(lines) == 1, lines
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["full"] is False
+        assert out["ms_per_step"] > 0 and abs(out["value"] - 2 / (out["ms_per_step"] * 1e-3)) <= 0.06 + 1e-3 * out["value"]
+        for key in ("metric", "unit", "higher_is_better", "dtype"):
+            assert key in out
+        for key in ("cpu_baseline", "roofline", "parity_max_rel_err", "other_configs", "ms_per_step_cold", "repeats"):
+            assert key not in out, key
+        assert out["outputs_dumped"]["files"] == 4
+        dumps.append(d)
+    names = sorted(os.listdir(dumps[0]))
+    assert names == sorted(os.listdir(dumps[1])) and len(names) == 4
+    for n in names:
+        a, b = np.load(os.path.join(dumps[0], n)), np.load(os.path.join(dumps[1], n))
+        assert a.dtype == np.float32 and a.shape[0] == 2 and np.array_equal(a, b)
+        assert np.abs(a).max() > 0
 
 
 def test_launcher_relays_a_failing_rank():

@@ -4,7 +4,7 @@
 WL=$1; shift
 for rep in 1 2; do
 for e in "" "$@"; do
-  env ESCOIN_LIB=${ESCOIN_LIB:-$PWD/tools/ab/libescoin_exp.so} $e python bench.py --workload $WL --no-cpu 2> /tmp/ab.err | python -c "
+  env ESCOIN_LIB=${ESCOIN_LIB:-$PWD/tools/ab/libescoin_exp.so} $e python bench.py --full --workload $WL --no-cpu 2> /tmp/ab.err | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print('%-28s %-10s ms/step %.4f  ' % ('$e', '$WL', d['ms_per_step']) + ' '.join('%.0f' % l['us'] for l in d['roofline']['per_layer'][:40]), 'parity %.1e' % d['parity_max_rel_err'])

@@ -34,6 +34,6 @@ for L in res2 res3 res4 res5; do
   done
   echo "abl $L done"
 done
-python bench.py --no-cpu > $OUT/bench_resnet50.json 2> $OUT/bench_resnet50.err
-python bench.py --no-cpu --workload googlenet > $OUT/bench_googlenet.json 2> $OUT/bench_googlenet.err
+python bench.py --full --no-cpu > $OUT/bench_resnet50.json 2> $OUT/bench_resnet50.err
+python bench.py --full --no-cpu --workload googlenet > $OUT/bench_googlenet.json 2> $OUT/bench_googlenet.err
 echo all done

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(workload, sparsity, kernel):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--sparsity", str(sparsity),
-           "--kernel", kernel, "--no-cpu"]
+           "--kernel", kernel, "--no-cpu", "--full"]
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=900).stdout.decode()
     d = json.loads(out.strip().splitlines()[-1])
     return ("%.3f (%s)" % (d["ms_per_step"], " ".join("%.1f" % l["us"] for l in d["roofline"]["per_layer"])), d.get("parity_max_rel_err"),

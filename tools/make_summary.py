@@ -10,7 +10,7 @@ import sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1] if len(sys.argv) > 1 else "r03"
 out = ["# %s: per-layer summary of the final binary (one MI355X)\n" % tag,
-       "us / TFLOP/s / fractions from `profiles/%s_bench_<set>.json` (`python bench.py --workload <set>`: every layer with its own bottom / top pair, per-launch events in 10 of the timed steps with their own cost taken off); `traffic / alg` = HBM bytes by PMC (`profiles/traffic_<set>.json`, separate rocprofv3 passes) over the algorithmic bytes of SURVEY 8(d); tiling = `escoin_plan_tiling_info()` as printed by `tools/caffe_test.py --model <set> --tilings` (cut = the image as the kernel walks it, tpl = quads per lane, G = output channels per wave, columns = workgroup columns per conv group, nseg = images per tile, bands = row bands per image, qpc = quads per staged channel plane, icb x n_icb = input channels per block x blocks, nbuf = plane buffers).\n" % tag]
+       "us / TFLOP/s / fractions from `profiles/%s_bench_<set>.json` (`python bench.py --full --workload <set>`: every layer with its own bottom / top pair, per-launch events in 10 of the timed steps with their own cost taken off); `traffic / alg` = HBM bytes by PMC (`profiles/traffic_<set>.json`, separate rocprofv3 passes) over the algorithmic bytes of SURVEY 8(d); tiling = `escoin_plan_tiling_info()` as printed by `tools/caffe_test.py --model <set> --tilings` (cut = the image as the kernel walks it, tpl = quads per lane, G = output channels per wave, columns = workgroup columns per conv group, nseg = images per tile, bands = row bands per image, qpc = quads per staged channel plane, icb x n_icb = input channels per block x blocks, nbuf = plane buffers).\n" % tag]
 for wl in ("resnet50", "alexnet", "googlenet", "lenet"):
     d = json.load(open("%s/profiles/%s_bench_%s.json" % (root, tag, wl)))
     r = d["roofline"]

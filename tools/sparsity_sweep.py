@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(workload, sparsity, cpu_budget):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--sparsity", str(sparsity),
-           "--cpu-budget", str(cpu_budget)]
+           "--cpu-budget", str(cpu_budget), "--full"]
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=900).stdout.decode()
     return json.loads(out.strip().splitlines()[-1])
 
