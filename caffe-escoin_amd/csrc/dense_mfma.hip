@@ -35,9 +35,8 @@
 #include "escoin_plan.h"
 #include "knobs.h"
 
-#ifdef ESCOIN_ABLATIONS
-#define ESC_DENSE_ABL(a, bits) ((a).abl & (bits))
-// In-kernel stamp profile (ESCOIN_PROF=1 on the ablation flavour; round 6, profiles/r06_dense_stamps.md): shader cycles of
+#ifdef ESCOIN_STAMPS
+// In-kernel stamp profile (ESCOIN_PROF=1 on the stamps flavour; round 6, profiles/r06_dense_stamps.md): shader cycles of
 // every wave by phase, summed over its tiles and k-steps --
 //   0 start-up (arguments, first tile's addressing, first fetch)    1 k-step top: wait for this wave's operand pieces
 //   2 k-step top: workgroup barrier                                 3 issuing the next k-step's fetch (LDS-DMA / gather)
@@ -59,7 +58,6 @@
     }                                                                                                               \
   }
 #else
-#define ESC_DENSE_ABL(a, bits) (0)
 #define ESC_DPROF_DECL
 #define ESC_DPROF(i)
 #define ESC_DPROF_EPI(which)
@@ -85,11 +83,8 @@ struct DenseArgs {
   int n_ptiles, n_mtiles, n_groups;        // tiles: pixel x channel x conv group (of this launch)
   unsigned in_bytes, w_bytes;              // buffer descriptor ranges
   int vec_out;                             // OH*OW % 4 == 0 and top 16-byte aligned: 16-byte stores through LDS
-  int s2_pair;                             // BMODE 2: a lane's two outputs come out of one aligned 16-byte quad (stride 2, even OW)
   unsigned long long group_mask;           // conv groups this launch covers (all ones: every group)
-  int abl;                                 // ESCOIN_ABLATIONS builds: timing experiments (wrong results)
-  unsigned long long *prof;                // ESCOIN_ABLATIONS builds: stamp profile [workgroup][wave][8] (ESC_DPROF)
-  int fetch_slots;                         // the next k-step's LDS-DMA pieces go out between this k-step's MFMAs (1) or as a burst at its top (0)
+  unsigned long long *prof;                // ESCOIN_STAMPS builds: stamp profile [workgroup][wave][8] (ESC_DPROF)
   // stream-K (STREAMK instantiations): every workgroup takes an equal, contiguous run of (tile, k-step) units;
   // a tile cut by a run boundary is finished by the workgroup holding its last k-steps, which adds the others'
   // partial accumulators from `sk_ws` ([workgroup][wave][16 quads][64 lanes] floats x 4) once their `sk_flag`
@@ -132,18 +127,11 @@ typedef unsigned __attribute__((address_space(1))) gu32;
 // BMODE: how the B tile (the im2col view) reaches LDS --
 //   0  gathered, 4 bytes per LDS-DMA lane (any kernel / stride / padding / dilation)
 //   1  pointwise (1x1, stride 1, no padding, H*W % 4 == 0): the column matrix IS the bottom blob, 16 bytes per DMA lane
-//   2  (experiments flavour only: measured slower than mode 0, see launch_dense)
-//      strided pointwise (1x1, stride > 1, no padding: ResNet-50's res{3,4,5}a_branch1 / branch2a): through registers.
-//      A lane owns two adjacent outputs of the tile; with stride 2 and an even output width their inputs are elements
-//      0 and 2 of ONE aligned 16-byte quad (a.s2_pair: one global_load_dwordx4 per k-row, the operand-side twin of
-//      the sparse path's strided view, sconv_tiled.hip TiledArgs::sub), otherwise two 4-byte loads; the two values go
-//      to LDS as one 8-byte write.  8 loads + 8 writes per wave and k-step where the gather issues 16 LDS-DMA
-//      instructions of 256 bytes -- an LDS-DMA instruction in a burst holds its wave ~100 cycles, and 16 of them were
-//      most of a k-step's 2048 MFMA cycles (profiles/r05_dense.md).
+// (A mode staging strided pointwise layers through registers was measured 0-9 % slower than the gather and removed:
+// profiles/r05_dense.md.)
 template <int WROWS, int BMODE, bool STREAMK = false>
 __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) {
   constexpr bool POINTWISE4 = BMODE == 1;
-  constexpr bool STRIDED1 = BMODE == 2;
   constexpr int BM = 64 * WROWS;
   constexpr int WCOLS = 4 / WROWS;           // waves along the pixel axis
   constexpr int WN = kBN / WCOLS;            // columns per wave: 64 or 32
@@ -189,25 +177,9 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
   unsigned fb_pix[2] = {0u, 0u};     // byte offset of the lane's pixel (window origin) in the blob
   int fb_ih0[2] = {0, 0}, fb_iw0[2] = {0, 0};
   int f_cg = 0, f_m0 = 0, f_p0 = 0;
-  // BMODE 2: element offsets (channel 0 of the conv group) of the lane's two outputs, the staging registers of the
-  // k-step in flight and where they go
-  size_t s_off[2] = {0, 0};
-  float4 s_q[STRIDED1 ? 8 : 1];
-  float s_d[STRIDED1 ? 16 : 1];
-  int s_k0 = 0, s_buf = 0;
-  bool s_pending = false;
   auto fetch_setup = [&](long tile) {
     tile_coords(tile, f_cg, f_m0, f_p0);
-    if (STRIDED1) {
-#pragma unroll
-      for (int e = 0; e < 2; ++e) {
-        // (pairs: the lane's first output is even and the second its right neighbour, also in the tile's clamped tail)
-        const int p = a.s2_pair ? min(f_p0 + 2 * lane, a.P - 2) + e : min(f_p0 + 2 * lane + e, a.P - 1);
-        const int n = p / ohw, rem = p - n * ohw;
-        const int oh = rem / a.OW, ow = rem - oh * a.OW;
-        s_off[e] = (((size_t)n * a.C + (size_t)f_cg * a.Cg) * a.H + (size_t)oh * a.stride_h) * a.W + (size_t)ow * a.stride_w;
-      }
-    } else if (POINTWISE4) {
+    if (POINTWISE4) {
       const int p = min(f_p0 + 4 * (lane & 31), a.P - 4);
       const int n = p / ohw, rem = p - n * ohw;
       fb_pix[0] = (unsigned)((((size_t)n * a.C + (size_t)f_cg * a.Cg + (lane >> 5)) * hw + rem) * 4);
@@ -232,28 +204,7 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
       const int i = wave + 4 * q;
       dma16(rA, ldsA + (unsigned)buf * kBufBytes + (unsigned)(i * 1024), voffA, sa + (unsigned)(i * 8 * a.lda * 4));
     }
-    if (STRIDED1) {
-      // this wave's 8 rows of the k-step into registers; rows past K are read from channel K - 1 and zeroed at the
-      // commit (a zero weight does not make NaNs harmless)
-      s_k0 = k0;
-      s_buf = buf;
-      s_pending = true;
-      if (a.s2_pair) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          const int kc = min(k0 + 8 * wave + r, a.K - 1);
-          s_q[r] = *reinterpret_cast<const float4 *>(a.in + s_off[0] + (size_t)kc * hw);
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-          const int kc = min(k0 + 8 * wave + r, a.K - 1);
-          s_d[2 * r] = a.in[s_off[0] + (size_t)kc * hw];
-          s_d[2 * r + 1] = a.in[s_off[1] + (size_t)kc * hw];
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);     // (the loads stay here, ahead of the k-step's MFMAs)
-    } else if (POINTWISE4) {
+    if (POINTWISE4) {
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int i = wave + 4 * q;          // rows k0 + 2 i, k0 + 2 i + 1
@@ -306,7 +257,7 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
         const unsigned vo = (k0 + 2 * i + (lane >> 5) < a.K) ? fb_pix[0] : kOOB;
         dma16(rB, ldsB + (unsigned)buf * kBufBytes + (unsigned)(i * 1024), vo, (unsigned)((size_t)(k0 + 2 * i) * hw * 4));
       }
-    } else if (!STRIDED1) {
+    } else {
       if (slot == 0) {
         const int4 *tp = reinterpret_cast<const int4 *>(a.ktab + k0 + 8 * wave);
 #pragma unroll
@@ -331,28 +282,6 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
     }
   };
 
-  // BMODE 2: the staged k-step's values into its B tile (row k, columns 2 lane and 2 lane + 1: 512 consecutive bytes
-  // per row and wave, conflict-free); the barrier at the next k-step's top publishes them
-  auto commit = [&]() {
-    if (!STRIDED1 || !s_pending) return;
-    s_pending = false;
-    float *dst = &sAB[s_buf][BM * kBK];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-      const int row = 8 * wave + r;
-      const bool live = s_k0 + row < a.K;
-      float2 v;
-      if (a.s2_pair) {
-        v.x = live ? s_q[r].x : 0.f;
-        v.y = live ? s_q[r].z : 0.f;
-      } else {
-        v.x = live ? s_d[2 * r] : 0.f;
-        v.y = live ? s_d[2 * r + 1] : 0.f;
-      }
-      *reinterpret_cast<float2 *>(&dst[row * kBN + 2 * lane]) = v;
-    }
-  };
-
   f32x16 acc[2][NB];
   // Work of this workgroup.  Tile mode: tiles blockIdx.x, + gridDim.x, ..., every k-step of each.  Stream-K:
   // units [u0, u1) of the (tile, k-step) sequence -- a run starts and ends anywhere in a tile.  The run's tiles are
@@ -373,7 +302,6 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
   if (!in_run(tile)) return;
   fetch_setup(tile);
   fetch(seg_lo(tile), 0);
-  commit();                       // (BMODE 2: the first step has no MFMAs to hide under)
   long f_tile = tile;             // tile of the step being fetched next
   int f_k = seg_lo(tile) + 1;     // ... and its k-step
   if (f_k == seg_hi(f_tile)) {
@@ -393,21 +321,12 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
     ESC_DPROF(5);
     for (int ks = k_lo; ks < k_hi; ++ks, buf ^= 1) {
       // this wave's pieces of the step have landed (and the stores of the last epilogue are out) ...
-#ifdef ESCOIN_ABLATIONS
-      if (!ESC_DENSE_ABL(a, 1))     // ESCOIN_DENSE_ABL: 1 no wait for the operands, 2 no operand traffic, 4 no MFMAs
-#endif
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       ESC_DPROF(1);
       __syncthreads();   // ... everyone's have, and everyone is done with the other buffer
       ESC_DPROF(2);
-      // the next k-step's operands: as one burst here (BMODE 2 and the experiments' ESCOIN_DENSE_SLOTS=0), or slot by
-      // slot between the MFMAs below
-      bool do_fetch = in_run(f_tile);
-#ifdef ESCOIN_ABLATIONS
-      if (ESC_DENSE_ABL(a, 2)) do_fetch = false;
-#endif
-      const bool slotted = !STRIDED1 && a.fetch_slots;
-      if (do_fetch && !slotted) fetch(f_k, buf ^ 1);
+      // the next k-step's operands go out slot by slot between the MFMAs below
+      const bool do_fetch = in_run(f_tile);
       ESC_DPROF(3);
       // fragments of k-group kg + 1 are read while the MFMAs of k-group kg run
       // lane (i, h): A rows wm * 64 + {0, 32} + i, k = 8 kg + 4 h + t; B columns wn * WN + 32 j + i
@@ -430,14 +349,11 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
         // keep the order: next group's LDS reads first, then this group's MFMAs (left alone, the
         // scheduler sinks each read to just above its use and every 4 MFMAs wait for LDS)
         __builtin_amdgcn_sched_barrier(0);
-#ifdef ESCOIN_ABLATIONS
-        if (ESC_DENSE_ABL(a, 4)) continue;
-#endif
         const float a0[4] = {fa[s][0].x, fa[s][0].y, fa[s][0].z, fa[s][0].w};
         const float a1[4] = {fa[s][1].x, fa[s][1].y, fa[s][1].z, fa[s][1].w};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-          if (do_fetch && slotted && 4 * kg + t < 8) {
+          if (do_fetch && 4 * kg + t < 8) {
             fetch_slot(f_k, buf ^ 1, 4 * kg + t);
             __builtin_amdgcn_sched_barrier(0);      // (the piece stays in front of this group's MFMAs)
           }
@@ -448,7 +364,6 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
           }
         }
       }
-      commit();       // (BMODE 2: the next step's B rows from the staging registers into the other buffer)
       if (do_fetch) {
         if (++f_k == seg_hi(f_tile)) {
           f_tile += tile_step;
@@ -556,7 +471,7 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
       // says everybody is done reading it, the barrier at the next k-step's top that everybody is
       // done with the staging.  A wave transposes its own 32 x WN half-tiles: no cross-wave traffic.
       __syncthreads();
-#ifdef ESCOIN_ABLATIONS
+#ifdef ESCOIN_STAMPS
       unsigned long long dps_ = 0;
       if (a.prof) { dps_ = __builtin_readcyclecounter(); dpt_[8] += dps_ - dpl_; }      // (since the last stamp: bias, pin, barrier)
 #endif
@@ -598,11 +513,11 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
 #pragma unroll
         for (int it = 0; it < 32 / kRowsPerIt; ++it) {
           const int m = m0 + wm * 64 + 32 * i + it * kRowsPerIt + r0;
-          if (m < a.Mg && pq < a.P && !ESC_DENSE_ABL(a, 8)) *reinterpret_cast<float4 *>(oq + (size_t)m * ohw) = vq[it];      // (ESCOIN_DENSE_ABL bit 3: no stores)
+          if (m < a.Mg && pq < a.P) *reinterpret_cast<float4 *>(oq + (size_t)m * ohw) = vq[it];
         }
         asm volatile("" ::: "memory");
       }
-#ifdef ESCOIN_ABLATIONS
+#ifdef ESCOIN_STAMPS
       if (a.prof) dpt_[9] += __builtin_readcyclecounter() - dps_;
 #endif
       ESC_DPROF(6);
@@ -624,7 +539,7 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_mfma_kernel(DenseArgs a) 
           if (m >= a.Mg) continue;
           float v = acc[i][j][reg] + bv[i][reg];
           if (a.relu) v = fmaxf(v, 0.f);
-          if (!ESC_DENSE_ABL(a, 8)) obase[(size_t)m * ohw] = v;
+          obase[(size_t)m * ohw] = v;
         }
       }
     }
@@ -745,34 +660,12 @@ int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, f
   const bool pointwise = g.d.KH == 1 && g.d.KW == 1 && g.d.stride_h == 1 && g.d.stride_w == 1 &&
                          g.d.pad_h == 0 && g.d.pad_w == 0;
   const bool vec_b = pointwise && (g.d.H * g.d.W) % 4 == 0 && (reinterpret_cast<uintptr_t>(bottom) & 15) == 0 && P >= 4;
-  // Strided pointwise layers (1x1, stride > 1, no padding) with the B tile staged through registers (kernel, BMODE 2: with
-  // stride 2, an even output width and 16-byte aligned rows a lane's two outputs are one aligned quad's elements 0 and
-  // 2) -- BUILT, MEASURED, NOT SHIPPED: same-call A/B on the ResNet-50 chain's six stride-2 layers at batch 256
-  // (profiles/r05_dense.md) 624-637 -> 642-678 us and 187-209 -> 188-228 us, i.e. 0-9 % SLOWER than the 4-byte LDS-DMA
-  // gather (parity green: tests/test_gpu_parity.py::test_dense_strided_pointwise_through_registers runs it in the
-  // experiments flavour).  Exists in the experiments flavour only, behind ESCOIN_DENSE_S2=1; the product gathers.
-#ifdef ESCOIN_EXPERIMENTS
-  static const bool s2_on = (ESC_KNOB("DENSE_S2", 0) != 0);
-#else
-  constexpr bool s2_on = false;
-#endif
-  const bool strided1 = s2_on && g.d.KH == 1 && g.d.KW == 1 && g.d.pad_h == 0 && g.d.pad_w == 0 && !pointwise && P >= 2;
-  a.s2_pair = strided1 && g.d.stride_w == 2 && g.OW % 2 == 0 && (g.d.H * g.d.W) % 4 == 0 && (g.d.stride_h * g.d.W) % 4 == 0 &&
-              (reinterpret_cast<uintptr_t>(bottom) & 15) == 0 ? 1 : 0;
-  {
-    static const bool vo = (ESC_KNOB("DENSE_VEC_OUT", 1) != 0);
-    a.vec_out = vo && (g.OH * g.OW) % 4 == 0 && (reinterpret_cast<uintptr_t>(top) & 15) == 0;
-  }
+  a.vec_out = (g.OH * g.OW) % 4 == 0 && (reinterpret_cast<uintptr_t>(top) & 15) == 0;
   a.group_mask = p->use_dense ? ~0ull : p->dense_mask;
-  a.abl = ESC_ABL_KNOB("DENSE_ABL");
-  {
-    static const int slots_knob = (int)ESC_KNOB("DENSE_SLOTS", 1);
-    a.fetch_slots = slots_knob != 0 ? 1 : 0;
-  }
   a.prof = nullptr;
-#ifdef ESCOIN_ABLATIONS
+#ifdef ESCOIN_STAMPS
   static unsigned long long *prof_buf = nullptr;
-  if (ESC_ABL_KNOB("PROF")) {
+  if (ESC_KNOB("PROF", 0) != 0) {
     if (!prof_buf) ESCOIN_HIP_TRY(hipMalloc(&prof_buf, sizeof(unsigned long long) * (68 * 4096 + 48 * 4096)));
     ESCOIN_HIP_TRY(hipMemsetAsync(prof_buf, 0, sizeof(unsigned long long) * (68 * 4096 + 48 * 4096), stream));
     a.prof = prof_buf;
@@ -801,7 +694,7 @@ int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, f
   //  with it, 3x3 layers have not been tried)
   const bool unit_1x1 = g.d.KH == 1 && g.d.KW == 1 && g.d.stride_h == 1 && g.d.stride_w == 1;
   bool streamk = sk_env >= 0 ? sk_env != 0 : (unit_1x1 && occupancy < 0.85 && nk >= 8 && tiles * nk >= 4 * slots);
-  if (tiles * nk < slots || strided1) streamk = false;
+  if (tiles * nk < slots) streamk = false;
   // (the workspace and the pinned give-up word were allocated by dense_build_ktab at WeightAlign; a launch never
   //  allocates -- a plan without them runs whole tiles)
   if (streamk && (!p->d_sk_ws || !p->h_sk_fail || !p->d_sk_fail ||
@@ -832,20 +725,14 @@ int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, f
   } while (0)
   if (bm == 64) {
     if (vec_b) ESC_DENSE_LAUNCH(1, 1);
-#ifdef ESCOIN_EXPERIMENTS
-    else if (strided1) hipLaunchKernelGGL((escoin_dense_mfma_kernel<1, 2, false>), grid, dim3(256), 0, stream, a);
-#endif
     else ESC_DENSE_LAUNCH(1, 0);
   } else {
     if (vec_b) ESC_DENSE_LAUNCH(2, 1);
-#ifdef ESCOIN_EXPERIMENTS
-    else if (strided1) hipLaunchKernelGGL((escoin_dense_mfma_kernel<2, 2, false>), grid, dim3(256), 0, stream, a);
-#endif
     else ESC_DENSE_LAUNCH(2, 0);
   }
 #undef ESC_DENSE_LAUNCH
   ESCOIN_HIP_TRY(hipGetLastError());
-#ifdef ESCOIN_ABLATIONS
+#ifdef ESCOIN_STAMPS
   if (a.prof && n_wg <= 4096) {
     // (every launch while ESCOIN_PROF=1: synchronises -- a profiling run, not a timing run)
     ESCOIN_HIP_TRY(hipStreamSynchronize(stream));

@@ -10,7 +10,6 @@
 #include <vector>
 
 #include "escoin_plan.h"
-#include "knobs.h"
 
 namespace escoin {
 
@@ -272,8 +271,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
         const double t_sparse = std::max((g.d.KH * g.d.KW > 1 ? 50.0 : 20.0) + 2.0 * pix * (double)nnz_g / (g.d.KH * g.d.KW > 1 ? 80e6 : 68e6), byt / 4.8e6 + 8.0);
         return t_dense < t_sparse;
       };
-      const bool use_model = p->dense_threshold_pct < 0 && fast_sparse && jit_available() &&
-                             (ESC_KNOB("DENSE_MODEL", 1) != 0);
+      const bool use_model = p->dense_threshold_pct < 0 && fast_sparse;
       if (G <= 64) {
         for (int grp = 0; grp < G; ++grp) {
           const long n_g = (long)p->colidx[grp].size();
@@ -327,20 +325,8 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     // column's code, and grouping the workgroup columns by XCD (sconv_tiled.hip, xcd_q) removed it:
     // over 50-95 % sparsity on every BASELINE 3x3 / 5x5 / 1x1 shape generated code is now ahead of the
     // stream kernel at every point (profiles/r04_crossover.md; the worst point, alex_conv2 @50 %, by 14 %).
-    // ESCOIN_JIT_MAX_DENSITY_PCT restores a density cut for experiments; code beyond kMaxJitBytes
-    // (sconv_tiled.hip) falls back to the stream kernel by itself.
-    static const int jit_max_density_pct = (int)ESC_KNOB("JIT_MAX_DENSITY_PCT", 100);
-    double dens_sparse = 0;
-    long nz_sparse = 0;
-    {
-      long ng = 0;
-      for (int grp = 0; grp < G; ++grp)
-        if (!dense[grp]) { nz_sparse += (long)p->colidx[grp].size(); ++ng; }
-      dens_sparse = ng ? (double)nz_sparse / (per_group * ng) : 0.0;
-    }
-    const bool sparse_enough = dens_sparse * 100.0 <= jit_max_density_pct;
-    const bool try_jit = p->kernel_choice == ESCOIN_KERNEL_JIT ||
-                         (p->kernel_choice == ESCOIN_KERNEL_AUTO && jit_available() && sparse_enough);
+    // Code beyond kMaxJitBytes (sconv_tiled.hip) falls back to the stream kernel by itself.
+    const bool try_jit = p->kernel_choice == ESCOIN_KERNEL_JIT || p->kernel_choice == ESCOIN_KERNEL_AUTO;
     int rc = ESCOIN_OK;
     p->import_fast = false;
     p->small_rule = 0;     // (set by tiled_build / tiled_import from the tiling, before any code is generated or loaded)

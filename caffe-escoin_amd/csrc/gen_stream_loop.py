@@ -54,10 +54,7 @@ IXT = [37, 38]               # alternating accumulator-index temporaries
 END0 = 38                    # END_n in s[END0 + n], n = 1..6; s[END0 + 7] = 0
 SGPR_LAST = 45
 MAX_SLOTS2 = 6
-ABL = set()                  # timing-only ablations (see main())
 PRIO_HI = 1                  # priority of a wave's even groups (odd groups run at 0)
-PRIO_QUADS = True            # four-group runs: one priority switch per two groups
-STORE_MOD = ""               # ESC_GEN_STORE_MOD: modifier on the epilogues' stores (experiments: " nt", " sc1")
 PRIO_BASE = 0                # added to both (the second-dispatched half of the workgroup: constant level 1, see main())
 
 
@@ -67,8 +64,6 @@ def bfe(dst, src, off, width):
 
 def pk4v(L, r, p):
     """Record r of the current group: value = half of a payload VGPR pair."""
-    if "nopk" in ABL:
-        return
     base = P0[p] if r < 3 else P1
     q = r % 3
     pair, sel = (base, 1) if q == 0 else ((base + 2, 0) if q == 1 else (base + 2, 1))
@@ -79,8 +74,6 @@ def pk4v(L, r, p):
 
 def xreads(L, p_next, areg):
     """Input quads of a group (tile A, tile B = tile A + 1 KiB) through the address in v[areg]."""
-    if "noxp" in ABL:
-        return
     L.append("ds_read_b128 v[%d:%d], v%d" % (XA[p_next], XA[p_next] + 3, areg))
     L.append("ds_read_b128 v[%d:%d], v%d offset:1024" % (XB[p_next], XB[p_next] + 3, areg))
 
@@ -88,8 +81,7 @@ def xreads(L, p_next, areg):
 def xaddr(L, areg):
     """LDS address of a group's tile-A quad from its row offset / 32 in s[HDR2].  Needs GPR index 0
     (a VALU instruction: its VGPR operands are relative like everybody's)."""
-    if "noxp" not in ABL:
-        L.append("v_lshl_add_u32 v%d, s%d, 5, %%[lbA]" % (areg, HDR2))
+    L.append("v_lshl_add_u32 v%d, s%d, 5, %%[lbA]" % (areg, HDR2))
 
 
 def pread(L, reg, off):
@@ -129,8 +121,8 @@ def body2(L, n, p, label, role):
     # The two waves of a SIMD are arbitrated oldest-first: left alone, the younger one runs ~25 %
     # slower all kernel long and every block waits for it.  Alternating priority by group parity
     # lets whichever wave is behind win its even groups.
-    if "noprio" not in ABL and PRIO_HI != 0:
-        if PRIO_QUADS and role in "ABCD":
+    if PRIO_HI != 0:
+        if role in "ABCD":
             # four-group runs: two groups up, two groups down, one switch per two groups
             if role in "AC":
                 A("s_setprio %d" % ((1 if role == "A" else 0) * PRIO_HI + PRIO_BASE))
@@ -159,10 +151,7 @@ def body2(L, n, p, label, role):
         xreads(L, 0, VA2)                   # address left by the phase-0 body
         pread(L, P0[0], LAG - 2 * stride if role == "B" else LAG)
     pair = role in "APC"
-    if "noxp" in ABL:
-        A("s_waitcnt lgkmcnt(%d)" % (2 if n > 3 else 1))
-    else:
-        A("s_waitcnt lgkmcnt(%d)" % (4 if n > 3 else 3))   # X(k), P0(k) landed
+    A("s_waitcnt lgkmcnt(%d)" % (4 if n > 3 else 3))   # X(k), P0(k) landed
     # meta of THIS group and the accumulator indices of its records 1, 2 are extracted before
     # record 0's FMAs: the VALU -> SGPR -> SALU -> M0 chain then runs under those 4 packed FMAs
     # instead of between record 0 and record 1
@@ -181,7 +170,7 @@ def body2(L, n, p, label, role):
     for r in range(1, n):
         t = IXT[r % 2]
         if r == 3:
-            A("s_waitcnt lgkmcnt(%d)" % (1 if "noxp" in ABL else 3))
+            A("s_waitcnt lgkmcnt(3)")
             A("v_readfirstlane_b32 s%d, v%d" % (META2, P1))
             for r2 in range(4, n):
                 A("s_lshr_b32 s%d, s%d, %d" % (IXT[r2 % 2], META2, 7 * (r2 - 3)))
@@ -208,7 +197,7 @@ def generate2():
     A("s_mov_b32 s%d, 0" % (END0 + MAX_SLOTS2 + 1))
     A("s_lshr_b32 s%d, s%d, 21" % (HDR2, META_P[1]))     # group 1
     A("s_set_gpr_idx_on s%d, gpr_idx(SRC2,DST)" % META_P[1])
-    if "noprio" not in ABL and PRIO_HI == 0:
+    if PRIO_HI == 0:
         A("s_setprio %d" % PRIO_BASE)                    # a constant level: set once
     A("s_branch ESC2_E%d_0_%%=" % MAX_SLOTS2)
     for n in range(MAX_SLOTS2, 0, -1):
@@ -266,8 +255,6 @@ def generate2():
     A("s_set_gpr_idx_off")
     A("ESC2_X_%=:")
     A("s_waitcnt lgkmcnt(0)")
-    if ALIGN is not None:
-        L, _ = align8(L, ALIGN)
     return L
 
 
@@ -309,57 +296,6 @@ def dma_site(L, n, p):
     A("ESC2_NS%d_%d_%%=:" % (n, p))
 
 
-LLVM_MC = "/opt/rocm/lib/llvm/bin/llvm-mc"
-# dummy registers for the inline-asm operands, only to let the assembler tell instruction sizes
-_SIZE_OPERANDS = {"h0": "s8", "h1": "s9", "h2": "s10", "h3": "s11", "h4": "s12", "h5": "s13", "h6": "s14",
-                  "lbA": "v1", "lbB": "v2", "sbase": "v3", "dst": "s16", "soff": "s17", "nch": "s18",
-                  "rsrc": "s[20:23]", "tv": "v4", "dstep": "s24", "sstep": "s25"}
-ALIGN = None                 # None: no alignment pass; 0 / 4: 8-byte instructions at 0 / 4 mod 8 (align8)
-
-
-def insn_sizes(lines):
-    """Encoded size in bytes of every line (0 for labels), from the assembler itself."""
-    import re
-    import subprocess
-    txt = []
-    for ln in lines:
-        ln = ln.replace("%=", "0").replace("%%", "%")
-        ln = re.sub(r"%\[(\w+)\]", lambda m: _SIZE_OPERANDS[m.group(1)], ln)
-        txt.append(ln)
-    r = subprocess.run([LLVM_MC, "-arch=amdgcn", "-mcpu=gfx950", "-show-encoding"], input="\n".join(txt) + "\n",
-                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True)
-    if r.returncode != 0 or "error" in r.stderr:
-        raise RuntimeError("llvm-mc: " + r.stderr[:2000])
-    enc = [len(m.split(",")) for m in re.findall(r"encoding: \[([^\]]*)\]", r.stdout)]
-    sizes, k = [], 0
-    for ln in txt:
-        if ln.rstrip().endswith(":") or ln.lstrip().startswith("."):
-            sizes.append(0)
-        else:
-            sizes.append(enc[k])
-            k += 1
-    assert k == len(enc), (k, len(enc))
-    return sizes
-
-
-def align8(lines, phase):
-    """Code placement (MI355X_MICROARCH.md, two waves per SIMD, item 8): a hand-written stream can
-    lose up to 13 % when its 8-byte instructions sit at 4 mod 8.  The block starts 8-byte aligned
-    (.p2align 3) and an s_nop goes in front of every 8-byte instruction that would not start at
-    `phase` mod 8.  Addresses are static, so one linear pass serves every path through the labels.
-    phase 4 exists to MEASURE the sensitivity (same instruction count, opposite placement)."""
-    sizes = insn_sizes(lines)
-    out, off, pads = [".p2align 3"], 0, 0
-    for ln, sz in zip(lines, sizes):
-        if sz == 8 and off % 8 != phase:
-            out.append("s_nop 0")
-            off += 4
-            pads += 1
-        out.append(ln)
-        off += sz
-    return out, pads
-
-
 def clobbers():
     c = ["memory", "scc", "m0"]
     c += ["s%d" % i for i in range(32, SGPR_LAST + 1)]
@@ -375,37 +311,18 @@ def emit_macro(out, name, lines):
 
 
 def main():
-    import os
-    if os.environ.get("ESC_GEN_NOPRIO"):
-        ABL.add("noprio")
-    global PRIO_HI, PRIO_QUADS, ALIGN, STORE_MOD
-    STORE_MOD = os.environ.get("ESC_GEN_STORE_MOD", "")
-    if os.environ.get("ESC_GEN_ALIGN", "") != "":
-        ALIGN = int(os.environ["ESC_GEN_ALIGN"])
-    PRIO_QUADS = os.environ.get("ESC_GEN_PRIO_QUADS", "1") == "1"
-    PRIO_HI = int(os.environ.get("ESC_GEN_PRIO_HI", PRIO_HI))
+    global PRIO_HI, PRIO_BASE, DMA_ON
     out = sys.stdout
     out.write("// GENERATED by gen_stream_loop.py -- do not edit.\n")
     out.write("#define ESC_NV %d\n#define ESC_NACC_TILE %d\n" % (NV, NACC_TILE))
-    global PRIO_BASE
-    global DMA_ON
     for DMA_ON in (False, True):
         sfx = "_DMA" if DMA_ON else ""
         emit_macro(out, "ESC2_LOOP_ASM_BAND" + sfx, generate2())
-        PRIO_BASE = int(os.environ.get("ESC_GEN_PRIO_YOUNG", "1"))
-        old_hi = PRIO_HI
-        PRIO_HI = int(os.environ.get("ESC_GEN_PRIO_YOUNG_HI", 0))
+        # the second-dispatched half of the workgroup: a constant priority 1
+        PRIO_BASE, PRIO_HI = 1, 0
         emit_macro(out, "ESC2_LOOP_ASM_BAND_YOUNG" + sfx, generate2())
-        PRIO_BASE = 0
-        PRIO_HI = old_hi
+        PRIO_BASE, PRIO_HI = 0, 1
     DMA_ON = False
-    # timing-only ablations (wrong results), compiled in with -DESCOIN_ABLATIONS
-    out.write("#ifdef ESCOIN_ABLATIONS\n")
-    for name in ("nopk", "noxp"):
-        ABL.add(name)
-        emit_macro(out, "ESC2_LOOP_ASM_" + name.upper(), generate2())
-        ABL.discard(name)
-    out.write("#endif\n")
     out.write("#define ESC_STREAM_LOOP_CLOBBERS \\\n  ")
     out.write(", ".join('"%s"' % c for c in clobbers()))
     out.write("\n")
@@ -500,7 +417,7 @@ def main():
                     "s_add_u32 s38, s34, s36",
                     "s_addc_u32 s39, s35, 0",
                     "s_mov_b64 exec, %[ok]",
-                    "global_store_dwordx4 %%[voff], v[%d:%d], s[38:39]%s" % (C0, C0 + 3, STORE_MOD),
+                    "global_store_dwordx4 %%[voff], v[%d:%d], s[38:39]" % (C0, C0 + 3),
                 ]
                 if r:
                     lines.append("s_mov_b64 exec, %[okp]")
@@ -567,7 +484,7 @@ def main():
                     "s_add_u32 s38, s34, s36",
                     "s_addc_u32 s39, s35, 0",
                     "s_mov_b64 exec, %[ok]",
-                    "global_store_dwordx4 %%[voff], v[%d:%d], s[38:39]%s" % (C0, C0 + 3, STORE_MOD),
+                    "global_store_dwordx4 %%[voff], v[%d:%d], s[38:39]" % (C0, C0 + 3),
                 ]
                 if r:
                     lines.append("s_mov_b64 exec, %[okp]")
@@ -586,7 +503,7 @@ def main():
     # ESC_EPI1S_<tile>: the same for pointwise layers (one class per channel, up to 24 channels per
     # wave, nothing to shift) whose output rows are whole quads
     # ESC_EPI1SN_<tile>: the same with non-temporal stores (plan option "stream_stores")
-    for tile, base, mod, mname in ((0, ACC_A, STORE_MOD, "ESC_EPI1S"), (1, ACC_B, STORE_MOD, "ESC_EPI1S"),
+    for tile, base, mod, mname in ((0, ACC_A, "", "ESC_EPI1S"), (1, ACC_B, "", "ESC_EPI1S"),
                                    (0, ACC_A, " nt", "ESC_EPI1SN"), (1, ACC_B, " nt", "ESC_EPI1SN")):
         lines = ["s_mov_b64 s[32:33], exec", "s_mov_b64 s[34:35], %[base]", "s_mov_b64 exec, %[ok]"]
         ng = NACC_TILE // 4
@@ -646,9 +563,9 @@ def main():
                 lines += [
                     "ESC_QR%d_%d_%d_%%=:" % (tile, r, g),
                     "s_mov_b64 exec, %[ok]",
-                    "global_store_dwordx4 %%[voff], v[%d:%d], s[34:35]%s" % (C0, C0 + 3, STORE_MOD),
+                    "global_store_dwordx4 %%[voff], v[%d:%d], s[34:35]" % (C0, C0 + 3),
                     "s_mov_b64 exec, %[okp]",
-                    part + STORE_MOD,
+                    part,
                     "s_mov_b64 exec, s[32:33]",
                 ]
                 if g + 1 < ng:
@@ -683,9 +600,9 @@ def main():
                 "v_max_f32 v%d, 0, v%d" % (C0 + 1, C0 + 1),
                 "ESC_SR%d_%d_%%=:" % (tile, g),
                 "s_mov_b64 exec, %[ok]",
-                "global_store_dwordx2 %%[voff], v[%d:%d], s[34:35]%s" % (C0, C0 + 1, STORE_MOD),
+                "global_store_dwordx2 %%[voff], v[%d:%d], s[34:35]" % (C0, C0 + 1),
                 "s_mov_b64 exec, %[okp]",
-                "global_store_dword %%[voff], v%d, s[34:35]%s" % (C0, STORE_MOD),
+                "global_store_dword %%[voff], v%d, s[34:35]" % C0,
                 "s_mov_b64 exec, s[32:33]",
             ]
             if g + 1 < ng:

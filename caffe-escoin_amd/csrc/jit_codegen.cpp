@@ -35,12 +35,9 @@ Options options_from_env() {
   o.depth = std::max(1, std::min(2, (int)ESC_KNOB("JIT_DEPTH", o.depth)));
   o.depth_one_tile = std::max(1, std::min(13, (int)ESC_KNOB("JIT_DEPTH1", o.depth_one_tile)));
   o.hi_sets = std::max(0, std::min(24, (int)ESC_KNOB("JIT_HI_SETS", o.hi_sets)));
-  o.hoist_weight = ESC_KNOB("JIT_HOIST", o.hoist_weight) != 0;
   o.prio_rows = std::max(0, (int)ESC_KNOB("JIT_PRIO_ROWS", o.prio_rows));
   o.prio_waves = std::max(0, (int)ESC_KNOB("JIT_PRIO_WAVES", o.prio_waves));
-  o.ablate = ESC_ABL_KNOB("JIT_ABL");
   o.prefetch = ESC_KNOB("JIT_PREFETCH", o.prefetch) != 0;
-  if (ESC_KNOB_SET("JIT_ONE_TILE")) o.one_tile = ESC_KNOB("JIT_ONE_TILE", 1) != 0 ? 0 : -1;
   return o;
 }
 
@@ -71,11 +68,9 @@ struct Piece {
 struct Lds {
   std::vector<uint32_t> &c;
   int issued = 0, done = 0;     // operations issued so far; operations known to have completed
-  int ablate;
   int issue() { return issued++; }
   void wait_for(int id) {       // operation `id` (0-based issue order) must have landed
     if (id < done) return;
-    if (ablate & 64) { done = id + 1; return; }      // (timing only: nobody waits for LDS)
     enc_waitcnt_lgkm(c, std::min(15, issued - 1 - id));
     done = std::max(done, issued - std::min(15, issued - 1 - id));
   }
@@ -84,8 +79,8 @@ struct Lds {
 // n_pref > 0: the unit starts with n_pref loads over the next unit's code; returns the index (in
 // `c`) of the distance literal to patch (0: none).
 // blk / n_icb: which block of its oc-group's chain this unit is (chaining only).
-// n_idx: accumulator quads per tile the epilogue reads (channels per wave x kernel columns): with Options::self_zero
-// block 0's unit leaves every one of them initialised.
+// n_idx: accumulator quads per tile the epilogue reads (channels per wave x kernel columns): block 0's unit leaves
+// every one of them initialised (jit_codegen.h: the code initialises its accumulators).
 size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const std::vector<Piece> &pieces,
                  const Options &opt_in, int n_pref, int wave, int blk, int n_icb, int n_idx) {
   Options opt = opt_in;
@@ -109,9 +104,9 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
     enc_s_mov(c, kSRecords, kSNextRecords);
     enc_v_add_u32_s(c, kVTabAddr, kSTabDelta, kVTabAddr);
   }
-  const int n = (opt.ablate & 8) ? 0 : (int)rows.size();
-  // (self_zero) which accumulator quads this unit still has to initialise: all of them in block 0's unit
-  const bool init_acc = opt.self_zero && blk == 0 && !(opt.ablate & 1);
+  const int n = (int)rows.size();
+  // which accumulator quads this unit still has to initialise: all of them in block 0's unit
+  const bool init_acc = blk == 0;
   std::vector<char> fresh(init_acc ? (size_t)n_idx : 0, 1);
   if (init_acc) {
     std::vector<char> touched((size_t)n_idx, 0);
@@ -131,7 +126,7 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
   // Weights through the scalar cache (Options::sweights): which line and slot every nonzero of the unit's walk takes.
   // A line ends where the next ROW would not fit (so that the switch to a line sits at a row top, where the wave waits
   // for LDS anyway); a row of more than 16 nonzeros runs over several lines.
-  bool sw = opt.sweights && !opt.ablate;
+  bool sw = opt.sweights;
   std::vector<int> line_of, slot_of;
   int n_lines = 0;
   size_t sw_patch = 0;          // index (in `c`) of the literal that carries the distance to the unit's weight lines
@@ -178,10 +173,9 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
     const int sidx = k % n_sets;
     return opt.one_tile > 0 && sidx >= 2 * kInSets ? kAccB + 4 * (sidx - 2 * kInSets) : kVIn0 + set_regs * sidx;
   };
-  Lds lds{c, 0, 0, opt.ablate};
+  Lds lds{c, 0, 0};
   std::vector<int> row_id(n, -1);       // issue id of a row's second read
   auto issue = [&](int k) {
-    if (opt.ablate & 2) return;
     const int base = set_base(k);
     enc_ds_read_b128(c, base, kVAddrA, rows[k].lds_off);
     lds.issue();
@@ -229,9 +223,9 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
     }
   };
   for (int k = 0; k < std::min(depth, n); ++k) issue(k);
-  // weights alternate between two SGPR pairs; with hoisting, the s_mov of the NEXT record (of this
-  // row or the next one) sits in front of the current record's FMAs: the scalar write is long done
-  // when the vector unit reads it
+  // weights alternate between two SGPR pairs; the s_mov of the NEXT record (of this row or the next
+  // one) sits in front of the current record's FMAs: the scalar write is long done when the vector
+  // unit reads it
   std::vector<const Rec *> flat;
   std::vector<int> first_of_row(n + 1, 0);
   for (int k = 0; k < n; ++k) {
@@ -240,14 +234,7 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
   }
   first_of_row[n] = (int)flat.size();
   auto sreg = [](int j) { return (j & 1) ? kSWeight1 : kSWeight0; };
-  if (!sw && opt.hoist_weight && !flat.empty() && !(opt.ablate & 4)) enc_s_mov_lit(c, sreg(0), flat[0]->bits);
-  if ((opt.ablate & 4) && (opt.ablate & 16384)) {
-    // no weight moves, but two nonzero weights in the registers: the FMAs do real arithmetic.  (With whatever the
-    // registers held -- zeros -- the chip draws less power and clocks higher: bit 2 alone overstates the moves' cost
-    // by a factor of three, profiles/r04_walk_limits.md)
-    enc_s_mov_lit(c, kSWeight0, 0x3F9E3779u);
-    enc_s_mov_lit(c, kSWeight1, 0xBF4A7B2Du);
-  }
+  if (!sw && !flat.empty()) enc_s_mov_lit(c, sreg(0), flat[0]->bits);
   int prio = 0;
   // (sweights) the switch to weight line L: everything outstanding lands -- the line, loaded a line ago, and the LDS
   // reads in flight --, then the line after it is requested into the other buffer
@@ -266,22 +253,16 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
       prio ^= 1;
       enc_setprio(c, prio);
     }
-    if (opt.ablate & 2) enc_waitcnt_lgkm(c, 0);
-    else lds.wait_for(row_id[k]);
+    lds.wait_for(row_id[k]);
     issue_pieces(k);
     const int xa = set_base(k), xb = xa + 4;
     for (int j = first_of_row[k]; j < first_of_row[k + 1]; ++j) {
       if (sw) {
         if (j > j0 && slot_of[j] == 0) switch_line(line_of[j]);     // (a row of more than 16 nonzeros)
-      } else if (opt.ablate & 4) {
-      } else if (opt.hoist_weight) {
-        if (j + 1 < (int)flat.size()) enc_s_mov_lit(c, sreg(j + 1), flat[j + 1]->bits);
-      } else {
-        enc_s_mov_lit(c, sreg(j), flat[j]->bits);
+      } else if (j + 1 < (int)flat.size()) {
+        enc_s_mov_lit(c, sreg(j + 1), flat[j + 1]->bits);
       }
-      if (opt.ablate & 1) continue;
       const int a = 4 * flat[j]->idx;
-      // (timing only: 512 = an s_nop behind every FMA -- four more instructions and 16 more bytes per nonzero)
       const bool first = init_acc && fresh[(size_t)flat[j]->idx];     // the quad's first product: multiply, do not accumulate
       auto fma = [&](int acc, int x) {
         if (sw) {
@@ -295,7 +276,6 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
         }
         if (first) enc_pk_mul(c, acc, sreg(j), x);
         else enc_pk_fma(c, acc, sreg(j), x);
-        if (opt.ablate & 512) enc_nop(c);
       };
       fma(kAccA + a, xa);
       fma(kAccA + a + 2, xa + 2);
@@ -317,8 +297,8 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
     // walked must have landed: with one fill in flight that is all of it; with two, all but this unit's own
     // vector-memory operations (its code touches and its pieces, which stage the block after the next).
     const int younger = opt.dma.ahead >= 2 ? n_pref + (int)pieces.size() : 0;
-    if (!(opt.ablate & 32)) enc_waitcnt_vm(c, std::min(63, younger));
-    if (!(opt.ablate & 16)) enc_barrier(c);
+    enc_waitcnt_vm(c, std::min(63, younger));
+    enc_barrier(c);
     const uint32_t all = (uint32_t)opt.chain.nbuf * opt.chain.buf_bytes;
     enc_s_mov(c, kSChainTmp, kSWalkBase);
     enc_s_add_u32_lit(c, kSWalkBase, kSWalkBase, opt.chain.buf_bytes);
@@ -527,8 +507,7 @@ Program build_program(const ConvGeom &g, const Tiling &t, const std::vector<std:
   // few) to a workgroup: no reads, no FMAs for it (the kernel's epilogue stores none of its lanes)
   // ... and a tiling with one quad per lane (stream_builder.h, Tiling::tpl) has no tile B at all: its
   // accumulators hold channels 24 .. 47 of the wave
-  if (t.tpl == 1 || (t.pix_waves == 1 && t.tr * t.nseg <= t.rows_per_slab && opt.one_tile >= 0)) opt.one_tile = 1;
-  else opt.one_tile = 0;
+  opt.one_tile = t.tpl == 1 || (t.pix_waves == 1 && t.tr * t.nseg <= t.rows_per_slab) ? 1 : 0;
   // tile B's accumulators as input registers: only where they hold nothing (two quads per lane in the tiling,
   // none of tile B's rows in the image) -- with one quad per lane they carry channels 24 .. 47
   if (!(opt.one_tile && t.tpl == 2)) opt.hi_sets = 0;

@@ -162,7 +162,12 @@ constexpr int kSWBuf0 = 56, kSWBuf1 = 72;   // two buffers of 16 weights: s[56:7
 constexpr int kSWBase = 88;                 // s[88:89]: address of the unit's weight lines
 constexpr int kSWLine = 16;                 // weights per line (one s_load_dwordx16, 64 bytes)
 inline void enc_nop(std::vector<uint32_t> &c) { c.push_back(0xBF800000u); }
-// ---- accumulators initialised by the code itself (Options::self_zero below) ----
+// ---- accumulators initialised by the code itself ----
+// The kernel body does not clear the accumulators at a tile's top for generated code (192 vector moves per wave and tile:
+// 7 us of a 120 us res2 launch) -- block 0's unit does: the FIRST product of an accumulator pair is a v_pk_mul_f32
+// instead of an FMA onto zero (the same value; a product of -0 keeps its sign where 0 + -0 gave +0), and the pairs
+// block 0 never touches are cleared at its top (rare: a (channel, kernel column) without a nonzero in the block's
+// channels).
 // v_pk_mul_f32 v[acc:acc+1], s[sw:sw+1], v[x:x+1] op_sel_hi:[0,1] -- the first product of an accumulator pair
 inline void enc_pk_mul(std::vector<uint32_t> &c, int acc, int sw, int x) {
   c.push_back(0xD3B14000u | (uint32_t)acc);
@@ -230,16 +235,10 @@ struct Options {
   int depth = 2;          // rows read ahead (1 or 2; three input sets allow 2)
   int depth_one_tile = 5; // ... in code without a tile B (six single-quad sets: up to 5; with hi_sets up to 13)
   int hi_sets = 24;       // extra single-quad input sets in v[160:255] (tile B's accumulators, where tile B has no rows)
-  int hoist_weight = 1;   // s_mov of record j+1 issued before the FMAs of record j
   int prio_rows = 0;      // > 0: s_setprio alternates 1 / 0 every this many rows (0: never) ...
   int prio_waves = 0;     // ... in the units of the first this many waves of a workgroup (0: every unit): the
                           // first-dispatched half loses to a second half that runs at a constant priority 1
                           // and wins every tie against it at 1 (oldest first), so it alternates
-  int ablate = 0;         // timing experiments only (ESCOIN_JIT_ABL; wrong results): 1 no FMAs, 2 no LDS
-                          // reads, 4 no weight moves (+ 16384: with two nonzero weights in the registers), 8 empty
-                          // units, 16 no barrier between chained units, 32 no wait for the plane DMA there, 64 no
-                          // waits for LDS reads, 512 an s_nop behind every FMA.  Builds that change the DATA the FMAs
-                          // see (1, 2, 4 alone) also change the chip's clock: profiles/r04_walk_limits.md
   DmaPlan dma;
   ChainPlan chain;
   int prefetch = 1;       // touch the next unit's code (above)
@@ -251,13 +250,8 @@ struct Options {
                           // load in flight, which can only make them wait longer.  4.06 instead of 5 instructions and 36 instead
                           // of 40 code bytes per nonzero; for the 3x3 / 5x5 layers (their kernel instantiation pays 34 more
                           // clobbered SGPRs around the call: sconv_tiled.hip)
-  int self_zero = 0;      // 1: the kernel body does not clear the accumulators at a tile's top (192 vector moves per wave and
-                          // tile: 7 us of a 120 us res2 launch) -- block 0's unit does: the FIRST product of an accumulator pair is
-                          // a v_pk_mul_f32 instead of an FMA onto zero (the same value; a product of -0 keeps its sign where
-                          // 0 + -0 gave +0), and the pairs block 0 never touches are cleared at its top (rare: a (channel, kernel
-                          // column) without a nonzero in the block's channels)
   int one_tile = 0;       // set by build_program: the tiling leaves tile B without rows, its reads and FMAs
-                          // are not generated (-1: never, ESCOIN_JIT_ONE_TILE=0)
+                          // are not generated
 };
 Options options_from_env();
 

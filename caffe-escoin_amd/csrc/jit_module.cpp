@@ -14,7 +14,6 @@
 
 #include "code_memory.h"
 #include "escoin_plan.h"
-#include "knobs.h"
 
 namespace escoin {
 
@@ -152,11 +151,6 @@ done:
 }
 
 }  // namespace
-
-bool jit_available() {
-  static const bool on = (ESC_KNOB("JIT", 1) != 0);
-  return on;
-}
 
 // Where the blob's temporary file goes: $TMPDIR unless it holds a character the assembler's string
 // syntax would need escaped (the path is spliced into an .incbin directive).
@@ -364,15 +358,13 @@ static int jit_load_direct(const uint32_t *code, size_t words, JitModule *out, h
 
 int jit_load(const uint32_t *code, size_t words, JitModule *out, hipStream_t stream, int loader) {
   if (!code || words == 0) return fail(ESCOIN_EINVAL, "jit: empty program");
-  static const bool direct_on = (ESC_KNOB("JIT_DIRECT", 1) != 0);
-  if (loader == 0 && direct_on) {
+  if (loader == 0) {
     if (jit_load_direct(code, words, out, stream) == ESCOIN_OK) return ESCOIN_OK;
     if (getenv("ESCOIN_VERBOSE")) fprintf(stderr, "[escoin] jit: no executable device memory (%s): the code object loader instead\n", escoin_last_error());
   }
-  static const bool wrap = (ESC_KNOB("JIT_WRAP", 1) != 0);
   const std::vector<uint32_t> words_v(code, code + words);
   std::vector<char> elf;
-  int rc = wrap ? jit_wrap(words_v, &elf) : ESCOIN_EHIP;
+  int rc = jit_wrap(words_v, &elf);
   if (rc == ESCOIN_OK) rc = jit_load_elf(elf, words * 4, out, stream);
   if (rc != ESCOIN_OK) {       // (no template, or a loader that does not take the grown one: the assembler's own)
     rc = jit_assemble(words_v, &elf);

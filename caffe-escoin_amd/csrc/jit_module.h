@@ -16,11 +16,9 @@ struct JitModule {
   size_t code_bytes = 0;
 };
 
-// False when generated code is switched off in this process (ESCOIN_JIT=0); the LDS-staged stream
-// kernel is then what KERNEL_AUTO picks.  (The library links libamd_comgr, a part of every ROCm
-// install and what the HIP runtime itself loads kernels with; a failure inside it at WeightAlign
-// makes KERNEL_AUTO fall back to the stream kernel with a message under ESCOIN_VERBOSE.)
-bool jit_available();
+// (The library links libamd_comgr, a part of every ROCm install and what the HIP runtime itself loads
+// kernels with; a failure inside it at WeightAlign makes KERNEL_AUTO fall back to the stream kernel
+// with a message under ESCOIN_VERBOSE.)
 
 // Puts `code` (jit_codegen.h: position-independent, called through code_base + offset) where the current device can
 // execute it.  loader 0: executable device memory straight from the ROCm runtime's allocator, filled by a copy kernel
@@ -39,7 +37,7 @@ inline int jit_load(const std::vector<uint32_t> &code, JitModule *out, hipStream
 //                 the insertion point moves by a whole number of pages, so file offsets, addresses and segment
 //                 alignments move together, and the headers, section table and symbols are rewritten accordingly.
 //                 tests/test_jit_codegen.py holds the two byte-identical.
-// The code object path of jit_load uses jit_wrap and falls back to jit_assemble (ESCOIN_JIT_WRAP=0: always the assembler).
+// The code object path of jit_load uses jit_wrap and falls back to jit_assemble when the wrapper is refused.
 int jit_assemble(const std::vector<uint32_t> &code, std::vector<char> *elf);
 int jit_wrap(const std::vector<uint32_t> &code, std::vector<char> *elf);
 // Loads a code object jit_wrap / jit_assemble produced.

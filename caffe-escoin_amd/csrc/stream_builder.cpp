@@ -86,8 +86,7 @@ Tiling tile_with(const ConvGeom &g, int waves_per_wg, int lds_budget_bytes, int 
   // A pointwise image walked as ONE row by a workgroup of its own (14 x 14 as 1 x 196: 49 quads on a
   // 64-quad row) needs no row pitch: the planes are packed to the quads that exist.  Lanes past the row
   // read the next channel's quads (theirs are results nobody stores); the fill moves 23 % fewer bytes.
-  if (g.sub == 1 && g.KH == 1 && g.KW == 1 && g.pad_h == 0 && g.pad_w == 0 && !t.band_mode && t.nseg == 1 && t.tr == 1 &&
-      (ESC_KNOB("PACK_ROW", 1) != 0))
+  if (g.sub == 1 && g.KH == 1 && g.KW == 1 && g.pad_h == 0 && g.pad_w == 0 && !t.band_mode && t.nseg == 1 && t.tr == 1)
     t.plane_ch_floats = std::min(t.plane_ch_floats, (g.W + 7) / 8 * 8);   // (whole 32 bytes: the stream's row offsets)
   const int per_ch = t.plane_ch_floats * 4;
   // (row offsets travel as offset / 32 in 11-bit fields of the stream: 64 KiB per plane buffer)
@@ -224,10 +223,9 @@ Tiling choose_tiling(const ConvGeom &g, int waves_per_wg, int lds_budget_bytes, 
       const double used = t.band_mode ? (double)t.H : (double)t.H * (t.rows_per_wg / t.H);
       return used * t.W / (rows * t.RS);
     };
-    static const bool no_recut = ESC_KNOB_SET("NORECUT");
     for (int w = 1; w <= 256 && w <= hw; ++w) {
       if (hw % w != 0 || w == g.W) continue;
-      if (g.W % 4 == 0 && (w % 4 != 0 || no_recut)) continue;   // never trade aligned rows for straddling ones
+      if (g.W % 4 == 0 && w % 4 != 0) continue;   // never trade aligned rows for straddling ones
       ConvGeom c = g;
       c.W = c.OW = w;
       c.H = c.OH = hw / w;
@@ -282,8 +280,7 @@ std::vector<uint32_t> balance_channels(const ConvGeom &g, const Tiling &t, const
   std::vector<uint32_t> slot(static_cast<size_t>(n_ocg) * G);
   for (int o = 0; o < n_ocg; ++o)
     for (int gl = 0; gl < G; ++gl) slot[(size_t)o * G + gl] = (uint32_t)std::min(o * G + gl, Mg - 1);
-  static const bool enabled = (ESC_KNOB("BALANCE", 1) != 0);
-  if (!enabled || g.KW == 1 || t.oc_waves < 2 || Mg < 2 * G) return slot;
+  if (g.KW == 1 || t.oc_waves < 2 || Mg < 2 * G) return slot;
   const double kGroupCost = group_cost, kRecordCost = record_cost;
   const int rows_per_blk = t.icb * g.KH;
   const int words = (rows_per_blk + 63) / 64;
@@ -307,9 +304,8 @@ std::vector<uint32_t> balance_channels(const ConvGeom &g, const Tiling &t, const
   // So first a global deal: channels by descending total cost (rows touched and nonzeros over all blocks), each to
   // the oc-group -- of ANY column -- with the least cost so far that still has a free slot (longest processing time
   // first).  Heavy filters end up on different waves and different workgroups, empty ones fill the gaps.
-  // Deterministic (stable sort, first minimum).  ESCOIN_DEAL_LPT=0 (experiments flavour): the natural order.
-  static const bool lpt = (ESC_KNOB("DEAL_LPT", 1) != 0);
-  if (lpt) {
+  // Deterministic (stable sort, first minimum).
+  {
     std::vector<double> cm(Mg, 0.0);
     for (int m = 0; m < Mg; ++m) {
       int rows = 0, rc = 0;

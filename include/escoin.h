@@ -157,7 +157,7 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  same words either way; tests use 1 to exercise the fallback.  stat "code_direct" says which.
  * Environment: the product build reads ESCOIN_VERBOSE (diagnostics on stderr) and TMPDIR (temporary file of the
  * code object manager's fallback path) and nothing else -- no environment variable can change a result
- * ("Environment"; csrc/knobs.h for the experiment flavours built by tools/mkabl.sh). */
+ * ("Environment"; csrc/knobs.h for the non-product flavours built by tools/mkabl.sh exp / stamps). */
 ESCOIN_API int escoin_plan_set_option(escoin_plan *plan, const char *key, int value);
 
 /* WeightAlign(): dense blobs_[0] (M x C/g x KH x KW, zeros = pruned) -> per-group CSR

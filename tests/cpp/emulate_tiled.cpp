@@ -59,7 +59,7 @@ struct JitChainCtx {
 };
 
 static long g_weight_lines = 0;      // s_load_dwordx16 executed (Options::sweights)
-static long g_first_products = 0, g_cleared = 0;   // v_pk_mul_f32 / v_pk_mov_b32 executed (Options::self_zero)
+static long g_first_products = 0, g_cleared = 0;   // v_pk_mul_f32 / v_pk_mov_b32 executed (the code initialises its accumulators)
 static int jit_run_unit(const std::vector<uint32_t> &code, size_t pc, JitWave &w, const std::vector<float> &lds,
                         const std::vector<uint32_t> &laneA /* LDS byte address of the lane's tile-A quad */,
                         JitDmaCtx *dma = nullptr, JitPref *pref = nullptr, JitChainCtx *chain = nullptr) {
@@ -338,7 +338,7 @@ static int jit_run_unit(const std::vector<uint32_t> &code, size_t pc, JitWave &w
       pc += 8;
       continue;
     }
-    if ((d0 & 0xFFFFF700u) == 0xD3B14000u) {   // v_pk_mul_f32 acc, s[w:w+1], v[x:x+1] op_sel_hi:[0,1] | op_sel:[1,0]: a quad's FIRST product (Options::self_zero)
+    if ((d0 & 0xFFFFF700u) == 0xD3B14000u) {   // v_pk_mul_f32 acc, s[w:w+1], v[x:x+1] op_sel_hi:[0,1] | op_sel:[1,0]: a quad's FIRST product (block 0 initialises its accumulators)
       const int acc = (int)(d0 & 0xFF), sw = (int)(d1 & 0x1FF);
       const int hi = (d0 >> 11) & 1;
       const int x = (int)((d1 >> 9) & 0x1FF) - 256;
@@ -407,17 +407,13 @@ static int run(const Case &cs, bool use_jit) {
   WeightStream ws2 = build_stream(g, t, rp, ci, va);
   jit::Program jp;
   jit::DmaPlan jdma;
-  bool jit_self_zero = false;
   if (use_jit) {
     jit::Options jo;
     jo.depth = 1 + (cs.N & 1);            // both read-ahead depths and both weight placements get exercised
-    jo.hoist_weight = (cs.C >> 1) & 1;
     jo.prio_rows = (cs.M & 1) ? 2 : 0;
     jo.hi_sets = (cs.N & 1) ? 24 : 0;     // (used only by code without a tile B: deeper read-ahead through tile B's registers)
     jo.depth_one_tile = (cs.N & 1) ? 5 + cs.N % 9 : 5;
-    jo.sweights = cs.KW != 1 && (cs.C & 3) != 1;
-    jo.self_zero = (cs.M % 3) != 0;       // the code initialises its accumulators (most geometries; the kernel's own clearing stays covered)
-    jit_self_zero = jo.self_zero != 0;     // weights through the scalar cache: most 3x3 / 5x5 geometries (not all: both forms stay covered)
+    jo.sweights = cs.KW != 1 && (cs.C & 3) != 1;   // weights through the scalar cache: most 3x3 / 5x5 geometries (not all: both forms stay covered)
     // plane DMA from inside the code wherever one wave owns an oc-group (whatever the table's size: the
     // product bounds it, the emulation does not need to)
     if (t.pix_waves == 1 && (t.waves == 8 || t.waves == 4)) {
@@ -486,8 +482,8 @@ static int run(const Case &cs, bool use_jit) {
     for (int cg = 0; cg < g.group; ++cg)
       for (int ocblk = 0; ocblk < t.n_ocblk; ++ocblk) {
         // per-wave accumulators: [wave][lane][192]
-        // (Options::self_zero: nobody clears the accumulators for the code -- they start as NaN, and an FMA onto one is an error)
-        const float acc0 = (use_jit && jit_self_zero) ? std::nanf("") : 0.f;
+        // (nobody clears the accumulators for generated code -- they start as NaN, and an FMA onto one is an error)
+        const float acc0 = use_jit ? std::nanf("") : 0.f;
         std::vector<float> acc((size_t)t.waves * 64 * kAccAll, acc0);
         auto fill_block = [&](int blk, std::vector<float> &lds) {
           std::fill(lds.begin(), lds.end(), 0.f);

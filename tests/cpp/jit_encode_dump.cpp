@@ -51,7 +51,7 @@ int main() {
              sd + 1, x, x + 1, acc, acc + 1);
     dump(buf, c);
   }
-  // accumulators initialised by the code (Options::self_zero)
+  // accumulators initialised by the code (jit_codegen.h)
   for (int i = 0; i < 60; ++i) {
     std::vector<uint32_t> c;
     const int acc = 64 + 2 * rnd(96), x = 36 + 2 * rnd(12);

@@ -144,6 +144,23 @@ def test_set_csr_validates_on_host(pkg):
         assert "ascending" in str(e.value)
 
 
+def test_experiment_switches_are_the_ones_knobs_h_lists():
+    """Every ESC_KNOB / ESC_KNOB_F / ESC_KNOB_SET name used across csrc/ is listed in knobs.h (one line each, with what it
+    overrides), and every listed name is used: the list is the whole set the experiments and stamps flavours read."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "caffe-escoin_amd", "csrc")
+    used = {}
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".cpp", ".h")) and fn != "knobs.h":
+            for name in re.findall(r'ESC_KNOB(?:_F|_SET)?\(\s*"([A-Z0-9_]+)"', open(os.path.join(csrc, fn)).read()):
+                used.setdefault(name, fn)
+    listed = re.findall(r"^//   ESCOIN_([A-Z0-9_]+)\s+\S", open(os.path.join(csrc, "knobs.h")).read(), re.M)
+    assert len(listed) == len(set(listed)), sorted(listed)
+    assert set(used) - set(listed) == set(), {n: used[n] for n in set(used) - set(listed)}
+    assert set(listed) - set(used) == set(), sorted(set(listed) - set(used))
+    assert len(listed) == 24
+
+
 def test_package_is_importable_under_alias():
     import __graft_entry__ as ge
     p = ge.load_package()
@@ -151,10 +168,10 @@ def test_package_is_importable_under_alias():
 
 
 def test_product_library_reads_no_experiment_switches():
-    """The product build reads ESCOIN_VERBOSE (diagnostics) and TMPDIR and nothing else: every tuning switch is a
-    compile-time constant there and the wrong-result switches (ESCOIN_DBG, ESCOIN_JIT_ABL, ESCOIN_DENSE_ABL) exist in
-    the -DESCOIN_ABLATIONS flavour only (csrc/knobs.h, tools/mkabl.sh).  The names must not even
-    be in the binary: a leftover environment variable cannot change a result."""
+    """The product build reads ESCOIN_VERBOSE (diagnostics) and TMPDIR and nothing else: every tuning override is a
+    compile-time constant there and the stamp profile (ESCOIN_PROF) exists in the -DESCOIN_STAMPS flavour only
+    (csrc/knobs.h, tools/mkabl.sh).  The names must not even be in the binary: a leftover
+    environment variable cannot change a result -- nor can the retired wrong-result switches come back."""
     import re
     import subprocess
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -172,6 +189,10 @@ def test_product_library_reads_no_experiment_switches():
         for line in open(os.path.join(csrc, fn)):
             for m in re.finditer(r'getenv\("([A-Z_0-9]+)"\)', line):
                 assert m.group(1) in ("ESCOIN_VERBOSE", "TMPDIR"), (fn, line.strip())
+    # (no switch that makes a result wrong exists in any flavour)
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".cpp", ".h", ".py")):
+            assert not re.search(r"ESC_ABL_KNOB|ESC_DBG|ESCOIN_ABLATIONS", open(os.path.join(csrc, fn)).read()), fn
     # and no A/B artefact sits in the package directory (it would ship with every push to a GPU box)
     extra = [f for f in os.listdir(os.path.join(ROOT, "caffe-escoin_amd")) if f.endswith(".so") and f != "libescoin_hip.so"]
     assert not extra, extra

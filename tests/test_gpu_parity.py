@@ -1327,18 +1327,16 @@ def test_batches_off_the_tilings_grid(pkg, oracle, synth, torch_cuda, n):
 
 def test_dense_strided_pointwise_through_registers(pkg, oracle, synth, torch_cuda):
     """Dense (fp32 MFMA) kernel, 1x1 convolutions with stride > 1 and no padding (ResNet-50's res{3,4,5}a_branch1 /
-    branch2a; the reference: forward_gpu_gemm + im2col, base_conv_layer.cpp:713-746).  The product gathers their B tile 4
-    bytes per LDS-DMA lane; the experiments flavour (ESCOIN_LIB=tools/ab/libescoin_exp.so ESCOIN_DENSE_S2=1) stages it
-    through registers instead -- one aligned 16-byte load per lane and k-row where the output width is even and the stride
-    2, two 4-byte loads otherwise: built for VERDICT r4 item 4, measured 0-9 % slower, not shipped (profiles/r05_dense.md).
-    Either way the same cases must hold: even and odd output widths, an odd input
+    branch2a; the reference: forward_gpu_gemm + im2col, base_conv_layer.cpp:713-746).  The kernel gathers their B tile 4
+    bytes per LDS-DMA lane (a mode staging it through registers was built for VERDICT r4 item 4, measured 0-9 % slower
+    and removed: profiles/r05_dense.md; the test keeps its name).  The cases: even and odd output widths, an odd input
     width, stride 3, conv groups, a channel count that is not whole k-steps (rows past K must read as zeros: NaNs are
     planted behind the blob), fewer output channels than a tile, a batch whose last tile is ragged, fused ReLU."""
     torch = torch_cuda
     dev = torch.device("cuda:0")
-    cases = [synth.shape("s2_56", 3, 64, 56, 56, 128, 1, stride=2, bias=True, sparsity=0.2),          # pair path, 128-row tiles
-             synth.shape("s2_28", 5, 96, 28, 28, 64, 1, stride=2, bias=True, sparsity=0.3),           # pair path, 64-row tiles
-             synth.shape("s2_14", 7, 128, 14, 14, 160, 1, stride=2, bias=False, sparsity=0.1),        # odd OW = 7: 4-byte loads
+    cases = [synth.shape("s2_56", 3, 64, 56, 56, 128, 1, stride=2, bias=True, sparsity=0.2),          # even OW, 128-row tiles
+             synth.shape("s2_28", 5, 96, 28, 28, 64, 1, stride=2, bias=True, sparsity=0.3),           # even OW, 64-row tiles
+             synth.shape("s2_14", 7, 128, 14, 14, 160, 1, stride=2, bias=False, sparsity=0.1),        # odd OW = 7
              synth.shape("s2_odd_w", 4, 40, 13, 13, 48, 1, stride=2, bias=True, sparsity=0.5),        # odd input width, K = 40: a k tail
              synth.shape("s3", 3, 36, 16, 16, 40, 1, stride=3, bias=True, sparsity=0.4),              # stride 3
              synth.shape("s2_groups", 3, 80, 12, 12, 96, 1, stride=2, group=2, bias=True, sparsity=0.3),  # K = 40 per group

@@ -11,7 +11,9 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_stream_and_tiling_against_cpu_emulation(tmp_path):
+def test_stream_and_self_initialising_code_against_cpu_emulation(tmp_path):
+    """The LDS-staged stream and the generated code of 40 geometries, emulated instruction by instruction against a
+    dense convolution.  Generated code always initialises its own accumulators (jit_codegen.h): every case must."""
     exe = str(tmp_path / "emulate_tiled")
     csrc = os.path.join(ROOT, "caffe-escoin_amd", "csrc")
     subprocess.check_call(["g++", "-O2", "-std=c++17", "-I" + csrc, "-o", exe,
@@ -25,15 +27,29 @@ def test_stream_and_tiling_against_cpu_emulation(tmp_path):
     # generates, interpreted instruction by instruction
     assert text.count("rel_err=") == 40 + 40
     assert len([l for l in text.splitlines() if l.startswith("jit ")]) == 40
-    # ... most of them with code that initialises its own accumulators (first products as multiplies, the quads block 0 never
-    # touches cleared at its top; the interpreter starts those accumulators as NaN and refuses an FMA onto one)
+    # ... every one of them with code that initialises its own accumulators (first products as multiplies, the quads block 0
+    # never touches cleared at its top; the interpreter starts those accumulators as NaN and refuses an FMA onto one)
     init = [tuple(int(v) for v in l.split("init=")[1].split()[0].split("+")) for l in text.splitlines() if l.startswith("jit ")]
     assert sum(1 for m, z in init if m > 0) >= 20 and sum(1 for m, z in init if z > 0) >= 3
-    assert sum(1 for m, z in init if m == 0 and z == 0) >= 8
+    assert all(m + z > 0 for m, z in init), init
     # ... a good part of them as chains (one call per tile), several blocks long, with one and two fills in flight
     chained = [l for l in text.splitlines() if l.startswith("jit chained ")]
     assert len(chained) >= 15
     assert sum(1 for l in chained if int(l.split("icb=")[1].split()[0].split("/")[1]) >= 3) >= 4
+
+
+def test_stream_loop_generator_reads_no_environment():
+    """gen_stream_loop.py writes the same stream_loop_asm.inc whatever the build shell holds: the ESC_GEN_* variables it
+    once read (priorities, store modifiers, an alignment pass) cannot change the product kernel."""
+    import sys
+    gen = os.path.join(ROOT, "caffe-escoin_amd", "csrc", "gen_stream_loop.py")
+    clean = {k: v for k, v in os.environ.items() if not k.startswith("ESC_GEN_")}
+    want = subprocess.run([sys.executable, gen], env=clean, stdout=subprocess.PIPE, check=True, timeout=300).stdout
+    dirty = dict(clean, ESC_GEN_NOPRIO="1", ESC_GEN_STORE_MOD=" nt", ESC_GEN_ALIGN="4", ESC_GEN_PRIO_QUADS="0",
+                 ESC_GEN_PRIO_HI="2", ESC_GEN_PRIO_YOUNG="0", ESC_GEN_PRIO_YOUNG_HI="1")
+    got = subprocess.run([sys.executable, gen], env=dirty, stdout=subprocess.PIPE, check=True, timeout=300).stdout
+    assert len(want) > 100000 and b"ESC2_LOOP_ASM_BAND_YOUNG_DMA" in want
+    assert got == want
 
 
 def test_channel_deal_is_a_permutation_and_never_worse(tmp_path):

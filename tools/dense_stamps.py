@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """In-kernel stamp profile of escoin_dense_mfma_kernel on named dense 1x1 shapes of the ResNet-50 chain.
-    ESCOIN_LIB=$PWD/tools/ab/libescoin_abl.so ESCOIN_PROF=1 python tools/dense_stamps.py          (stamps, stderr)
+    ESCOIN_LIB=$PWD/tools/ab/libescoin_stamps.so ESCOIN_PROF=1 python tools/dense_stamps.py          (stamps, stderr)
     python tools/dense_stamps.py                                                                  (timing only)"""
 import os
 import sys

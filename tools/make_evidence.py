@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Condenses what tools/evidence.sh left under gpurun_out/<tag>/ into tracked files under profiles/:
-   <round>_probe_valu_rate.txt, <round>_probe_mixload.txt, <round>_stamp_profile.md, <round>_jit_ablations.md
+   <round>_probe_valu_rate.txt, <round>_probe_mixload.txt, <round>_stamp_profile.md
      python tools/make_evidence.py gpurun_out/r04a r04
 """
 import os
@@ -33,7 +33,7 @@ names = {"goog0": "conv2/3x3_reduce 64@56x56->64", "goog5": "inception_3b/1x1 25
 cats = ["tab+zero", "hdr load", "vmcnt wait", "barrier", "issue_fill", "loop", "epilogue", "tile misc"]
 with open(os.path.join(out, "%s_stamp_profile.md" % tag), "w") as f:
     f.write("# In-kernel stamp profile of the shipped kernels (generated-code path), one MI355X, %s\n\n" % tag)
-    f.write("`tools/evidence.sh`: the `-DESCOIN_ABLATIONS` build of the tree (`tools/mkabl.sh`) with `ESCOIN_PROF=1`, one layer at\n"
+    f.write("`tools/evidence.sh`: the `-DESCOIN_STAMPS` build of the tree (`tools/mkabl.sh stamps`) with `ESCOIN_PROF=1`, one layer at\n"
             "batch 256 per process (`tools/one_layer.py <layer> 2`, four rotating blob pairs: every launch reads from HBM).\n"
             "Cycle stamps (`s_memtime`, shader clock) of WAVE 0 of every workgroup, summed over its tiles and blocks and averaged\n"
             "over the workgroups of the LAST launch; `GHz` = shader cycles / `s_memrealtime` (100 MHz) over a workgroup's life.\n"
@@ -58,8 +58,8 @@ with open(os.path.join(out, "%s_stamp_profile.md" % tag), "w") as f:
         vals = {k: int(v) for k, v in re.findall(r"(tab\+zero|hdr load|vmcnt wait|barrier|issue_fill|loop|epilogue|tile misc)=(\d+)", w0)}
         byw = spread.split("loop by wave id:")[1].split()
         t_prod = last(os.path.join(src, "time_%s.log" % L), "us per launch").split(":")[-1].split()
-        t_abl = last(os.path.join(src, "time_abl_%s.log" % L), "us per launch").split(":")[-1].split()
-        kp, ka = sorted(map(float, t_prod))[len(t_prod) // 2], sorted(map(float, t_abl))[len(t_abl) // 2]
+        t_stamps = last(os.path.join(src, "time_stamps_%s.log" % L), "us per launch").split(":")[-1].split()
+        kp, ka = sorted(map(float, t_prod))[len(t_prod) // 2], sorted(map(float, t_stamps))[len(t_stamps) // 2]
         f.write("| %s | %.1f / %.1f | %.1f @ %.2f | %s | %s |\n" %
                 (names[L], kp, ka, us, ghz,
                  " | ".join("%d (%.1f us, %d %%)" % (vals[c], vals[c] / ghz * 1e-3, round(100.0 * vals[c] / sum(vals.values()))) for c in cats),
@@ -76,29 +76,4 @@ with open(os.path.join(out, "%s_stamp_profile.md" % tag), "w") as f:
         parts = [c("tile misc") * scale, c("tab+zero") * scale, tops * scale, c("loop") * scale, c("epilogue") * scale, ka - us]
         f.write("| %s | %s | %.1f | %.1f |\n" % (names[L], " | ".join("%.1f" % x for x in parts), sum(parts), kp))
 
-if not os.path.exists(os.path.join(src, "jit_abl_res2.txt")):
-    print("written (stamp profile only)")
-    sys.exit(0)
-with open(os.path.join(out, "%s_jit_ablations.md" % tag), "w") as f:
-    f.write("# Timing-only ablations of the generated-code kernel, ResNet-50 3x3 shapes @90 %%, batch 256, one MI355X, %s\n\n" % tag)
-    f.write("`tools/evidence.sh`: `tools/one_layer.py <layer> 100` (four rotating blob pairs: every launch reads from HBM), us per launch,\n"
-            "median of five runs of 100 launches.  Results are WRONG for every row but the first: these builds only tell where the time goes.\n"
-            "`ESCOIN_JIT_ABL` (code generator): 1 = no FMAs emitted, 2 = no LDS reads, 4 = no weight moves, 8 = empty units (the units only\n"
-            "stage the next block's planes and return); `ESCOIN_DBG` (kernel body): 1 = plane DMA reads zeros (no HBM reads), 2 = units never\n"
-            "entered (plane DMA issued from the C++ block top instead), 3 = both, 4 = units entered but the plane DMA issued from C++,\n"
-            "128 = no stores, 64 = no code touches before the first unit.\n\n")
-    rows = [("ABL=0", "the product"), ("ABL=1", "no FMAs"), ("ABL=2", "no LDS reads"), ("ABL=4", "no weight moves"),
-            ("ABL=3", "no FMAs, no LDS reads"), ("ABL=7", "rows and waits only"), ("ABL=8", "empty units"),
-            ("DBG=1", "zero-fill plane DMA"), ("DBG=2", "no walk, DMA from the block top"), ("DBG=3", "no walk, zero fill"),
-            ("DBG=4", "walk + DMA from the block top"), ("DBG=128", "no stores"), ("DBG=64", "no first-unit code touches")]
-    data = {}
-    for L in ("res2", "res3", "res4", "res5"):
-        for line in open(os.path.join(src, "jit_abl_%s.txt" % L)):
-            key = line.split()[0]
-            ts = sorted(map(float, line.split(":")[-1].split()))
-            data[(L, key)] = ts[len(ts) // 2]
-    f.write("| build | what is left out | res2 | res3 | res4 | res5 |\n|---|---|---|---|---|---|\n")
-    for key, what in rows:
-        f.write("| `%s` | %s | %s |\n" % (key.replace("ABL", "ESCOIN_JIT_ABL").replace("DBG", "ESCOIN_DBG"), what,
-                                        " | ".join("%.1f" % data[(L, key)] for L in ("res2", "res3", "res4", "res5"))))
 print("written")

@@ -1,19 +1,19 @@
 #!/bin/bash
-# Builds a NON-PRODUCT flavour of the library into tools/ab/ (never into the package directory; csrc/knobs.h):
-#   tools/mkabl.sh          -> tools/ab/libescoin_abl.so   -DESCOIN_ABLATIONS: in-kernel stamp profile (ESCOIN_PROF=1),
-#                                                          wrong-result timing switches (ESCOIN_DBG, ESCOIN_JIT_ABL,
-#                                                          ESCOIN_DENSE_ABL) and every tuning switch
-#   tools/mkabl.sh exp      -> tools/ab/libescoin_exp.so   -DESCOIN_EXPERIMENTS: the tuning switches only (tilings,
-#                                                          buffers, kernel selection ...); results stay right
+# Builds a NON-PRODUCT flavour of the library into tools/ab/ (never into the package directory; csrc/knobs.h lists
+# the switches they read).  Neither flavour can produce a wrong result:
+#   tools/mkabl.sh exp      -> tools/ab/libescoin_exp.so      -DESCOIN_EXPERIMENTS: the tuning overrides are live (tilings,
+#                                                             buffers, XCD grouping, DMA spread ...)
+#   tools/mkabl.sh stamps   -> tools/ab/libescoin_stamps.so   -DESCOIN_STAMPS: the above plus the in-kernel stamp profiles
+#                                                             of the tiled and dense kernels (ESCOIN_PROF=1)
 # ABL_CFLAGS adds flags (e.g. -DESCOIN_PROF_STARTUP), ABL_NAME overrides the output tag.  Select a flavour at run
 # time with ESCOIN_LIB=$PWD/tools/ab/libescoin_<tag>.so (the Python binding; the product never reads it).
 set -e
 cd "$(dirname "$0")/../caffe-escoin_amd/csrc"
-FLAVOUR=${1:-abl}
+FLAVOUR=${1:-}
 case $FLAVOUR in
-  abl) DEF=-DESCOIN_ABLATIONS ;;
   exp) DEF=-DESCOIN_EXPERIMENTS ;;
-  *) echo "usage: $0 [abl|exp]"; exit 2 ;;
+  stamps) DEF=-DESCOIN_STAMPS ;;
+  *) echo "usage: $0 exp|stamps"; exit 2 ;;
 esac
 TAG=${ABL_NAME:-$FLAVOUR}
 make stream_loop_asm.inc

@@ -16,4 +16,4 @@ for (C, H, M) in [(256, 14, 256), (128, 28, 128)]:
     a.record()
     for _ in range(200): y = plan.forward(x, None)
     b.record(); torch.cuda.synchronize()
-    print("BALANCE=%s C%d %dx%d M%d channel densities U(0,0.2): %.1f us  (%s, density %.3f)" % (os.environ.get("ESCOIN_BALANCE", "1"), C, H, H, M, a.elapsed_time(b) / 200 * 1e3, plan.kernel_name, float((w != 0).mean())))
+    print("C%d %dx%d M%d channel densities U(0,0.2): %.1f us  (%s, density %.3f)" % (C, H, H, M, a.elapsed_time(b) / 200 * 1e3, plan.kernel_name, float((w != 0).mean())))
