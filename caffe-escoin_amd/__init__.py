@@ -42,6 +42,8 @@ API_SYMBOLS = [
     "escoin_cpu_kernel_name", "escoin_cpu_kernel_select", "escoin_weight_align_cpu", "escoin_weight_align_cpu_f64",
     "escoin_forward_cpu", "escoin_forward_cpu_f64", "escoin_cpu_sconv", "escoin_cpu_sconv_f64",
     "escoin_cpu_sparse_dense2csr", "escoin_cpu_sparse_dense2csr_f64",
+    # Backward (pattern-preserving)
+    "escoin_backward", "escoin_backward_f64", "escoin_backward_cpu", "escoin_backward_cpu_f64",
 ]
 
 
@@ -159,6 +161,9 @@ def lib():
             L.escoin_gpu_sparse_dense2csr_f64.argtypes = L.escoin_gpu_sparse_dense2csr.argtypes
             L.escoin_gpu_sparse_csrmm_f64.restype = ip
             L.escoin_gpu_sparse_csrmm_f64.argtypes = [ip, ip, ip, ip, real, vp, vp, vp, vp, real, vp, vp]
+    for name in ("escoin_backward", "escoin_backward_f64", "escoin_backward_cpu", "escoin_backward_cpu_f64"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = ip, [vp] * 7 + [ip, vp if "cpu" not in name else ip]
     L.escoin_cpu_kernel_name.restype = cp
     L.escoin_cpu_kernel_name.argtypes = []
     L.escoin_cpu_kernel_select.restype = ip
@@ -370,3 +375,76 @@ class Plan(object):
         self.forward_ptr(bottom.data_ptr(), bias.data_ptr() if bias is not None else 0,
                          top.data_ptr(), n, stream)
         return top
+
+    # ---- Backward (pattern-preserving; include/escoin.h "Backward") ----------------------------------------------------
+    def _grad_shapes(self):
+        d = self.desc
+        return (d.C // d.group, d.KH, d.KW)
+
+    def backward(self, top_diff, bottom=None, top=None, bottom_diff=True, weight_diff=None, bias_diff=None):
+        """Backward_gpu on torch CUDA tensors, on torch's current stream.  bottom_diff: True = a new tensor, a tensor =
+        written (overwritten) in place, None / False = not computed.  weight_diff / bias_diff: True = a new zeroed tensor,
+        a tensor = accumulated into (+=, at the CSR positions only for the weights), None / False = not computed.
+        Returns (bottom_diff, weight_diff, bias_diff)."""
+        import torch
+        d = self.desc
+        g = top_diff
+        dt = g.dtype
+        assert g.is_cuda and dt in (torch.float32, torch.float64) and g.is_contiguous()
+        n = g.shape[0]
+        assert tuple(g.shape[1:]) == (d.M,) + tuple(self.out_hw), "top_diff shape mismatch"
+
+        def _new_or(t, shape, zero):
+            if t is None or t is False:
+                return None
+            if t is True:
+                return (torch.zeros if zero else torch.empty)(shape, device=g.device, dtype=dt)
+            assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+            return t
+
+        bd = _new_or(bottom_diff, (n, d.C, d.H, d.W), False)
+        wd = _new_or(weight_diff, (d.M,) + self._grad_shapes(), True)
+        bsd = _new_or(bias_diff, (d.M,), True)
+        for t in (bottom, top):
+            if t is not None:
+                assert t.is_cuda and t.dtype == dt and t.is_contiguous()
+
+        def _p(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+
+        stream = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
+        fn = lib().escoin_backward_f64 if dt == torch.float64 else lib().escoin_backward
+        check(fn(self._h, _p(bottom), _p(top), _p(g), _p(bd), _p(wd), _p(bsd), int(n), stream), "escoin_backward")
+        return bd, wd, bsd
+
+    def backward_cpu(self, top_diff, bottom=None, top=None, bottom_diff=True, weight_diff=None, bias_diff=None,
+                     n_threads=0):
+        """Backward_cpu on numpy arrays (float32 or float64, matching the aligned weights); arguments and result as in
+        backward()."""
+        d = self.desc
+        f64 = top_diff.dtype == np.float64
+        dt = np.float64 if f64 else np.float32
+        g = np.ascontiguousarray(top_diff, dt)
+        n = g.shape[0]
+        assert tuple(g.shape[1:]) == (d.M,) + tuple(self.out_hw), "top_diff shape mismatch"
+
+        def _new_or(t, shape, zero):
+            if t is None or t is False:
+                return None
+            if t is True:
+                return (np.zeros if zero else np.empty)(shape, dt)
+            assert t.dtype == dt and t.flags["C_CONTIGUOUS"] and tuple(t.shape) == tuple(shape)
+            return t
+
+        bd = _new_or(bottom_diff, (n, d.C, d.H, d.W), False)
+        wd = _new_or(weight_diff, (d.M,) + self._grad_shapes(), True)
+        bsd = _new_or(bias_diff, (d.M,), True)
+        x = None if bottom is None else np.ascontiguousarray(bottom, dt)
+        t = None if top is None else np.ascontiguousarray(top, dt)
+
+        def _p(a):
+            return _np_ptr(a) if a is not None else None
+
+        fn = lib().escoin_backward_cpu_f64 if f64 else lib().escoin_backward_cpu
+        check(fn(self._h, _p(x), _p(t), _p(g), _p(bd), _p(wd), _p(bsd), int(n), int(n_threads)), "escoin_backward_cpu")
+        return bd, wd, bsd

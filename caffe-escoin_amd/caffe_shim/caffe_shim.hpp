@@ -12,6 +12,10 @@
 //   caffe::ConvolutionLayer      include/caffe/layers/conv_layer.hpp:30-80, conv_layer.cu:8-40
 //   caffe::ConvolutionReLULayer  include/caffe/layers/conv_relu_layer.hpp, conv_relu_layer.cu:8-30
 //
+// Backward_gpu / Backward_cpu (conv_layer.cu:42-73, conv_layer.cpp:65-99) call the library's pattern-preserving
+// backward (escoin_backward[_cpu], include/escoin.h): gradients flow through the CSR's nonzeros only and the weight
+// gradient lands at the CSR's positions only, so a fine-tuning step keeps the pruned weights at 0.
+//
 // Forward_gpu and Forward_cpu both call the C ABI (include/escoin.h): Caffe::GPU mode runs the HIP kernels,
 // Caffe::CPU mode the library's host kernel (escoin_forward_cpu; no device is touched, so a CPU-mode net runs on a
 // machine without a GPU).  Every class is a template over Dtype = float | double like the reference's
@@ -104,12 +108,16 @@ template <> struct EscApi<float> {
   static int weight_align_cpu(escoin_plan *p, const float *w) { return escoin_weight_align_cpu(p, w); }
   static int forward(escoin_plan *p, const float *b, const float *bias, float *t, int n, void *s) { return escoin_forward(p, b, bias, t, n, s); }
   static int forward_cpu(escoin_plan *p, const float *b, const float *bias, float *t, int n, int threads) { return escoin_forward_cpu(p, b, bias, t, n, threads); }
+  static int backward(escoin_plan *p, const float *b, const float *t, const float *td, float *bd, float *wd, float *bsd, int n, void *s) { return escoin_backward(p, b, t, td, bd, wd, bsd, n, s); }
+  static int backward_cpu(escoin_plan *p, const float *b, const float *t, const float *td, float *bd, float *wd, float *bsd, int n, int threads) { return escoin_backward_cpu(p, b, t, td, bd, wd, bsd, n, threads); }
 };
 template <> struct EscApi<double> {
   static int weight_align(escoin_plan *p, const double *w, int on_dev, void *s) { return escoin_weight_align_f64(p, w, on_dev, s); }
   static int weight_align_cpu(escoin_plan *p, const double *w) { return escoin_weight_align_cpu_f64(p, w); }
   static int forward(escoin_plan *p, const double *b, const double *bias, double *t, int n, void *s) { return escoin_forward_f64(p, b, bias, t, n, s); }
   static int forward_cpu(escoin_plan *p, const double *b, const double *bias, double *t, int n, int threads) { return escoin_forward_cpu_f64(p, b, bias, t, n, threads); }
+  static int backward(escoin_plan *p, const double *b, const double *t, const double *td, double *bd, double *wd, double *bsd, int n, void *s) { return escoin_backward_f64(p, b, t, td, bd, wd, bsd, n, s); }
+  static int backward_cpu(escoin_plan *p, const double *b, const double *t, const double *td, double *bd, double *wd, double *bsd, int n, int threads) { return escoin_backward_cpu_f64(p, b, t, td, bd, wd, bsd, n, threads); }
 };
 
 // syncedmem.hpp:56-91: lazily mirrored host/device buffer with a head state.
@@ -165,7 +173,7 @@ class SyncedMemory {
 };
 
 template <typename Dtype>
-class Blob {   // blob.hpp (data only: the forward path never touches diff_)
+class Blob {   // blob.hpp (data and diff)
  public:
   Blob() : count_(0), capacity_(0) {}
   explicit Blob(const vector<int> &shape) : count_(0), capacity_(0) { Reshape(shape); }
@@ -184,6 +192,7 @@ class Blob {   // blob.hpp (data only: the forward path never touches diff_)
     if (count_ > capacity_) {
       capacity_ = count_;
       data_.reset(new SyncedMemory(capacity_ * sizeof(Dtype)));
+      diff_.reset(new SyncedMemory(capacity_ * sizeof(Dtype)));   // blob.cpp:31-33: allocated with the data
     }
   }
   const vector<int> &shape() const { return shape_; }
@@ -203,9 +212,14 @@ class Blob {   // blob.hpp (data only: the forward path never touches diff_)
   const Dtype *gpu_data() const { ESC_CHECK(data_); return (const Dtype *)data_->gpu_data(); }
   Dtype *mutable_cpu_data() { ESC_CHECK(data_); return (Dtype *)data_->mutable_cpu_data(); }
   Dtype *mutable_gpu_data() { ESC_CHECK(data_); return (Dtype *)data_->mutable_gpu_data(); }
+  // blob.hpp:224-229
+  const Dtype *cpu_diff() const { ESC_CHECK(diff_); return (const Dtype *)diff_->cpu_data(); }
+  const Dtype *gpu_diff() const { ESC_CHECK(diff_); return (const Dtype *)diff_->gpu_data(); }
+  Dtype *mutable_cpu_diff() { ESC_CHECK(diff_); return (Dtype *)diff_->mutable_cpu_data(); }
+  Dtype *mutable_gpu_diff() { ESC_CHECK(diff_); return (Dtype *)diff_->mutable_gpu_data(); }
 
  private:
-  shared_ptr<SyncedMemory> data_;
+  shared_ptr<SyncedMemory> data_, diff_;
   vector<int> shape_;
   int count_, capacity_;
 };
@@ -267,6 +281,23 @@ class Layer {   // layer.hpp:33-475
     }
     return 0;
   }
+  // layer.hpp:478-491: the mode switch; the bottoms' diffs for propagate_down[i], the parameters' diffs accumulated
+  // for param_propagate_down
+  inline void Backward(const vector<Blob<Dtype> *> &top, const vector<bool> &propagate_down,
+                       const vector<Blob<Dtype> *> &bottom) {
+    switch (Caffe::mode()) {
+      case Caffe::CPU: Backward_cpu(top, propagate_down, bottom); break;
+      case Caffe::GPU: Backward_gpu(top, propagate_down, bottom); break;
+    }
+  }
+  // layer.hpp:287-300
+  inline bool param_propagate_down(const int param_id) {
+    return (param_propagate_down_.size() > (size_t)param_id) ? param_propagate_down_[param_id] : false;
+  }
+  inline void set_param_propagate_down(const int param_id, const bool value) {
+    if (param_propagate_down_.size() <= (size_t)param_id) param_propagate_down_.resize(param_id + 1, true);
+    param_propagate_down_[param_id] = value;
+  }
   vector<shared_ptr<Blob<Dtype> > > &blobs() { return blobs_; }
   const LayerParameter &layer_param() const { return layer_param_; }
   virtual inline const char *type() const { return ""; }
@@ -280,8 +311,17 @@ class Layer {   // layer.hpp:33-475
   virtual void Forward_gpu(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &top) {
     Forward_cpu(bottom, top);
   }
+  // layer.hpp:330-345 (Backward_cpu is pure there; here a layer without a backward aborts when asked for one)
+  virtual void Backward_cpu(const vector<Blob<Dtype> *> &, const vector<bool> &, const vector<Blob<Dtype> *> &) {
+    NOT_IMPLEMENTED;
+  }
+  virtual void Backward_gpu(const vector<Blob<Dtype> *> &top, const vector<bool> &propagate_down,
+                            const vector<Blob<Dtype> *> &bottom) {
+    Backward_cpu(top, propagate_down, bottom);
+  }
   LayerParameter layer_param_;
   vector<shared_ptr<Blob<Dtype> > > blobs_;
+  vector<bool> param_propagate_down_;   // layer.hpp:434
   float test_time_;
 };
 
@@ -309,6 +349,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
     wshape[0] = num_output_; wshape[1] = channels_ / group_; wshape[2] = cp.kernel_h; wshape[3] = cp.kernel_w;
     this->blobs_[0].reset(new Blob<Dtype>(wshape));
     if (bias_term_) this->blobs_[1].reset(new Blob<Dtype>(vector<int>(1, num_output_)));
+    this->param_propagate_down_.resize(this->blobs_.size(), true);   // :445
   }
 
   // base_conv_layer.cpp:449-530: output shape, all bottoms identical, top reshape
@@ -427,6 +468,25 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
     const Dtype *bias = bias_term_ ? this->blobs_[1]->cpu_data() : nullptr;
     ESCOIN_CHECK(EscApi<Dtype>::forward_cpu(plan_, input, bias, output, num_, Caffe::cpu_threads()));
   }
+  // Backward_gpu's body for one bottom/top pair (backward_gpu_gemm / weight_gpu_gemm / backward_gpu_bias,
+  // base_conv_layer.cpp:859-897, pattern-preserving): a NULL output is not computed.  A plan aligned in CPU mode is
+  // aligned on the device on the spot, as in forward_gpu_sconv_par.
+  void backward_gpu_sconv(const Dtype *bottom, const Dtype *top, const Dtype *top_diff, Dtype *bottom_diff,
+                          Dtype *weight_diff, Dtype *bias_diff) {
+    ESC_CHECK(aligned_);
+    if (!aligned_on_device_) {
+      ESCOIN_CHECK(EscApi<Dtype>::weight_align(plan_, this->blobs_[0]->gpu_data(), 1, Caffe::stream()));
+      aligned_on_device_ = true;
+    }
+    ESCOIN_CHECK(EscApi<Dtype>::backward(plan_, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, num_,
+                                         Caffe::stream()));
+  }
+  void backward_cpu_sconv(const Dtype *bottom, const Dtype *top, const Dtype *top_diff, Dtype *bottom_diff,
+                          Dtype *weight_diff, Dtype *bias_diff) {
+    ESC_CHECK(aligned_);
+    ESCOIN_CHECK(EscApi<Dtype>::backward_cpu(plan_, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, num_,
+                                             Caffe::cpu_threads()));
+  }
   escoin_plan *plan_;
   escoin_conv_desc desc_;
   bool aligned_ = false, aligned_on_device_ = false;
@@ -463,10 +523,41 @@ class ConvolutionLayer : public BaseConvolutionLayer<Dtype> {   // conv_layer.hp
       this->forward_gpu_sconv_par(bottom_data, weight, top_data);
     }
   }
+  // conv_layer.cu:42-73 / conv_layer.cpp:65-99: per bottom/top pair the bias gradient (bias_term_ &&
+  // param_propagate_down(1)), the weight gradient (param_propagate_down(0)) and the bottom gradient (propagate_down[i]),
+  // each accumulated / written as there -- through the CSR's nonzeros only.  For ConvolutionReLU the forward's top
+  // supplies the ReLU mask.
+  virtual void Backward_gpu(const vector<Blob<Dtype> *> &top, const vector<bool> &propagate_down,
+                            const vector<Blob<Dtype> *> &bottom) {
+    for (size_t i = 0; i < top.size(); ++i) {
+      Dtype *weight_diff = this->param_propagate_down(0) ? this->blobs_[0]->mutable_gpu_diff() : nullptr;
+      Dtype *bias_diff = this->bias_term_ && this->param_propagate_down(1) ? this->blobs_[1]->mutable_gpu_diff() : nullptr;
+      Dtype *bottom_diff = propagate_down.size() > i && propagate_down[i] ? bottom[i]->mutable_gpu_diff() : nullptr;
+      if (!weight_diff && !bias_diff && !bottom_diff) continue;
+      this->backward_gpu_sconv(weight_diff ? bottom[i]->gpu_data() : nullptr,
+                               this->fuse_relu_ ? top[i]->gpu_data() : nullptr, top[i]->gpu_diff(), bottom_diff,
+                               weight_diff, bias_diff);
+    }
+  }
+  virtual void Backward_cpu(const vector<Blob<Dtype> *> &top, const vector<bool> &propagate_down,
+                            const vector<Blob<Dtype> *> &bottom) {
+    for (size_t i = 0; i < top.size(); ++i) {
+      Dtype *weight_diff = this->param_propagate_down(0) ? this->blobs_[0]->mutable_cpu_diff() : nullptr;
+      Dtype *bias_diff = this->bias_term_ && this->param_propagate_down(1) ? this->blobs_[1]->mutable_cpu_diff() : nullptr;
+      Dtype *bottom_diff = propagate_down.size() > i && propagate_down[i] ? bottom[i]->mutable_cpu_diff() : nullptr;
+      if (!weight_diff && !bias_diff && !bottom_diff) continue;
+      this->backward_cpu_sconv(weight_diff ? bottom[i]->cpu_data() : nullptr,
+                               this->fuse_relu_ ? top[i]->cpu_data() : nullptr, top[i]->cpu_diff(), bottom_diff,
+                               weight_diff, bias_diff);
+    }
+  }
 };
 
 template <typename Dtype>
 class ConvolutionReLULayer : public ConvolutionLayer<Dtype> {   // conv_relu_layer.hpp / .cu:8-30
+  // Backward: ConvolutionLayer's, which hands the forward's top to the library for the ReLU mask
+  // (G = top_diff x [top > 0]).  The reference's conv_relu_layer.cu:33-63 is the plain conv body and ignores the
+  // ReLU -- a wrong gradient wherever the ReLU clipped; not copied.
  public:
   explicit ConvolutionReLULayer(const LayerParameter &param) : ConvolutionLayer<Dtype>(param) {
     this->fuse_relu_ = true;

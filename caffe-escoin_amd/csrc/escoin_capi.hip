@@ -68,7 +68,39 @@ static int validate(const escoin_conv_desc *d, Geometry *g) {
   return ESCOIN_OK;
 }
 
+void bwd_release(escoin_plan *p) {
+  BwdState *s = p->bwd;
+  if (!s) return;
+  if (s->tplan) escoin_plan_destroy(s->tplan);
+  if (s->d_trow) (void)hipFree(s->d_trow);
+  if (s->d_ttap) (void)hipFree(s->d_ttap);
+  if (s->d_tval) (void)hipFree(s->d_tval);
+  if (s->d_wpos) (void)hipFree(s->d_wpos);
+  if (s->d_slab) (void)hipFree(s->d_slab);
+  if (s->d_g) (void)hipFree(s->d_g);
+  delete s;
+  p->bwd = nullptr;
+}
+
+long bwd_stat(const escoin_plan *p, const char *key) {
+  const BwdState *s = p->bwd;
+  if (!strcmp(key, "bwd_data_kernel")) {
+    if (!s) return fail(ESCOIN_ESTATE, "bwd_data_kernel: no backward has run on this alignment");
+    return s->data_kernel;
+  }
+  if (!strcmp(key, "bwd_device_bytes")) return s ? (long)(s->device_bytes + (s->tplan ? s->tplan->device_bytes : 0)) : 0;
+  if (!strcmp(key, "bwd_chunks")) return s ? s->last_chunks : 0;
+  if (!strcmp(key, "bwd_align_us")) return s ? (long)(s->align_ms * 1e3) : 0;
+  return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
+}
+
+size_t bwd_device_bytes(const escoin_plan *p) {
+  const BwdState *s = p->bwd;
+  return s ? s->device_bytes + (s->tplan ? s->tplan->device_bytes : 0) : 0;
+}
+
 static void free_device(escoin_plan *p) {
+  bwd_release(p);
   if (p->d_rowptr) (void)hipFree(p->d_rowptr);
   if (p->d_taps) (void)hipFree(p->d_taps);
   if (p->d_vals) (void)hipFree(p->d_vals);
@@ -559,6 +591,11 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->code_loader = value;
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "backward_kernel")) {
+      if (value < ESCOIN_KERNEL_AUTO || value > ESCOIN_KERNEL_JIT) return fail(ESCOIN_EINVAL, "unknown kernel id");
+      p->bwd_kernel = value;
+      return ESCOIN_OK;
+    }
     if (!strcmp(key, "stream_stores")) {
       if (value < -1 || value > 1) return fail(ESCOIN_EINVAL, "stream_stores must be -1, 0 or 1");
       p->stream_stores = value;
@@ -850,6 +887,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
     return (long)v;
   }
   if (!strcmp(key, "streamk")) return p->sk_used ? 1 : 0;
+  if (!strncmp(key, "bwd_", 4)) return bwd_stat(p, key);
   if (!strcmp(key, "is_f64")) return p->is_f64 ? 1 : 0;
   if (!strcmp(key, "host_aligned")) return p->host_aligned ? 1 : 0;
   if (!strcmp(key, "kernel_choice")) {
@@ -879,7 +917,7 @@ int escoin_plan_get_csr_f64(const escoin_plan *p, int *rowptr, int *colidx, doub
   return guarded([&]() -> int { return get_csr_t<double>(p, rowptr, colidx, values, stretched); });
 }
 
-size_t escoin_plan_workspace_bytes(const escoin_plan *p) { return p ? p->device_bytes : 0; }
+size_t escoin_plan_workspace_bytes(const escoin_plan *p) { return p ? p->device_bytes + bwd_device_bytes(p) : 0; }
 
 const char *escoin_plan_kernel_name(const escoin_plan *p) {
   if (p && p->aligned && !p->is_f64 && p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE &&

@@ -88,6 +88,24 @@ struct CpuWorkspace {
   unsigned long call = 0;        // ... as of this escoin_forward_cpu call
 };
 
+// What the first escoin_backward on an alignment builds (sconv_backward.hip); released with the device side.
+struct BwdState {
+  escoin_plan *tplan = nullptr;   // transposed forward plan (path a), or null: the gather kernel (path b)
+  int data_kernel = ESCOIN_KERNEL_GENERIC;
+  int *d_trow = nullptr;          // [C + 1] absolute offsets into d_ttap / d_tval (gather kernel)
+  int *d_ttap = nullptr;          // per transposed entry: ocl << 16 | kr << 8 | kc
+  void *d_tval = nullptr;         // float or double values, in the transposed order
+  int *d_wpos = nullptr;          // per CSR entry: oc * kdim + colidx (its position in weight_diff)
+  void *d_slab = nullptr;         // [chunks_max][nnz] weight partials, then [chunks_max][M] bias partials
+  void *d_g = nullptr;            // fuse_relu + path (a): top_diff * [top > 0], desc.N x M x OH x OW
+  long nnz = 0;
+  int chunks_max = 0, last_chunks = 0;
+  size_t device_bytes = 0;        // the arrays above (the transposed plan's own bytes are added in bwd_device_bytes)
+  double align_ms = 0.0;
+};
+
+constexpr int kBwdChunkPixels = 1024;   // flattened (n, oh, ow) pixels per chunk of the weight-gradient reduction
+
 }  // namespace escoin
 
 struct escoin_plan {
@@ -174,6 +192,11 @@ struct escoin_plan {
 
   size_t device_bytes = 0;
   std::string kernel_name = "(not aligned)";
+
+  // Backward (sconv_backward.hip): option "backward_kernel" and the state the first escoin_backward builds; released
+  // with the device side (free_device), so weight_align / set_csr / import_aligned drop it
+  int bwd_kernel = ESCOIN_KERNEL_AUTO;
+  escoin::BwdState *bwd = nullptr;
 };
 
 namespace escoin {
@@ -190,6 +213,12 @@ int launch_generic_f64(const escoin_plan *p, const double *bottom, const double 
                        int n_images, hipStream_t stream);
 const char *generic_kernel_name(bool relu);
 const char *generic_kernel_name_f64(bool relu);
+
+// escoin_capi.hip: the backward state's release (no-op without one), its "bwd_*" stats and device bytes (the
+// transposed plan's included).  sconv_backward.hip builds the state.
+void bwd_release(escoin_plan *p);
+long bwd_stat(const escoin_plan *p, const char *key);
+size_t bwd_device_bytes(const escoin_plan *p);
 
 // sconv_tiled.hip
 bool tiled_supported(const Geometry &g);

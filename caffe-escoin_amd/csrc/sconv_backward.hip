@@ -1,0 +1,534 @@
+// sconv_backward.hip -- ConvolutionLayer::Backward_gpu (conv_layer.cu:42-73) that keeps the sparsity pattern:
+// gradients flow through the plan's CSR nonzeros only, and the weight gradient is written at the CSR's positions only
+// (the reference's dense im2col + GEMM backward, base_conv_layer.cpp:859-897, revives pruned weights the sparse
+// forward never reads).  Let G = top_diff (x [top > 0] for fuse_relu plans).
+//
+//   data gradient   bottom_diff[n][c][h][w] = sum over the CSR entries (oc, c, kr, kc) and the output pixels that read
+//                   (h, w) of value * G[n][oc][oh][ow]; overwritten.
+//     (a) stride-1 float plans with pad <= dil * (K - 1): a FORWARD sparse convolution of G with the transposed,
+//         flipped weights (colidx' = ocl*KH*KW + (KH-1-kr)*KW + (KW-1-kc), pad' = dil*(K-1) - pad), run by an internal
+//         plan built through set_csr -- so the data gradient gets the generated-code / tiled / MFMA kernels of the
+//         forward with no new device code;
+//     (b) everything else (stride > 1, larger pads, double, option backward_kernel = GENERIC):
+//         escoin_sconv_bwd_data_kernel, one lane per bottom pixel, the wave walking its input channel's transposed-CSR
+//         row in ascending (ocl, kr, kc) order with one fma per contributing entry from 0 -- the order of the CPU mode's
+//         data gradient (sconv_cpu_backward.cpp), so the two are bit-identical.
+//   weight gradient weight_diff[oc][colidx] += sum over (n, oh, ow) of G * bottom[...], at the CSR positions only;
+//   bias gradient   bias_diff[oc] += sum over (n, oh, ow) of G.
+//     Two deterministic stages, no float atomics (the order of every sum is a function of the geometry and n_images):
+//     escoin_sconv_wgrad_partial_kernel  one workgroup per (chunk of kChunkPixels flattened (n, oh, ow) pixels, output
+//                                        channel): every lane holds G for its kPixPerLane pixels in registers, the waves
+//                                        walk the row's CSR entries (tap wave-uniform), reduce each entry's per-lane
+//                                        partial with a fixed butterfly, then over the four waves in wave order, and
+//                                        write one partial per (chunk, entry) -- and per (chunk, oc) for the bias --
+//                                        into a slab with plain stores;
+//     escoin_sconv_wgrad_sum_kernel      one lane per entry (and per bias): its slab column summed in chunk order, the
+//                                        total added into weight_diff / bias_diff.  Every position has one owner.
+//
+// The backward state (transposed CSR or transposed plan, slab, ReLU scratch) is built by the first backward on an
+// aligned plan and dropped with the device side (free_device: weight_align / set_csr / import_aligned / destroy); later
+// calls allocate nothing and synchronise nothing, so they can be captured into a graph.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "escoin_plan.h"
+
+namespace escoin {
+
+constexpr int kBwdWaves = 4;                         // waves per workgroup (both kernels)
+constexpr int kPixPerLane = 4;                       // wgrad: pixels each lane holds
+constexpr int kChunkPixels = kBwdChunkPixels;
+static_assert(kChunkPixels == 64 * kBwdWaves * kPixPerLane, "a chunk is one pixel per lane and step");
+constexpr int kEntryBatch = 64;                      // wgrad: entries reduced per barrier pair
+
+
+template <typename T> const std::vector<std::vector<T>> &plan_values_t(const escoin_plan *p);
+template <> const std::vector<std::vector<float>> &plan_values_t<float>(const escoin_plan *p) { return p->values; }
+template <> const std::vector<std::vector<double>> &plan_values_t<double>(const escoin_plan *p) { return p->values64; }
+
+template <typename T> __device__ inline T bfma(T a, T b, T c);
+template <> __device__ inline float bfma<float>(float a, float b, float c) { return fmaf(a, b, c); }
+template <> __device__ inline double bfma<double>(double a, double b, double c) { return fma(a, b, c); }
+
+// ---- data gradient: gather kernel -------------------------------------------------------------------------------
+template <typename T>
+struct BwdDataArgs {
+  const T *__restrict__ top_diff;
+  const T *__restrict__ top;       // fuse_relu only
+  T *__restrict__ bottom_diff;
+  const int *__restrict__ trow;
+  const int *__restrict__ ttap;
+  const T *__restrict__ tval;
+  int C, H, W, M, OH, OW;
+  int pad_h, pad_w, stride_h, stride_w, dil_h, dil_w;
+  int Cg, Mg;
+};
+
+template <typename T, bool RELU>
+__device__ inline void bwd_data_body(const BwdDataArgs<T> &a) {
+  const int lane = threadIdx.x;
+  const int c = __builtin_amdgcn_readfirstlane(blockIdx.y * kBwdWaves + threadIdx.y);
+  if (c >= a.C) return;
+  const int n = blockIdx.z;
+  const int npix = a.H * a.W;
+  const int p = blockIdx.x * 64 + lane;
+  const bool live = p < npix;
+  const int h = live ? p / a.W : 0;
+  const int w = live ? p - h * a.W : 0;
+  const int grp = c / a.Cg;
+  const size_t opix = (size_t)a.OH * a.OW;
+  const T *__restrict__ gd = a.top_diff + ((size_t)n * a.M + (size_t)grp * a.Mg) * opix;
+  const T *__restrict__ tp = RELU ? a.top + ((size_t)n * a.M + (size_t)grp * a.Mg) * opix : nullptr;
+  const int jb = a.trow[c], je = a.trow[c + 1];
+  T sum = 0;
+  for (int j = jb; j < je; ++j) {
+    const unsigned tap = (unsigned)a.ttap[j];
+    const T v = a.tval[j];
+    const int ocl = (int)(tap >> 16), kr = (tap >> 8) & 0xff, kc = tap & 0xff;
+    const int th = h + a.pad_h - kr * a.dil_h;
+    const int tw = w + a.pad_w - kc * a.dil_w;
+    if (!live || th < 0 || tw < 0) continue;
+    const int oh = th / a.stride_h, ow = tw / a.stride_w;
+    if (oh * a.stride_h != th || ow * a.stride_w != tw || oh >= a.OH || ow >= a.OW) continue;
+    const size_t gi = (size_t)ocl * opix + (size_t)oh * a.OW + ow;
+    T g = gd[gi];
+    if (RELU && !(tp[gi] > T(0))) g = T(0);
+    sum = bfma<T>(v, g, sum);
+  }
+  if (live) a.bottom_diff[((size_t)n * a.C + c) * npix + p] = sum;
+}
+
+template <bool RELU>
+__global__ void __launch_bounds__(64 * kBwdWaves)
+escoin_sconv_bwd_data_kernel(BwdDataArgs<float> a) { bwd_data_body<float, RELU>(a); }
+
+template <bool RELU>
+__global__ void __launch_bounds__(64 * kBwdWaves)
+escoin_sconv_bwd_data_f64_kernel(BwdDataArgs<double> a) { bwd_data_body<double, RELU>(a); }
+
+// fuse_relu + transposed plan: G = top_diff * [top > 0] into scratch, the transposed plan's bottom
+__global__ void __launch_bounds__(256)
+escoin_sconv_bwd_relu_mask_kernel(const float *__restrict__ top_diff, const float *__restrict__ top,
+                                  float *__restrict__ g, size_t count) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (size_t)gridDim.x * 256)
+    g[i] = top[i] > 0.f ? top_diff[i] : 0.f;
+}
+
+// ---- weight / bias gradient -------------------------------------------------------------------------------------
+template <typename T>
+struct WgradArgs {
+  const T *__restrict__ bottom;
+  const T *__restrict__ top_diff;
+  const T *__restrict__ top;       // fuse_relu only
+  const int *__restrict__ rowptr;  // [M + 1] absolute
+  const int *__restrict__ taps;    // packed (ic, kr, kc), ic group-local
+  T *__restrict__ slab_w;          // [chunks][nnz]
+  T *__restrict__ slab_b;          // [chunks][M]
+  long total;                      // n_images * OH * OW
+  int nnz;
+  int C, H, W, M, OH, OW;
+  int pad_h, pad_w, stride_h, stride_w, dil_h, dil_w;
+  int Cg, Mg;
+  int want_w, want_b;
+};
+
+// Sum over the wave's 64 lanes with a fixed butterfly: the same tree on every call.
+template <typename T>
+__device__ inline T wave_sum(T v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
+}
+
+template <typename T, bool RELU>
+__device__ inline void wgrad_partial_body(const WgradArgs<T> &a) {
+  __shared__ T red[kBwdWaves][kEntryBatch];
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int chunk = blockIdx.x;
+  const int oc = blockIdx.y;
+  const int grp = oc / a.Mg;
+  const int opix = a.OH * a.OW;
+  const size_t plane = (size_t)a.H * a.W;
+  T g[kPixPerLane];
+  size_t img[kPixPerLane];
+  int ih0[kPixPerLane], iw0[kPixPerLane];
+#pragma unroll
+  for (int i = 0; i < kPixPerLane; ++i) {
+    const long q = (long)chunk * kChunkPixels + i * 64 * kBwdWaves + tid;
+    const bool live = q < a.total;
+    const long n = live ? q / opix : 0;
+    const int r = live ? (int)(q - n * opix) : 0;
+    const int oh = r / a.OW, ow = r - oh * a.OW;
+    const size_t gi = ((size_t)n * a.M + oc) * opix + r;
+    T gv = live ? a.top_diff[gi] : T(0);
+    if (RELU && live && !(a.top[gi] > T(0))) gv = T(0);
+    g[i] = gv;
+    img[i] = ((size_t)n * a.C + (size_t)grp * a.Cg) * plane;
+    // a dead lane gets an origin no tap can bring inside the image: it reads nothing
+    ih0[i] = live ? oh * a.stride_h - a.pad_h : -(1 << 29);
+    iw0[i] = ow * a.stride_w - a.pad_w;
+  }
+  if (a.want_b) {
+    T s = g[0];
+#pragma unroll
+    for (int i = 1; i < kPixPerLane; ++i) s += g[i];
+    s = wave_sum(s);
+    if (lane == 0) red[wave][0] = s;
+    __syncthreads();
+    if (tid == 0) {
+      T t = red[0][0];
+      for (int k = 1; k < kBwdWaves; ++k) t += red[k][0];
+      a.slab_b[(size_t)chunk * a.M + oc] = t;
+    }
+    __syncthreads();
+  }
+  if (!a.want_w) return;
+  const int jb = a.rowptr[oc], je = a.rowptr[oc + 1];
+  for (int j0 = jb; j0 < je; j0 += kEntryBatch) {
+    const int jn = min(kEntryBatch, je - j0);
+    for (int k = 0; k < jn; ++k) {
+      const int tap = a.taps[j0 + k];
+      const int ic = tap >> 16, kr = (tap >> 8) & 0xff, kc = tap & 0xff;
+      T acc = 0;
+#pragma unroll
+      for (int i = 0; i < kPixPerLane; ++i) {
+        const int ih = ih0[i] + kr * a.dil_h;
+        const int iw = iw0[i] + kc * a.dil_w;
+        T x = 0;
+        if ((unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W)
+          x = a.bottom[img[i] + (size_t)ic * plane + (size_t)ih * a.W + iw];
+        acc = bfma<T>(g[i], x, acc);
+      }
+      acc = wave_sum(acc);
+      if (lane == 0) red[wave][k] = acc;
+    }
+    __syncthreads();
+    if (tid < jn) {
+      T t = red[0][tid];
+      for (int k = 1; k < kBwdWaves; ++k) t += red[k][tid];
+      a.slab_w[(size_t)chunk * a.nnz + j0 + tid] = t;
+    }
+    __syncthreads();
+  }
+}
+
+template <bool RELU>
+__global__ void __launch_bounds__(64 * kBwdWaves)
+escoin_sconv_wgrad_partial_kernel(WgradArgs<float> a) { wgrad_partial_body<float, RELU>(a); }
+
+template <bool RELU>
+__global__ void __launch_bounds__(64 * kBwdWaves)
+escoin_sconv_wgrad_partial_f64_kernel(WgradArgs<double> a) { wgrad_partial_body<double, RELU>(a); }
+
+// One lane per weight entry, then one per bias: the slab column in chunk order, then += into the gradient.
+template <typename T>
+__device__ inline void wgrad_sum_body(const T *__restrict__ slab_w, const T *__restrict__ slab_b,
+                                      const int *__restrict__ wpos, T *__restrict__ weight_diff,
+                                      T *__restrict__ bias_diff, int nnz, int M, int chunks) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (weight_diff && e < nnz) {
+    T s = 0;
+    for (int c = 0; c < chunks; ++c) s += slab_w[(size_t)c * nnz + e];
+    const int pos = wpos[e];
+    weight_diff[pos] = weight_diff[pos] + s;
+    return;
+  }
+  const long b = e - (weight_diff ? nnz : 0);
+  if (bias_diff && b >= 0 && b < M) {
+    T s = 0;
+    for (int c = 0; c < chunks; ++c) s += slab_b[(size_t)c * M + b];
+    bias_diff[b] = bias_diff[b] + s;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+escoin_sconv_wgrad_sum_kernel(const float *slab_w, const float *slab_b, const int *wpos, float *weight_diff,
+                              float *bias_diff, int nnz, int M, int chunks) {
+  wgrad_sum_body<float>(slab_w, slab_b, wpos, weight_diff, bias_diff, nnz, M, chunks);
+}
+
+__global__ void __launch_bounds__(256)
+escoin_sconv_wgrad_sum_f64_kernel(const double *slab_w, const double *slab_b, const int *wpos, double *weight_diff,
+                                  double *bias_diff, int nnz, int M, int chunks) {
+  wgrad_sum_body<double>(slab_w, slab_b, wpos, weight_diff, bias_diff, nnz, M, chunks);
+}
+
+// ---- backward state ---------------------------------------------------------------------------------------------
+bool bwd_transposable(const escoin_plan *p) {
+  const escoin_conv_desc &d = p->g.d;
+  return !p->is_f64 && d.stride_h == 1 && d.stride_w == 1 && d.pad_h <= d.dil_h * (d.KH - 1) &&
+         d.pad_w <= d.dil_w * (d.KW - 1) && p->g.Mg <= 32767;
+}
+
+template <typename T>
+static int dev_upload(T **dst, const std::vector<T> &src, size_t *bytes, hipStream_t stream) {
+  const size_t n = std::max<size_t>(src.size(), 1);
+  ESCOIN_HIP_TRY(hipMalloc(dst, sizeof(T) * n));
+  *bytes += sizeof(T) * n;
+  if (!src.empty())
+    ESCOIN_HIP_TRY(hipMemcpyAsync(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, stream));
+  return ESCOIN_OK;
+}
+
+// The transposed forward plan of path (a): geometry of the data gradient as a stride-1 forward of G.
+static int build_transposed_plan(escoin_plan *p, BwdState *s, hipStream_t stream) {
+  const Geometry &g = p->g;
+  const escoin_conv_desc &d = g.d;
+  escoin_conv_desc t = d;
+  t.C = d.M; t.H = g.OH; t.W = g.OW; t.M = d.C;
+  t.pad_h = d.dil_h * (d.KH - 1) - d.pad_h;
+  t.pad_w = d.dil_w * (d.KW - 1) - d.pad_w;
+  t.stride_h = t.stride_w = 1;
+  t.has_bias = 0;
+  t.fuse_relu = 0;
+  int rc = escoin_plan_create(&t, &s->tplan);
+  if (rc != ESCOIN_OK) return rc;
+  const int kk = d.KH * d.KW;
+  if (p->bwd_kernel != ESCOIN_KERNEL_AUTO && (rc = escoin_plan_set_option(s->tplan, "kernel", p->bwd_kernel)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(s->tplan, "tiling_batch", p->tiling_batch)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(s->tplan, "max_launch_bytes", (int)std::min<long>(p->max_launch_bytes, 0x7fffffff))) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(s->tplan, "dense_threshold_pct", p->dense_threshold_pct)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(s->tplan, "dense_gate", p->dense_gate)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(s->tplan, "code_loader", p->code_loader)) != ESCOIN_OK) return rc;
+  // CSR': row = input channel icl of a group, entry (ocl, icl, kr, kc) -> colidx' = ocl*KH*KW + (KH-1-kr)*KW + (KW-1-kc),
+  // ascending within the row
+  std::vector<int> rowptr((size_t)d.group * (g.Cg + 1)), colidx, nnz_g(d.group);
+  std::vector<float> vals;
+  std::vector<std::vector<std::pair<int, float>>> rows(g.Cg);
+  for (int grp = 0; grp < d.group; ++grp) {
+    for (auto &r : rows) r.clear();
+    const std::vector<int> &rp = p->rowptr[grp], &ci = p->colidx[grp];
+    for (int m = 0; m < g.Mg; ++m)
+      for (int j = rp[m]; j < rp[m + 1]; ++j) {
+        const int col = ci[j], icl = col / kk, kr = (col / d.KW) % d.KH, kc = col % d.KW;
+        rows[icl].emplace_back(m * kk + (d.KH - 1 - kr) * d.KW + (d.KW - 1 - kc), p->values[grp][j]);
+      }
+    int *trp = rowptr.data() + (size_t)grp * (g.Cg + 1);
+    trp[0] = 0;
+    for (int c = 0; c < g.Cg; ++c) {
+      std::sort(rows[c].begin(), rows[c].end(),
+                [](const std::pair<int, float> &x, const std::pair<int, float> &y) { return x.first < y.first; });
+      for (const auto &e : rows[c]) { colidx.push_back(e.first); vals.push_back(e.second); }
+      trp[c + 1] = trp[c] + (int)rows[c].size();
+    }
+    nnz_g[grp] = trp[g.Cg];
+  }
+  rc = escoin_plan_set_csr(s->tplan, rowptr.data(), colidx.data(), vals.data(), nnz_g.data(), stream);
+  if (rc != ESCOIN_OK) return rc;
+  s->data_kernel = (int)escoin_plan_stat(s->tplan, "kernel_choice");
+  return ESCOIN_OK;
+}
+
+// The gather kernel's transposed CSR: per input channel c, its entries in ascending (ocl, kr, kc) -- the order the
+// original rows visit them in when they are walked oc by oc.
+template <typename T>
+static int build_gather(escoin_plan *p, BwdState *s, const std::vector<std::vector<T>> &values, hipStream_t stream) {
+  const Geometry &g = p->g;
+  const escoin_conv_desc &d = g.d;
+  const int kk = d.KH * d.KW;
+  std::vector<int> cnt(d.C + 1, 0);
+  for (int grp = 0; grp < d.group; ++grp)
+    for (int col : p->colidx[grp]) ++cnt[grp * g.Cg + col / kk + 1];
+  for (int c = 0; c < d.C; ++c) cnt[c + 1] += cnt[c];
+  std::vector<int> trow(cnt), fill(cnt.begin(), cnt.end() - 1), ttap((size_t)s->nnz);
+  std::vector<T> tval((size_t)s->nnz);
+  for (int grp = 0; grp < d.group; ++grp) {
+    const std::vector<int> &rp = p->rowptr[grp], &ci = p->colidx[grp];
+    for (int m = 0; m < g.Mg; ++m)
+      for (int j = rp[m]; j < rp[m + 1]; ++j) {
+        const int col = ci[j], c = grp * g.Cg + col / kk;
+        const int at = fill[c]++;
+        ttap[at] = (m << 16) | (((col / d.KW) % d.KH) << 8) | (col % d.KW);
+        tval[at] = values[grp][j];
+      }
+  }
+  int rc = dev_upload(&s->d_trow, trow, &s->device_bytes, stream);
+  if (rc == ESCOIN_OK) rc = dev_upload(&s->d_ttap, ttap, &s->device_bytes, stream);
+  T *tv = nullptr;
+  if (rc == ESCOIN_OK) rc = dev_upload(&tv, tval, &s->device_bytes, stream);
+  s->d_tval = tv;
+  if (rc != ESCOIN_OK) return rc;
+  ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
+  return ESCOIN_OK;
+}
+
+template <typename T>
+static int bwd_build(escoin_plan *p, hipStream_t stream) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const Geometry &g = p->g;
+  const escoin_conv_desc &d = g.d;
+  if (g.Mg > 65535) return fail(ESCOIN_EINVAL, "backward: more than 65535 output channels per group");
+  if (d.C > 4 * 65535 || d.N > 65535) return fail(ESCOIN_EINVAL, "backward: grid dimension exceeds 65535");
+  const bool transposable = bwd_transposable(p);
+  const bool forced = p->bwd_kernel == ESCOIN_KERNEL_TILED || p->bwd_kernel == ESCOIN_KERNEL_JIT ||
+                      p->bwd_kernel == ESCOIN_KERNEL_DENSE;
+  if (forced && !transposable)
+    return fail(ESCOIN_EINVAL, "backward_kernel: this plan has no transposed forward plan (needs a float plan, stride 1, "
+                               "pad <= dilation * (kernel - 1)); only the gather kernel serves it");
+  BwdState *s = new BwdState();
+  p->bwd = s;
+  for (const auto &c : p->colidx) s->nnz += (long)c.size();
+  if (s->nnz > 0x7fffffffL) return fail(ESCOIN_EINVAL, "backward: more than 2^31 nonzeros");
+  int rc = ESCOIN_OK;
+  if (transposable && p->bwd_kernel != ESCOIN_KERNEL_GENERIC) {
+    rc = build_transposed_plan(p, s, stream);
+    if (rc == ESCOIN_OK && d.fuse_relu) {
+      const size_t bytes = sizeof(float) * (size_t)d.N * d.M * g.OH * g.OW;
+      ESCOIN_HIP_TRY(hipMalloc(&s->d_g, bytes));
+      s->device_bytes += bytes;
+    }
+  } else {
+    s->data_kernel = ESCOIN_KERNEL_GENERIC;
+    rc = build_gather<T>(p, s, plan_values_t<T>(p), stream);
+  }
+  if (rc != ESCOIN_OK) return rc;
+  std::vector<int> wpos((size_t)s->nnz);
+  long e = 0;
+  for (int grp = 0; grp < d.group; ++grp)
+    for (int m = 0; m < g.Mg; ++m)
+      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j)
+        wpos[e++] = (grp * g.Mg + m) * g.kdim + p->colidx[grp][j];
+  rc = dev_upload(&s->d_wpos, wpos, &s->device_bytes, stream);
+  if (rc != ESCOIN_OK) return rc;
+  s->chunks_max = (int)(((long)d.N * g.OH * g.OW + kChunkPixels - 1) / kChunkPixels);
+  const size_t slab = sizeof(T) * (size_t)s->chunks_max * (size_t)(s->nnz + d.M);
+  ESCOIN_HIP_TRY(hipMalloc(&s->d_slab, slab));
+  s->device_bytes += slab;
+  ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
+  s->align_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return ESCOIN_OK;
+}
+
+template <typename T>
+static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *top_diff, T *bottom_diff,
+                        T *weight_diff, T *bias_diff, int n_images, void *stream_v) {
+  if (!p) return fail(ESCOIN_EINVAL, "null plan");
+  if (!p->aligned) return fail(ESCOIN_ESTATE, "backward called before weight_align / set_csr");
+  if (p->is_f64 != (sizeof(T) == 8))
+    return fail(ESCOIN_ESTATE, p->is_f64 ? "backward: the plan holds double weights (use the _f64 entry point)"
+                                         : "backward_f64: the plan holds float weights");
+  {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
+      return fail(ESCOIN_ESTATE, "backward: the current device is not the device the plan was aligned on");
+  }
+  const Geometry &g = p->g;
+  const escoin_conv_desc &d = g.d;
+  if (!top_diff) return fail(ESCOIN_EINVAL, "backward: top_diff is required");
+  if (d.fuse_relu && !top) return fail(ESCOIN_EINVAL, "backward: a fuse_relu plan needs the forward's top");
+  if (weight_diff && !bottom) return fail(ESCOIN_EINVAL, "backward: the weight gradient needs bottom");
+  if (n_images < 0 || n_images > d.N) return fail(ESCOIN_EINVAL, "n_images outside [0, desc.N]");
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (!p->bwd) {
+    const int rc = bwd_build<T>(p, stream);
+    if (rc != ESCOIN_OK) {
+      bwd_release(p);
+      return rc;
+    }
+  }
+  BwdState *s = p->bwd;
+  if (n_images == 0) return ESCOIN_OK;
+  const bool relu = d.fuse_relu != 0;
+  if (bottom_diff) {
+    if (s->tplan) {
+      const float *src = reinterpret_cast<const float *>(top_diff);
+      if (relu) {
+        const size_t count = (size_t)n_images * d.M * g.OH * g.OW;
+        const unsigned blocks = (unsigned)std::min<size_t>((count + 255) / 256, 8192);
+        hipLaunchKernelGGL(escoin_sconv_bwd_relu_mask_kernel, dim3(blocks), dim3(256), 0, stream,
+                           reinterpret_cast<const float *>(top_diff), reinterpret_cast<const float *>(top),
+                           static_cast<float *>(s->d_g), count);
+        ESCOIN_HIP_TRY(hipGetLastError());
+        src = static_cast<const float *>(s->d_g);
+      }
+      const int rc = escoin_forward(s->tplan, src, nullptr, reinterpret_cast<float *>(bottom_diff), n_images, stream);
+      if (rc != ESCOIN_OK) return rc;
+    } else {
+      BwdDataArgs<T> a;
+      a.top_diff = top_diff; a.top = top; a.bottom_diff = bottom_diff;
+      a.trow = s->d_trow; a.ttap = s->d_ttap; a.tval = static_cast<const T *>(s->d_tval);
+      a.C = d.C; a.H = d.H; a.W = d.W; a.M = d.M; a.OH = g.OH; a.OW = g.OW;
+      a.pad_h = d.pad_h; a.pad_w = d.pad_w; a.stride_h = d.stride_h; a.stride_w = d.stride_w;
+      a.dil_h = d.dil_h; a.dil_w = d.dil_w; a.Cg = g.Cg; a.Mg = g.Mg;
+      const dim3 grid((d.H * d.W + 63) / 64, (d.C + kBwdWaves - 1) / kBwdWaves, n_images), block(64, kBwdWaves);
+      if constexpr (sizeof(T) == 8) {
+        if (relu) hipLaunchKernelGGL(escoin_sconv_bwd_data_f64_kernel<true>, grid, block, 0, stream, a);
+        else hipLaunchKernelGGL(escoin_sconv_bwd_data_f64_kernel<false>, grid, block, 0, stream, a);
+      } else {
+        if (relu) hipLaunchKernelGGL(escoin_sconv_bwd_data_kernel<true>, grid, block, 0, stream, a);
+        else hipLaunchKernelGGL(escoin_sconv_bwd_data_kernel<false>, grid, block, 0, stream, a);
+      }
+      ESCOIN_HIP_TRY(hipGetLastError());
+    }
+  }
+  if (weight_diff || bias_diff) {
+    const long total = (long)n_images * g.OH * g.OW;
+    const int chunks = (int)((total + kChunkPixels - 1) / kChunkPixels);
+    s->last_chunks = chunks;
+    T *slab_w = static_cast<T *>(s->d_slab);
+    T *slab_b = slab_w + (size_t)s->chunks_max * (size_t)s->nnz;
+    WgradArgs<T> a;
+    a.bottom = bottom; a.top_diff = top_diff; a.top = top;
+    a.rowptr = p->d_rowptr; a.taps = p->d_taps;
+    a.slab_w = slab_w; a.slab_b = slab_b;
+    a.total = total; a.nnz = (int)s->nnz;
+    a.C = d.C; a.H = d.H; a.W = d.W; a.M = d.M; a.OH = g.OH; a.OW = g.OW;
+    a.pad_h = d.pad_h; a.pad_w = d.pad_w; a.stride_h = d.stride_h; a.stride_w = d.stride_w;
+    a.dil_h = d.dil_h; a.dil_w = d.dil_w; a.Cg = g.Cg; a.Mg = g.Mg;
+    a.want_w = weight_diff != nullptr;
+    a.want_b = bias_diff != nullptr;
+    const dim3 grid(chunks, d.M), block(64 * kBwdWaves);
+    if (d.M > 65535) return fail(ESCOIN_EINVAL, "backward: more than 65535 output channels");
+    if constexpr (sizeof(T) == 8) {
+      if (relu) hipLaunchKernelGGL(escoin_sconv_wgrad_partial_f64_kernel<true>, grid, block, 0, stream, a);
+      else hipLaunchKernelGGL(escoin_sconv_wgrad_partial_f64_kernel<false>, grid, block, 0, stream, a);
+    } else {
+      if (relu) hipLaunchKernelGGL(escoin_sconv_wgrad_partial_kernel<true>, grid, block, 0, stream, a);
+      else hipLaunchKernelGGL(escoin_sconv_wgrad_partial_kernel<false>, grid, block, 0, stream, a);
+    }
+    ESCOIN_HIP_TRY(hipGetLastError());
+    const long lanes = (weight_diff ? s->nnz : 0) + (bias_diff ? d.M : 0);
+    if (lanes > 0) {
+      const dim3 sgrid((unsigned)((lanes + 255) / 256));
+      if constexpr (sizeof(T) == 8)
+        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_f64_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, s->d_wpos,
+                           weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
+      else
+        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, s->d_wpos,
+                           weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
+      ESCOIN_HIP_TRY(hipGetLastError());
+    }
+  }
+  return ESCOIN_OK;
+}
+
+}  // namespace escoin
+
+using namespace escoin;
+
+extern "C" {
+
+int escoin_backward(escoin_plan *plan, const float *bottom_dev, const float *top_dev, const float *top_diff_dev,
+                    float *bottom_diff_dev, float *weight_diff_dev, float *bias_diff_dev, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    return backward_gpu<float>(plan, bottom_dev, top_dev, top_diff_dev, bottom_diff_dev, weight_diff_dev, bias_diff_dev,
+                               n_images, stream);
+  });
+}
+
+int escoin_backward_f64(escoin_plan *plan, const double *bottom_dev, const double *top_dev, const double *top_diff_dev,
+                        double *bottom_diff_dev, double *weight_diff_dev, double *bias_diff_dev, int n_images,
+                        void *stream) {
+  return guarded([&]() -> int {
+    return backward_gpu<double>(plan, bottom_dev, top_dev, top_diff_dev, bottom_diff_dev, weight_diff_dev,
+                                bias_diff_dev, n_images, stream);
+  });
+}
+
+}  // extern "C"

@@ -372,6 +372,58 @@ ESCOIN_API int escoin_cpu_sparse_dense2csr(int M, int N, const float *A, float *
 ESCOIN_API int escoin_cpu_sparse_dense2csr_f64(int M, int N, const double *A, double *A_nonzero_buf,
                                     int *A_nonzero_idx_buf, int *A_idx_pointer_buf);
 
+/* ---- Backward: ConvolutionLayer::Backward_gpu / Backward_cpu that keeps the sparsity pattern ------------------------
+ *   ConvolutionLayer<Dtype>::Backward_gpu            conv_layer.cu:42-73
+ *     -> backward_gpu_gemm / weight_gpu_gemm / backward_gpu_bias   base_conv_layer.cpp:859-897
+ * The reference's backward is dense (im2col + GEMM): in SCONV mode it writes a dense weight gradient, so a solver step
+ * brings pruned weights back while the sparse forward -- which reads the CSR WeightAlign built -- never sees them.  This
+ * backward propagates through the plan's CSR nonzeros only and gives a gradient only to the weights the CSR holds: it
+ * is consistent with the forward, costs about density x the dense FLOPs, and equals the reference's gradient on
+ * unpruned weights.  With the masked gradient plain SGD (momentum, weight decay) and Adam keep a pruned weight at exactly
+ * 0, so re-aligning after the update reproduces the pattern.
+ *
+ * Let G = top_diff, or top_diff x [top > 0] for fuse_relu plans.  For one bottom/top pair, whole batch:
+ *   bottom_diff[n][c][h][w]  = sum of value x G[n][oc][oh][ow] over the CSR entries (oc, c, kr, kc) and the output
+ *                              pixels with oh*stride_h - pad_h + kr*dil_h = h, ow*stride_w - pad_w + kc*dil_w = w;
+ *                              OVERWRITTEN (backward_gpu_gemm: beta 0, then col2im);
+ *   weight_diff[oc*Cg*KH*KW + colidx] += sum over (n, oh, ow) of G x bottom[...] (0 outside the image), at the plan's CSR
+ *                              positions ONLY -- explicit zeros handed to set_csr included; no other element is read or
+ *                              written (a NaN there stays NaN);
+ *   bias_diff[oc]            += sum over (n, oh, ow) of G.
+ * A NULL output is not computed (propagate_down / param_propagate_down).  bottom is required iff weight_diff != NULL,
+ * top iff desc.fuse_relu, top_diff always.  The plan's conv_mode is ignored: all four modes compute the same function.
+ * Errors: ESCOIN_ESTATE before an align, on the other Dtype's entry point or (GPU) on another device; ESCOIN_EINVAL for a
+ * NULL top_diff, fuse_relu without top, weight_diff without bottom, n_images outside [0, desc.N] (GPU) / < 0 (CPU).
+ * Deterministic: for a fixed plan, inputs and n_images the output bits are the same on every call, on any stream and
+ * for any n_threads (no float atomics; every sum's order is a function of the geometry and n_images only).
+ * The first GPU backward on an aligned plan builds the backward state: the data-gradient path, the weight-gradient
+ * reduction slab (chunks of 1024 (n, oh, ow) pixels x nonzeros) and, for fuse_relu plans on the transposed path, a
+ * G buffer of desc.N x M x OH x OW.  Later calls allocate and synchronise nothing (they can be captured into a graph);
+ * weight_align / set_csr / import_aligned drop the state, escoin_plan_workspace_bytes counts it.
+ * Data gradient: on a float plan with stride 1 and pad <= dil x (K - 1) a forward sparse convolution of G with the
+ * transposed, flipped weights, run by an internal plan (C' = M, H' x W' = OH x OW, M' = C, pad' = dil x (K - 1) - pad,
+ * no bias, no ReLU; it inherits tiling_batch, max_launch_bytes, dense_threshold_pct, dense_gate, code_loader) -- the
+ * forward's kernel families; otherwise the order-preserving gather kernel escoin_sconv_bwd_data_kernel, bit-identical
+ * to escoin_backward_cpu.  Weight / bias gradient: escoin_sconv_wgrad_partial_kernel (one partial per (chunk, entry))
+ * then escoin_sconv_wgrad_sum_kernel (each entry's partials in chunk order, then +=).
+ * Option "backward_kernel" (before the align, like the others): AUTO (default) = the transposed plan picks its kernel
+ * where it exists; GENERIC = the gather kernel; TILED / JIT / DENSE = that kernel on the transposed plan (the first
+ * backward fails with ESCOIN_EINVAL where there is none).
+ * Stats: "bwd_data_kernel" (ESCOIN_KERNEL_GENERIC = the gather kernel, otherwise the transposed plan's resolved kernel;
+ * ESCOIN_ESTATE before the first backward), "bwd_device_bytes", "bwd_chunks" (chunks the last weight / bias gradient
+ * reduced over), "bwd_align_us" (build time of the backward state). */
+ESCOIN_API int escoin_backward(escoin_plan *plan, const float *bottom_dev, const float *top_dev, const float *top_diff_dev,
+                    float *bottom_diff_dev, float *weight_diff_dev, float *bias_diff_dev, int n_images, void *stream);
+ESCOIN_API int escoin_backward_f64(escoin_plan *plan, const double *bottom_dev, const double *top_dev,
+                        const double *top_diff_dev, double *bottom_diff_dev, double *weight_diff_dev,
+                        double *bias_diff_dev, int n_images, void *stream);
+/* Backward_cpu (conv_layer.cpp:65-99): the same function on host pointers, on a plan with a host CSR (any align);
+ * n_threads as in escoin_forward_cpu.  Plain loops; the data gradient is bit-identical to the device gather kernel's. */
+ESCOIN_API int escoin_backward_cpu(escoin_plan *plan, const float *bottom, const float *top, const float *top_diff,
+                        float *bottom_diff, float *weight_diff, float *bias_diff, int n_images, int n_threads);
+ESCOIN_API int escoin_backward_cpu_f64(escoin_plan *plan, const double *bottom, const double *top, const double *top_diff,
+                            double *bottom_diff, double *weight_diff, double *bias_diff, int n_images, int n_threads);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,331 @@
+"""Pattern-preserving Backward on the MI355X (escoin_backward[_f64]): goldens and odd geometries through every
+backward_kernel against torch float64 autograd, the gather kernel bit for bit against the CPU mode, the BASELINE shapes,
+one full-size res2 layer on sampled entries, determinism, memory, re-align and graph capture."""
+import numpy as np
+import pytest
+
+from conftest import Golden, golden_params, rel_err
+
+torch = pytest.importorskip("torch")
+F = torch.nn.functional
+
+pytestmark = pytest.mark.gpu
+TOL = 1e-4
+
+
+@pytest.fixture(scope="module")
+def dev(pkg):
+    if not torch.cuda.is_available() or pkg.device_count() < 1:
+        pytest.fail("no HIP device visible (these tests run on the MI355X)")
+    return torch.device("cuda:0")
+
+
+def torch_backward(x, w, bias, s, top_diff, top=None):
+    X = torch.tensor(np.asarray(x, np.float64), requires_grad=True)
+    Wt = torch.tensor(np.asarray(w, np.float64), requires_grad=True)
+    B = torch.tensor(np.asarray(bias, np.float64), requires_grad=True) if bias is not None else None
+    y = F.conv2d(X, Wt, B, stride=(s.stride_h, s.stride_w), padding=(s.pad_h, s.pad_w),
+                 dilation=(s.dil_h, s.dil_w), groups=s.group)
+    g = torch.tensor(np.asarray(top_diff, np.float64))
+    if top is not None:
+        g = g * torch.tensor((np.asarray(top) > 0).astype(np.float64))
+    y.backward(g)
+    return X.grad.numpy(), Wt.grad.numpy() * (np.asarray(w) != 0), B.grad.numpy() if B is not None else None
+
+
+def _seeded(shape, seed, dt=np.float32):
+    return np.random.RandomState(seed).uniform(-1, 1, shape).astype(dt)
+
+
+def _transposable(s):
+    return (s.stride_h == 1 and s.stride_w == 1 and s.pad_h <= s.dil_h * (s.KH - 1) and
+            s.pad_w <= s.dil_w * (s.KW - 1))
+
+
+def _run(pkg, dev, s, desc, w, x, b, kernel=None, dt=np.float32, relu=False, **opts):
+    """One GPU backward (all three gradients) + the forward top it needs; returns numpy results and the plan."""
+    if kernel is not None:
+        opts["backward_kernel"] = kernel
+    plan = pkg.Plan(desc, **opts)
+    plan.weight_align(w.astype(dt))
+    xt = torch.from_numpy(x.astype(dt)).to(dev)
+    bt = torch.from_numpy(b.astype(dt)).to(dev) if b is not None else None
+    top = plan.forward(xt, bt) if relu else None
+    td = _seeded((x.shape[0], desc.M) + tuple(plan.out_hw), 21, dt)
+    bd, wd, bsd = plan.backward(torch.from_numpy(td).to(dev), bottom=xt, top=top, weight_diff=True,
+                                bias_diff=True if b is not None else None)
+    torch.cuda.synchronize()
+    return (plan, td, None if top is None else top.cpu().numpy(), bd.cpu().numpy(), wd.cpu().numpy(),
+            None if bsd is None else bsd.cpu().numpy())
+
+
+def _check_against_torch(s, w, x, b, td, top, bd, wd, bsd, tol=TOL, what=""):
+    want_bd, want_wd, want_bsd = torch_backward(x, w, b, s, td, top)
+    assert rel_err(bd, want_bd) <= tol, (what, "bottom_diff", rel_err(bd, want_bd))
+    assert rel_err(wd, want_wd) <= tol, (what, "weight_diff", rel_err(wd, want_wd))
+    assert np.all(wd[np.asarray(w) == 0] == 0), what
+    if b is not None:
+        assert rel_err(bsd, want_bsd) <= tol, (what, "bias_diff")
+
+
+ODD = [
+    # N, C, H, W, M, KH, KW, pad_h, pad_w, stride_h, stride_w, dil_h, dil_w, group
+    (2, 6, 11, 9, 8, 3, 3, 2, 2, 1, 1, 2, 2, 2),      # dilation 2, groups (transposed plan: generic kernel)
+    (2, 8, 10, 12, 6, 3, 5, 0, 1, 1, 1, 1, 1, 1),     # KH != KW, asymmetric pads
+    (3, 16, 14, 14, 24, 1, 1, 0, 0, 2, 2, 1, 1, 1),   # 1x1 stride 2: gather kernel
+    (2, 8, 9, 9, 8, 3, 3, 3, 3, 1, 1, 1, 1, 1),       # pad > dil * (K - 1): gather kernel
+    (1, 12, 17, 13, 12, 5, 5, 2, 2, 2, 1, 1, 1, 3),   # stride 2 x 1, groups 3
+]
+
+
+def _odd_shape(synth, t, i):
+    N, C, H, W, M, KH, KW, ph, pw, sh, sw, dh, dw, g = t
+    return synth.shape("odd%d" % i, N, C, H, W, M, KH, pad=ph, stride=sh, dil=dh, group=g, KW=KW, pad_w=pw,
+                       stride_w=sw, dil_w=dw, sparsity=0.6)
+
+
+@pytest.mark.parametrize("path", golden_params())
+def test_goldens_match_torch_for_every_backward_kernel(pkg, dev, path):
+    gd = Golden(path)
+    kernels = [pkg.KERNEL_AUTO, pkg.KERNEL_GENERIC]
+    if _transposable(gd):
+        kernels += [pkg.KERNEL_TILED, pkg.KERNEL_JIT, pkg.KERNEL_DENSE]
+    for relu in (False, True):
+        for k in kernels:
+            try:
+                plan, td, top, bd, wd, bsd = _run(pkg, dev, gd, gd.desc(pkg, fuse_relu=relu), gd.w, gd.x, gd.bias,
+                                                  kernel=k, relu=relu)
+            except pkg.EscoinError:
+                # a forced kernel the transposed geometry does not fit: the forward refuses it the same way
+                assert k in (pkg.KERNEL_TILED, pkg.KERNEL_JIT)
+                continue
+            got_k = plan.stat("bwd_data_kernel")
+            if k == pkg.KERNEL_GENERIC or not _transposable(gd):
+                assert got_k == pkg.KERNEL_GENERIC
+            elif k != pkg.KERNEL_AUTO:
+                assert got_k == k, (k, got_k)
+            _check_against_torch(gd, gd.w, gd.x, gd.bias, td, top, bd, wd, bsd, what=(gd.name, k, relu))
+            plan.close()
+
+
+@pytest.mark.parametrize("i", range(len(ODD)))
+def test_odd_geometries_match_torch(pkg, dev, synth, i):
+    s = _odd_shape(synth, ODD[i], i)
+    w = synth.pruned_weights(s, 100 + i)
+    x = synth.activations(s, 200 + i)
+    b = synth.bias_vector(s, 300 + i)
+    for k in (pkg.KERNEL_AUTO, pkg.KERNEL_GENERIC):
+        for relu in (False, True):
+            plan, td, top, bd, wd, bsd = _run(pkg, dev, s, pkg.ConvDesc.from_shape(s, fuse_relu=relu), w, x, b,
+                                              kernel=k, relu=relu)
+            _check_against_torch(s, w, x, b, td, top, bd, wd, bsd, what=(s.name, k, relu))
+            plan.close()
+
+
+@pytest.mark.parametrize("dt", [np.float32, np.float64], ids=["float", "double"])
+@pytest.mark.parametrize("path", golden_params())
+def test_gather_kernel_is_bit_equal_to_the_cpu_mode(pkg, dev, path, dt):
+    gd = Golden(path)
+    for relu in (False, True):
+        desc = gd.desc(pkg, fuse_relu=relu)
+        plan, td, top, bd, wd, bsd = _run(pkg, dev, gd, desc, gd.w, gd.x, gd.bias, kernel=pkg.KERNEL_GENERIC, dt=dt,
+                                          relu=relu)
+        assert plan.stat("bwd_data_kernel") == pkg.KERNEL_GENERIC
+        cbd, cwd, cbsd = plan.backward_cpu(td, bottom=gd.x.astype(dt), top=top, weight_diff=True)
+        assert bd.tobytes() == cbd.tobytes(), (gd.name, relu)
+        tol = 1e-12 if dt == np.float64 else TOL
+        assert rel_err(wd, cwd) <= tol
+        if dt == np.float64:
+            _check_against_torch(gd, gd.w, gd.x, gd.bias, td, top, bd, wd, bsd, tol=1e-12, what=gd.name)
+        plan.close()
+
+
+def _baseline_shapes(synth):
+    out = [s for s in synth.resnet50_3x3(N=2)] + synth.alexnet(N=2) + synth.lenet_conv2(N=2)
+    g = synth.googlenet_1x1(N=2)
+    out += [g[1], g[8], g[-1]]
+    return out
+
+
+_CONFIG_BATCH = {"res": 256, "alex": 128, "lenet": 64}
+
+
+def test_baseline_shapes_match_torch(pkg, dev, synth):
+    for s in _baseline_shapes(synth):
+        tb = next((v for k, v in _CONFIG_BATCH.items() if s.name.startswith(k)), 256)
+        w = synth.pruned_weights(s, 41)
+        x = synth.activations(s, 42)
+        b = synth.bias_vector(s, 43)
+        plan, td, top, bd, wd, bsd = _run(pkg, dev, s, pkg.ConvDesc.from_shape(s), w, x, b, tiling_batch=tb)
+        _check_against_torch(s, w, x, b, td, top, bd, wd, bsd, what=(s.name, plan.stat("bwd_data_kernel")))
+        plan.close()
+
+
+def test_full_size_res2_on_sampled_entries_and_pixels(pkg, dev, synth):
+    s = synth.resnet50_3x3(N=256)[0]
+    w = synth.pruned_weights(s, 51)
+    x = synth.activations(s, 52)
+    plan = pkg.Plan(pkg.ConvDesc.from_shape(s))
+    plan.weight_align(w)
+    xt = torch.from_numpy(x).to(dev)
+    td = torch.empty((s.N, s.M, 56, 56), device=dev).uniform_(-1, 1, generator=torch.Generator(dev).manual_seed(5))
+    bd, wd, _ = plan.backward(td, bottom=xt, weight_diff=True)
+    torch.cuda.synchronize()
+    g = td.cpu().numpy().astype(np.float64)
+    xd = np.pad(x.astype(np.float64), ((0, 0), (0, 0), (1, 1), (1, 1)))
+    wd = wd.cpu().numpy()
+    nz = np.argwhere(w != 0)
+    rs = np.random.RandomState(3)
+    for oc, ic, kr, kc in nz[rs.choice(len(nz), 32, replace=False)]:
+        want = float(np.sum(g[:, oc] * xd[:, ic, kr:kr + 56, kc:kc + 56]))
+        assert abs(wd[oc, ic, kr, kc] - want) <= 1e-4 * max(1.0, abs(want)) + 1e-5 * np.sqrt(s.N * 56 * 56), (oc, ic, kr, kc)
+    gp = np.pad(g, ((0, 0), (0, 0), (1, 1), (1, 1)))
+    bdn = bd.cpu().numpy()
+    for _ in range(32):
+        n, c, h, ww = rs.randint(s.N), rs.randint(s.C), rs.randint(56), rs.randint(56)
+        # bottom_diff[n, c, h, w] = sum_oc,kr,kc w[oc, c, kr, kc] * G[n, oc, h + 1 - kr, w + 1 - kc]
+        win = gp[n, :, h:h + 3, ww:ww + 3][:, ::-1, ::-1]
+        want = float(np.sum(w[:, c].astype(np.float64) * win))
+        assert abs(bdn[n, c, h, ww] - want) <= 1e-4 * max(1.0, abs(want)), (n, c, h, ww)
+    assert plan.stat("bwd_chunks") == (s.N * 56 * 56 + 1023) // 1024
+    plan.close()
+
+
+def test_determinism_memory_and_realign(pkg, dev, synth):
+    for s in (synth.resnet50_3x3(N=4)[2], _odd_shape(synth, ODD[2], 2)):
+        w = synth.pruned_weights(s, 61)
+        x = synth.activations(s, 62)
+        b = synth.bias_vector(s, 63)
+        plan = pkg.Plan(pkg.ConvDesc.from_shape(s))
+        plan.weight_align(w)
+        ws0 = plan.workspace_bytes
+        xt = torch.from_numpy(x).to(dev)
+        td = torch.from_numpy(_seeded((s.N, s.M) + tuple(plan.out_hw), 64)).to(dev)
+        r1 = plan.backward(td, bottom=xt, weight_diff=True, bias_diff=True if b is not None else None)
+        ws1 = plan.workspace_bytes
+        assert ws1 > ws0 and plan.stat("bwd_device_bytes") == ws1 - ws0
+        r2 = plan.backward(td, bottom=xt, weight_diff=True, bias_diff=True if b is not None else None)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            r3 = plan.backward(td, bottom=xt, weight_diff=True, bias_diff=True if b is not None else None)
+        torch.cuda.synchronize()
+        assert plan.workspace_bytes == ws1
+        for a, c, e in zip(r1, r2, r3):
+            if a is not None:
+                assert a.cpu().numpy().tobytes() == c.cpu().numpy().tobytes() == e.cpu().numpy().tobytes()
+        # re-align with new weights: the state is rebuilt and the gradients are the new weights'
+        w2 = synth.pruned_weights(s, 65)
+        plan.weight_align(w2)
+        assert plan.stat("bwd_device_bytes") == 0
+        bd, wd, _ = plan.backward(td, bottom=xt, weight_diff=True)
+        torch.cuda.synchronize()
+        want_bd, want_wd, _ = torch_backward(x, w2, None, s, td.cpu().numpy())
+        assert rel_err(bd.cpu().numpy(), want_bd) <= TOL and rel_err(wd.cpu().numpy(), want_wd) <= TOL
+        plan.close()
+
+
+def test_argument_and_state_errors_on_the_device(pkg, dev, synth):
+    import ctypes as C
+    L = pkg.lib()
+    s = synth.shape("e", 2, 4, 7, 7, 6, 3, pad=1, sparsity=0.5)
+    plan = pkg.Plan(pkg.ConvDesc.from_shape(s, fuse_relu=True))
+    buf = torch.zeros(4096, device=dev)
+    p = C.c_void_p(buf.data_ptr())
+    assert L.escoin_backward(plan._h, p, p, p, p, None, None, 1, None) == -4          # before align
+    plan.weight_align(synth.pruned_weights(s, 1))
+    assert L.escoin_backward_f64(plan._h, p, p, p, p, None, None, 1, None) == -4      # wrong dtype
+    assert L.escoin_backward(plan._h, p, p, None, p, None, None, 1, None) == -1       # no top_diff
+    assert L.escoin_backward(plan._h, p, None, p, p, None, None, 1, None) == -1       # fuse_relu without top
+    assert L.escoin_backward(plan._h, None, p, p, None, p, None, 1, None) == -1       # weight_diff without bottom
+    assert L.escoin_backward(plan._h, p, p, p, p, None, None, 3, None) == -1          # n_images > desc.N
+    assert L.escoin_backward(plan._h, p, p, p, p, None, None, -1, None) == -1
+    plan.close()
+    # a forced transposed-plan kernel on a geometry without a transposed plan
+    s2 = synth.shape("e2", 2, 4, 8, 8, 6, 3, pad=1, stride=2, sparsity=0.5)
+    plan = pkg.Plan(pkg.ConvDesc.from_shape(s2), backward_kernel=pkg.KERNEL_JIT)
+    plan.weight_align(synth.pruned_weights(s2, 1))
+    with pytest.raises(pkg.EscoinError):
+        plan.backward(torch.zeros((2, 6, 4, 4), device=dev))
+    plan.close()
+
+
+def test_explicit_zeros_handed_to_set_csr_receive_a_gradient_on_the_device(pkg, dev):
+    d = pkg.ConvDesc(1, 2, 5, 5, 2, 3, 3, 1, 1, 1, 1, 1, 1, 1, 0, 0)
+    x = _seeded((1, 2, 5, 5), 12)
+    td = _seeded((1, 2, 5, 5), 13)
+    Wt = torch.zeros((2, 2, 3, 3), dtype=torch.float64, requires_grad=True)
+    F.conv2d(torch.tensor(x.astype(np.float64)), Wt, None, padding=1).backward(torch.tensor(td.astype(np.float64)))
+    full = Wt.grad.numpy().reshape(2, -1)
+    for k in (pkg.KERNEL_AUTO, pkg.KERNEL_GENERIC):
+        plan = pkg.Plan(d, backward_kernel=k)
+        plan.set_csr(np.array([0, 2, 3], np.int32), np.array([0, 4, 13], np.int32),
+                     np.array([0.0, 1.5, 0.0], np.float32), [3])
+        _, wd, _ = plan.backward(torch.from_numpy(td).to(dev), bottom=torch.from_numpy(x).to(dev), bottom_diff=None,
+                                 weight_diff=True)
+        flat = wd.cpu().numpy().reshape(2, -1)
+        mask = np.zeros_like(flat, bool)
+        mask[0, 0] = mask[0, 4] = mask[1, 13] = True
+        assert np.all(flat[~mask] == 0)
+        assert np.all(np.abs(flat[mask] - full[mask]) <= 1e-4 * np.abs(full).max()) and np.all(flat[mask] != 0)
+        plan.close()
+
+
+def test_forward_backward_graph_capture(pkg, dev, synth):
+    """After one warm-up call, forward + backward of three layers captured into one graph: a generated-code transposed
+    plan, a gather-kernel layer, a fuse_relu layer.  Two replays on new data, each checked against torch."""
+    specs = [
+        (synth.resnet50_3x3(N=2)[3], pkg.KERNEL_JIT, False),
+        (_odd_shape(synth, ODD[2], 2), pkg.KERNEL_AUTO, False),
+        (synth.shape("relu3x3", 2, 16, 12, 12, 24, 3, pad=1, sparsity=0.7), pkg.KERNEL_AUTO, True),
+    ]
+    layers = []
+    for i, (s, k, relu) in enumerate(specs):
+        w = synth.pruned_weights(s, 70 + i)
+        b = synth.bias_vector(s, 80 + i)
+        plan = pkg.Plan(pkg.ConvDesc.from_shape(s, fuse_relu=relu), backward_kernel=k, tiling_batch=256)
+        plan.weight_align(w)
+        oh, ow = plan.out_hw
+        bufs = dict(x=torch.zeros((s.N, s.C, s.H, s.W), device=dev), td=torch.zeros((s.N, s.M, oh, ow), device=dev),
+                    y=torch.zeros((s.N, s.M, oh, ow), device=dev), bd=torch.zeros((s.N, s.C, s.H, s.W), device=dev),
+                    wd=torch.zeros((s.M, s.C // s.group, s.KH, s.KW), device=dev),
+                    bsd=torch.zeros((s.M,), device=dev) if b is not None else None,
+                    b=torch.from_numpy(b).to(dev) if b is not None else None)
+        layers.append((s, plan, w, b, relu, bufs))
+
+    def step():
+        for s, plan, w, b, relu, u in layers:
+            plan.forward(u["x"], u["b"], u["y"])
+            plan.backward(u["td"], bottom=u["x"], top=u["y"] if relu else None, bottom_diff=u["bd"],
+                          weight_diff=u["wd"], bias_diff=u["bsd"])
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        step()                      # warm-up: builds the backward state outside the capture
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    assert layers[0][1].stat("bwd_data_kernel") == pkg.KERNEL_JIT
+    assert layers[1][1].stat("bwd_data_kernel") == pkg.KERNEL_GENERIC
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        step()
+    for rnd in range(2):
+        inputs = []
+        for k, (s, plan, w, b, relu, u) in enumerate(layers):
+            x = synth.activations(s, 900 + 10 * rnd + k)
+            td = _seeded(tuple(u["td"].shape), 950 + 10 * rnd + k)
+            u["x"].copy_(torch.from_numpy(x))
+            u["td"].copy_(torch.from_numpy(td))
+            u["bd"].fill_(float("nan"))
+            u["wd"].zero_()
+            if u["bsd"] is not None:
+                u["bsd"].zero_()
+            inputs.append((x, td))
+        g.replay()
+        torch.cuda.synchronize()
+        for (s, plan, w, b, relu, u), (x, td) in zip(layers, inputs):
+            top = u["y"].cpu().numpy() if relu else None
+            _check_against_torch(s, w, x, b, td, top, u["bd"].cpu().numpy(), u["wd"].cpu().numpy(),
+                                 None if b is None else u["bsd"].cpu().numpy(), what=(s.name, rnd))
+    for s, plan, *_ in layers:
+        plan.close()

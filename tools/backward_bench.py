@@ -1,0 +1,102 @@
+#!/usr/bin/env python3
+"""Backward on the MI355X: per layer, forward / data-gradient / weight-gradient / bias-gradient time of the
+pattern-preserving backward (escoin_backward), the kernels that ran, and the same shapes through torch's dense conv
+backward (MIOpen, dense weights) as a comparison point.
+
+Sets: the four ResNet-50 3x3 shapes @90 % (batch 256), the GoogLeNet 1x1 layers @95 % (batch 256), AlexNet conv2-5
+@80 % (batch 128).  Times are device events around `--reps` back-to-back calls after a warm-up, the median of
+`--regions` regions, per call.  Prints one JSON line (and progress on stderr).
+
+    python tools/backward_bench.py [--sets resnet,googlenet,alexnet] [--regions 7] [--reps 5] [--no-torch]
+"""
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import __graft_entry__ as ge  # noqa: E402
+
+FAMILY = {0: "auto", 1: "gather (escoin_sconv_bwd_data_kernel)", 2: "tiled (transposed plan)",
+          3: "dense MFMA (transposed plan)", 4: "generated code (transposed plan)"}
+
+
+def timed(fn, regions, reps):
+    import torch
+    for _ in range(2):
+        fn()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(regions):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            fn()
+        e1.record()
+        e1.synchronize()
+        out.append(e0.elapsed_time(e1) * 1e3 / reps)
+    out.sort()
+    return out[len(out) // 2]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sets", default="resnet,googlenet,alexnet")
+    ap.add_argument("--regions", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-torch", action="store_true")
+    a = ap.parse_args()
+    import torch
+    pkg = ge.load_package()
+    synth = pkg.synth
+    dev = torch.device("cuda:0")
+    layers = []
+    sets = a.sets.split(",")
+    if "resnet" in sets:
+        layers += synth.resnet50_3x3(N=256, sparsity=0.9)
+    if "googlenet" in sets:
+        layers += synth.googlenet_1x1(N=256, sparsity=0.95)
+    if "alexnet" in sets:
+        layers += synth.alexnet(N=128, sparsity=0.8)
+    rows = []
+    for i, s in enumerate(layers):
+        w = synth.pruned_weights(s, 1000 + i)
+        b = synth.bias_vector(s, 2000 + i)
+        x = torch.from_numpy(synth.activations(s, 3000 + i)).to(dev)
+        plan = pkg.Plan(pkg.ConvDesc.from_shape(s))
+        plan.weight_align(w)
+        bt = torch.from_numpy(b).to(dev) if b is not None else None
+        top = plan.forward(x, bt)
+        td = torch.empty_like(top).uniform_(-1, 1)
+        bd = torch.empty_like(x)
+        wd = torch.zeros((s.M, s.C // s.group, s.KH, s.KW), device=dev)
+        bsd = torch.zeros((s.M,), device=dev)
+        plan.backward(td, bottom=x, bottom_diff=bd, weight_diff=wd, bias_diff=bsd)   # builds the backward state
+        r = dict(layer=s.name, N=s.N, density=round(float((w != 0).mean()), 4), fwd_kernel=plan.kernel_name,
+                 bwd_data_kernel=FAMILY[plan.stat("bwd_data_kernel")], bwd_chunks=plan.stat("bwd_chunks"),
+                 bwd_align_ms=plan.stat("bwd_align_us") * 1e-3, bwd_device_mb=plan.stat("bwd_device_bytes") / 1e6)
+        r["fwd_us"] = timed(lambda: plan.forward(x, bt, top), a.regions, a.reps)
+        r["bwd_data_us"] = timed(lambda: plan.backward(td, bottom_diff=bd), a.regions, a.reps)
+        r["bwd_weight_us"] = timed(lambda: plan.backward(td, bottom=x, bottom_diff=None, weight_diff=wd), a.regions, a.reps)
+        r["bwd_bias_us"] = timed(lambda: plan.backward(td, bottom_diff=None, bias_diff=bsd), a.regions, a.reps)
+        r["data_over_fwd"] = round(r["bwd_data_us"] / r["fwd_us"], 3)
+        r["weight_over_fwd"] = round(r["bwd_weight_us"] / r["fwd_us"], 3)
+        if not a.no_torch:
+            wdense = torch.from_numpy(w).to(dev)
+            args = ([s.stride_h, s.stride_w], [s.pad_h, s.pad_w], [s.dil_h, s.dil_w], False, [0, 0], s.group)
+            conv_bwd = torch.ops.aten.convolution_backward
+            r["torch_data_us"] = timed(lambda: conv_bwd(td, x, wdense, None, *args, [True, False, False]), a.regions, a.reps)
+            r["torch_weight_us"] = timed(lambda: conv_bwd(td, x, wdense, None, *args, [False, True, False]), a.regions, a.reps)
+        plan.close()
+        rows.append(r)
+        print("%-28s fwd %8.1f  data %8.1f  weight %8.1f  bias %7.1f us  [%s]%s" % (
+            s.name, r["fwd_us"], r["bwd_data_us"], r["bwd_weight_us"], r["bwd_bias_us"], r["bwd_data_kernel"],
+            "" if a.no_torch else "  torch data %8.1f weight %8.1f" % (r["torch_data_us"], r["torch_weight_us"])),
+            file=sys.stderr, flush=True)
+    print(json.dumps(dict(tool="backward_bench", device=torch.cuda.get_device_name(0), layers=rows)))
+
+
+if __name__ == "__main__":
+    main()
