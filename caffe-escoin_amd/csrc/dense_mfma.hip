@@ -603,11 +603,8 @@ int dense_build_ktab(escoin_plan *p, hipStream_t stream) {
       tab[2 * k + 1] = 0x7FFF | (0x7FFF << 16);
     }
   }
-  if (p->d_ktab) (void)hipFree(p->d_ktab);
-  p->d_ktab = nullptr;
-  ESCOIN_HIP_TRY(hipMalloc(&p->d_ktab, sizeof(int) * tab.size()));
-  p->device_bytes += sizeof(int) * tab.size();
-  ESCOIN_HIP_TRY(hipMemcpyAsync(p->d_ktab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice, stream));
+  DenseArrays &dn = p->dense;
+  ESCOIN_HIP_TRY(dn.ktab.upload(tab, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
   // Stream-K workspace, here and not at the first launch: escoin_forward must neither allocate nor synchronise (a host
   // may capture its very first forward into a HIP graph).  A stream-K launch always runs
@@ -618,17 +615,10 @@ int dense_build_ktab(escoin_plan *p, hipStream_t stream) {
     const long n_wg = 2l * dense_device_cus();
     const size_t ws_bytes = (size_t)n_wg * 4 * 16 * 64 * 4 * sizeof(float);
     const size_t flag_bytes = ((size_t)(n_wg + 1) * 4 + 15) / 16 * 16;
-    if (!p->h_sk_fail) ESCOIN_HIP_TRY(hipHostMalloc((void **)&p->h_sk_fail, 64, hipHostMallocMapped));
-    *p->h_sk_fail = 0u;
-    ESCOIN_HIP_TRY(hipHostGetDevicePointer((void **)&p->d_sk_fail, p->h_sk_fail, 0));
-    if (p->d_sk_ws) (void)hipFree(p->d_sk_ws);
-    p->d_sk_ws = nullptr;
-    p->sk_ws_bytes = 0;
-    ESCOIN_HIP_TRY(hipMalloc(&p->d_sk_ws, ws_bytes + flag_bytes));
-    p->sk_ws_bytes = ws_bytes + flag_bytes;
-    p->device_bytes += ws_bytes + flag_bytes;
-    ESCOIN_HIP_TRY(hipMemset(p->d_sk_ws, 0, flag_bytes));
-    p->sk_flag_words = (int)n_wg + 1;
+    ESCOIN_HIP_TRY(dn.sk_fail.alloc());
+    ESCOIN_HIP_TRY(dn.sk_ws.alloc(ws_bytes + flag_bytes));
+    ESCOIN_HIP_TRY(hipMemset(dn.sk_ws.get<void>(), 0, flag_bytes));
+    dn.sk_flag_words = (int)n_wg + 1;
   }
   return ESCOIN_OK;
 }
@@ -636,10 +626,11 @@ int dense_build_ktab(escoin_plan *p, hipStream_t stream) {
 int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, float *top,
                  int n_images, hipStream_t stream) {
   const Geometry &g = p->g;
-  if (!p->d_ktab || !p->d_dense_w) return fail(ESCOIN_ESTATE, "dense kernel: plan has no dense weights");
+  const DenseArrays &dn = p->dense;
+  if (!dn.ktab.get<void>() || !dn.w.get<void>()) return fail(ESCOIN_ESTATE, "dense kernel: plan has no dense weights");
   DenseArgs a;
-  a.in = bottom; a.w = p->d_dense_w; a.bias = bias; a.out = top;
-  a.ktab = reinterpret_cast<const int2 *>(p->d_ktab);
+  a.in = bottom; a.w = dn.w.get<const float>(); a.bias = bias; a.out = top;
+  a.ktab = dn.ktab.get<const int2>();
   a.n_images = n_images; a.C = g.d.C; a.H = g.d.H; a.W = g.d.W; a.M = g.d.M; a.OH = g.OH; a.OW = g.OW;
   a.pad_h = g.d.pad_h; a.pad_w = g.d.pad_w; a.stride_h = g.d.stride_h; a.stride_w = g.d.stride_w;
   a.Cg = g.Cg; a.Mg = g.Mg; a.K = g.kdim; a.lda = dense_lda(g.kdim); a.relu = g.d.fuse_relu;
@@ -697,18 +688,18 @@ int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, f
   if (tiles * nk < slots) streamk = false;
   // (the workspace and the pinned give-up word were allocated by dense_build_ktab at WeightAlign; a launch never
   //  allocates -- a plan without them runs whole tiles)
-  if (streamk && (!p->d_sk_ws || !p->h_sk_fail || !p->d_sk_fail ||
-                  p->sk_ws_bytes < (size_t)slots * 4 * 16 * 64 * 4 * sizeof(float) + ((size_t)(slots + 1) * 4 + 15) / 16 * 16))
+  if (streamk && (!dn.sk_ws.get<void>() || !dn.sk_fail.host() || !dn.sk_fail.device() ||
+                  dn.sk_ws.bytes() < (size_t)slots * 4 * 16 * 64 * 4 * sizeof(float) + ((size_t)(slots + 1) * 4 + 15) / 16 * 16))
     streamk = false;
   const long n_wg = streamk ? slots : std::min<long>(tiles, slots);
   a.sk_ws = nullptr;
   a.sk_flag = nullptr;
   a.sk_fail = nullptr;
   if (streamk) {
-    a.sk_fail = p->d_sk_fail;
+    a.sk_fail = dn.sk_fail.device();
     const size_t flag_bytes = ((size_t)(n_wg + 1) * 4 + 15) / 16 * 16;
-    a.sk_flag = reinterpret_cast<unsigned *>(p->d_sk_ws);
-    a.sk_ws = reinterpret_cast<float *>(reinterpret_cast<char *>(p->d_sk_ws) + flag_bytes);
+    a.sk_flag = dn.sk_ws.get<unsigned>();
+    a.sk_ws = reinterpret_cast<float *>(dn.sk_ws.get<char>() + flag_bytes);
     // re-arm the flags with a KERNEL, not hipMemsetAsync: captured into a HIP graph, a memset node of this size
     // (2064 bytes) left garbage in its last 16 bytes -- the give-up word -- from the second replay on (ROCm 7.2, MI355X;
     // tools/dbg/sk_graph.py: eager launches and the first replay read 0, later replays 0xDB3F....), while kernel nodes
@@ -716,7 +707,7 @@ int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, f
     hipLaunchKernelGGL(escoin_sk_clear_kernel, dim3(((unsigned)(flag_bytes / 4) + 255) / 256), dim3(256), 0, stream, a.sk_flag,
                        (int)(flag_bytes / 4));
   }
-  p->sk_used = streamk;
+  dn.sk_used = streamk;
   dim3 grid((unsigned)n_wg, 1, 1);
 #define ESC_DENSE_LAUNCH(WR, MODE)                                                                                 \
   do {                                                                                                             \

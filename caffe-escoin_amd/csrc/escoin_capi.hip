@@ -33,9 +33,6 @@ static double ms_since(std::chrono::steady_clock::time_point t0) {
 
 template <typename T>
 int set_csr_host(escoin_plan *p, const int *rowptr, const int *colidx, const T *values, const int *nnz_per_group);
-template <typename T> std::vector<std::vector<T>> &plan_vals(escoin_plan *p);
-template <> std::vector<std::vector<float>> &plan_vals<float>(escoin_plan *p) { return p->values; }
-template <> std::vector<std::vector<double>> &plan_vals<double>(escoin_plan *p) { return p->values64; }
 
 static int out_dim(int in, int k, int pad, int stride, int dil) {
   // conv_layer.cpp:16-19
@@ -68,63 +65,36 @@ static int validate(const escoin_conv_desc *d, Geometry *g) {
   return ESCOIN_OK;
 }
 
-void bwd_release(escoin_plan *p) {
-  BwdState *s = p->bwd;
-  if (!s) return;
-  if (s->tplan) escoin_plan_destroy(s->tplan);
-  if (s->d_trow) (void)hipFree(s->d_trow);
-  if (s->d_ttap) (void)hipFree(s->d_ttap);
-  if (s->d_tval) (void)hipFree(s->d_tval);
-  if (s->d_wpos) (void)hipFree(s->d_wpos);
-  if (s->d_slab) (void)hipFree(s->d_slab);
-  if (s->d_g) (void)hipFree(s->d_g);
-  delete s;
-  p->bwd = nullptr;
+DeviceBytes device_bytes(const escoin_plan *p) {
+  const TiledArrays &t = p->tiled_dev;
+  const DenseArrays &dn = p->dense;
+  DeviceBytes b{p->gen.rowptr.bytes() + p->gen.taps.bytes() + p->gen.vals.bytes() + t.stream.bytes() + t.unit_hdr.bytes() +
+                    t.chan.bytes() + t.jit.code_bytes + dn.w.bytes() + dn.ktab.bytes() + dn.sk_ws.bytes() + p->col.bytes(),
+                0};
+  if (const BwdState *s = p->bwd.get())
+    b.bwd = s->trow.bytes() + s->ttap.bytes() + s->tval.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() +
+            (s->tplan ? device_bytes(s->tplan.get()).fwd : 0);
+  return b;
 }
 
 long bwd_stat(const escoin_plan *p, const char *key) {
-  const BwdState *s = p->bwd;
+  const BwdState *s = p->bwd.get();
   if (!strcmp(key, "bwd_data_kernel")) {
     if (!s) return fail(ESCOIN_ESTATE, "bwd_data_kernel: no backward has run on this alignment");
     return s->data_kernel;
   }
-  if (!strcmp(key, "bwd_device_bytes")) return s ? (long)(s->device_bytes + (s->tplan ? s->tplan->device_bytes : 0)) : 0;
+  if (!strcmp(key, "bwd_device_bytes")) return (long)device_bytes(p).bwd;
   if (!strcmp(key, "bwd_chunks")) return s ? s->last_chunks : 0;
   if (!strcmp(key, "bwd_align_us")) return s ? (long)(s->align_ms * 1e3) : 0;
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
 
-size_t bwd_device_bytes(const escoin_plan *p) {
-  const BwdState *s = p->bwd;
-  return s ? s->device_bytes + (s->tplan ? s->tplan->device_bytes : 0) : 0;
-}
-
 static void free_device(escoin_plan *p) {
-  bwd_release(p);
-  if (p->d_rowptr) (void)hipFree(p->d_rowptr);
-  if (p->d_taps) (void)hipFree(p->d_taps);
-  if (p->d_vals) (void)hipFree(p->d_vals);
-  if (p->d_vals64) (void)hipFree(p->d_vals64);
-  p->d_vals64 = nullptr;
+  p->bwd.reset();
+  p->gen = GenericArrays();
   tiled_release(p);
-  if (p->d_col) (void)hipFree(p->d_col);
-  p->d_col = nullptr;
-  p->col_bytes = 0;
-  if (p->d_dense_w) (void)hipFree(p->d_dense_w);
-  p->d_dense_w = nullptr;
-  if (p->d_ktab) (void)hipFree(p->d_ktab);
-  p->d_ktab = nullptr;
-  if (p->d_sk_ws) (void)hipFree(p->d_sk_ws);
-  p->d_sk_ws = nullptr;
-  p->sk_ws_bytes = 0;
-  p->sk_flag_words = 0;
-  if (p->h_sk_fail) (void)hipHostFree(p->h_sk_fail);
-  p->h_sk_fail = nullptr;
-  p->d_sk_fail = nullptr;
-  p->sk_used = false;
-  p->d_rowptr = p->d_taps = nullptr;
-  p->d_vals = nullptr;
-  p->device_bytes = 0;
+  p->col.reset();
+  p->dense = DenseArrays();
 }
 
 // Small launches.  The LDS-tiled kernels walk a tile block by block, every block a round trip to HBM, on as many
@@ -170,15 +140,13 @@ int small_launch_rule(const escoin_plan *p, const Tiling &t, bool chained) {
   return pick;
 }
 
-// Dtype = double: rowptr / packed taps / double values for the order-preserving generic kernel -- the only device
-// kernel a double plan runs, in every conv_mode (fp64 vector FMA is native on gfx950; the LDS-tiled, generated-code and
-// MFMA kernels are fp32: north_star measures fp32, double is boundary completeness, conv_layer.cu:75).
-static int upload_f64(escoin_plan *p, hipStream_t stream) {
+// The generic kernel's device CSR (p->gen) from the host CSR: rowptr, packed taps and values of the plan's Dtype.
+template <typename T>
+static int upload_generic(escoin_plan *p, long nnz, hipStream_t stream) {
   const Geometry &g = p->g;
-  long nnz = 0;
-  for (int grp = 0; grp < g.d.group; ++grp) nnz += (long)p->colidx[grp].size();
+  const std::vector<std::vector<T>> &values = plan_vals<T>(p);
   std::vector<int> rowptr(g.d.M + 1), taps((size_t)(nnz > 0 ? nnz : 1));
-  std::vector<double> vals((size_t)(nnz > 0 ? nnz : 1));
+  std::vector<T> vals((size_t)(nnz > 0 ? nnz : 1));
   long base = 0;
   for (int grp = 0; grp < g.d.group; ++grp) {
     for (int m = 0; m < g.Mg; ++m) rowptr[grp * g.Mg + m] = (int)(base + p->rowptr[grp][m]);
@@ -186,29 +154,15 @@ static int upload_f64(escoin_plan *p, hipStream_t stream) {
     for (long j = 0; j < n_g; ++j) {
       const int col = p->colidx[grp][j];
       taps[base + j] = pack_tap(col / (g.d.KW * g.d.KH), (col / g.d.KW) % g.d.KH, col % g.d.KW);
-      vals[base + j] = p->values64[grp][j];
+      vals[base + j] = values[grp][j];
     }
     base += n_g;
   }
   rowptr[g.d.M] = (int)base;
-  ESCOIN_HIP_TRY(hipMalloc(&p->d_rowptr, sizeof(int) * rowptr.size()));
-  ESCOIN_HIP_TRY(hipMalloc(&p->d_taps, sizeof(int) * taps.size()));
-  ESCOIN_HIP_TRY(hipMalloc(&p->d_vals64, sizeof(double) * vals.size()));
-  p->device_bytes += sizeof(int) * (rowptr.size() + taps.size()) + sizeof(double) * vals.size();
-  ESCOIN_HIP_TRY(hipMemcpyAsync(p->d_rowptr, rowptr.data(), sizeof(int) * rowptr.size(), hipMemcpyHostToDevice, stream));
-  ESCOIN_HIP_TRY(hipMemcpyAsync(p->d_taps, taps.data(), sizeof(int) * taps.size(), hipMemcpyHostToDevice, stream));
-  ESCOIN_HIP_TRY(hipMemcpyAsync(p->d_vals64, vals.data(), sizeof(double) * vals.size(), hipMemcpyHostToDevice, stream));
+  ESCOIN_HIP_TRY(p->gen.rowptr.upload(rowptr, stream));
+  ESCOIN_HIP_TRY(p->gen.taps.upload(taps, stream));
+  ESCOIN_HIP_TRY(p->gen.vals.upload(vals, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));  // host vectors die at scope exit
-  p->tiled = TiledConfig();
-  p->n_dense_groups = 0;
-  p->n_sparse_groups = g.d.group;
-  p->use_dense = false;
-  p->dense_mask = 0;
-  p->sparse_mask = ~0ull;
-  p->small_rule = 0;
-  p->import_fast = false;
-  p->kernel_name = generic_kernel_name_f64(g.d.fuse_relu != 0);
-  p->aligned = true;
   return ESCOIN_OK;
 }
 
@@ -222,38 +176,21 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     return fail(ESCOIN_ENODEVICE, "no HIP device: escoin_weight_align / set_csr / import_aligned prepare the GPU path (Caffe::CPU mode has its own entry points: escoin_weight_align_cpu, escoin_forward_cpu)");
   ESCOIN_HIP_TRY(hipGetDevice(&p->device));
   free_device(p);
-  if (p->is_f64) return upload_f64(p, stream);
   const Geometry &g = p->g;
   long nnz = 0;
   for (int grp = 0; grp < g.d.group; ++grp) nnz += (long)p->colidx[grp].size();
-  std::vector<int> rowptr(g.d.M + 1), taps((size_t)(nnz > 0 ? nnz : 1));
-  std::vector<float> vals((size_t)(nnz > 0 ? nnz : 1));
-  long base = 0;
-  for (int grp = 0; grp < g.d.group; ++grp) {
-    for (int m = 0; m < g.Mg; ++m) rowptr[grp * g.Mg + m] = (int)(base + p->rowptr[grp][m]);
-    const long n_g = (long)p->colidx[grp].size();
-    for (long j = 0; j < n_g; ++j) {
-      const int col = p->colidx[grp][j];
-      const int kc = col % g.d.KW, kr = (col / g.d.KW) % g.d.KH, ic = col / (g.d.KW * g.d.KH);
-      taps[base + j] = pack_tap(ic, kr, kc);
-      vals[base + j] = p->values[grp][j];
-    }
-    base += n_g;
+  const int rc_gen = p->is_f64 ? upload_generic<double>(p, nnz, stream) : upload_generic<float>(p, nnz, stream);
+  if (rc_gen != ESCOIN_OK) return rc_gen;
+  if (p->is_f64) {
+    // Dtype = double: the order-preserving generic kernel is the only device kernel a double plan runs, in every
+    // conv_mode (fp64 vector FMA is native on gfx950; the LDS-tiled, generated-code and MFMA kernels are fp32: north_star
+    // measures fp32, double is boundary completeness, conv_layer.cu:75).
+    p->n_dense_groups = 0; p->n_sparse_groups = g.d.group; p->use_dense = false;
+    p->dense_mask = 0; p->sparse_mask = ~0ull; p->small_rule = 0; p->import_fast = false;
+    p->kernel_name = generic_kernel_name_f64(g.d.fuse_relu != 0);
+    p->aligned = true;
+    return ESCOIN_OK;
   }
-  rowptr[g.d.M] = (int)base;
-  ESCOIN_HIP_TRY(hipMalloc(&p->d_rowptr, sizeof(int) * rowptr.size()));
-  ESCOIN_HIP_TRY(hipMalloc(&p->d_taps, sizeof(int) * taps.size()));
-  ESCOIN_HIP_TRY(hipMalloc(&p->d_vals, sizeof(float) * vals.size()));
-  p->device_bytes += sizeof(int) * (rowptr.size() + taps.size()) + sizeof(float) * vals.size();
-  ESCOIN_HIP_TRY(hipMemcpyAsync(p->d_rowptr, rowptr.data(), sizeof(int) * rowptr.size(),
-                                hipMemcpyHostToDevice, stream));
-  ESCOIN_HIP_TRY(hipMemcpyAsync(p->d_taps, taps.data(), sizeof(int) * taps.size(),
-                                hipMemcpyHostToDevice, stream));
-  ESCOIN_HIP_TRY(hipMemcpyAsync(p->d_vals, vals.data(), sizeof(float) * vals.size(),
-                                hipMemcpyHostToDevice, stream));
-  ESCOIN_HIP_TRY(hipStreamSynchronize(stream));  // host vectors die at scope exit
-
-  p->tiled = TiledConfig();
   // ---- which conv groups go to the dense (fp32 MFMA) kernel -------------------------------
   //  * kernel DENSE or conv_mode LOWERED_GEMM (forward_gpu_gemm, base_conv_layer.cpp:713-746): all;
   //  * dense_gate = 1: the reference's gate -- group 0's density decides for the whole layer
@@ -332,10 +269,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
       for (int m = 0; m < g.Mg; ++m)
         for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j)
           dw[((size_t)grp * g.Mg + m) * lda + p->colidx[grp][j]] = p->values[grp][j];
-    ESCOIN_HIP_TRY(hipMalloc(&p->d_dense_w, sizeof(float) * dw.size()));
-    p->device_bytes += sizeof(float) * dw.size();
-    ESCOIN_HIP_TRY(hipMemcpyAsync(p->d_dense_w, dw.data(), sizeof(float) * dw.size(),
-                                  hipMemcpyHostToDevice, stream));
+    ESCOIN_HIP_TRY(p->dense.w.upload(dw, stream));
     ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
     const int rc = dense_build_ktab(p, stream);
     if (rc != ESCOIN_OK) return rc;
@@ -549,8 +483,6 @@ int escoin_plan_create(const escoin_conv_desc *desc, escoin_plan **plan) {
 }
 
 int escoin_plan_destroy(escoin_plan *plan) {
-  if (!plan) return ESCOIN_OK;
-  free_device(plan);
   delete plan;
   return ESCOIN_OK;
 }
@@ -861,12 +793,12 @@ int escoin_plan_import_aligned_dev(escoin_plan *p, const void *dev_buf, size_t b
 long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!p || !key) return fail(ESCOIN_EINVAL, "null argument");
   if (!strcmp(key, "align_us")) return (long)(p->align_ms * 1e3);
-  if (!strcmp(key, "code_bytes")) return (long)(p->tiled.enabled && p->tiled.jit ? p->jit_module.code_bytes : 0);
-  if (!strcmp(key, "device_bytes")) return (long)p->device_bytes;
+  if (!strcmp(key, "code_bytes")) return (long)(p->tiled.enabled && p->tiled.jit ? p->tiled_dev.jit.code_bytes : 0);
+  if (!strcmp(key, "device_bytes")) return (long)device_bytes(p).fwd;
   if (!strcmp(key, "import_fast")) return p->import_fast ? 1 : 0;
   if (!strcmp(key, "cpu_images_per_job")) return p->cpu_img_last;   // images per job of the last escoin_forward_cpu
   if (!strcmp(key, "cpu_channel_block")) return p->cpu_blk_cb;     // channels per block of the last escoin_forward_cpu (0: unblocked, -1: none yet)
-  if (!strcmp(key, "code_direct")) return p->jit_module.direct ? 1 : 0;     // the plan's code sits in executable memory the library filled itself
+  if (!strcmp(key, "code_direct")) return p->tiled_dev.jit.direct ? 1 : 0;     // the plan's code sits in executable memory the library filled itself
   if (!strcmp(key, "small_launch_rule")) return p->small_rule;
   if (!strcmp(key, "jit_rows")) return p->tiled.jit ? p->tiled.jit_rows : 0;
   if (!strcmp(key, "jit_records")) return p->tiled.jit ? p->tiled.jit_records : 0;
@@ -879,14 +811,15 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "streamk_gave_up")) {
     // dense kernel, stream-K launches: 1 if a workgroup's bounded wait for another one's partial sums ran out in
     // the last launch (its results are then wrong); synchronises with the device.  0 for plans that never split K.
-    if (!p->d_sk_ws || p->sk_flag_words < 1 || !p->sk_used) return 0;
-    if (p->h_sk_fail && *(volatile unsigned *)p->h_sk_fail != 0u) return 1;      // (sticky: any launch since WeightAlign)
+    const DenseArrays &dn = p->dense;
+    if (!dn.sk_ws.get<void>() || dn.sk_flag_words < 1 || !dn.sk_used) return 0;
+    if (dn.sk_fail.host() && *(volatile unsigned *)dn.sk_fail.host() != 0u) return 1;      // (sticky: any launch since WeightAlign)
     unsigned v = 0;
-    if (hipMemcpy(&v, static_cast<const unsigned *>(p->d_sk_ws) + (p->sk_flag_words - 1), 4, hipMemcpyDeviceToHost) != hipSuccess)
+    if (hipMemcpy(&v, dn.sk_ws.get<const unsigned>() + (dn.sk_flag_words - 1), 4, hipMemcpyDeviceToHost) != hipSuccess)
       return fail(ESCOIN_EHIP, "streamk_gave_up: device read failed");
     return (long)v;
   }
-  if (!strcmp(key, "streamk")) return p->sk_used ? 1 : 0;
+  if (!strcmp(key, "streamk")) return p->dense.sk_used ? 1 : 0;
   if (!strncmp(key, "bwd_", 4)) return bwd_stat(p, key);
   if (!strcmp(key, "is_f64")) return p->is_f64 ? 1 : 0;
   if (!strcmp(key, "host_aligned")) return p->host_aligned ? 1 : 0;
@@ -917,7 +850,11 @@ int escoin_plan_get_csr_f64(const escoin_plan *p, int *rowptr, int *colidx, doub
   return guarded([&]() -> int { return get_csr_t<double>(p, rowptr, colidx, values, stretched); });
 }
 
-size_t escoin_plan_workspace_bytes(const escoin_plan *p) { return p ? p->device_bytes + bwd_device_bytes(p) : 0; }
+size_t escoin_plan_workspace_bytes(const escoin_plan *p) {
+  if (!p) return 0;
+  const DeviceBytes b = device_bytes(p);
+  return b.fwd + b.bwd;
+}
 
 const char *escoin_plan_kernel_name(const escoin_plan *p) {
   if (p && p->aligned && !p->is_f64 && p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE &&
@@ -947,7 +884,7 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
     // dense kernel, stream-K: a fix-up wait that ran out in an EARLIER launch of this plan left wrong results in that
     // launch's top blob.  The word lives in pinned host memory (no synchronisation here) and stays set until the
     // next WeightAlign: the caller hears about it at the next call at the latest (dense_mfma.hip).
-    if (p->h_sk_fail && *(volatile unsigned *)p->h_sk_fail != 0u)
+    if (p->dense.sk_fail.host() && *(volatile unsigned *)p->dense.sk_fail.host() != 0u)
       return fail(ESCOIN_EHIP, "dense kernel (stream-K): a workgroup gave up waiting for another one's partial sums in an "
                                "earlier launch of this plan; that launch's results are wrong");
     hipStream_t s = (hipStream_t)stream;

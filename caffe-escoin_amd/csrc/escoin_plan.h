@@ -4,11 +4,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <new>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "device_buffer.h"
 #include "escoin.h"
 #include "jit_module.h"
 #include "stream_builder.h"
@@ -88,20 +90,46 @@ struct CpuWorkspace {
   unsigned long call = 0;        // ... as of this escoin_forward_cpu call
 };
 
-// What the first escoin_backward on an alignment builds (sconv_backward.hip); released with the device side.
+// What the first escoin_backward on an alignment builds (sconv_backward.hip); reset with the device side.
 struct BwdState {
-  escoin_plan *tplan = nullptr;   // transposed forward plan (path a), or null: the gather kernel (path b)
+  // transposed forward plan (path a), or null: the gather kernel (path b)
+  std::unique_ptr<escoin_plan, int (*)(escoin_plan *)> tplan{nullptr, escoin_plan_destroy};
   int data_kernel = ESCOIN_KERNEL_GENERIC;
-  int *d_trow = nullptr;          // [C + 1] absolute offsets into d_ttap / d_tval (gather kernel)
-  int *d_ttap = nullptr;          // per transposed entry: ocl << 16 | kr << 8 | kc
-  void *d_tval = nullptr;         // float or double values, in the transposed order
-  int *d_wpos = nullptr;          // per CSR entry: oc * kdim + colidx (its position in weight_diff)
-  void *d_slab = nullptr;         // [chunks_max][nnz] weight partials, then [chunks_max][M] bias partials
-  void *d_g = nullptr;            // fuse_relu + path (a): top_diff * [top > 0], desc.N x M x OH x OW
+  DeviceBuffer trow;   // [C + 1] absolute offsets into ttap / tval (gather kernel)
+  DeviceBuffer ttap;   // per transposed entry: ocl << 16 | kr << 8 | kc
+  DeviceBuffer tval;   // float or double values, in the transposed order
+  DeviceBuffer wpos;   // per CSR entry: oc * kdim + colidx (its position in weight_diff)
+  DeviceBuffer slab;   // [chunks_max][nnz] weight partials, then [chunks_max][M] bias partials
+  DeviceBuffer g;      // fuse_relu + path (a): top_diff * [top > 0], desc.N x M x OH x OW
   long nnz = 0;
   int chunks_max = 0, last_chunks = 0;
-  size_t device_bytes = 0;        // the arrays above (the transposed plan's own bytes are added in bwd_device_bytes)
   double align_ms = 0.0;
+};
+
+// The generic kernel's device CSR (escoin_capi.hip upload): rowptr [M + 1] absolute offsets into taps / vals; taps and
+// vals [max(nnz, 1)], the packed (ic,kr,kc) and the values of the plan's Dtype
+struct GenericArrays { DeviceBuffer rowptr, taps, vals; };
+
+// What tiled_build / tiled_import put on the device for the tiled kernels
+struct TiledArrays {
+  DeviceBuffer stream;     // unit bodies of the weight stream (stream_builder.h)
+  DeviceBuffer unit_hdr;   // 8 dwords per (conv group, oc group, ic block); generated code: 1 (code offset)
+  DeviceBuffer chan;       // slot -> output channel (WeightStream::chan)
+  JitModule jit;           // generated-code kernel: where the plan's code lives on the device (jit_module.h)
+  // host copies of what a generated-code plan loaded, kept for escoin_plan_export_aligned: the code
+  // (position-independent words, jit_codegen.h), the unit table and the channel deal
+  std::vector<uint32_t> jit_code, h_unit_off, h_chan;
+};
+
+// The dense fallback's device side (upload, dense_build_ktab)
+struct DenseArrays {
+  DeviceBuffer w;          // [M + dense_spare_rows()][dense_lda(Cg*KH*KW)], zero padded
+  DeviceBuffer ktab;       // im2col decode per k: {image offset, dy | dx << 16} (dense_mfma.hip)
+  // stream-K (dense_mfma.hip), allocated at WeightAlign for layers whose launches may split K: a launch never allocates
+  DeviceBuffer sk_ws;      // flag words, then the partial accumulators
+  int sk_flag_words = 0;
+  MappedWord sk_fail;      // the word the kernel sets when a fix-up wait gave up (sticky until the next WeightAlign)
+  mutable bool sk_used = false;   // the last dense launch of this plan split K (escoin_plan_stat "streamk")
 };
 
 constexpr int kBwdChunkPixels = 1024;   // flattened (n, oh, ow) pixels per chunk of the weight-gradient reduction
@@ -127,7 +155,6 @@ struct escoin_plan {
   // values here, runs the order-preserving generic kernel on the device (no fast path) and the same host kernel
   std::vector<std::vector<double>> values64;
   bool is_f64 = false;
-  double *d_vals64 = nullptr;
   // Caffe::CPU mode (sconv_cpu.cpp): true once a CSR is on the host, whether or not a device was there to upload to;
   // cpu_off = the nonzeros' offsets into the shared-halo padded image for THIS geometry (dilation folded in), built on
   // the first escoin_forward_cpu after an align
@@ -144,24 +171,12 @@ struct escoin_plan {
   std::vector<escoin::CpuWorkspace> cpu_ws;   // per team thread: padded image + store scratch
   unsigned long cpu_calls = 0;
 
-  // device arrays for the generic kernel
-  int *d_rowptr = nullptr;   // [M+1] absolute offsets into d_taps/d_vals
-  int *d_taps = nullptr;     // [nnz] packed (ic,kr,kc)
-  float *d_vals = nullptr;   // [nnz]
-
-  // device arrays for the tiled kernel
-  escoin::TiledConfig tiled;
-  unsigned *d_stream = nullptr;   // unit bodies of the weight stream (stream_builder.h)
-  unsigned *d_unit_hdr = nullptr; // 8 dwords per (conv group, oc group, ic block); generated code: 1 (code offset)
-  escoin::JitModule jit_module;   // generated-code kernel: where the plan's code lives on the device (jit_module.h)
-  unsigned *d_chan = nullptr;     // slot -> output channel (WeightStream::chan)
-  size_t stream_words = 0;
-  size_t tiled_device_bytes = 0;  // device bytes of the five members above (part of device_bytes)
-  // host copies of what a generated-code plan loaded, kept for escoin_plan_export_aligned: the code
-  // (position-independent words, jit_codegen.h), the unit table and the channel deal
-  std::vector<uint32_t> jit_code;
+  // Device memory has one owner each (gen, tiled_dev, dense, col, bwd): the device bytes are computed from them, and
+  // weight_align / set_csr / import_aligned reset them all (free_device) before they build anew.
+  escoin::GenericArrays gen;
+  escoin::TiledConfig tiled;      // the tiled kernel's parameters (a plain value)
+  escoin::TiledArrays tiled_dev;
   int code_loader = 0;            // option "code_loader": 0 executable device memory first, 1 the code object loader (jit_module.h)
-  std::vector<uint32_t> h_unit_off, h_chan;
   double align_ms = 0.0;          // wall time of the last weight_align / set_csr / import_aligned
   bool import_fast = false;       // the last import_aligned loaded a persisted code object as it was
   int small_rule = 0;              // KERNEL_AUTO's small-launch rule applied to this plan: 0 not considered, 1 kept generated code, 2 took the generic kernel
@@ -169,34 +184,22 @@ struct escoin_plan {
   // dense fallback (fp32 MFMA implicit GEMM), chosen per conv group: bit g of dense_mask = group g
   // goes to the MFMA kernel, bit g of sparse_mask = to the sparse kernels (layers with more than 64
   // groups take one decision for all of them: both masks are then all-ones / zero)
-  float *d_dense_w = nullptr;     // [M + dense_spare_rows()][dense_lda(Cg*KH*KW)], zero padded
-  int *d_ktab = nullptr;          // im2col decode per k: {image offset, dy | dx << 16} (dense_mfma.hip)
+  escoin::DenseArrays dense;
   bool use_dense = false;         // every group dense
   unsigned long long dense_mask = 0, sparse_mask = ~0ull;
   int n_dense_groups = 0, n_sparse_groups = 0;
   int dense_threshold_pct = -1;   // option "dense_threshold_pct" (-1: the measured default)
   int stream_stores = -1;         // option "stream_stores": pointwise layers write the top blob with non-temporal stores (1), never (0), by size (-1)
 
-  // stream-K workspace of the dense kernel (dense_mfma.hip): flag words, then the partial accumulators; grown on
-  // allocated at WeightAlign for layers whose launches may split K (dense_build_ktab): a launch never allocates
-  mutable void *d_sk_ws = nullptr;
-  mutable size_t sk_ws_bytes = 0;
-  mutable int sk_flag_words = 0;
-  mutable bool sk_used = false;            // the last dense launch of this plan split K (escoin_plan_stat "streamk")
-  unsigned *d_sk_fail = nullptr;           // device address of h_sk_fail (looked up once, at WeightAlign)
-  mutable unsigned *h_sk_fail = nullptr;   // pinned host word the kernel sets when a fix-up wait gave up (sticky until the next WeightAlign)
+  // LOWERED_SPARSE comparator (sconv_lowered.hip): column buffer, grown on demand by the forward
+  escoin::DeviceBuffer col;
 
-  // LOWERED_SPARSE comparator (sconv_lowered.hip): column buffer, grown on demand
-  float *d_col = nullptr;
-  size_t col_bytes = 0;
-
-  size_t device_bytes = 0;
   std::string kernel_name = "(not aligned)";
 
-  // Backward (sconv_backward.hip): option "backward_kernel" and the state the first escoin_backward builds; released
-  // with the device side (free_device), so weight_align / set_csr / import_aligned drop it
+  // Backward (sconv_backward.hip): option "backward_kernel" and the state the first escoin_backward builds; reset with
+  // the device side (free_device), so weight_align / set_csr / import_aligned drop it
   int bwd_kernel = ESCOIN_KERNEL_AUTO;
-  escoin::BwdState *bwd = nullptr;
+  std::unique_ptr<escoin::BwdState> bwd;
 };
 
 namespace escoin {
@@ -214,17 +217,23 @@ int launch_generic_f64(const escoin_plan *p, const double *bottom, const double 
 const char *generic_kernel_name(bool relu);
 const char *generic_kernel_name_f64(bool relu);
 
-// escoin_capi.hip: the backward state's release (no-op without one), its "bwd_*" stats and device bytes (the
-// transposed plan's included).  sconv_backward.hip builds the state.
-void bwd_release(escoin_plan *p);
+// The values of a plan's Dtype: p->values (float) or p->values64 (double).
+template <typename T> std::vector<std::vector<T>> &plan_vals(escoin_plan *p);
+template <> inline std::vector<std::vector<float>> &plan_vals<float>(escoin_plan *p) { return p->values; }
+template <> inline std::vector<std::vector<double>> &plan_vals<double>(escoin_plan *p) { return p->values64; }
+
+// escoin_capi.hip: the device bytes a plan's owners hold -- the forward's (stat "device_bytes") and the backward
+// state's, its transposed plan's included (stat "bwd_device_bytes"); escoin_plan_workspace_bytes is their sum.
+struct DeviceBytes { size_t fwd, bwd; };
+DeviceBytes device_bytes(const escoin_plan *p);
+// sconv_backward.hip builds the backward state; escoin_capi.hip answers its "bwd_*" stats
 long bwd_stat(const escoin_plan *p, const char *key);
-size_t bwd_device_bytes(const escoin_plan *p);
 
 // sconv_tiled.hip
 bool tiled_supported(const Geometry &g);
 int tiled_device_cus();             // compute units of the current device
 int tiled_build(escoin_plan *p, hipStream_t stream, bool jit);  // fills p->tiled, uploads streams / loads generated code
-void tiled_release(escoin_plan *p);   // frees what tiled_build put on the device (and its share of device_bytes)
+void tiled_release(escoin_plan *p);   // resets p->tiled_dev and p->tiled
 // The fast half of escoin_plan_import_aligned: a generated-code plan restored from what
 // escoin_plan_export_aligned wrote (tiling, channel deal, unit table, code object) -- no channel
 // deal, no generator pass, no assembler.  `blob` points behind the CSR section.

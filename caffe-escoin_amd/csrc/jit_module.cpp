@@ -201,13 +201,11 @@ int jit_load_elf(const std::vector<char> &elf, size_t code_bytes, JitModule *out
   if (e == hipSuccess) e = hipMemcpyAsync(&addr, d_addr, sizeof(addr), hipMemcpyDeviceToHost, stream);
   if (e == hipSuccess) e = hipStreamSynchronize(stream);
   if (d_addr) (void)hipFree(d_addr);
-  if (e != hipSuccess || addr == 0) {
-    (void)hipModuleUnload(m.module);
+  if (e != hipSuccess || addr == 0)   // (m unloads the module)
     return fail(ESCOIN_EHIP, std::string("jit: locating the generated code failed: ") + hipGetErrorString(e));
-  }
   m.code_base = addr;
   m.code_bytes = code_bytes;
-  *out = m;
+  *out = std::move(m);
   return ESCOIN_OK;
 }
 
@@ -352,7 +350,7 @@ static int jit_load_direct(const uint32_t *code, size_t words, JitModule *out, h
   m.direct = exec;
   m.code_base = (unsigned long long)(uintptr_t)exec;
   m.code_bytes = bytes;
-  *out = m;
+  *out = std::move(m);
   return ESCOIN_OK;
 }
 
@@ -381,7 +379,7 @@ void jit_unload(JitModule *m) {
     (void)hipDeviceSynchronize();
     code_mem_free(m->direct);
   }
-  if (m) *m = JitModule();
+  if (m) m->forget();
 }
 
 }  // namespace escoin

@@ -5,15 +5,35 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+#include <utility>
 #include <vector>
 
 namespace escoin {
 
+struct JitModule;
+void jit_unload(JitModule *m);
+
+// Owns what jit_load put on the device: released (jit_unload) on destruction and when another module is moved in.
 struct JitModule {
   hipModule_t module = nullptr;       // code object loader: the loaded module ...
   void *direct = nullptr;             // ... or executable device memory the library filled itself (code_memory.h)
   unsigned long long code_base = 0;   // device address of the first byte of the generated code
   size_t code_bytes = 0;
+
+  JitModule() = default;
+  JitModule(JitModule &&o) noexcept { *this = std::move(o); }
+  JitModule &operator=(JitModule &&o) noexcept {
+    if (this == &o) return *this;
+    jit_unload(this);
+    module = o.module, direct = o.direct, code_base = o.code_base, code_bytes = o.code_bytes;
+    o.forget();
+    return *this;
+  }
+  ~JitModule() { jit_unload(this); }
+
+ private:
+  friend void jit_unload(JitModule *m);
+  void forget() { module = nullptr, direct = nullptr, code_base = 0, code_bytes = 0; }   // (what they named is released)
 };
 
 // (The library links libamd_comgr, a part of every ROCm install and what the HIP runtime itself loads
@@ -42,7 +62,6 @@ int jit_assemble(const std::vector<uint32_t> &code, std::vector<char> *elf);
 int jit_wrap(const std::vector<uint32_t> &code, std::vector<char> *elf);
 // Loads a code object jit_wrap / jit_assemble produced.
 int jit_load_elf(const std::vector<char> &elf, size_t code_bytes, JitModule *out, hipStream_t stream);
-void jit_unload(JitModule *m);
 
 }  // namespace escoin
 #endif

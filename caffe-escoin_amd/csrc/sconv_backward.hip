@@ -26,7 +26,7 @@
 //                                        total added into weight_diff / bias_diff.  Every position has one owner.
 //
 // The backward state (transposed CSR or transposed plan, slab, ReLU scratch) is built by the first backward on an
-// aligned plan and dropped with the device side (free_device: weight_align / set_csr / import_aligned / destroy); later
+// aligned plan and dropped with the device side (free_device: weight_align / set_csr / import_aligned; destroy); later
 // calls allocate nothing and synchronise nothing, so they can be captured into a graph.
 #include <hip/hip_runtime.h>
 
@@ -46,10 +46,6 @@ constexpr int kChunkPixels = kBwdChunkPixels;
 static_assert(kChunkPixels == 64 * kBwdWaves * kPixPerLane, "a chunk is one pixel per lane and step");
 constexpr int kEntryBatch = 64;                      // wgrad: entries reduced per barrier pair
 
-
-template <typename T> const std::vector<std::vector<T>> &plan_values_t(const escoin_plan *p);
-template <> const std::vector<std::vector<float>> &plan_values_t<float>(const escoin_plan *p) { return p->values; }
-template <> const std::vector<std::vector<double>> &plan_values_t<double>(const escoin_plan *p) { return p->values64; }
 
 template <typename T> __device__ inline T bfma(T a, T b, T c);
 template <> __device__ inline float bfma<float>(float a, float b, float c) { return fmaf(a, b, c); }
@@ -267,12 +263,10 @@ bool bwd_transposable(const escoin_plan *p) {
 }
 
 template <typename T>
-static int dev_upload(T **dst, const std::vector<T> &src, size_t *bytes, hipStream_t stream) {
-  const size_t n = std::max<size_t>(src.size(), 1);
-  ESCOIN_HIP_TRY(hipMalloc(dst, sizeof(T) * n));
-  *bytes += sizeof(T) * n;
+static int dev_upload(DeviceBuffer &dst, const std::vector<T> &src, hipStream_t stream) {
+  ESCOIN_HIP_TRY(dst.alloc(sizeof(T) * std::max<size_t>(src.size(), 1)));
   if (!src.empty())
-    ESCOIN_HIP_TRY(hipMemcpyAsync(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, stream));
+    ESCOIN_HIP_TRY(hipMemcpyAsync(dst.get<T>(), src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, stream));
   return ESCOIN_OK;
 }
 
@@ -287,15 +281,17 @@ static int build_transposed_plan(escoin_plan *p, BwdState *s, hipStream_t stream
   t.stride_h = t.stride_w = 1;
   t.has_bias = 0;
   t.fuse_relu = 0;
-  int rc = escoin_plan_create(&t, &s->tplan);
+  escoin_plan *tp = nullptr;
+  int rc = escoin_plan_create(&t, &tp);
+  s->tplan.reset(tp);
   if (rc != ESCOIN_OK) return rc;
   const int kk = d.KH * d.KW;
-  if (p->bwd_kernel != ESCOIN_KERNEL_AUTO && (rc = escoin_plan_set_option(s->tplan, "kernel", p->bwd_kernel)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(s->tplan, "tiling_batch", p->tiling_batch)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(s->tplan, "max_launch_bytes", (int)std::min<long>(p->max_launch_bytes, 0x7fffffff))) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(s->tplan, "dense_threshold_pct", p->dense_threshold_pct)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(s->tplan, "dense_gate", p->dense_gate)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(s->tplan, "code_loader", p->code_loader)) != ESCOIN_OK) return rc;
+  if (p->bwd_kernel != ESCOIN_KERNEL_AUTO && (rc = escoin_plan_set_option(tp, "kernel", p->bwd_kernel)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(tp, "tiling_batch", p->tiling_batch)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(tp, "max_launch_bytes", (int)std::min<long>(p->max_launch_bytes, 0x7fffffff))) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(tp, "dense_threshold_pct", p->dense_threshold_pct)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(tp, "dense_gate", p->dense_gate)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(tp, "code_loader", p->code_loader)) != ESCOIN_OK) return rc;
   // CSR': row = input channel icl of a group, entry (ocl, icl, kr, kc) -> colidx' = ocl*KH*KW + (KH-1-kr)*KW + (KW-1-kc),
   // ascending within the row
   std::vector<int> rowptr((size_t)d.group * (g.Cg + 1)), colidx, nnz_g(d.group);
@@ -319,9 +315,9 @@ static int build_transposed_plan(escoin_plan *p, BwdState *s, hipStream_t stream
     }
     nnz_g[grp] = trp[g.Cg];
   }
-  rc = escoin_plan_set_csr(s->tplan, rowptr.data(), colidx.data(), vals.data(), nnz_g.data(), stream);
+  rc = escoin_plan_set_csr(tp, rowptr.data(), colidx.data(), vals.data(), nnz_g.data(), stream);
   if (rc != ESCOIN_OK) return rc;
-  s->data_kernel = (int)escoin_plan_stat(s->tplan, "kernel_choice");
+  s->data_kernel = (int)escoin_plan_stat(tp, "kernel_choice");
   return ESCOIN_OK;
 }
 
@@ -348,11 +344,9 @@ static int build_gather(escoin_plan *p, BwdState *s, const std::vector<std::vect
         tval[at] = values[grp][j];
       }
   }
-  int rc = dev_upload(&s->d_trow, trow, &s->device_bytes, stream);
-  if (rc == ESCOIN_OK) rc = dev_upload(&s->d_ttap, ttap, &s->device_bytes, stream);
-  T *tv = nullptr;
-  if (rc == ESCOIN_OK) rc = dev_upload(&tv, tval, &s->device_bytes, stream);
-  s->d_tval = tv;
+  int rc = dev_upload(s->trow, trow, stream);
+  if (rc == ESCOIN_OK) rc = dev_upload(s->ttap, ttap, stream);
+  if (rc == ESCOIN_OK) rc = dev_upload(s->tval, tval, stream);
   if (rc != ESCOIN_OK) return rc;
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
   return ESCOIN_OK;
@@ -371,8 +365,8 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   if (forced && !transposable)
     return fail(ESCOIN_EINVAL, "backward_kernel: this plan has no transposed forward plan (needs a float plan, stride 1, "
                                "pad <= dilation * (kernel - 1)); only the gather kernel serves it");
-  BwdState *s = new BwdState();
-  p->bwd = s;
+  p->bwd.reset(new BwdState());
+  BwdState *s = p->bwd.get();
   for (const auto &c : p->colidx) s->nnz += (long)c.size();
   if (s->nnz > 0x7fffffffL) return fail(ESCOIN_EINVAL, "backward: more than 2^31 nonzeros");
   int rc = ESCOIN_OK;
@@ -380,12 +374,11 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
     rc = build_transposed_plan(p, s, stream);
     if (rc == ESCOIN_OK && d.fuse_relu) {
       const size_t bytes = sizeof(float) * (size_t)d.N * d.M * g.OH * g.OW;
-      ESCOIN_HIP_TRY(hipMalloc(&s->d_g, bytes));
-      s->device_bytes += bytes;
+      ESCOIN_HIP_TRY(s->g.alloc(bytes));
     }
   } else {
     s->data_kernel = ESCOIN_KERNEL_GENERIC;
-    rc = build_gather<T>(p, s, plan_values_t<T>(p), stream);
+    rc = build_gather<T>(p, s, plan_vals<T>(p), stream);
   }
   if (rc != ESCOIN_OK) return rc;
   std::vector<int> wpos((size_t)s->nnz);
@@ -394,12 +387,11 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
     for (int m = 0; m < g.Mg; ++m)
       for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j)
         wpos[e++] = (grp * g.Mg + m) * g.kdim + p->colidx[grp][j];
-  rc = dev_upload(&s->d_wpos, wpos, &s->device_bytes, stream);
+  rc = dev_upload(s->wpos, wpos, stream);
   if (rc != ESCOIN_OK) return rc;
   s->chunks_max = (int)(((long)d.N * g.OH * g.OW + kChunkPixels - 1) / kChunkPixels);
   const size_t slab = sizeof(T) * (size_t)s->chunks_max * (size_t)(s->nnz + d.M);
-  ESCOIN_HIP_TRY(hipMalloc(&s->d_slab, slab));
-  s->device_bytes += slab;
+  ESCOIN_HIP_TRY(s->slab.alloc(slab));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
   s->align_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return ESCOIN_OK;
@@ -428,11 +420,11 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
   if (!p->bwd) {
     const int rc = bwd_build<T>(p, stream);
     if (rc != ESCOIN_OK) {
-      bwd_release(p);
+      p->bwd.reset();
       return rc;
     }
   }
-  BwdState *s = p->bwd;
+  BwdState *s = p->bwd.get();
   if (n_images == 0) return ESCOIN_OK;
   const bool relu = d.fuse_relu != 0;
   if (bottom_diff) {
@@ -443,16 +435,16 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
         const unsigned blocks = (unsigned)std::min<size_t>((count + 255) / 256, 8192);
         hipLaunchKernelGGL(escoin_sconv_bwd_relu_mask_kernel, dim3(blocks), dim3(256), 0, stream,
                            reinterpret_cast<const float *>(top_diff), reinterpret_cast<const float *>(top),
-                           static_cast<float *>(s->d_g), count);
+                           s->g.get<float>(), count);
         ESCOIN_HIP_TRY(hipGetLastError());
-        src = static_cast<const float *>(s->d_g);
+        src = s->g.get<const float>();
       }
-      const int rc = escoin_forward(s->tplan, src, nullptr, reinterpret_cast<float *>(bottom_diff), n_images, stream);
+      const int rc = escoin_forward(s->tplan.get(), src, nullptr, reinterpret_cast<float *>(bottom_diff), n_images, stream);
       if (rc != ESCOIN_OK) return rc;
     } else {
       BwdDataArgs<T> a;
       a.top_diff = top_diff; a.top = top; a.bottom_diff = bottom_diff;
-      a.trow = s->d_trow; a.ttap = s->d_ttap; a.tval = static_cast<const T *>(s->d_tval);
+      a.trow = s->trow.get<int>(); a.ttap = s->ttap.get<int>(); a.tval = s->tval.get<T>();
       a.C = d.C; a.H = d.H; a.W = d.W; a.M = d.M; a.OH = g.OH; a.OW = g.OW;
       a.pad_h = d.pad_h; a.pad_w = d.pad_w; a.stride_h = d.stride_h; a.stride_w = d.stride_w;
       a.dil_h = d.dil_h; a.dil_w = d.dil_w; a.Cg = g.Cg; a.Mg = g.Mg;
@@ -471,11 +463,11 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
     const long total = (long)n_images * g.OH * g.OW;
     const int chunks = (int)((total + kChunkPixels - 1) / kChunkPixels);
     s->last_chunks = chunks;
-    T *slab_w = static_cast<T *>(s->d_slab);
+    T *slab_w = s->slab.get<T>();
     T *slab_b = slab_w + (size_t)s->chunks_max * (size_t)s->nnz;
     WgradArgs<T> a;
     a.bottom = bottom; a.top_diff = top_diff; a.top = top;
-    a.rowptr = p->d_rowptr; a.taps = p->d_taps;
+    a.rowptr = p->gen.rowptr.get<int>(); a.taps = p->gen.taps.get<int>();
     a.slab_w = slab_w; a.slab_b = slab_b;
     a.total = total; a.nnz = (int)s->nnz;
     a.C = d.C; a.H = d.H; a.W = d.W; a.M = d.M; a.OH = g.OH; a.OW = g.OW;
@@ -497,10 +489,10 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
     if (lanes > 0) {
       const dim3 sgrid((unsigned)((lanes + 255) / 256));
       if constexpr (sizeof(T) == 8)
-        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_f64_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, s->d_wpos,
+        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_f64_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, s->wpos.get<int>(),
                            weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
       else
-        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, s->d_wpos,
+        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, s->wpos.get<int>(),
                            weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
       ESCOIN_HIP_TRY(hipGetLastError());
     }

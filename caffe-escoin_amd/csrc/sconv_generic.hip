@@ -95,15 +95,15 @@ const char *generic_kernel_name_f64(bool relu) {
 }
 
 template <typename T>
-static int launch_generic_t(const escoin_plan *p, const T *vals, const T *bottom, const T *bias, T *top, int n_images,
+static int launch_generic_t(const escoin_plan *p, const T *bottom, const T *bias, T *top, int n_images,
                             hipStream_t stream) {
   const Geometry &g = p->g;
   GenericArgs<T> a;
   a.in = bottom;
   a.out = top;
-  a.rowptr = p->d_rowptr;
-  a.taps = p->d_taps;
-  a.vals = vals;
+  a.rowptr = p->gen.rowptr.get<int>();
+  a.taps = p->gen.taps.get<int>();
+  a.vals = p->gen.vals.get<T>();
   a.bias = bias;
   a.C = g.d.C; a.H = g.d.H; a.W = g.d.W; a.M = g.d.M; a.OH = g.OH; a.OW = g.OW;
   a.pad_h = g.d.pad_h; a.pad_w = g.d.pad_w; a.stride_h = g.d.stride_h; a.stride_w = g.d.stride_w;
@@ -131,11 +131,11 @@ static int launch_generic_t(const escoin_plan *p, const T *vals, const T *bottom
 
 int launch_generic(const escoin_plan *p, const float *bottom, const float *bias, float *top, int n_images,
                    hipStream_t stream) {
-  return launch_generic_t<float>(p, p->d_vals, bottom, bias, top, n_images, stream);
+  return launch_generic_t<float>(p, bottom, bias, top, n_images, stream);
 }
 int launch_generic_f64(const escoin_plan *p, const double *bottom, const double *bias, double *top, int n_images,
                        hipStream_t stream) {
-  return launch_generic_t<double>(p, p->d_vals64, bottom, bias, top, n_images, stream);
+  return launch_generic_t<double>(p, bottom, bias, top, n_images, stream);
 }
 
 // ------------------------------------------------------------------------------------

@@ -161,17 +161,8 @@ int launch_lowered(escoin_plan *p, const float *bottom, const float *bias, float
   if (!pointwise) {
     chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_images, kColBytes / per_image));
     const size_t need = per_image * chunk;
-    if (p->col_bytes < need) {
-      // the plan never holds a size for a buffer it no longer has: a failed hipMalloc leaves
-      // d_col = nullptr AND col_bytes = 0, so a later, smaller forward allocates again
-      if (p->d_col) (void)hipFree(p->d_col);
-      p->d_col = nullptr;
-      p->device_bytes -= p->col_bytes;
-      p->col_bytes = 0;
-      ESCOIN_HIP_TRY(hipMalloc(&p->d_col, need));
-      p->device_bytes += need;
-      p->col_bytes = need;
-    }
+    // (a failed allocation leaves the buffer empty: a later, smaller forward allocates again)
+    if (p->col.bytes() < need) ESCOIN_HIP_TRY(p->col.alloc(need));
   }
   const long in_image = (long)g.d.C * g.d.H * g.d.W, out_image = (long)g.d.M * npix;
   for (int n0 = 0; n0 < n_images; n0 += chunk) {
@@ -182,7 +173,7 @@ int launch_lowered(escoin_plan *p, const float *bottom, const float *bias, float
       long b_stride = in_image;
       if (!pointwise) {
         Im2colArgs ia;
-        ia.in = in_g; ia.col = p->d_col; ia.Cg = g.Cg; ia.H = g.d.H; ia.W = g.d.W; ia.KH = g.d.KH;
+        ia.in = in_g; ia.col = p->col.get<float>(); ia.Cg = g.Cg; ia.H = g.d.H; ia.W = g.d.W; ia.KH = g.d.KH;
         ia.KW = g.d.KW; ia.OH = g.OH; ia.OW = g.OW; ia.pad_h = g.d.pad_h; ia.pad_w = g.d.pad_w;
         ia.stride_h = g.d.stride_h; ia.stride_w = g.d.stride_w; ia.dil_h = g.d.dil_h; ia.dil_w = g.d.dil_w;
         ia.in_stride = in_image;
@@ -190,11 +181,11 @@ int launch_lowered(escoin_plan *p, const float *bottom, const float *bias, float
         if (grid.y > 65535u || grid.z > 65535u) return fail(ESCOIN_EINVAL, "im2col: grid dimension exceeds 65535");
         hipLaunchKernelGGL(escoin_im2col_kernel, grid, dim3(256), 0, stream, ia);
         ESCOIN_HIP_TRY(hipGetLastError());
-        B = p->d_col;
+        B = p->col.get<float>();
         b_stride = (long)g.kdim * npix;
       }
       CsrmmArgs a;
-      a.vals = p->d_vals; a.rowptr = p->d_rowptr + (size_t)grp * g.Mg; a.colidx = p->d_taps;
+      a.vals = p->gen.vals.get<float>(); a.rowptr = p->gen.rowptr.get<int>() + (size_t)grp * g.Mg; a.colidx = p->gen.taps.get<int>();
       a.B = B; a.C = top + (size_t)n0 * out_image + (size_t)grp * g.Mg * npix;
       a.bias = bias ? bias + (size_t)grp * g.Mg : nullptr;
       a.M = g.Mg; a.N = npix; a.K = g.kdim; a.taps = 1; a.KH = g.d.KH; a.KW = g.d.KW;

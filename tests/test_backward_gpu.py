@@ -217,7 +217,7 @@ def test_determinism_memory_and_realign(pkg, dev, synth):
         # re-align with new weights: the state is rebuilt and the gradients are the new weights'
         w2 = synth.pruned_weights(s, 65)
         plan.weight_align(w2)
-        assert plan.stat("bwd_device_bytes") == 0
+        assert plan.stat("bwd_device_bytes") == 0 and plan.workspace_bytes == plan.stat("device_bytes")
         bd, wd, _ = plan.backward(td, bottom=xt, weight_diff=True)
         torch.cuda.synchronize()
         want_bd, want_wd, _ = torch_backward(x, w2, None, s, td.cpu().numpy())

@@ -397,8 +397,23 @@ def test_weight_align_from_device_and_csr_roundtrip(pkg, oracle, synth, torch_cu
     c = p2.forward(xd, bd).cpu().numpy()
     assert np.array_equal(a, c)
     assert p1.workspace_bytes > 0
+    # the device bytes are those of what the plan holds: the same after a second align of the same weights, after a
+    # conv_mode flip to LOWERED_GEMM and back, and on a plan that imported p1's aligned form
+    def held(p):
+        return p.stat("device_bytes"), p.workspace_bytes
+    before = held(p1)
+    assert before[0] == before[1]
+    p1.weight_align(w)
+    assert held(p1) == before
+    p1.set_option("conv_mode", pkg.CONV_MODE_LOWERED_GEMM)
+    p1.set_option("conv_mode", pkg.CONV_MODE_SCONV_PAR)
+    assert held(p1) == before
+    p3 = pkg.Plan(pkg.ConvDesc.from_shape(s))
+    p3.import_aligned(p1.export_aligned())
+    assert held(p3) == before
     p1.close()
     p2.close()
+    p3.close()
 
 
 def test_math_functions_level_dropins(pkg, oracle, synth, torch_cuda):
