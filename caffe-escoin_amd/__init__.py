@@ -44,6 +44,9 @@ API_SYMBOLS = [
     "escoin_cpu_sparse_dense2csr", "escoin_cpu_sparse_dense2csr_f64",
     # Backward (pattern-preserving)
     "escoin_backward", "escoin_backward_f64", "escoin_backward_cpu", "escoin_backward_cpu_f64",
+    # Weight updates in place
+    "escoin_update_values", "escoin_update_values_f64", "escoin_plan_set_values", "escoin_plan_set_values_f64",
+    "escoin_update_values_cpu", "escoin_update_values_cpu_f64",
 ]
 
 
@@ -164,6 +167,12 @@ def lib():
     for name in ("escoin_backward", "escoin_backward_f64", "escoin_backward_cpu", "escoin_backward_cpu_f64"):
         f = getattr(L, name)
         f.restype, f.argtypes = ip, [vp] * 7 + [ip, vp if "cpu" not in name else ip]
+    for name in ("escoin_update_values", "escoin_update_values_f64", "escoin_plan_set_values", "escoin_plan_set_values_f64"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = ip, [vp, vp, ip, vp]
+    for name in ("escoin_update_values_cpu", "escoin_update_values_cpu_f64"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = ip, [vp, vp]
     L.escoin_cpu_kernel_name.restype = cp
     L.escoin_cpu_kernel_name.argtypes = []
     L.escoin_cpu_kernel_select.restype = ip
@@ -244,6 +253,37 @@ class Plan(object):
             assert w.is_cuda and w.dtype.is_floating_point and w.element_size() in (4, 8)
             fn = lib().escoin_weight_align_f64 if w.element_size() == 8 else lib().escoin_weight_align
             check(fn(self._h, C.c_void_p(w.data_ptr()), 1, stream), "escoin_weight_align")
+
+    # ---- weight updates in place (include/escoin.h "Weight updates") -----------------------------------------------------
+    def _update(self, a, dense, stream):
+        base = "escoin_update_values" if dense else "escoin_plan_set_values"
+        if isinstance(a, np.ndarray):
+            f64 = a.dtype == np.float64
+            w = np.ascontiguousarray(a, np.float64 if f64 else np.float32)
+            check(getattr(lib(), base + ("_f64" if f64 else ""))(self._h, _np_ptr(w), 0, stream), base)
+            return
+        import torch
+        w = a.contiguous()
+        assert w.is_cuda and w.dtype in (torch.float32, torch.float64)
+        if stream is None:
+            stream = C.c_void_p(torch.cuda.current_stream(w.device).cuda_stream)
+        check(getattr(lib(), base + ("_f64" if w.element_size() == 8 else ""))(self._h, C.c_void_p(w.data_ptr()), 1, stream), base)
+
+    def update_values(self, dense_w, stream=None):
+        """New weights at the old pattern, in place.  dense_w: blobs_[0] as numpy (host) or a torch CUDA tensor (device:
+        asynchronous on `stream`, default torch's current stream); read at the plan's CSR positions only."""
+        self._update(dense_w, True, stream)
+
+    def set_values(self, values, stream=None):
+        """The same from the compact value array (nnz elements in get_csr()'s order), numpy or torch CUDA."""
+        self._update(values, False, stream)
+
+    def update_values_cpu(self, dense_w):
+        """update_values for a plan aligned by weight_align_cpu (host CSR only); float32 or float64 numpy."""
+        f64 = dense_w.dtype == np.float64
+        w = np.ascontiguousarray(dense_w, np.float64 if f64 else np.float32)
+        fn = lib().escoin_update_values_cpu_f64 if f64 else lib().escoin_update_values_cpu
+        check(fn(self._h, _np_ptr(w)), "escoin_update_values_cpu")
 
     # ---- Caffe::CPU mode (no device needed) ----------------------------------------------------
     def weight_align_cpu(self, dense_w):

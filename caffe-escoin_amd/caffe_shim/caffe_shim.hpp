@@ -110,6 +110,8 @@ template <> struct EscApi<float> {
   static int forward_cpu(escoin_plan *p, const float *b, const float *bias, float *t, int n, int threads) { return escoin_forward_cpu(p, b, bias, t, n, threads); }
   static int backward(escoin_plan *p, const float *b, const float *t, const float *td, float *bd, float *wd, float *bsd, int n, void *s) { return escoin_backward(p, b, t, td, bd, wd, bsd, n, s); }
   static int backward_cpu(escoin_plan *p, const float *b, const float *t, const float *td, float *bd, float *wd, float *bsd, int n, int threads) { return escoin_backward_cpu(p, b, t, td, bd, wd, bsd, n, threads); }
+  static int update_values(escoin_plan *p, const float *w, int on_dev, void *s) { return escoin_update_values(p, w, on_dev, s); }
+  static int update_values_cpu(escoin_plan *p, const float *w) { return escoin_update_values_cpu(p, w); }
 };
 template <> struct EscApi<double> {
   static int weight_align(escoin_plan *p, const double *w, int on_dev, void *s) { return escoin_weight_align_f64(p, w, on_dev, s); }
@@ -118,6 +120,8 @@ template <> struct EscApi<double> {
   static int forward_cpu(escoin_plan *p, const double *b, const double *bias, double *t, int n, int threads) { return escoin_forward_cpu_f64(p, b, bias, t, n, threads); }
   static int backward(escoin_plan *p, const double *b, const double *t, const double *td, double *bd, double *wd, double *bsd, int n, void *s) { return escoin_backward_f64(p, b, t, td, bd, wd, bsd, n, s); }
   static int backward_cpu(escoin_plan *p, const double *b, const double *t, const double *td, double *bd, double *wd, double *bsd, int n, int threads) { return escoin_backward_cpu_f64(p, b, t, td, bd, wd, bsd, n, threads); }
+  static int update_values(escoin_plan *p, const double *w, int on_dev, void *s) { return escoin_update_values_f64(p, w, on_dev, s); }
+  static int update_values_cpu(escoin_plan *p, const double *w) { return escoin_update_values_cpu_f64(p, w); }
 };
 
 // syncedmem.hpp:56-91: lazily mirrored host/device buffer with a head state.
@@ -254,6 +258,9 @@ class Layer {   // layer.hpp:33-475
   virtual void LayerSetUp(const vector<Blob<Dtype> *> &, const vector<Blob<Dtype> *> &) {}
   virtual void Reshape(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &top) = 0;
   virtual void WeightAlign() {}   // layer.hpp:97-98, called by Net::CopyTrainedLayersFrom (net.cpp:819)
+  // What a solver calls after ApplyUpdate (Net::Update, net.cpp) on every layer: the learnable blobs changed, the
+  // sparsity pattern did not.  The reference has no counterpart -- it would have to WeightAlign again.
+  virtual void WeightUpdate() {}
   // layer.hpp:435-475: Reshape every call, mode switch, per-layer forward time in microseconds
   inline Dtype Forward(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &top) {
     Reshape(bottom, top);
@@ -402,6 +409,25 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       aligned_on_device_ = false;
     }
     aligned_ = true;
+  }
+
+  // After a solver step that kept the pattern (the masked gradient of Backward does): the new values of blobs_[0] go
+  // into the aligned plan in place (include/escoin.h, "Weight updates") -- no CSR rebuild, no code generation, no
+  // allocation, the backward state stays.  GPU mode reads the device blob, asynchronously on Caffe::stream(); CPU mode
+  // the host blob, and updates the device side too if the plan has one.  A layer that is not aligned yet, or that was
+  // aligned in CPU mode and now runs in GPU mode, aligns.
+  virtual void WeightUpdate() {
+    ESC_CHECK(plan_ != nullptr);
+    if (!aligned_ || (Caffe::mode() == Caffe::GPU && !aligned_on_device_)) {
+      WeightAlign();
+      return;
+    }
+    if (Caffe::mode() == Caffe::GPU)
+      ESCOIN_CHECK(EscApi<Dtype>::update_values(plan_, this->blobs_[0]->gpu_data(), 1, Caffe::stream()));
+    else if (aligned_on_device_)
+      ESCOIN_CHECK(EscApi<Dtype>::update_values(plan_, this->blobs_[0]->cpu_data(), 0, Caffe::stream()));
+    else
+      ESCOIN_CHECK(EscApi<Dtype>::update_values_cpu(plan_, this->blobs_[0]->cpu_data()));
   }
 
   // The aligned form as one byte blob (CSR + channel deal + unit table + code object), and WeightAlign from such

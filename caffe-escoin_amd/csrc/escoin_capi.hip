@@ -70,7 +70,9 @@ DeviceBytes device_bytes(const escoin_plan *p) {
   const DenseArrays &dn = p->dense;
   DeviceBytes b{p->gen.rowptr.bytes() + p->gen.taps.bytes() + p->gen.vals.bytes() + t.stream.bytes() + t.unit_hdr.bytes() +
                     t.chan.bytes() + t.jit.code_bytes + dn.w.bytes() + dn.ktab.bytes() + dn.sk_ws.bytes() + p->col.bytes(),
-                0};
+                0, 0};
+  if (const UpdState *u = p->upd.get())
+    b.upd = u->src.bytes() + u->off.bytes() + u->buf.bytes() + u->wpos.bytes() + u->stage.bytes();
   if (const BwdState *s = p->bwd.get())
     b.bwd = s->trow.bytes() + s->ttap.bytes() + s->tval.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() +
             (s->tplan ? device_bytes(s->tplan.get()).fwd : 0);
@@ -89,7 +91,22 @@ long bwd_stat(const escoin_plan *p, const char *key) {
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
 
+int sync_host_values(escoin_plan *p) {
+  if (!p || !p->dev_authoritative || !p->sync_host_fn) return ESCOIN_OK;
+  return p->sync_host_fn(p);
+}
+
+long upd_stat(const escoin_plan *p, const char *key) {
+  if (!strcmp(key, "update_fast")) return p->upd_last_fast;
+  if (!strcmp(key, "update_count")) return p->upd_count;
+  if (!strcmp(key, "update_destinations")) return p->upd ? p->upd->n_dst : 0;
+  if (!strcmp(key, "upd_device_bytes")) return (long)device_bytes(p).upd;
+  return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
+}
+
 static void free_device(escoin_plan *p) {
+  p->upd.reset();
+  p->dev_authoritative = false;
   p->bwd.reset();
   p->gen = GenericArrays();
   tiled_release(p);
@@ -333,6 +350,8 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
 }
 
 
+int realign_from_host_csr(escoin_plan *p, hipStream_t stream) { return upload(p, stream); }
+
 template <typename T>
 void csr_from_dense(escoin_plan *p, const T *w) {
   const Geometry &g = p->g;
@@ -410,6 +429,7 @@ static int get_csr_t(const escoin_plan *p, int *rowptr, int *colidx, T *values, 
   if (values && p->host_aligned && p->is_f64 != (sizeof(T) == 8))
     return fail(ESCOIN_ESTATE, p->is_f64 ? "get_csr: the plan holds double values (use escoin_plan_get_csr_f64)"
                                          : "get_csr_f64: the plan holds float values (use escoin_plan_get_csr)");
+  if (const int rc = sync_host_values(const_cast<escoin_plan *>(p))) return rc;
   const Geometry &g = p->g;
   const std::vector<std::vector<T>> &vals = plan_vals<T>(const_cast<escoin_plan *>(p));
   long base = 0;
@@ -551,6 +571,8 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
         int dev = -1;
         if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
           return fail(ESCOIN_ESTATE, "conv_mode flip on an aligned plan: the current device is not the plan's device");
+        // (after device-source updates the host CSR the rebuild reads is stale: the values come back first)
+        if (const int rcs = sync_host_values(p)) return rcs;
         p->aligned = false;
         return upload(p, nullptr);
       }
@@ -682,6 +704,7 @@ int escoin_plan_export_aligned(const escoin_plan *p, void *buf, size_t capacity,
     if (!p || !bytes) return fail(ESCOIN_EINVAL, "null argument");
     if (!p->aligned) return fail(ESCOIN_ESTATE, "export_aligned before weight_align / set_csr");
     if (p->is_f64) return fail(ESCOIN_ESTATE, "export_aligned: the aligned form is defined for float plans (a double plan has no generated code to persist; hand its CSR over with escoin_plan_get_csr_f64 / set_csr_f64)");
+    if (const int rcs = sync_host_values(const_cast<escoin_plan *>(p))) return rcs;
     const Geometry &g = p->g;
     std::vector<char> jit;
     const int rc = tiled_export(p, &jit);
@@ -821,6 +844,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   }
   if (!strcmp(key, "streamk")) return p->dense.sk_used ? 1 : 0;
   if (!strncmp(key, "bwd_", 4)) return bwd_stat(p, key);
+  if (!strncmp(key, "upd", 3)) return upd_stat(p, key);
   if (!strcmp(key, "is_f64")) return p->is_f64 ? 1 : 0;
   if (!strcmp(key, "host_aligned")) return p->host_aligned ? 1 : 0;
   if (!strcmp(key, "kernel_choice")) {
@@ -853,7 +877,7 @@ int escoin_plan_get_csr_f64(const escoin_plan *p, int *rowptr, int *colidx, doub
 size_t escoin_plan_workspace_bytes(const escoin_plan *p) {
   if (!p) return 0;
   const DeviceBytes b = device_bytes(p);
-  return b.fwd + b.bwd;
+  return b.fwd + b.bwd + b.upd;
 }
 
 const char *escoin_plan_kernel_name(const escoin_plan *p) {

@@ -104,6 +104,24 @@ struct BwdState {
   long nnz = 0;
   int chunks_max = 0, last_chunks = 0;
   double align_ms = 0.0;
+  // host: per entry of the transposed order (tplan's CSR, or ttap / tval) the index of the plan's CSR entry (groups
+  // concatenated) it is a copy of -- how escoin_update_values reaches the backward state's values (update_values.hip)
+  std::vector<int> tsrc;
+};
+
+// What the first escoin_update_values on an alignment builds (update_values.hip); reset with the device side.  One flat
+// scatter list over every device word that holds a weight of this alignment: destination k receives the value of CSR
+// entry src[k] at element off[k] (elements of the plan's Dtype) of buffer buf[k].
+constexpr int kUpdMaxBuffers = 8;
+struct UpdState {
+  DeviceBuffer src, off, buf;   // [n_dst] int32 / uint32 / uint8, sorted by (buffer, CSR entry)
+  DeviceBuffer wpos;            // [nnz] per CSR entry: its position in blobs_[0] (oc * kdim + colidx)
+  DeviceBuffer stage;           // [nnz] compact values of a host-source update on their way to the kernel
+  void *base[kUpdMaxBuffers] = {};
+  int n_buffers = 0;
+  long n_dst = 0, nnz = 0;
+  bool has_bwd = false;         // the list covers the backward state's copies (rebuilt once when that state appears later)
+  std::vector<char> h_stage;    // host side of `stage`
 };
 
 // The generic kernel's device CSR (escoin_capi.hip upload): rowptr [M + 1] absolute offsets into taps / vals; taps and
@@ -116,6 +134,9 @@ struct TiledArrays {
   DeviceBuffer unit_hdr;   // 8 dwords per (conv group, oc group, ic block); generated code: 1 (code offset)
   DeviceBuffer chan;       // slot -> output channel (WeightStream::chan)
   JitModule jit;           // generated-code kernel: where the plan's code lives on the device (jit_module.h)
+  // host: [conv group][index in colidx] -> the word of the stream / of the generated code that holds the value
+  // (WeightStream::val_word, jit::Program::val_word); empty for a plan restored by the fast import
+  std::vector<std::vector<uint32_t>> val_word;
   // host copies of what a generated-code plan loaded, kept for escoin_plan_export_aligned: the code
   // (position-independent words, jit_codegen.h), the unit table and the channel deal
   std::vector<uint32_t> jit_code, h_unit_off, h_chan;
@@ -200,6 +221,16 @@ struct escoin_plan {
   // the device side (free_device), so weight_align / set_csr / import_aligned drop it
   int bwd_kernel = ESCOIN_KERNEL_AUTO;
   std::unique_ptr<escoin::BwdState> bwd;
+
+  // In-place weight updates (update_values.hip): the state the first escoin_update_values builds; reset with the device
+  // side.  From a device-source update until the next align (or host-source update) the DEVICE holds the plan's values
+  // and the host mirrors are stale: whatever reads weights from the host calls sync_host_values first.
+  std::unique_ptr<escoin::UpdState> upd;
+  bool dev_authoritative = false;
+  int (*sync_host_fn)(escoin_plan *) = nullptr;   // set with dev_authoritative: the read-back (update_values.hip)
+  hipStream_t upd_stream = nullptr;   // the stream of the last device-source update
+  int upd_last_fast = 0;              // stat "update_fast"
+  long upd_count = 0;                 // stat "update_count": updates since the plan was created
 };
 
 namespace escoin {
@@ -224,8 +255,20 @@ template <> inline std::vector<std::vector<double>> &plan_vals<double>(escoin_pl
 
 // escoin_capi.hip: the device bytes a plan's owners hold -- the forward's (stat "device_bytes") and the backward
 // state's, its transposed plan's included (stat "bwd_device_bytes"); escoin_plan_workspace_bytes is their sum.
-struct DeviceBytes { size_t fwd, bwd; };
+struct DeviceBytes { size_t fwd, bwd, upd; };
 DeviceBytes device_bytes(const escoin_plan *p);
+// escoin_capi.hip: the shared tail of weight_align / set_csr -- rebuilds the device side from the host CSR
+int realign_from_host_csr(escoin_plan *p, hipStream_t stream);
+// escoin_capi.hip: brings the host mirrors (CSR values, the kept copy of the generated code, the transposed plan's) up
+// to date after device-source updates -- through escoin_plan::sync_host_fn, which the update that made the device
+// authoritative left (the host-only translation units do not depend on update_values.hip); a no-op otherwise.  Waits
+// for the update's stream.
+int sync_host_values(escoin_plan *p);
+long upd_stat(const escoin_plan *p, const char *key);
+// whether group `grp` of the plan runs on the dense kernel (its units in the stream / generated code are empty)
+inline bool group_is_dense(const escoin_plan *p, int grp) {
+  return p->n_dense_groups > 0 && (grp >= 64 || ((p->dense_mask >> grp) & 1ull));
+}
 // sconv_backward.hip builds the backward state; escoin_capi.hip answers its "bwd_*" stats
 long bwd_stat(const escoin_plan *p, const char *key);
 

@@ -46,7 +46,10 @@ namespace {
 struct Rec {
   uint32_t bits;   // the weight
   int idx;         // accumulator quad: gl * KW + kc
+  int entry;       // the CSR entry it came from: index into the conv group's colidx / values
 };
+// Where a unit put a CSR entry's value: the word of the code vector that holds it (Program::val_word).
+struct ValAt { int entry; size_t word; };
 struct Row {
   uint32_t lds_off;
   std::vector<Rec> recs;
@@ -81,8 +84,9 @@ struct Lds {
 // blk / n_icb: which block of its oc-group's chain this unit is (chaining only).
 // n_idx: accumulator quads per tile the epilogue reads (channels per wave x kernel columns): block 0's unit leaves
 // every one of them initialised (jit_codegen.h: the code initialises its accumulators).
+// val_at: every record's value word is appended -- the literal of its s_mov_b32 or its slot in the weight lines.
 size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const std::vector<Piece> &pieces,
-                 const Options &opt_in, int n_pref, int wave, int blk, int n_icb, int n_idx) {
+                 const Options &opt_in, int n_pref, int wave, int blk, int n_icb, int n_idx, std::vector<ValAt> *val_at) {
   Options opt = opt_in;
   if (opt.prio_waves > 0 && (wave < 0 || wave >= opt.prio_waves)) opt.prio_rows = 0;
   size_t patch = 0;
@@ -234,7 +238,12 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
   }
   first_of_row[n] = (int)flat.size();
   auto sreg = [](int j) { return (j & 1) ? kSWeight1 : kSWeight0; };
-  if (!sw && !flat.empty()) enc_s_mov_lit(c, sreg(0), flat[0]->bits);
+  // (a value is always the full 32-bit literal behind its move -- never an inline constant --: its word is the last one)
+  auto mov_weight = [&](int j) {
+    enc_s_mov_lit(c, sreg(j), flat[j]->bits);
+    val_at->push_back({flat[j]->entry, c.size() - 1});
+  };
+  if (!sw && !flat.empty()) mov_weight(0);
   int prio = 0;
   // (sweights) the switch to weight line L: everything outstanding lands -- the line, loaded a line ago, and the LDS
   // reads in flight --, then the line after it is requested into the other buffer
@@ -260,7 +269,7 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
       if (sw) {
         if (j > j0 && slot_of[j] == 0) switch_line(line_of[j]);     // (a row of more than 16 nonzeros)
       } else if (j + 1 < (int)flat.size()) {
-        enc_s_mov_lit(c, sreg(j + 1), flat[j + 1]->bits);
+        mov_weight(j + 1);
       }
       const int a = 4 * flat[j]->idx;
       const bool first = init_acc && fresh[(size_t)flat[j]->idx];     // the quad's first product: multiply, do not accumulate
@@ -326,7 +335,10 @@ size_t emit_unit(std::vector<uint32_t> &c, const std::vector<Row> &rows, const s
     const long long dist = (long long)(c.size() * 4) - (long long)sw_from;
     c[sw_patch] = (uint32_t)dist;
     std::vector<uint32_t> lines((size_t)n_lines * kSWLine, 0u);
-    for (size_t j = 0; j < flat.size(); ++j) lines[(size_t)line_of[j] * kSWLine + slot_of[j]] = flat[j]->bits;
+    for (size_t j = 0; j < flat.size(); ++j) {
+      lines[(size_t)line_of[j] * kSWLine + slot_of[j]] = flat[j]->bits;
+      val_at->push_back({flat[j]->entry, c.size() + (size_t)line_of[j] * kSWLine + slot_of[j]});
+    }
     c.insert(c.end(), lines.begin(), lines.end());
   }
   return patch;       // (chained: the next unit follows; alignment padding is s_nop)
@@ -344,6 +356,7 @@ struct ChainOut {
   bool overflow = false;
   size_t max_unit = 0;
   std::vector<double> blk_cost;     // [n_icb] instructions of the walk per block: 3 per nonempty row + 5 per nonzero
+  std::vector<ValAt> val_at;        // every nonzero of the chain's channels: its word, relative to the chain's first word
 };
 
 void emit_chain(const ConvGeom &g, const Tiling &t, const std::vector<int> &rowptr, const std::vector<int> &colidx,
@@ -369,6 +382,7 @@ void emit_chain(const ConvGeom &g, const Tiling &t, const std::vector<int> &rowp
         Rec rec;
         std::memcpy(&rec.bits, &values[(size_t)(cp - colidx.data())], 4);
         rec.idx = gl * g.KW + kc;
+        rec.entry = (int)(cp - colidx.data());
         rows[(ic - ic_lo) * g.KH + kr].recs.push_back(rec);
       }
     }
@@ -415,7 +429,7 @@ void emit_chain(const ConvGeom &g, const Tiling &t, const std::vector<int> &rowp
     while ((p.code.size() * 4) % kUnitAlign) enc_nop(p.code);
     p.off[blk] = (uint32_t)(p.code.size() * 4);
     const size_t at = p.code.size();
-    patches.push_back(emit_unit(p.code, live, pieces, opt, n_pref, t.pix_waves == 1 ? ocg % t.oc_waves : -1, blk, t.n_icb, t.G * g.KW));
+    patches.push_back(emit_unit(p.code, live, pieces, opt, n_pref, t.pix_waves == 1 ? ocg % t.oc_waves : -1, blk, t.n_icb, t.G * g.KW, &p.val_at));
     p.max_unit = std::max(p.max_unit, (p.code.size() - at) * 4);
   }
   // the distances: unit blk touches the code of unit (blk + 1) % n_icb
@@ -438,6 +452,8 @@ static Program build_pass(const ConvGeom &g, const Tiling &t, const std::vector<
   const size_t n_chains = (size_t)g.group * t.n_ocg, n_units = n_chains * t.n_icb;
   p.unit_off.assign(n_units, 0u);
   p.chan = chan;
+  p.val_word.resize(g.group);
+  for (int cg = 0; cg < g.group; ++cg) p.val_word[cg].assign(colidx[cg].size(), 0u);
   // the chains are independent (a unit's touches stay inside its chain): large layers generate them on up to eight
   // threads, and the blobs are put together in order -- the same bytes as one thread would write
   std::vector<ChainOut> outs(n_chains);
@@ -461,6 +477,7 @@ static Program build_pass(const ConvGeom &g, const Tiling &t, const std::vector<
     const uint32_t base = (uint32_t)(p.code.size() * 4);
     p.code.insert(p.code.end(), c.code.begin(), c.code.end());
     for (int blk = 0; blk < t.n_icb; ++blk) p.unit_off[ci * t.n_icb + blk] = base + c.off[blk];
+    for (const ValAt &v : c.val_at) p.val_word[ci / t.n_ocg][(size_t)v.entry] = (uint32_t)(base / 4 + v.word);   // (rebased like unit_off)
     p.n_rows += c.n_rows; p.n_records += c.n_records; p.n_dma += c.n_dma;
     p.overflow = p.overflow || c.overflow;
     *max_unit_bytes = std::max(*max_unit_bytes, c.max_unit);

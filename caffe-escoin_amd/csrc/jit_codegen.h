@@ -259,6 +259,11 @@ struct Program {
   std::vector<uint32_t> code;       // every unit, back to back, each aligned to kUnitAlign bytes
   std::vector<uint32_t> unit_off;   // [conv group][n_ocg][n_icb]: byte offset of the unit's entry
   std::vector<uint32_t> chan;       // slot -> output channel, as WeightStream::chan
+  // [conv group][index in the group's colidx]: the word of `code` that holds the entry's value -- the literal of its
+  // s_mov_b32 or its slot in its unit's weight lines.  The pattern alone shapes the code: code generated from other
+  // values at the same pattern differs at these words only (tests/cpp/value_map_check.cpp), which is what lets
+  // escoin_update_values patch a plan's code in place.
+  std::vector<std::vector<uint32_t>> val_word;
   long n_rows = 0, n_records = 0, n_dma = 0;
   int n_pref = 0;                   // code touches (plain loads) at the start of every unit
   bool overflow = false;            // an LDS offset does not fit the instruction's 16-bit field

@@ -296,24 +296,33 @@ static int build_transposed_plan(escoin_plan *p, BwdState *s, hipStream_t stream
   // ascending within the row
   std::vector<int> rowptr((size_t)d.group * (g.Cg + 1)), colidx, nnz_g(d.group);
   std::vector<float> vals;
-  std::vector<std::vector<std::pair<int, float>>> rows(g.Cg);
+  // (column', index of the entry in its group's CSR): the columns of a row are distinct, so the order is a function of
+  // the pattern alone; s->tsrc records it for escoin_update_values
+  std::vector<std::vector<std::pair<int, int>>> rows(g.Cg);
+  s->tsrc.clear();
+  int group_base = 0;
   for (int grp = 0; grp < d.group; ++grp) {
     for (auto &r : rows) r.clear();
     const std::vector<int> &rp = p->rowptr[grp], &ci = p->colidx[grp];
     for (int m = 0; m < g.Mg; ++m)
       for (int j = rp[m]; j < rp[m + 1]; ++j) {
         const int col = ci[j], icl = col / kk, kr = (col / d.KW) % d.KH, kc = col % d.KW;
-        rows[icl].emplace_back(m * kk + (d.KH - 1 - kr) * d.KW + (d.KW - 1 - kc), p->values[grp][j]);
+        rows[icl].emplace_back(m * kk + (d.KH - 1 - kr) * d.KW + (d.KW - 1 - kc), j);
       }
     int *trp = rowptr.data() + (size_t)grp * (g.Cg + 1);
     trp[0] = 0;
     for (int c = 0; c < g.Cg; ++c) {
       std::sort(rows[c].begin(), rows[c].end(),
-                [](const std::pair<int, float> &x, const std::pair<int, float> &y) { return x.first < y.first; });
-      for (const auto &e : rows[c]) { colidx.push_back(e.first); vals.push_back(e.second); }
+                [](const std::pair<int, int> &x, const std::pair<int, int> &y) { return x.first < y.first; });
+      for (const auto &e : rows[c]) {
+        colidx.push_back(e.first);
+        vals.push_back(p->values[grp][e.second]);
+        s->tsrc.push_back(group_base + e.second);
+      }
       trp[c + 1] = trp[c] + (int)rows[c].size();
     }
     nnz_g[grp] = trp[g.Cg];
+    group_base += (int)ci.size();
   }
   rc = escoin_plan_set_csr(tp, rowptr.data(), colidx.data(), vals.data(), nnz_g.data(), stream);
   if (rc != ESCOIN_OK) return rc;
@@ -334,6 +343,8 @@ static int build_gather(escoin_plan *p, BwdState *s, const std::vector<std::vect
   for (int c = 0; c < d.C; ++c) cnt[c + 1] += cnt[c];
   std::vector<int> trow(cnt), fill(cnt.begin(), cnt.end() - 1), ttap((size_t)s->nnz);
   std::vector<T> tval((size_t)s->nnz);
+  s->tsrc.assign((size_t)s->nnz, 0);
+  int group_base = 0;
   for (int grp = 0; grp < d.group; ++grp) {
     const std::vector<int> &rp = p->rowptr[grp], &ci = p->colidx[grp];
     for (int m = 0; m < g.Mg; ++m)
@@ -342,7 +353,9 @@ static int build_gather(escoin_plan *p, BwdState *s, const std::vector<std::vect
         const int at = fill[c]++;
         ttap[at] = (m << 16) | (((col / d.KW) % d.KH) << 8) | (col % d.KW);
         tval[at] = values[grp][j];
+        s->tsrc[at] = group_base + j;
       }
+    group_base += (int)ci.size();
   }
   int rc = dev_upload(s->trow, trow, stream);
   if (rc == ESCOIN_OK) rc = dev_upload(s->ttap, ttap, stream);
@@ -359,6 +372,8 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   const escoin_conv_desc &d = g.d;
   if (g.Mg > 65535) return fail(ESCOIN_EINVAL, "backward: more than 65535 output channels per group");
   if (d.C > 4 * 65535 || d.N > 65535) return fail(ESCOIN_EINVAL, "backward: grid dimension exceeds 65535");
+  // (after device-source weight updates the host CSR this state is built from is stale: the values come back first)
+  if (const int rcs = sync_host_values(p)) return rcs;
   const bool transposable = bwd_transposable(p);
   const bool forced = p->bwd_kernel == ESCOIN_KERNEL_TILED || p->bwd_kernel == ESCOIN_KERNEL_JIT ||
                       p->bwd_kernel == ESCOIN_KERNEL_DENSE;

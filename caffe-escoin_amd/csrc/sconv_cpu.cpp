@@ -262,6 +262,7 @@ static int forward_cpu(escoin_plan *p, const T *bottom, const T *bias, T *top, i
                                          : "forward_cpu_f64: the plan holds float weights");
   if (n_images < 0) return fail(ESCOIN_EINVAL, "n_images must be >= 0");
   if (n_images == 0) return ESCOIN_OK;
+  if (const int rcs = sync_host_values(p)) return rcs;     // (device-source weight updates: the values come back first)
   if (isa() == kNone) return fail(ESCOIN_ENODEVICE, "the CPU path needs AVX2 + FMA (the reference builds with -mavx2 -mfma too)");
   if (!p->cpu_off_valid) build_offsets(p);
   if (p->cpu_blk_cb < 0 || p->cpu_blk_isa != (int)isa() || p->cpu_blk_elem != (int)sizeof(T)) build_channel_blocks<T>(p);
@@ -439,6 +440,29 @@ static int weight_align_cpu(escoin_plan *p, const T *dense_w) {
   return ESCOIN_OK;
 }
 
+// escoin_update_values_cpu: new values at the old pattern, for plans that live on the host only.  Reads blobs_[0] at the
+// CSR's positions and nowhere else; the offsets and the channel blocking of the CPU mode depend on the pattern alone.
+template <typename T>
+static int update_values_cpu(escoin_plan *p, const T *dense_w) {
+  if (!p || !dense_w) return fail(ESCOIN_EINVAL, "null argument");
+  if (!p->host_aligned) return fail(ESCOIN_ESTATE, "update_values_cpu called before weight_align_cpu");
+  if (p->aligned)
+    return fail(ESCOIN_ESTATE, "update_values_cpu: the plan has a device side, which this entry point would leave behind; "
+                               "escoin_update_values(..., w_on_device = 0, ...) updates both sides");
+  if (p->is_f64 != (sizeof(T) == 8))
+    return fail(ESCOIN_ESTATE, p->is_f64 ? "update_values_cpu: the plan holds double weights (use the _f64 entry point)"
+                                         : "update_values_cpu_f64: the plan holds float weights");
+  const Geometry &g = p->g;
+  std::vector<std::vector<T>> &vals = plan_vals<T>(p);
+  for (int grp = 0; grp < g.d.group; ++grp)
+    for (int m = 0; m < g.Mg; ++m) {
+      const T *row = dense_w + ((size_t)grp * g.Mg + m) * g.kdim;
+      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j) vals[grp][j] = row[p->colidx[grp][j]];
+    }
+  ++p->upd_count;
+  return ESCOIN_OK;
+}
+
 }  // namespace cpu
 }  // namespace escoin
 
@@ -477,6 +501,13 @@ int escoin_weight_align_cpu(escoin_plan *p, const float *dense_w) {
 }
 int escoin_weight_align_cpu_f64(escoin_plan *p, const double *dense_w) {
   return guarded([&]() -> int { return cpu::weight_align_cpu<double>(p, dense_w); });
+}
+
+int escoin_update_values_cpu(escoin_plan *p, const float *dense_w) {
+  return guarded([&]() -> int { return cpu::update_values_cpu<float>(p, dense_w); });
+}
+int escoin_update_values_cpu_f64(escoin_plan *p, const double *dense_w) {
+  return guarded([&]() -> int { return cpu::update_values_cpu<double>(p, dense_w); });
 }
 
 int escoin_forward_cpu(escoin_plan *p, const float *bottom, const float *bias, float *top, int n_images, int n_threads) {

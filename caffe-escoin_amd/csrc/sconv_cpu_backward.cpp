@@ -38,6 +38,7 @@ static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *
   if (weight_diff && !bottom) return fail(ESCOIN_EINVAL, "backward_cpu: the weight gradient needs bottom");
   if (n_images < 0) return fail(ESCOIN_EINVAL, "n_images must be >= 0");
   if (n_images == 0) return ESCOIN_OK;
+  if (const int rcs = sync_host_values(p)) return rcs;     // (device-source weight updates: the values come back first)
   if (n_threads <= 0) {
     const unsigned hc = std::thread::hardware_concurrency();
     n_threads = hc ? (int)hc : 1;

@@ -267,6 +267,7 @@ namespace {
 struct Rec {
   float val;
   uint8_t idx;
+  int entry;      // the CSR entry it came from: index into the conv group's colidx / values
 };
 struct Group {
   uint32_t lds_off;
@@ -477,6 +478,8 @@ WeightStream build_stream(const ConvGeom &g, const Tiling &t,
     return u;
   };
   ws.chan.reserve((size_t)g.group * t.n_ocg * t.G);
+  ws.val_word.resize(g.group);
+  for (int cg = 0; cg < g.group; ++cg) ws.val_word[cg].assign(colidx[cg].size(), 0u);
   for (int cg = 0; cg < g.group; ++cg) {
     const std::vector<uint32_t> sl = balance_channels(g, t, rowptr[cg], colidx[cg]);
     ws.chan.insert(ws.chan.end(), sl.begin(), sl.end());
@@ -496,6 +499,7 @@ WeightStream build_stream(const ConvGeom &g, const Tiling &t,
             Rec rec;
             rec.val = values[cg][j];
             rec.idx = (uint8_t)(gl * g.KW + kc);
+            rec.entry = j;
             rows[(ic - ic_lo) * g.KH + kr].push_back(rec);
           }
         }
@@ -547,6 +551,7 @@ WeightStream build_stream(const ConvGeom &g, const Tiling &t,
             q[4] |= 4u * gr.recs[s].idx << (7 * (s - 3));
             q[5 + (s - 3)] = f2u(gr.recs[s].val);
           }
+          for (int s = 0; s < n; ++s) ws.val_word[cg][(size_t)gr.recs[s].entry] = (uint32_t)(ws.words.size() + (s < 3 ? 1 + s : 2 + s));
           ws.words.insert(ws.words.end(), q, q + (n > 3 ? 8 : 4));
           ws.n_records += n;
         }

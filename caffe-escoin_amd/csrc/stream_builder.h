@@ -116,6 +116,9 @@ struct WeightStream {
   // chan[(group * n_ocg + ocg) * G + gl].  The identity (ocg * G + gl) unless the channels were
   // re-dealt over the waves (balance_channels); slots past the group's last channel repeat it.
   std::vector<uint32_t> chan;
+  // [conv group][index in the group's colidx]: the word of `words` that holds the entry's value (v0 .. v5 of its quad).
+  // Everything else in the stream is a function of the pattern: escoin_update_values patches these words in place.
+  std::vector<std::vector<uint32_t>> val_word;
 };
 
 // Deals the output channels of one conv group over the waves (oc-groups) so that, block by

@@ -1,0 +1,303 @@
+// update_values.hip -- in-place weight updates: the second half of a training step (include/escoin.h, "Weight updates").
+//
+// Everything WeightAlign decides is a function of the sparsity PATTERN and the options; a value enters the device side
+// as a full 32-bit (64-bit: double plans) word at a position the builders record (jit::Program::val_word,
+// WeightStream::val_word; tests/cpp/value_map_check.cpp proves that nothing else depends on a value).  For an unchanged
+// pattern a weight update is therefore a scatter of the nnz values into every device word that holds one:
+//   gen.vals                                   the generic kernel's and the LOWERED_SPARSE comparator's values
+//   the generated code / the weight stream     sparse conv groups of a tiled plan
+//   dense.w                                    the MFMA kernel's padded matrix
+//   bwd: tval, or the transposed plan's own    the backward state's copies, through BwdState::tsrc
+// The first update on an alignment builds that list (UpdState); later updates launch one kernel and nothing else.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "escoin_plan.h"
+
+namespace escoin {
+
+struct UpdArgs {
+  void *base[kUpdMaxBuffers];
+  const int *src;
+  const unsigned *off;
+  const unsigned char *buf;
+  const int *wpos;
+  long n_dst;
+};
+
+// One lane per destination, one plain vector store each.  The list is sorted by (buffer, CSR entry): the lanes of a wave
+// read ascending addresses of the source (CSR order ascends in blobs_[0]) and, for gen.vals, write consecutive ones.
+//
+// Patched CODE becomes visible the way freshly filled code does (code_memory.hip, escoin_code_copy_kernel, and the
+// comment at the generated-code kernel's first jump, sconv_tiled.hip): these are ordinary vector stores, which reach L2 /
+// memory when this kernel ends; the scalar cache -- through which the walk reads its weight lines -- is invalidated at
+// every dispatch; literals are fetched by the instruction cache, which wave 0 of every workgroup of the generated-code
+// kernel drops before the first jump, so the next launch refetches them from L2.  No cache instruction is needed here.
+template <typename T, bool FromDense>
+__global__ void __launch_bounds__(256) escoin_update_values_kernel(UpdArgs a, const T *__restrict__ in) {
+  const long k = (long)blockIdx.x * 256 + threadIdx.x;
+  if (k >= a.n_dst) return;
+  const int e = a.src[k];
+  const T v = FromDense ? in[a.wpos[e]] : in[e];
+  static_cast<T *>(a.base[a.buf[k]])[a.off[k]] = v;
+}
+
+namespace {
+
+struct Dst { unsigned char buf; int src; unsigned off; };
+
+// The destinations of one plan's forward side (the plan itself, or the backward state's transposed plan): entry e of q's
+// CSR (groups concatenated) is a copy of entry src_of[e] of the updated plan's (nullptr: the identity).  Every offset is
+// checked against the size of the buffer it indexes: a list that would write out of bounds is refused, never launched.
+template <typename T>
+int collect(const escoin_plan *q, const int *src_of, UpdState *u, std::vector<Dst> *out) {
+  const Geometry &g = q->g;
+  auto add_buffer = [&](void *ptr) -> int {
+    if (u->n_buffers >= kUpdMaxBuffers) return -1;
+    u->base[u->n_buffers] = ptr;
+    return u->n_buffers++;
+  };
+  long nnz = 0;
+  for (const auto &c : q->colidx) nnz += (long)c.size();
+  if (nnz == 0) return ESCOIN_OK;
+  const int b_gen = add_buffer(q->gen.vals.get<void>());
+  const bool have_dense = q->n_dense_groups > 0 && q->dense.w.get<void>();
+  const int b_dense = have_dense ? add_buffer(q->dense.w.get<void>()) : -1;
+  const bool tiled = q->tiled.enabled;
+  void *tiled_ptr = tiled ? (q->tiled.jit ? reinterpret_cast<void *>(q->tiled_dev.jit.code_base) : q->tiled_dev.stream.get<void>()) : nullptr;
+  const size_t tiled_words = tiled ? (q->tiled.jit ? q->tiled_dev.jit.code_bytes / 4 : q->tiled_dev.stream.bytes() / 4) : 0;
+  const int b_tiled = tiled ? add_buffer(tiled_ptr) : -1;
+  if (b_gen < 0 || (have_dense && b_dense < 0) || (tiled && b_tiled < 0)) return fail(ESCOIN_EINVAL, "update_values: too many buffers");
+  if (q->gen.vals.bytes() < sizeof(T) * (size_t)nnz) return fail(ESCOIN_EINVAL, "update_values: the plan's value array is shorter than its CSR");
+  const size_t lda = have_dense ? (size_t)dense_lda(g.kdim) : 0;
+  long e = 0;
+  for (int grp = 0; grp < g.d.group; ++grp) {
+    const bool sparse_here = tiled && !group_is_dense(q, grp);
+    if (sparse_here && (grp >= (int)q->tiled_dev.val_word.size() || q->tiled_dev.val_word[grp].size() != q->colidx[grp].size()))
+      return fail(ESCOIN_EINVAL, "update_values: the plan's value map does not match its CSR");
+    for (int m = 0; m < g.Mg; ++m)
+      for (int j = q->rowptr[grp][m]; j < q->rowptr[grp][m + 1]; ++j, ++e) {
+        const int s = src_of ? src_of[e] : (int)e;
+        out->push_back({(unsigned char)b_gen, s, (unsigned)e});
+        if (have_dense) {
+          // (the padded matrix holds every group's rows, whichever kernel runs them)
+          const size_t at = ((size_t)grp * g.Mg + m) * lda + (size_t)q->colidx[grp][j];
+          if ((at + 1) * sizeof(T) > q->dense.w.bytes()) return fail(ESCOIN_EINVAL, "update_values: dense destination out of range");
+          out->push_back({(unsigned char)b_dense, s, (unsigned)at});
+        }
+        if (sparse_here) {
+          const unsigned w = q->tiled_dev.val_word[grp][(size_t)j];
+          if ((size_t)w >= tiled_words) return fail(ESCOIN_EINVAL, "update_values: code / stream destination out of range");
+          out->push_back({(unsigned char)b_tiled, s, w});
+        }
+      }
+  }
+  return ESCOIN_OK;
+}
+
+// Whether the in-place path exists for plan q: generated code must sit in memory the library filled itself and carry a
+// value map (a plan restored by the fast import has code but no map).
+bool in_place_ok(const escoin_plan *q) {
+  if (!(q->tiled.enabled && q->tiled.jit)) return true;
+  return q->tiled_dev.jit.direct != nullptr && !q->tiled_dev.val_word.empty();
+}
+
+template <typename T>
+int build_state(escoin_plan *p, hipStream_t stream) {
+  const Geometry &g = p->g;
+  std::unique_ptr<UpdState> u(new UpdState());
+  std::vector<Dst> dst;
+  int rc = collect<T>(p, nullptr, u.get(), &dst);
+  if (rc != ESCOIN_OK) return rc;
+  for (const auto &c : p->colidx) u->nnz += (long)c.size();
+  if (const BwdState *s = p->bwd.get()) {
+    if ((long)s->tsrc.size() != u->nnz) return fail(ESCOIN_EINVAL, "update_values: the backward state does not match the CSR");
+    if (s->tplan) {
+      rc = collect<T>(s->tplan.get(), s->tsrc.data(), u.get(), &dst);
+      if (rc != ESCOIN_OK) return rc;
+    } else if (u->nnz > 0) {
+      if (u->n_buffers >= kUpdMaxBuffers || s->tval.bytes() < sizeof(T) * (size_t)u->nnz) return fail(ESCOIN_EINVAL, "update_values: bad backward value array");
+      const int b = u->n_buffers++;
+      u->base[b] = s->tval.get<void>();
+      for (long k = 0; k < u->nnz; ++k) dst.push_back({(unsigned char)b, s->tsrc[(size_t)k], (unsigned)k});
+    }
+    u->has_bwd = true;
+  }
+  std::stable_sort(dst.begin(), dst.end(), [](const Dst &a, const Dst &b) { return a.buf != b.buf ? a.buf < b.buf : a.src < b.src; });
+  u->n_dst = (long)dst.size();
+  const size_t n = std::max<size_t>(dst.size(), 1), nz = std::max<size_t>((size_t)u->nnz, 1);
+  std::vector<int> src(n, 0), wpos(nz, 0);
+  std::vector<unsigned> off(n, 0);
+  std::vector<unsigned char> buf(n, 0);
+  for (size_t k = 0; k < dst.size(); ++k) src[k] = dst[k].src, off[k] = dst[k].off, buf[k] = dst[k].buf;
+  long e = 0;
+  for (int grp = 0; grp < g.d.group; ++grp)
+    for (int m = 0; m < g.Mg; ++m)
+      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j) wpos[(size_t)e++] = (grp * g.Mg + m) * g.kdim + p->colidx[grp][j];
+  ESCOIN_HIP_TRY(u->src.upload(src, stream));
+  ESCOIN_HIP_TRY(u->off.upload(off, stream));
+  ESCOIN_HIP_TRY(u->buf.upload(buf, stream));
+  ESCOIN_HIP_TRY(u->wpos.upload(wpos, stream));
+  ESCOIN_HIP_TRY(u->stage.alloc(sizeof(T) * nz));
+  u->h_stage.assign(sizeof(T) * nz, 0);
+  ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
+  p->upd = std::move(u);
+  return ESCOIN_OK;
+}
+
+// New values (compact, the plan's CSR order) into every HOST copy plan q keeps: the CSR's values and the kept copy of the
+// generated code.  src_of as in collect().
+template <typename T>
+void patch_host(escoin_plan *q, const T *vals, const int *src_of) {
+  std::vector<std::vector<T>> &hv = plan_vals<T>(q);
+  const bool code = q->tiled.enabled && q->tiled.jit && !q->tiled_dev.jit_code.empty() && !q->tiled_dev.val_word.empty();
+  long e = 0;
+  for (int grp = 0; grp < q->g.d.group; ++grp) {
+    const bool in_code = code && !group_is_dense(q, grp) && q->tiled_dev.val_word[grp].size() == q->colidx[grp].size();
+    for (size_t j = 0; j < q->colidx[grp].size(); ++j, ++e) {
+      const T v = vals[src_of ? src_of[e] : e];
+      hv[grp][j] = v;
+      if constexpr (sizeof(T) == 4)
+        if (in_code) std::memcpy(&q->tiled_dev.jit_code[q->tiled_dev.val_word[grp][j]], &v, 4);
+    }
+  }
+}
+
+template <typename T>
+void patch_host_all(escoin_plan *p, const T *vals) {
+  patch_host<T>(p, vals, nullptr);
+  if constexpr (sizeof(T) == 4)
+    if (p->bwd && p->bwd->tplan) patch_host<float>(p->bwd->tplan.get(), vals, p->bwd->tsrc.data());
+}
+
+// The fallback: the device side rebuilt from the host CSR with the new values, exactly as set_csr would.
+template <typename T>
+int update_by_rebuild(escoin_plan *p, const T *in, bool from_dense, bool on_device, hipStream_t stream) {
+  const Geometry &g = p->g;
+  long nnz = 0;
+  for (const auto &c : p->colidx) nnz += (long)c.size();
+  std::vector<T> host;
+  const T *src = in;
+  if (on_device) {
+    const size_t count = from_dense ? (size_t)g.d.M * g.kdim : (size_t)nnz;
+    host.resize(std::max<size_t>(count, 1));
+    if (count) ESCOIN_HIP_TRY(hipMemcpyAsync(host.data(), in, sizeof(T) * count, hipMemcpyDeviceToHost, stream));
+    ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
+    src = host.data();
+  }
+  std::vector<std::vector<T>> &hv = plan_vals<T>(p);
+  long e = 0;
+  for (int grp = 0; grp < g.d.group; ++grp)
+    for (int m = 0; m < g.Mg; ++m)
+      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j, ++e)
+        hv[grp][j] = from_dense ? src[((size_t)grp * g.Mg + m) * g.kdim + p->colidx[grp][j]] : src[e];
+  p->aligned = false;
+  const int rc = realign_from_host_csr(p, stream);     // (ends a device-authoritative state like any align)
+  p->upd_last_fast = 0;
+  return rc;
+}
+
+int sync_host(escoin_plan *p);
+
+template <typename T>
+int update_t(escoin_plan *p, const T *in, bool from_dense, int on_device, void *stream_v) {
+  const char *name = from_dense ? "update_values" : "set_values";
+  if (!p || !in) return fail(ESCOIN_EINVAL, std::string(name) + ": null argument");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
+    return fail(ESCOIN_ENODEVICE, std::string(name) + ": no HIP device (a plan aligned by escoin_weight_align_cpu is updated by escoin_update_values_cpu)");
+  if (!p->aligned) return fail(ESCOIN_ESTATE, std::string(name) + " called before weight_align / set_csr");
+  if (p->is_f64 != (sizeof(T) == 8))
+    return fail(ESCOIN_ESTATE, std::string(name) + (p->is_f64 ? ": the plan holds double weights (use the _f64 entry point)" : "_f64: the plan holds float weights"));
+  {
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
+      return fail(ESCOIN_ESTATE, std::string(name) + ": the current device is not the device the plan was aligned on");
+  }
+  hipStream_t stream = (hipStream_t)stream_v;
+  ++p->upd_count;
+  const BwdState *bs = p->bwd.get();
+  if (!in_place_ok(p) || (bs && bs->tplan && !in_place_ok(bs->tplan.get()))) return update_by_rebuild<T>(p, in, from_dense, on_device != 0, stream);
+  if (!p->upd || (p->bwd && !p->upd->has_bwd)) {
+    p->upd.reset();
+    const int rc = build_state<T>(p, stream);
+    if (rc != ESCOIN_OK) return rc;
+  }
+  UpdState *u = p->upd.get();
+  p->upd_last_fast = 1;
+  if (u->n_dst == 0) return ESCOIN_OK;
+  UpdArgs a;
+  for (int b = 0; b < kUpdMaxBuffers; ++b) a.base[b] = u->base[b];
+  a.src = u->src.get<int>(); a.off = u->off.get<unsigned>(); a.buf = u->buf.get<unsigned char>(); a.wpos = u->wpos.get<int>();
+  a.n_dst = u->n_dst;
+  const dim3 grid((unsigned)((u->n_dst + 255) / 256)), block(256);
+  if (on_device) {
+    if (from_dense) hipLaunchKernelGGL((escoin_update_values_kernel<T, true>), grid, block, 0, stream, a, in);
+    else hipLaunchKernelGGL((escoin_update_values_kernel<T, false>), grid, block, 0, stream, a, in);
+    ESCOIN_HIP_TRY(hipGetLastError());
+    // the plan cannot see a graph replay: from here until the next align the device holds the values
+    p->dev_authoritative = true;
+    p->sync_host_fn = sync_host;
+    p->upd_stream = stream;
+    return ESCOIN_OK;
+  }
+  // host source: compact values -> the host mirrors directly, and through the staging buffer into the same kernel
+  T *hs = reinterpret_cast<T *>(u->h_stage.data());
+  long e = 0;
+  const Geometry &g = p->g;
+  for (int grp = 0; grp < g.d.group; ++grp)
+    for (int m = 0; m < g.Mg; ++m)
+      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j, ++e)
+        hs[e] = from_dense ? in[((size_t)grp * g.Mg + m) * g.kdim + p->colidx[grp][j]] : in[e];
+  patch_host_all<T>(p, hs);
+  p->dev_authoritative = false;      // (every value was just replaced on both sides)
+  ESCOIN_HIP_TRY(hipMemcpyAsync(u->stage.get<T>(), hs, sizeof(T) * (size_t)u->nnz, hipMemcpyHostToDevice, stream));
+  hipLaunchKernelGGL((escoin_update_values_kernel<T, false>), grid, block, 0, stream, a, u->stage.get<const T>());
+  ESCOIN_HIP_TRY(hipGetLastError());
+  ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // the staging area is reused by the next host-source update
+  return ESCOIN_OK;
+}
+
+template <typename T>
+int sync_host_t(escoin_plan *p) {
+  long nnz = 0;
+  for (const auto &c : p->colidx) nnz += (long)c.size();
+  if (nnz > 0) {
+    // gen.vals is the device's value array in CSR order (every plan kind keeps it)
+    std::vector<T> vals((size_t)nnz);
+    ESCOIN_HIP_TRY(hipMemcpyAsync(vals.data(), p->gen.vals.get<T>(), sizeof(T) * (size_t)nnz, hipMemcpyDeviceToHost, p->upd_stream));
+    ESCOIN_HIP_TRY(hipStreamSynchronize(p->upd_stream));
+    patch_host_all<T>(p, vals.data());
+  }
+  p->dev_authoritative = false;
+  return ESCOIN_OK;
+}
+
+int sync_host(escoin_plan *p) { return p->is_f64 ? sync_host_t<double>(p) : sync_host_t<float>(p); }
+
+}  // namespace
+
+}  // namespace escoin
+
+using namespace escoin;
+
+extern "C" {
+
+int escoin_update_values(escoin_plan *p, const float *dense_w, int w_on_device, void *stream) {
+  return guarded([&]() -> int { return update_t<float>(p, dense_w, true, w_on_device, stream); });
+}
+int escoin_update_values_f64(escoin_plan *p, const double *dense_w, int w_on_device, void *stream) {
+  return guarded([&]() -> int { return update_t<double>(p, dense_w, true, w_on_device, stream); });
+}
+int escoin_plan_set_values(escoin_plan *p, const float *values, int on_device, void *stream) {
+  return guarded([&]() -> int { return update_t<float>(p, values, false, on_device, stream); });
+}
+int escoin_plan_set_values_f64(escoin_plan *p, const double *values, int on_device, void *stream) {
+  return guarded([&]() -> int { return update_t<double>(p, values, false, on_device, stream); });
+}
+
+}  // extern "C"

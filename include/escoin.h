@@ -185,7 +185,7 @@ ESCOIN_API long escoin_plan_nnz(const escoin_plan *plan, int group);
 ESCOIN_API int escoin_plan_get_csr(const escoin_plan *plan, int *rowptr, int *colidx, float *values,
                         int stretched);
 
-/* Device bytes owned by the plan (CSR + weight streams / generated code + scratch). */
+/* Device bytes owned by the plan (CSR + weight streams / generated code + scratch, the backward state and the update state). */
 ESCOIN_API size_t escoin_plan_workspace_bytes(const escoin_plan *plan);
 
 /* The aligned form as one relocatable byte blob: the CSR and -- for a generated-code plan -- the
@@ -423,6 +423,61 @@ ESCOIN_API int escoin_backward_cpu(escoin_plan *plan, const float *bottom, const
                         float *bottom_diff, float *weight_diff, float *bias_diff, int n_images, int n_threads);
 ESCOIN_API int escoin_backward_cpu_f64(escoin_plan *plan, const double *bottom, const double *top, const double *top_diff,
                             double *bottom_diff, double *weight_diff, double *bias_diff, int n_images, int n_threads);
+
+/* ---- Weight updates: the second half of a training step -------------------------------------------------------------
+ *   Solver::ApplyUpdate -> Net::Update -> Blob::Update (solver.cpp, blob.cpp) changes blobs_[0]; the reference then has
+ *   to run WeightAlign again before the sparse forward sees the new weights.
+ * A plan computes from COPIES of the weights that WeightAlign made -- the generic kernel's value array, the stream
+ * kernel's quads, the dense kernel's padded matrix, 32-bit words inside generated machine code, and the backward state's
+ * transposed copies of all of these.  Everything else WeightAlign decides is a function of the sparsity PATTERN and the
+ * options, and the masked gradient of escoin_backward keeps the pattern: after a solver step only the values differ.
+ * These entry points write the new values into every copy, in place.
+ *   dense_w  blobs_[0] (M x C/g x KH x KW).  Only the elements at the plan's CSR positions are read; every other element
+ *            is ignored (it is 0 under the masked gradient; a NaN there does no harm).  A caller that GREW the pattern
+ *            must call escoin_weight_align.  A kept weight whose new value is exactly 0 stays in the CSR as an explicit
+ *            zero (-0.0 stays -0.0).
+ *   values   (escoin_plan_set_values) the compact array, nnz elements in the order of escoin_plan_get_csr -- what rank 0
+ *            would broadcast after a step instead of a blob.
+ * The pattern, tiling, kernel choice, channel deal, the generated code's instructions, every device allocation and the
+ * backward state stay.  After the call every consumer of the plan -- escoin_forward in all four conv_modes (a later flip
+ * to or from LOWERED_GEMM included), escoin_backward's data gradient on the transposed plan or the gather kernel,
+ * escoin_plan_get_csr, escoin_plan_export_aligned, escoin_forward_cpu / escoin_backward_cpu -- behaves BIT FOR BIT like a
+ * fresh plan with the same options aligned (escoin_plan_set_csr) on the new values at the old pattern.
+ * Device source (w_on_device / on_device != 0): one launch of escoin_update_values_kernel (one lane per destination word,
+ * one plain store each), asynchronous on `stream`, no host synchronisation.  The FIRST update on an alignment builds the
+ * update state (the scatter list: device memory, a synchronisation); so does the first one after the backward state
+ * appeared.  Later calls allocate nothing and can be captured into a graph together with escoin_forward and
+ * escoin_backward.  Ordering against launches of the plan on OTHER streams is the caller's, as for any buffer.
+ * Host source: the host CSR is updated directly, the compact values go through a staging buffer the update state owns,
+ * then the same kernel; the call returns when the copy is done.
+ * Host mirrors after a device-source update: the plan cannot see a graph replay, so from the first device-source update
+ * until the next align (or host-source update) the DEVICE is authoritative.  Everything that reads weights from the host
+ * -- get_csr, export_aligned, the CPU entry points, a backward state that is built later, the rebuild a conv_mode flip
+ * to or from LOWERED_GEMM does -- first reads the value array back: a copy of nnz values on the stream the last update
+ * used, then a wait on that stream (which must therefore still exist, and must not be capturing; after graph REPLAYS the
+ * caller synchronises the replay's stream first -- the plan saw the capture, not the replays), then the host CSR and
+ * the host's copy of the generated code are patched, so that an exported blob and its content tags carry the new
+ * values.  Mixed CPU / GPU use pays that read-back once per device-source update followed by a host read: alternate
+ * escoin_forward_cpu with device-source updates and every step copies nnz values and waits for the stream.
+ * Fallback (correct, slow; stat "update_fast" = 0): where the in-place path does not exist the update rebuilds the device
+ * side from the host CSR with the new values, exactly as escoin_plan_set_csr would -- it synchronises, allocates and
+ * drops the backward state; only update_fast = 1 calls are capturable.  Two plan kinds take it: generated code that the
+ * HIP module loader placed (stat "code_direct" = 0: its memory is the loader's), and a plan restored by the fast import
+ * (its blob carries code but no value map; the rebuild produces one, so the NEXT update is in place).
+ * escoin_update_values_cpu[_f64]: for plans aligned by escoin_weight_align_cpu only (host CSR, no device side); no HIP
+ * call.  On a device-aligned plan it returns ESCOIN_ESTATE: escoin_update_values(..., w_on_device = 0, ...) updates both
+ * sides.
+ * Errors: ESCOIN_EINVAL for a NULL argument; ESCOIN_ENODEVICE for the GPU entry points without a device (no silent CPU
+ * fallback, as everywhere); ESCOIN_ESTATE before an align, on the other Dtype's entry point, on another device.
+ * Stats: "update_fast" (1: the last update was the in-place scatter, 0: it took the fallback), "update_count" (updates
+ * since the plan was created), "update_destinations" (words one update writes), "upd_device_bytes" (the update state's
+ * device memory; escoin_plan_workspace_bytes = device_bytes + bwd_device_bytes + upd_device_bytes). */
+ESCOIN_API int escoin_update_values(escoin_plan *plan, const float *dense_w, int w_on_device, void *stream);
+ESCOIN_API int escoin_update_values_f64(escoin_plan *plan, const double *dense_w, int w_on_device, void *stream);
+ESCOIN_API int escoin_plan_set_values(escoin_plan *plan, const float *values, int on_device, void *stream);
+ESCOIN_API int escoin_plan_set_values_f64(escoin_plan *plan, const double *values, int on_device, void *stream);
+ESCOIN_API int escoin_update_values_cpu(escoin_plan *plan, const float *dense_w);
+ESCOIN_API int escoin_update_values_cpu_f64(escoin_plan *plan, const double *dense_w);
 
 #ifdef __cplusplus
 }
