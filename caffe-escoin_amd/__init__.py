@@ -23,6 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ESCOIN_LIB") or os.path.join(_HERE, "libescoin_hip.so")
 
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TILED, KERNEL_DENSE, KERNEL_JIT = 0, 1, 2, 3, 4
+WGRAD_AUTO, WGRAD_ENTRY, WGRAD_STAGED = 0, 1, 2   # option / stat "wgrad_kernel"
 CONV_MODE_LOWERED_GEMM, CONV_MODE_LOWERED_SPARSE, CONV_MODE_SCONV, CONV_MODE_SCONV_PAR = 0, 1, 2, 3
 
 # every symbol include/escoin.h declares (tests check the library exports all of them)
@@ -44,6 +45,7 @@ API_SYMBOLS = [
     "escoin_cpu_sparse_dense2csr", "escoin_cpu_sparse_dense2csr_f64",
     # Backward (pattern-preserving)
     "escoin_backward", "escoin_backward_f64", "escoin_backward_cpu", "escoin_backward_cpu_f64",
+    "escoin_backward_values", "escoin_backward_values_f64", "escoin_backward_values_cpu", "escoin_backward_values_cpu_f64",
     # Weight updates in place
     "escoin_update_values", "escoin_update_values_f64", "escoin_plan_set_values", "escoin_plan_set_values_f64",
     "escoin_update_values_cpu", "escoin_update_values_cpu_f64",
@@ -164,7 +166,9 @@ def lib():
             L.escoin_gpu_sparse_dense2csr_f64.argtypes = L.escoin_gpu_sparse_dense2csr.argtypes
             L.escoin_gpu_sparse_csrmm_f64.restype = ip
             L.escoin_gpu_sparse_csrmm_f64.argtypes = [ip, ip, ip, ip, real, vp, vp, vp, vp, real, vp, vp]
-    for name in ("escoin_backward", "escoin_backward_f64", "escoin_backward_cpu", "escoin_backward_cpu_f64"):
+    for name in ("escoin_backward", "escoin_backward_f64", "escoin_backward_cpu", "escoin_backward_cpu_f64",
+                 "escoin_backward_values", "escoin_backward_values_f64", "escoin_backward_values_cpu",
+                 "escoin_backward_values_cpu_f64"):
         f = getattr(L, name)
         f.restype, f.argtypes = ip, [vp] * 7 + [ip, vp if "cpu" not in name else ip]
     for name in ("escoin_update_values", "escoin_update_values_f64", "escoin_plan_set_values", "escoin_plan_set_values_f64"):
@@ -421,11 +425,14 @@ class Plan(object):
         d = self.desc
         return (d.C // d.group, d.KH, d.KW)
 
-    def backward(self, top_diff, bottom=None, top=None, bottom_diff=True, weight_diff=None, bias_diff=None):
+    def backward(self, top_diff, bottom=None, top=None, bottom_diff=True, weight_diff=None, bias_diff=None,
+                 values_diff=None):
         """Backward_gpu on torch CUDA tensors, on torch's current stream.  bottom_diff: True = a new tensor, a tensor =
         written (overwritten) in place, None / False = not computed.  weight_diff / bias_diff: True = a new zeroed tensor,
         a tensor = accumulated into (+=, at the CSR positions only for the weights), None / False = not computed.
-        Returns (bottom_diff, weight_diff, bias_diff)."""
+        values_diff (instead of weight_diff): the weight gradient in compact form, a 1-D tensor of nnz elements in
+        get_csr()'s order -- the order set_values() reads; True / tensor / None as for weight_diff.
+        Returns (bottom_diff, weight_diff or values_diff, bias_diff)."""
         import torch
         d = self.desc
         g = top_diff
@@ -442,8 +449,11 @@ class Plan(object):
             assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == tuple(shape)
             return t
 
+        compact = values_diff is not None and values_diff is not False
+        if compact and weight_diff is not None and weight_diff is not False:
+            raise EscoinError("backward: weight_diff and values_diff are two layouts of one gradient: ask for one")
         bd = _new_or(bottom_diff, (n, d.C, d.H, d.W), False)
-        wd = _new_or(weight_diff, (d.M,) + self._grad_shapes(), True)
+        wd = _new_or(values_diff, (self.nnz(),), True) if compact else _new_or(weight_diff, (d.M,) + self._grad_shapes(), True)
         bsd = _new_or(bias_diff, (d.M,), True)
         for t in (bottom, top):
             if t is not None:
@@ -453,12 +463,12 @@ class Plan(object):
             return C.c_void_p(t.data_ptr()) if t is not None else None
 
         stream = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
-        fn = lib().escoin_backward_f64 if dt == torch.float64 else lib().escoin_backward
+        fn = getattr(lib(), "escoin_backward" + ("_values" if compact else "") + ("_f64" if dt == torch.float64 else ""))
         check(fn(self._h, _p(bottom), _p(top), _p(g), _p(bd), _p(wd), _p(bsd), int(n), stream), "escoin_backward")
         return bd, wd, bsd
 
     def backward_cpu(self, top_diff, bottom=None, top=None, bottom_diff=True, weight_diff=None, bias_diff=None,
-                     n_threads=0):
+                     n_threads=0, values_diff=None):
         """Backward_cpu on numpy arrays (float32 or float64, matching the aligned weights); arguments and result as in
         backward()."""
         d = self.desc
@@ -476,8 +486,11 @@ class Plan(object):
             assert t.dtype == dt and t.flags["C_CONTIGUOUS"] and tuple(t.shape) == tuple(shape)
             return t
 
+        compact = values_diff is not None and values_diff is not False
+        if compact and weight_diff is not None and weight_diff is not False:
+            raise EscoinError("backward_cpu: weight_diff and values_diff are two layouts of one gradient: ask for one")
         bd = _new_or(bottom_diff, (n, d.C, d.H, d.W), False)
-        wd = _new_or(weight_diff, (d.M,) + self._grad_shapes(), True)
+        wd = _new_or(values_diff, (self.nnz(),), True) if compact else _new_or(weight_diff, (d.M,) + self._grad_shapes(), True)
         bsd = _new_or(bias_diff, (d.M,), True)
         x = None if bottom is None else np.ascontiguousarray(bottom, dt)
         t = None if top is None else np.ascontiguousarray(top, dt)
@@ -485,6 +498,6 @@ class Plan(object):
         def _p(a):
             return _np_ptr(a) if a is not None else None
 
-        fn = lib().escoin_backward_cpu_f64 if f64 else lib().escoin_backward_cpu
+        fn = getattr(lib(), "escoin_backward" + ("_values" if compact else "") + "_cpu" + ("_f64" if f64 else ""))
         check(fn(self._h, _p(x), _p(t), _p(g), _p(bd), _p(wd), _p(bsd), int(n), int(n_threads)), "escoin_backward_cpu")
         return bd, wd, bsd

@@ -74,7 +74,7 @@ DeviceBytes device_bytes(const escoin_plan *p) {
   if (const UpdState *u = p->upd.get())
     b.upd = u->src.bytes() + u->off.bytes() + u->buf.bytes() + u->wpos.bytes() + u->stage.bytes();
   if (const BwdState *s = p->bwd.get())
-    b.bwd = s->trow.bytes() + s->ttap.bytes() + s->tval.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() +
+    b.bwd = s->trow.bytes() + s->ttap.bytes() + s->tval.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() + s->stg_blk.bytes() + s->stg_off.bytes() +
             (s->tplan ? device_bytes(s->tplan.get()).fwd : 0);
   return b;
 }
@@ -87,6 +87,11 @@ long bwd_stat(const escoin_plan *p, const char *key) {
   }
   if (!strcmp(key, "bwd_device_bytes")) return (long)device_bytes(p).bwd;
   if (!strcmp(key, "bwd_chunks")) return s ? s->last_chunks : 0;
+  if (!strcmp(key, "wgrad_kernel")) {
+    if (!s || !s->last_wgrad) return fail(ESCOIN_ESTATE, "wgrad_kernel: no weight / bias gradient has run on this alignment");
+    return s->last_wgrad;
+  }
+  if (!strcmp(key, "wgrad_lds_bytes")) return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg_lds_bytes : 0;
   if (!strcmp(key, "bwd_align_us")) return s ? (long)(s->align_ms * 1e3) : 0;
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
@@ -548,6 +553,16 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->bwd_kernel = value;
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "wgrad_kernel")) {
+      if (value < ESCOIN_WGRAD_AUTO || value > ESCOIN_WGRAD_STAGED) return fail(ESCOIN_EINVAL, "wgrad_kernel must be 0 (auto), 1 (entry) or 2 (staged)");
+      p->wgrad_kernel = value;
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "wgrad_channel_block")) {
+      if (value < 0) return fail(ESCOIN_EINVAL, "wgrad_channel_block must be >= 0");
+      p->wgrad_channel_block = value;
+      return ESCOIN_OK;
+    }
     if (!strcmp(key, "stream_stores")) {
       if (value < -1 || value > 1) return fail(ESCOIN_EINVAL, "stream_stores must be -1, 0 or 1");
       p->stream_stores = value;
@@ -843,7 +858,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
     return (long)v;
   }
   if (!strcmp(key, "streamk")) return p->dense.sk_used ? 1 : 0;
-  if (!strncmp(key, "bwd_", 4)) return bwd_stat(p, key);
+  if (!strncmp(key, "bwd_", 4) || !strncmp(key, "wgrad_", 6)) return bwd_stat(p, key);
   if (!strncmp(key, "upd", 3)) return upd_stat(p, key);
   if (!strcmp(key, "is_f64")) return p->is_f64 ? 1 : 0;
   if (!strcmp(key, "host_aligned")) return p->host_aligned ? 1 : 0;

@@ -103,6 +103,15 @@ struct BwdState {
   DeviceBuffer g;      // fuse_relu + path (a): top_diff * [top > 0], desc.N x M x OH x OW
   long nnz = 0;
   int chunks_max = 0, last_chunks = 0;
+  // weight gradient, LDS-staged kernel (option "wgrad_kernel"): wgrad = what the option resolved to on this alignment,
+  // last_wgrad = what the last weight / bias gradient ran (0: none yet)
+  int wgrad = ESCOIN_WGRAD_ENTRY, last_wgrad = 0;
+  int stg_icb = 0, stg_nblk = 0;       // input channels per staged block, blocks per conv group
+  int stg_rows = 0;                    // padded rows of the LDS tile (the longest chunk's span)
+  int stg_osplit = 1;                  // workgroups a conv group's output channels are dealt over
+  size_t stg_lds_bytes = 0;
+  DeviceBuffer stg_blk;  // [M][stg_nblk + 1] absolute entry index where output channel oc's entries of block b begin
+  DeviceBuffer stg_off;  // [nnz] per CSR entry: its tap's float offset inside the staged block's LDS tile
   double align_ms = 0.0;
   // host: per entry of the transposed order (tplan's CSR, or ttap / tval) the index of the plan's CSR entry (groups
   // concatenated) it is a copy of -- how escoin_update_values reaches the backward state's values (update_values.hip)
@@ -220,6 +229,8 @@ struct escoin_plan {
   // Backward (sconv_backward.hip): option "backward_kernel" and the state the first escoin_backward builds; reset with
   // the device side (free_device), so weight_align / set_csr / import_aligned drop it
   int bwd_kernel = ESCOIN_KERNEL_AUTO;
+  int wgrad_kernel = ESCOIN_WGRAD_AUTO;   // option "wgrad_kernel"
+  int wgrad_channel_block = 0;            // option "wgrad_channel_block" (0: from the geometry and the LDS budget)
   std::unique_ptr<escoin::BwdState> bwd;
 
   // In-place weight updates (update_values.hip): the state the first escoin_update_values builds; reset with the device

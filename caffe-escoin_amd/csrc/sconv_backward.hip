@@ -231,7 +231,7 @@ __device__ inline void wgrad_sum_body(const T *__restrict__ slab_w, const T *__r
   if (weight_diff && e < nnz) {
     T s = 0;
     for (int c = 0; c < chunks; ++c) s += slab_w[(size_t)c * nnz + e];
-    const int pos = wpos[e];
+    const long pos = wpos ? wpos[e] : e;   // compact output (escoin_backward_values): entry e itself
     weight_diff[pos] = weight_diff[pos] + s;
     return;
   }
@@ -253,6 +253,227 @@ __global__ void __launch_bounds__(256)
 escoin_sconv_wgrad_sum_f64_kernel(const double *slab_w, const double *slab_b, const int *wpos, double *weight_diff,
                                   double *bias_diff, int nnz, int M, int chunks) {
   wgrad_sum_body<double>(slab_w, slab_b, wpos, weight_diff, bias_diff, nnz, M, chunks);
+}
+
+// ---- weight / bias gradient, LDS-staged (option "wgrad_kernel" = STAGED; float plans, stride 1) ---------------------
+// Stage 1 of the same two-stage reduction (same chunks, same slab), with the bottom read from global memory once per
+// workgroup instead of once per nonzero.  Stride 1 makes the padded input image the natural frame: with Hp = H + 2 pad_h
+// = OH + dil_h (KH - 1) and Wp likewise, output pixel (n, oh, ow) and tap (kr, kc) read padded pixel
+// (n * Hp + oh + kr * dil_h, ow + kc * dil_w) -- a per-lane base plus a wave-uniform tap offset.  One workgroup per
+// (chunk, slice of a conv group's output channels, block of input channels):
+//   staging   the padded rows the chunk's pixels touch (images stacked Hp rows apart, the halo and images past n_images
+//             as zeros), for the block's channels, into LDS -- once;
+//   walk      each wave takes whole output channels: G for all 1024 pixels of the chunk in registers (16 per lane), then
+//             the channel's CSR entries of this block (the host table stg_blk: rows are sorted by input channel); per
+//             entry 16 LDS reads and 16 FMAs into the lane's own partial, no cross-lane step;
+//   reduce    eight entries at a time: three halving exchanges (a lane keeps half the entries and receives its partner's
+//             partials for them), then a butterfly over the last three lane bits -- per entry the pairing (lane ^ 32,
+//             ^ 16, ... ^ 1) of wave_sum, so an entry's bits depend neither on its place in a batch nor on the blocking;
+//   bias      summed from the same registers by the workgroups of block 0; a bias-only call launches those alone, stages
+//             nothing and walks nothing.
+// An entry belongs to one (output channel, input-channel block): every slab element has one writer.  Dead pixels of the
+// last chunk are masked by select (their G is 0, but 0 x a staged non-finite value is not): a non-finite bottom element
+// reaches only the entries whose tap reads it.
+constexpr int kStgWaves = 8;                         // waves per workgroup
+constexpr int kStgPix = kChunkPixels / 64;           // pixels per lane: a wave covers the whole chunk
+constexpr int kStgBatch = 8;                         // entries per batched reduction
+constexpr size_t kStgLdsBudget = 64 * 1024;          // two workgroups per CU
+constexpr int kStgSmallInt = 1 << 21;                // div_small's range
+
+struct StagedArgs {
+  const float *__restrict__ bottom;
+  const float *__restrict__ top_diff;
+  const float *__restrict__ top;      // fuse_relu only
+  const int *__restrict__ blk;        // [M][nblk + 1]
+  const int *__restrict__ off;        // [nnz]
+  float *__restrict__ slab_w;         // [chunks][nnz]
+  float *__restrict__ slab_b;         // [chunks][M]
+  long total;                         // n_images * OH * OW
+  int nnz, n_images;
+  int C, H, W, M, OH, OW;
+  int pad_h, pad_w, span_h;           // span_h = dil_h * (KH - 1)
+  int Cg, Mg, Hp, Wp;
+  int icb, nblk, rows_max, cs;        // cs = rows_max * Wp: floats per staged channel
+  int osplit, mper;                   // slices per conv group, output channels per slice
+  int want_w, want_b;
+  float inv_opix, inv_ow, inv_wp, inv_hp;
+};
+
+// x / d for 0 <= x < kStgSmallInt through the float reciprocal, corrected: exact.
+__device__ inline int div_small(int x, int d, float inv, int &rem) {
+  int k = (int)((float)x * inv);
+  rem = x - k * d;
+  if (rem < 0) { --k; rem += d; }
+  else if (rem >= d) { ++k; rem -= d; }
+  return k;
+}
+
+// Sums v[k] over the wave for k < 8; lane l returns the total of entry l >> 3.
+__device__ inline float stg_reduce8(const float (&v)[kStgBatch], int lane) {
+  float t[4], u[2];
+  bool hi = (lane & 32) != 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) t[j] = (hi ? v[j + 4] : v[j]) + __shfl_xor(hi ? v[j] : v[j + 4], 32, 64);
+  hi = (lane & 16) != 0;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) u[j] = (hi ? t[j + 2] : t[j]) + __shfl_xor(hi ? t[j] : t[j + 2], 16, 64);
+  hi = (lane & 8) != 0;
+  float w = (hi ? u[1] : u[0]) + __shfl_xor(hi ? u[0] : u[1], 8, 64);
+  w += __shfl_xor(w, 4, 64);
+  w += __shfl_xor(w, 2, 64);
+  w += __shfl_xor(w, 1, 64);
+  return w;
+}
+
+template <bool RELU, bool PARTIAL>
+__device__ inline void stg_walk(const StagedArgs &a, const float *tile, int chunk, int grp, int part, int b, int wave,
+                                int lane, int n0, int r0, int P0) {
+  const int opix = a.OH * a.OW;
+  int base[kStgPix];
+  unsigned gb[kStgPix];
+  unsigned livemask = 0;
+#pragma unroll
+  for (int i = 0; i < kStgPix; ++i) {
+    const int ql = i * 64 + lane;
+    const bool live = (long)chunk * kChunkPixels + ql < a.total;
+    int r, ow;
+    const int dn = div_small(r0 + ql, opix, a.inv_opix, r);
+    const int oh = div_small(r, a.OW, a.inv_ow, ow);
+    const int n = n0 + dn;
+    base[i] = live ? ((n * a.Hp + oh - P0) * a.Wp + ow) : 0;
+    gb[i] = live ? (unsigned)n * (unsigned)a.M * (unsigned)opix + (unsigned)r : 0u;
+    livemask |= live ? (1u << i) : 0u;
+  }
+  const int m_end = min(a.Mg, (part + 1) * a.mper);
+  const bool bias_here = a.want_b && b == 0;
+  for (int m = part * a.mper + wave; m < m_end; m += kStgWaves) {
+    const int oc = grp * a.Mg + m;
+    const int jb = a.blk[(size_t)oc * (a.nblk + 1) + b];
+    const int je = a.want_w ? a.blk[(size_t)oc * (a.nblk + 1) + b + 1] : jb;
+    if (jb == je && !bias_here) continue;
+    float g[kStgPix];
+    const unsigned oco = (unsigned)oc * (unsigned)opix;
+#pragma unroll
+    for (int i = 0; i < kStgPix; ++i) {
+      float gv = 0.f;
+      if (!PARTIAL || ((livemask >> i) & 1u)) {
+        gv = a.top_diff[gb[i] + oco];
+        if (RELU && !(a.top[gb[i] + oco] > 0.f)) gv = 0.f;
+      }
+      g[i] = gv;
+    }
+    if (bias_here) {
+      float sb = g[0];
+#pragma unroll
+      for (int i = 1; i < kStgPix; ++i) sb += g[i];
+      sb = wave_sum(sb);
+      if (lane == 0) a.slab_b[(size_t)chunk * a.M + oc] = sb;
+    }
+    // the tap offsets of a batch are fetched one batch ahead (stg_off is padded by two batches): a scalar load shares
+    // its counter with the LDS reads, so waiting for one inside the walk would drain the other
+    int o[kStgBatch], o_next[kStgBatch] = {};
+    if (jb != je) {   // (a bias-only walk fetches nothing)
+#pragma unroll
+      for (int k = 0; k < kStgBatch; ++k) o_next[k] = a.off[jb + k];
+    }
+    for (int j0 = jb; j0 < je; j0 += kStgBatch) {
+      const int jn = min(kStgBatch, je - j0);
+#pragma unroll
+      for (int k = 0; k < kStgBatch; ++k) {
+        o[k] = o_next[k];
+        o_next[k] = a.off[j0 + kStgBatch + k];
+      }
+      float acc[kStgBatch];
+#pragma unroll
+      for (int k = 0; k < kStgBatch; ++k) {
+        acc[k] = 0.f;
+        if (k < jn) {
+#pragma unroll
+          for (int i = 0; i < kStgPix; ++i) {
+            float x = tile[base[i] + o[k]];
+            if (PARTIAL) x = ((livemask >> i) & 1u) ? x : 0.f;
+            acc[k] = fmaf(g[i], x, acc[k]);
+          }
+        }
+      }
+      const float t = stg_reduce8(acc, lane);
+      if ((lane & 7) == 0 && (lane >> 3) < jn) a.slab_w[(size_t)chunk * a.nnz + j0 + (lane >> 3)] = t;
+    }
+  }
+}
+
+template <bool RELU>
+__global__ void __launch_bounds__(64 * kStgWaves)
+escoin_sconv_wgrad_staged_kernel(StagedArgs a) {
+  extern __shared__ float stg_tile[];
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const int chunk = blockIdx.x;
+  const int grp = blockIdx.y / a.osplit, part = blockIdx.y - grp * a.osplit;
+  const int b = blockIdx.z;
+  const int opix = a.OH * a.OW;
+  const long q0 = (long)chunk * kChunkPixels;
+  const long q1 = min(a.total, q0 + kChunkPixels) - 1;
+  const int n0 = (int)(q0 / opix), r0 = (int)(q0 - (long)n0 * opix);
+  const int n1 = (int)(q1 / opix), r1 = (int)(q1 - (long)n1 * opix);
+  const int P0 = n0 * a.Hp + r0 / a.OW;
+  const int rows = min(n1 * a.Hp + r1 / a.OW + a.span_h - P0 + 1, a.rows_max);
+  if (a.want_w) {
+    const int ic0 = b * a.icb;
+    const int nch = min(a.icb, a.Cg - ic0);
+    const int count = nch * rows * a.Wp;
+    const size_t plane = (size_t)a.H * a.W;
+    const float inv_rows = 1.0f / (float)rows;
+    const int ihp0 = P0 - n0 * a.Hp;
+    const float *__restrict__ src = a.bottom + ((size_t)grp * a.Cg + ic0) * plane;
+    for (int idx = tid; idx < count; idx += 64 * kStgWaves) {
+      int col, r, ihp;
+      const int pr = div_small(idx, a.Wp, a.inv_wp, col);
+      const int ch = div_small(pr, rows, inv_rows, r);
+      const int n = n0 + div_small(ihp0 + r, a.Hp, a.inv_hp, ihp);
+      const int ih = ihp - a.pad_h, iw = col - a.pad_w;
+      float v = 0.f;
+      if (n < a.n_images && (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W)
+        v = src[((size_t)n * a.C + ch) * plane + (size_t)ih * a.W + iw];
+      stg_tile[ch * a.cs + r * a.Wp + col] = v;
+    }
+    __syncthreads();
+  }
+  if (q0 + kChunkPixels > a.total) stg_walk<RELU, true>(a, stg_tile, chunk, grp, part, b, wave, lane, n0, r0, P0);
+  else stg_walk<RELU, false>(a, stg_tile, chunk, grp, part, b, wave, lane, n0, r0, P0);
+}
+
+// Stage 2 of the staged path: 16 items (weight entries, then biases) per workgroup, the chunk axis dealt over 16 lanes
+// per item (lane c sums chunks c, c + 16, ... in that order), then the 16 partials in lane order, then += into the
+// gradient.  wpos == nullptr: compact output, entry e goes to weight_diff[e].
+__global__ void __launch_bounds__(256)
+escoin_sconv_wgrad_tree_sum_kernel(const float *__restrict__ slab_w, const float *__restrict__ slab_b,
+                                   const int *__restrict__ wpos, float *weight_diff, float *bias_diff, int nnz, int M,
+                                   int chunks) {
+  __shared__ float red[16][17];
+  const int el = threadIdx.x & 15, cl = threadIdx.x >> 4;
+  const long n_w = weight_diff ? nnz : 0;
+  const long items = n_w + (bias_diff ? M : 0);
+  const long item = (long)blockIdx.x * 16 + el;
+  float s = 0.f;
+  if (item < items) {
+    const float *col = item < n_w ? slab_w + item : slab_b + (item - n_w);
+    const size_t stride = item < n_w ? (size_t)nnz : (size_t)M;
+    for (int c = cl; c < chunks; c += 16) s += col[(size_t)c * stride];
+  }
+  red[cl][el] = s;
+  __syncthreads();
+  if (cl == 0 && item < items) {
+    float t = red[0][el];
+#pragma unroll
+    for (int k = 1; k < 16; ++k) t += red[k][el];
+    if (item < n_w) {
+      const long pos = wpos ? wpos[item] : item;
+      weight_diff[pos] = weight_diff[pos] + t;
+    } else {
+      bias_diff[item - n_w] = bias_diff[item - n_w] + t;
+    }
+  }
 }
 
 // ---- backward state ---------------------------------------------------------------------------------------------
@@ -365,6 +586,117 @@ static int build_gather(escoin_plan *p, BwdState *s, const std::vector<std::vect
   return ESCOIN_OK;
 }
 
+// The staged weight-gradient kernel's block plan (sconv_backward.hip header of that kernel): the LDS tile and the split
+// of a conv group's input channels into staged blocks.  AUTO's rule and stg_build both read this one.
+struct StgPlan {
+  int rows_max = 0;   // padded rows of the tile: the longest chunk's span
+  int cs = 0;         // floats per staged channel: rows_max * Wp
+  int icb = 0;        // input channels per staged block
+  int nblk = 0;       // blocks per conv group (grid z)
+  int chunks = 0;     // chunks of the full batch
+  int osplit = 1;     // workgroups a conv group's output channels are dealt over
+};
+
+// Whether the staged kernel serves this plan, and its block plan where it does.
+static bool stg_plan(const escoin_plan *p, StgPlan *sp) {
+  const Geometry &g = p->g;
+  const escoin_conv_desc &d = g.d;
+  if (p->is_f64 || d.stride_h != 1 || d.stride_w != 1) return false;
+  const long opix = (long)g.OH * g.OW;
+  const long Hp = (long)d.H + 2 * d.pad_h, Wp = (long)d.W + 2 * d.pad_w;
+  if (opix > kStgSmallInt / 2 || Hp > kStgSmallInt / 2 || Wp > kStgSmallInt / 2) return false;   // div_small
+  if ((double)d.N * d.M * (double)opix >= 2147483648.0 || (double)d.N * d.C * (double)d.H * d.W >= 2147483648.0) return false;
+  if ((double)d.N * (double)Hp >= 1073741824.0) return false;
+  // the longest span of padded rows a chunk touches
+  const long total = (long)d.N * opix;
+  const int span_h = d.dil_h * (d.KH - 1);
+  long rows = 0;
+  for (long q0 = 0; q0 < total; q0 += kChunkPixels) {
+    const long q1 = std::min(total, q0 + kChunkPixels) - 1;
+    const long n0 = q0 / opix, n1 = q1 / opix;
+    const long P0 = n0 * Hp + (q0 - n0 * opix) / g.OW, P1 = n1 * Hp + (q1 - n1 * opix) / g.OW + span_h;
+    rows = std::max(rows, P1 - P0 + 1);
+  }
+  if (rows < 1 || (size_t)rows * (size_t)Wp * sizeof(float) > kStgLdsBudget) return false;
+  sp->rows_max = (int)rows;
+  sp->cs = (int)(rows * Wp);
+  sp->icb = (int)std::min<size_t>((size_t)g.Cg, kStgLdsBudget / (sizeof(float) * (size_t)sp->cs));
+  if (p->wgrad_channel_block > 0) sp->icb = std::min(sp->icb, p->wgrad_channel_block);
+  sp->nblk = (g.Cg + sp->icb - 1) / sp->icb;
+  sp->chunks = (int)((total + kChunkPixels - 1) / kChunkPixels);
+  // enough workgroups for two per CU where the chunks and blocks alone do not give them: deal the output channels
+  const long wgs = (long)sp->chunks * d.group * sp->nblk;
+  const long want = 2L * std::max(tiled_device_cus(), 1);
+  const int osplit = (int)std::min<long>((g.Mg + kStgWaves - 1) / kStgWaves, (want + wgs - 1) / std::max(wgs, 1L));
+  sp->osplit = std::max(1, std::min(osplit, 65535 / std::max(d.group, 1)));
+  return sp->nblk <= 65535;   // grid z
+}
+
+// AUTO's rule for the weight gradient: a function of the geometry, nnz and the device's CU count only -- the two
+// kernels' times in microseconds from a cost model fitted to one MI355X run of tools/backward_bench.py
+// (profiles/backward_mi355x.md, "AUTO's rule": the fit, its coefficients and its residuals on the 47 benched layers).
+// Both kernels run in rounds of resident workgroups: the entry kernel's (chunk, output channel) workgroups of 4 waves
+// sit 8 to a CU, the staged kernel's 64 KiB workgroups 2 to a CU.  A last, partly filled round still costs a
+// workgroup's latency, hence the floor on its fraction.
+//   entry   21.3 + 0.153 chunks (its stage 2 walks the chunks serially) + rounds x (3.0 + 1.138 x entries per row)
+//   staged  13.4 + rounds x (19.3 (staging the tile) + steps x (1.02 (loading G) + 0.426 x entries per (row, block)))
+//           with steps = output channels a wave takes in turn
+static double stg_rounds(double workgroups, double resident, double tail_floor) {
+  const double r = workgroups / resident, whole = std::floor(r), tail = r - whole;
+  return whole + (tail > 0 ? std::max(tail, tail_floor) : 0.0);
+}
+static bool stg_auto_prefers(const escoin_plan *p, long nnz, const StgPlan &sp) {
+  const Geometry &g = p->g;
+  const escoin_conv_desc &d = g.d;
+  if (nnz <= 0) return false;
+  const double cus = (double)std::max(tiled_device_cus(), 1);
+  const double entry = 21.3 + 0.153 * sp.chunks +
+                       stg_rounds((double)sp.chunks * d.M, 8.0 * cus, 0.3) * (3.0 + 1.138 * (double)nnz / d.M);
+  const int steps = ((g.Mg + sp.osplit - 1) / sp.osplit + kStgWaves - 1) / kStgWaves;
+  const double per_pair = (double)nnz / ((double)d.M * sp.nblk);
+  const double staged = 13.4 + stg_rounds((double)sp.chunks * d.group * sp.nblk * sp.osplit, 2.0 * cus, 0.4) *
+                                   (19.3 + steps * (1.02 + 0.426 * per_pair));
+  return staged < entry;
+}
+
+static int stg_build(escoin_plan *p, BwdState *s, const StgPlan &sp, hipStream_t stream) {
+  const Geometry &g = p->g;
+  const escoin_conv_desc &d = g.d;
+  const int Wp = d.W + 2 * d.pad_w;
+  const int cs = sp.cs, icb = sp.icb, nblk = sp.nblk;
+  s->stg_icb = icb;
+  s->stg_nblk = nblk;
+  s->stg_rows = sp.rows_max;
+  s->stg_lds_bytes = sizeof(float) * (size_t)icb * (size_t)cs;
+  s->stg_osplit = sp.osplit;
+  const int kk = d.KH * d.KW;
+  std::vector<int> blk((size_t)d.M * (nblk + 1)), off((size_t)s->nnz + 2 * kStgBatch, 0);   // (padding: the walk reads ahead)
+  long base = 0;
+  for (int grp = 0; grp < d.group; ++grp) {
+    const std::vector<int> &rp = p->rowptr[grp], &ci = p->colidx[grp];
+    for (int m = 0; m < g.Mg; ++m) {
+      int *row = blk.data() + (size_t)(grp * g.Mg + m) * (nblk + 1);
+      int j = rp[m];
+      for (int b = 0; b <= nblk; ++b) {
+        // the columns of a row ascend (set_csr checks it), so its input channels do
+        while (b < nblk && j < rp[m + 1] && ci[j] / kk < b * icb) ++j;
+        if (b == nblk) j = rp[m + 1];
+        row[b] = (int)(base + j);
+      }
+      for (int e = rp[m]; e < rp[m + 1]; ++e) {
+        const int col = ci[e], icl = col / kk, kr = (col / d.KW) % d.KH, kc = col % d.KW;
+        off[(size_t)base + e] = (icl % icb) * cs + kr * d.dil_h * Wp + kc * d.dil_w;
+      }
+    }
+    base += (long)ci.size();
+  }
+  int rc = dev_upload(s->stg_blk, blk, stream);
+  if (rc == ESCOIN_OK) rc = dev_upload(s->stg_off, off, stream);
+  if (rc != ESCOIN_OK) return rc;
+  ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
+  return ESCOIN_OK;
+}
+
 template <typename T>
 static int bwd_build(escoin_plan *p, hipStream_t stream) {
   const auto t0 = std::chrono::steady_clock::now();
@@ -380,6 +712,11 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   if (forced && !transposable)
     return fail(ESCOIN_EINVAL, "backward_kernel: this plan has no transposed forward plan (needs a float plan, stride 1, "
                                "pad <= dilation * (kernel - 1)); only the gather kernel serves it");
+  StgPlan sp;
+  const bool staged_ok = stg_plan(p, &sp);
+  if (p->wgrad_kernel == ESCOIN_WGRAD_STAGED && !staged_ok)
+    return fail(ESCOIN_EINVAL, "wgrad_kernel: the staged weight-gradient kernel needs a float plan with stride 1 whose "
+                               "chunk tile of one input channel fits the LDS budget; only the entry kernel serves this plan");
   p->bwd.reset(new BwdState());
   BwdState *s = p->bwd.get();
   for (const auto &c : p->colidx) s->nnz += (long)c.size();
@@ -407,6 +744,12 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   s->chunks_max = (int)(((long)d.N * g.OH * g.OW + kChunkPixels - 1) / kChunkPixels);
   const size_t slab = sizeof(T) * (size_t)s->chunks_max * (size_t)(s->nnz + d.M);
   ESCOIN_HIP_TRY(s->slab.alloc(slab));
+  s->wgrad = ESCOIN_WGRAD_ENTRY;
+  if (staged_ok && (p->wgrad_kernel == ESCOIN_WGRAD_STAGED ||
+                    (p->wgrad_kernel == ESCOIN_WGRAD_AUTO && stg_auto_prefers(p, s->nnz, sp)))) {
+    if ((rc = stg_build(p, s, sp, stream)) != ESCOIN_OK) return rc;
+    s->wgrad = ESCOIN_WGRAD_STAGED;
+  }
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
   s->align_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   return ESCOIN_OK;
@@ -414,7 +757,7 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
 
 template <typename T>
 static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *top_diff, T *bottom_diff,
-                        T *weight_diff, T *bias_diff, int n_images, void *stream_v) {
+                        T *weight_diff, T *bias_diff, int n_images, void *stream_v, bool compact) {
   if (!p) return fail(ESCOIN_EINVAL, "null plan");
   if (!p->aligned) return fail(ESCOIN_ESTATE, "backward called before weight_align / set_csr");
   if (p->is_f64 != (sizeof(T) == 8))
@@ -490,6 +833,38 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
     a.dil_h = d.dil_h; a.dil_w = d.dil_w; a.Cg = g.Cg; a.Mg = g.Mg;
     a.want_w = weight_diff != nullptr;
     a.want_b = bias_diff != nullptr;
+    // compact output (escoin_backward_values): stage 2 writes entry e to weight_diff[e]
+    const int *wpos = compact ? nullptr : s->wpos.get<int>();
+    s->last_wgrad = s->wgrad;
+    if constexpr (sizeof(T) == 4) {
+      if (s->wgrad == ESCOIN_WGRAD_STAGED) {
+        StagedArgs sa;
+        sa.bottom = bottom; sa.top_diff = top_diff; sa.top = top;
+        sa.blk = s->stg_blk.get<int>(); sa.off = s->stg_off.get<int>();
+        sa.slab_w = slab_w; sa.slab_b = slab_b;
+        sa.total = total; sa.nnz = (int)s->nnz; sa.n_images = n_images;
+        sa.C = d.C; sa.H = d.H; sa.W = d.W; sa.M = d.M; sa.OH = g.OH; sa.OW = g.OW;
+        sa.pad_h = d.pad_h; sa.pad_w = d.pad_w; sa.span_h = d.dil_h * (d.KH - 1);
+        sa.Cg = g.Cg; sa.Mg = g.Mg; sa.Hp = d.H + 2 * d.pad_h; sa.Wp = d.W + 2 * d.pad_w;
+        sa.icb = s->stg_icb; sa.nblk = s->stg_nblk; sa.rows_max = s->stg_rows; sa.cs = s->stg_rows * sa.Wp;
+        sa.osplit = s->stg_osplit; sa.mper = (g.Mg + s->stg_osplit - 1) / s->stg_osplit;
+        sa.want_w = a.want_w; sa.want_b = a.want_b;
+        sa.inv_opix = 1.0f / (float)(g.OH * g.OW); sa.inv_ow = 1.0f / (float)g.OW;
+        sa.inv_wp = 1.0f / (float)sa.Wp; sa.inv_hp = 1.0f / (float)sa.Hp;
+        const dim3 sgrid(chunks, d.group * s->stg_osplit, a.want_w ? s->stg_nblk : 1), sblock(64 * kStgWaves);
+        const size_t lds = a.want_w ? s->stg_lds_bytes : 0;
+        if (relu) hipLaunchKernelGGL(escoin_sconv_wgrad_staged_kernel<true>, sgrid, sblock, lds, stream, sa);
+        else hipLaunchKernelGGL(escoin_sconv_wgrad_staged_kernel<false>, sgrid, sblock, lds, stream, sa);
+        ESCOIN_HIP_TRY(hipGetLastError());
+        const long items = (weight_diff ? s->nnz : 0) + (bias_diff ? d.M : 0);
+        if (items > 0) {
+          hipLaunchKernelGGL(escoin_sconv_wgrad_tree_sum_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, stream,
+                             slab_w, slab_b, wpos, weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
+          ESCOIN_HIP_TRY(hipGetLastError());
+        }
+        return ESCOIN_OK;
+      }
+    }
     const dim3 grid(chunks, d.M), block(64 * kBwdWaves);
     if (d.M > 65535) return fail(ESCOIN_EINVAL, "backward: more than 65535 output channels");
     if constexpr (sizeof(T) == 8) {
@@ -504,10 +879,10 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
     if (lanes > 0) {
       const dim3 sgrid((unsigned)((lanes + 255) / 256));
       if constexpr (sizeof(T) == 8)
-        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_f64_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, s->wpos.get<int>(),
+        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_f64_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, wpos,
                            weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
       else
-        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, s->wpos.get<int>(),
+        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, wpos,
                            weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
       ESCOIN_HIP_TRY(hipGetLastError());
     }
@@ -525,7 +900,7 @@ int escoin_backward(escoin_plan *plan, const float *bottom_dev, const float *top
                     float *bottom_diff_dev, float *weight_diff_dev, float *bias_diff_dev, int n_images, void *stream) {
   return guarded([&]() -> int {
     return backward_gpu<float>(plan, bottom_dev, top_dev, top_diff_dev, bottom_diff_dev, weight_diff_dev, bias_diff_dev,
-                               n_images, stream);
+                               n_images, stream, false);
   });
 }
 
@@ -534,7 +909,25 @@ int escoin_backward_f64(escoin_plan *plan, const double *bottom_dev, const doubl
                         void *stream) {
   return guarded([&]() -> int {
     return backward_gpu<double>(plan, bottom_dev, top_dev, top_diff_dev, bottom_diff_dev, weight_diff_dev,
-                                bias_diff_dev, n_images, stream);
+                                bias_diff_dev, n_images, stream, false);
+  });
+}
+
+int escoin_backward_values(escoin_plan *plan, const float *bottom_dev, const float *top_dev, const float *top_diff_dev,
+                           float *bottom_diff_dev, float *values_diff_dev, float *bias_diff_dev, int n_images,
+                           void *stream) {
+  return guarded([&]() -> int {
+    return backward_gpu<float>(plan, bottom_dev, top_dev, top_diff_dev, bottom_diff_dev, values_diff_dev, bias_diff_dev,
+                               n_images, stream, true);
+  });
+}
+
+int escoin_backward_values_f64(escoin_plan *plan, const double *bottom_dev, const double *top_dev,
+                               const double *top_diff_dev, double *bottom_diff_dev, double *values_diff_dev,
+                               double *bias_diff_dev, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    return backward_gpu<double>(plan, bottom_dev, top_dev, top_diff_dev, bottom_diff_dev, values_diff_dev,
+                                bias_diff_dev, n_images, stream, true);
   });
 }
 

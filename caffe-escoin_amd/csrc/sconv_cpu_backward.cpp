@@ -25,7 +25,7 @@ template <> const std::vector<std::vector<double>> &plan_values_bwd<double>(cons
 
 template <typename T>
 static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *top_diff, T *bottom_diff, T *weight_diff,
-                        T *bias_diff, int n_images, int n_threads) {
+                        T *bias_diff, int n_images, int n_threads, bool compact) {
   if (!p) return fail(ESCOIN_EINVAL, "null plan");
   if (!p->host_aligned) return fail(ESCOIN_ESTATE, "backward_cpu called before weight_align / set_csr");
   if (p->is_f64 != (sizeof(T) == 8))
@@ -47,6 +47,9 @@ static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *
   const int kk = d.KH * d.KW;
   const size_t plane = (size_t)d.H * d.W, opix = (size_t)g.OH * g.OW;
   const auto &values = plan_values_bwd<T>(p);
+  // compact (escoin_backward_values_cpu): weight_diff is the nnz-element array in get_csr order, groups concatenated
+  std::vector<size_t> group_base(d.group, 0);
+  for (int grp = 1; grp < d.group; ++grp) group_base[grp] = group_base[grp - 1] + p->colidx[grp - 1].size();
   // G at (n, oc, pixel)
   auto grad_at = [&](size_t gi) -> T { return relu && !(top[gi] > T(0)) ? T(0) : top_diff[gi]; };
 
@@ -110,7 +113,7 @@ static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *
             }
           }
         }
-        const size_t pos = (size_t)oc * g.kdim + col;
+        const size_t pos = compact ? group_base[grp] + (size_t)j : (size_t)oc * g.kdim + col;
         weight_diff[pos] = weight_diff[pos] + s;
       }
     });
@@ -128,7 +131,7 @@ extern "C" {
 int escoin_backward_cpu(escoin_plan *plan, const float *bottom, const float *top, const float *top_diff,
                         float *bottom_diff, float *weight_diff, float *bias_diff, int n_images, int n_threads) {
   return guarded([&]() -> int {
-    return cpu::backward_cpu<float>(plan, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images, n_threads);
+    return cpu::backward_cpu<float>(plan, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images, n_threads, false);
   });
 }
 
@@ -136,7 +139,23 @@ int escoin_backward_cpu_f64(escoin_plan *plan, const double *bottom, const doubl
                             double *bottom_diff, double *weight_diff, double *bias_diff, int n_images, int n_threads) {
   return guarded([&]() -> int {
     return cpu::backward_cpu<double>(plan, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images,
-                                     n_threads);
+                                     n_threads, false);
+  });
+}
+
+int escoin_backward_values_cpu(escoin_plan *plan, const float *bottom, const float *top, const float *top_diff,
+                               float *bottom_diff, float *values_diff, float *bias_diff, int n_images, int n_threads) {
+  return guarded([&]() -> int {
+    return cpu::backward_cpu<float>(plan, bottom, top, top_diff, bottom_diff, values_diff, bias_diff, n_images, n_threads, true);
+  });
+}
+
+int escoin_backward_values_cpu_f64(escoin_plan *plan, const double *bottom, const double *top, const double *top_diff,
+                                   double *bottom_diff, double *values_diff, double *bias_diff, int n_images,
+                                   int n_threads) {
+  return guarded([&]() -> int {
+    return cpu::backward_cpu<double>(plan, bottom, top, top_diff, bottom_diff, values_diff, bias_diff, n_images,
+                                     n_threads, true);
   });
 }
 

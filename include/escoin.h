@@ -411,7 +411,26 @@ ESCOIN_API int escoin_cpu_sparse_dense2csr_f64(int M, int N, const double *A, do
  * backward fails with ESCOIN_EINVAL where there is none).
  * Stats: "bwd_data_kernel" (ESCOIN_KERNEL_GENERIC = the gather kernel, otherwise the transposed plan's resolved kernel;
  * ESCOIN_ESTATE before the first backward), "bwd_device_bytes", "bwd_chunks" (chunks the last weight / bias gradient
- * reduced over), "bwd_align_us" (build time of the backward state). */
+ * reduced over), "bwd_align_us" (build time of the backward state).
+ * Option "wgrad_kernel" (before the align): which stage 1 produces the per-chunk partials of the weight / bias gradient.
+ * ESCOIN_WGRAD_ENTRY = escoin_sconv_wgrad_partial_kernel, which reads the bottom from global memory once per nonzero,
+ * then escoin_sconv_wgrad_sum_kernel.  ESCOIN_WGRAD_STAGED = escoin_sconv_wgrad_staged_kernel: one workgroup per (chunk,
+ * slice of output channels, block of input channels) stages the chunk's padded bottom rows of the block in LDS once;
+ * each wave holds G of one output channel for the whole chunk in registers and walks that channel's entries of the block
+ * with one LDS read per FMA, reducing across lanes eight entries at a time; then escoin_sconv_wgrad_tree_sum_kernel,
+ * which deals the chunk axis over 16 lanes per entry.  It serves float plans with stride 1 (any pad, dilation, group
+ * count, KH != KW) whose tile of one input channel fits 64 KiB of LDS; forcing it elsewhere makes the first backward fail
+ * with ESCOIN_EINVAL.  ESCOIN_WGRAD_AUTO (default) = the staged kernel where it serves the plan and a cost model of the
+ * two kernels -- a function of the geometry, nnz and the device's CU count, never a timing -- has it faster (the model,
+ * its fit and its measurements: profiles/backward_mi355x.md).  The two kernels sum in different orders: the low bits of the gradient differ between
+ * them, each is deterministic.  The chunks and the slab are the same ("bwd_chunks" keeps its meaning).
+ * Option "wgrad_channel_block" (test option, before the align): 0 = as many input channels per staged block as the
+ * LDS budget holds, n = at most n.  Results do not depend on it.
+ * Stats: "wgrad_kernel" (ESCOIN_WGRAD_ENTRY / _STAGED: what the last weight / bias gradient ran; ESCOIN_ESTATE before
+ * the first one), "wgrad_lds_bytes" (LDS of a staged workgroup; 0 on the entry kernel). */
+#define ESCOIN_WGRAD_AUTO 0
+#define ESCOIN_WGRAD_ENTRY 1   /* escoin_sconv_wgrad_partial_kernel: one workgroup per (chunk, output channel) */
+#define ESCOIN_WGRAD_STAGED 2  /* escoin_sconv_wgrad_staged_kernel: the chunk's bottom staged in LDS */
 ESCOIN_API int escoin_backward(escoin_plan *plan, const float *bottom_dev, const float *top_dev, const float *top_diff_dev,
                     float *bottom_diff_dev, float *weight_diff_dev, float *bias_diff_dev, int n_images, void *stream);
 ESCOIN_API int escoin_backward_f64(escoin_plan *plan, const double *bottom_dev, const double *top_dev,
@@ -423,6 +442,26 @@ ESCOIN_API int escoin_backward_cpu(escoin_plan *plan, const float *bottom, const
                         float *bottom_diff, float *weight_diff, float *bias_diff, int n_images, int n_threads);
 ESCOIN_API int escoin_backward_cpu_f64(escoin_plan *plan, const double *bottom, const double *top, const double *top_diff,
                             double *bottom_diff, double *weight_diff, double *bias_diff, int n_images, int n_threads);
+
+/* The same backward with the weight gradient in COMPACT form: values_diff holds nnz elements in the order of
+ * escoin_plan_get_csr, groups concatenated -- the order escoin_plan_set_values reads, so a solver can run on compact
+ * tensors (v -= lr * values_diff; escoin_plan_set_values(v)) and a data-parallel all-reduce moves nnz values, not a
+ * blob that is 90-95 % zeros.  values_diff is accumulated (+=); explicit zeros of the CSR receive a gradient; nothing
+ * outside the nnz elements is touched.  Everything else is escoin_backward's contract with values_diff in the place
+ * of weight_diff (bottom required iff values_diff != NULL, the same errors, determinism, no allocation after the first
+ * call).  No new work: stage 2 of the reduction writes entry e to values_diff[e] instead of weight_diff[position of e],
+ * so for the same "wgrad_kernel" values_diff equals weight_diff gathered at the CSR positions bit for bit. */
+ESCOIN_API int escoin_backward_values(escoin_plan *plan, const float *bottom_dev, const float *top_dev,
+                           const float *top_diff_dev, float *bottom_diff_dev, float *values_diff_dev,
+                           float *bias_diff_dev, int n_images, void *stream);
+ESCOIN_API int escoin_backward_values_f64(escoin_plan *plan, const double *bottom_dev, const double *top_dev,
+                               const double *top_diff_dev, double *bottom_diff_dev, double *values_diff_dev,
+                               double *bias_diff_dev, int n_images, void *stream);
+ESCOIN_API int escoin_backward_values_cpu(escoin_plan *plan, const float *bottom, const float *top, const float *top_diff,
+                               float *bottom_diff, float *values_diff, float *bias_diff, int n_images, int n_threads);
+ESCOIN_API int escoin_backward_values_cpu_f64(escoin_plan *plan, const double *bottom, const double *top,
+                                   const double *top_diff, double *bottom_diff, double *values_diff,
+                                   double *bias_diff, int n_images, int n_threads);
 
 /* ---- Weight updates: the second half of a training step -------------------------------------------------------------
  *   Solver::ApplyUpdate -> Net::Update -> Blob::Update (solver.cpp, blob.cpp) changes blobs_[0]; the reference then has
@@ -437,7 +476,8 @@ ESCOIN_API int escoin_backward_cpu_f64(escoin_plan *plan, const double *bottom, 
  *            must call escoin_weight_align.  A kept weight whose new value is exactly 0 stays in the CSR as an explicit
  *            zero (-0.0 stays -0.0).
  *   values   (escoin_plan_set_values) the compact array, nnz elements in the order of escoin_plan_get_csr -- what rank 0
- *            would broadcast after a step instead of a blob.
+ *            would broadcast after a step instead of a blob.  escoin_backward_values writes its values_diff in the same
+ *            order: element e of one is the gradient of element e of the other.
  * The pattern, tiling, kernel choice, channel deal, the generated code's instructions, every device allocation and the
  * backward state stay.  After the call every consumer of the plan -- escoin_forward in all four conv_modes (a later flip
  * to or from LOWERED_GEMM included), escoin_backward's data gradient on the transposed plan or the gather kernel,

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Backward on the MI355X: per layer, forward / data-gradient / weight-gradient / bias-gradient time of the
 pattern-preserving backward (escoin_backward), the kernels that ran, and the same shapes through torch's dense conv
-backward (MIOpen, dense weights) as a comparison point.
+backward (MIOpen, dense weights) as a comparison point.  The weight gradient is timed three ways in the same call, on
+separate plans: option wgrad_kernel = ENTRY, = STAGED (skipped where the staged kernel does not serve the plan) and the
+default AUTO; the compact entry point (escoin_backward_values) on the AUTO plan.
 
 Sets: the four ResNet-50 3x3 shapes @90 % (batch 256), the GoogLeNet 1x1 layers @95 % (batch 256), AlexNet conv2-5
 @80 % (batch 128).  Times are device events around `--reps` back-to-back calls after a warm-up, the median of
@@ -23,7 +25,16 @@ FAMILY = {0: "auto", 1: "gather (escoin_sconv_bwd_data_kernel)", 2: "tiled (tran
           3: "dense MFMA (transposed plan)", 4: "generated code (transposed plan)"}
 
 
+WGRAD = {1: "entry", 2: "staged"}
+
+
 def timed(fn, regions, reps):
+    out = timed_regions(fn, regions, reps)
+    return out[len(out) // 2]
+
+
+def timed_regions(fn, regions, reps):
+    """Sorted per-call times (us) of `regions` regions of `reps` back-to-back calls."""
     import torch
     for _ in range(2):
         fn()
@@ -38,7 +49,7 @@ def timed(fn, regions, reps):
         e1.synchronize()
         out.append(e0.elapsed_time(e1) * 1e3 / reps)
     out.sort()
-    return out[len(out) // 2]
+    return out
 
 
 def main():
@@ -81,6 +92,25 @@ def main():
         r["bwd_data_us"] = timed(lambda: plan.backward(td, bottom_diff=bd), a.regions, a.reps)
         r["bwd_weight_us"] = timed(lambda: plan.backward(td, bottom=x, bottom_diff=None, weight_diff=wd), a.regions, a.reps)
         r["bwd_bias_us"] = timed(lambda: plan.backward(td, bottom_diff=None, bias_diff=bsd), a.regions, a.reps)
+        r["wgrad_kernel"] = WGRAD[plan.stat("wgrad_kernel")]
+        r["wgrad_lds_bytes"] = plan.stat("wgrad_lds_bytes")
+        vd = torch.zeros((plan.nnz(),), device=dev)
+        r["bwd_values_us"] = timed(lambda: plan.backward(td, bottom=x, bottom_diff=None, values_diff=vd), a.regions, a.reps)
+        for kid in (pkg.WGRAD_ENTRY, pkg.WGRAD_STAGED):
+            forced = pkg.Plan(pkg.ConvDesc.from_shape(s), wgrad_kernel=kid)
+            forced.weight_align(w)
+            key = "bwd_weight_%s" % WGRAD[kid]
+            try:
+                forced.backward(td, bottom=x, bottom_diff=None, weight_diff=wd)
+            except pkg.EscoinError:
+                r[key + "_us"] = None          # the staged kernel does not serve this plan
+                forced.close()
+                continue
+            regions = timed_regions(lambda: forced.backward(td, bottom=x, bottom_diff=None, weight_diff=wd), a.regions, a.reps)
+            r[key + "_us"] = regions[len(regions) // 2]
+            r[key + "_spread_us"] = [regions[0], regions[-1]]
+            r["bwd_bias_%s_us" % WGRAD[kid]] = timed(lambda: forced.backward(td, bottom_diff=None, bias_diff=bsd), a.regions, a.reps)
+            forced.close()
         r["data_over_fwd"] = round(r["bwd_data_us"] / r["fwd_us"], 3)
         r["weight_over_fwd"] = round(r["bwd_weight_us"] / r["fwd_us"], 3)
         if not a.no_torch:
@@ -91,8 +121,10 @@ def main():
             r["torch_weight_us"] = timed(lambda: conv_bwd(td, x, wdense, None, *args, [False, True, False]), a.regions, a.reps)
         plan.close()
         rows.append(r)
-        print("%-28s fwd %8.1f  data %8.1f  weight %8.1f  bias %7.1f us  [%s]%s" % (
-            s.name, r["fwd_us"], r["bwd_data_us"], r["bwd_weight_us"], r["bwd_bias_us"], r["bwd_data_kernel"],
+        print("%-28s fwd %8.1f  data %8.1f  weight %8.1f (%s; entry %s staged %s; compact %.1f)  bias %7.1f us  [%s]%s" % (
+            s.name, r["fwd_us"], r["bwd_data_us"], r["bwd_weight_us"], r["wgrad_kernel"],
+            "%.1f" % r["bwd_weight_entry_us"], "-" if r["bwd_weight_staged_us"] is None else "%.1f" % r["bwd_weight_staged_us"],
+            r["bwd_values_us"], r["bwd_bias_us"], r["bwd_data_kernel"],
             "" if a.no_torch else "  torch data %8.1f weight %8.1f" % (r["torch_data_us"], r["torch_weight_us"])),
             file=sys.stderr, flush=True)
     print(json.dumps(dict(tool="backward_bench", device=torch.cuda.get_device_name(0), layers=rows)))
