@@ -1,0 +1,434 @@
+// align_rules.cpp -- WeightAlign's decisions as functions of values (align_rules.h).  No HIP, no device, no plan.
+#include "align_rules.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+
+#include "knobs.h"
+
+namespace escoin {
+
+// Density above which KERNEL_AUTO sends a conv group to the dense fp32-MFMA kernel: the measured
+// crossover between the tiled sparse kernel and the dense kernel (profiles/r02_crossover.md).
+constexpr int kDefaultDenseThresholdPct = 50;
+constexpr int kGenericDenseThresholdPct = 4;
+
+// ---- which conv groups go to the dense (fp32 MFMA) kernel -------------------------------
+//  * kernel DENSE or conv_mode LOWERED_GEMM (forward_gpu_gemm, base_conv_layer.cpp:713-746): all;
+//  * dense_gate = 1: the reference's gate -- group 0's density decides for the whole layer
+//    (nz_num_[0] / (M/g * kernel_dim) > 0.2, base_conv_layer.cpp:750, :805; quirk 5);
+//  * otherwise (AUTO): each group by its own density against the measured crossover
+//    (profiles/r02_crossover.md; option "dense_threshold_pct" overrides).
+std::vector<char> dense_groups(const Geometry &g, const std::vector<long> &nnz_per_group, const SplitOptions &o, int n_cu) {
+  const int G = g.d.group;
+  std::vector<char> dense(G, 0);
+  const double per_group = (double)g.Mg * g.kdim;
+  long nnz = 0;
+  for (long n_g : nnz_per_group) nnz += n_g;
+  if (o.kernel == ESCOIN_KERNEL_DENSE || o.conv_mode == ESCOIN_CONV_MODE_LOWERED_GEMM) {
+    dense.assign(G, 1);
+  } else if (o.kernel == ESCOIN_KERNEL_AUTO) {
+    if (o.dense_gate) {
+      if ((double)nnz_per_group[0] / per_group > 0.2) dense.assign(G, 1);
+    } else {
+      // a geometry the tiled kernels do not cover (stride / dilation != 1) has only the generic kernel on
+      // the sparse side -- one lane per output pixel, ~2 sparse TFLOP/s -- against 65-110 dense TFLOP/s:
+      // the MFMA kernel wins from ~4 % density on (ResNet-50's stride-2 1x1 layers pruned @90 %:
+      // 2.2-2.7 ms generic vs 0.17-0.58 ms dense, profiles/r04_chain_prune_1x1.md)
+      const bool fast_sparse = tiled_supported(g, n_cu);
+      const int auto_thr = fast_sparse ? kDefaultDenseThresholdPct : kGenericDenseThresholdPct;
+      const double thr = (o.dense_threshold_pct >= 0 ? o.dense_threshold_pct : auto_thr) / 100.0;
+      // Above the cut the dense kernel used to win by rule.  With generated code on every sparse layer it
+      // does not: measured crossovers (profiles/r04_crossover.md) sit between 53 % density (AlexNet conv3, whose
+      // 507 output tiles fill the 512 MFMA slots exactly) and > 90 % (res2, 64 output channels: half-empty
+      // 64 x 128 tiles) -- no single density separates them, what WeightAlign knows about the two kernels does:
+      //   dense  = rounds of 128 x 128 (64 x 128 when a group has <= 64 channels) output tiles on 512 slots at
+      //            120 TFLOP/s (x 0.7 for the narrow tiles), no faster than the blobs at 4.0 TB/s;
+      //   sparse = 50 us + 2 * pixels * nonzeros at 80 TFLOP/s (3x3 / 5x5), 20 us + ... at 68 (1x1), no faster than
+      //            the blobs at 4.8 TB/s.
+      // Re-fitted in round 5 (profiles/r05_crossover.md; round 4's constants -- 25 us + 68 / 58 TFLOP/s against 110 --
+      // were fitted to generated code that still moved a literal per nonzero, and on round 5's code sent res2 @10 %
+      // sparsity to the dense kernel at 782 us against 588, res4 / res5 @20 % at 688 / 682 against 583 / 574).
+      // Worst regret over the 14 shapes x 12 sparsities of the table: 7.7 % (round 4's constants on this table: 33 %;
+      // a fixed 50 % cut: 42 %).  The model only ever decides ABOVE the cut; below it the sparse kernel always won, and
+      // above 92 % density the dense one (an unpruned layer is never turned into megabytes of code).  An explicit
+      // dense_threshold_pct option is obeyed as given.
+      auto model_says_dense = [&](long nnz_g) {
+        if ((double)nnz_g > 0.92 * per_group) return true;
+        const double n = (double)(o.tiling_batch > 0 ? o.tiling_batch : g.d.N);
+        const double pix = n * g.OH * g.OW;
+        const int tm = g.Mg <= 64 ? 64 : 128;
+        const double tiles = std::ceil((double)g.Mg / tm) * std::ceil(pix / 128.0);
+        const double rounds = std::ceil(tiles / 512.0);
+        const double byt = 4.0 * n * ((double)g.Cg * g.d.H * g.d.W + (double)g.Mg * g.OH * g.OW);
+        const double t_dense = std::max(rounds * 2.0 * tm * 128.0 * g.kdim / (120e6 * (tm == 64 ? 0.7 : 1.0) / 512.0), byt / 4.0e6);
+        const double t_sparse = std::max((g.d.KH * g.d.KW > 1 ? 50.0 : 20.0) + 2.0 * pix * (double)nnz_g / (g.d.KH * g.d.KW > 1 ? 80e6 : 68e6), byt / 4.8e6 + 8.0);
+        return t_dense < t_sparse;
+      };
+      const bool use_model = o.dense_threshold_pct < 0 && fast_sparse;
+      if (G <= 64) {
+        for (int grp = 0; grp < G; ++grp) {
+          const long n_g = nnz_per_group[grp];
+          dense[grp] = (double)n_g / per_group > thr && (!use_model || model_says_dense(n_g));
+        }
+      } else if ((double)nnz / (per_group * G) > thr && (!use_model || model_says_dense(nnz / G))) {
+        dense.assign(G, 1);
+      }
+    }
+  }
+  return dense;
+}
+
+GroupSplit group_split(const std::vector<char> &dense) {
+  const int G = (int)dense.size();
+  GroupSplit s;
+  for (int grp = 0; grp < G; ++grp)
+    if (dense[grp]) {
+      ++s.n_dense;
+      if (grp < 64) s.dense_mask |= 1ull << grp;
+    }
+  s.n_sparse = G - s.n_dense;
+  s.use_dense = s.n_dense == G;
+  if (s.use_dense) s.dense_mask = ~0ull;
+  s.sparse_mask = s.n_dense == 0 ? ~0ull : ~s.dense_mask & (G >= 64 ? ~0ull : ((1ull << G) - 1));
+  return s;
+}
+
+// Workgroup shape: 8 waves sharing one staged input tile, 64 KB of planes per buffer (measured
+// best over {1,2,4,8} waves x {16,32,64} KB on the ResNet / AlexNet / GoogLeNet layer sets).
+// (The weight stream stores LDS row offsets / 32 in 11-bit fields: a plane buffer may not exceed
+// 64 KiB, whatever ESCOIN_LDS_KB says.)
+int default_lds_budget() {
+  static const int lds_kb = (int)ESC_KNOB("LDS_KB", kLdsBudget / 1024);
+  return std::max(4, std::min(lds_kb, 64)) * 1024;
+}
+
+Tiling pick_tiling(const Geometry &g, int n_cu, int lds_budget, float density, int tiling_batch, bool one_tile_ok,
+                   int waves_per_wg) {
+  // tuning overrides for experiments: ESCOIN_WAVES (1,2,4,8), ESCOIN_LDS_KB
+  static const int knob_waves = (int)ESC_KNOB("WAVES", kTiledWaves);
+  const int waves = waves_per_wg > 0 ? waves_per_wg : knob_waves;
+  ConvGeom c = to_geom(g);
+  c.density = density;
+  if (tiling_batch > 0) c.N = tiling_batch;   // plan option "tiling_batch": tile as for this batch
+  return choose_tiling(c, waves, lds_budget > 0 ? lds_budget : default_lds_budget(), n_cu, one_tile_ok);
+}
+
+bool tiled_supported(const Geometry &g, int n_cu) {
+  if ((g.d.stride_h != 1 || g.d.stride_w != 1 || g.d.dil_h != 1 || g.d.dil_w != 1) && !strided_pointwise(g)) return false;
+  Tiling t = pick_tiling(g, n_cu);
+  if (!t.ok) return false;
+  return true;
+}
+
+std::string tiling_info(const Tiling &t, bool jit, int nbuf, size_t lds_bytes, int tab_len, bool chained) {
+  char b[320];
+  snprintf(b, sizeof(b), "%s cut=%dx%d S4=%d tpl=%d G=%d n_ocg=%d columns=%d oc_waves=%d pix_waves=%d tr=%d nseg=%d band=%d bands=%d "
+           "qpc=%d icb=%d n_icb=%d nbuf=%d lds=%zu dma_in_code=%d period=%d chained=%d", jit ? "generated-code" : "stream", t.H, t.W, t.S4, t.tpl,
+           t.G, t.n_ocg, t.n_ocblk, t.oc_waves, t.pix_waves, t.tr, t.nseg, (int)t.band_mode, t.bands, t.plane_ch_floats / 4, t.icb,
+           t.n_icb, nbuf, lds_bytes, (int)(tab_len > 0), tab_len, (int)chained);
+  return b;
+}
+
+// Small launches.  The LDS-tiled kernels walk a tile block by block, every block a round trip to HBM, on as many
+// workgroups as the batch has tiles x columns: 11-19 us for one image of a GoogLeNet 1x1 layer; the generic kernel
+// puts a lane on every output pixel of the whole chip and needs 7-12 (profiles/r04_batch_sweep.md -- the reference's
+// SCONV mode calls the layer image by image, conv_layer.cu:16-26).  Round 4 TIMED both kernels; a layer's bits then
+// depended on the box's noise (two ranks could settle differently).  Now a RULE decides, from what WeightAlign knows --
+// the same weights, options and batch give the same kernel in every process on the same device model:
+//   pointwise layers only (the 3x3 / 5x5 layers keep generated code at every batch: the generic kernel needs
+//   16-81 us where code needs 12-16), a launch of one round (tiles x columns <= workgroup slots of the chip: CUs, or
+//   2 x CUs for the half-workgroup tilings) under 64 MFLOP;
+//   generic  ~ max(7.0, 5.8 + 0.125 r, 6.2 + waves x (0.143 + 0.0473 r) / 1000)   us; r = nonzeros per output row (the
+//              CSR row a wave walks with scalar loads: a latency chain), waves = N x M x ceil(OH OW / 64)
+//   code     ~ 7.6 + (0.6 chained | 1.1 one call per block) x blocks per tile + 0.1 x MB of blobs    us
+//   the kernel with the lower estimate.
+// Fitted to 180 cells (profiles/r05_small_launch_fit.md; tools/small_launch_fit.py: both kernels forced, 1-32 images
+// of every distinct GoogLeNet 1x1 shape): the models are within 6 % (code) / 12 % (generic) rms of the measurements
+// and the rule's pick is at most 12.7 % behind the faster kernel, two cells of 180 more than 10 %.
+// Evaluated from the TILING, before any code is generated or loaded (round 6): a layer the rule sends to
+// the generic kernel no longer pays for code generation and a module load / unload at every WeightAlign.
+// Returns 0 (not considered), 1 (generated code), 2 (generic kernel).
+int small_launch_rule(const Geometry &g, int kernel_choice, int n_dense_groups, int tiling_batch, long nnz, const Tiling &t,
+                      bool chained, int n_cu) {
+  if (!(kernel_choice == ESCOIN_KERNEL_AUTO && n_dense_groups == 0 && (tiling_batch <= 0 || tiling_batch == g.d.N) &&
+        g.d.KH == 1 && g.d.KW == 1))
+    return 0;
+  const double flops = 2.0 * g.d.N * g.OH * g.OW * (double)nnz;
+  const long tiles = t.band_mode ? (long)g.d.N * t.bands : ((long)g.d.N + t.nseg - 1) / t.nseg;
+  const long wgs = tiles * t.n_ocblk * g.d.group;
+  const long slots = (long)n_cu * (t.waves == 4 ? 2 : 1);
+  if (!(flops < 64e6 && wgs <= slots)) return 0;
+  const double r = (double)nnz / (double)g.d.M;
+  const double waves = (double)g.d.N * g.d.M * std::ceil((double)g.OH * g.OW / 64.0);
+  const double mb = 4.0 * g.d.N * ((double)g.d.C * g.d.H * g.d.W + (double)g.d.M * g.OH * g.OW) * 1e-6;
+  const double t_gen = std::max(std::max(7.0, 5.8 + 0.125 * r), 6.2 + waves * (0.143 + 0.0473 * r) * 1e-3);
+  const double t_code = 7.6 + (chained ? 0.6 : 1.1) * t.n_icb + 0.1 * mb;
+  const int pick = t_gen < t_code ? 2 : 1;
+  if (getenv("ESCOIN_VERBOSE"))
+    fprintf(stderr, "[escoin] small launch (%.1f MFLOP, %ld workgroups on %ld slots, %d blocks): code ~%.1f us, generic ~%.1f us -> %s\n",
+            flops * 1e-6, wgs, slots, t.n_icb, t_code, t_gen, pick == 2 ? "generic" : "code");
+  return pick;
+}
+
+// Generated code: nothing but the planes (and two small tables) lives in LDS -- the first tiling
+// the budget allows is the one.  WeightAlign = tiling, channel deal, code generation, code
+// object (jit_module.h), unit table.
+JitLayout jit_layout(const Geometry &g, float density, int tiling_batch, int n_cu) {
+  JitLayout lay;
+  ConvGeom cg = to_geom(g);
+  cg.density = density;
+  // Plane buffers: two, or three of 48 KiB with TWO fills in flight (the unit of block k stages block
+  // k + 2) for layers that wait for their planes rather than walk: pointwise layers at <= 10 % density
+  // spend 15-50 % of a launch in the walk, and with one fill in flight the LDS-DMA engine of a CU idles
+  // from the landing of one block to the first instruction of the next (barrier, issue, HBM latency:
+  // 1.6 of 4.5 us per block on GoogLeNet's 28 x 28 layers).  ESCOIN_JIT_NBUF forces 2 or 3.
+  static const int env_jit_nbuf = (int)ESC_KNOB("JIT_NBUF", 0);
+  // Measured on GoogLeNet's 39 pointwise layers at 95 %, same-box bench steps (profiles/r03_nbuf_sweep.md):
+  // with up to 192 output channels per conv group the third buffer wins (set -5 %; the 48 KiB budget
+  // also steers 160-channel layers to one pass of 20 channels per wave instead of two of 10: -30 % on
+  // those); 256 and 384 output channels walked long enough to cover one fill and lost 5-10 % to the
+  // smaller blocks -- until their code stopped computing a tile B without rows (jit_codegen.cpp): since
+  // then the third buffer wins there too (5b/1x1: 48.7 -> 44.3 us).
+  int jit_nbuf = env_jit_nbuf == 2 || env_jit_nbuf == 3 ? env_jit_nbuf
+                 : (g.d.KH == 1 && g.d.KW == 1 && density <= 0.101f && g.Mg <= 384) ? 3 : 2;
+  int jit_budget = jit_nbuf == 3 ? std::min(default_lds_budget(), 48 * 1024) : default_lds_budget();
+  Tiling t = pick_tiling(g, n_cu, jit_budget, density, tiling_batch, true);
+  if (!t.ok) return lay;
+  // 3x3 / 5x5 layers with more than one workgroup column: 32 KiB plane buffers instead of 64.  Since the units
+  // chain themselves a block costs ~14 instructions and a barrier, not 1300 cycles of compiled code, and smaller
+  // blocks start the first walk sooner and keep the fills finer under it: same-call pairs, ResNet step 1.953 ->
+  // 1.902 ms (res3 -3.7 %, res4 -4.7 %, res5 -5.0 %), AlexNet 0.555 -> 0.531 ms (every layer -3..-6 %).  Not for
+  // layers with ONE column (res2: +4.8 % -- its planes come from HBM, non-temporal, and need the longer blocks'
+  // lead) and not for pointwise layers (GoogLeNet set +3.5 %: they wait for their planes, not for the walk).
+  // ESCOIN_LDS_KB set: as it says.
+  if (!ESC_KNOB_SET("LDS_KB") && g.d.KH * g.d.KW > 1 && t.n_ocblk > 1 && jit_nbuf == 2 && jit_budget > 32 * 1024) {
+    const Tiling t32 = pick_tiling(g, n_cu, 32 * 1024, density, tiling_batch, true);
+    if (t32.ok) {
+      t = t32;
+      jit_budget = 32 * 1024;
+    }
+  }
+  if (jit_nbuf == 3 && t.n_icb < 2) {      // (the fill sequence may run one tile ahead only)
+    jit_nbuf = 2;
+    t = pick_tiling(g, n_cu, default_lds_budget(), density, tiling_batch, true);
+    if (!t.ok) return lay;
+  }
+  static const int max_period = (int)ESC_KNOB("JIT_DMA_PERIOD", 2048);
+  // Two 4-wave workgroups per CU instead of one of eight, for HBM-bound pointwise layers with two to four tiles per
+  // workgroup (GoogLeNet's 28 x 28 layers with up to 96 output channels at batch 256).  A workgroup's life is
+  // start-up, then per tile [stream the planes at the DMA engine's rate | epilogue: the stores, during which its
+  // DMA queue runs dry], and with one workgroup per CU nothing runs under the ends (profiles/r05_pointwise_ends.md:
+  // without the stores a 28 x 28 layer is 29 % shorter).  Two independent workgroups on a CU overlap by themselves:
+  // one streams while the other stores or starts.  Same-call A/B, HBM-cold (profiles/r05_half_workgroups.md):
+  // 192@28x28 -> 64 / 96 / 16 / 32 channels -11 / -9 / -10 / -12 %, 256@28x28 -> 32 / 64 -9 / -10 % -- within 2 % of
+  // what a copy of the layer's bytes takes at 6.3 TB/s plus 8 us; 56 x 56 (seven tiles per workgroup: already at that
+  // bound) +1 %, 14 x 14 and smaller (one tile per workgroup) 0..+50 %: not taken there; nor for 128 channels at
+  // 28 x 28 as one column of four waves with one quad per lane (G = 32, four bands of 25 rows): 69 -> 79 us.  Needs every output
+  // channel in ONE column of four waves (G <= 24: up to 96 channels), 32 KiB plane buffers x 2 so that two
+  // workgroups share a CU's LDS, and at least one tile per workgroup.  ESCOIN_HALF_WG = 0 / 1: never / wherever it fits.
+  {
+    static const int half_knob = (int)ESC_KNOB("HALF_WG", -1);
+    const long nb = tiling_batch > 0 ? tiling_batch : g.d.N;
+    auto tiles_of = [&](const Tiling &tt) { return tt.band_mode ? nb * tt.bands : (nb + tt.nseg - 1) / tt.nseg; };
+    const bool pointwise = g.d.KH == 1 && g.d.KW == 1 && g.d.pad_h == 0 && g.d.pad_w == 0 && !strided_pointwise(g) &&
+                           g.d.group == 1;
+    const bool rule = pointwise && t.n_ocblk == 1 && g.Mg <= 96 && tiles_of(t) >= 2l * n_cu && tiles_of(t) <= 4l * n_cu &&
+                      !ESC_KNOB_SET("WAVES") && !ESC_KNOB_SET("LDS_KB") && env_jit_nbuf == 0;
+    if (half_knob != 0 && pointwise && (rule || half_knob == 1)) {
+      const Tiling t4 = pick_tiling(g, n_cu, 32 * 1024, density, tiling_batch, true, 4);
+      if (t4.ok && t4.waves == 4 && t4.pix_waves == 1 && t4.n_ocblk == 1 && t4.n_ocg % t4.oc_waves == 0 && tiles_of(t4) >= 2l * n_cu) {
+        int padded = 0;
+        const int period = jit::dma_period(t4.plane_ch_floats / 4, max_period, 0.07, &padded);
+        if (period > 0) {
+          const Tiling tp = padded * 4 == t4.plane_ch_floats ? t4 : repad_planes(cg, t4, padded, 32 * 1024);
+          if (tp.ok && lds_bytes_for(tp, 0, 2, period) <= kLdsPerWorkgroup / 2) {
+            t = t4;
+            jit_nbuf = 2;
+            jit_budget = 32 * 1024;
+          }
+        }
+      }
+    }
+  }
+  jit::Options jopt = jit::options_from_env();
+  // Plane DMA from inside the generated code: one wave per oc-group (the unit then knows which wave
+  // runs it), a quad table of at most 2048 entries per tile parity; a plane may grow by up to 7 %
+  // to get there (res5: 162 -> 168 quads, period 1344 instead of 5184; 28 x 28 pointwise: 98 -> 104).
+  int tab_len = 0;
+  if (t.pix_waves == 1 && (t.waves == 8 || t.waves == 4)) {
+    int padded = 0;
+    const int period = jit::dma_period(t.plane_ch_floats / 4, max_period, 0.07, &padded);
+    if (period > 0) {
+      const Tiling tp = padded * 4 == t.plane_ch_floats ? t : repad_planes(cg, t, padded, jit_budget);
+      if (tp.ok && lds_bytes_for(tp, 0, jit_nbuf, period) <= kLdsPerWorkgroup && (jit_nbuf == 2 || tp.n_icb >= 2)) {
+        t = tp;
+        tab_len = period;
+        jopt.dma.on = true;
+        jopt.dma.qpc = padded;
+        jopt.dma.period = period;
+        jopt.dma.chan_bytes = (uint32_t)((size_t)g.d.H * g.d.W * 4);
+        jopt.dma.waves = t.waves;
+        jopt.dma.nt = t.n_ocblk == 1;
+        jopt.dma.ahead = jit_nbuf - 1;
+        // the pieces of the next block go out over ALL rows of a unit (an LDS-DMA instruction among
+        // FMAs costs its wave 5-20 cycles, in a burst ~100), except where a tile has few blocks (res2:
+        // three; the last pieces then land too close to the block top that needs them: 70 %).  Same-call
+        // pairs, 100 against 70 % everywhere: GoogLeNet set -0.8 %, res3 / res4 / res5 -1.5 %, res2 +2.5 %.
+        // (round 5, with the weights through the scalar cache the 3x3 / 5x5 rows are shorter: res3 at 70 % -3 %, res4
+        // -1 %, res5 +1 % -- 70 % up to 16 blocks there; profiles/r05_knob_retune.md)
+        jopt.dma.spread_pct = t.n_icb <= (g.d.KW != 1 ? 16 : 3) ? 70 : 100;
+        if (ESC_KNOB_SET("JIT_DMA_SPREAD")) jopt.dma.spread_pct = std::max(1, std::min(100, (int)ESC_KNOB("JIT_DMA_SPREAD", 100)));
+      }
+    }
+  }
+  if (tab_len == 0 && jit_nbuf == 3) {     // two fills in flight only where the code stages its planes itself
+    jit_nbuf = 2;
+    t = pick_tiling(g, n_cu, default_lds_budget(), density, tiling_batch, true);
+    if (!t.ok) return lay;
+  }
+  if (lds_bytes_for(t, 0, jit_nbuf, tab_len) > kLdsPerWorkgroup) return lay;
+  // block-to-block chaining (jit_codegen.h ChainPlan): wherever the code stages its planes itself and
+  // every wave of every workgroup column has an oc-group
+  jopt.chain.on = tab_len > 0 && t.pix_waves == 1 && t.n_ocg % t.oc_waves == 0;
+  jopt.chain.nbuf = jit_nbuf;
+  jopt.chain.buf_bytes = (uint32_t)((t.planes_bytes + 1023) / 1024 * 1024 + 1024);
+  // weights through the scalar cache instead of a literal move per nonzero: the 3x3 / 5x5 layers (their kernel
+  // instantiations carry the longer clobber list, tiled_body)
+  jopt.sweights = g.d.KW != 1 ? 1 : 0;
+  // s_setprio 1 / 0 alternating every four rows in the units of the first half of a workgroup's waves: the two
+  // waves of a SIMD then take turns at the FMA pipe in bursts instead of interleaving instruction by instruction,
+  // and the halves drift apart so that one half's row tops (LDS reads, the scalar loads) fall under the other's
+  // FMAs.  Same-call pairs (profiles/r05_knob_retune.md): ResNet-50 set -0.5..-1.4 %, AlexNet -1.7 %, GoogLeNet -0.5 %.
+  if (!ESC_KNOB_SET("JIT_PRIO_ROWS")) jopt.prio_rows = 4;
+  if (!ESC_KNOB_SET("JIT_PRIO_WAVES")) jopt.prio_waves = t.waves / 2;
+  lay.ok = true;
+  lay.t = t;
+  lay.nbuf = jit_nbuf;
+  lay.budget = jit_budget;
+  lay.tab_len = tab_len;
+  lay.jopt = jopt;
+  return lay;
+}
+
+bool jit_generate(const Geometry &g, float density, int tiling_batch, int n_cu, JitLayout *lay, const CsrIndex &rowptr,
+                  const CsrIndex &colidx, const CsrValues &values, jit::Program *prog) {
+  ConvGeom cg = to_geom(g);
+  cg.density = density;
+  const Tiling &t = lay->t;
+  jit::Options &jopt = lay->jopt;
+  *prog = jit::build_program(cg, t, rowptr, colidx, values, jopt);
+  // Code touches (a unit loads the first bytes of the code that runs next, so that it is in the L2 by then) cost
+  // every wave a load per unit and a wait; where ALL of a layer's code is small enough to stay in every XCD's L2
+  // beside the streaming input, the first workgroups' instruction fetches do the same job.  Same-call pairs
+  // (profiles/r05_knob_retune.md): without them GoogLeNet's 56 x 56 layer -3.8 %, its 14 x 14 layers -2..-8 %; the half-workgroup layers and the 4 x 4 ones (fewer tiles than CUs: too few
+  // workgroups share the fetches) +1..+10 % (kept there), res3..res5 / AlexNet (megabytes of code) +7..+40 %, and res2 (168 KB) -2 % alone but +3 % together with the
+  // s_setprio rows above: pointwise layers only.
+  // ESCOIN_JIT_PREFETCH = 0 / 1 overrides (experiments flavour).
+  const long nb = tiling_batch > 0 ? tiling_batch : g.d.N;
+  const long tiles_total = t.band_mode ? nb * t.bands : (nb + t.nseg - 1) / t.nseg;
+  if (jopt.prefetch && !ESC_KNOB_SET("JIT_PREFETCH") && !prog->overflow && g.d.KH == 1 && g.d.KW == 1 && t.waves == 8 &&
+      t.n_icb >= 2 && prog->code.size() * 4 <= 256u * 1024u && tiles_total >= n_cu) {
+    jopt.prefetch = 0;
+    *prog = jit::build_program(cg, t, rowptr, colidx, values, jopt);
+  }
+  return !(prog->overflow || prog->code.size() * 4 > kMaxJitBytes);
+}
+
+StreamLayout stream_layout(const Geometry &g, float density, int tiling_batch, int n_cu, const CsrIndex &rowptr,
+                           const CsrIndex &colidx, const CsrValues &values) {
+  StreamLayout lay;
+  ConvGeom cg = to_geom(g);
+  cg.density = density;
+  // Buffers.  Two plane/staging buffers overlap one block's DMA with the previous block's walk.
+  // Three (two blocks in flight, counted vmcnt waits inside a tile; ESCOIN_NBUF=3) were measured
+  // on the HBM-bound pointwise layers and on the ResNet set: 7-8 % SLOWER -- the smaller planes
+  // mean more blocks, and a block's fixed costs (barrier, DMA issue, loop prologue) outweigh the
+  // DMA latency the third buffer hides.
+  static const int env_nbuf = (int)ESC_KNOB("NBUF", 0);
+  for (int nbuf = env_nbuf == 3 ? 3 : 2; nbuf >= 2; --nbuf) {
+    // the staging areas share the workgroup's LDS with the plane buffers: shrink the planes until
+    // everything fits (the body size depends on the channels per block, so this is a short search)
+    const int start = nbuf == 2 ? default_lds_budget() : std::min(default_lds_budget(), 48 * 1024);
+    for (int budget = start; budget >= 16 * 1024; budget -= 4 * 1024) {
+      const Tiling t = pick_tiling(g, n_cu, budget, density, tiling_batch);
+      if (!t.ok) break;
+      if (nbuf == 3 && t.n_icb < 2) break;          // the fill sequence may run one tile ahead only
+      WeightStream ws = build_stream(cg, t, rowptr, colidx, values);
+      if (ws.overflow) continue;
+      const int stage = stage_bytes_for(ws.max_body_bytes);
+      if (lds_bytes_for(t, stage, nbuf) > kLdsPerWorkgroup) continue;
+      lay.ok = true;
+      lay.t = t;
+      lay.nbuf = nbuf;
+      lay.budget = budget;
+      lay.stage_bytes = stage;
+      lay.ws = std::move(ws);
+      return lay;
+    }
+  }
+  return lay;   // not ok: the caller falls back to the generic kernel
+}
+
+bool stg_plan(const Geometry &g, bool is_f64, int wgrad_channel_block, int n_cu, StgPlan *sp) {
+  const escoin_conv_desc &d = g.d;
+  if (is_f64 || d.stride_h != 1 || d.stride_w != 1) return false;
+  const long opix = (long)g.OH * g.OW;
+  const long Hp = (long)d.H + 2 * d.pad_h, Wp = (long)d.W + 2 * d.pad_w;
+  if (opix > kStgSmallInt / 2 || Hp > kStgSmallInt / 2 || Wp > kStgSmallInt / 2) return false;   // div_small
+  if ((double)d.N * d.M * (double)opix >= 2147483648.0 || (double)d.N * d.C * (double)d.H * d.W >= 2147483648.0) return false;
+  if ((double)d.N * (double)Hp >= 1073741824.0) return false;
+  // the longest span of padded rows a chunk touches
+  const long total = (long)d.N * opix;
+  const int span_h = d.dil_h * (d.KH - 1);
+  long rows = 0;
+  for (long q0 = 0; q0 < total; q0 += kBwdChunkPixels) {
+    const long q1 = std::min(total, q0 + kBwdChunkPixels) - 1;
+    const long n0 = q0 / opix, n1 = q1 / opix;
+    const long P0 = n0 * Hp + (q0 - n0 * opix) / g.OW, P1 = n1 * Hp + (q1 - n1 * opix) / g.OW + span_h;
+    rows = std::max(rows, P1 - P0 + 1);
+  }
+  if (rows < 1 || (size_t)rows * (size_t)Wp * sizeof(float) > kStgLdsBudget) return false;
+  sp->rows_max = (int)rows;
+  sp->cs = (int)(rows * Wp);
+  sp->icb = (int)std::min<size_t>((size_t)g.Cg, kStgLdsBudget / (sizeof(float) * (size_t)sp->cs));
+  if (wgrad_channel_block > 0) sp->icb = std::min(sp->icb, wgrad_channel_block);
+  sp->nblk = (g.Cg + sp->icb - 1) / sp->icb;
+  sp->chunks = (int)((total + kBwdChunkPixels - 1) / kBwdChunkPixels);
+  // enough workgroups for two per CU where the chunks and blocks alone do not give them: deal the output channels
+  const long wgs = (long)sp->chunks * d.group * sp->nblk;
+  const long want = 2L * std::max(n_cu, 1);
+  const int osplit = (int)std::min<long>((g.Mg + kStgWaves - 1) / kStgWaves, (want + wgs - 1) / std::max(wgs, 1L));
+  sp->osplit = std::max(1, std::min(osplit, 65535 / std::max(d.group, 1)));
+  return sp->nblk <= 65535;   // grid z
+}
+
+// AUTO's rule for the weight gradient: a function of the geometry, nnz and the device's CU count only -- the two
+// kernels' times in microseconds from a cost model fitted to one MI355X run of tools/backward_bench.py
+// (profiles/backward_mi355x.md, "AUTO's rule": the fit, its coefficients and its residuals on the 47 benched layers).
+// Both kernels run in rounds of resident workgroups: the entry kernel's (chunk, output channel) workgroups of 4 waves
+// sit 8 to a CU, the staged kernel's 64 KiB workgroups 2 to a CU.  A last, partly filled round still costs a
+// workgroup's latency, hence the floor on its fraction.
+//   entry   21.3 + 0.153 chunks (its stage 2 walks the chunks serially) + rounds x (3.0 + 1.138 x entries per row)
+//   staged  13.4 + rounds x (19.3 (staging the tile) + steps x (1.02 (loading G) + 0.426 x entries per (row, block)))
+//           with steps = output channels a wave takes in turn
+static double stg_rounds(double workgroups, double resident, double tail_floor) {
+  const double r = workgroups / resident, whole = std::floor(r), tail = r - whole;
+  return whole + (tail > 0 ? std::max(tail, tail_floor) : 0.0);
+}
+bool stg_auto_prefers(const Geometry &g, long nnz, const StgPlan &sp, int n_cu) {
+  const escoin_conv_desc &d = g.d;
+  if (nnz <= 0) return false;
+  const double cus = (double)std::max(n_cu, 1);
+  const double entry = 21.3 + 0.153 * sp.chunks +
+                       stg_rounds((double)sp.chunks * d.M, 8.0 * cus, 0.3) * (3.0 + 1.138 * (double)nnz / d.M);
+  const int steps = ((g.Mg + sp.osplit - 1) / sp.osplit + kStgWaves - 1) / kStgWaves;
+  const double per_pair = (double)nnz / ((double)d.M * sp.nblk);
+  const double staged = 13.4 + stg_rounds((double)sp.chunks * d.group * sp.nblk * sp.osplit, 2.0 * cus, 0.4) *
+                                   (19.3 + steps * (1.02 + 0.426 * per_pair));
+  return staged < entry;
+}
+
+}  // namespace escoin

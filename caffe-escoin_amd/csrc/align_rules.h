@@ -1,0 +1,100 @@
+// align_rules.h -- WeightAlign's decisions: which conv groups go to the dense kernel, which kernel and layout the sparse
+// ones get, which weight-gradient kernel the backward runs.  Pure C++ (no HIP, no escoin_plan): every rule is a function
+// of values -- geometry, nonzero counts, option values and the device's CU count -- so that it runs, and is tested, on
+// a machine without a GPU (tests/test_align_rules.py).  The .hip files call these and do the device work: uploads,
+// code loads, launches.
+#ifndef ESCOIN_ALIGN_RULES_H_
+#define ESCOIN_ALIGN_RULES_H_
+
+#include <string>
+#include <vector>
+
+#include "geometry.h"
+#include "jit_codegen.h"
+#include "stream_builder.h"
+
+namespace escoin {
+
+constexpr int kTiledWaves = 8;
+constexpr int kLdsBudget = 64 * 1024;   // per plane buffer; two buffers per workgroup
+
+typedef std::vector<std::vector<int>> CsrIndex;     // [conv group][...]: rowptr / colidx of the host CSR
+typedef std::vector<std::vector<float>> CsrValues;
+
+// ---- dense / sparse split of the conv groups -----------------------------------------------------------------------
+// The plan options the split reads (escoin_plan_set_option).
+struct SplitOptions {
+  int kernel, conv_mode, dense_gate, dense_threshold_pct, tiling_batch;
+};
+// One flag per conv group: 1 = the group runs on the dense (fp32 MFMA) kernel.
+std::vector<char> dense_groups(const Geometry &g, const std::vector<long> &nnz_per_group, const SplitOptions &o, int n_cu);
+
+// What the plan keeps of the flags: bit g of dense_mask = group g goes to the MFMA kernel, bit g of sparse_mask = to the
+// sparse kernels (layers with more than 64 groups take one decision for all of them: both masks are then all-ones / zero).
+struct GroupSplit {
+  int n_dense = 0, n_sparse = 0;
+  bool use_dense = false;         // every group dense
+  unsigned long long dense_mask = 0, sparse_mask = ~0ull;
+};
+GroupSplit group_split(const std::vector<char> &dense);
+
+// ---- the tiled kernels ---------------------------------------------------------------------------------------------
+int default_lds_budget();
+Tiling pick_tiling(const Geometry &g, int n_cu, int lds_budget = 0, float density = 0.f, int tiling_batch = 0,
+                   bool one_tile_ok = false, int waves_per_wg = 0);
+bool tiled_supported(const Geometry &g, int n_cu);
+
+// escoin_plan_tiling_info's line
+std::string tiling_info(const Tiling &t, bool jit, int nbuf, size_t lds_bytes, int tab_len, bool chained);
+
+// KERNEL_AUTO's rule for pointwise launches of one round of workgroups under 64 MFLOP, evaluated from the tiling before
+// any code is generated or loaded: 0 not considered, 1 generated code, 2 the generic kernel.
+int small_launch_rule(const Geometry &g, int kernel_choice, int n_dense_groups, int tiling_batch, long nnz, const Tiling &t,
+                      bool chained, int n_cu);
+
+// Generated code: the tiling, the plane buffers and the generator's options.  ok == false: the layer does not fit.
+struct JitLayout {
+  bool ok = false;
+  Tiling t;
+  int nbuf = 2;        // plane buffers
+  int budget = 0;      // plane-buffer budget the tiling was chosen with
+  int tab_len = 0;     // quad-table period of the code's own plane DMA (0: the kernel body stages the planes)
+  jit::Options jopt;
+};
+JitLayout jit_layout(const Geometry &g, float density, int tiling_batch, int n_cu);
+// Generates the layout's program, applies the code-touch rule (which may generate it again without touches:
+// lay->jopt.prefetch says which one came out) and checks its size.  false: the code overflows or is too large.
+bool jit_generate(const Geometry &g, float density, int tiling_batch, int n_cu, JitLayout *lay, const CsrIndex &rowptr,
+                  const CsrIndex &colidx, const CsrValues &values, jit::Program *prog);
+
+// The LDS-staged stream: the first (buffers, plane budget) whose stream fits the workgroup's LDS, with that stream.
+struct StreamLayout {
+  bool ok = false;
+  Tiling t;
+  int nbuf = 2, budget = 0, stage_bytes = 0;
+  WeightStream ws;
+};
+StreamLayout stream_layout(const Geometry &g, float density, int tiling_batch, int n_cu, const CsrIndex &rowptr,
+                           const CsrIndex &colidx, const CsrValues &values);
+
+// ---- the staged weight-gradient kernel (sconv_backward.hip) --------------------------------------------------------
+constexpr int kStgWaves = 8;                         // waves per workgroup
+constexpr size_t kStgLdsBudget = 64 * 1024;          // two workgroups per CU
+constexpr int kStgSmallInt = 1 << 21;                // div_small's range
+
+// The staged weight-gradient kernel's block plan (sconv_backward.hip header of that kernel): the LDS tile and the split
+// of a conv group's input channels into staged blocks.  AUTO's rule and stg_build both read this one.
+struct StgPlan {
+  int rows_max = 0;   // padded rows of the tile: the longest chunk's span
+  int cs = 0;         // floats per staged channel: rows_max * Wp
+  int icb = 0;        // input channels per staged block
+  int nblk = 0;       // blocks per conv group (grid z)
+  int chunks = 0;     // chunks of the full batch
+  int osplit = 1;     // workgroups a conv group's output channels are dealt over
+};
+// Whether the staged kernel serves this plan, and its block plan where it does.
+bool stg_plan(const Geometry &g, bool is_f64, int wgrad_channel_block, int n_cu, StgPlan *sp);
+bool stg_auto_prefers(const Geometry &g, long nnz, const StgPlan &sp, int n_cu);
+
+}  // namespace escoin
+#endif  // ESCOIN_ALIGN_RULES_H_

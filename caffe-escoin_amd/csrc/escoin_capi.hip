@@ -3,12 +3,12 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
-#include <cmath>
 #include <cstring>
 #include <new>
 #include <string>
 #include <vector>
 
+#include "align_rules.h"
 #include "escoin_plan.h"
 
 namespace escoin {
@@ -21,11 +21,6 @@ int fail(int code, const std::string &msg) {
   g_last_error = msg;
   return code;
 }
-
-// Density above which KERNEL_AUTO sends a conv group to the dense fp32-MFMA kernel: the measured
-// crossover between the tiled sparse kernel and the dense kernel (profiles/r02_crossover.md).
-constexpr int kDefaultDenseThresholdPct = 50;
-constexpr int kGenericDenseThresholdPct = 4;
 
 static double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -119,49 +114,6 @@ static void free_device(escoin_plan *p) {
   p->dense = DenseArrays();
 }
 
-// Small launches.  The LDS-tiled kernels walk a tile block by block, every block a round trip to HBM, on as many
-// workgroups as the batch has tiles x columns: 11-19 us for one image of a GoogLeNet 1x1 layer; the generic kernel
-// puts a lane on every output pixel of the whole chip and needs 7-12 (profiles/r04_batch_sweep.md -- the reference's
-// SCONV mode calls the layer image by image, conv_layer.cu:16-26).  Round 4 TIMED both kernels; a layer's bits then
-// depended on the box's noise (two ranks could settle differently).  Now a RULE decides, from what WeightAlign knows --
-// the same weights, options and batch give the same kernel in every process on the same device model:
-//   pointwise layers only (the 3x3 / 5x5 layers keep generated code at every batch: the generic kernel needs
-//   16-81 us where code needs 12-16), a launch of one round (tiles x columns <= workgroup slots of the chip: CUs, or
-//   2 x CUs for the half-workgroup tilings) under 64 MFLOP;
-//   generic  ~ max(7.0, 5.8 + 0.125 r, 6.2 + waves x (0.143 + 0.0473 r) / 1000)   us; r = nonzeros per output row (the
-//              CSR row a wave walks with scalar loads: a latency chain), waves = N x M x ceil(OH OW / 64)
-//   code     ~ 7.6 + (0.6 chained | 1.1 one call per block) x blocks per tile + 0.1 x MB of blobs    us
-//   the kernel with the lower estimate.
-// Fitted to 180 cells (profiles/r05_small_launch_fit.md; tools/small_launch_fit.py: both kernels forced, 1-32 images
-// of every distinct GoogLeNet 1x1 shape): the models are within 6 % (code) / 12 % (generic) rms of the measurements
-// and the rule's pick is at most 12.7 % behind the faster kernel, two cells of 180 more than 10 %.
-// Evaluated from the TILING, before any code is generated or loaded (round 6): a layer the rule sends to
-// the generic kernel no longer pays for code generation and a module load / unload at every WeightAlign.
-// Returns 0 (not considered), 1 (generated code), 2 (generic kernel).
-int small_launch_rule(const escoin_plan *p, const Tiling &t, bool chained) {
-  const Geometry &g = p->g;
-  if (!(p->kernel_choice == ESCOIN_KERNEL_AUTO && p->n_dense_groups == 0 && (p->tiling_batch <= 0 || p->tiling_batch == g.d.N) &&
-        g.d.KH == 1 && g.d.KW == 1))
-    return 0;
-  long nnz = 0;
-  for (const auto &c : p->colidx) nnz += (long)c.size();
-  const double flops = 2.0 * g.d.N * g.OH * g.OW * (double)nnz;
-  const long tiles = t.band_mode ? (long)g.d.N * t.bands : ((long)g.d.N + t.nseg - 1) / t.nseg;
-  const long wgs = tiles * t.n_ocblk * g.d.group;
-  const long slots = (long)tiled_device_cus() * (t.waves == 4 ? 2 : 1);
-  if (!(flops < 64e6 && wgs <= slots)) return 0;
-  const double r = (double)nnz / (double)g.d.M;
-  const double waves = (double)g.d.N * g.d.M * std::ceil((double)g.OH * g.OW / 64.0);
-  const double mb = 4.0 * g.d.N * ((double)g.d.C * g.d.H * g.d.W + (double)g.d.M * g.OH * g.OW) * 1e-6;
-  const double t_gen = std::max(std::max(7.0, 5.8 + 0.125 * r), 6.2 + waves * (0.143 + 0.0473 * r) * 1e-3);
-  const double t_code = 7.6 + (chained ? 0.6 : 1.1) * t.n_icb + 0.1 * mb;
-  const int pick = t_gen < t_code ? 2 : 1;
-  if (getenv("ESCOIN_VERBOSE"))
-    fprintf(stderr, "[escoin] small launch (%.1f MFLOP, %ld workgroups on %ld slots, %d blocks): code ~%.1f us, generic ~%.1f us -> %s\n",
-            flops * 1e-6, wgs, slots, t.n_icb, t_code, t_gen, pick == 2 ? "generic" : "code");
-  return pick;
-}
-
 // The generic kernel's device CSR (p->gen) from the host CSR: rowptr, packed taps and values of the plan's Dtype.
 template <typename T>
 static int upload_generic(escoin_plan *p, long nnz, hipStream_t stream) {
@@ -199,8 +151,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
   ESCOIN_HIP_TRY(hipGetDevice(&p->device));
   free_device(p);
   const Geometry &g = p->g;
-  long nnz = 0;
-  for (int grp = 0; grp < g.d.group; ++grp) nnz += (long)p->colidx[grp].size();
+  const long nnz = plan_nnz(p);
   const int rc_gen = p->is_f64 ? upload_generic<double>(p, nnz, stream) : upload_generic<float>(p, nnz, stream);
   if (rc_gen != ESCOIN_OK) return rc_gen;
   if (p->is_f64) {
@@ -213,77 +164,18 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     p->aligned = true;
     return ESCOIN_OK;
   }
-  // ---- which conv groups go to the dense (fp32 MFMA) kernel -------------------------------
-  //  * kernel DENSE or conv_mode LOWERED_GEMM (forward_gpu_gemm, base_conv_layer.cpp:713-746): all;
-  //  * dense_gate = 1: the reference's gate -- group 0's density decides for the whole layer
-  //    (nz_num_[0] / (M/g * kernel_dim) > 0.2, base_conv_layer.cpp:750, :805; quirk 5);
-  //  * otherwise (AUTO): each group by its own density against the measured crossover
-  //    (profiles/r02_crossover.md; option "dense_threshold_pct" overrides).
+  // which conv groups go to the dense (fp32 MFMA) kernel (align_rules.h)
   const int G = g.d.group;
-  std::vector<char> dense(G, 0);
-  const double per_group = (double)g.Mg * g.kdim;
-  if (p->kernel_choice == ESCOIN_KERNEL_DENSE || p->conv_mode == ESCOIN_CONV_MODE_LOWERED_GEMM) {
-    dense.assign(G, 1);
-  } else if (p->kernel_choice == ESCOIN_KERNEL_AUTO) {
-    if (p->dense_gate) {
-      if ((double)p->colidx[0].size() / per_group > 0.2) dense.assign(G, 1);
-    } else {
-      // a geometry the tiled kernels do not cover (stride / dilation != 1) has only the generic kernel on
-      // the sparse side -- one lane per output pixel, ~2 sparse TFLOP/s -- against 65-110 dense TFLOP/s:
-      // the MFMA kernel wins from ~4 % density on (ResNet-50's stride-2 1x1 layers pruned @90 %:
-      // 2.2-2.7 ms generic vs 0.17-0.58 ms dense, profiles/r04_chain_prune_1x1.md)
-      const bool fast_sparse = tiled_supported(g);
-      const int auto_thr = fast_sparse ? kDefaultDenseThresholdPct : kGenericDenseThresholdPct;
-      const double thr = (p->dense_threshold_pct >= 0 ? p->dense_threshold_pct : auto_thr) / 100.0;
-      // Above the cut the dense kernel used to win by rule.  With generated code on every sparse layer it
-      // does not: measured crossovers (profiles/r04_crossover.md) sit between 53 % density (AlexNet conv3, whose
-      // 507 output tiles fill the 512 MFMA slots exactly) and > 90 % (res2, 64 output channels: half-empty
-      // 64 x 128 tiles) -- no single density separates them, what WeightAlign knows about the two kernels does:
-      //   dense  = rounds of 128 x 128 (64 x 128 when a group has <= 64 channels) output tiles on 512 slots at
-      //            120 TFLOP/s (x 0.7 for the narrow tiles), no faster than the blobs at 4.0 TB/s;
-      //   sparse = 50 us + 2 * pixels * nonzeros at 80 TFLOP/s (3x3 / 5x5), 20 us + ... at 68 (1x1), no faster than
-      //            the blobs at 4.8 TB/s.
-      // Re-fitted in round 5 (profiles/r05_crossover.md; round 4's constants -- 25 us + 68 / 58 TFLOP/s against 110 --
-      // were fitted to generated code that still moved a literal per nonzero, and on round 5's code sent res2 @10 %
-      // sparsity to the dense kernel at 782 us against 588, res4 / res5 @20 % at 688 / 682 against 583 / 574).
-      // Worst regret over the 14 shapes x 12 sparsities of the table: 7.7 % (round 4's constants on this table: 33 %;
-      // a fixed 50 % cut: 42 %).  The model only ever decides ABOVE the cut; below it the sparse kernel always won, and
-      // above 92 % density the dense one (an unpruned layer is never turned into megabytes of code).  An explicit
-      // dense_threshold_pct option is obeyed as given.
-      auto model_says_dense = [&](long nnz_g) {
-        if ((double)nnz_g > 0.92 * per_group) return true;
-        const double n = (double)(p->tiling_batch > 0 ? p->tiling_batch : g.d.N);
-        const double pix = n * g.OH * g.OW;
-        const int tm = g.Mg <= 64 ? 64 : 128;
-        const double tiles = std::ceil((double)g.Mg / tm) * std::ceil(pix / 128.0);
-        const double rounds = std::ceil(tiles / 512.0);
-        const double byt = 4.0 * n * ((double)g.Cg * g.d.H * g.d.W + (double)g.Mg * g.OH * g.OW);
-        const double t_dense = std::max(rounds * 2.0 * tm * 128.0 * g.kdim / (120e6 * (tm == 64 ? 0.7 : 1.0) / 512.0), byt / 4.0e6);
-        const double t_sparse = std::max((g.d.KH * g.d.KW > 1 ? 50.0 : 20.0) + 2.0 * pix * (double)nnz_g / (g.d.KH * g.d.KW > 1 ? 80e6 : 68e6), byt / 4.8e6 + 8.0);
-        return t_dense < t_sparse;
-      };
-      const bool use_model = p->dense_threshold_pct < 0 && fast_sparse;
-      if (G <= 64) {
-        for (int grp = 0; grp < G; ++grp) {
-          const long n_g = (long)p->colidx[grp].size();
-          dense[grp] = (double)n_g / per_group > thr && (!use_model || model_says_dense(n_g));
-        }
-      } else if ((double)nnz / (per_group * G) > thr && (!use_model || model_says_dense(nnz / G))) {
-        dense.assign(G, 1);
-      }
-    }
-  }
-  p->n_dense_groups = 0;
-  p->dense_mask = 0;
-  for (int grp = 0; grp < G; ++grp)
-    if (dense[grp]) {
-      ++p->n_dense_groups;
-      if (grp < 64) p->dense_mask |= 1ull << grp;
-    }
-  p->n_sparse_groups = G - p->n_dense_groups;
-  p->use_dense = p->n_dense_groups == G;
-  if (p->use_dense) p->dense_mask = ~0ull;
-  p->sparse_mask = p->n_dense_groups == 0 ? ~0ull : ~p->dense_mask & (G >= 64 ? ~0ull : ((1ull << G) - 1));
+  std::vector<long> nnz_per_group(G);
+  for (int grp = 0; grp < G; ++grp) nnz_per_group[grp] = (long)p->colidx[grp].size();
+  const GroupSplit split = group_split(dense_groups(
+      g, nnz_per_group, SplitOptions{p->kernel_choice, p->conv_mode, p->dense_gate, p->dense_threshold_pct, p->tiling_batch},
+      tiled_device_cus()));
+  p->n_dense_groups = split.n_dense;
+  p->n_sparse_groups = split.n_sparse;
+  p->use_dense = split.use_dense;
+  p->dense_mask = split.dense_mask;
+  p->sparse_mask = split.sparse_mask;
   if (p->n_dense_groups > 0) {
     const size_t lda = (size_t)dense_lda(g.kdim);
     std::vector<float> dw(((size_t)g.d.M + dense_spare_rows()) * lda, 0.f);
@@ -313,7 +205,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     // column's code, and grouping the workgroup columns by XCD (sconv_tiled.hip, xcd_q) removed it:
     // over 50-95 % sparsity on every BASELINE 3x3 / 5x5 / 1x1 shape generated code is now ahead of the
     // stream kernel at every point (profiles/r04_crossover.md; the worst point, alex_conv2 @50 %, by 14 %).
-    // Code beyond kMaxJitBytes (sconv_tiled.hip) falls back to the stream kernel by itself.
+    // Code beyond kMaxJitBytes (geometry.h) falls back to the stream kernel by itself.
     const bool try_jit = p->kernel_choice == ESCOIN_KERNEL_JIT || p->kernel_choice == ESCOIN_KERNEL_AUTO;
     int rc = ESCOIN_OK;
     p->import_fast = false;

@@ -12,6 +12,7 @@
 
 #include "device_buffer.h"
 #include "escoin.h"
+#include "geometry.h"
 #include "jit_module.h"
 #include "stream_builder.h"
 
@@ -43,30 +44,9 @@ inline int guarded(F &&body) {
   }
 }
 
-// A nonzero's kernel tap packed for the generic kernel: ic << 16 | kr << 8 | kc
-// (ic group-local).
-inline int pack_tap(int ic, int kr, int kc) { return (ic << 16) | (kr << 8) | kc; }
-
-struct Geometry {
-  escoin_conv_desc d;
-  int OH, OW;
-  int Cg, Mg;   // channels per group
-  int kdim;     // kernel_dim_ = Cg*KH*KW
-};
-
 // Parameters of the tiled kernel chosen in weight_align (see sconv_tiled.hip).
 struct TiledConfig {
   bool enabled = false;
-  int s4 = 0;          // quads (4 floats) per LDS row, power of two
-  int kw_classes = 0;  // KW
-  int tile_rows = 0;   // output rows (over the flattened (image,row) axis) per workgroup
-  int imgs_per_wg = 0; // whole images per workgroup (0: row bands of one image)
-  int pix_waves = 0;   // waves along the pixel axis
-  int oc_waves = 0;    // waves along the output-channel axis
-  int G = 0;           // output channels per wave
-  int icb = 0;         // input channels per LDS block
-  int n_icb = 0;       // blocks per group
-  int slots = 0;       // records per row group in the weight stream
   size_t lds_bytes = 0;
   int lds_budget = 0;  // plane-buffer budget the tiling was chosen with
   float density = 0.f; // nonzero fraction of the weights the tiling was chosen with
@@ -161,8 +141,6 @@ struct DenseArrays {
   MappedWord sk_fail;      // the word the kernel sets when a fix-up wait gave up (sticky until the next WeightAlign)
   mutable bool sk_used = false;   // the last dense launch of this plan split K (escoin_plan_stat "streamk")
 };
-
-constexpr int kBwdChunkPixels = 1024;   // flattened (n, oh, ow) pixels per chunk of the weight-gradient reduction
 
 }  // namespace escoin
 
@@ -276,6 +254,12 @@ int realign_from_host_csr(escoin_plan *p, hipStream_t stream);
 // for the update's stream.
 int sync_host_values(escoin_plan *p);
 long upd_stat(const escoin_plan *p, const char *key);
+// total nonzeros of the plan's host CSR
+inline long plan_nnz(const escoin_plan *p) {
+  long nnz = 0;
+  for (const auto &c : p->colidx) nnz += (long)c.size();
+  return nnz;
+}
 // whether group `grp` of the plan runs on the dense kernel (its units in the stream / generated code are empty)
 inline bool group_is_dense(const escoin_plan *p, int grp) {
   return p->n_dense_groups > 0 && (grp >= 64 || ((p->dense_mask >> grp) & 1ull));
@@ -284,8 +268,8 @@ inline bool group_is_dense(const escoin_plan *p, int grp) {
 long bwd_stat(const escoin_plan *p, const char *key);
 
 // sconv_tiled.hip
-bool tiled_supported(const Geometry &g);
 int tiled_device_cus();             // compute units of the current device
+bool tiled_supported(const Geometry &g);   // align_rules.h's, for the current device
 int tiled_build(escoin_plan *p, hipStream_t stream, bool jit);  // fills p->tiled, uploads streams / loads generated code
 void tiled_release(escoin_plan *p);   // resets p->tiled_dev and p->tiled
 // The fast half of escoin_plan_import_aligned: a generated-code plan restored from what
@@ -296,10 +280,6 @@ int tiled_import(escoin_plan *p, const char *blob, size_t bytes, hipStream_t str
 int launch_tiled(const escoin_plan *p, const float *bottom, const float *bias, float *top,
                  int n_images, hipStream_t stream);
 const char *tiled_kernel_name(const escoin_plan *p);
-
-// escoin_capi.hip: KERNEL_AUTO's rule for pointwise launches of one round of workgroups under 64 MFLOP, evaluated from
-// the tiling before any code is generated or loaded: 0 not considered, 1 generated code, 2 the generic kernel.
-int small_launch_rule(const escoin_plan *p, const Tiling &t, bool chained);
 
 // sconv_lowered.hip (conv_mode LOWERED_SPARSE: im2col + CSR x dense, the lowering baseline)
 int launch_lowered(escoin_plan *p, const float *bottom, const float *bias, float *top, int n_images,

@@ -36,6 +36,7 @@
 #include <string>
 #include <vector>
 
+#include "align_rules.h"
 #include "escoin_plan.h"
 
 namespace escoin {
@@ -274,11 +275,9 @@ escoin_sconv_wgrad_sum_f64_kernel(const double *slab_w, const double *slab_b, co
 // An entry belongs to one (output channel, input-channel block): every slab element has one writer.  Dead pixels of the
 // last chunk are masked by select (their G is 0, but 0 x a staged non-finite value is not): a non-finite bottom element
 // reaches only the entries whose tap reads it.
-constexpr int kStgWaves = 8;                         // waves per workgroup
+// (kStgWaves waves per workgroup, kStgLdsBudget, kStgSmallInt: align_rules.h, with the rule that plans the blocks)
 constexpr int kStgPix = kChunkPixels / 64;           // pixels per lane: a wave covers the whole chunk
 constexpr int kStgBatch = 8;                         // entries per batched reduction
-constexpr size_t kStgLdsBudget = 64 * 1024;          // two workgroups per CU
-constexpr int kStgSmallInt = 1 << 21;                // div_small's range
 
 struct StagedArgs {
   const float *__restrict__ bottom;
@@ -586,79 +585,6 @@ static int build_gather(escoin_plan *p, BwdState *s, const std::vector<std::vect
   return ESCOIN_OK;
 }
 
-// The staged weight-gradient kernel's block plan (sconv_backward.hip header of that kernel): the LDS tile and the split
-// of a conv group's input channels into staged blocks.  AUTO's rule and stg_build both read this one.
-struct StgPlan {
-  int rows_max = 0;   // padded rows of the tile: the longest chunk's span
-  int cs = 0;         // floats per staged channel: rows_max * Wp
-  int icb = 0;        // input channels per staged block
-  int nblk = 0;       // blocks per conv group (grid z)
-  int chunks = 0;     // chunks of the full batch
-  int osplit = 1;     // workgroups a conv group's output channels are dealt over
-};
-
-// Whether the staged kernel serves this plan, and its block plan where it does.
-static bool stg_plan(const escoin_plan *p, StgPlan *sp) {
-  const Geometry &g = p->g;
-  const escoin_conv_desc &d = g.d;
-  if (p->is_f64 || d.stride_h != 1 || d.stride_w != 1) return false;
-  const long opix = (long)g.OH * g.OW;
-  const long Hp = (long)d.H + 2 * d.pad_h, Wp = (long)d.W + 2 * d.pad_w;
-  if (opix > kStgSmallInt / 2 || Hp > kStgSmallInt / 2 || Wp > kStgSmallInt / 2) return false;   // div_small
-  if ((double)d.N * d.M * (double)opix >= 2147483648.0 || (double)d.N * d.C * (double)d.H * d.W >= 2147483648.0) return false;
-  if ((double)d.N * (double)Hp >= 1073741824.0) return false;
-  // the longest span of padded rows a chunk touches
-  const long total = (long)d.N * opix;
-  const int span_h = d.dil_h * (d.KH - 1);
-  long rows = 0;
-  for (long q0 = 0; q0 < total; q0 += kChunkPixels) {
-    const long q1 = std::min(total, q0 + kChunkPixels) - 1;
-    const long n0 = q0 / opix, n1 = q1 / opix;
-    const long P0 = n0 * Hp + (q0 - n0 * opix) / g.OW, P1 = n1 * Hp + (q1 - n1 * opix) / g.OW + span_h;
-    rows = std::max(rows, P1 - P0 + 1);
-  }
-  if (rows < 1 || (size_t)rows * (size_t)Wp * sizeof(float) > kStgLdsBudget) return false;
-  sp->rows_max = (int)rows;
-  sp->cs = (int)(rows * Wp);
-  sp->icb = (int)std::min<size_t>((size_t)g.Cg, kStgLdsBudget / (sizeof(float) * (size_t)sp->cs));
-  if (p->wgrad_channel_block > 0) sp->icb = std::min(sp->icb, p->wgrad_channel_block);
-  sp->nblk = (g.Cg + sp->icb - 1) / sp->icb;
-  sp->chunks = (int)((total + kChunkPixels - 1) / kChunkPixels);
-  // enough workgroups for two per CU where the chunks and blocks alone do not give them: deal the output channels
-  const long wgs = (long)sp->chunks * d.group * sp->nblk;
-  const long want = 2L * std::max(tiled_device_cus(), 1);
-  const int osplit = (int)std::min<long>((g.Mg + kStgWaves - 1) / kStgWaves, (want + wgs - 1) / std::max(wgs, 1L));
-  sp->osplit = std::max(1, std::min(osplit, 65535 / std::max(d.group, 1)));
-  return sp->nblk <= 65535;   // grid z
-}
-
-// AUTO's rule for the weight gradient: a function of the geometry, nnz and the device's CU count only -- the two
-// kernels' times in microseconds from a cost model fitted to one MI355X run of tools/backward_bench.py
-// (profiles/backward_mi355x.md, "AUTO's rule": the fit, its coefficients and its residuals on the 47 benched layers).
-// Both kernels run in rounds of resident workgroups: the entry kernel's (chunk, output channel) workgroups of 4 waves
-// sit 8 to a CU, the staged kernel's 64 KiB workgroups 2 to a CU.  A last, partly filled round still costs a
-// workgroup's latency, hence the floor on its fraction.
-//   entry   21.3 + 0.153 chunks (its stage 2 walks the chunks serially) + rounds x (3.0 + 1.138 x entries per row)
-//   staged  13.4 + rounds x (19.3 (staging the tile) + steps x (1.02 (loading G) + 0.426 x entries per (row, block)))
-//           with steps = output channels a wave takes in turn
-static double stg_rounds(double workgroups, double resident, double tail_floor) {
-  const double r = workgroups / resident, whole = std::floor(r), tail = r - whole;
-  return whole + (tail > 0 ? std::max(tail, tail_floor) : 0.0);
-}
-static bool stg_auto_prefers(const escoin_plan *p, long nnz, const StgPlan &sp) {
-  const Geometry &g = p->g;
-  const escoin_conv_desc &d = g.d;
-  if (nnz <= 0) return false;
-  const double cus = (double)std::max(tiled_device_cus(), 1);
-  const double entry = 21.3 + 0.153 * sp.chunks +
-                       stg_rounds((double)sp.chunks * d.M, 8.0 * cus, 0.3) * (3.0 + 1.138 * (double)nnz / d.M);
-  const int steps = ((g.Mg + sp.osplit - 1) / sp.osplit + kStgWaves - 1) / kStgWaves;
-  const double per_pair = (double)nnz / ((double)d.M * sp.nblk);
-  const double staged = 13.4 + stg_rounds((double)sp.chunks * d.group * sp.nblk * sp.osplit, 2.0 * cus, 0.4) *
-                                   (19.3 + steps * (1.02 + 0.426 * per_pair));
-  return staged < entry;
-}
-
 static int stg_build(escoin_plan *p, BwdState *s, const StgPlan &sp, hipStream_t stream) {
   const Geometry &g = p->g;
   const escoin_conv_desc &d = g.d;
@@ -713,7 +639,7 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
     return fail(ESCOIN_EINVAL, "backward_kernel: this plan has no transposed forward plan (needs a float plan, stride 1, "
                                "pad <= dilation * (kernel - 1)); only the gather kernel serves it");
   StgPlan sp;
-  const bool staged_ok = stg_plan(p, &sp);
+  const bool staged_ok = stg_plan(g, p->is_f64, p->wgrad_channel_block, tiled_device_cus(), &sp);
   if (p->wgrad_kernel == ESCOIN_WGRAD_STAGED && !staged_ok)
     return fail(ESCOIN_EINVAL, "wgrad_kernel: the staged weight-gradient kernel needs a float plan with stride 1 whose "
                                "chunk tile of one input channel fits the LDS budget; only the entry kernel serves this plan");
@@ -746,7 +672,7 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   ESCOIN_HIP_TRY(s->slab.alloc(slab));
   s->wgrad = ESCOIN_WGRAD_ENTRY;
   if (staged_ok && (p->wgrad_kernel == ESCOIN_WGRAD_STAGED ||
-                    (p->wgrad_kernel == ESCOIN_WGRAD_AUTO && stg_auto_prefers(p, s->nnz, sp)))) {
+                    (p->wgrad_kernel == ESCOIN_WGRAD_AUTO && stg_auto_prefers(g, s->nnz, sp, tiled_device_cus())))) {
     if ((rc = stg_build(p, s, sp, stream)) != ESCOIN_OK) return rc;
     s->wgrad = ESCOIN_WGRAD_STAGED;
   }

@@ -1,5 +1,7 @@
 // stream_builder.h -- host-side construction of the tiled kernel's tiling and weight stream.
 // Pure C++ (no HIP): WeightAlign's MI355X-specific half, unit-testable on a CPU-only box.
+// (The rules that choose among these tilings per layer -- plane budgets, buffers, half-workgroups -- are align_rules.h's,
+// host-only like this file.)
 //
 // The tiled kernel (sconv_tiled.hip) computes, per workgroup, an output block of
 //   (oc_waves * G output channels) x (pix_waves * 2 * 64 output "quads" of 4 adjacent pixels)

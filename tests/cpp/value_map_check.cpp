@@ -15,6 +15,7 @@
 #include <cstring>
 #include <vector>
 
+#include "align_rules.h"
 #include "jit_codegen.h"
 #include "stream_builder.h"
 
@@ -31,7 +32,33 @@ static uint32_t bits_of(float v) {
   return u;
 }
 
-struct Case { int N, C, H, W, M, KH, KW, ph, pw, group; float sparsity; int waves; int lds; int ncu = 1; };
+struct Case { int N, C, H, W, M, KH, KW, ph, pw, group; float sparsity; int waves; int lds; int ncu = 1; int product = 0; };
+
+// Cases with `product` set take the tiling and the generator's options of their generated-code run from the product's
+// own layout rule (csrc/align_rules.h jit_layout) for a batch of 256 on 256 CUs instead of assembling them by hand;
+// the value names the branch of the rule the case is there for, and missing it fails the case:
+//   1 = 3x3 with more than one workgroup column (32 KiB planes), 2 = one column (64 KiB planes),
+//   3 = three plane buffers (pointwise), 4 = two 4-wave workgroups per CU (pointwise)
+static bool product_layout(const Case &cs, float density, Tiling *t, jit::Options *jo) {
+  Geometry G{};
+  G.d = escoin_conv_desc{cs.N, cs.C, cs.H, cs.W, cs.M, cs.KH, cs.KW, cs.ph, cs.pw, 1, 1, 1, 1, cs.group, 1, 0};
+  G.OH = cs.H + 2 * cs.ph - cs.KH + 1;
+  G.OW = cs.W + 2 * cs.pw - cs.KW + 1;
+  G.Cg = cs.C / cs.group;
+  G.Mg = cs.M / cs.group;
+  G.kdim = G.Cg * cs.KH * cs.KW;
+  const JitLayout lay = jit_layout(G, density, 256, 256);
+  if (!lay.ok) { printf("product layout: the layer does not fit\n"); return false; }
+  const bool hit = cs.product == 1 ? lay.t.n_ocblk > 1 && lay.budget == 32 * 1024 && lay.t.waves == 8
+                 : cs.product == 2 ? lay.t.n_ocblk == 1 && lay.budget == 64 * 1024 && lay.nbuf == 2
+                 : cs.product == 3 ? lay.nbuf == 3 && lay.jopt.dma.ahead == 2
+                                   : lay.t.waves == 4 && lay.nbuf == 2;
+  if (!hit) { printf("product layout: branch %d not taken (columns=%d budget=%d nbuf=%d waves=%d)\n", cs.product, lay.t.n_ocblk, lay.budget, lay.nbuf, lay.t.waves); return false; }
+  *t = lay.t;
+  *jo = lay.jopt;
+  return true;
+}
+
 
 typedef std::vector<std::vector<int>> Idx;
 typedef std::vector<std::vector<float>> Val;
@@ -103,12 +130,15 @@ static int run(const Case &cs, bool use_jit) {
   // (options as tests/cpp/emulate_tiled.cpp derives them from the case: both read-ahead depths, both weight placements,
   //  plane DMA with one and two fills in flight, chained and unchained units)
   jit::Options jo;
-  jo.depth = 1 + (cs.N & 1);
-  jo.prio_rows = (cs.M & 1) ? 2 : 0;
-  jo.hi_sets = (cs.N & 1) ? 24 : 0;
-  jo.depth_one_tile = (cs.N & 1) ? 5 + cs.N % 9 : 5;
-  jo.sweights = cs.KW != 1 && (cs.C & 3) != 1;
-  if (t.pix_waves == 1 && (t.waves == 8 || t.waves == 4)) {
+  if (cs.product && !product_layout(cs, g.density, &t, &jo)) return 2;
+  if (!cs.product) {
+    jo.depth = 1 + (cs.N & 1);
+    jo.prio_rows = (cs.M & 1) ? 2 : 0;
+    jo.hi_sets = (cs.N & 1) ? 24 : 0;
+    jo.depth_one_tile = (cs.N & 1) ? 5 + cs.N % 9 : 5;
+    jo.sweights = cs.KW != 1 && (cs.C & 3) != 1;
+  }
+  if (!cs.product && t.pix_waves == 1 && (t.waves == 8 || t.waves == 4)) {
     int padded = 0;
     jo.dma.period = jit::dma_period(t.plane_ch_floats / 4, 1 << 24, 0.0, &padded);
     jo.dma.on = jo.dma.period > 0 && padded == t.plane_ch_floats / 4;
@@ -183,6 +213,11 @@ int main() {
       // tiny images, the whole layer in one block: units of more than 30 000 nonzeros keep their literal moves while the
       // other units of the same program use weight lines
       {1, 900, 2, 2, 380, 3, 3, 1, 1, 1, 0.05f, 8, 65536},
+      // tiling and options from the product's layout rule (product_layout above)
+      {2, 40, 14, 14, 80, 3, 3, 1, 1, 1, 0.9f, 8, 65536, 256, 1},
+      {2, 5, 56, 56, 16, 3, 3, 1, 1, 1, 0.9f, 8, 65536, 256, 2},
+      {3, 120, 14, 14, 24, 1, 1, 0, 0, 1, 0.95f, 8, 65536, 256, 3},
+      {3, 24, 28, 28, 16, 1, 1, 0, 0, 1, 0.95f, 8, 65536, 256, 4},
   };
   int bad = 0;
   for (const Case &c : cases) {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""GPU box: the data KERNEL_AUTO's small-launch rule (escoin_capi.hip) is fitted to.  For 1 .. 32 images of every distinct
+"""GPU box: the data KERNEL_AUTO's small-launch rule (csrc/align_rules.cpp) is fitted to.  For 1 .. 32 images of every distinct
 GoogLeNet 1x1 shape (and the four ResNet 3x3 shapes for reference): generated code and the generic kernel, both FORCED
 (plan option "kernel"), 60 launches, best of three, on one reused bottom / top pair (what an image-by-image caller --
 the reference's SCONV mode, conv_layer.cu:16-26 -- does).  One line of JSON per cell with the features the rule may use.
