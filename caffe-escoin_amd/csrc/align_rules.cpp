@@ -173,6 +173,31 @@ int small_launch_rule(const Geometry &g, int kernel_choice, int n_dense_groups, 
   return pick;
 }
 
+bool epi5_reach_ok(const Tiling &t) {
+  const int r = t.W & 3, full = (t.W + 3) / 4;          // quads holding the row
+  return (r == 1 || r == 2) || t.RS >= 4 * (full + 1) || (r == 0 && t.S4 == 16);
+}
+
+int body_variant(const Geometry &g, const Tiling &t, const BodyLaunch &l, int option) {
+  if (option == 0) return 0;
+  // the plan: what ChainPlan needs (jit_layout; an imported blob is checked again here)
+  if (!(l.jit && l.chained && l.dma_in_code && l.stage_bytes == 0 && t.pix_waves == 1 && t.oc_waves == t.waves &&
+        t.n_ocg % t.oc_waves == 0))
+    return 0;
+  if (!static_pad(g) || l.strided || l.n_dense_groups > 0 || !l.epi_store) return 0;
+  // the body divides workgroup ids by grid.x and by the columns with a float reciprocal (exact below these bounds)
+  if (l.workgroups >= (1l << 20) || t.n_ocblk >= 4096) return 0;
+  if (g.d.KW != 1) {
+    // in-place asm epilogue: the element a row-edge lane pulls in through DPP is a zero anyway (padding column, after
+    // masking) or the row ends at a DPP row boundary
+    const bool wide = t.S4 > 16;
+    const bool fast_epi = !wide && (t.RS > t.W || t.S4 == 16);
+    if (!fast_epi) return 0;
+    if (g.d.KW == 5 && !epi5_reach_ok(t)) return 0;
+  }
+  return 1;
+}
+
 // Generated code: nothing but the planes (and two small tables) lives in LDS -- the first tiling
 // the budget allows is the one.  WeightAlign = tiling, channel deal, code generation, code
 // object (jit_module.h), unit table.

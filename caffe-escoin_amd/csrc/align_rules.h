@@ -52,6 +52,25 @@ std::string tiling_info(const Tiling &t, bool jit, int nbuf, size_t lds_bytes, i
 int small_launch_rule(const Geometry &g, int kernel_choice, int n_dense_groups, int tiling_batch, long nnz, const Tiling &t,
                       bool chained, int n_cu);
 
+// 5x5 / pad 2 reaches two columns past a row: the asm epilogue needs whatever lies there in the lane order to be a
+// zero-filled quad (or masked elements of the row's own partial quad).
+bool epi5_reach_ok(const Tiling &t);
+
+// Which compiled body a launch of generated code runs (sconv_tiled.hip): 1 = the chained instantiation, 0 = the
+// generic body.  The chained one serves plans whose code stages its own planes and runs a tile as one call, on
+// launches whose epilogue is the asm one that stores from the accumulators: static padding (1x1 / 0, 3x3 / 1,
+// 5x5 / 2), rows no longer than a DPP row whose edge lanes pull in zeros (3x3, 5x5; for 5x5 also epi5_reach_ok), a
+// top blob under 2 GiB.  option: plan option "body_variant" (-1 this rule, 0 always generic).
+struct BodyLaunch {
+  bool jit = false, chained = false, dma_in_code = false;   // the plan: generated code, jit_chain, jit_dma
+  int stage_bytes = 0;                                      // LDS-staged weight stream per wave (0 for generated code)
+  bool strided = false;                                     // strided pointwise view
+  int n_dense_groups = 0;                                   // conv groups on the MFMA kernel
+  bool epi_store = false;                                   // the launch's top blob is under 2 GiB
+  long workgroups = 0;                                      // grid.x * grid.y
+};
+int body_variant(const Geometry &g, const Tiling &t, const BodyLaunch &l, int option);
+
 // Generated code: the tiling, the plane buffers and the generator's options.  ok == false: the layer does not fit.
 struct JitLayout {
   bool ok = false;

@@ -455,6 +455,11 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->wgrad_channel_block = value;
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "body_variant")) {
+      if (value < -1 || value > 0) return fail(ESCOIN_EINVAL, "body_variant must be -1 (automatic) or 0 (generic)");
+      p->body_variant = value;
+      return ESCOIN_OK;
+    }
     if (!strcmp(key, "stream_stores")) {
       if (value < -1 || value > 1) return fail(ESCOIN_EINVAL, "stream_stores must be -1, 0 or 1");
       p->stream_stores = value;
@@ -737,6 +742,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "deal_slowest_over_mean_x1000")) return p->tiled.jit ? (long)(p->tiled.deal_slowest_over_mean * 1000.f + 0.5f) : 0;
   if (!strcmp(key, "deal_worst_block_x1000")) return p->tiled.jit ? (long)(p->tiled.deal_worst_block * 1000.f + 0.5f) : 0;
   if (!strcmp(key, "lds_bytes")) return p->tiled.enabled ? (long)p->tiled.lds_bytes : 0;
+  if (!strcmp(key, "body_variant")) return p->tiled.enabled ? p->tiled.body_variant_last : 0;
   if (!strcmp(key, "workgroup_columns")) return p->tiled.enabled ? p->tiled.tiling.n_ocblk : 0;
   if (!strcmp(key, "streamk_gave_up")) {
     // dense kernel, stream-K launches: 1 if a workgroup's bounded wait for another one's partial sums ran out in

@@ -61,6 +61,7 @@ struct TiledConfig {
   bool jit_chain = false;    // a tile's units run as one chain (jit_codegen.h ChainPlan)
   float deal_slowest_over_mean = 1.f, deal_worst_block = 1.f;   // balance of the channel deal (jit_codegen.h Program)
   std::string info;          // escoin_plan_tiling_info
+  mutable int body_variant_last = 0;   // stat "body_variant": the compiled body of the last tiled launch (0 generic, 1 chained)
 };
 
 // One host thread's buffers of the CPU mode (sconv_cpu.cpp): the shared-halo padded image and the store scratch.
@@ -197,6 +198,7 @@ struct escoin_plan {
   unsigned long long dense_mask = 0, sparse_mask = ~0ull;
   int n_dense_groups = 0, n_sparse_groups = 0;
   int dense_threshold_pct = -1;   // option "dense_threshold_pct" (-1: the measured default)
+  int body_variant = -1;          // option "body_variant": -1 the rule (align_rules.h body_variant), 0 always the generic body
   int stream_stores = -1;         // option "stream_stores": pointwise layers write the top blob with non-temporal stores (1), never (0), by size (-1)
 
   // LOWERED_SPARSE comparator (sconv_lowered.hip): column buffer, grown on demand by the forward

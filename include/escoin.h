@@ -155,6 +155,11 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  and the code object loader where that is not to be had; 1: always the code object loader
  *                  (hipModuleLoadData on the code wrapped in a code object, 0.6-1 ms per megabyte).  The code is the
  *                  same words either way; tests use 1 to exercise the fallback.  stat "code_direct" says which.
+ *   "body_variant" = which compiled kernel body runs around a chained plan's generated code.  -1 (default): the
+ *                  chained instantiation wherever the plan and the launch meet its conditions (csrc/align_rules.h
+ *                  body_variant), the generic body otherwise; 0: always the generic body.  Both call the same code
+ *                  and run the same epilogue: results are bit-identical; tests and same-call A/B runs use 0.  May be
+ *                  set on an aligned plan; stat "body_variant" = what the last forward ran (0 generic, 1 chained).
  * Environment: the product build reads ESCOIN_VERBOSE (diagnostics on stderr) and TMPDIR (temporary file of the
  * code object manager's fallback path) and nothing else -- no environment variable can change a result
  * ("Environment"; csrc/knobs.h for the non-product flavours built by tools/mkabl.sh exp / stamps). */
@@ -216,6 +221,7 @@ ESCOIN_API int escoin_plan_import_aligned_dev(escoin_plan *plan, const void *dev
  * "device_bytes", "import_fast", "code_direct" (1: the plan's generated code sits in executable device memory the library
  * filled itself, 0: in a module the HIP loader loaded -- option "code_loader"), "cpu_channel_block" / "cpu_images_per_job"
  * (what the last escoin_forward_cpu used), "jit_rows", "jit_records", "lds_bytes", "workgroup_columns",
+ * "body_variant" (the compiled body the last tiled launch ran: 0 generic, 1 chained -- option "body_variant"),
  * "kernel_choice" (the ESCOIN_KERNEL_* id AUTO resolved to for the sparse groups), "small_launch_rule" (KERNEL_AUTO's
  * rule for pointwise launches under 64 MFLOP that fit one round of workgroups -- the reference's SCONV mode runs
  * image by image, conv_layer.cu:16-26 --: 0 not considered, 1 kept generated code, 2 took the generic kernel (decided
