@@ -198,6 +198,37 @@ int body_variant(const Geometry &g, const Tiling &t, const BodyLaunch &l, int op
   return 1;
 }
 
+TiledLaunchShape tiled_launch_shape(const Geometry &g, const Tiling &t, int n_images, int groups, bool jit, long code_bytes,
+                                    int n_cu) {
+  TiledLaunchShape s;
+  s.tiles = t.band_mode ? n_images * t.bands : (n_images + t.nseg - 1) / t.nseg;
+  s.epi_store = (size_t)n_images * g.d.M * t.OH * t.OW * 4 < ((size_t)1 << 31);
+  // persistent workgroups: one 8-wave workgroup per CU is resident (2 waves/SIMD); each walks
+  // its share of the pixel tiles so that prologue, first fill and epilogue overlap across tiles
+  s.grid_y = groups * t.n_ocblk;
+  const int wg_per_cu = std::max(1, 8 / t.waves);
+  const int gx = std::max(1, (n_cu * wg_per_cu) / s.grid_y);
+  s.grid_x = std::min(s.tiles, gx);
+  // Workgroup columns grouped by XCD (sconv_tiled.hip tiled_body): for generated code of more than one column whose bytes
+  // do not sit comfortably in an XCD's 4 MiB L2 beside the streaming input -- from 2 MB of code (round 4: 4 MB for
+  // layers without conv groups; with the round-5 code res4 @90 %, 2.9 MB, gains 4 %: profiles/r05_knob_retune.md).  Measured, same-call pairs
+  // (profiles/r04_xcd_map.md): the gain grows with the code -- below 2 MB none, 2-4 MB 2-12 %, above 5 MB
+  // 17-31 % (AlexNet @80 % all on generated code 0.632 -> 0.524 ms per step; res5 @70 % 369 -> 281 us).  The
+  // price: every XCD reads the input tiles of its own columns instead of sharing them through one L2 -- extra
+  // L2 misses (served mostly by the Infinity Cache), which is why layers whose code fits keep the launch order
+  // (res2-res4 @90 %: time within 1 % either way, 1.2-1.5x instead of 1.6-2.7x algorithmic bytes fetched).
+  // The stream kernel has no code to keep apart and always keeps the launch order.
+  // ESCOIN_XCD_MAP: 0 never, 1 wherever there is more than one column, unset: the rule above.
+  static const int xm = (int)ESC_KNOB("XCD_MAP", -1);
+  static const long min_code_env = ESC_KNOB_SET("XCD_MIN_CODE_KB") ? ESC_KNOB("XCD_MIN_CODE_KB", 0) * 1024 : -1;
+  const long min_code = min_code_env >= 0 ? min_code_env : 2l << 20;
+  const int nwg = s.grid_x * s.grid_y;
+  const bool on = s.grid_y > 1 && nwg >= 8 && (xm == 1 || (xm < 0 && jit && code_bytes >= min_code));
+  s.xcd_q = on ? nwg / 8 : -1;
+  s.xcd_r = on ? nwg % 8 : 0;
+  return s;
+}
+
 // Generated code: nothing but the planes (and two small tables) lives in LDS -- the first tiling
 // the budget allows is the one.  WeightAlign = tiling, channel deal, code generation, code
 // object (jit_module.h), unit table.
@@ -321,7 +352,7 @@ JitLayout jit_layout(const Geometry &g, float density, int tiling_batch, int n_c
   jopt.chain.nbuf = jit_nbuf;
   jopt.chain.buf_bytes = (uint32_t)((t.planes_bytes + 1023) / 1024 * 1024 + 1024);
   // weights through the scalar cache instead of a literal move per nonzero: the 3x3 / 5x5 layers (their kernel
-  // instantiations carry the longer clobber list, tiled_body)
+  // instantiations carry the longer clobber list, sconv_tiled.hip chain_call)
   jopt.sweights = g.d.KW != 1 ? 1 : 0;
   // s_setprio 1 / 0 alternating every four rows in the units of the first half of a workgroup's waves: the two
   // waves of a SIMD then take turns at the FMA pipe in bursts instead of interleaving instruction by instruction,

@@ -71,6 +71,18 @@ struct BodyLaunch {
 };
 int body_variant(const Geometry &g, const Tiling &t, const BodyLaunch &l, int option);
 
+// One launch of a tiled plan (sconv_tiled.hip launch_tiled_once) over n_images images: the pixel tiles, the grid of
+// persistent workgroups that walk them and whether the workgroup columns are grouped by XCD.  groups: the conv groups
+// the launch covers (the sparse ones when others run on the MFMA kernel); jit / code_bytes: generated code and its size.
+struct TiledLaunchShape {
+  int tiles = 0;                 // pixel tiles; a workgroup walks tiles blockIdx.x, + grid_x, ...
+  int grid_x = 0, grid_y = 0;    // grid_y = groups x workgroup columns (n_ocblk)
+  int xcd_q = -1, xcd_r = 0;     // columns grouped by XCD: workgroups / 8 and % 8; xcd_q < 0: the launch order
+  bool epi_store = false;        // the launch's top blob is under 2 GiB (the asm epilogues' 32-bit store offsets)
+};
+TiledLaunchShape tiled_launch_shape(const Geometry &g, const Tiling &t, int n_images, int groups, bool jit, long code_bytes,
+                                    int n_cu);
+
 // Generated code: the tiling, the plane buffers and the generator's options.  ok == false: the layer does not fit.
 struct JitLayout {
   bool ok = false;

@@ -3,8 +3,8 @@
 //
 // Compiled with plain g++ against align_rules.cpp, stream_builder.cpp and jit_codegen.cpp: no HIP header, no device.
 // Reads align_rules_check.cpp's manifest (one case per line, the options kernel / tiling_batch and n_cu are used),
-// takes each case to its layout the way sconv_tiled.hip's tiled_build does, sizes the launch of the full batch the way
-// launch_tiled_once does and prints one JSON line per case: the layout's tiling_info and the rule's answer.
+// takes each case to its layout the way sconv_tiled.hip's tiled_build does, sizes the launch of the full batch with
+// tiled_launch_shape, as launch_tiled_once does, and prints one JSON line per case: the layout's tiling_info and the rule's answer.
 #include <algorithm>
 #include <cstdio>
 #include <fstream>
@@ -72,13 +72,11 @@ int main(int argc, char **argv) {
     }
     int variant = 0;
     if (t.ok) {
-      // the launch of the full batch (launch_tiled_once)
+      // the launch of the full batch, every conv group sparse (the XCD grouping does not enter the rule: no code size)
+      const TiledLaunchShape ls = tiled_launch_shape(g, t, d.N, d.group, bl.jit, 0, n_cu);
       bl.strided = strided_pointwise(g);
-      bl.epi_store = (size_t)d.N * d.M * t.OH * t.OW * 4 < ((size_t)1 << 31);
-      const long tiles = t.band_mode ? (long)d.N * t.bands : ((long)d.N + t.nseg - 1) / t.nseg;
-      const long gy = (long)d.group * t.n_ocblk;
-      const long gx = std::max(1l, (long)n_cu * std::max(1, 8 / t.waves) / gy);
-      bl.workgroups = std::min(tiles, gx) * gy;
+      bl.epi_store = ls.epi_store;
+      bl.workgroups = (long)ls.grid_x * ls.grid_y;
       variant = body_variant(g, t, bl, -1);
       if (body_variant(g, t, bl, 0) != 0) { fprintf(stderr, "option 0 must give the generic body\n"); return 2; }
     }

@@ -37,7 +37,23 @@ CASES = [
     # pointwise chain with three plane buffers
     ("pointwise", (5, 64, 14, 14, 64, 1, 0, 0.95), ("nbuf=3", "chained=1"), 1),
     ("five", (4, 16, 13, 13, 32, 5, 2, 0.8), ("chained=1",), 1),
+    # the asm epilogue families the two bodies share (sconv_tiled.hip epi_asm_*), one row per family and OW % 4; a fifth
+    # element holds further plan options
+    # pointwise, rows of whole quads (ESC_EPI1S), both tiles; the same with non-temporal stores (ESC_EPI1SN)
+    ("pw28", (3, 64, 28, 28, 64, 1, 0, 0.95), ("cut=98x8", "band=1", "n_icb=4", "chained=1"), 1),
+    ("pw28_nt", (3, 64, 28, 28, 64, 1, 0, 0.95), ("cut=98x8", "band=1", "n_icb=4", "chained=1"), 1, {"stream_stores": 1}),
+    # pointwise, rows ending in a partial quad (ESC_EPI1SP): OW % 4 = 1, 2, 3
+    ("pw7x7", (9, 64, 7, 7, 128, 1, 0, 0.95), ("cut=1x49", "chained=1"), 1),
+    ("pw6x7", (9, 64, 6, 7, 64, 1, 0, 0.95), ("cut=1x42", "chained=1"), 1),
+    ("pw5x7", (9, 64, 5, 7, 64, 1, 0, 0.95), ("cut=1x35", "chained=1"), 1),
+    # one quad per lane, 32 channels per wave: slots 24 .. 47 come out of tile B's registers -- partial and whole quads
+    ("pw_tail_p", (17, 64, 7, 7, 768, 1, 0, 0.95), ("cut=1x49", "tpl=1", " G=32", "chained=1"), 1),
+    ("pw_tail_w", (5, 64, 8, 8, 768, 1, 0, 0.95), ("cut=1x64", "tpl=1", " G=32", "chained=1"), 1),
+    # 5x5: OW % 4 = 2; band mode with OW % 4 = 0
+    ("five14", (4, 16, 14, 14, 32, 5, 2, 0.8), ("cut=14x14", "chained=1"), 1),
+    ("five28", (3, 16, 28, 28, 32, 5, 2, 0.8), ("cut=28x28", "band=1", "chained=1"), 1),
 ]
+CASES = [c if len(c) == 5 else c + ({},) for c in CASES]
 
 
 @pytest.fixture(scope="module")
@@ -66,8 +82,8 @@ def _tiling_or_skip(torch, info, expect):
     assert not missing, (missing, info)
 
 
-@pytest.mark.parametrize("name,dims,expect,variant", CASES, ids=[c[0] for c in CASES])
-def test_chained_body_equals_generic_body(pkg, oracle, synth, torch_cuda, name, dims, expect, variant):
+@pytest.mark.parametrize("name,dims,expect,variant,options", CASES, ids=[c[0] for c in CASES])
+def test_chained_body_equals_generic_body(pkg, oracle, synth, torch_cuda, name, dims, expect, variant, options):
     torch = torch_cuda
     dev = torch.device("cuda:0")
     for k, on in enumerate((False, True)):          # bias and ReLU off, then on
@@ -77,7 +93,7 @@ def test_chained_body_equals_generic_body(pkg, oracle, synth, torch_cuda, name, 
         want = oracle.conv_forward(g, x, w, b, relu=on, gate=False, threads=4)
         xd = torch.from_numpy(x).to(dev)
         bd = torch.from_numpy(b).to(dev) if b is not None else None
-        auto, generic = _plan(pkg, s, w, on), _plan(pkg, s, w, on, body_variant=0)
+        auto, generic = _plan(pkg, s, w, on, **options), _plan(pkg, s, w, on, body_variant=0, **options)
         assert "jit" in auto.kernel_name and auto.kernel_name == generic.kernel_name
         assert auto.tiling_info == generic.tiling_info
         _tiling_or_skip(torch, auto.tiling_info, expect)
