@@ -49,7 +49,12 @@ API_SYMBOLS = [
     # Weight updates in place
     "escoin_update_values", "escoin_update_values_f64", "escoin_plan_set_values", "escoin_plan_set_values_f64",
     "escoin_update_values_cpu", "escoin_update_values_cpu_f64",
+    # Solver step
+    "escoin_solver_step", "escoin_solver_step_f64", "escoin_solver_step_cpu", "escoin_solver_step_cpu_f64",
+    "escoin_solver_array_step", "escoin_solver_array_step_f64", "escoin_solver_array_step_cpu", "escoin_solver_array_step_cpu_f64",
 ]
+SOLVER_SGD, SOLVER_NESTEROV, SOLVER_ADAM = 0, 1, 2
+REG_NONE, REG_L2, REG_L1 = 0, 1, 2
 
 
 class EscoinError(RuntimeError):
@@ -68,6 +73,69 @@ class ConvDesc(C.Structure):
         return cls(s.N if N is None else N, s.C, s.H, s.W, s.M, s.KH, s.KW, s.pad_h, s.pad_w,
                    s.stride_h, s.stride_w, s.dil_h, s.dil_w, s.group, int(bool(s.bias)),
                    int(bool(fuse_relu)))
+
+
+class SolverDesc(C.Structure):
+    """Mirror of escoin_solver_desc (include/escoin.h "Solver step").  type / regularization also by name:
+    SolverDesc.make(type="adam", regularization="L2", rate=1e-3, ...); rate_dev: an address, or a one-element tensor /
+    array of the plan's Dtype (which the caller keeps alive)."""
+    _fields_ = [("type", C.c_int), ("regularization", C.c_int), ("rate", C.c_double), ("momentum", C.c_double),
+                ("momentum2", C.c_double), ("delta", C.c_double), ("decay", C.c_double), ("diff_scale", C.c_double),
+                ("rate_dev", C.c_void_p), ("diff_is_dense", C.c_int), ("clear_diff", C.c_int)]
+    TYPES = {"sgd": SOLVER_SGD, "nesterov": SOLVER_NESTEROV, "adam": SOLVER_ADAM}
+    REGS = {"none": REG_NONE, "l2": REG_L2, "l1": REG_L1}
+
+    @classmethod
+    def make(cls, type=SOLVER_SGD, regularization=REG_NONE, rate=0.0, momentum=0.0, momentum2=0.999, delta=1e-8, decay=0.0,
+             diff_scale=1.0, rate_dev=None, diff_is_dense=0, clear_diff=0):
+        if isinstance(type, str):
+            type = cls.TYPES[type.lower()]
+        if isinstance(regularization, str):
+            regularization = cls.REGS[regularization.lower()]
+        if rate_dev is not None and not isinstance(rate_dev, int):
+            rate_dev = rate_dev.data_ptr() if hasattr(rate_dev, "data_ptr") else rate_dev.ctypes.data
+        return cls(int(type), int(regularization), rate, momentum, momentum2, delta, decay, diff_scale, rate_dev,
+                   int(bool(diff_is_dense)), int(bool(clear_diff)))
+
+
+def _solver_desc(desc, kw):
+    if desc is not None and kw:
+        raise EscoinError("solver step: pass a SolverDesc or keyword fields, not both")
+    return desc if desc is not None else SolverDesc.make(**kw)
+
+
+def _solver_arrays(arrays, on_device):
+    """Checks one solver call's arrays (None allowed): all numpy or all torch CUDA, one dtype, contiguous (they are written
+    in place).  Returns (their addresses, is_f64)."""
+    some = [a for a in arrays if a is not None]
+    if on_device:
+        import torch
+        assert all(a.is_cuda and a.is_contiguous() for a in some), "solver step: contiguous torch CUDA tensors"
+        assert some[0].dtype in (torch.float32, torch.float64) and all(a.dtype == some[0].dtype for a in some)
+        return [None if a is None else C.c_void_p(a.data_ptr()) for a in arrays], some[0].dtype == torch.float64
+    assert all(isinstance(a, np.ndarray) and a.flags["C_CONTIGUOUS"] and a.flags["WRITEABLE"] for a in some), "solver step: contiguous numpy arrays"
+    assert some[0].dtype in (np.float32, np.float64) and all(a.dtype == some[0].dtype for a in some)
+    return [None if a is None else _np_ptr(a) for a in arrays], some[0].dtype == np.float64
+
+
+def solver_array_step(data, diff, history, history2=None, stream=None, desc=None, **kw):
+    """escoin_solver_array_step: the solver's rule on a plain blob (the bias), torch CUDA tensors updated in place on
+    `stream` (default torch's current stream).  The rule: a SolverDesc, or its fields as keywords."""
+    import torch
+    d = _solver_desc(desc, kw)
+    ptrs, f64 = _solver_arrays([data, diff, history, history2], True)
+    if stream is None:
+        stream = C.c_void_p(torch.cuda.current_stream(data.device).cuda_stream)
+    fn = lib().escoin_solver_array_step_f64 if f64 else lib().escoin_solver_array_step
+    check(fn(C.byref(d), data.numel(), *ptrs, stream), "escoin_solver_array_step")
+
+
+def solver_array_step_cpu(data, diff, history, history2=None, desc=None, **kw):
+    """escoin_solver_array_step_cpu: the same on numpy arrays, in place."""
+    d = _solver_desc(desc, kw)
+    ptrs, f64 = _solver_arrays([data, diff, history, history2], False)
+    fn = lib().escoin_solver_array_step_cpu_f64 if f64 else lib().escoin_solver_array_step_cpu
+    check(fn(C.byref(d), data.size, *ptrs), "escoin_solver_array_step_cpu")
 
 
 def build(verbose=False):
@@ -177,6 +245,16 @@ def lib():
     for name in ("escoin_update_values_cpu", "escoin_update_values_cpu_f64"):
         f = getattr(L, name)
         f.restype, f.argtypes = ip, [vp, vp]
+    sp = C.POINTER(SolverDesc)
+    for suffix in ("", "_f64"):
+        f = getattr(L, "escoin_solver_step" + suffix)
+        f.restype, f.argtypes = ip, [vp, sp, vp, vp, vp, vp, vp]
+        f = getattr(L, "escoin_solver_step_cpu" + suffix)
+        f.restype, f.argtypes = ip, [vp, sp, vp, vp, vp, vp]
+        f = getattr(L, "escoin_solver_array_step" + suffix)
+        f.restype, f.argtypes = ip, [sp, C.c_long, vp, vp, vp, vp, vp]
+        f = getattr(L, "escoin_solver_array_step_cpu" + suffix)
+        f.restype, f.argtypes = ip, [sp, C.c_long, vp, vp, vp, vp]
     L.escoin_cpu_kernel_name.restype = cp
     L.escoin_cpu_kernel_name.argtypes = []
     L.escoin_cpu_kernel_select.restype = ip
@@ -288,6 +366,37 @@ class Plan(object):
         w = np.ascontiguousarray(dense_w, np.float64 if f64 else np.float32)
         fn = lib().escoin_update_values_cpu_f64 if f64 else lib().escoin_update_values_cpu
         check(fn(self._h, _np_ptr(w)), "escoin_update_values_cpu")
+
+    # ---- solver step (include/escoin.h "Solver step") ---------------------------------------------------------------------
+    def solver_step(self, diff, history, history2=None, dense_w=None, stream=None, desc=None, **kw):
+        """The solver's rule and the in-place update in one launch, on torch CUDA tensors (all updated in place),
+        asynchronous on `stream` (default torch's current stream).  diff: values_diff (1-D, nnz elements, get_csr()'s
+        order) or, with diff_is_dense=1, a blobs_[0]-shaped weight_diff; history / history2: nnz elements; dense_w:
+        blobs_[0], which receives the new values at the pattern.  The rule: a SolverDesc, or its fields as keywords
+        (type="sgd" | "nesterov" | "adam", regularization, rate, momentum, momentum2, delta, decay, diff_scale, rate_dev,
+        diff_is_dense, clear_diff)."""
+        import torch
+        d = _solver_desc(desc, kw)
+        ptrs, f64 = _solver_arrays([diff, history, history2, dense_w], True)
+        n = self.nnz()
+        assert diff.numel() == (self.desc.M * int(np.prod(self._grad_shapes())) if d.diff_is_dense else n), "diff: wrong size for its layout"
+        assert history.numel() == n and (history2 is None or history2.numel() == n), "history: nnz elements"
+        assert dense_w is None or dense_w.numel() == self.desc.M * int(np.prod(self._grad_shapes())), "dense_w: blobs_[0]'s size"
+        if stream is None:
+            stream = C.c_void_p(torch.cuda.current_stream(diff.device).cuda_stream)
+        fn = lib().escoin_solver_step_f64 if f64 else lib().escoin_solver_step
+        check(fn(self._h, C.byref(d), *ptrs, stream), "escoin_solver_step")
+
+    def solver_step_cpu(self, diff, history, history2=None, dense_w=None, desc=None, **kw):
+        """solver_step for a plan aligned by weight_align_cpu, on numpy arrays (updated in place)."""
+        d = _solver_desc(desc, kw)
+        ptrs, f64 = _solver_arrays([diff, history, history2, dense_w], False)
+        n = self.nnz()
+        assert diff.size == (self.desc.M * int(np.prod(self._grad_shapes())) if d.diff_is_dense else n), "diff: wrong size for its layout"
+        assert history.size == n and (history2 is None or history2.size == n), "history: nnz elements"
+        assert dense_w is None or dense_w.size == self.desc.M * int(np.prod(self._grad_shapes())), "dense_w: blobs_[0]'s size"
+        fn = lib().escoin_solver_step_cpu_f64 if f64 else lib().escoin_solver_step_cpu
+        check(fn(self._h, C.byref(d), *ptrs), "escoin_solver_step_cpu")
 
     # ---- Caffe::CPU mode (no device needed) ----------------------------------------------------
     def weight_align_cpu(self, dense_w):

@@ -112,6 +112,10 @@ template <> struct EscApi<float> {
   static int backward_cpu(escoin_plan *p, const float *b, const float *t, const float *td, float *bd, float *wd, float *bsd, int n, int threads) { return escoin_backward_cpu(p, b, t, td, bd, wd, bsd, n, threads); }
   static int update_values(escoin_plan *p, const float *w, int on_dev, void *s) { return escoin_update_values(p, w, on_dev, s); }
   static int update_values_cpu(escoin_plan *p, const float *w) { return escoin_update_values_cpu(p, w); }
+  static int solver_step(escoin_plan *p, const escoin_solver_desc *d, float *g, float *h, float *h2, float *w, void *s) { return escoin_solver_step(p, d, g, h, h2, w, s); }
+  static int solver_step_cpu(escoin_plan *p, const escoin_solver_desc *d, float *g, float *h, float *h2, float *w) { return escoin_solver_step_cpu(p, d, g, h, h2, w); }
+  static int solver_array_step(const escoin_solver_desc *d, long n, float *w, float *g, float *h, float *h2, void *s) { return escoin_solver_array_step(d, n, w, g, h, h2, s); }
+  static int solver_array_step_cpu(const escoin_solver_desc *d, long n, float *w, float *g, float *h, float *h2) { return escoin_solver_array_step_cpu(d, n, w, g, h, h2); }
 };
 template <> struct EscApi<double> {
   static int weight_align(escoin_plan *p, const double *w, int on_dev, void *s) { return escoin_weight_align_f64(p, w, on_dev, s); }
@@ -122,6 +126,10 @@ template <> struct EscApi<double> {
   static int backward_cpu(escoin_plan *p, const double *b, const double *t, const double *td, double *bd, double *wd, double *bsd, int n, int threads) { return escoin_backward_cpu_f64(p, b, t, td, bd, wd, bsd, n, threads); }
   static int update_values(escoin_plan *p, const double *w, int on_dev, void *s) { return escoin_update_values_f64(p, w, on_dev, s); }
   static int update_values_cpu(escoin_plan *p, const double *w) { return escoin_update_values_cpu_f64(p, w); }
+  static int solver_step(escoin_plan *p, const escoin_solver_desc *d, double *g, double *h, double *h2, double *w, void *s) { return escoin_solver_step_f64(p, d, g, h, h2, w, s); }
+  static int solver_step_cpu(escoin_plan *p, const escoin_solver_desc *d, double *g, double *h, double *h2, double *w) { return escoin_solver_step_cpu_f64(p, d, g, h, h2, w); }
+  static int solver_array_step(const escoin_solver_desc *d, long n, double *w, double *g, double *h, double *h2, void *s) { return escoin_solver_array_step_f64(d, n, w, g, h, h2, s); }
+  static int solver_array_step_cpu(const escoin_solver_desc *d, long n, double *w, double *g, double *h, double *h2) { return escoin_solver_array_step_cpu_f64(d, n, w, g, h, h2); }
 };
 
 // syncedmem.hpp:56-91: lazily mirrored host/device buffer with a head state.
@@ -261,6 +269,9 @@ class Layer {   // layer.hpp:33-475
   // What a solver calls after ApplyUpdate (Net::Update, net.cpp) on every layer: the learnable blobs changed, the
   // sparsity pattern did not.  The reference has no counterpart -- it would have to WeightAlign again.
   virtual void WeightUpdate() {}
+  // SGDSolver::ApplyUpdate's per-parameter work (Normalize, Regularize, ComputeUpdateValue) and Net::Update for this
+  // layer's learnable blobs in one call (include/escoin.h, "Solver step"); a layer without learnable blobs does nothing.
+  virtual void SolverUpdate(const escoin_solver_desc &) {}
   // layer.hpp:435-475: Reshape every call, mode switch, per-layer forward time in microseconds
   inline Dtype Forward(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &top) {
     Reshape(bottom, top);
@@ -409,6 +420,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       aligned_on_device_ = false;
     }
     aligned_ = true;
+    history_.clear();   // SolverUpdate's histories are per CSR entry of THIS alignment
   }
 
   // After a solver step that kept the pattern (the masked gradient of Backward does): the new values of blobs_[0] go
@@ -428,6 +440,47 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(EscApi<Dtype>::update_values(plan_, this->blobs_[0]->cpu_data(), 0, Caffe::stream()));
     else
       ESCOIN_CHECK(EscApi<Dtype>::update_values_cpu(plan_, this->blobs_[0]->cpu_data()));
+  }
+
+  // SGDSolver::ComputeUpdateValue + Net::Update of this layer as one fused call per blob (include/escoin.h, "Solver
+  // step"): blobs_[0] through escoin_solver_step on the dense diff -- read and cleared at the pattern, the new values
+  // written into the blob's data at the pattern AND into every copy the plan computes from, so no WeightUpdate follows
+  // -- and blobs_[1] through the array step.  `rule` is the solver's rule for both blobs; its diff_is_dense and
+  // clear_diff are set here.  The histories are layer-owned: for blobs_[0] compact (nnz elements in the plan's CSR order),
+  // created zeroed on first use and dropped by every WeightAlign / WeightAlignFrom (the entries of a new alignment are
+  // other weights, whether or not nnz changed; a solver that re-aligns mid-training restarts this layer's momentum).  The brew picks host or device pointers (a
+  // rule.rate_dev must match it); a plan that has a device side is stepped on the device in either brew, which keeps
+  // both sides current.  A layer that is not aligned yet aligns first.
+  virtual void SolverUpdate(const escoin_solver_desc &rule) {
+    ESC_CHECK(plan_ != nullptr);
+    if (!aligned_ || (Caffe::mode() == Caffe::GPU && !aligned_on_device_)) WeightAlign();
+    escoin_solver_desc d = rule;
+    d.diff_is_dense = 1;
+    d.clear_diff = 1;
+    const bool adam = rule.type == ESCOIN_SOLVER_ADAM;
+    const long n = nnz();
+    if (history_.empty()) {
+      history_.assign(4, shared_ptr<Blob<Dtype> >());
+      for (int k = 0; k < 4; ++k) history_[k].reset(new Blob<Dtype>(vector<int>(1, k < 2 ? (int)n : (bias_term_ ? num_output_ : 0))));
+    }
+    Blob<Dtype> &w = *this->blobs_[0];
+    if (aligned_on_device_) {
+      ESCOIN_CHECK(EscApi<Dtype>::solver_step(plan_, &d, w.mutable_gpu_diff(), history_[0]->mutable_gpu_data(),
+                                              adam ? history_[1]->mutable_gpu_data() : nullptr, w.mutable_gpu_data(), Caffe::stream()));
+      if (bias_term_) {
+        Blob<Dtype> &b = *this->blobs_[1];
+        ESCOIN_CHECK(EscApi<Dtype>::solver_array_step(&d, b.count(), b.mutable_gpu_data(), b.mutable_gpu_diff(), history_[2]->mutable_gpu_data(),
+                                                      adam ? history_[3]->mutable_gpu_data() : nullptr, Caffe::stream()));
+      }
+    } else {
+      ESCOIN_CHECK(EscApi<Dtype>::solver_step_cpu(plan_, &d, w.mutable_cpu_diff(), history_[0]->mutable_cpu_data(),
+                                                  adam ? history_[1]->mutable_cpu_data() : nullptr, w.mutable_cpu_data()));
+      if (bias_term_) {
+        Blob<Dtype> &b = *this->blobs_[1];
+        ESCOIN_CHECK(EscApi<Dtype>::solver_array_step_cpu(&d, b.count(), b.mutable_cpu_data(), b.mutable_cpu_diff(), history_[2]->mutable_cpu_data(),
+                                                          adam ? history_[3]->mutable_cpu_data() : nullptr));
+      }
+    }
   }
 
   // The aligned form as one byte blob (CSR + channel deal + unit table + code object), and WeightAlign from such
@@ -451,6 +504,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
     ESCOIN_CHECK(escoin_plan_import_aligned(plan_, blob.data(), blob.size(), Caffe::stream()));
     aligned_ = true;
     aligned_on_device_ = true;
+    history_.clear();
     return escoin_plan_stat(plan_, "import_fast") == 1;
   }
 
@@ -516,6 +570,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
   escoin_plan *plan_;
   escoin_conv_desc desc_;
   bool aligned_ = false, aligned_on_device_ = false;
+  vector<shared_ptr<Blob<Dtype> > > history_;   // SolverUpdate's: {weights' h / m, weights' v, bias' h / m, bias' v}
   Caffe::ConvMode aligned_mode_ = Caffe::SCONV_PAR;
   int num_, channels_, group_, num_output_;
   bool bias_term_, fuse_relu_;

@@ -67,7 +67,7 @@ DeviceBytes device_bytes(const escoin_plan *p) {
                     t.chan.bytes() + t.jit.code_bytes + dn.w.bytes() + dn.ktab.bytes() + dn.sk_ws.bytes() + p->col.bytes(),
                 0, 0};
   if (const UpdState *u = p->upd.get())
-    b.upd = u->src.bytes() + u->off.bytes() + u->buf.bytes() + u->wpos.bytes() + u->stage.bytes();
+    b.upd = u->src.bytes() + u->off.bytes() + u->buf.bytes() + u->wpos.bytes() + u->stage.bytes() + u->e_ptr.bytes() + u->e_off.bytes() + u->e_buf.bytes();
   if (const BwdState *s = p->bwd.get())
     b.bwd = s->trow.bytes() + s->ttap.bytes() + s->tval.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() + s->stg_blk.bytes() + s->stg_off.bytes() +
             (s->tplan ? device_bytes(s->tplan.get()).fwd : 0);

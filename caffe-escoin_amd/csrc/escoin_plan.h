@@ -112,6 +112,24 @@ struct UpdState {
   long n_dst = 0, nnz = 0;
   bool has_bwd = false;         // the list covers the backward state's copies (rebuilt once when that state appears later)
   std::vector<char> h_stage;    // host side of `stage`
+  // The same list entry-major, for the solver step (solver_step.hip), which computes a value once per CSR entry: entry e
+  // is stored at element e_off[k] of buffer e_buf[k] for k in [e_ptr[e], e_ptr[e + 1]).  Built with the first solver
+  // step on an alignment (entry_view), kept by the rebuild that follows the backward state's appearance.
+  DeviceBuffer e_ptr, e_off, e_buf;   // [nnz + 1] int32, [n_dst] uint32, [n_dst] uint8
+  bool entry_view = false;
+  bool vals_only = false;       // a plan without an in-place path: the value array is the only destination (solver step, then a rebuild)
+};
+
+// What a solver step needs of the update state (update_values.hip): where the plan's current values are and the
+// entry-major destinations of the new ones.
+struct SolverTargets {
+  void *base[kUpdMaxBuffers];
+  const int *e_ptr, *wpos;
+  const unsigned *e_off;
+  const unsigned char *e_buf;
+  void *vals;        // gen.vals: nnz elements of the plan's Dtype, CSR order
+  long nnz;
+  bool in_place;     // false: the value array is the only destination and solver_end rebuilds the plan from it
 };
 
 // The generic kernel's device CSR (escoin_capi.hip upload): rowptr [M + 1] absolute offsets into taps / vals; taps and
@@ -256,6 +274,12 @@ int realign_from_host_csr(escoin_plan *p, hipStream_t stream);
 // for the update's stream.
 int sync_host_values(escoin_plan *p);
 long upd_stat(const escoin_plan *p, const char *key);
+// update_values.hip, for solver_step.hip.  solver_begin: the checks of a device-source update (`name` for the messages),
+// update_count, and the update state with its entry-major view, built if need be; t->nnz == 0: nothing to launch.
+// solver_end, after the kernel is in `stream`: the device becomes authoritative, or (no in-place path) the plan is
+// rebuilt from its value array.  T = float | double.
+template <typename T> int solver_begin(escoin_plan *p, const char *name, hipStream_t stream, SolverTargets *t);
+template <typename T> int solver_end(escoin_plan *p, const SolverTargets &t, hipStream_t stream);
 // total nonzeros of the plan's host CSR
 inline long plan_nnz(const escoin_plan *p) {
   long nnz = 0;

@@ -106,15 +106,25 @@ bool in_place_ok(const escoin_plan *q) {
   return q->tiled_dev.jit.direct != nullptr && !q->tiled_dev.val_word.empty();
 }
 
+// entry_view: also the entry-major form of the list (UpdState::e_ptr), for the solver step.  vals_only: the plan has no
+// in-place path -- the list is the value array alone, which a solver step writes before the plan is rebuilt from it.
 template <typename T>
-int build_state(escoin_plan *p, hipStream_t stream) {
+int build_state(escoin_plan *p, hipStream_t stream, bool entry_view, bool vals_only = false) {
   const Geometry &g = p->g;
   std::unique_ptr<UpdState> u(new UpdState());
   std::vector<Dst> dst;
-  int rc = collect<T>(p, nullptr, u.get(), &dst);
-  if (rc != ESCOIN_OK) return rc;
+  int rc = ESCOIN_OK;
   for (const auto &c : p->colidx) u->nnz += (long)c.size();
-  if (const BwdState *s = p->bwd.get()) {
+  if (vals_only) {
+    if (u->nnz > 0 && p->gen.vals.bytes() < sizeof(T) * (size_t)u->nnz) return fail(ESCOIN_EINVAL, "solver_step: the plan's value array is shorter than its CSR");
+    u->base[u->n_buffers++] = p->gen.vals.get<void>();
+    for (long k = 0; k < u->nnz; ++k) dst.push_back({(unsigned char)0, (int)k, (unsigned)k});
+    u->vals_only = true;
+  } else {
+    rc = collect<T>(p, nullptr, u.get(), &dst);
+  }
+  if (rc != ESCOIN_OK) return rc;
+  if (const BwdState *s = vals_only ? nullptr : p->bwd.get()) {
     if ((long)s->tsrc.size() != u->nnz) return fail(ESCOIN_EINVAL, "update_values: the backward state does not match the CSR");
     if (s->tplan) {
       rc = collect<T>(s->tplan.get(), s->tsrc.data(), u.get(), &dst);
@@ -144,6 +154,27 @@ int build_state(escoin_plan *p, hipStream_t stream) {
   ESCOIN_HIP_TRY(u->wpos.upload(wpos, stream));
   ESCOIN_HIP_TRY(u->stage.alloc(sizeof(T) * nz));
   u->h_stage.assign(sizeof(T) * nz, 0);
+  std::vector<int> e_ptr;
+  std::vector<unsigned> e_off;
+  std::vector<unsigned char> e_buf;
+  if (entry_view) {
+    // a counting sort of the (bounds-checked) list by CSR entry; within an entry the buffers ascend
+    e_ptr.assign(nz + 1, 0), e_off.assign(n, 0), e_buf.assign(n, 0);
+    for (const Dst &d : dst) {
+      if (d.src < 0 || (long)d.src >= u->nnz) return fail(ESCOIN_EINVAL, "solver_step: a destination names no CSR entry");
+      ++e_ptr[(size_t)d.src + 1];
+    }
+    for (size_t i = 0; i < nz; ++i) e_ptr[i + 1] += e_ptr[i];
+    std::vector<int> at(e_ptr.begin(), e_ptr.end() - 1);
+    for (const Dst &d : dst) {
+      const size_t k = (size_t)at[(size_t)d.src]++;
+      e_off[k] = d.off, e_buf[k] = d.buf;
+    }
+    ESCOIN_HIP_TRY(u->e_ptr.upload(e_ptr, stream));
+    ESCOIN_HIP_TRY(u->e_off.upload(e_off, stream));
+    ESCOIN_HIP_TRY(u->e_buf.upload(e_buf, stream));
+    u->entry_view = true;
+  }
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
   p->upd = std::move(u);
   return ESCOIN_OK;
@@ -203,10 +234,9 @@ int update_by_rebuild(escoin_plan *p, const T *in, bool from_dense, bool on_devi
 
 int sync_host(escoin_plan *p);
 
+// What every device entry point that changes a plan's values checks first.
 template <typename T>
-int update_t(escoin_plan *p, const T *in, bool from_dense, int on_device, void *stream_v) {
-  const char *name = from_dense ? "update_values" : "set_values";
-  if (!p || !in) return fail(ESCOIN_EINVAL, std::string(name) + ": null argument");
+int check_updatable(const escoin_plan *p, const char *name) {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
     return fail(ESCOIN_ENODEVICE, std::string(name) + ": no HIP device (a plan aligned by escoin_weight_align_cpu is updated by escoin_update_values_cpu)");
@@ -218,13 +248,26 @@ int update_t(escoin_plan *p, const T *in, bool from_dense, int on_device, void *
     if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
       return fail(ESCOIN_ESTATE, std::string(name) + ": the current device is not the device the plan was aligned on");
   }
+  return ESCOIN_OK;
+}
+
+bool plan_in_place_ok(const escoin_plan *p) {
+  const BwdState *bs = p->bwd.get();
+  return in_place_ok(p) && !(bs && bs->tplan && !in_place_ok(bs->tplan.get()));
+}
+
+template <typename T>
+int update_t(escoin_plan *p, const T *in, bool from_dense, int on_device, void *stream_v) {
+  const char *name = from_dense ? "update_values" : "set_values";
+  if (!p || !in) return fail(ESCOIN_EINVAL, std::string(name) + ": null argument");
+  if (const int rc = check_updatable<T>(p, name)) return rc;
   hipStream_t stream = (hipStream_t)stream_v;
   ++p->upd_count;
-  const BwdState *bs = p->bwd.get();
-  if (!in_place_ok(p) || (bs && bs->tplan && !in_place_ok(bs->tplan.get()))) return update_by_rebuild<T>(p, in, from_dense, on_device != 0, stream);
-  if (!p->upd || (p->bwd && !p->upd->has_bwd)) {
+  if (!plan_in_place_ok(p)) return update_by_rebuild<T>(p, in, from_dense, on_device != 0, stream);
+  if (!p->upd || p->upd->vals_only || (p->bwd && !p->upd->has_bwd)) {
+    const bool entry_view = p->upd && p->upd->entry_view && !p->upd->vals_only;
     p->upd.reset();
-    const int rc = build_state<T>(p, stream);
+    const int rc = build_state<T>(p, stream, entry_view);
     if (rc != ESCOIN_OK) return rc;
   }
   UpdState *u = p->upd.get();
@@ -280,6 +323,47 @@ int sync_host_t(escoin_plan *p) {
 int sync_host(escoin_plan *p) { return p->is_f64 ? sync_host_t<double>(p) : sync_host_t<float>(p); }
 
 }  // namespace
+
+template <typename T>
+int solver_begin(escoin_plan *p, const char *name, hipStream_t stream, SolverTargets *t) {
+  if (const int rc = check_updatable<T>(p, name)) return rc;
+  ++p->upd_count;
+  *t = SolverTargets();
+  t->in_place = plan_in_place_ok(p);
+  t->nnz = plan_nnz(p);
+  if (t->nnz == 0) return ESCOIN_OK;      // (nothing is launched: "update_fast" keeps what the last real update left)
+  const UpdState *have = p->upd.get();
+  if (!have || !have->entry_view || have->vals_only != !t->in_place || (t->in_place && p->bwd && !have->has_bwd)) {
+    p->upd.reset();
+    const int rc = build_state<T>(p, stream, true, !t->in_place);
+    if (rc != ESCOIN_OK) return rc;
+  }
+  const UpdState *u = p->upd.get();
+  if (u->nnz != t->nnz || p->gen.vals.bytes() < sizeof(T) * (size_t)t->nnz) return fail(ESCOIN_EINVAL, std::string(name) + ": the update state does not match the CSR");
+  for (int b = 0; b < kUpdMaxBuffers; ++b) t->base[b] = u->base[b];
+  t->e_ptr = u->e_ptr.get<int>(), t->e_off = u->e_off.get<unsigned>(), t->e_buf = u->e_buf.get<unsigned char>(), t->wpos = u->wpos.get<int>();
+  t->vals = p->gen.vals.get<void>();
+  p->upd_last_fast = t->in_place ? 1 : 0;   // (as in update_t: only once the state exists)
+  return ESCOIN_OK;
+}
+
+template <typename T>
+int solver_end(escoin_plan *p, const SolverTargets &t, hipStream_t stream) {
+  if (t.nnz == 0) return ESCOIN_OK;
+  if (!t.in_place) {
+    // the value array holds the new values: read back, everything rebuilt from them as set_csr would (this drops p->upd)
+    return update_by_rebuild<T>(p, static_cast<const T *>(t.vals), false, true, stream);
+  }
+  // the plan cannot see a graph replay: from here until the next align the device holds the values
+  p->dev_authoritative = true;
+  p->sync_host_fn = sync_host;
+  p->upd_stream = stream;
+  return ESCOIN_OK;
+}
+template int solver_begin<float>(escoin_plan *, const char *, hipStream_t, SolverTargets *);
+template int solver_begin<double>(escoin_plan *, const char *, hipStream_t, SolverTargets *);
+template int solver_end<float>(escoin_plan *, const SolverTargets &, hipStream_t);
+template int solver_end<double>(escoin_plan *, const SolverTargets &, hipStream_t);
 
 }  // namespace escoin
 

@@ -451,7 +451,8 @@ ESCOIN_API int escoin_backward_cpu_f64(escoin_plan *plan, const double *bottom, 
 
 /* The same backward with the weight gradient in COMPACT form: values_diff holds nnz elements in the order of
  * escoin_plan_get_csr, groups concatenated -- the order escoin_plan_set_values reads, so a solver can run on compact
- * tensors (v -= lr * values_diff; escoin_plan_set_values(v)) and a data-parallel all-reduce moves nnz values, not a
+ * tensors (v -= lr * values_diff; escoin_plan_set_values(v) -- or escoin_solver_step on values_diff, below) and a
+ * data-parallel all-reduce moves nnz values, not a
  * blob that is 90-95 % zeros.  values_diff is accumulated (+=); explicit zeros of the CSR receive a gradient; nothing
  * outside the nnz elements is touched.  Everything else is escoin_backward's contract with values_diff in the place
  * of weight_diff (bottom required iff values_diff != NULL, the same errors, determinism, no allocation after the first
@@ -524,6 +525,88 @@ ESCOIN_API int escoin_plan_set_values(escoin_plan *plan, const float *values, in
 ESCOIN_API int escoin_plan_set_values_f64(escoin_plan *plan, const double *values, int on_device, void *stream);
 ESCOIN_API int escoin_update_values_cpu(escoin_plan *plan, const float *dense_w);
 ESCOIN_API int escoin_update_values_cpu_f64(escoin_plan *plan, const double *dense_w);
+
+/* ---- Solver step: the solver's element-wise rule fused into the in-place update ----------------------------------------
+ *   SGDSolver::ApplyUpdate = Normalize, Regularize, ComputeUpdateValue (sgd_solver.cpp:118-204 and one element-wise kernel
+ *   per rule: sgd_solver.cu:7-12, nesterov_solver.cu:7-14, adam_solver.cu:7-15), then Net::Update -> Blob::Update.
+ * Every operand of that kernel is at hand for a lane that holds one CSR entry of the plan, so a training step of a pruned
+ * layer is escoin_forward -> escoin_backward_values -> escoin_solver_step: three calls, nothing of the caller's between
+ * them, and the same three nodes in a graph.
+ *   diff      the gradient: values_diff (nnz elements, escoin_plan_get_csr's order; diff_is_dense = 0) or a blobs_[0]-
+ *             shaped weight_diff (diff_is_dense = 1), read -- and with clear_diff set to +0 -- at the CSR positions only
+ *   history   SGD / Nesterov: h; Adam: m.  history2: Adam's v, otherwise NULL (ignored).  Caller-owned arrays of nnz
+ *             elements in get_csr's order, like every blob of this ABI: snapshots, all-reduces and re-alignments stay the
+ *             caller's business.
+ *   dense_w   NULL, or blobs_[0]: the new values are also written there, at the CSR positions only
+ * The plan's value array (every plan kind keeps one) is the current weight w.  The pointers must not overlap each other
+ * or the plan's memory.
+ * Arithmetic, per CSR entry e, every operation in the plan's Dtype, each rounded once, never contracted into a fused
+ * multiply-add; the hyper-parameters (and 1 + momentum, 1 - beta1, 1 - beta2) are converted / formed in Dtype once per call:
+ *   g = diff[e];                      if diff_scale != 1: g = diff_scale * g
+ *   L2: g = g + decay * w             L1: g = g + decay * sign(w)   (sign(+-0) = sign(NaN) = 0; skipped when decay == 0)
+ *   SGD:      h' = momentum*h + rate*g;                 u = h'
+ *   Nesterov: h' = momentum*h + rate*g;                 u = (1 + momentum)*h' - momentum*h
+ *   Adam:     m' = m*beta1 + g*(1 - beta1);  v' = v*beta2 + (g*g)*(1 - beta2);   u = (rate*m') / (sqrt(v') + delta)
+ *   w' = w - u
+ * The reference's Nesterov and Adam kernels keep `float` temporaries in their double instantiation; that quirk is NOT
+ * reproduced: the _f64 entry points compute in double throughout.
+ * Effect: escoin_plan_set_values' contract on the new values w' -- every consumer of the plan then behaves bit for bit
+ * like a fresh plan aligned by escoin_plan_set_csr on w' at the old pattern, in all four conv_modes and for the backward
+ * state's copies; the device is authoritative afterwards and the host mirrors follow as after a device-source update;
+ * "update_count" increments, "update_fast" reports the path.  An explicit zero of the pattern is updated like any entry.
+ * With nnz == 0 the call returns ESCOIN_OK without a launch.
+ * One launch of escoin_solver_step_kernel, one lane per CSR ENTRY: the lane reads w, diff, h (h2), computes the rule once,
+ * writes h (h2), dense_w, the cleared diff, and stores w' to each of the entry's destinations (the value array, the code
+ * word or stream quad, the dense matrix, the backward state's copies) through an entry-major view of the update state's
+ * destination list.  No atomics; no lane reads a word another lane of the launch writes.  The view is built with the
+ * first solver step on an alignment (and once more when the backward state appears): device memory, a synchronisation;
+ * later steps allocate and synchronise nothing and can be captured.  rate_dev lets a captured step follow an lr policy.
+ * Plans without an in-place path (see "Fallback" above) run the same kernel with the value array as the only destination
+ * and then rebuild from it: update_fast = 0, not capturable; the next step on the rebuilt plan is in place.
+ * escoin_solver_array_step: the same rule on a plain array (`data` is w and the only destination): the bias, any blob.
+ * The _cpu entry points are plain host loops with the same bits: escoin_solver_step_cpu for plans aligned by
+ * escoin_weight_align_cpu only (as escoin_update_values_cpu), all pointers host pointers, rate_dev included.
+ * Errors: ESCOIN_EINVAL for a NULL desc / diff / history (array step: data, or n < 0), an unknown type or regularization,
+ * Adam without history2; ESCOIN_ENODEVICE for the device entry points without a device; ESCOIN_ESTATE before an align, on
+ * the other Dtype's entry point, on another device, and for escoin_solver_step_cpu on a device-aligned plan. */
+#define ESCOIN_SOLVER_SGD 0        /* sgd_solver.cu:7-12      */
+#define ESCOIN_SOLVER_NESTEROV 1   /* nesterov_solver.cu:7-14 */
+#define ESCOIN_SOLVER_ADAM 2       /* adam_solver.cu:7-15     */
+#define ESCOIN_REG_NONE 0
+#define ESCOIN_REG_L2 1            /* sgd_solver.cpp:155-160  */
+#define ESCOIN_REG_L1 2            /* sgd_solver.cpp:161-168  */
+typedef struct escoin_solver_desc {
+  int type, regularization;
+  double rate;        /* the kernel's local_rate; for Adam the corrected_local_rate (adam_solver.cpp:39-41,80): the caller
+                         applies lr_mult and the bias correction, the library knows no iteration count */
+  double momentum;    /* SGD / Nesterov momentum; Adam beta1 */
+  double momentum2;   /* Adam beta2 */
+  double delta;       /* Adam eps_hat */
+  double decay;       /* local_decay = weight_decay * decay_mult; 0 = no regularisation term */
+  double diff_scale;  /* multiplies the gradient first: Normalize's 1/iter_size, ClipGradients' scale, 1/world_size;
+                         exactly 1.0 = no multiplication */
+  const void *rate_dev; /* NULL, or a device (host for _cpu) pointer to ONE Dtype that replaces `rate`, read by the kernel:
+                           a captured step then follows an lr policy / Adam's correction without re-capture */
+  int diff_is_dense;  /* 0: diff is values_diff (nnz, get_csr's order); 1: diff is a blobs_[0]-shaped weight_diff, read
+                         (and cleared) at the CSR positions only.  Ignored by the array step. */
+  int clear_diff;     /* 1: the elements of diff that were read are set to +0 (Net::ClearParamDiffs for the next +=) */
+} escoin_solver_desc;
+ESCOIN_API int escoin_solver_step(escoin_plan *plan, const escoin_solver_desc *desc, float *diff, float *history,
+                       float *history2, float *dense_w, void *stream);
+ESCOIN_API int escoin_solver_step_f64(escoin_plan *plan, const escoin_solver_desc *desc, double *diff, double *history,
+                           double *history2, double *dense_w, void *stream);
+ESCOIN_API int escoin_solver_step_cpu(escoin_plan *plan, const escoin_solver_desc *desc, float *diff, float *history,
+                           float *history2, float *dense_w);
+ESCOIN_API int escoin_solver_step_cpu_f64(escoin_plan *plan, const escoin_solver_desc *desc, double *diff, double *history,
+                               double *history2, double *dense_w);
+ESCOIN_API int escoin_solver_array_step(const escoin_solver_desc *desc, long n, float *data, float *diff, float *history,
+                             float *history2, void *stream);
+ESCOIN_API int escoin_solver_array_step_f64(const escoin_solver_desc *desc, long n, double *data, double *diff,
+                                 double *history, double *history2, void *stream);
+ESCOIN_API int escoin_solver_array_step_cpu(const escoin_solver_desc *desc, long n, float *data, float *diff,
+                                 float *history, float *history2);
+ESCOIN_API int escoin_solver_array_step_cpu_f64(const escoin_solver_desc *desc, long n, double *data, double *diff,
+                                     double *history, double *history2);
 
 #ifdef __cplusplus
 }
