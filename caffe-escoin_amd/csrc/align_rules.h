@@ -112,6 +112,8 @@ StreamLayout stream_layout(const Geometry &g, float density, int tiling_batch, i
 constexpr int kStgWaves = 8;                         // waves per workgroup
 constexpr size_t kStgLdsBudget = 64 * 1024;          // two workgroups per CU
 constexpr int kStgSmallInt = 1 << 21;                // div_small's range
+constexpr int kStgBatch = 8;                         // entries per batched reduction; the walk reads its tap offsets one
+                                                     // batch ahead, so their table is padded by two (csr_tables.h)
 
 // The staged weight-gradient kernel's block plan (sconv_backward.hip header of that kernel): the LDS tile and the split
 // of a conv group's input channels into staged blocks.  AUTO's rule and stg_build both read this one.

@@ -1,0 +1,110 @@
+// csr_tables.h -- every integer table the library derives from a plan's host CSR, and the one walk over that CSR they
+// are built with.  Pure C++ (no HIP, no escoin_plan), like align_rules.h: a builder takes the CSR and plain integers and
+// returns plain vectors, so that the indices that decide which device word a weight is written to and which LDS float a
+// tap reads are checked on a machine without a GPU (tests/test_csr_tables.py).  The .hip files call these and do the
+// device work: upload, synchronise.
+//
+// Lengths: DeviceBuffer::upload allocates what it is handed, and a kernel argument may not be a null pointer, so the
+// tables that an empty pattern would leave empty are padded to one (zero) element: generic_tables' taps,
+// dense_positions, gather_transpose's ttap.  staged_tables' off is padded by two batches of zeros, which the staged
+// kernel's walk reads ahead into.  The host-side lists (tsrc) have exactly nnz elements.
+#ifndef ESCOIN_CSR_TABLES_H_
+#define ESCOIN_CSR_TABLES_H_
+
+#include <cstddef>
+#include <vector>
+
+#include "geometry.h"
+
+namespace escoin {
+
+// The host CSR of a plan, per conv group (escoin_plan::rowptr / colidx): rows are the group's Mg output channels,
+// columns the taps of its Cg input channels, ascending within a row.
+struct CsrView {
+  const Geometry *g;
+  const std::vector<std::vector<int>> *rowptr, *colidx;   // [group][Mg + 1], [group][nnz of the group]
+  long nnz() const {
+    long n = 0;
+    for (const auto &c : *colidx) n += (long)c.size();
+    return n;
+  }
+  // flat index (groups concatenated) of group grp's first entry
+  long group_base(int grp) const {
+    long n = 0;
+    for (int k = 0; k < grp; ++k) n += (long)(*colidx)[k].size();
+    return n;
+  }
+};
+
+// Entry j of group grp's CSR: in row m (group-local output channel), at column col; e = its flat index.
+struct CsrEntry {
+  int grp, m, j;
+  long e;
+  int col;
+};
+
+// The walk: every entry once, in CSR order (group, row, column), which is the order of e.
+template <typename F>
+inline void for_each_entry(const CsrView &v, F &&fn) {
+  long e = 0;
+  for (int grp = 0; grp < v.g->d.group; ++grp) {
+    const std::vector<int> &rp = (*v.rowptr)[grp], &ci = (*v.colidx)[grp];
+    for (int m = 0; m < v.g->Mg; ++m)
+      for (int j = rp[m]; j < rp[m + 1]; ++j, ++e) fn(CsrEntry{grp, m, j, e, ci[j]});
+  }
+}
+
+// Per-group arrays of the CSR (its values) in flat order, at least min_size elements long.
+template <typename T>
+inline std::vector<T> flat_entries(const std::vector<std::vector<T>> &per_group, size_t min_size = 0) {
+  std::vector<T> out;
+  for (const auto &v : per_group) out.insert(out.end(), v.begin(), v.end());
+  if (out.size() < min_size) out.resize(min_size);
+  return out;
+}
+
+// The generic kernel's device CSR (also the entry weight-gradient kernel's): rowptr [M + 1] absolute, taps
+// [max(nnz, 1)] = pack_tap(ic, kr, kc).
+struct GenericTables { std::vector<int> rowptr, taps; };
+GenericTables generic_tables(const CsrView &v);
+
+// [max(nnz, 1)]: (grp * Mg + m) * row_stride + col -- the entry's position in a dense M x row_stride matrix.
+// row_stride = kdim: its position in blobs_[0] (wpos); row_stride = dense_lda(kdim): in the MFMA kernel's matrix.
+std::vector<int> dense_positions(const CsrView &v, int row_stride);
+
+// The gather kernel's transposed CSR: per global input channel c the entries of rows trow[c] .. trow[c + 1], in
+// ascending (ocl, kr, kc) -- the order the original rows visit them in when they are walked oc by oc.
+// trow [C + 1], ttap [max(nnz, 1)] = pack_tap(ocl, kr, kc), tsrc [nnz] = the flat index of the entry at that place
+// (its value: values_flat[tsrc[k]]).  The CPU mode's data gradient walks the same trow / tsrc.
+struct GatherTables { std::vector<int> trow, ttap, tsrc; };
+GatherTables gather_transpose(const CsrView &v);
+
+// The CSR of the transposed forward plan (the data gradient as a stride-1 forward of top_diff), in set_csr's form:
+// per group, row = input channel icl, entry (ocl, icl, kr, kc) at column ocl*KH*KW + (KH-1-kr)*KW + (KW-1-kc), ascending
+// within the row.  rowptr [group * (Cg + 1)] group-relative, colidx [nnz], nnz_g [group], tsrc [nnz] as above.
+struct ForwardTranspose { std::vector<int> rowptr, colidx, tsrc, nnz_g; };
+ForwardTranspose forward_transpose(const CsrView &v);
+
+// The staged weight-gradient kernel's tables for blocks of icb input channels, nblk per conv group, cs floats per staged
+// channel, rows of Wp floats: blk [M * (nblk + 1)], blk[oc * (nblk + 1) + b] = the flat index where output channel oc's
+// entries of block b begin (b = nblk: where the row ends); off [nnz + 2 * kStgBatch], the entry's tap as a float offset
+// inside the staged block's LDS tile, (icl % icb) * cs + kr * dil_h * Wp + kc * dil_w, then zeros.
+struct StagedTables { std::vector<int> blk, off; };
+StagedTables staged_tables(const CsrView &v, int icb, int nblk, int cs, int Wp);
+
+// A scatter list (destination k: CSR entry src[k], element off[k] of buffer buf[k]) entry-major: entry e's destinations
+// are e_off[k] / e_buf[k] for k in [e_ptr[e], e_ptr[e + 1]), in the order of the list.  e_ptr [max(nnz, 1) + 1], e_off
+// and e_buf [max(n, 1)] for a list of n.  false (and nothing built): a destination names no CSR entry.
+struct EntryMajor {
+  std::vector<int> e_ptr;
+  std::vector<unsigned> e_off;
+  std::vector<unsigned char> e_buf;
+};
+bool entry_major(const std::vector<int> &src, const std::vector<unsigned> &off, const std::vector<unsigned char> &buf,
+                 long nnz, EntryMajor *out);
+
+// Column col of the CSR as the reference stretches it for its padded input image (base_conv_layer.cpp:99-105).
+int stretched_col(int col, const escoin_conv_desc &d);
+
+}  // namespace escoin
+#endif  // ESCOIN_CSR_TABLES_H_

@@ -594,9 +594,9 @@ int dense_build_ktab(escoin_plan *p, hipStream_t stream) {
   std::vector<int> tab((size_t)Kpad * 2);
   for (int k = 0; k < Kpad; ++k) {
     if (k < K) {
-      const int kc = k % g.d.KW, kr = (k / g.d.KW) % g.d.KH, ic = k / (g.d.KW * g.d.KH);
-      const int dy = kr * g.d.dil_h, dx = kc * g.d.dil_w;
-      tab[2 * k] = (ic * g.d.H + dy) * g.d.W + dx;
+      const Tap tap = decode_tap(k, g.d.KH, g.d.KW);
+      const int dy = tap.kr * g.d.dil_h, dx = tap.kc * g.d.dil_w;
+      tab[2 * k] = (tap.ic * g.d.H + dy) * g.d.W + dx;
       tab[2 * k + 1] = (dy & 0xFFFF) | (dx << 16);
     } else {
       tab[2 * k] = 0;

@@ -116,25 +116,11 @@ static void free_device(escoin_plan *p) {
 
 // The generic kernel's device CSR (p->gen) from the host CSR: rowptr, packed taps and values of the plan's Dtype.
 template <typename T>
-static int upload_generic(escoin_plan *p, long nnz, hipStream_t stream) {
-  const Geometry &g = p->g;
-  const std::vector<std::vector<T>> &values = plan_vals<T>(p);
-  std::vector<int> rowptr(g.d.M + 1), taps((size_t)(nnz > 0 ? nnz : 1));
-  std::vector<T> vals((size_t)(nnz > 0 ? nnz : 1));
-  long base = 0;
-  for (int grp = 0; grp < g.d.group; ++grp) {
-    for (int m = 0; m < g.Mg; ++m) rowptr[grp * g.Mg + m] = (int)(base + p->rowptr[grp][m]);
-    const long n_g = (long)p->colidx[grp].size();
-    for (long j = 0; j < n_g; ++j) {
-      const int col = p->colidx[grp][j];
-      taps[base + j] = pack_tap(col / (g.d.KW * g.d.KH), (col / g.d.KW) % g.d.KH, col % g.d.KW);
-      vals[base + j] = values[grp][j];
-    }
-    base += n_g;
-  }
-  rowptr[g.d.M] = (int)base;
-  ESCOIN_HIP_TRY(p->gen.rowptr.upload(rowptr, stream));
-  ESCOIN_HIP_TRY(p->gen.taps.upload(taps, stream));
+static int upload_generic(escoin_plan *p, hipStream_t stream) {
+  const GenericTables t = generic_tables(csr_view(p));
+  const std::vector<T> vals = flat_entries(plan_vals<T>(p), 1);
+  ESCOIN_HIP_TRY(p->gen.rowptr.upload(t.rowptr, stream));
+  ESCOIN_HIP_TRY(p->gen.taps.upload(t.taps, stream));
   ESCOIN_HIP_TRY(p->gen.vals.upload(vals, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));  // host vectors die at scope exit
   return ESCOIN_OK;
@@ -151,8 +137,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
   ESCOIN_HIP_TRY(hipGetDevice(&p->device));
   free_device(p);
   const Geometry &g = p->g;
-  const long nnz = plan_nnz(p);
-  const int rc_gen = p->is_f64 ? upload_generic<double>(p, nnz, stream) : upload_generic<float>(p, nnz, stream);
+  const int rc_gen = p->is_f64 ? upload_generic<double>(p, stream) : upload_generic<float>(p, stream);
   if (rc_gen != ESCOIN_OK) return rc_gen;
   if (p->is_f64) {
     // Dtype = double: the order-preserving generic kernel is the only device kernel a double plan runs, in every
@@ -179,10 +164,9 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
   if (p->n_dense_groups > 0) {
     const size_t lda = (size_t)dense_lda(g.kdim);
     std::vector<float> dw(((size_t)g.d.M + dense_spare_rows()) * lda, 0.f);
-    for (int grp = 0; grp < G; ++grp)
-      for (int m = 0; m < g.Mg; ++m)
-        for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j)
-          dw[((size_t)grp * g.Mg + m) * lda + p->colidx[grp][j]] = p->values[grp][j];
+    const std::vector<int> at = dense_positions(csr_view(p), (int)lda);
+    const std::vector<float> vals = flat_entries(p->values);
+    for (size_t e = 0; e < vals.size(); ++e) dw[(size_t)at[e]] = vals[e];
     ESCOIN_HIP_TRY(p->dense.w.upload(dw, stream));
     ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
     const int rc = dense_build_ktab(p, stream);
@@ -335,10 +319,7 @@ static int get_csr_t(const escoin_plan *p, int *rowptr, int *colidx, T *values, 
     const long n_g = (long)p->colidx[grp].size();
     for (long j = 0; j < n_g; ++j) {
       int col = p->colidx[grp][j];
-      if (stretched) {  // base_conv_layer.cpp:99-105
-        const int kc = col % g.d.KW, kr = (col / g.d.KW) % g.d.KH, ic = col / (g.d.KW * g.d.KH);
-        col = (ic * (g.d.H + g.d.pad_h) + kr) * (g.d.W + g.d.pad_w) + kc;
-      }
+      if (stretched) col = stretched_col(col, g.d);
       if (colidx) colidx[base + j] = col;
       if (values) values[base + j] = vals[grp][j];
     }
@@ -621,8 +602,7 @@ int escoin_plan_export_aligned(const escoin_plan *p, void *buf, size_t capacity,
     std::vector<char> jit;
     const int rc = tiled_export(p, &jit);
     if (rc != ESCOIN_OK) return rc;
-    uint64_t nnz = 0;
-    for (const auto &c : p->colidx) nnz += c.size();
+    const uint64_t nnz = (uint64_t)plan_nnz(p);
     const size_t need = sizeof(AlignedHdr) + sizeof(escoin_conv_desc) + 4 * (size_t)g.d.group +
                         4 * (size_t)g.d.group * (g.Mg + 1) + 8 * (size_t)nnz + jit.size();
     *bytes = need;
@@ -774,9 +754,7 @@ long escoin_plan_nnz(const escoin_plan *p, int group) {
   if (!p) return fail(ESCOIN_EINVAL, "null plan");
   if (group >= p->g.d.group) return fail(ESCOIN_EINVAL, "group out of range");
   if (group >= 0) return (long)p->colidx[group].size();
-  long n = 0;
-  for (const auto &c : p->colidx) n += (long)c.size();
-  return n;
+  return plan_nnz(p);
 }
 
 int escoin_plan_get_csr(const escoin_plan *p, int *rowptr, int *colidx, float *values, int stretched) {

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "csr_tables.h"
 #include "device_buffer.h"
 #include "escoin.h"
 #include "geometry.h"
@@ -112,6 +113,7 @@ struct UpdState {
   long n_dst = 0, nnz = 0;
   bool has_bwd = false;         // the list covers the backward state's copies (rebuilt once when that state appears later)
   std::vector<char> h_stage;    // host side of `stage`
+  std::vector<int> h_wpos;      // host side of `wpos`: where a host-source update finds entry e in a dense blobs_[0]
   // The same list entry-major, for the solver step (solver_step.hip), which computes a value once per CSR entry: entry e
   // is stored at element e_off[k] of buffer e_buf[k] for k in [e_ptr[e], e_ptr[e + 1]).  Built with the first solver
   // step on an alignment (entry_view), kept by the rebuild that follows the backward state's appearance.
@@ -132,8 +134,8 @@ struct SolverTargets {
   bool in_place;     // false: the value array is the only destination and solver_end rebuilds the plan from it
 };
 
-// The generic kernel's device CSR (escoin_capi.hip upload): rowptr [M + 1] absolute offsets into taps / vals; taps and
-// vals [max(nnz, 1)], the packed (ic,kr,kc) and the values of the plan's Dtype
+// The generic kernel's device CSR (escoin_capi.hip upload; csr_tables.h generic_tables): rowptr [M + 1] absolute offsets
+// into taps / vals; taps and vals [max(nnz, 1)], the packed (ic,kr,kc) and the values of the plan's Dtype
 struct GenericArrays { DeviceBuffer rowptr, taps, vals; };
 
 // What tiled_build / tiled_import put on the device for the tiled kernels
@@ -280,12 +282,9 @@ long upd_stat(const escoin_plan *p, const char *key);
 // rebuilt from its value array.  T = float | double.
 template <typename T> int solver_begin(escoin_plan *p, const char *name, hipStream_t stream, SolverTargets *t);
 template <typename T> int solver_end(escoin_plan *p, const SolverTargets &t, hipStream_t stream);
-// total nonzeros of the plan's host CSR
-inline long plan_nnz(const escoin_plan *p) {
-  long nnz = 0;
-  for (const auto &c : p->colidx) nnz += (long)c.size();
-  return nnz;
-}
+// the plan's host CSR as the table builders read it (csr_tables.h), and its total nonzeros
+inline CsrView csr_view(const escoin_plan *p) { return CsrView{&p->g, &p->rowptr, &p->colidx}; }
+inline long plan_nnz(const escoin_plan *p) { return csr_view(p).nnz(); }
 // whether group `grp` of the plan runs on the dense kernel (its units in the stream / generated code are empty)
 inline bool group_is_dense(const escoin_plan *p, int grp) {
   return p->n_dense_groups > 0 && (grp >= 64 || ((p->dense_mask >> grp) & 1ull));

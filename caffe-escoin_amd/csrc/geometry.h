@@ -10,9 +10,12 @@
 
 namespace escoin {
 
-// A nonzero's kernel tap packed for the generic kernel: ic << 16 | kr << 8 | kc
-// (ic group-local).
-inline int pack_tap(int ic, int kr, int kc) { return (ic << 16) | (kr << 8) | kc; }
+// A kernel tap: column col = (ic * KH + kr) * KW + kc of a conv group's weight matrix (ic group-local).
+struct Tap { int ic, kr, kc; };
+inline Tap decode_tap(int col, int KH, int KW) { return Tap{col / (KW * KH), (col / KW) % KH, col % KW}; }
+// A tap packed for the device tables (the generic kernel's taps; the gather kernel's ttap, with the group-local output
+// channel in ic's place): ic << 16 | kr << 8 | kc
+inline int pack_tap(const Tap &t) { return (int)(((unsigned)t.ic << 16) | ((unsigned)t.kr << 8) | (unsigned)t.kc); }
 
 struct Geometry {
   escoin_conv_desc d;

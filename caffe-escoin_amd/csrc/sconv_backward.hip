@@ -26,7 +26,7 @@
 //                                        total added into weight_diff / bias_diff.  Every position has one owner.
 //
 // The backward state (transposed CSR or transposed plan, slab, ReLU scratch) is built by the first backward on an
-// aligned plan and dropped with the device side (free_device: weight_align / set_csr / import_aligned; destroy); later
+// aligned plan -- its index tables by the host-only builders of csr_tables.h, this file uploads them -- and dropped with the device side (free_device: weight_align / set_csr / import_aligned; destroy); later
 // calls allocate nothing and synchronise nothing, so they can be captured into a graph.
 #include <hip/hip_runtime.h>
 
@@ -275,9 +275,9 @@ escoin_sconv_wgrad_sum_f64_kernel(const double *slab_w, const double *slab_b, co
 // An entry belongs to one (output channel, input-channel block): every slab element has one writer.  Dead pixels of the
 // last chunk are masked by select (their G is 0, but 0 x a staged non-finite value is not): a non-finite bottom element
 // reaches only the entries whose tap reads it.
-// (kStgWaves waves per workgroup, kStgLdsBudget, kStgSmallInt: align_rules.h, with the rule that plans the blocks)
+// (kStgWaves waves per workgroup, kStgBatch entries per batched reduction, kStgLdsBudget, kStgSmallInt: align_rules.h,
+// with the rule that plans the blocks)
 constexpr int kStgPix = kChunkPixels / 64;           // pixels per lane: a wave covers the whole chunk
-constexpr int kStgBatch = 8;                         // entries per batched reduction
 
 struct StagedArgs {
   const float *__restrict__ bottom;
@@ -482,14 +482,6 @@ bool bwd_transposable(const escoin_plan *p) {
          d.pad_w <= d.dil_w * (d.KW - 1) && p->g.Mg <= 32767;
 }
 
-template <typename T>
-static int dev_upload(DeviceBuffer &dst, const std::vector<T> &src, hipStream_t stream) {
-  ESCOIN_HIP_TRY(dst.alloc(sizeof(T) * std::max<size_t>(src.size(), 1)));
-  if (!src.empty())
-    ESCOIN_HIP_TRY(hipMemcpyAsync(dst.get<T>(), src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, stream));
-  return ESCOIN_OK;
-}
-
 // The transposed forward plan of path (a): geometry of the data gradient as a stride-1 forward of G.
 static int build_transposed_plan(escoin_plan *p, BwdState *s, hipStream_t stream) {
   const Geometry &g = p->g;
@@ -505,120 +497,48 @@ static int build_transposed_plan(escoin_plan *p, BwdState *s, hipStream_t stream
   int rc = escoin_plan_create(&t, &tp);
   s->tplan.reset(tp);
   if (rc != ESCOIN_OK) return rc;
-  const int kk = d.KH * d.KW;
   if (p->bwd_kernel != ESCOIN_KERNEL_AUTO && (rc = escoin_plan_set_option(tp, "kernel", p->bwd_kernel)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(tp, "tiling_batch", p->tiling_batch)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(tp, "max_launch_bytes", (int)std::min<long>(p->max_launch_bytes, 0x7fffffff))) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(tp, "dense_threshold_pct", p->dense_threshold_pct)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(tp, "dense_gate", p->dense_gate)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(tp, "code_loader", p->code_loader)) != ESCOIN_OK) return rc;
-  // CSR': row = input channel icl of a group, entry (ocl, icl, kr, kc) -> colidx' = ocl*KH*KW + (KH-1-kr)*KW + (KW-1-kc),
-  // ascending within the row
-  std::vector<int> rowptr((size_t)d.group * (g.Cg + 1)), colidx, nnz_g(d.group);
-  std::vector<float> vals;
-  // (column', index of the entry in its group's CSR): the columns of a row are distinct, so the order is a function of
-  // the pattern alone; s->tsrc records it for escoin_update_values
-  std::vector<std::vector<std::pair<int, int>>> rows(g.Cg);
-  s->tsrc.clear();
-  int group_base = 0;
-  for (int grp = 0; grp < d.group; ++grp) {
-    for (auto &r : rows) r.clear();
-    const std::vector<int> &rp = p->rowptr[grp], &ci = p->colidx[grp];
-    for (int m = 0; m < g.Mg; ++m)
-      for (int j = rp[m]; j < rp[m + 1]; ++j) {
-        const int col = ci[j], icl = col / kk, kr = (col / d.KW) % d.KH, kc = col % d.KW;
-        rows[icl].emplace_back(m * kk + (d.KH - 1 - kr) * d.KW + (d.KW - 1 - kc), j);
-      }
-    int *trp = rowptr.data() + (size_t)grp * (g.Cg + 1);
-    trp[0] = 0;
-    for (int c = 0; c < g.Cg; ++c) {
-      std::sort(rows[c].begin(), rows[c].end(),
-                [](const std::pair<int, int> &x, const std::pair<int, int> &y) { return x.first < y.first; });
-      for (const auto &e : rows[c]) {
-        colidx.push_back(e.first);
-        vals.push_back(p->values[grp][e.second]);
-        s->tsrc.push_back(group_base + e.second);
-      }
-      trp[c + 1] = trp[c] + (int)rows[c].size();
-    }
-    nnz_g[grp] = trp[g.Cg];
-    group_base += (int)ci.size();
-  }
-  rc = escoin_plan_set_csr(tp, rowptr.data(), colidx.data(), vals.data(), nnz_g.data(), stream);
+  // (s->tsrc records the transposed order for escoin_update_values)
+  ForwardTranspose ft = forward_transpose(csr_view(p));
+  const std::vector<float> flat = flat_entries(p->values);
+  std::vector<float> vals(ft.tsrc.size());
+  for (size_t k = 0; k < vals.size(); ++k) vals[k] = flat[(size_t)ft.tsrc[k]];
+  s->tsrc = std::move(ft.tsrc);
+  rc = escoin_plan_set_csr(tp, ft.rowptr.data(), ft.colidx.data(), vals.data(), ft.nnz_g.data(), stream);
   if (rc != ESCOIN_OK) return rc;
   s->data_kernel = (int)escoin_plan_stat(tp, "kernel_choice");
   return ESCOIN_OK;
 }
 
-// The gather kernel's transposed CSR: per input channel c, its entries in ascending (ocl, kr, kc) -- the order the
-// original rows visit them in when they are walked oc by oc.
+// The gather kernel's transposed CSR (csr_tables.h gather_transpose), with the values in its order.
 template <typename T>
-static int build_gather(escoin_plan *p, BwdState *s, const std::vector<std::vector<T>> &values, hipStream_t stream) {
-  const Geometry &g = p->g;
-  const escoin_conv_desc &d = g.d;
-  const int kk = d.KH * d.KW;
-  std::vector<int> cnt(d.C + 1, 0);
-  for (int grp = 0; grp < d.group; ++grp)
-    for (int col : p->colidx[grp]) ++cnt[grp * g.Cg + col / kk + 1];
-  for (int c = 0; c < d.C; ++c) cnt[c + 1] += cnt[c];
-  std::vector<int> trow(cnt), fill(cnt.begin(), cnt.end() - 1), ttap((size_t)s->nnz);
-  std::vector<T> tval((size_t)s->nnz);
-  s->tsrc.assign((size_t)s->nnz, 0);
-  int group_base = 0;
-  for (int grp = 0; grp < d.group; ++grp) {
-    const std::vector<int> &rp = p->rowptr[grp], &ci = p->colidx[grp];
-    for (int m = 0; m < g.Mg; ++m)
-      for (int j = rp[m]; j < rp[m + 1]; ++j) {
-        const int col = ci[j], c = grp * g.Cg + col / kk;
-        const int at = fill[c]++;
-        ttap[at] = (m << 16) | (((col / d.KW) % d.KH) << 8) | (col % d.KW);
-        tval[at] = values[grp][j];
-        s->tsrc[at] = group_base + j;
-      }
-    group_base += (int)ci.size();
-  }
-  int rc = dev_upload(s->trow, trow, stream);
-  if (rc == ESCOIN_OK) rc = dev_upload(s->ttap, ttap, stream);
-  if (rc == ESCOIN_OK) rc = dev_upload(s->tval, tval, stream);
-  if (rc != ESCOIN_OK) return rc;
+static int build_gather(escoin_plan *p, BwdState *s, hipStream_t stream) {
+  GatherTables t = gather_transpose(csr_view(p));
+  const std::vector<T> flat = flat_entries(plan_vals<T>(p));
+  std::vector<T> tval(t.ttap.size(), T(0));
+  for (size_t k = 0; k < t.tsrc.size(); ++k) tval[k] = flat[(size_t)t.tsrc[k]];
+  ESCOIN_HIP_TRY(s->trow.upload(t.trow, stream));
+  ESCOIN_HIP_TRY(s->ttap.upload(t.ttap, stream));
+  ESCOIN_HIP_TRY(s->tval.upload(tval, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
+  s->tsrc = std::move(t.tsrc);
   return ESCOIN_OK;
 }
 
 static int stg_build(escoin_plan *p, BwdState *s, const StgPlan &sp, hipStream_t stream) {
-  const Geometry &g = p->g;
-  const escoin_conv_desc &d = g.d;
-  const int Wp = d.W + 2 * d.pad_w;
-  const int cs = sp.cs, icb = sp.icb, nblk = sp.nblk;
-  s->stg_icb = icb;
-  s->stg_nblk = nblk;
+  s->stg_icb = sp.icb;
+  s->stg_nblk = sp.nblk;
   s->stg_rows = sp.rows_max;
-  s->stg_lds_bytes = sizeof(float) * (size_t)icb * (size_t)cs;
+  s->stg_lds_bytes = sizeof(float) * (size_t)sp.icb * (size_t)sp.cs;
   s->stg_osplit = sp.osplit;
-  const int kk = d.KH * d.KW;
-  std::vector<int> blk((size_t)d.M * (nblk + 1)), off((size_t)s->nnz + 2 * kStgBatch, 0);   // (padding: the walk reads ahead)
-  long base = 0;
-  for (int grp = 0; grp < d.group; ++grp) {
-    const std::vector<int> &rp = p->rowptr[grp], &ci = p->colidx[grp];
-    for (int m = 0; m < g.Mg; ++m) {
-      int *row = blk.data() + (size_t)(grp * g.Mg + m) * (nblk + 1);
-      int j = rp[m];
-      for (int b = 0; b <= nblk; ++b) {
-        // the columns of a row ascend (set_csr checks it), so its input channels do
-        while (b < nblk && j < rp[m + 1] && ci[j] / kk < b * icb) ++j;
-        if (b == nblk) j = rp[m + 1];
-        row[b] = (int)(base + j);
-      }
-      for (int e = rp[m]; e < rp[m + 1]; ++e) {
-        const int col = ci[e], icl = col / kk, kr = (col / d.KW) % d.KH, kc = col % d.KW;
-        off[(size_t)base + e] = (icl % icb) * cs + kr * d.dil_h * Wp + kc * d.dil_w;
-      }
-    }
-    base += (long)ci.size();
-  }
-  int rc = dev_upload(s->stg_blk, blk, stream);
-  if (rc == ESCOIN_OK) rc = dev_upload(s->stg_off, off, stream);
-  if (rc != ESCOIN_OK) return rc;
+  const StagedTables t = staged_tables(csr_view(p), sp.icb, sp.nblk, sp.cs, p->g.d.W + 2 * p->g.d.pad_w);
+  ESCOIN_HIP_TRY(s->stg_blk.upload(t.blk, stream));
+  ESCOIN_HIP_TRY(s->stg_off.upload(t.off, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
   return ESCOIN_OK;
 }
@@ -645,7 +565,7 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
                                "chunk tile of one input channel fits the LDS budget; only the entry kernel serves this plan");
   p->bwd.reset(new BwdState());
   BwdState *s = p->bwd.get();
-  for (const auto &c : p->colidx) s->nnz += (long)c.size();
+  s->nnz = plan_nnz(p);
   if (s->nnz > 0x7fffffffL) return fail(ESCOIN_EINVAL, "backward: more than 2^31 nonzeros");
   int rc = ESCOIN_OK;
   if (transposable && p->bwd_kernel != ESCOIN_KERNEL_GENERIC) {
@@ -656,17 +576,11 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
     }
   } else {
     s->data_kernel = ESCOIN_KERNEL_GENERIC;
-    rc = build_gather<T>(p, s, plan_vals<T>(p), stream);
+    rc = build_gather<T>(p, s, stream);
   }
   if (rc != ESCOIN_OK) return rc;
-  std::vector<int> wpos((size_t)s->nnz);
-  long e = 0;
-  for (int grp = 0; grp < d.group; ++grp)
-    for (int m = 0; m < g.Mg; ++m)
-      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j)
-        wpos[e++] = (grp * g.Mg + m) * g.kdim + p->colidx[grp][j];
-  rc = dev_upload(s->wpos, wpos, stream);
-  if (rc != ESCOIN_OK) return rc;
+  const std::vector<int> wpos = dense_positions(csr_view(p), g.kdim);   // (lives until the synchronise below)
+  ESCOIN_HIP_TRY(s->wpos.upload(wpos, stream));
   s->chunks_max = (int)(((long)d.N * g.OH * g.OW + kChunkPixels - 1) / kChunkPixels);
   const size_t slab = sizeof(T) * (size_t)s->chunks_max * (size_t)(s->nnz + d.M);
   ESCOIN_HIP_TRY(s->slab.alloc(slab));

@@ -206,9 +206,8 @@ static void build_offsets(escoin_plan *p) {
     for (size_t j = 0; j < ci.size(); ++j) {
       // the stretch of base_conv_layer.cpp:96-107 with the dilation folded in (the reference decodes it again per
       // multiply-add in its dilated branch, math_functions.cpp:142-160)
-      const int col = ci[j];
-      const int kc = col % g.d.KW, kr = (col / g.d.KW) % g.d.KH, ic = col / (g.d.KW * g.d.KH);
-      off[j] = (ic * PH + kr * g.d.dil_h) * PW + kc * g.d.dil_w;
+      const Tap tap = decode_tap(ci[j], g.d.KH, g.d.KW);
+      off[j] = (tap.ic * PH + tap.kr * g.d.dil_h) * PW + tap.kc * g.d.dil_w;
     }
   }
   p->cpu_off_valid = true;
@@ -222,8 +221,7 @@ static void build_channel_blocks(escoin_plan *p) {
   const Geometry &g = p->g;
   const escoin_conv_desc &d = g.d;
   const int PW = d.W + d.pad_w;
-  long nnz = 0;
-  for (int grp = 0; grp < d.group; ++grp) nnz += (long)p->colidx[grp].size();
+  const long nnz = plan_nnz(p);
   const double avg_row = (double)nnz / std::max(1, d.group * g.Mg);
   int cb = 0;
   if (d.stride_h == 1 && d.stride_w == 1)
@@ -454,11 +452,9 @@ static int update_values_cpu(escoin_plan *p, const T *dense_w) {
                                          : "update_values_cpu_f64: the plan holds float weights");
   const Geometry &g = p->g;
   std::vector<std::vector<T>> &vals = plan_vals<T>(p);
-  for (int grp = 0; grp < g.d.group; ++grp)
-    for (int m = 0; m < g.Mg; ++m) {
-      const T *row = dense_w + ((size_t)grp * g.Mg + m) * g.kdim;
-      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j) vals[grp][j] = row[p->colidx[grp][j]];
-    }
+  for_each_entry(csr_view(p), [&](const CsrEntry &c) {
+    vals[c.grp][c.j] = dense_w[((size_t)c.grp * g.Mg + c.m) * g.kdim + (size_t)c.col];
+  });
   ++p->upd_count;
   return ESCOIN_OK;
 }

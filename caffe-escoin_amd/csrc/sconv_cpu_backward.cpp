@@ -2,8 +2,9 @@
 // host (escoin_backward_cpu[_f64]; the device twin and the contract are in sconv_backward.hip / include/escoin.h).
 // Plain loops, no SIMD work: the CPU mode is the baseline the device is checked against.
 //   data gradient    threaded over (image, input channel).  A channel's outputs start at 0 and take one fma per
-//                    contributing entry of the channel's transposed-CSR row, in ascending (ocl, kr, kc) order -- the
-//                    device gather kernel's order, so the two are bit-identical;
+//                    contributing entry of the channel's transposed-CSR row, in ascending (ocl, kr, kc) order: the rows
+//                    are csr_tables.h's gather_transpose, the table the device gather kernel walks, so the two share
+//                    their order by construction and are bit-identical;
 //   weight / bias    threaded over CSR rows; every entry (and bias) is one sum over (n, oh, ow) in that order, then
 //                    added into the gradient.
 // Every output is summed in a fixed order: the bits do not depend on n_threads.  Works on any plan with a host CSR
@@ -18,10 +19,6 @@
 
 namespace escoin {
 namespace cpu {
-
-template <typename T> static const std::vector<std::vector<T>> &plan_values_bwd(const escoin_plan *p);
-template <> const std::vector<std::vector<float>> &plan_values_bwd<float>(const escoin_plan *p) { return p->values; }
-template <> const std::vector<std::vector<double>> &plan_values_bwd<double>(const escoin_plan *p) { return p->values64; }
 
 template <typename T>
 static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *top_diff, T *bottom_diff, T *weight_diff,
@@ -44,25 +41,21 @@ static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *
     n_threads = hc ? (int)hc : 1;
   }
   const bool relu = d.fuse_relu != 0;
-  const int kk = d.KH * d.KW;
   const size_t plane = (size_t)d.H * d.W, opix = (size_t)g.OH * g.OW;
-  const auto &values = plan_values_bwd<T>(p);
-  // compact (escoin_backward_values_cpu): weight_diff is the nnz-element array in get_csr order, groups concatenated
-  std::vector<size_t> group_base(d.group, 0);
-  for (int grp = 1; grp < d.group; ++grp) group_base[grp] = group_base[grp - 1] + p->colidx[grp - 1].size();
+  const CsrView csr = csr_view(p);
+  const auto &values = plan_vals<T>(p);
   // G at (n, oc, pixel)
   auto grad_at = [&](size_t gi) -> T { return relu && !(top[gi] > T(0)) ? T(0) : top_diff[gi]; };
 
   if (bottom_diff) {
-    // transposed CSR: per input channel, its entries in ascending (ocl, kr, kc)
+    // transposed CSR: input channel c's entries are tsrc[trow[c] .. trow[c + 1]), in ascending (ocl, kr, kc)
     struct Ent { int ocl, kr, kc; T v; };
-    std::vector<std::vector<Ent>> trows(d.C);
-    for (int grp = 0; grp < d.group; ++grp)
-      for (int m = 0; m < g.Mg; ++m)
-        for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j) {
-          const int col = p->colidx[grp][j];
-          trows[grp * g.Cg + col / kk].push_back(Ent{m, (col / d.KW) % d.KH, col % d.KW, values[grp][j]});
-        }
+    std::vector<Ent> ents((size_t)csr.nnz());
+    for_each_entry(csr, [&](const CsrEntry &c) {
+      const Tap tap = decode_tap(c.col, d.KH, d.KW);
+      ents[(size_t)c.e] = Ent{c.m, tap.kr, tap.kc, values[c.grp][c.j]};
+    });
+    const GatherTables gt = gather_transpose(csr);
     parallel_for((size_t)n_images * d.C, (size_t)n_threads, [&](size_t item) {
       const int n = (int)(item / d.C), c = (int)(item % d.C), grp = c / g.Cg;
       T *out = bottom_diff + ((size_t)n * d.C + c) * plane;
@@ -70,7 +63,8 @@ static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *
       const size_t gbase = ((size_t)n * d.M + (size_t)grp * g.Mg) * opix;
       // entry outer, pixel inner: every bottom pixel still takes its fmas in entry order (a tap maps distinct output
       // pixels to distinct bottom pixels)
-      for (const Ent &e : trows[c])
+      for (int k = gt.trow[c]; k < gt.trow[c + 1]; ++k) {
+        const Ent &e = ents[(size_t)gt.tsrc[k]];
         for (int oh = 0; oh < g.OH; ++oh) {
           const int h = oh * d.stride_h - d.pad_h + e.kr * d.dil_h;
           if (h < 0 || h >= d.H) continue;
@@ -81,6 +75,7 @@ static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *
             out[(size_t)h * d.W + w] = std::fma(e.v, gv, out[(size_t)h * d.W + w]);
           }
         }
+      }
     });
   }
 
@@ -96,24 +91,26 @@ static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *
         bias_diff[oc] = bias_diff[oc] + s;
       }
       if (!weight_diff) return;
+      // compact (escoin_backward_values_cpu): weight_diff is the nnz-element array in get_csr order, groups concatenated
+      const size_t base = compact ? (size_t)csr.group_base(grp) : (size_t)oc * g.kdim;
       for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j) {
         const int col = p->colidx[grp][j];
-        const int ic = col / kk, kr = (col / d.KW) % d.KH, kc = col % d.KW;
+        const Tap tap = decode_tap(col, d.KH, d.KW);
         T s = 0;
         for (int n = 0; n < n_images; ++n) {
           const size_t gbase = ((size_t)n * d.M + oc) * opix;
-          const T *img = bottom + ((size_t)n * d.C + (size_t)grp * g.Cg + ic) * plane;
+          const T *img = bottom + ((size_t)n * d.C + (size_t)grp * g.Cg + tap.ic) * plane;
           for (int oh = 0; oh < g.OH; ++oh) {
-            const int h = oh * d.stride_h - d.pad_h + kr * d.dil_h;
+            const int h = oh * d.stride_h - d.pad_h + tap.kr * d.dil_h;
             if (h < 0 || h >= d.H) continue;
             for (int ow = 0; ow < g.OW; ++ow) {
-              const int w = ow * d.stride_w - d.pad_w + kc * d.dil_w;
+              const int w = ow * d.stride_w - d.pad_w + tap.kc * d.dil_w;
               if (w < 0 || w >= d.W) continue;
               s = std::fma(grad_at(gbase + (size_t)oh * g.OW + ow), img[(size_t)h * d.W + w], s);
             }
           }
         }
-        const size_t pos = compact ? group_base[grp] + (size_t)j : (size_t)oc * g.kdim + col;
+        const size_t pos = base + (size_t)(compact ? j : col);
         weight_diff[pos] = weight_diff[pos] + s;
       }
     });

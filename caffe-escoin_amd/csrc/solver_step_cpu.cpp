@@ -27,14 +27,11 @@ struct PlanLoop {
     const Geometry &g = p->g;
     const T rate = s.rate_ptr ? *s.rate_ptr : s.rate;
     std::vector<std::vector<T>> &vals = plan_vals<T>(p);
-    long e = 0;
-    for (int grp = 0; grp < g.d.group; ++grp)
-      for (int m = 0; m < g.Mg; ++m)
-        for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j, ++e) {
-          const size_t at = ((size_t)grp * g.Mg + m) * g.kdim + (size_t)p->colidx[grp][j];
-          step_one<T, Rule, Reg>(s, rate, &vals[grp][j], diff + (s.diff_is_dense ? at : (size_t)e), h + e, h2 ? h2 + e : nullptr);
-          if (dense_w) dense_w[at] = vals[grp][j];
-        }
+    for_each_entry(csr_view(p), [&](const CsrEntry &c) {
+      const size_t at = ((size_t)c.grp * g.Mg + c.m) * g.kdim + (size_t)c.col;
+      step_one<T, Rule, Reg>(s, rate, &vals[c.grp][c.j], diff + (s.diff_is_dense ? at : (size_t)c.e), h + c.e, h2 ? h2 + c.e : nullptr);
+      if (dense_w) dense_w[at] = vals[c.grp][c.j];
+    });
   }
 };
 

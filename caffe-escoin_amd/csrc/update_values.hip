@@ -9,6 +9,8 @@
 //   dense.w                                    the MFMA kernel's padded matrix
 //   bwd: tval, or the transposed plan's own    the backward state's copies, through BwdState::tsrc
 // The first update on an alignment builds that list (UpdState); later updates launch one kernel and nothing else.
+// The list's device facts (buffers, their sizes, the bounds checks) are collected here; the indices derived from the CSR
+// alone -- dense positions, the entry-major view -- come from the host-only builders of csr_tables.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -61,8 +63,7 @@ int collect(const escoin_plan *q, const int *src_of, UpdState *u, std::vector<Ds
     u->base[u->n_buffers] = ptr;
     return u->n_buffers++;
   };
-  long nnz = 0;
-  for (const auto &c : q->colidx) nnz += (long)c.size();
+  const long nnz = plan_nnz(q);
   if (nnz == 0) return ESCOIN_OK;
   const int b_gen = add_buffer(q->gen.vals.get<void>());
   const bool have_dense = q->n_dense_groups > 0 && q->dense.w.get<void>();
@@ -73,30 +74,31 @@ int collect(const escoin_plan *q, const int *src_of, UpdState *u, std::vector<Ds
   const int b_tiled = tiled ? add_buffer(tiled_ptr) : -1;
   if (b_gen < 0 || (have_dense && b_dense < 0) || (tiled && b_tiled < 0)) return fail(ESCOIN_EINVAL, "update_values: too many buffers");
   if (q->gen.vals.bytes() < sizeof(T) * (size_t)nnz) return fail(ESCOIN_EINVAL, "update_values: the plan's value array is shorter than its CSR");
-  const size_t lda = have_dense ? (size_t)dense_lda(g.kdim) : 0;
-  long e = 0;
+  std::vector<char> sparse_here(g.d.group, 0);
   for (int grp = 0; grp < g.d.group; ++grp) {
-    const bool sparse_here = tiled && !group_is_dense(q, grp);
-    if (sparse_here && (grp >= (int)q->tiled_dev.val_word.size() || q->tiled_dev.val_word[grp].size() != q->colidx[grp].size()))
+    sparse_here[grp] = tiled && !group_is_dense(q, grp);
+    if (sparse_here[grp] && (grp >= (int)q->tiled_dev.val_word.size() || q->tiled_dev.val_word[grp].size() != q->colidx[grp].size()))
       return fail(ESCOIN_EINVAL, "update_values: the plan's value map does not match its CSR");
-    for (int m = 0; m < g.Mg; ++m)
-      for (int j = q->rowptr[grp][m]; j < q->rowptr[grp][m + 1]; ++j, ++e) {
-        const int s = src_of ? src_of[e] : (int)e;
-        out->push_back({(unsigned char)b_gen, s, (unsigned)e});
-        if (have_dense) {
-          // (the padded matrix holds every group's rows, whichever kernel runs them)
-          const size_t at = ((size_t)grp * g.Mg + m) * lda + (size_t)q->colidx[grp][j];
-          if ((at + 1) * sizeof(T) > q->dense.w.bytes()) return fail(ESCOIN_EINVAL, "update_values: dense destination out of range");
-          out->push_back({(unsigned char)b_dense, s, (unsigned)at});
-        }
-        if (sparse_here) {
-          const unsigned w = q->tiled_dev.val_word[grp][(size_t)j];
-          if ((size_t)w >= tiled_words) return fail(ESCOIN_EINVAL, "update_values: code / stream destination out of range");
-          out->push_back({(unsigned char)b_tiled, s, w});
-        }
-      }
   }
-  return ESCOIN_OK;
+  // (the padded matrix holds every group's rows, whichever kernel runs them)
+  const std::vector<int> dense_at = have_dense ? dense_positions(csr_view(q), dense_lda(g.kdim)) : std::vector<int>();
+  const char *refused = nullptr;
+  for_each_entry(csr_view(q), [&](const CsrEntry &c) {
+    if (refused) return;
+    const int s = src_of ? src_of[c.e] : (int)c.e;
+    out->push_back({(unsigned char)b_gen, s, (unsigned)c.e});
+    if (have_dense) {
+      const size_t at = (size_t)dense_at[(size_t)c.e];
+      if ((at + 1) * sizeof(T) > q->dense.w.bytes()) { refused = "update_values: dense destination out of range"; return; }
+      out->push_back({(unsigned char)b_dense, s, (unsigned)at});
+    }
+    if (sparse_here[c.grp]) {
+      const unsigned w = q->tiled_dev.val_word[c.grp][(size_t)c.j];
+      if ((size_t)w >= tiled_words) { refused = "update_values: code / stream destination out of range"; return; }
+      out->push_back({(unsigned char)b_tiled, s, w});
+    }
+  });
+  return refused ? fail(ESCOIN_EINVAL, refused) : ESCOIN_OK;
 }
 
 // Whether the in-place path exists for plan q: generated code must sit in memory the library filled itself and carry a
@@ -110,11 +112,10 @@ bool in_place_ok(const escoin_plan *q) {
 // in-place path -- the list is the value array alone, which a solver step writes before the plan is rebuilt from it.
 template <typename T>
 int build_state(escoin_plan *p, hipStream_t stream, bool entry_view, bool vals_only = false) {
-  const Geometry &g = p->g;
   std::unique_ptr<UpdState> u(new UpdState());
   std::vector<Dst> dst;
   int rc = ESCOIN_OK;
-  for (const auto &c : p->colidx) u->nnz += (long)c.size();
+  u->nnz = plan_nnz(p);
   if (vals_only) {
     if (u->nnz > 0 && p->gen.vals.bytes() < sizeof(T) * (size_t)u->nnz) return fail(ESCOIN_EINVAL, "solver_step: the plan's value array is shorter than its CSR");
     u->base[u->n_buffers++] = p->gen.vals.get<void>();
@@ -140,39 +141,25 @@ int build_state(escoin_plan *p, hipStream_t stream, bool entry_view, bool vals_o
   std::stable_sort(dst.begin(), dst.end(), [](const Dst &a, const Dst &b) { return a.buf != b.buf ? a.buf < b.buf : a.src < b.src; });
   u->n_dst = (long)dst.size();
   const size_t n = std::max<size_t>(dst.size(), 1), nz = std::max<size_t>((size_t)u->nnz, 1);
-  std::vector<int> src(n, 0), wpos(nz, 0);
-  std::vector<unsigned> off(n, 0);
-  std::vector<unsigned char> buf(n, 0);
+  std::vector<int> src(dst.size());
+  std::vector<unsigned> off(dst.size());
+  std::vector<unsigned char> buf(dst.size());
   for (size_t k = 0; k < dst.size(); ++k) src[k] = dst[k].src, off[k] = dst[k].off, buf[k] = dst[k].buf;
-  long e = 0;
-  for (int grp = 0; grp < g.d.group; ++grp)
-    for (int m = 0; m < g.Mg; ++m)
-      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j) wpos[(size_t)e++] = (grp * g.Mg + m) * g.kdim + p->colidx[grp][j];
+  // the (bounds-checked) list by CSR entry; within an entry the buffers ascend
+  EntryMajor em;
+  if (entry_view && !entry_major(src, off, buf, u->nnz, &em)) return fail(ESCOIN_EINVAL, "solver_step: a destination names no CSR entry");
+  src.resize(n, 0), off.resize(n, 0), buf.resize(n, 0);   // (an empty list still uploads one element)
+  u->h_wpos = dense_positions(csr_view(p), p->g.kdim);
   ESCOIN_HIP_TRY(u->src.upload(src, stream));
   ESCOIN_HIP_TRY(u->off.upload(off, stream));
   ESCOIN_HIP_TRY(u->buf.upload(buf, stream));
-  ESCOIN_HIP_TRY(u->wpos.upload(wpos, stream));
+  ESCOIN_HIP_TRY(u->wpos.upload(u->h_wpos, stream));
   ESCOIN_HIP_TRY(u->stage.alloc(sizeof(T) * nz));
   u->h_stage.assign(sizeof(T) * nz, 0);
-  std::vector<int> e_ptr;
-  std::vector<unsigned> e_off;
-  std::vector<unsigned char> e_buf;
   if (entry_view) {
-    // a counting sort of the (bounds-checked) list by CSR entry; within an entry the buffers ascend
-    e_ptr.assign(nz + 1, 0), e_off.assign(n, 0), e_buf.assign(n, 0);
-    for (const Dst &d : dst) {
-      if (d.src < 0 || (long)d.src >= u->nnz) return fail(ESCOIN_EINVAL, "solver_step: a destination names no CSR entry");
-      ++e_ptr[(size_t)d.src + 1];
-    }
-    for (size_t i = 0; i < nz; ++i) e_ptr[i + 1] += e_ptr[i];
-    std::vector<int> at(e_ptr.begin(), e_ptr.end() - 1);
-    for (const Dst &d : dst) {
-      const size_t k = (size_t)at[(size_t)d.src]++;
-      e_off[k] = d.off, e_buf[k] = d.buf;
-    }
-    ESCOIN_HIP_TRY(u->e_ptr.upload(e_ptr, stream));
-    ESCOIN_HIP_TRY(u->e_off.upload(e_off, stream));
-    ESCOIN_HIP_TRY(u->e_buf.upload(e_buf, stream));
+    ESCOIN_HIP_TRY(u->e_ptr.upload(em.e_ptr, stream));
+    ESCOIN_HIP_TRY(u->e_off.upload(em.e_off, stream));
+    ESCOIN_HIP_TRY(u->e_buf.upload(em.e_buf, stream));
     u->entry_view = true;
   }
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
@@ -209,8 +196,7 @@ void patch_host_all(escoin_plan *p, const T *vals) {
 template <typename T>
 int update_by_rebuild(escoin_plan *p, const T *in, bool from_dense, bool on_device, hipStream_t stream) {
   const Geometry &g = p->g;
-  long nnz = 0;
-  for (const auto &c : p->colidx) nnz += (long)c.size();
+  const long nnz = plan_nnz(p);
   std::vector<T> host;
   const T *src = in;
   if (on_device) {
@@ -221,11 +207,8 @@ int update_by_rebuild(escoin_plan *p, const T *in, bool from_dense, bool on_devi
     src = host.data();
   }
   std::vector<std::vector<T>> &hv = plan_vals<T>(p);
-  long e = 0;
-  for (int grp = 0; grp < g.d.group; ++grp)
-    for (int m = 0; m < g.Mg; ++m)
-      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j, ++e)
-        hv[grp][j] = from_dense ? src[((size_t)grp * g.Mg + m) * g.kdim + p->colidx[grp][j]] : src[e];
+  const std::vector<int> wpos = from_dense ? dense_positions(csr_view(p), g.kdim) : std::vector<int>();
+  for_each_entry(csr_view(p), [&](const CsrEntry &c) { hv[c.grp][c.j] = from_dense ? src[wpos[(size_t)c.e]] : src[c.e]; });
   p->aligned = false;
   const int rc = realign_from_host_csr(p, stream);     // (ends a device-authoritative state like any align)
   p->upd_last_fast = 0;
@@ -290,12 +273,7 @@ int update_t(escoin_plan *p, const T *in, bool from_dense, int on_device, void *
   }
   // host source: compact values -> the host mirrors directly, and through the staging buffer into the same kernel
   T *hs = reinterpret_cast<T *>(u->h_stage.data());
-  long e = 0;
-  const Geometry &g = p->g;
-  for (int grp = 0; grp < g.d.group; ++grp)
-    for (int m = 0; m < g.Mg; ++m)
-      for (int j = p->rowptr[grp][m]; j < p->rowptr[grp][m + 1]; ++j, ++e)
-        hs[e] = from_dense ? in[((size_t)grp * g.Mg + m) * g.kdim + p->colidx[grp][j]] : in[e];
+  for (long e = 0; e < u->nnz; ++e) hs[e] = from_dense ? in[u->h_wpos[(size_t)e]] : in[e];
   patch_host_all<T>(p, hs);
   p->dev_authoritative = false;      // (every value was just replaced on both sides)
   ESCOIN_HIP_TRY(hipMemcpyAsync(u->stage.get<T>(), hs, sizeof(T) * (size_t)u->nnz, hipMemcpyHostToDevice, stream));
@@ -307,8 +285,7 @@ int update_t(escoin_plan *p, const T *in, bool from_dense, int on_device, void *
 
 template <typename T>
 int sync_host_t(escoin_plan *p) {
-  long nnz = 0;
-  for (const auto &c : p->colidx) nnz += (long)c.size();
+  const long nnz = plan_nnz(p);
   if (nnz > 0) {
     // gen.vals is the device's value array in CSR order (every plan kind keeps it)
     std::vector<T> vals((size_t)nnz);
