@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "align_rules.h"
+#include "aligned_form.h"
 #include "escoin_plan.h"
 
 namespace escoin {
@@ -552,45 +553,7 @@ template int set_csr_host<double>(escoin_plan *, const int *, const int *, const
 
 extern "C" {
 
-// ---- the persisted aligned form -----------------------------------------------------------------
-// [AlignedHdr][desc][nnz_per_group][rowptr][colidx][values][generated-code section (sconv_tiled.hip)]
-namespace {
-constexpr uint32_t kAlignedMagic = 0x4E474C41u;   // "ALGN"
-constexpr uint32_t kAlignedVersion = 2u;          // 2: content tags over the CSR and the code section (round 6)
-struct AlignedHdr {
-  uint32_t magic, version;
-  uint64_t total_bytes, nnz, jit_bytes;
-  // Content tags: 64-bit hashes of the CSR section (descriptor included) and of the generated-code section, and a
-  // third one binding the two -- the code was generated FROM this CSR.  A blob whose sections come from different
-  // exports (a torn or spliced broadcast, a stale cache file patched with new weights) is refused instead of running
-  // code that disagrees with its CSR.  Not a security boundary: an integrity check against accidents.
-  uint64_t csr_tag, jit_tag, pair_tag;
-};
-
-// 4 x 64-bit multiply-rotate lanes over 32-byte stripes (the shape of XXH64's main loop): ~10 GB/s on a host core, so
-// tagging the 54 MB of the 16 ResNet layers costs ~5 ms per side.
-inline uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-uint64_t content_tag(const void *data, size_t n, uint64_t seed) {
-  const uint64_t P1 = 0x9E3779B185EBCA87ull, P2 = 0xC2B2AE3D27D4EB4Full, P3 = 0x165667B19E3779F9ull;
-  const unsigned char *p = static_cast<const unsigned char *>(data);
-  uint64_t v[4] = {seed + P1 + P2, seed + P2, seed, seed - P1};
-  size_t i = 0;
-  for (; i + 32 <= n; i += 32)
-    for (int k = 0; k < 4; ++k) {
-      uint64_t w;
-      memcpy(&w, p + i + 8 * k, 8);
-      v[k] = rotl64(v[k] + w * P2, 31) * P1;
-    }
-  uint64_t h = rotl64(v[0], 1) + rotl64(v[1], 7) + rotl64(v[2], 12) + rotl64(v[3], 18) + (uint64_t)n;
-  for (; i < n; ++i) h = rotl64(h ^ (p[i] * P3), 11) * P1;
-  h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32;
-  return h;
-}
-uint64_t pair_tag_of(uint64_t a, uint64_t b) {
-  const uint64_t both[2] = {a, b};
-  return content_tag(both, sizeof(both), 0x6573636F696E3236ull);
-}
-}  // namespace
+// ---- the persisted aligned form (its byte layout, writer and parser: aligned_form.h) --------------------------------
 
 int escoin_plan_export_aligned(const escoin_plan *p, void *buf, size_t capacity, size_t *bytes) {
   return guarded([&]() -> int {
@@ -598,31 +561,14 @@ int escoin_plan_export_aligned(const escoin_plan *p, void *buf, size_t capacity,
     if (!p->aligned) return fail(ESCOIN_ESTATE, "export_aligned before weight_align / set_csr");
     if (p->is_f64) return fail(ESCOIN_ESTATE, "export_aligned: the aligned form is defined for float plans (a double plan has no generated code to persist; hand its CSR over with escoin_plan_get_csr_f64 / set_csr_f64)");
     if (const int rcs = sync_host_values(const_cast<escoin_plan *>(p))) return rcs;
-    const Geometry &g = p->g;
     std::vector<char> jit;
     const int rc = tiled_export(p, &jit);
     if (rc != ESCOIN_OK) return rc;
-    const uint64_t nnz = (uint64_t)plan_nnz(p);
-    const size_t need = sizeof(AlignedHdr) + sizeof(escoin_conv_desc) + 4 * (size_t)g.d.group +
-                        4 * (size_t)g.d.group * (g.Mg + 1) + 8 * (size_t)nnz + jit.size();
+    const size_t need = aligned_bytes(p->g, (uint64_t)plan_nnz(p), jit.size());
     *bytes = need;
     if (!buf) return ESCOIN_OK;                       // size query
     if (capacity < need) return fail(ESCOIN_EINVAL, "export_aligned: buffer too small");
-    char *q = static_cast<char *>(buf);
-    AlignedHdr h{kAlignedMagic, kAlignedVersion, (uint64_t)need, nnz, (uint64_t)jit.size(), 0, 0, 0};
-    char *const hdr_at = q;
-    q += sizeof(h);
-    const char *const csr_at = q;
-    memcpy(q, &g.d, sizeof(g.d)); q += sizeof(g.d);
-    for (int grp = 0; grp < g.d.group; ++grp) { const int n = (int)p->colidx[grp].size(); memcpy(q, &n, 4); q += 4; }
-    for (int grp = 0; grp < g.d.group; ++grp) { memcpy(q, p->rowptr[grp].data(), 4 * (size_t)(g.Mg + 1)); q += 4 * (size_t)(g.Mg + 1); }
-    for (int grp = 0; grp < g.d.group; ++grp) { memcpy(q, p->colidx[grp].data(), 4 * p->colidx[grp].size()); q += 4 * p->colidx[grp].size(); }
-    for (int grp = 0; grp < g.d.group; ++grp) { memcpy(q, p->values[grp].data(), 4 * p->values[grp].size()); q += 4 * p->values[grp].size(); }
-    h.csr_tag = content_tag(csr_at, (size_t)(q - csr_at), 1);
-    if (!jit.empty()) memcpy(q, jit.data(), jit.size());
-    h.jit_tag = content_tag(q, jit.size(), 2);
-    h.pair_tag = pair_tag_of(h.csr_tag, h.jit_tag);
-    memcpy(hdr_at, &h, sizeof(h));
+    aligned_write(p->g, p->rowptr, p->colidx, p->values, jit, buf);
     return ESCOIN_OK;
   });
 }
@@ -631,55 +577,19 @@ int escoin_plan_import_aligned(escoin_plan *p, const void *buf, size_t bytes, vo
   return guarded([&]() -> int {
     if (!p || !buf) return fail(ESCOIN_EINVAL, "null argument");
     const auto t_start = std::chrono::steady_clock::now();
-    const Geometry &g = p->g;
-    AlignedHdr h;
-    if (bytes < sizeof(h) + sizeof(escoin_conv_desc)) return fail(ESCOIN_EINVAL, "import_aligned: truncated blob");
-    const char *q = static_cast<const char *>(buf);
-    memcpy(&h, q, sizeof(h)); q += sizeof(h);
-    if (h.magic != kAlignedMagic || h.version != kAlignedVersion || h.total_bytes != bytes)
-      return fail(ESCOIN_EINVAL, "import_aligned: not an aligned-form blob of this library build");
-    escoin_conv_desc d;
-    memcpy(&d, q, sizeof(d)); q += sizeof(d);
-    // the weights' own geometry must match; batch, bias and ReLU are the importing plan's business
-    if (d.C != g.d.C || d.M != g.d.M || d.KH != g.d.KH || d.KW != g.d.KW || d.group != g.d.group)
-      return fail(ESCOIN_EINVAL, "import_aligned: the blob was exported for other weights (C / M / kernel / group differ)");
-    // (bounded before it sizes anything: a layer has at most group * Mg * kdim weights)
-    if (h.nnz > (uint64_t)g.d.group * (uint64_t)g.Mg * (uint64_t)g.kdim || h.jit_bytes > bytes)
-      return fail(ESCOIN_EINVAL, "import_aligned: nnz or code section larger than the layer / the blob");
-    const size_t csr_bytes = 4 * (size_t)g.d.group + 4 * (size_t)g.d.group * (g.Mg + 1) + 8 * (size_t)h.nnz;
-    if (sizeof(h) + sizeof(d) + csr_bytes + h.jit_bytes != bytes) return fail(ESCOIN_EINVAL, "import_aligned: section sizes do not add up");
-    {
-      // the content tags, before a single byte of either section is trusted
-      const char *csr_at = static_cast<const char *>(buf) + sizeof(h);
-      const size_t csr_sec = sizeof(d) + csr_bytes;
-      const uint64_t ct = content_tag(csr_at, csr_sec, 1), jt = content_tag(csr_at + csr_sec, (size_t)h.jit_bytes, 2);
-      if (ct != h.csr_tag || jt != h.jit_tag || pair_tag_of(ct, jt) != h.pair_tag)
-        return fail(ESCOIN_EINVAL, "import_aligned: content tag mismatch -- the blob is torn, or its code section does not belong to its CSR section");
-    }
-    const double ms_tags = ms_since(t_start);
-    std::vector<int> ng(g.d.group), rp((size_t)g.d.group * (g.Mg + 1)), ci((size_t)h.nnz);
-    std::vector<float> va((size_t)h.nnz);
-    memcpy(ng.data(), q, 4 * ng.size()); q += 4 * ng.size();
-    memcpy(rp.data(), q, 4 * rp.size()); q += 4 * rp.size();
-    memcpy(ci.data(), q, 4 * ci.size()); q += 4 * ci.size();
-    memcpy(va.data(), q, 4 * va.size()); q += 4 * va.size();
-    uint64_t sum = 0;
-    for (int n : ng) sum += (uint64_t)std::max(0, n);
-    if (sum != h.nnz) return fail(ESCOIN_EINVAL, "import_aligned: nnz_per_group does not match the blob's nnz");
-    const int rc = set_csr_host<float>(p, rp.data(), ci.data(), va.data(), ng.data());
+    const AlignedForm f = aligned_parse(buf, bytes, p->g);
+    if (f.rc != ESCOIN_OK) return fail(f.rc, f.error);
+    const double ms_parse = ms_since(t_start);
+    const int rc = set_csr_host<float>(p, f.rowptr.data(), f.colidx.data(), f.values.data(), f.nnz_per_group.data());
     if (rc != ESCOIN_OK) return rc;
     p->aligned = false;
-    // the code section only counts for the geometry it was generated for (the LDS offsets in the code
-    // are this H x W's) and for the same epilogue flags
-    const bool same_geom = d.H == g.d.H && d.W == g.d.W && d.pad_h == g.d.pad_h && d.pad_w == g.d.pad_w &&
-                           d.stride_h == g.d.stride_h && d.stride_w == g.d.stride_w && d.dil_h == g.d.dil_h &&
-                           d.dil_w == g.d.dil_w && d.N == g.d.N;
     const double ms_csr = ms_since(t_start);
-    const int rc2 = upload(p, (hipStream_t)stream, same_geom && h.jit_bytes ? q : nullptr, same_geom ? (size_t)h.jit_bytes : 0);
+    const bool code = f.same_geom && f.code_section_bytes > 0;
+    const int rc2 = upload(p, (hipStream_t)stream, code ? f.code_section : nullptr, f.same_geom ? f.code_section_bytes : 0);
     p->align_ms = ms_since(t_start);
     if (getenv("ESCOIN_VERBOSE"))
-      fprintf(stderr, "[escoin] import_aligned: %zu bytes (code %llu): tags %.2f ms, CSR checks %.2f ms, upload + code load %.2f ms\n",
-              bytes, (unsigned long long)h.jit_bytes, ms_tags, ms_csr - ms_tags, p->align_ms - ms_csr);
+      fprintf(stderr, "[escoin] import_aligned: %zu bytes (code %zu): tags + parse %.2f ms, CSR checks %.2f ms, upload + code load %.2f ms\n",
+              bytes, f.code_section_bytes, ms_parse, ms_csr - ms_parse, p->align_ms - ms_csr);
     return rc2;
   });
 }

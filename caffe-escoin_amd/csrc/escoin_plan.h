@@ -299,7 +299,8 @@ int tiled_build(escoin_plan *p, hipStream_t stream, bool jit);  // fills p->tile
 void tiled_release(escoin_plan *p);   // resets p->tiled_dev and p->tiled
 // The fast half of escoin_plan_import_aligned: a generated-code plan restored from what
 // escoin_plan_export_aligned wrote (tiling, channel deal, unit table, code object) -- no channel
-// deal, no generator pass, no assembler.  `blob` points behind the CSR section.
+// deal, no generator pass, no assembler.  `blob` is the code section of the persisted form, whose bytes
+// aligned_form.h writes and parses; these two do the device side around it.
 int tiled_export(const escoin_plan *p, std::vector<char> *out);
 int tiled_import(escoin_plan *p, const char *blob, size_t bytes, hipStream_t stream);
 int launch_tiled(const escoin_plan *p, const float *bottom, const float *bias, float *top,

@@ -41,7 +41,7 @@ def test_code_object_without_the_assembler_is_the_assemblers(tmp_path):
     import __graft_entry__ as ge
     ge.build()      # (the library's objects: the check links jit_module.o and what it refers to)
     objs = [os.path.join(CSRC, o) for o in ("jit_module.o", "escoin_capi.o", "sconv_generic.o", "sconv_tiled.o", "dense_mfma.o",
-                                            "sconv_lowered.o", "code_memory.o", "align_rules.o", "csr_tables.o", "stream_builder.o", "jit_codegen.o", "sconv_cpu.o",
+                                            "sconv_lowered.o", "code_memory.o", "align_rules.o", "aligned_form.o", "csr_tables.o", "stream_builder.o", "jit_codegen.o", "sconv_cpu.o",
                                             "sconv_cpu_kernel_avx2.o", "sconv_cpu_kernel_avx512.o")]
     assert all(os.path.exists(o) for o in objs)
     obj, exe = str(tmp_path / "jit_wrap_check.o"), str(tmp_path / "jit_wrap_check")

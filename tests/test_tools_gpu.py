@@ -234,6 +234,39 @@ def test_export_import_aligned_round_trip(pkg, oracle, synth):
     assert float(np.abs(want - ref).max()) <= 1e-4 * float(np.abs(ref).max())
 
 
+def test_golden_aligned_forms_export_and_import_unchanged(pkg, oracle, synth):
+    """tests/golden/aligned_form_*.bin pin the persisted form across library versions (an MI355X's exports at the commit
+    the sidecar names; recipe: tests/golden/make_aligned_form_golden.py): the same weights and options export the same
+    bytes, and a plan that imports the golden loads its code as persisted and computes the same bits.  A device with
+    another CU count or ISA fails here: the goldens are MI355X's."""
+    import json
+    import torch
+    dev = torch.device("cuda:0")
+    golden = os.path.join(ROOT, "tests", "golden")
+    with open(os.path.join(golden, "aligned_form.json")) as f:
+        side = json.load(f)
+    opts = dict(kernel=getattr(pkg, side["kernel"]), tiling_batch=side["tiling_batch"])
+    for k, case in enumerate(side["cases"]):
+        c = case["shape"]
+        s = synth.shape(case["file"], c["N"], c["C"], c["H"], c["W"], c["M"], c["K"], pad=c["pad"], group=c["group"],
+                        bias=False, sparsity=c["sparsity"])
+        blob = np.fromfile(os.path.join(golden, case["file"]), np.uint8)
+        w = synth.pruned_weights(s, case["weights_seed"])
+        x = synth.activations(s, 3200 + k)
+        plan = pkg.Plan(pkg.ConvDesc.from_shape(s), **opts)
+        plan.weight_align(w)
+        assert np.array_equal(plan.export_aligned(), blob), "%s: this build on this device exports other bytes" % case["file"]
+        want = plan.forward(torch.from_numpy(x).to(dev), None).cpu().numpy()
+        p2 = pkg.Plan(pkg.ConvDesc.from_shape(s), **opts)
+        p2.import_aligned(blob)
+        assert p2.stat("import_fast") == 1, "%s: the persisted code was not loaded (CU count / ISA / build differ from the golden's)" % case["file"]
+        assert np.array_equal(p2.forward(torch.from_numpy(x).to(dev), None).cpu().numpy(), want), case["file"]
+        g = oracle.geom(s.C, s.H, s.W, s.M, s.KH, s.KW, s.pad_h, s.pad_w, group=s.group)
+        assert rel_err(want, oracle.conv_forward(g, x, w, None, gate=False)) <= 1e-4, case["file"]
+        plan.close()
+        p2.close()
+
+
 def test_caffe_test_chain_from_persisted_aligned_form(tmp_path):
     """resnet50_chain: --save-aligned, then a second run --load-aligned: every layer restored without the
     channel deal / generator / assembler, oracle check green."""
