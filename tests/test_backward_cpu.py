@@ -9,22 +9,7 @@ from conftest import Golden, golden_params, rel_err
 torch = pytest.importorskip("torch")
 F = torch.nn.functional
 
-
-def torch_backward(x, w, bias, s, top_diff, top=None):
-    """torch float64 autograd on the CPU: (bottom_diff, weight_diff masked by w != 0, bias_diff).  With `top` (a fuse_relu
-    layer's forward output) the gradient is top_diff x [top > 0] -- the mask the library applies, taken from the same
-    top."""
-    X = torch.tensor(np.asarray(x, np.float64), requires_grad=True)
-    Wt = torch.tensor(np.asarray(w, np.float64), requires_grad=True)
-    B = torch.tensor(np.asarray(bias, np.float64), requires_grad=True) if bias is not None else None
-    y = F.conv2d(X, Wt, B, stride=(s.stride_h, s.stride_w), padding=(s.pad_h, s.pad_w),
-                 dilation=(s.dil_h, s.dil_w), groups=s.group)
-    g = torch.tensor(np.asarray(top_diff, np.float64))
-    if top is not None:
-        g = g * torch.tensor((np.asarray(top) > 0).astype(np.float64))
-    y.backward(g)
-    return (X.grad.numpy(), Wt.grad.numpy() * (np.asarray(w) != 0),
-            B.grad.numpy() if B is not None else None)
+from wgrad_common import EDGES, csr_positions, edge_inputs, torch_backward  # noqa: E402
 
 
 def _seeded(shape, seed, dt):
@@ -176,4 +161,31 @@ def test_explicit_zeros_handed_to_set_csr_receive_a_gradient(pkg):
     mask = np.zeros_like(flat, bool)
     mask[0, 0] = mask[0, 4] = mask[1, 13] = True
     assert np.all(flat[~mask] == 0)
+    plan.close()
+
+
+@pytest.mark.parametrize("name", list(EDGES))
+def test_directed_edges_match_torch(pkg, name):
+    """The shapes test_backward_gpu.py runs on the device kernels (wgrad_common.EDGES), through backward_cpu: more than
+    32767 output channels per group, transposed pads 0 and 4, partial batches with fuse_relu, padding beyond the kernel's
+    reach and none, a conv group without a nonzero."""
+    synth = pkg.synth
+    s, w, x, b = edge_inputs(synth, name)
+    relu = name == "relu3x3_n7"
+    plan = pkg.Plan(pkg.ConvDesc.from_shape(s, fuse_relu=relu))
+    plan.weight_align_cpu(w)
+    top = plan.forward_cpu(x, b) if relu else None
+    td = _seeded((s.N, s.M) + plan.out_hw, 21, np.float32)
+    full = None
+    for n in ((s.N, 1, 3, 6) if relu else (s.N,)):
+        tp = None if top is None else top[:n]
+        bd, wd, bsd = plan.backward_cpu(td[:n], bottom=x[:n], top=tp, weight_diff=True, bias_diff=True)
+        want = torch_backward(x[:n], w, b, s, td[:n], tp)
+        for got, ref in zip((bd, wd, bsd), want):
+            assert rel_err(got, ref) <= 1e-4, (name, n, rel_err(got, ref))
+        assert np.all(wd[w == 0] == 0)
+        full = bd if full is None else full
+        assert bd.tobytes() == full[:n].tobytes()
+        _, vd, _ = plan.backward_cpu(td[:n], bottom=x[:n], top=tp, bottom_diff=None, values_diff=True)
+        assert vd.tobytes() == wd.reshape(-1)[csr_positions(plan)].tobytes()
     plan.close()

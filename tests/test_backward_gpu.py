@@ -9,6 +9,8 @@ from conftest import Golden, golden_params, rel_err
 torch = pytest.importorskip("torch")
 F = torch.nn.functional
 
+from wgrad_common import EDGES, csr_positions, edge_inputs, torch_backward  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
 
@@ -18,19 +20,6 @@ def dev(pkg):
     if not torch.cuda.is_available() or pkg.device_count() < 1:
         pytest.fail("no HIP device visible (these tests run on the MI355X)")
     return torch.device("cuda:0")
-
-
-def torch_backward(x, w, bias, s, top_diff, top=None):
-    X = torch.tensor(np.asarray(x, np.float64), requires_grad=True)
-    Wt = torch.tensor(np.asarray(w, np.float64), requires_grad=True)
-    B = torch.tensor(np.asarray(bias, np.float64), requires_grad=True) if bias is not None else None
-    y = F.conv2d(X, Wt, B, stride=(s.stride_h, s.stride_w), padding=(s.pad_h, s.pad_w),
-                 dilation=(s.dil_h, s.dil_w), groups=s.group)
-    g = torch.tensor(np.asarray(top_diff, np.float64))
-    if top is not None:
-        g = g * torch.tensor((np.asarray(top) > 0).astype(np.float64))
-    y.backward(g)
-    return X.grad.numpy(), Wt.grad.numpy() * (np.asarray(w) != 0), B.grad.numpy() if B is not None else None
 
 
 def _seeded(shape, seed, dt=np.float32):
@@ -328,4 +317,120 @@ def test_forward_backward_graph_capture(pkg, dev, synth):
             _check_against_torch(s, w, x, b, td, top, u["bd"].cpu().numpy(), u["wd"].cpu().numpy(),
                                  None if b is None else u["bsd"].cpu().numpy(), what=(s.name, rnd))
     for s, plan, *_ in layers:
+        plan.close()
+
+
+# ---- directed edges (wgrad_common.EDGES; test_backward_cpu.py runs the same shapes through backward_cpu) -----------------
+def test_more_than_32767_output_channels_per_group_take_the_gather_kernel(pkg, dev, synth):
+    """ocl fills the upper bits of the gather table's ttap, the entry kernel's grid.y is M."""
+    s, w, x, b = edge_inputs(synth, "mg40000")
+    for k, wk in ((pkg.KERNEL_AUTO, pkg.WGRAD_AUTO), (pkg.KERNEL_GENERIC, pkg.WGRAD_ENTRY)):
+        plan, td, top, bd, wd, bsd = _run(pkg, dev, s, pkg.ConvDesc.from_shape(s), w, x, b, kernel=k, wgrad_kernel=wk)
+        assert plan.stat("bwd_data_kernel") == pkg.KERNEL_GENERIC
+        if wk == pkg.WGRAD_ENTRY:
+            assert plan.stat("wgrad_kernel") == pkg.WGRAD_ENTRY
+        _check_against_torch(s, w, x, b, td, top, bd, wd, bsd, what=(s.name, k))
+        plan.close()
+    plan = pkg.Plan(pkg.ConvDesc.from_shape(s), backward_kernel=pkg.KERNEL_JIT)
+    plan.weight_align(w)
+    with pytest.raises(pkg.EscoinError, match="no transposed forward plan"):
+        plan.backward(torch.zeros((s.N, s.M, 2, 2), device=dev))
+    plan.close()
+
+
+@pytest.mark.parametrize("name", ["lenet5x5_pad0", "5x5_pad4", "3x5_pad2x0", "group_pruned"])
+def test_transposed_pads_and_a_fully_pruned_group_on_the_forced_fast_kernels(pkg, dev, synth, name):
+    s, w, x, b = edge_inputs(synth, name)
+    for k in (pkg.KERNEL_TILED, pkg.KERNEL_JIT):
+        plan, td, top, bd, wd, bsd = _run(pkg, dev, s, pkg.ConvDesc.from_shape(s), w, x, b, kernel=k)
+        assert plan.stat("bwd_data_kernel") == k
+        _check_against_torch(s, w, x, b, td, top, bd, wd, bsd, what=(name, k))
+        plan.close()
+
+
+def test_partial_batches_on_a_fuse_relu_transposed_plan(pkg, dev, synth):
+    s, w, x, b = edge_inputs(synth, "relu3x3_n7")
+    xt, bt = torch.from_numpy(x).to(dev), torch.from_numpy(b).to(dev)
+    td = _seeded((s.N, s.M) + synth.out_hw(s), 21)
+    tdt = torch.from_numpy(td).to(dev)
+    for k in (pkg.KERNEL_TILED, pkg.KERNEL_JIT):
+        plan = pkg.Plan(pkg.ConvDesc.from_shape(s, fuse_relu=True), backward_kernel=k, tiling_batch=256)
+        plan.weight_align(w)
+        top = plan.forward(xt, bt)
+        top_np = top.cpu().numpy()
+        full = None
+        for n in (0, s.N, 1, 3, 6):      # 0 images first: a no-op that still builds the state
+            out = torch.full((s.N, s.C, s.H, s.W), -7.5, device=dev)
+            if n == 0:      # (an empty torch tensor has no address: the C entry point with the full blobs' pointers)
+                import ctypes as C
+                wd, bsd = torch.zeros((s.M, s.C, 3, 3), device=dev), torch.zeros((s.M,), device=dev)
+                P = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
+                assert pkg.lib().escoin_backward(plan._h, P(xt), P(top), P(tdt), P(out), P(wd), P(bsd), 0,
+                                                 C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+            else:
+                _, wd, bsd = plan.backward(tdt[:n], bottom=xt[:n], top=top[:n], bottom_diff=out[:n], weight_diff=True,
+                                           bias_diff=True)
+            torch.cuda.synchronize()
+            assert plan.stat("bwd_data_kernel") == k
+            got = out.cpu().numpy()
+            assert np.all(got[n:] == -7.5), (k, n)
+            if n == 0:
+                assert not wd.cpu().numpy().any() and not bsd.cpu().numpy().any()
+                continue
+            _check_against_torch(s, w, x[:n], b, td[:n], top_np[:n], got[:n], wd.cpu().numpy(), bsd.cpu().numpy(), what=(k, n))
+            if n == s.N:
+                full = got
+            assert got[:n].tobytes() == full[:n].tobytes(), (k, n)
+        plan.close()
+
+
+def test_sub_batch_launches_of_the_transposed_plan(pkg, dev, synth):
+    s, w, x, b = edge_inputs(synth, "chunked")
+    oh, ow = synth.out_hw(s)
+    for k in (pkg.KERNEL_TILED, pkg.KERNEL_JIT):
+        # three images of the transposed plan's bottom (top_diff) per launch: 11 images in four launches
+        plan, td, top, bd, wd, bsd = _run(pkg, dev, s, pkg.ConvDesc.from_shape(s), w, x, b, kernel=k,
+                                          max_launch_bytes=3 * s.M * oh * ow * 4 + 100)
+        assert plan.stat("bwd_data_kernel") == k
+        _check_against_torch(s, w, x, b, td, top, bd, wd, bsd, what=(s.name, k))
+        plan.close()
+        # No stat counts the launches, and a split cannot change a result.  That the option does reach the transposed
+        # plan shows where it must refuse: with less than ONE image of top_diff per launch the transposed plan's launcher
+        # says so (the plan's own forward, whose bottom the option also bounds, is never called here).
+        plan = pkg.Plan(pkg.ConvDesc.from_shape(s), backward_kernel=k, max_launch_bytes=s.M * oh * ow * 4 - 4)
+        plan.weight_align(w)
+        with pytest.raises(pkg.EscoinError, match="one image exceeds"):
+            plan.backward(torch.from_numpy(td).to(dev))
+        plan.close()
+
+
+def test_a_weight_stream_beyond_the_lds_budget_refuses_forced_tiled_only(pkg, dev, synth):
+    """Found by tools/fuzz_backward.py (profiles/backward_fuzz.md): the transposed descriptor passes the geometry
+    predicate, but at tiling_batch 256 the stream kernel's weight stream (2 x 630 entries per group, 70 % dense 5 x 5) does
+    not fit beside the input planes.  A forced TILED says so; AUTO and JIT compute the gradient."""
+    s, w, x, b = edge_inputs(synth, "stream_budget")
+    opts = dict(tiling_batch=256, max_launch_bytes=121060)
+    plan = pkg.Plan(pkg.ConvDesc.from_shape(s), backward_kernel=pkg.KERNEL_TILED, **opts)
+    plan.weight_align(w)
+    with pytest.raises(pkg.EscoinError, match="weight stream does not fit the LDS budget"):
+        plan.backward(torch.zeros((s.N, s.M) + synth.out_hw(s), device=dev))
+    plan.close()
+    for k in (pkg.KERNEL_AUTO, pkg.KERNEL_JIT):
+        plan, td, top, bd, wd, bsd = _run(pkg, dev, s, pkg.ConvDesc.from_shape(s), w, x, b, kernel=k, **opts)
+        assert plan.stat("bwd_data_kernel") == pkg.KERNEL_JIT, k
+        _check_against_torch(s, w, x, b, td, top, bd, wd, bsd, what=(s.name, k))
+        plan.close()
+
+
+@pytest.mark.parametrize("name", ["overpad3x3", "nopad3x3", "nopad3x3_n4"])
+def test_staged_weight_gradient_with_more_padding_than_the_kernel_reaches_and_with_none(pkg, dev, synth, name):
+    s, w, x, b = edge_inputs(synth, name)
+    for relu in (False, True):
+        plan, td, top, bd, wd, bsd = _run(pkg, dev, s, pkg.ConvDesc.from_shape(s, fuse_relu=relu), w, x, b, relu=relu,
+                                          wgrad_kernel=pkg.WGRAD_STAGED)
+        assert plan.stat("wgrad_kernel") == pkg.WGRAD_STAGED
+        _check_against_torch(s, w, x, b, td, top, bd, wd, bsd, what=(name, relu))
+        _, vd, _ = plan.backward(torch.from_numpy(td).to(dev), bottom=torch.from_numpy(x).to(dev),
+                                 top=None if top is None else torch.from_numpy(top).to(dev), bottom_diff=None, values_diff=True)
+        assert vd.cpu().numpy().tobytes() == wd.reshape(-1)[csr_positions(plan)].tobytes(), (name, relu)
         plan.close()

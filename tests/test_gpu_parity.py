@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import Golden, golden_params, naive_conv, rel_err
+from wgrad_common import tiled_ok as _tiled_ok      # (shared with tools/fuzz_backward.py)
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-4
@@ -45,9 +46,6 @@ def _kernels(pkg, desc=None):
     return ks
 
 
-def _tiled_ok(d):
-    return (d.stride_h == 1 and d.stride_w == 1 and d.dil_h == 1 and d.dil_w == 1 and d.KW <= 5 and
-            max(d.W, d.W + 2 * d.pad_w - d.KW + 1) <= 256 and d.pad_w <= 4 and d.KW - 1 - d.pad_w <= 4)
 
 
 def _fast(name):
