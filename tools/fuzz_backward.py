@@ -4,7 +4,10 @@ mode) against torch float64 autograd on the CPU: the data gradient through every
 plan on every forward kernel family, the gather kernel bit for bit against the CPU mode), the weight / bias gradient under
 every wgrad_kernel in dense and compact form, accumulation into prefilled blobs, calls on fewer images than the plan's
 batch, blobs that are windows of larger allocations off a 16-byte boundary, in-place weight updates between two calls, and
-determinism.  A sibling of tools/fuzz_parity.py.
+determinism.  One case in four runs on inputs whose rows, channels and images differ in scale by up to 2^48
+(tools/error_bound.py skew) and is checked element by element against the derived bound instead of the max-norm; which cases
+is drawn from a second generator, so a (seed, k) names the same geometry and weights as before.  A sibling of
+tools/fuzz_parity.py.
     python tools/fuzz_backward.py [cases] [seed] [--cpu] > fuzz_backward.txt
 Prints one line per failure (everything needed to rebuild the case) and a summary; exit code 1 on any failure.  Unlike
 fuzz_parity.py an exception that is not a documented refusal (EscoinError, ESCOIN_EINVAL) ends the run at once: nothing
@@ -17,10 +20,11 @@ from collections import namedtuple
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-for _p in (ROOT, os.path.join(ROOT, "tests")):
+for _p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 import __graft_entry__ as ge  # noqa: E402
+import error_bound as eb  # noqa: E402
 from conftest import rel_err  # noqa: E402
 from upd_common import new_weights  # noqa: E402
 from wgrad_common import csr_positions, tiled_ok, torch_backward  # noqa: E402
@@ -29,7 +33,10 @@ TOL = 1e-4          # the project's fp32 tolerance (tests/test_backward_gpu.py)
 TOL_F64 = 1e-12
 SENTINEL = -1234.5  # exact in float32
 
-Case = namedtuple("Case", "k cls s dist relu tb mlb f64 accumulate n_part window update")
+SKEW_STREAM = 0x5CA1E       # which cases are skewed: RandomState(seed ^ SKEW_STREAM), apart from the generator's own
+SKEWED = "(cases skewed and checked per element)"
+
+Case = namedtuple("Case", "k cls s dist relu tb mlb f64 accumulate n_part window update skew")
 
 DATA_KERNELS = ("auto", "generic", "tiled", "jit", "dense")
 KERNEL_NAMES = {0: "auto", 1: "generic", 2: "tiled", 3: "dense", 4: "jit"}
@@ -42,6 +49,7 @@ def generate(cases, seed, synth):
     kernel serve it), 2: pointwise, 3: many channels, 4: many small images.  Sizes are the smallest that still cross
     each boundary: 1024-pixel chunks that span several images, tile slots past the batch, more than one channel block."""
     rng = np.random.RandomState(seed)
+    rng_skew = np.random.RandomState((seed ^ SKEW_STREAM) & 0xFFFFFFFF)
     out = []
     for k in range(cases):
         cls = k % 5
@@ -88,7 +96,8 @@ def generate(cases, seed, synth):
         n_part = int(rng.randint(1, N)) if N > 1 and rng.randint(3) == 0 else 0
         window = int(rng.choice([1, 3])) if rng.randint(4) == 0 else 0
         update = rng.randint(5) == 0
-        out.append(Case(k, cls, s, dist, relu, tb, mlb, bool(f64), bool(accumulate), n_part, window, bool(update)))
+        out.append(Case(k, cls, s, dist, relu, tb, mlb, bool(f64), bool(accumulate), n_part, window, bool(update),
+                        bool(rng_skew.randint(4) == 0)))
     return out
 
 
@@ -159,7 +168,8 @@ def expected_runs(synth, cs):
 
 
 def inputs(synth, c):
-    """(w, x, bias, top_diff) of a case in its dtype; the double cases hold the float values."""
+    """(w, x, bias, top_diff) of a case in its dtype; the double cases hold the float values.  A skewed case's are scaled
+    by exact powers of two (error_bound.skew)."""
     s = c.s
     dt = np.float64 if c.f64 else np.float32
     w = synth.pruned_weights(s, 1000 + c.k, dist=c.dist)
@@ -167,13 +177,16 @@ def inputs(synth, c):
     x = synth.activations(s, 3000 + c.k)
     oh, ow = synth.out_hw(s)
     td = np.random.RandomState(4000 + c.k).uniform(-1, 1, (s.N, s.M, oh, ow)).astype(np.float32)
+    if c.skew:
+        sk = eb.skew(s, w, x, b, 7000 + c.k, top_diff=td)
+        w, x, b, td = sk.w, sk.x, sk.b, sk.top_diff
     return w.astype(dt), x.astype(dt), None if b is None else b.astype(dt), td.astype(dt)
 
 
 def describe(seed, c):
     s = c.s
-    return ("seed=%d k=%d %s dist=%s relu=%d tb=%d mlb=%d f64=%d acc=%d n_part=%d window=%d update=%d" %
-            (seed, c.k, tuple(s[1:17]), c.dist, c.relu, c.tb, c.mlb, c.f64, c.accumulate, c.n_part, c.window, c.update))
+    return ("seed=%d k=%d %s dist=%s relu=%d tb=%d mlb=%d f64=%d acc=%d n_part=%d window=%d update=%d skew=%d" %
+            (seed, c.k, tuple(s[1:17]), c.dist, c.relu, c.tb, c.mlb, c.f64, c.accumulate, c.n_part, c.window, c.update, c.skew))
 
 
 def _prefill(c, w, pattern):
@@ -192,7 +205,7 @@ class _Checker(object):
     """Collects failure lines; every line carries the seed, k, the shape tuple and the options."""
 
     def __init__(self, seed, out):
-        self.seed, self.out, self.lines, self.worst = seed, out, [], 0.0
+        self.seed, self.out, self.lines, self.worst = seed, out, [], {}
 
     def fail(self, c, what):
         line = "FAIL %s: %s" % (what, describe(self.seed, c))
@@ -211,45 +224,84 @@ class _Checker(object):
         if a.shape != b.shape or a.tobytes() != b.tobytes():
             self.fail(c, "%s: bytes differ (rel err %.3g)" % (what, rel_err(a, b) if a.shape == b.shape and a.size else -1))
 
-    def gradients(self, c, what, got, want, pattern, tol, base=None):
+    def bounded(self, c, what, got, want, B, name):
+        """A skewed case's check: every element within its bound (error_bound.check); the worst ratio is kept per `name`."""
+        if got.shape != want.shape:
+            self.fail(c, "%s: shape %s, want %s" % (what, got.shape, want.shape))
+            return
+        ratio, idx = eb.check(got, want, B)
+        self.worst[name] = max(self.worst.get(name, 0.0), ratio)
+        if not ratio <= 1.0:
+            self.fail(c, "%s via %s: element %s off by %.3g x its bound (got %r, want %r)" %
+                      (what, name, idx, ratio, float(got[idx]), float(want[idx])))
+
+    def gradients(self, c, what, got, want, pattern, tol, base=None, bounds=None, names=("", ""), n_images=None):
         """(bottom_diff, weight_diff, bias_diff) against the reference; with `base` = (weight_diff, bias_diff) before
-        the call the outputs accumulated: base + gradient at the pattern, the bits outside it unchanged."""
+        the call the outputs accumulated: base + gradient at the pattern, the bits outside it unchanged.  With `bounds`
+        (a skewed case: error_bound.backward_bound's) every element is held to its bound instead of the max-norm `tol`;
+        names: (data-gradient kernel, weight-gradient kernel) for the summary."""
         bd, wd, bsd = got
         if bd is not None:
-            self.close(c, what + " bottom_diff", bd, want[0], tol)
+            if bounds is None:
+                self.close(c, what + " bottom_diff", bd, want[0], tol)
+            else:
+                self.bounded(c, what + " bottom_diff", bd, want[0], bounds[0], names[0])
+        n_terms = (c.s.N if n_images is None else n_images) * int(np.prod(ge.load_package().synth.out_hw(c.s)))
         if wd is not None:
             if base is None:
-                self.close(c, what + " weight_diff", wd, want[1], tol)
+                if bounds is None:
+                    self.close(c, what + " weight_diff", wd, want[1], tol)
+                else:
+                    self.bounded(c, what + " weight_diff", wd, want[1], bounds[1], names[1])
                 if np.any(wd[~pattern] != 0):
                     self.fail(c, what + " weight_diff: written outside the pattern")
             else:
-                self.close(c, what + " weight_diff (accumulated)", np.where(pattern, wd, 0),
-                           np.where(pattern, base[0].astype(np.float64) + want[1], 0), tol)
+                acc_want = np.where(pattern, base[0].astype(np.float64) + want[1], 0)
+                if bounds is None:
+                    self.close(c, what + " weight_diff (accumulated)", np.where(pattern, wd, 0), acc_want, tol)
+                else:
+                    B = eb.accumulated_bound(bounds[1], np.where(pattern, base[0], 0), n_terms, c.f64)
+                    self.bounded(c, what + " weight_diff (accumulated)", np.where(pattern, wd, 0), acc_want, B, names[1])
                 if not _same_nan_bits(wd, base[0], ~pattern):
                     self.fail(c, what + " weight_diff: the prefill outside the pattern changed")
         if bsd is not None:
-            self.close(c, what + " bias_diff", bsd, want[2] if base is None else base[1].astype(np.float64) + want[2], tol)
+            bwant = want[2] if base is None else base[1].astype(np.float64) + want[2]
+            if bounds is None:
+                self.close(c, what + " bias_diff", bsd, bwant, tol)
+            else:
+                B = bounds[2] if base is None else eb.accumulated_bound(bounds[2], base[1], n_terms, c.f64)
+                self.bounded(c, what + " bias_diff", bsd, bwant, B, names[1] + " bias")
 
 
 # ---- CPU mode -----------------------------------------------------------------------------------------------------------
-def _cpu_case(pkg, synth, c, chk, count):
-    s = c.s
-    w32, x32, b32, td32 = inputs(synth, c._replace(f64=False))
+def _reference(c, x, w, b, td, top, mask=None):
+    """(the float64 gradients, their per-element bounds for a skewed case or None)."""
+    if c.skew:
+        return eb.backward_bound(c.s, w, x, b, td, top, f64=c.f64, mask=mask)
+    return torch_backward(x, w, b, c.s, td, top, mask=mask), None
+
+
+def _cpu_case(pkg, synth, c0, chk, count):
+    s = c0.s
+    w32, x32, b32, td32 = inputs(synth, c0._replace(f64=False))
     pattern = w32 != 0
     want = None
     for dt in (np.float32, np.float64):
+        c = c0._replace(f64=dt == np.float64)       # (the dtype of this pass: what the bounds and a failure line go by)
         tol = TOL if dt == np.float32 else TOL_F64
         w, x, td = w32.astype(dt), x32.astype(dt), td32.astype(dt)
         b = None if b32 is None else b32.astype(dt)
         plan = pkg.Plan(pkg.ConvDesc.from_shape(s, fuse_relu=c.relu))
         plan.weight_align_cpu(w)
         top = plan.forward_cpu(x, b) if c.relu else None
-        # (the float and the double forward may disagree on the sign of an output next to zero: one reference each then)
-        if want is None or c.relu:
-            want = torch_backward(x, w, b, s, td, top)
+        # (the float and the double forward may disagree on the sign of an output next to zero: one reference each then;
+        #  a skewed case's bounds depend on the dtype)
+        if want is None or c.relu or c.skew:
+            want, bounds = _reference(c, x, w, b, td, top)
         what = "cpu %s" % np.dtype(dt).name
+        names = (what + " data", what + " weights")
         got = plan.backward_cpu(td, bottom=x, top=top, weight_diff=True, bias_diff=True if b is not None else None)
-        chk.gradients(c, what, got, want, pattern, tol)
+        chk.gradients(c, what, got, want, pattern, tol, bounds=bounds, names=names)
         _, vd, bsd2 = plan.backward_cpu(td, bottom=x, top=top, bottom_diff=None, values_diff=True,
                                         bias_diff=True if b is not None else None)
         chk.same(c, what + " values_diff against weight_diff at the CSR positions", vd, got[1].reshape(-1)[csr_positions(plan)])
@@ -264,18 +316,19 @@ def _cpu_case(pkg, synth, c, chk, count):
             wd0, bsd0 = _prefill(c, w, pattern)
             wd, bsd = wd0.copy(), bsd0.copy() if b is not None else None
             acc = plan.backward_cpu(td, bottom=x, top=top, weight_diff=wd, bias_diff=bsd)
-            chk.gradients(c, what + " accumulate", acc, want, pattern, tol, base=(wd0, bsd0))
+            chk.gradients(c, what + " accumulate", acc, want, pattern, tol, base=(wd0, bsd0), bounds=bounds, names=names)
             chk.same(c, what + " accumulate bottom_diff", acc[0], got[0])
             count("accumulation cases", dt == np.float32)
         if c.n_part:
             n = c.n_part
             ptop = None if top is None else top[:n]
-            pwant = torch_backward(x[:n], w, b, s, td[:n], ptop)
+            pwant, pbounds = _reference(c, x[:n], w, b, td[:n], ptop)
             part = plan.backward_cpu(td[:n], bottom=x[:n], top=ptop, weight_diff=True, bias_diff=True if b is not None else None)
-            chk.gradients(c, what + " partial %d" % n, part, pwant, pattern, tol)
+            chk.gradients(c, what + " partial %d" % n, part, pwant, pattern, tol, bounds=pbounds, names=names, n_images=n)
             chk.same(c, what + " partial %d bottom_diff against the full call's" % n, part[0], got[0][:n])
             count("partial calls", dt == np.float32)
         plan.close()
+    count(SKEWED, c0.skew)
 
 
 # ---- device ------------------------------------------------------------------------------------------------------------
@@ -324,7 +377,7 @@ def _device_case(pkg, synth, torch, dev, c, chk, count):
 
     def reference(key, xx, ww, tt, top, mask=None):
         if key not in refs:
-            refs[key] = torch_backward(xx, ww, b, s, tt, top, mask=mask)
+            refs[key] = _reference(c, xx, ww, b, tt, top, mask=mask)
         return refs[key]
 
     # (data kernel, weight-gradient kernel, outputs asked for)
@@ -343,7 +396,7 @@ def _device_case(pkg, synth, torch, dev, c, chk, count):
             if c.relu and top_np is None:
                 top_np = down(top)      # every plan of the case has the same forward: one mask, one reference
             topd = up(top_np)
-            want = reference("full", x, w, td, top_np)
+            want, bounds = reference("full", x, w, td, top_np)
             call = dict(bottom=xd, top=topd, bottom_diff=True if want_bd else None, weight_diff=True,
                         bias_diff=True if has_b else None)
             try:
@@ -365,8 +418,9 @@ def _device_case(pkg, synth, torch, dev, c, chk, count):
                 continue
             torch.cuda.synchronize()
             got = tuple(down(t) for t in r1)
-            chk.gradients(c, what, got, want, pattern, tol)
             ran_k, ran_w = plan.stat("bwd_data_kernel"), plan.stat("wgrad_kernel")
+            how = dict(bounds=bounds, names=("bwd_data_kernel " + KERNEL_NAMES[ran_k], "wgrad_kernel " + WGRAD_NAMES[ran_w]))
+            chk.gradients(c, what, got, want, pattern, tol, **how)
             if want_bd:
                 count("bwd_data_kernel " + KERNEL_NAMES[ran_k], 1)
                 on_tplan = transposable(c) and kn != "generic"
@@ -399,19 +453,19 @@ def _device_case(pkg, synth, torch, dev, c, chk, count):
                 acc = plan.backward(tdd, bottom=xd, top=topd, bottom_diff=None, weight_diff=up(wd0),
                                     bias_diff=up(bsd0) if has_b else None)
                 torch.cuda.synchronize()
-                chk.gradients(c, what + " accumulate", tuple(down(t) for t in acc), want, pattern, tol, base=(wd0, bsd0))
+                chk.gradients(c, what + " accumulate", tuple(down(t) for t in acc), want, pattern, tol, base=(wd0, bsd0), **how)
                 count("accumulation cases", kn == "auto")
             if c.n_part:
                 n = c.n_part
                 ptop = None if top_np is None else top_np[:n]
-                pwant = reference("part", x[:n], w, td[:n], ptop)
+                pwant, pbounds = reference("part", x[:n], w, td[:n], ptop)
                 full = torch.full((s.N, s.C, s.H, s.W), SENTINEL, dtype=tdt, device=dev)
                 part = plan.backward(tdd[:n], bottom=xd[:n], top=None if topd is None else topd[:n],
                                      bottom_diff=full[:n] if want_bd else None, weight_diff=True,
                                      bias_diff=True if has_b else None)
                 torch.cuda.synchronize()
                 pg = tuple(down(t) for t in part)
-                chk.gradients(c, what + " partial %d" % n, pg, pwant, pattern, tol)
+                chk.gradients(c, what + " partial %d" % n, pg, pwant, pattern, tol, n_images=n, **dict(how, bounds=pbounds))
                 if want_bd:
                     chk.same(c, what + " partial %d bottom_diff against the full call's" % n, pg[0], got[0][:n])
                     if np.any(down(full[n:]) != SENTINEL):
@@ -431,7 +485,7 @@ def _device_case(pkg, synth, torch, dev, c, chk, count):
                     if a is not None and np.any(np.isnan(a if name != "weight_diff" else a[pattern])):
                         chk.fail(c, "%s window +%d: NaN from outside an input blob reached %s" % (what, c.window, name))
                 chk.gradients(c, what + " window +%d" % c.window, wg, want, pattern, tol,
-                              base=(wd0, bsd0) if c.accumulate else None)
+                              base=(wd0, bsd0) if c.accumulate else None, **how)
                 for name, o in zip(("bottom_diff", "weight_diff", "bias_diff"), outs):
                     if o is not None:
                         intact("%s window +%d %s" % (what, c.window, name), *o)
@@ -442,19 +496,22 @@ def _device_case(pkg, synth, torch, dev, c, chk, count):
                 utop = plan.forward(xd, bd_) if c.relu else None
                 utop_np = down(utop)
                 # (the new top is this plan's own: its forward kernel family may differ in the last bits from another's)
-                uwant = torch_backward(x, w_new, b, s, td, utop_np, mask=pattern)
+                uwant, ubounds = _reference(c, x, w_new, b, td, utop_np, mask=pattern)
                 ur = plan.backward(tdd, bottom=xd, top=utop, bottom_diff=True if want_bd else None, weight_diff=True,
                                    bias_diff=True if has_b else None)
                 torch.cuda.synchronize()
-                chk.gradients(c, what + " after update_values", tuple(down(t) for t in ur), uwant, pattern, tol)
+                chk.gradients(c, what + " after update_values", tuple(down(t) for t in ur), uwant, pattern, tol,
+                              **dict(how, bounds=ubounds))
                 count("update cases", kn == "auto")
         finally:
             plan.close()
+    count(SKEWED, c.skew)
 
 
-def fuzz(cases, seed, out=sys.stdout, device=True):
+def fuzz(cases, seed, out=sys.stdout, device=True, worst=None):
     """Runs `cases` random geometries; returns (runs, failure lines, counts by name).  device=False: the same generator
-    and reference through backward_cpu only (no torch.cuda)."""
+    and reference through backward_cpu only (no torch.cuda).  worst: a dict that receives the largest err / bound of the
+    skewed cases per kernel name."""
     pkg = ge.load_package()
     synth = pkg.synth
     chk = _Checker(seed, out)
@@ -465,7 +522,7 @@ def fuzz(cases, seed, out=sys.stdout, device=True):
     if device:
         import torch
         dev = torch.device("cuda:0")
-    for name in ("partial calls", "accumulation cases", "window cases", "update cases",
+    for name in ("partial calls", "accumulation cases", "window cases", "update cases", SKEWED,
                  "staged refusals (float, stride 1: the LDS budget)", STREAM_REFUSALS, AUTO_FAST):
         count(name, 0)
     t0 = time.time()
@@ -481,6 +538,8 @@ def fuzz(cases, seed, out=sys.stdout, device=True):
         if c.k % 50 == 49:
             print("# %d cases, %d failures, %.0f s" % (c.k + 1, len(chk.lines), time.time() - t0), file=out, flush=True)
     runs = sum(v for n, v in by_name.items() if n.startswith(("bwd_data_kernel", "wgrad_kernel", "cpu backward")))
+    if worst is not None:
+        worst.update(chk.worst)
     return runs, chk.lines, by_name
 
 
@@ -489,10 +548,14 @@ def main():
     cases = int(args[0]) if len(args) > 0 else 300
     seed = int(args[1]) if len(args) > 1 else 20261019
     t0 = time.time()
-    ran, lines, by_name = fuzz(cases, seed, device="--cpu" not in sys.argv[1:])
+    worst = {}
+    ran, lines, by_name = fuzz(cases, seed, device="--cpu" not in sys.argv[1:], worst=worst)
     print("cases %d seed %d runs %d failures %d seconds %.0f" % (cases, seed, ran, len(lines), time.time() - t0))
     for n in sorted(by_name):
         print("  %-60s %d" % (n, by_name[n]))
+    print("worst err / bound of the skewed cases, per kernel:")
+    for n in sorted(worst):
+        print("  %-60s %.3g" % (n, worst[n]))
     sys.exit(1 if lines else 0)
 
 

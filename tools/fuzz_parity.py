@@ -2,7 +2,10 @@
 """GPU box: seeded random convolution geometries through every kernel family against the oracle -- wider than the
 suite's randomised tests (strides, dilations, non-square kernels and pads, conv groups, up to 600 channels, skewed
 sparsity, fused ReLU, tilings of batches the inputs do not have).  The oracle (oracle/, the CPU restatement of the
-reference's loop nest) is the checker, as in tests/.
+reference's loop nest) is the checker, as in tests/.  One case in four runs on inputs whose rows, channels and images
+differ in scale by up to 2^48 (tools/error_bound.py skew) and is checked element by element against a float64 reference and
+the derived bound instead of the max-norm; which cases is drawn from a second generator, so a (seed, k) names the same
+geometry and weights as before.
     python tools/fuzz_parity.py [cases] [seed] > gpurun_out/fuzz.txt
 Prints one line per failure (everything needed to rebuild the case) and a summary; exit code 1 on any failure."""
 import os
@@ -13,10 +16,15 @@ import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+for _p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tools")):
+    if _p not in sys.path:
+        sys.path.insert(0, _p)
 import __graft_entry__ as ge  # noqa: E402
+import error_bound as eb  # noqa: E402
 
 TOL = 5e-5
+SKEW_STREAM = 0x5CA1E       # which cases are skewed: RandomState(seed ^ SKEW_STREAM), apart from the generator's own
+SKEWED = "(cases skewed and checked per element)"
 
 
 def rel_err(got, want):
@@ -74,11 +82,15 @@ def dropin_chain(pkg, oracle, synth, dev, s, w, x, k):
     return None
 
 
-def fuzz(cases, seed, out=sys.stdout):
-    """Runs `cases` random geometries; returns (kernel runs, failure lines, runs per kernel name)."""
+def fuzz(cases, seed, out=sys.stdout, worst=None):
+    """Runs `cases` random geometries; returns (kernel runs, failure lines, runs per kernel name).  worst: a dict that
+    receives the largest err / bound of the skewed cases per kernel name."""
     pkg, oracle = ge.load_package(), ge.load_oracle()
     synth = pkg.synth
     rng = np.random.RandomState(seed)
+    rng_skew = np.random.RandomState((seed ^ SKEW_STREAM) & 0xFFFFFFFF)
+    worst = {} if worst is None else worst
+    skewed = 0
     dev = torch.device("cuda:0")
     kernels = {"generic": pkg.KERNEL_GENERIC, "auto": pkg.KERNEL_AUTO, "tiled": pkg.KERNEL_TILED, "jit": pkg.KERNEL_JIT,
                "dense": pkg.KERNEL_DENSE}
@@ -136,6 +148,17 @@ def fuzz(cases, seed, out=sys.stdout):
             if why:
                 report("FAIL drop-in chain %s seed=%d k=%d: %s" % (tuple(s), seed, k, why))
                 failed += 1
+        # one case in four: skewed inputs (after the drop-in chain, which keeps the plain ones), every element of every
+        # kernel's output against the float64 reference within its bound
+        bound = None
+        if rng_skew.randint(4) == 0:
+            sk = eb.skew(s, w, x, b, 9000 + k)
+            w, x, b = sk.w, sk.x, sk.b
+            want = oracle.conv_forward(g, x, w, b, gate=False)
+            if relu:
+                want = np.maximum(want, 0.0)
+            want64, bound = eb.forward_bound(s, w, x, b, relu=relu)
+            skewed += 1
         tb = int(rng.choice([0, 0, 64, 256, 257, 1000])) if cls != 4 else 0
         mlb = int(rng.choice([0, 0, 1])) * (4 * C * H * W * int(rng.randint(3, 60)) + 100)     # sub-batch launches
         desc = pkg.ConvDesc.from_shape(s, fuse_relu=relu)
@@ -209,6 +232,14 @@ def fuzz(cases, seed, out=sys.stdout):
             by_name[name] = by_name.get(name, 0) + 1
             err = rel_err(got, want)
             exact = "generic" in name and not np.array_equal(got, want)
+            if bound is not None and got.shape == want64.shape:
+                ratio, idx = eb.check(got, want64, bound)
+                worst[name] = max(worst.get(name, 0.0), ratio)
+                if not ratio <= 1.0:
+                    report("FAIL bound %s via %s %s tb=%d dist=%s relu=%d seed=%d k=%d: element %s off by %.3g x its bound "
+                           "(row scale 2^%d)" % (kn, name, tuple(s), tb, dist, relu, seed, k, idx, ratio, sk.row_exp[idx[1]]))
+                    failed += 1
+                err = 0.0       # (a skewed case is held to the bound, not to the max-norm)
             if err > TOL or got.shape != want.shape or exact:
                 report("FAIL parity %s via %s %s tb=%d dist=%s relu=%d seed=%d k=%d: rel err %.3g%s" %
                        (kn, name, tuple(s), tb, dist, relu, seed, k, err, " (generic kernel not bit-exact)" if exact else ""))
@@ -219,16 +250,21 @@ def fuzz(cases, seed, out=sys.stdout):
     by_name["(math_functions-level drop-in chains)"] = chains
     by_name["(calls on fewer images than the plan's batch)"] = partial
     by_name["(plans in another Caffe::conv_mode)"] = modes
+    by_name[SKEWED] = skewed
     return ran, lines, by_name
 
 
 def main():
     cases = int(sys.argv[1]) if len(sys.argv) > 1 else 300
     seed = int(sys.argv[2]) if len(sys.argv) > 2 else 20261004
-    ran, lines, by_name = fuzz(cases, seed)
+    worst = {}
+    ran, lines, by_name = fuzz(cases, seed, worst=worst)
     print("cases %d seed %d runs %d failures %d" % (cases, seed, ran, len(lines)))
     for n in sorted(by_name):
         print("  %-60s %d" % (n, by_name[n]))
+    print("worst err / bound of the skewed cases, per kernel:")
+    for n in sorted(worst):
+        print("  %-60s %.3g" % (n, worst[n]))
     sys.exit(1 if lines else 0)
 
 
