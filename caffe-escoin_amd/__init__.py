@@ -23,7 +23,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("ESCOIN_LIB") or os.path.join(_HERE, "libescoin_hip.so")
 
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TILED, KERNEL_DENSE, KERNEL_JIT = 0, 1, 2, 3, 4
-WGRAD_AUTO, WGRAD_ENTRY, WGRAD_STAGED = 0, 1, 2   # option / stat "wgrad_kernel"
+WGRAD_AUTO, WGRAD_ENTRY, WGRAD_STAGED, WGRAD_MFMA = 0, 1, 2, 3   # option / stat "wgrad_kernel"
 CONV_MODE_LOWERED_GEMM, CONV_MODE_LOWERED_SPARSE, CONV_MODE_SCONV, CONV_MODE_SCONV_PAR = 0, 1, 2, 3
 
 # every symbol include/escoin.h declares (tests check the library exports all of them)

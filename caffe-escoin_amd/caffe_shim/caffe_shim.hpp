@@ -92,13 +92,18 @@ class Caffe {
   // batch loop (conv_layer.cpp:41-43); there is no OpenMP runtime here, so the number is a setting
   static int cpu_threads() { return Get().cpu_threads_; }
   static void set_cpu_threads(int n) { Get().cpu_threads_ = n; }
+  // the weight gradient's stage-1 kernel (ESCOIN_WGRAD_*, include/escoin.h option "wgrad_kernel") of the plans layers
+  // create from now on; CPU mode has one weight gradient and ignores it
+  static int wgrad_kernel() { return Get().wgrad_kernel_; }
+  static void set_wgrad_kernel(int k) { Get().wgrad_kernel_ = k; }
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
+  int wgrad_kernel_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -392,6 +397,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       // that was aligned is re-aligned from blobs_[0] on the spot, so Forward keeps working.
       escoin_plan *fresh = nullptr;
       ESCOIN_CHECK(escoin_plan_create(&d, &fresh));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_kernel", Caffe::wgrad_kernel()));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;
@@ -512,6 +518,8 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
   virtual inline int MinTopBlobs() const { return 1; }
   virtual inline bool EqualNumBottomTopBlobs() const { return true; }
   long nnz() const { return plan_ ? escoin_plan_nnz(plan_, -1) : 0; }
+  // a stat of the layer's plan (include/escoin.h escoin_plan_stat), e.g. "wgrad_kernel" after a Backward in GPU mode
+  long plan_stat(const char *key) const { return plan_ ? escoin_plan_stat(plan_, key) : -1; }
   const char *kernel_name() const {
     if (Caffe::mode() == Caffe::CPU) return escoin_cpu_kernel_name();
     return plan_ ? escoin_plan_kernel_name(plan_) : "";

@@ -487,4 +487,26 @@ bool stg_auto_prefers(const Geometry &g, long nnz, const StgPlan &sp, int n_cu) 
   return staged < entry;
 }
 
+bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp) {
+  const escoin_conv_desc &d = g.d;
+  if (is_f64) return false;
+  const double two31 = 2147483648.0;
+  const long lim28 = 1L << 28;
+  if ((double)d.N * g.OH * (double)g.OW >= two31 || (double)d.M * (double)g.kdim >= two31 ||
+      (double)g.Cg * d.H * (double)d.W >= two31)
+    return false;
+  if (d.H >= lim28 || d.W >= lim28 || d.pad_h >= lim28 || d.pad_w >= lim28 || (long)d.dil_h * (d.KH - 1) >= lim28 ||
+      (long)d.dil_w * (d.KW - 1) >= lim28)
+    return false;
+  WgmPlan p;
+  p.mtiles = (g.Mg + p.tile_m - 1) / p.tile_m;
+  p.ktiles = (g.kdim + p.tile_k - 1) / p.tile_k;
+  if ((long)d.group * p.mtiles > 65535 || p.ktiles > 65535) return false;   // grid y, z
+  p.kpad = p.ktiles * p.tile_k;
+  p.chunks = (int)(((long)d.N * g.OH * g.OW + kBwdChunkPixels - 1) / kBwdChunkPixels);
+  p.lds_bytes = kWgmLdsBytes;
+  *wp = p;
+  return true;
+}
+
 }  // namespace escoin

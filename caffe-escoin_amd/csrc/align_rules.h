@@ -129,5 +129,29 @@ struct StgPlan {
 bool stg_plan(const Geometry &g, bool is_f64, int wgrad_channel_block, int n_cu, StgPlan *sp);
 bool stg_auto_prefers(const Geometry &g, long nnz, const StgPlan &sp, int n_cu);
 
+// ---- the fp32-MFMA weight-gradient kernel (wgrad_mfma.hip) ---------------------------------------------------------
+// One workgroup of four waves per (chunk, tile of kWgmTileM output channels of a conv group, tile of kWgmTileK columns
+// of the group's weight matrix); the chunk's pixels go through LDS kWgmStepPixels at a time, double buffered.
+constexpr int kWgmTileM = 64, kWgmTileK = 64;
+constexpr int kWgmStepPixels = 32;                   // pixels per LDS step: 16 k-steps of v_mfma_f32_32x32x2_f32
+constexpr int kWgmLdsRow = kWgmTileM + 1;            // floats per staged pixel row (odd: spreads stores and reads over the banks)
+static_assert(kWgmTileM == kWgmTileK, "the G and the bottom tile share one row length");
+constexpr size_t kWgmLdsBytes = sizeof(float) * 2 * 2 * kWgmStepPixels * kWgmLdsRow;   // 2 buffers x (G tile, bottom tile)
+constexpr size_t kWgmLdsBudget = 64 * 1024;          // what the kernel is compiled for: two workgroups per CU at least
+static_assert(kWgmLdsBytes <= kWgmLdsBudget, "the MFMA weight-gradient tiles exceed their LDS budget");
+
+struct WgmPlan {
+  int tile_m = kWgmTileM, tile_k = kWgmTileK;
+  int mtiles = 0, ktiles = 0;     // tiles per conv group along the output channels / the columns
+  int kpad = 0;                   // columns rounded up to whole tiles: the length of the kernel's ktab
+  int chunks = 0;                 // chunks of the full batch
+  size_t lds_bytes = 0;
+};
+// Whether the MFMA weight-gradient kernel serves this plan, and its tile plan where it does: float plans of any stride,
+// pad, dilation, group count and kernel shape whose indices fit the kernel's 32-bit arithmetic (N*OH*OW, M*Cg*KH*KW and
+// Cg*H*W below 2^31; H, W, the pads and the dilated kernel extent below 2^28; at most 65535 (group, M-tile) pairs and
+// column tiles: the grid).
+bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp);
+
 }  // namespace escoin
 #endif  // ESCOIN_ALIGN_RULES_H_

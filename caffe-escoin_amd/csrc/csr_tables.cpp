@@ -114,6 +114,29 @@ StagedTables staged_tables(const CsrView &v, int icb, int nblk, int cs, int Wp) 
   return t;
 }
 
+WgmTables wgrad_mfma_tables(const CsrView &v, int tile_m, int tile_k) {
+  const Geometry &g = *v.g;
+  const escoin_conv_desc &d = g.d;
+  const int mtiles = (g.Mg + tile_m - 1) / tile_m, ktiles = (g.kdim + tile_k - 1) / tile_k;
+  WgmTables t;
+  t.ent.assign(at_least_one((long)d.M * g.kdim), -1);
+  t.tile_cnt.assign(at_least_one((long)d.group * mtiles * ktiles), 0);
+  for_each_entry(v, [&](const CsrEntry &c) {
+    t.ent[((size_t)c.grp * g.Mg + c.m) * g.kdim + c.col] = (int)c.e;
+    ++t.tile_cnt[((size_t)c.grp * mtiles + c.m / tile_m) * ktiles + c.col / tile_k];
+  });
+  t.ktab.assign(at_least_one(4L * ktiles * tile_k), 0);
+  for (int k = 0; k < g.kdim; ++k) {
+    const Tap tap = decode_tap(k, d.KH, d.KW);
+    const int dy = tap.kr * d.dil_h, dx = tap.kc * d.dil_w;
+    t.ktab[4 * (size_t)k] = (tap.ic * d.H + dy) * d.W + dx;
+    t.ktab[4 * (size_t)k + 1] = dy;
+    t.ktab[4 * (size_t)k + 2] = dx;
+    t.ktab[4 * (size_t)k + 3] = 1;
+  }
+  return t;
+}
+
 bool entry_major(const std::vector<int> &src, const std::vector<unsigned> &off, const std::vector<unsigned char> &buf,
                  long nnz, EntryMajor *out) {
   const size_t n = src.size(), nz = at_least_one(nnz);

@@ -7,7 +7,8 @@
 // Lengths: DeviceBuffer::upload allocates what it is handed, and a kernel argument may not be a null pointer, so the
 // tables that an empty pattern would leave empty are padded to one (zero) element: generic_tables' taps,
 // dense_positions, gather_transpose's ttap.  staged_tables' off is padded by two batches of zeros, which the staged
-// kernel's walk reads ahead into.  The host-side lists (tsrc) have exactly nnz elements.
+// kernel's walk reads ahead into.  wgrad_mfma_tables' ent has M * kdim elements whatever the pattern.  The host-side
+// lists (tsrc) have exactly nnz elements.
 #ifndef ESCOIN_CSR_TABLES_H_
 #define ESCOIN_CSR_TABLES_H_
 
@@ -91,6 +92,16 @@ ForwardTranspose forward_transpose(const CsrView &v);
 // inside the staged block's LDS tile, (icl % icb) * cs + kr * dil_h * Wp + kc * dil_w, then zeros.
 struct StagedTables { std::vector<int> blk, off; };
 StagedTables staged_tables(const CsrView &v, int icb, int nblk, int cs, int Wp);
+
+// The MFMA weight-gradient kernel's tables for tiles of tile_m output channels x tile_k columns, mtiles x ktiles per conv
+// group: ent [max(M * kdim, 1)], ent[(grp * Mg + m) * kdim + col] = the flat index of the CSR entry at that (row, column),
+// -1 where the pattern has none -- the inverse of dense_positions(v, kdim); tile_cnt [group * mtiles * ktiles], the
+// entries inside tile (grp, mt, kt) at [(grp * mtiles + mt) * ktiles + kt] (a workgroup whose tile holds none leaves at
+// once); ktab [4 * ktiles * tile_k], the im2col decode of column k as four ints: the element offset of its tap inside a
+// conv group's image (ic * H + kr * dil_h) * W + kc * dil_w, dy = kr * dil_h, dx = kc * dil_w, 1; the columns at or
+// past kdim (the last tile's padding) carry {0, 0, 0, 0}: "no such column".
+struct WgmTables { std::vector<int> ent, tile_cnt, ktab; };
+WgmTables wgrad_mfma_tables(const CsrView &v, int tile_m, int tile_k);
 
 // A scatter list (destination k: CSR entry src[k], element off[k] of buffer buf[k]) entry-major: entry e's destinations
 // are e_off[k] / e_buf[k] for k in [e_ptr[e], e_ptr[e + 1]), in the order of the list.  e_ptr [max(nnz, 1) + 1], e_off

@@ -71,6 +71,7 @@ DeviceBytes device_bytes(const escoin_plan *p) {
     b.upd = u->src.bytes() + u->off.bytes() + u->buf.bytes() + u->wpos.bytes() + u->stage.bytes() + u->e_ptr.bytes() + u->e_off.bytes() + u->e_buf.bytes();
   if (const BwdState *s = p->bwd.get())
     b.bwd = s->trow.bytes() + s->ttap.bytes() + s->tval.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() + s->stg_blk.bytes() + s->stg_off.bytes() +
+            s->wgm_ent.bytes() + s->wgm_cnt.bytes() + s->wgm_ktab.bytes() +
             (s->tplan ? device_bytes(s->tplan.get()).fwd : 0);
   return b;
 }
@@ -87,7 +88,10 @@ long bwd_stat(const escoin_plan *p, const char *key) {
     if (!s || !s->last_wgrad) return fail(ESCOIN_ESTATE, "wgrad_kernel: no weight / bias gradient has run on this alignment");
     return s->last_wgrad;
   }
-  if (!strcmp(key, "wgrad_lds_bytes")) return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg_lds_bytes : 0;
+  if (!strcmp(key, "wgrad_lds_bytes")) {
+    if (s && s->wgrad == ESCOIN_WGRAD_MFMA) return (long)s->wgm_lds_bytes;
+    return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg_lds_bytes : 0;
+  }
   if (!strcmp(key, "bwd_align_us")) return s ? (long)(s->align_ms * 1e3) : 0;
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
@@ -389,7 +393,10 @@ int escoin_plan_destroy(escoin_plan *plan) {
 int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
   return guarded([&]() -> int {
     if (!p || !key) return fail(ESCOIN_EINVAL, "null argument");
-    if (p->aligned && strcmp(key, "conv_mode") != 0 && strcmp(key, "cpu_channel_block") != 0 && strcmp(key, "cpu_images_per_job") != 0)
+    // ("wgrad_kernel" on an aligned plan: read when the next backward state is built -- after a refused forced kernel, or
+    //  after the next align; a state that exists keeps its kernel)
+    if (p->aligned && strcmp(key, "conv_mode") != 0 && strcmp(key, "cpu_channel_block") != 0 && strcmp(key, "cpu_images_per_job") != 0 &&
+        strcmp(key, "wgrad_kernel") != 0)
       return fail(ESCOIN_ESTATE, "this option must be set before weight_align/set_csr");
     if (!strcmp(key, "tiling_batch")) {
       if (value < 0) return fail(ESCOIN_EINVAL, "tiling_batch must be >= 0");
@@ -428,7 +435,7 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       return ESCOIN_OK;
     }
     if (!strcmp(key, "wgrad_kernel")) {
-      if (value < ESCOIN_WGRAD_AUTO || value > ESCOIN_WGRAD_STAGED) return fail(ESCOIN_EINVAL, "wgrad_kernel must be 0 (auto), 1 (entry) or 2 (staged)");
+      if (value < ESCOIN_WGRAD_AUTO || value > ESCOIN_WGRAD_MFMA) return fail(ESCOIN_EINVAL, "wgrad_kernel must be 0 (auto), 1 (entry), 2 (staged) or 3 (mfma)");
       p->wgrad_kernel = value;
       return ESCOIN_OK;
     }

@@ -94,6 +94,12 @@ struct BwdState {
   size_t stg_lds_bytes = 0;
   DeviceBuffer stg_blk;  // [M][stg_nblk + 1] absolute entry index where output channel oc's entries of block b begin
   DeviceBuffer stg_off;  // [nnz] per CSR entry: its tap's float offset inside the staged block's LDS tile
+  // weight gradient, fp32-MFMA kernel (wgrad_mfma.hip; the tables: csr_tables.h wgrad_mfma_tables)
+  int wgm_mtiles = 0, wgm_ktiles = 0;  // tiles per conv group along the output channels / the columns
+  size_t wgm_lds_bytes = 0;
+  DeviceBuffer wgm_ent;   // [M * kdim] (row, column) -> CSR entry, -1: none
+  DeviceBuffer wgm_cnt;   // [group * mtiles * ktiles] entries per tile
+  DeviceBuffer wgm_ktab;  // [4 * ktiles * tile_k] the im2col decode of a column
   double align_ms = 0.0;
   // host: per entry of the transposed order (tplan's CSR, or ttap / tval) the index of the plan's CSR entry (groups
   // concatenated) it is a copy of -- how escoin_update_values reaches the backward state's values (update_values.hip)
@@ -323,6 +329,12 @@ const char *dense_kernel_name();
 int dense_build_ktab(escoin_plan *p, hipStream_t stream);
 int dense_lda(int K);          // floats per row of d_dense_w (K rounded up to whole k-steps)
 int dense_spare_rows();       // zero rows after row M - 1
+
+// wgrad_mfma.hip (option "wgrad_kernel" = MFMA): builds the kernel's tables into the backward state; stage 1 of the
+// weight gradient over `chunks` chunks of n_images images into slab_w [chunks][nnz]
+int wgm_build(escoin_plan *p, BwdState *s, hipStream_t stream);
+int launch_wgrad_mfma(const escoin_plan *p, const BwdState *s, const float *bottom, const float *top,
+                      const float *top_diff, float *slab_w, int n_images, int chunks, hipStream_t stream);
 
 // Index of the k-th set bit of `mask` (k < popcount): blockIdx -> conv group when only some groups
 // of a layer run in a launch.  Wave-uniform scalar code on the device.

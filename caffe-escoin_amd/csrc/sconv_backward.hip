@@ -24,6 +24,8 @@
 //                                        into a slab with plain stores;
 //     escoin_sconv_wgrad_sum_kernel      one lane per entry (and per bias): its slab column summed in chunk order, the
 //                                        total added into weight_diff / bias_diff.  Every position has one owner.
+//     (option "wgrad_kernel": stage 1 by the LDS-staged kernel below, or by the fp32-MFMA kernel of wgrad_mfma.hip -- same
+//     chunks, same slab; the MFMA kernel's bias gradient is the entry kernel's, launched for the bias alone)
 //
 // The backward state (transposed CSR or transposed plan, slab, ReLU scratch) is built by the first backward on an
 // aligned plan -- its index tables by the host-only builders of csr_tables.h, this file uploads them -- and dropped with the device side (free_device: weight_align / set_csr / import_aligned; destroy); later
@@ -563,6 +565,10 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   if (p->wgrad_kernel == ESCOIN_WGRAD_STAGED && !staged_ok)
     return fail(ESCOIN_EINVAL, "wgrad_kernel: the staged weight-gradient kernel needs a float plan with stride 1 whose "
                                "chunk tile of one input channel fits the LDS budget; only the entry kernel serves this plan");
+  WgmPlan wp;
+  if (p->wgrad_kernel == ESCOIN_WGRAD_MFMA && !wgm_plan(g, p->is_f64, &wp))
+    return fail(ESCOIN_EINVAL, "wgrad_kernel: the MFMA weight-gradient kernel needs a float plan whose pixel, weight and "
+                               "image indices fit 31 bits; the entry kernel serves this plan");
   p->bwd.reset(new BwdState());
   BwdState *s = p->bwd.get();
   s->nnz = plan_nnz(p);
@@ -585,7 +591,12 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   const size_t slab = sizeof(T) * (size_t)s->chunks_max * (size_t)(s->nnz + d.M);
   ESCOIN_HIP_TRY(s->slab.alloc(slab));
   s->wgrad = ESCOIN_WGRAD_ENTRY;
-  if (staged_ok && (p->wgrad_kernel == ESCOIN_WGRAD_STAGED ||
+  if (p->wgrad_kernel == ESCOIN_WGRAD_MFMA) {
+    if constexpr (sizeof(T) == 4) {
+      if ((rc = wgm_build(p, s, stream)) != ESCOIN_OK) return rc;
+      s->wgrad = ESCOIN_WGRAD_MFMA;
+    }
+  } else if (staged_ok && (p->wgrad_kernel == ESCOIN_WGRAD_STAGED ||
                     (p->wgrad_kernel == ESCOIN_WGRAD_AUTO && stg_auto_prefers(g, s->nnz, sp, tiled_device_cus())))) {
     if ((rc = stg_build(p, s, sp, stream)) != ESCOIN_OK) return rc;
     s->wgrad = ESCOIN_WGRAD_STAGED;
@@ -700,6 +711,31 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
         if (items > 0) {
           hipLaunchKernelGGL(escoin_sconv_wgrad_tree_sum_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, stream,
                              slab_w, slab_b, wpos, weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
+          ESCOIN_HIP_TRY(hipGetLastError());
+        }
+        return ESCOIN_OK;
+      }
+      if (s->wgrad == ESCOIN_WGRAD_MFMA) {
+        // weights: the MFMA kernel's partials, then the tree sum; bias: the entry kernel's bias-only stage 1 and its
+        // serial stage 2 -- the entry kernel's bias bits
+        if (weight_diff) {
+          const int rc = launch_wgrad_mfma(p, s, bottom, top, top_diff, slab_w, n_images, chunks, stream);
+          if (rc != ESCOIN_OK) return rc;
+          if (s->nnz > 0) {
+            hipLaunchKernelGGL(escoin_sconv_wgrad_tree_sum_kernel, dim3((unsigned)((s->nnz + 15) / 16)), dim3(256), 0, stream,
+                               slab_w, slab_b, wpos, weight_diff, (float *)nullptr, (int)s->nnz, d.M, chunks);
+            ESCOIN_HIP_TRY(hipGetLastError());
+          }
+        }
+        if (bias_diff) {
+          if (d.M > 65535) return fail(ESCOIN_EINVAL, "backward: more than 65535 output channels");
+          a.want_w = 0;
+          const dim3 bgrid(chunks, d.M), bblock(64 * kBwdWaves);
+          if (relu) hipLaunchKernelGGL(escoin_sconv_wgrad_partial_kernel<true>, bgrid, bblock, 0, stream, a);
+          else hipLaunchKernelGGL(escoin_sconv_wgrad_partial_kernel<false>, bgrid, bblock, 0, stream, a);
+          ESCOIN_HIP_TRY(hipGetLastError());
+          hipLaunchKernelGGL(escoin_sconv_wgrad_sum_kernel, dim3((unsigned)((d.M + 255) / 256)), dim3(256), 0, stream, slab_w,
+                             slab_b, wpos, (float *)nullptr, bias_diff, (int)s->nnz, d.M, chunks);
           ESCOIN_HIP_TRY(hipGetLastError());
         }
         return ESCOIN_OK;

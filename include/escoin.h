@@ -118,7 +118,9 @@ ESCOIN_API long escoin_padded_len(const escoin_conv_desc *desc);
 ESCOIN_API int escoin_plan_create(const escoin_conv_desc *desc, escoin_plan **plan);
 ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
 
-/* Options (all but "conv_mode", "cpu_channel_block" and "cpu_images_per_job" must precede weight_align / set_csr):
+/* Options (all but "conv_mode", "cpu_channel_block", "cpu_images_per_job" and "wgrad_kernel" must precede weight_align /
+ * set_csr; "wgrad_kernel" set on an aligned plan is read when the next backward state is built: by the first backward
+ * after the next align, or -- when none has run on this alignment, e.g. after a refused forced kernel -- by the next one):
  *   "kernel"     = ESCOIN_KERNEL_*;
  *   "conv_mode"  = Caffe::ConvMode (common.hpp:112; tools/caffe.cpp:292-301 -conv_mode N):
  *                  SCONV / SCONV_PAR = the direct sparse path (the two differ only in the
@@ -430,13 +432,27 @@ ESCOIN_API int escoin_cpu_sparse_dense2csr_f64(int M, int N, const double *A, do
  * two kernels -- a function of the geometry, nnz and the device's CU count, never a timing -- has it faster (the model,
  * its fit and its measurements: profiles/backward_mi355x.md).  The two kernels sum in different orders: the low bits of the gradient differ between
  * them, each is deterministic.  The chunks and the slab are the same ("bwd_chunks" keeps its meaning).
+ * ESCOIN_WGRAD_MFMA = escoin_sconv_wgrad_mfma_kernel, for layers kept dense (conv1, dense 1x1 layers, groups the forward
+ * sends to its MFMA kernel): one workgroup per (chunk, 64 output channels of a conv group, 64 columns of its Cg*KH*KW
+ * weight matrix) multiplies G[64 x pixels] by the im2col view of the bottom [pixels x 64] on the fp32 matrix cores
+ * (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 sums), 32 pixels per LDS step, and writes the tile's elements that
+ * are CSR entries to the slab; tiles without entries do no work; then escoin_sconv_wgrad_tree_sum_kernel.  Never chosen by
+ * AUTO.  It serves float plans of any stride, pad, dilation, group count and kernel shape with N*OH*OW, M*Cg*KH*KW and
+ * Cg*H*W below 2^31 (H, W, pads and dilated kernel extents below 2^28), at most 65535 (group, 64-channel tile) pairs and
+ * 65535 column tiles; forcing it on a double plan or
+ * outside these makes the first backward fail with ESCOIN_EINVAL.  Sum order: per (chunk, entry) the chunk's live
+ * pixels ascending, 32 per step and two per matrix instruction, then the chunks by the tree sum -- a function of the
+ * geometry and n_images only; its low bits differ from the other two kernels'.  Only CSR positions are written (a NaN
+ * elsewhere stays NaN, explicit zeros receive their gradient).  Its bias gradient is the entry kernel's, bit for bit:
+ * escoin_sconv_wgrad_partial_kernel launched for the bias alone, then escoin_sconv_wgrad_sum_kernel.
  * Option "wgrad_channel_block" (test option, before the align): 0 = as many input channels per staged block as the
  * LDS budget holds, n = at most n.  Results do not depend on it.
- * Stats: "wgrad_kernel" (ESCOIN_WGRAD_ENTRY / _STAGED: what the last weight / bias gradient ran; ESCOIN_ESTATE before
- * the first one), "wgrad_lds_bytes" (LDS of a staged workgroup; 0 on the entry kernel). */
+ * Stats: "wgrad_kernel" (ESCOIN_WGRAD_ENTRY / _STAGED / _MFMA: what the last weight / bias gradient ran; ESCOIN_ESTATE
+ * before the first one), "wgrad_lds_bytes" (LDS of a staged or an MFMA workgroup; 0 on the entry kernel). */
 #define ESCOIN_WGRAD_AUTO 0
 #define ESCOIN_WGRAD_ENTRY 1   /* escoin_sconv_wgrad_partial_kernel: one workgroup per (chunk, output channel) */
 #define ESCOIN_WGRAD_STAGED 2  /* escoin_sconv_wgrad_staged_kernel: the chunk's bottom staged in LDS */
+#define ESCOIN_WGRAD_MFMA 3    /* escoin_sconv_wgrad_mfma_kernel: G x im2col(bottom) on the fp32 matrix cores */
 ESCOIN_API int escoin_backward(escoin_plan *plan, const float *bottom_dev, const float *top_dev, const float *top_diff_dev,
                     float *bottom_diff_dev, float *weight_diff_dev, float *bias_diff_dev, int n_images, void *stream);
 ESCOIN_API int escoin_backward_f64(escoin_plan *plan, const double *bottom_dev, const double *top_dev,

@@ -2,14 +2,16 @@
 """Backward on the MI355X: per layer, forward / data-gradient / weight-gradient / bias-gradient time of the
 pattern-preserving backward (escoin_backward), the kernels that ran, and the same shapes through torch's dense conv
 backward (MIOpen, dense weights) as a comparison point.  The weight gradient is timed three ways in the same call, on
-separate plans: option wgrad_kernel = ENTRY, = STAGED (skipped where the staged kernel does not serve the plan) and the
-default AUTO; the compact entry point (escoin_backward_values) on the AUTO plan.
+separate plans: option wgrad_kernel = ENTRY, = STAGED (skipped where the staged kernel does not serve the plan), = MFMA
+and the default AUTO; the compact entry point (escoin_backward_values) on the AUTO plan.
 
 Sets: the four ResNet-50 3x3 shapes @90 % (batch 256), the GoogLeNet 1x1 layers @95 % (batch 256), AlexNet conv2-5
-@80 % (batch 128).  Times are device events around `--reps` back-to-back calls after a warm-up, the median of
-`--regions` regions, per call.  Prints one JSON line (and progress on stderr).
+@80 % (batch 128); "chain": the layers the forward keeps dense -- the distinct 1x1 shapes and the four 3x3 shapes of the
+ResNet-50 chain at batch 256 and density 1.0, conv1 of AlexNet (11x11 stride 4) and of ResNet-50 (7x7 stride 2); "sweep":
+res2_branch2b, res5_branch2b and the chain's res4_branch2c at densities 1.0 / 0.5 / 0.3 / 0.2 / 0.1.  Times are device
+events around `--reps` back-to-back calls after a warm-up, the median of `--regions` regions, per call.  Prints one JSON line (and progress on stderr).
 
-    python tools/backward_bench.py [--sets resnet,googlenet,alexnet] [--regions 7] [--reps 5] [--no-torch]
+    python tools/backward_bench.py [--sets resnet,googlenet,alexnet,chain,sweep] [--regions 7] [--reps 5] [--no-torch]
 """
 import argparse
 import json
@@ -25,7 +27,40 @@ FAMILY = {0: "auto", 1: "gather (escoin_sconv_bwd_data_kernel)", 2: "tiled (tran
           3: "dense MFMA (transposed plan)", 4: "generated code (transposed plan)"}
 
 
-WGRAD = {1: "entry", 2: "staged"}
+WGRAD = {1: "entry", 2: "staged", 3: "mfma"}
+SWEEP = (1.0, 0.5, 0.3, 0.2, 0.1)
+
+
+def chain_layers(synth, N=256):
+    """The layers of the ResNet-50 chain (tools/caffe_test.py --model resnet50_chain) at density 1.0, one per distinct
+    shape, then the two conv1 layers."""
+    out, seen = [], set()
+    cin, hw = 64, 56
+    for si, (mid, cout, blocks, stride) in enumerate([(64, 256, 3, 1), (128, 512, 4, 2), (256, 1024, 6, 2), (512, 2048, 3, 2)]):
+        for b in range(blocks):
+            st = stride if b == 0 else 1
+            tag = "res%d%s" % (si + 2, "abcdef"[b])
+            ohw = hw // st
+            cand = [(tag + "_branch2a", cin, hw, mid, 1, dict(stride=st)), (tag + "_branch2b", mid, ohw, mid, 3, dict(pad=1)),
+                    (tag + "_branch2c", mid, ohw, cout, 1, {})]
+            if b == 0:
+                cand.insert(0, (tag + "_branch1", cin, hw, cout, 1, dict(stride=st)))
+            for name, c, h, m, k, kw in cand:
+                key = (c, h, m, k, tuple(sorted(kw.items())))
+                if key not in seen:
+                    seen.add(key)
+                    out.append(synth.shape(name, N, c, h, h, m, k, bias=False, sparsity=0.0, **kw))
+            cin, hw = cout, ohw
+    out.append(synth.shape("alex_conv1", 128, 3, 227, 227, 96, 11, stride=4, sparsity=0.0))
+    out.append(synth.shape("resnet_conv1", N, 3, 224, 224, 64, 7, pad=3, stride=2, sparsity=0.0))
+    return out
+
+
+def sweep_layers(synth, N=256):
+    base = [("res2_branch2b", 64, 56, 64, 3, dict(pad=1)), ("res5_branch2b", 512, 7, 512, 3, dict(pad=1)),
+            ("res4_branch2c", 256, 14, 1024, 1, {})]
+    return [synth.shape("%s@%.1f" % (name, d), N, c, h, h, m, k, bias=False, sparsity=1.0 - d, **kw)
+            for name, c, h, m, k, kw in base for d in SWEEP]
 
 
 def timed(fn, regions, reps):
@@ -71,6 +106,10 @@ def main():
         layers += synth.googlenet_1x1(N=256, sparsity=0.95)
     if "alexnet" in sets:
         layers += synth.alexnet(N=128, sparsity=0.8)
+    if "chain" in sets:
+        layers += chain_layers(synth)
+    if "sweep" in sets:
+        layers += sweep_layers(synth)
     rows = []
     for i, s in enumerate(layers):
         w = synth.pruned_weights(s, 1000 + i)
@@ -96,14 +135,14 @@ def main():
         r["wgrad_lds_bytes"] = plan.stat("wgrad_lds_bytes")
         vd = torch.zeros((plan.nnz(),), device=dev)
         r["bwd_values_us"] = timed(lambda: plan.backward(td, bottom=x, bottom_diff=None, values_diff=vd), a.regions, a.reps)
-        for kid in (pkg.WGRAD_ENTRY, pkg.WGRAD_STAGED):
+        for kid in (pkg.WGRAD_ENTRY, pkg.WGRAD_STAGED, pkg.WGRAD_MFMA):
             forced = pkg.Plan(pkg.ConvDesc.from_shape(s), wgrad_kernel=kid)
             forced.weight_align(w)
             key = "bwd_weight_%s" % WGRAD[kid]
             try:
                 forced.backward(td, bottom=x, bottom_diff=None, weight_diff=wd)
             except pkg.EscoinError:
-                r[key + "_us"] = None          # the staged kernel does not serve this plan
+                r[key + "_us"] = None          # the forced kernel does not serve this plan
                 forced.close()
                 continue
             regions = timed_regions(lambda: forced.backward(td, bottom=x, bottom_diff=None, weight_diff=wd), a.regions, a.reps)
@@ -111,6 +150,10 @@ def main():
             r[key + "_spread_us"] = [regions[0], regions[-1]]
             r["bwd_bias_%s_us" % WGRAD[kid]] = timed(lambda: forced.backward(td, bottom_diff=None, bias_diff=bsd), a.regions, a.reps)
             forced.close()
+        r["mfma_over_fwd"] = round(r["bwd_weight_mfma_us"] / r["fwd_us"], 3)
+        # the MFMA kernel multiplies the whole M x Kd tile grid whatever the density: its rate on the dense problem
+        r["mfma_dense_tflops"] = round(2.0 * s.N * plan.out_hw[0] * plan.out_hw[1] * s.M * (s.C // s.group) * s.KH * s.KW /
+                                       (r["bwd_weight_mfma_us"] * 1e-6) / 1e12, 2)
         r["data_over_fwd"] = round(r["bwd_data_us"] / r["fwd_us"], 3)
         r["weight_over_fwd"] = round(r["bwd_weight_us"] / r["fwd_us"], 3)
         if not a.no_torch:
@@ -121,9 +164,9 @@ def main():
             r["torch_weight_us"] = timed(lambda: conv_bwd(td, x, wdense, None, *args, [False, True, False]), a.regions, a.reps)
         plan.close()
         rows.append(r)
-        print("%-28s fwd %8.1f  data %8.1f  weight %8.1f (%s; entry %s staged %s; compact %.1f)  bias %7.1f us  [%s]%s" % (
+        print("%-28s fwd %8.1f  data %8.1f  weight %8.1f (%s; entry %s staged %s mfma %.1f; compact %.1f)  bias %7.1f us  [%s]%s" % (
             s.name, r["fwd_us"], r["bwd_data_us"], r["bwd_weight_us"], r["wgrad_kernel"],
-            "%.1f" % r["bwd_weight_entry_us"], "-" if r["bwd_weight_staged_us"] is None else "%.1f" % r["bwd_weight_staged_us"],
+            "%.1f" % r["bwd_weight_entry_us"], "-" if r["bwd_weight_staged_us"] is None else "%.1f" % r["bwd_weight_staged_us"], r["bwd_weight_mfma_us"],
             r["bwd_values_us"], r["bwd_bias_us"], r["bwd_data_kernel"],
             "" if a.no_torch else "  torch data %8.1f weight %8.1f" % (r["torch_data_us"], r["torch_weight_us"])),
             file=sys.stderr, flush=True)

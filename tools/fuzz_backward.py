@@ -40,7 +40,7 @@ Case = namedtuple("Case", "k cls s dist relu tb mlb f64 accumulate n_part window
 
 DATA_KERNELS = ("auto", "generic", "tiled", "jit", "dense")
 KERNEL_NAMES = {0: "auto", 1: "generic", 2: "tiled", 3: "dense", 4: "jit"}
-WGRAD_NAMES = {0: "auto", 1: "entry", 2: "staged"}
+WGRAD_NAMES = {0: "auto", 1: "entry", 2: "staged", 3: "mfma"}
 
 
 # ---- generator and geometry predicates (no device, no library) --------------------------------------------------------
@@ -384,6 +384,7 @@ def _device_case(pkg, synth, torch, dev, c, chk, count):
     runs = [(kn, "auto", True) for kn in data_kernels(c)]
     runs[1] = ("generic", "entry", True)
     runs.append(("generic", "staged", False))
+    runs.append(("generic", "mfma", False))
     top_np = None
     for kn, wk, want_bd in runs:
         kernel = getattr(pkg, "KERNEL_" + kn.upper())
@@ -407,6 +408,9 @@ def _device_case(pkg, synth, torch, dev, c, chk, count):
                 if wk == "staged":
                     if staged_candidate(c):
                         count("staged refusals (float, stride 1: the LDS budget)", 1)
+                    continue
+                if wk == "mfma" and c.f64:
+                    count("mfma refusals (double plans)", 1)
                     continue
                 fast = kn in ("tiled", "jit", "dense")
                 if fast and (not transposable(c) or (kn != "dense" and not tiled_admits(synth, c))):
