@@ -96,14 +96,19 @@ class Caffe {
   // create from now on; CPU mode has one weight gradient and ignores it
   static int wgrad_kernel() { return Get().wgrad_kernel_; }
   static void set_wgrad_kernel(int k) { Get().wgrad_kernel_ = k; }
+  // the data gradient's kernel (ESCOIN_KERNEL_* or ESCOIN_BWD_MFMA, include/escoin.h option "backward_kernel") of the
+  // plans layers create from now on; CPU mode has one data gradient and ignores it
+  static int backward_kernel() { return Get().backward_kernel_; }
+  static void set_backward_kernel(int k) { Get().backward_kernel_ = k; }
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
   int wgrad_kernel_;
+  int backward_kernel_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -398,6 +403,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       escoin_plan *fresh = nullptr;
       ESCOIN_CHECK(escoin_plan_create(&d, &fresh));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_kernel", Caffe::wgrad_kernel()));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "backward_kernel", Caffe::backward_kernel()));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;

@@ -509,4 +509,46 @@ bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp) {
   return true;
 }
 
+bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp) {
+  const escoin_conv_desc &d = g.d;
+  if (is_f64) return false;
+  const double two31 = 2147483648.0;
+  const long lim28 = 1L << 28;
+  if ((double)d.N * d.H * (double)d.W >= two31 || (double)g.Mg * g.OH * (double)g.OW >= two31) return false;
+  if (d.H >= lim28 || d.W >= lim28 || d.pad_h >= lim28 || d.pad_w >= lim28 || (long)d.dil_h * (d.KH - 1) >= lim28 ||
+      (long)d.dil_w * (d.KW - 1) >= lim28)
+    return false;
+  DgmPlan p;
+  p.phases_h = d.stride_h;
+  p.phases_w = d.stride_w;
+  p.ctiles = (g.Cg + p.tile_c - 1) / p.tile_c;
+  if ((long)d.stride_h * d.stride_w > 65535 || (long)d.group * p.ctiles > 65535) return false;   // grid y, z
+  if ((double)d.stride_h * d.stride_w * (double)d.group * p.ctiles >= two31) return false;        // the live lists' index
+  // one axis of the split: the residue's first pixel, its pixel count and its taps
+  auto axis = [](int r, int size, int pad, int stride, int dil, int K, int *first, int *count, int *taps) {
+    *first = ((r - pad) % stride + stride) % stride;
+    *count = *first < size ? (size - *first + stride - 1) / stride : 0;
+    *taps = 0;
+    for (int k = 0; k < K; ++k) *taps += (int)((long)k * dil % stride == r);
+  };
+  p.phase.resize((size_t)d.stride_h * d.stride_w);
+  for (int rh = 0; rh < d.stride_h; ++rh)
+    for (int rw = 0; rw < d.stride_w; ++rw) {
+      DgmPhase &ph = p.phase[(size_t)rh * d.stride_w + rw];
+      axis(rh, d.H, d.pad_h, d.stride_h, d.dil_h, d.KH, &ph.h0, &ph.rows, &ph.taps_h);
+      axis(rw, d.W, d.pad_w, d.stride_w, d.dil_w, d.KW, &ph.w0, &ph.cols, &ph.taps_w);
+      ph.kp = g.Mg * ph.taps_h * ph.taps_w;
+      ph.ksteps = (ph.kp + p.step_k - 1) / p.step_k;
+      ph.tiles = ((long)d.N * ph.rows * ph.cols + p.tile_p - 1) / p.tile_p;
+      p.tiles_max = std::max(p.tiles_max, ph.tiles);
+      p.cols_total += (long)ph.ksteps * p.step_k;
+    }
+  const double mat = (double)d.group * p.ctiles * p.tile_c * (double)p.cols_total;
+  if (mat >= two31) return false;
+  p.mat_floats = (long)mat;
+  p.lds_bytes = kDgmLdsBytes;
+  *dp = p;
+  return true;
+}
+
 }  // namespace escoin

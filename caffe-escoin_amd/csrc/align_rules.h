@@ -153,5 +153,41 @@ struct WgmPlan {
 // column tiles: the grid).
 bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp);
 
+// ---- the fp32-MFMA data-gradient kernel (dgrad_mfma.hip) -----------------------------------------------------------
+// The bottom pixels split into stride_h x stride_w phases ((h + pad_h) % stride_h, (w + pad_w) % stride_w); inside a phase
+// every pixel has the same contributing taps, so a phase is a stride-1 implicit GEMM.  One workgroup of four waves per
+// (phase, tile of kDgmTileP phase pixels, (conv group, tile of kDgmTileC input channels)); the phase's columns (output
+// channel, tap) go through LDS kDgmStepK at a time, double buffered.  The geometry is the weight-gradient kernel's.
+constexpr int kDgmTileC = kWgmTileM, kDgmTileP = kWgmTileK;
+constexpr int kDgmStepK = kWgmStepPixels;            // columns per LDS step: 16 k-steps of v_mfma_f32_32x32x2_f32
+constexpr int kDgmLdsRow = kWgmLdsRow;               // floats per staged column (odd, as in the weight-gradient kernel)
+constexpr size_t kDgmLdsBytes = sizeof(float) * 2 * 2 * kDgmStepK * kDgmLdsRow;   // 2 buffers x (weight block, G block)
+constexpr size_t kDgmLdsBudget = 64 * 1024;
+static_assert(kDgmLdsBytes <= kDgmLdsBudget, "the MFMA data-gradient tiles exceed their LDS budget");
+
+// One phase: the bottom pixels (h0 + stride_h * hh, w0 + stride_w * ww), hh < rows, ww < cols, and its taps.
+struct DgmPhase {
+  int h0 = 0, w0 = 0, rows = 0, cols = 0;
+  int taps_h = 0, taps_w = 0;     // kernel rows / columns with kr * dil_h % stride_h == the phase's row residue (columns likewise)
+  int kp = 0;                     // Mg * taps_h * taps_w: the phase's columns
+  int ksteps = 0;                 // kp in whole steps
+  long tiles = 0;                 // pixel tiles of the full batch: ceil(N * rows * cols / kDgmTileP)
+};
+struct DgmPlan {
+  int tile_c = kDgmTileC, tile_p = kDgmTileP, step_k = kDgmStepK;
+  int phases_h = 0, phases_w = 0;       // = stride_h, stride_w; phase index = residue_h * phases_w + residue_w
+  int ctiles = 0;                       // channel tiles per conv group
+  long tiles_max = 0;                   // the longest phase's pixel tiles (grid x of the full batch)
+  long cols_total = 0;                  // sum of ksteps * step_k over the phases: the length of the column decode table
+  long mat_floats = 0;                  // the phase matrices: group * ctiles * tile_c * cols_total
+  size_t lds_bytes = 0;
+  std::vector<DgmPhase> phase;          // [phases_h * phases_w]
+};
+// Whether the MFMA data-gradient kernel serves this plan, and its tile plan where it does: float plans of any stride,
+// pad, dilation, group count and kernel shape whose indices fit the kernel's 32-bit arithmetic (N*H*W, Mg*OH*OW and the
+// phase matrices' floats below 2^31; H, W, the pads and the dilated kernel extent below 2^28; at most 65535 phases and
+// 65535 (group, channel tile) pairs: the grid's y and z; fewer than 2^31 (group, phase, channel tile) triples).
+bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp);
+
 }  // namespace escoin
 #endif  // ESCOIN_ALIGN_RULES_H_

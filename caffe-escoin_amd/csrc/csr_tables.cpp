@@ -137,6 +137,74 @@ WgmTables wgrad_mfma_tables(const CsrView &v, int tile_m, int tile_k) {
   return t;
 }
 
+DgmTables dgrad_mfma_tables(const CsrView &v, const DgmPlan &plan) {
+  const Geometry &g = *v.g;
+  const escoin_conv_desc &d = g.d;
+  const int P = plan.phases_h * plan.phases_w;
+  const long opix = (long)g.OH * g.OW;
+  DgmTables t;
+  t.phase.assign(8 * (size_t)P, 0);
+  t.tap_ptr.assign((size_t)P + 1, 0);
+  // a tap's rank among the taps of its residue, per axis: its place in the phase's ascending tap list
+  std::vector<int> rank_h(d.KH), rank_w(d.KW);
+  for (int kr = 0; kr < d.KH; ++kr) {
+    rank_h[kr] = 0;
+    for (int q = 0; q < kr; ++q) rank_h[kr] += (int)((long)q * d.dil_h % d.stride_h == (long)kr * d.dil_h % d.stride_h);
+  }
+  for (int kc = 0; kc < d.KW; ++kc) {
+    rank_w[kc] = 0;
+    for (int q = 0; q < kc; ++q) rank_w[kc] += (int)((long)q * d.dil_w % d.stride_w == (long)kc * d.dil_w % d.stride_w);
+  }
+  t.col.assign(at_least_one(4 * plan.cols_total), 0);
+  std::vector<int> col0((size_t)P, 0);
+  long cols = 0;
+  for (int ph = 0; ph < P; ++ph) {
+    const DgmPhase &f = plan.phase[(size_t)ph];
+    const int rh = ph / plan.phases_w, rw = ph - rh * plan.phases_w;
+    const int ntaps = f.taps_h * f.taps_w;
+    col0[(size_t)ph] = (int)cols;
+    int *row = t.phase.data() + 8 * (size_t)ph;
+    row[0] = f.h0, row[1] = f.w0, row[2] = f.rows, row[3] = f.cols, row[4] = f.kp, row[5] = f.ksteps, row[6] = (int)cols, row[7] = ntaps;
+    for (int kr = 0; kr < d.KH; ++kr)
+      for (int kc = 0; kc < d.KW; ++kc) {
+        if ((long)kr * d.dil_h % d.stride_h != rh || (long)kc * d.dil_w % d.stride_w != rw) continue;
+        t.taps.push_back(kr << 8 | kc);
+        const int tap = rank_h[kr] * f.taps_w + rank_w[kc];
+        const int dh = (f.h0 + d.pad_h - kr * d.dil_h) / d.stride_h, dw = (f.w0 + d.pad_w - kc * d.dil_w) / d.stride_w;
+        for (int ocl = 0; ocl < g.Mg; ++ocl) {
+          int *c = t.col.data() + 4 * (size_t)(cols + (long)ocl * ntaps + tap);
+          c[0] = (int)(ocl * opix), c[1] = dh, c[2] = dw, c[3] = 1;
+        }
+      }
+    t.tap_ptr[(size_t)ph + 1] = (int)t.taps.size();
+    cols += (long)f.ksteps * plan.step_k;
+  }
+  if (t.taps.empty()) t.taps.push_back(0);
+  // the entries' places, and which steps of which (group, phase, channel tile) hold one
+  t.pos.assign(at_least_one(v.nnz()), 0);
+  const size_t lists = (size_t)d.group * P * plan.ctiles;
+  std::vector<std::vector<char>> has(lists);
+  for_each_entry(v, [&](const CsrEntry &c) {
+    const Tap tap = decode_tap(c.col, d.KH, d.KW);
+    const int ph = (int)((long)tap.kr * d.dil_h % d.stride_h) * plan.phases_w + (int)((long)tap.kc * d.dil_w % d.stride_w);
+    const DgmPhase &f = plan.phase[(size_t)ph];
+    const int k = c.m * (f.taps_h * f.taps_w) + rank_h[tap.kr] * f.taps_w + rank_w[tap.kc];
+    const int ct = tap.ic / plan.tile_c;
+    t.pos[(size_t)c.e] = (int)((((long)c.grp * plan.ctiles + ct) * plan.cols_total + col0[(size_t)ph] + k) * plan.tile_c + tap.ic % plan.tile_c);
+    std::vector<char> &h = has[((size_t)c.grp * P + ph) * plan.ctiles + ct];
+    if (h.empty()) h.assign((size_t)f.ksteps, 0);
+    h[(size_t)(k / plan.step_k)] = 1;
+  });
+  t.live_ptr.assign(lists + 1, 0);
+  for (size_t l = 0; l < lists; ++l) {
+    for (size_t s = 0; s < has[l].size(); ++s)
+      if (has[l][s]) t.live.push_back((int)s);
+    t.live_ptr[l + 1] = (int)t.live.size();
+  }
+  if (t.live.empty()) t.live.push_back(0);
+  return t;
+}
+
 bool entry_major(const std::vector<int> &src, const std::vector<unsigned> &off, const std::vector<unsigned char> &buf,
                  long nnz, EntryMajor *out) {
   const size_t n = src.size(), nz = at_least_one(nnz);

@@ -7,7 +7,8 @@
 // Lengths: DeviceBuffer::upload allocates what it is handed, and a kernel argument may not be a null pointer, so the
 // tables that an empty pattern would leave empty are padded to one (zero) element: generic_tables' taps,
 // dense_positions, gather_transpose's ttap.  staged_tables' off is padded by two batches of zeros, which the staged
-// kernel's walk reads ahead into.  wgrad_mfma_tables' ent has M * kdim elements whatever the pattern.  The host-side
+// kernel's walk reads ahead into.  wgrad_mfma_tables' ent has M * kdim elements whatever the pattern; dgrad_mfma_tables'
+// taps, col, pos and live are padded to one element.  The host-side
 // lists (tsrc) have exactly nnz elements.
 #ifndef ESCOIN_CSR_TABLES_H_
 #define ESCOIN_CSR_TABLES_H_
@@ -102,6 +103,27 @@ StagedTables staged_tables(const CsrView &v, int icb, int nblk, int cs, int Wp);
 // past kdim (the last tile's padding) carry {0, 0, 0, 0}: "no such column".
 struct WgmTables { std::vector<int> ent, tile_cnt, ktab; };
 WgmTables wgrad_mfma_tables(const CsrView &v, int tile_m, int tile_k);
+
+// The MFMA data-gradient kernel's tables for a tile plan of align_rules.h dgm_plan (P phases, phase index = row residue *
+// stride_w + column residue; ctiles channel tiles of tile_c per conv group; steps of step_k columns):
+//   phase    [8 * P]: {h0, w0, rows, cols, kp, ksteps, col0, ntaps} -- the phase's bottom pixels are (h0 + stride_h * hh,
+//            w0 + stride_w * ww), hh < rows, ww < cols; kp = Mg * ntaps columns in ksteps steps; col0 = its first column in
+//            `col` and in the matrices;
+//   tap_ptr  [P + 1], taps [max(sum of ntaps, 1)]: the phase's taps kr << 8 | kc, ascending -- the (kr, kc) with
+//            kr * dil_h % stride_h and kc * dil_w % stride_w equal to the phase's residues (host side only);
+//   col      [4 * cols_total]: column k of a phase, k = ocl * ntaps + t, at col0 + k as four ints {ocl * OH * OW, dh, dw, 1}:
+//            tap t of pixel (hh, ww) reads G[ocl][hh + dh][ww + dw], dh = (h0 + pad_h - kr * dil_h) / stride_h (exact), dw
+//            likewise; the columns at or past kp (the last step's padding) carry {0, 0, 0, 0};
+//   the phase matrices: one transposed dense copy of the weights, mat_floats floats, zero where the pattern has no entry.
+//            Block (grp, ct) holds cols_total rows of tile_c floats: the weight of (column col0 + k of the phase, input
+//            channel ct * tile_c + i) at ((grp * ctiles + ct) * cols_total + col0 + k) * tile_c + i -- a step's 64 x 32
+//            block is contiguous, and so is what a wave loads of it;
+//   pos      [max(nnz, 1)]: the one matrix element that holds CSR entry e (how weight updates reach the matrix);
+//   live_ptr [group * P * ctiles + 1], live [max(total, 1)]: per (grp, phase, ct), at (grp * P + phase) * ctiles + ct, the
+//            ascending steps whose 64 x 32 weight block holds a CSR entry.  An empty list: the tile's pixels are zeros.
+struct DgmPlan;
+struct DgmTables { std::vector<int> phase, tap_ptr, taps, col, pos, live_ptr, live; };
+DgmTables dgrad_mfma_tables(const CsrView &v, const DgmPlan &plan);
 
 // A scatter list (destination k: CSR entry src[k], element off[k] of buffer buf[k]) entry-major: entry e's destinations
 // are e_off[k] / e_buf[k] for k in [e_ptr[e], e_ptr[e + 1]), in the order of the list.  e_ptr [max(nnz, 1) + 1], e_off

@@ -72,6 +72,7 @@ DeviceBytes device_bytes(const escoin_plan *p) {
   if (const BwdState *s = p->bwd.get())
     b.bwd = s->trow.bytes() + s->ttap.bytes() + s->tval.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() + s->stg_blk.bytes() + s->stg_off.bytes() +
             s->wgm_ent.bytes() + s->wgm_cnt.bytes() + s->wgm_ktab.bytes() +
+            s->dgm_mat.bytes() + s->dgm_phase.bytes() + s->dgm_col.bytes() + s->dgm_lptr.bytes() + s->dgm_live.bytes() +
             (s->tplan ? device_bytes(s->tplan.get()).fwd : 0);
   return b;
 }
@@ -92,6 +93,7 @@ long bwd_stat(const escoin_plan *p, const char *key) {
     if (s && s->wgrad == ESCOIN_WGRAD_MFMA) return (long)s->wgm_lds_bytes;
     return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg_lds_bytes : 0;
   }
+  if (!strcmp(key, "dgrad_lds_bytes")) return s && s->data_kernel == ESCOIN_BWD_MFMA ? (long)s->dgm_lds_bytes : 0;
   if (!strcmp(key, "bwd_align_us")) return s ? (long)(s->align_ms * 1e3) : 0;
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
@@ -430,7 +432,7 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       return ESCOIN_OK;
     }
     if (!strcmp(key, "backward_kernel")) {
-      if (value < ESCOIN_KERNEL_AUTO || value > ESCOIN_KERNEL_JIT) return fail(ESCOIN_EINVAL, "unknown kernel id");
+      if (value < ESCOIN_KERNEL_AUTO || value > ESCOIN_BWD_MFMA) return fail(ESCOIN_EINVAL, "backward_kernel must be a kernel id (0..4) or 5 (the MFMA data-gradient kernel)");
       p->bwd_kernel = value;
       return ESCOIN_OK;
     }
@@ -653,7 +655,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
     return (long)v;
   }
   if (!strcmp(key, "streamk")) return p->dense.sk_used ? 1 : 0;
-  if (!strncmp(key, "bwd_", 4) || !strncmp(key, "wgrad_", 6)) return bwd_stat(p, key);
+  if (!strncmp(key, "bwd_", 4) || !strncmp(key, "wgrad_", 6) || !strncmp(key, "dgrad_", 6)) return bwd_stat(p, key);
   if (!strncmp(key, "upd", 3)) return upd_stat(p, key);
   if (!strcmp(key, "is_f64")) return p->is_f64 ? 1 : 0;
   if (!strcmp(key, "host_aligned")) return p->host_aligned ? 1 : 0;

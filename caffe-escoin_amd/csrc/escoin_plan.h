@@ -74,7 +74,8 @@ struct CpuWorkspace {
 
 // What the first escoin_backward on an alignment builds (sconv_backward.hip); reset with the device side.
 struct BwdState {
-  // transposed forward plan (path a), or null: the gather kernel (path b)
+  // transposed forward plan (path a), or null: the gather kernel (path b) or the MFMA data-gradient kernel (path c);
+  // data_kernel says which
   std::unique_ptr<escoin_plan, int (*)(escoin_plan *)> tplan{nullptr, escoin_plan_destroy};
   int data_kernel = ESCOIN_KERNEL_GENERIC;
   DeviceBuffer trow;   // [C + 1] absolute offsets into ttap / tval (gather kernel)
@@ -100,6 +101,17 @@ struct BwdState {
   DeviceBuffer wgm_ent;   // [M * kdim] (row, column) -> CSR entry, -1: none
   DeviceBuffer wgm_cnt;   // [group * mtiles * ktiles] entries per tile
   DeviceBuffer wgm_ktab;  // [4 * ktiles * tile_k] the im2col decode of a column
+  // data gradient, fp32-MFMA kernel (dgrad_mfma.hip, option "backward_kernel" = ESCOIN_BWD_MFMA; the tables: csr_tables.h
+  // dgrad_mfma_tables)
+  int dgm_phases = 0, dgm_ctiles = 0, dgm_cols_total = 0;
+  size_t dgm_lds_bytes = 0;
+  DeviceBuffer dgm_mat;    // the phase matrices: the weights transposed, columns permuted by phase, zero outside the pattern
+  DeviceBuffer dgm_phase;  // [phases][8] a phase's pixels, columns and place in dgm_col / dgm_mat
+  DeviceBuffer dgm_col;    // [4 * cols_total] the decode of a column: {G offset of ocl, dh, dw, valid}
+  DeviceBuffer dgm_lptr;   // [group * phases * ctiles + 1] into dgm_live
+  DeviceBuffer dgm_live;   // the live steps of every (group, phase, channel tile), ascending
+  std::vector<int> dgm_ppix;   // host: [phases] a phase's pixels per image (the launch's grid)
+  std::vector<int> dgm_pos;    // host: [nnz] the element of dgm_mat that holds CSR entry e -- how weight updates reach it
   double align_ms = 0.0;
   // host: per entry of the transposed order (tplan's CSR, or ttap / tval) the index of the plan's CSR entry (groups
   // concatenated) it is a copy of -- how escoin_update_values reaches the backward state's values (update_values.hip)
@@ -335,6 +347,12 @@ int dense_spare_rows();       // zero rows after row M - 1
 int wgm_build(escoin_plan *p, BwdState *s, hipStream_t stream);
 int launch_wgrad_mfma(const escoin_plan *p, const BwdState *s, const float *bottom, const float *top,
                       const float *top_diff, float *slab_w, int n_images, int chunks, hipStream_t stream);
+
+// dgrad_mfma.hip (option "backward_kernel" = ESCOIN_BWD_MFMA): builds the phase matrices and the kernel's tables into the
+// backward state; the data gradient of n_images images
+int dgm_build(escoin_plan *p, BwdState *s, hipStream_t stream);
+int launch_dgrad_mfma(const escoin_plan *p, const BwdState *s, const float *top, const float *top_diff,
+                      float *bottom_diff, int n_images, hipStream_t stream);
 
 // Index of the k-th set bit of `mask` (k < popcount): blockIdx -> conv group when only some groups
 // of a layer run in a launch.  Wave-uniform scalar code on the device.

@@ -12,7 +12,9 @@
 //     (b) everything else (stride > 1, larger pads, double, option backward_kernel = GENERIC):
 //         escoin_sconv_bwd_data_kernel, one lane per bottom pixel, the wave walking its input channel's transposed-CSR
 //         row in ascending (ocl, kr, kc) order with one fma per contributing entry from 0 -- the order of the CPU mode's
-//         data gradient (sconv_cpu_backward.cpp), so the two are bit-identical.
+//         data gradient (sconv_cpu_backward.cpp), so the two are bit-identical;
+//     (c) option backward_kernel = ESCOIN_BWD_MFMA (never AUTO's choice): escoin_sconv_dgrad_mfma_kernel of dgrad_mfma.hip,
+//         one stride-1 gather-GEMM per stride phase on the fp32 matrix cores, for float plans of any geometry.
 //   weight gradient weight_diff[oc][colidx] += sum over (n, oh, ow) of G * bottom[...], at the CSR positions only;
 //   bias gradient   bias_diff[oc] += sum over (n, oh, ow) of G.
 //     Two deterministic stages, no float atomics (the order of every sum is a function of the geometry and n_images):
@@ -569,12 +571,21 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   if (p->wgrad_kernel == ESCOIN_WGRAD_MFMA && !wgm_plan(g, p->is_f64, &wp))
     return fail(ESCOIN_EINVAL, "wgrad_kernel: the MFMA weight-gradient kernel needs a float plan whose pixel, weight and "
                                "image indices fit 31 bits; the entry kernel serves this plan");
+  DgmPlan dp;
+  if (p->bwd_kernel == ESCOIN_BWD_MFMA && !dgm_plan(g, p->is_f64, &dp))
+    return fail(ESCOIN_EINVAL, "backward_kernel: the MFMA data-gradient kernel needs a float plan whose pixel, top and "
+                               "matrix indices fit 31 bits; the gather kernel serves this plan");
   p->bwd.reset(new BwdState());
   BwdState *s = p->bwd.get();
   s->nnz = plan_nnz(p);
   if (s->nnz > 0x7fffffffL) return fail(ESCOIN_EINVAL, "backward: more than 2^31 nonzeros");
   int rc = ESCOIN_OK;
-  if (transposable && p->bwd_kernel != ESCOIN_KERNEL_GENERIC) {
+  if (p->bwd_kernel == ESCOIN_BWD_MFMA) {
+    if constexpr (sizeof(T) == 4) {
+      s->data_kernel = ESCOIN_BWD_MFMA;
+      rc = dgm_build(p, s, stream);
+    }
+  } else if (transposable && p->bwd_kernel != ESCOIN_KERNEL_GENERIC) {
     rc = build_transposed_plan(p, s, stream);
     if (rc == ESCOIN_OK && d.fuse_relu) {
       const size_t bytes = sizeof(float) * (size_t)d.N * d.M * g.OH * g.OW;
@@ -650,6 +661,11 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
       }
       const int rc = escoin_forward(s->tplan.get(), src, nullptr, reinterpret_cast<float *>(bottom_diff), n_images, stream);
       if (rc != ESCOIN_OK) return rc;
+    } else if (s->data_kernel == ESCOIN_BWD_MFMA) {
+      if constexpr (sizeof(T) == 4) {
+        const int rc = launch_dgrad_mfma(p, s, top, top_diff, bottom_diff, n_images, stream);
+        if (rc != ESCOIN_OK) return rc;
+      }
     } else {
       BwdDataArgs<T> a;
       a.top_diff = top_diff; a.top = top; a.bottom_diff = bottom_diff;

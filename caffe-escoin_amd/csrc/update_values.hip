@@ -8,6 +8,7 @@
 //   the generated code / the weight stream     sparse conv groups of a tiled plan
 //   dense.w                                    the MFMA kernel's padded matrix
 //   bwd: tval, or the transposed plan's own    the backward state's copies, through BwdState::tsrc
+//   bwd: dgm_mat                               the MFMA data gradient's phase matrices, through BwdState::dgm_pos
 // The first update on an alignment builds that list (UpdState); later updates launch one kernel and nothing else.
 // The list's device facts (buffers, their sizes, the bounds checks) are collected here; the indices derived from the CSR
 // alone -- dense positions, the entry-major view -- come from the host-only builders of csr_tables.h.
@@ -126,8 +127,21 @@ int build_state(escoin_plan *p, hipStream_t stream, bool entry_view, bool vals_o
   }
   if (rc != ESCOIN_OK) return rc;
   if (const BwdState *s = vals_only ? nullptr : p->bwd.get()) {
-    if ((long)s->tsrc.size() != u->nnz) return fail(ESCOIN_EINVAL, "update_values: the backward state does not match the CSR");
-    if (s->tplan) {
+    const bool dgm = s->data_kernel == ESCOIN_BWD_MFMA;
+    if ((long)(dgm ? s->dgm_pos.size() : s->tsrc.size()) != u->nnz) return fail(ESCOIN_EINVAL, "update_values: the backward state does not match the CSR");
+    if (dgm) {
+      // the MFMA data gradient's phase matrices: one element per CSR entry (csr_tables.h dgrad_mfma_tables)
+      if (u->nnz > 0) {
+        if (u->n_buffers >= kUpdMaxBuffers || sizeof(T) != 4) return fail(ESCOIN_EINVAL, "update_values: bad backward phase matrices");
+        const int b = u->n_buffers++;
+        u->base[b] = s->dgm_mat.get<void>();
+        for (long k = 0; k < u->nnz; ++k) {
+          const size_t at = (size_t)s->dgm_pos[(size_t)k];
+          if ((at + 1) * sizeof(T) > s->dgm_mat.bytes()) return fail(ESCOIN_EINVAL, "update_values: phase-matrix destination out of range");
+          dst.push_back({(unsigned char)b, (int)k, (unsigned)at});
+        }
+      }
+    } else if (s->tplan) {
       rc = collect<T>(s->tplan.get(), s->tsrc.data(), u.get(), &dst);
       if (rc != ESCOIN_OK) return rc;
     } else if (u->nnz > 0) {

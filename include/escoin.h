@@ -417,9 +417,32 @@ ESCOIN_API int escoin_cpu_sparse_dense2csr_f64(int M, int N, const double *A, do
  * Option "backward_kernel" (before the align, like the others): AUTO (default) = the transposed plan picks its kernel
  * where it exists; GENERIC = the gather kernel; TILED / JIT / DENSE = that kernel on the transposed plan (the first
  * backward fails with ESCOIN_EINVAL where there is none).
- * Stats: "bwd_data_kernel" (ESCOIN_KERNEL_GENERIC = the gather kernel, otherwise the transposed plan's resolved kernel;
- * ESCOIN_ESTATE before the first backward), "bwd_device_bytes", "bwd_chunks" (chunks the last weight / bias gradient
- * reduced over), "bwd_align_us" (build time of the backward state).
+ * ESCOIN_BWD_MFMA (5; a value of "backward_kernel" only -- option "kernel" rejects it; never chosen by AUTO) =
+ * escoin_sconv_dgrad_mfma_kernel, for the layers kept dense that have no transposed plan (stride > 1, or pad > dil x
+ * (K - 1)).  The bottom pixels split into stride_h x stride_w phases ((h + pad_h) % stride_h, (w + pad_w) % stride_w);
+ * inside a phase every pixel has the same contributing taps, so a phase is one stride-1 implicit GEMM
+ * dX_phase[Cg x P] = Wt_phase[Cg x Mg*taps] x gather(G)[Mg*taps x P] over the phase's (n, h, w) pixels, run on the fp32
+ * matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 sums) by one workgroup per (phase, 64 phase pixels, 64
+ * input channels of a conv group), 32 columns per LDS step, the whole reduction in that workgroup (no split-K, no atomics).
+ * A phase without taps (three of the four of a 1x1 stride-2 layer) writes zeros; every bottom element is overwritten
+ * once, and images at or past n_images are not touched.  The weights are kept as one transposed dense copy with the
+ * columns permuted by phase (zero outside the pattern), which escoin_update_values, escoin_plan_set_values and
+ * escoin_solver_step reach in place: after any of them the data gradient equals, bit for bit, that of a fresh plan
+ * aligned by set_csr on the new values.  It serves float plans of any stride, pad, dilation, group count and kernel shape
+ * with N*H*W, Mg*OH*OW and the matrices' floats (about C*Mg*KH*KW rounded up to 64 channels and 32 columns per phase)
+ * below 2^31, H, W, pads and dilated kernel extents below 2^28, at most 65535 phases and 65535 (group, 64-channel tile)
+ * pairs; on a double plan or outside these the first backward fails with ESCOIN_EINVAL.  Sum order: per element the live
+ * steps of 32 columns ascending (a step is live when its 64 channels x 32 columns hold a CSR entry), inside a step the
+ * matrix instruction's own order -- a function of the geometry and the pattern only, not of n_images nor of an image's
+ * place in the batch; equality of its bits with the gather kernel's is no part of the contract.  The work is the dense problem restricted to live
+ * steps: a pruned position inside a live step contributes 0 x G, so a NON-FINITE G element gives NaN in input channels
+ * whose weight for it is pruned, where the gather kernel gives a finite value (the forward's DENSE kernel has the same
+ * property towards a non-finite bottom).  The weight / bias gradient paths are untouched and combine with it freely.
+ * Stats: "bwd_data_kernel" (ESCOIN_KERNEL_GENERIC = the gather kernel, ESCOIN_BWD_MFMA = the MFMA data-gradient kernel,
+ * otherwise the transposed plan's resolved kernel;
+ * ESCOIN_ESTATE before the first backward), "bwd_device_bytes" (the phase matrices and their tables included),
+ * "dgrad_lds_bytes" (LDS of an MFMA data-gradient workgroup; 0 on the other paths), "bwd_chunks" (chunks the last
+ * weight / bias gradient reduced over), "bwd_align_us" (build time of the backward state).
  * Option "wgrad_kernel" (before the align): which stage 1 produces the per-chunk partials of the weight / bias gradient.
  * ESCOIN_WGRAD_ENTRY = escoin_sconv_wgrad_partial_kernel, which reads the bottom from global memory once per nonzero,
  * then escoin_sconv_wgrad_sum_kernel.  ESCOIN_WGRAD_STAGED = escoin_sconv_wgrad_staged_kernel: one workgroup per (chunk,
@@ -453,6 +476,7 @@ ESCOIN_API int escoin_cpu_sparse_dense2csr_f64(int M, int N, const double *A, do
 #define ESCOIN_WGRAD_ENTRY 1   /* escoin_sconv_wgrad_partial_kernel: one workgroup per (chunk, output channel) */
 #define ESCOIN_WGRAD_STAGED 2  /* escoin_sconv_wgrad_staged_kernel: the chunk's bottom staged in LDS */
 #define ESCOIN_WGRAD_MFMA 3    /* escoin_sconv_wgrad_mfma_kernel: G x im2col(bottom) on the fp32 matrix cores */
+#define ESCOIN_BWD_MFMA 5      /* option "backward_kernel" only: escoin_sconv_dgrad_mfma_kernel, one gather-GEMM per stride phase */
 ESCOIN_API int escoin_backward(escoin_plan *plan, const float *bottom_dev, const float *top_dev, const float *top_diff_dev,
                     float *bottom_diff_dev, float *weight_diff_dev, float *bias_diff_dev, int n_images, void *stream);
 ESCOIN_API int escoin_backward_f64(escoin_plan *plan, const double *bottom_dev, const double *top_dev,

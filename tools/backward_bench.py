@@ -3,15 +3,20 @@
 pattern-preserving backward (escoin_backward), the kernels that ran, and the same shapes through torch's dense conv
 backward (MIOpen, dense weights) as a comparison point.  The weight gradient is timed three ways in the same call, on
 separate plans: option wgrad_kernel = ENTRY, = STAGED (skipped where the staged kernel does not serve the plan), = MFMA
-and the default AUTO; the compact entry point (escoin_backward_values) on the AUTO plan.
+and the default AUTO; the compact entry point (escoin_backward_values) on the AUTO plan.  Where AUTO ran the gather kernel
+for the data gradient (stride > 1, pad > dil x (K - 1)), the data gradient is timed a second time on a plan forced to
+backward_kernel = BWD_MFMA (escoin_sconv_dgrad_mfma_kernel), with the regions of both, so that "the MFMA kernel's slowest
+region is shorter than the gather kernel's fastest" can be read off one call ("dgrad_mfma_faster").
 
 Sets: the four ResNet-50 3x3 shapes @90 % (batch 256), the GoogLeNet 1x1 layers @95 % (batch 256), AlexNet conv2-5
 @80 % (batch 128); "chain": the layers the forward keeps dense -- the distinct 1x1 shapes and the four 3x3 shapes of the
 ResNet-50 chain at batch 256 and density 1.0, conv1 of AlexNet (11x11 stride 4) and of ResNet-50 (7x7 stride 2); "sweep":
-res2_branch2b, res5_branch2b and the chain's res4_branch2c at densities 1.0 / 0.5 / 0.3 / 0.2 / 0.1.  Times are device
+res2_branch2b, res5_branch2b and the chain's res4_branch2c at densities 1.0 / 0.5 / 0.3 / 0.2 / 0.1; "strided": the 3x3
+stride-2 pad-1 shapes 128 @ 56, 256 @ 28 and 512 @ 14 (ResNet-50 v1.5) @90 % (batch 256).  --only keeps the layers whose
+name contains one of the given substrings.  Times are device
 events around `--reps` back-to-back calls after a warm-up, the median of `--regions` regions, per call.  Prints one JSON line (and progress on stderr).
 
-    python tools/backward_bench.py [--sets resnet,googlenet,alexnet,chain,sweep] [--regions 7] [--reps 5] [--no-torch]
+    python tools/backward_bench.py [--sets resnet,googlenet,alexnet,chain,sweep,strided] [--only a,b] [--regions 7] [--reps 5] [--no-torch]
 """
 import argparse
 import json
@@ -24,7 +29,7 @@ sys.path.insert(0, ROOT)
 import __graft_entry__ as ge  # noqa: E402
 
 FAMILY = {0: "auto", 1: "gather (escoin_sconv_bwd_data_kernel)", 2: "tiled (transposed plan)",
-          3: "dense MFMA (transposed plan)", 4: "generated code (transposed plan)"}
+          3: "dense MFMA (transposed plan)", 4: "generated code (transposed plan)", 5: "MFMA (escoin_sconv_dgrad_mfma_kernel)"}
 
 
 WGRAD = {1: "entry", 2: "staged", 3: "mfma"}
@@ -63,6 +68,11 @@ def sweep_layers(synth, N=256):
             for name, c, h, m, k, kw in base for d in SWEEP]
 
 
+def strided_layers(synth, N=256):
+    return [synth.shape("s2_3x3_%d@%d" % (c, hw), N, c, hw, hw, c, 3, pad=1, stride=2, bias=False, sparsity=0.9)
+            for c, hw in ((128, 56), (256, 28), (512, 14))]
+
+
 def timed(fn, regions, reps):
     out = timed_regions(fn, regions, reps)
     return out[len(out) // 2]
@@ -93,6 +103,7 @@ def main():
     ap.add_argument("--regions", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--only", default="", help="comma-separated substrings: keep the layers whose name contains one")
     a = ap.parse_args()
     import torch
     pkg = ge.load_package()
@@ -110,6 +121,10 @@ def main():
         layers += chain_layers(synth)
     if "sweep" in sets:
         layers += sweep_layers(synth)
+    if "strided" in sets:
+        layers += strided_layers(synth)
+    if a.only:
+        layers = [s for s in layers if any(k in s.name for k in a.only.split(","))]
     rows = []
     for i, s in enumerate(layers):
         w = synth.pruned_weights(s, 1000 + i)
@@ -128,7 +143,25 @@ def main():
                  bwd_data_kernel=FAMILY[plan.stat("bwd_data_kernel")], bwd_chunks=plan.stat("bwd_chunks"),
                  bwd_align_ms=plan.stat("bwd_align_us") * 1e-3, bwd_device_mb=plan.stat("bwd_device_bytes") / 1e6)
         r["fwd_us"] = timed(lambda: plan.forward(x, bt, top), a.regions, a.reps)
-        r["bwd_data_us"] = timed(lambda: plan.backward(td, bottom_diff=bd), a.regions, a.reps)
+        regions = timed_regions(lambda: plan.backward(td, bottom_diff=bd), a.regions, a.reps)
+        r["bwd_data_us"] = regions[len(regions) // 2]
+        r["bwd_data_spread_us"] = [regions[0], regions[-1]]
+        if plan.stat("bwd_data_kernel") == pkg.KERNEL_GENERIC:
+            # the gather kernel ran: the same data gradient on the fp32 matrix cores, in the same call
+            forced = pkg.Plan(pkg.ConvDesc.from_shape(s), backward_kernel=pkg.BWD_MFMA)
+            forced.weight_align(w)
+            forced.backward(td, bottom_diff=bd)
+            assert forced.stat("bwd_data_kernel") == pkg.BWD_MFMA
+            mregions = timed_regions(lambda: forced.backward(td, bottom_diff=bd), a.regions, a.reps)
+            r["bwd_data_mfma_us"] = mregions[len(mregions) // 2]
+            r["bwd_data_mfma_spread_us"] = [mregions[0], mregions[-1]]
+            r["dgrad_mfma_faster"] = bool(mregions[-1] < regions[0])       # its slowest region against the gather's fastest
+            r["dgrad_lds_bytes"] = forced.stat("dgrad_lds_bytes")
+            r["dgrad_mfma_over_fwd"] = round(r["bwd_data_mfma_us"] / r["fwd_us"], 3)
+            # the kernel multiplies every live 64 x 32 weight block whatever its density: its rate on the dense problem
+            r["dgrad_dense_tflops"] = round(2.0 * s.N * plan.out_hw[0] * plan.out_hw[1] * s.M * (s.C // s.group) * s.KH * s.KW /
+                                            (r["bwd_data_mfma_us"] * 1e-6) / 1e12, 2)
+            forced.close()
         r["bwd_weight_us"] = timed(lambda: plan.backward(td, bottom=x, bottom_diff=None, weight_diff=wd), a.regions, a.reps)
         r["bwd_bias_us"] = timed(lambda: plan.backward(td, bottom_diff=None, bias_diff=bsd), a.regions, a.reps)
         r["wgrad_kernel"] = WGRAD[plan.stat("wgrad_kernel")]
@@ -170,6 +203,11 @@ def main():
             r["bwd_values_us"], r["bwd_bias_us"], r["bwd_data_kernel"],
             "" if a.no_torch else "  torch data %8.1f weight %8.1f" % (r["torch_data_us"], r["torch_weight_us"])),
             file=sys.stderr, flush=True)
+        if "bwd_data_mfma_us" in r:
+            print("%-28s data gradient: gather %.1f .. %.1f us, MFMA %.1f .. %.1f us (%.2f x fwd, %.1f TFLOP/s dense)  %s" % (
+                s.name, r["bwd_data_spread_us"][0], r["bwd_data_spread_us"][1], r["bwd_data_mfma_spread_us"][0],
+                r["bwd_data_mfma_spread_us"][1], r["dgrad_mfma_over_fwd"], r["dgrad_dense_tflops"],
+                "MFMA faster" if r["dgrad_mfma_faster"] else "MFMA NOT faster"), file=sys.stderr, flush=True)
     print(json.dumps(dict(tool="backward_bench", device=torch.cuda.get_device_name(0), layers=rows)))
 
 
