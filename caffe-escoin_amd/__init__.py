@@ -53,9 +53,12 @@ API_SYMBOLS = [
     # Solver step
     "escoin_solver_step", "escoin_solver_step_f64", "escoin_solver_step_cpu", "escoin_solver_step_cpu_f64",
     "escoin_solver_array_step", "escoin_solver_array_step_f64", "escoin_solver_array_step_cpu", "escoin_solver_array_step_cpu_f64",
+    # Pruning
+    "escoin_plan_prune", "escoin_plan_prune_cpu", "escoin_compact_entries",
 ]
 SOLVER_SGD, SOLVER_NESTEROV, SOLVER_ADAM = 0, 1, 2
 REG_NONE, REG_L2, REG_L1 = 0, 1, 2
+PRUNE_KEEP, PRUNE_THRESHOLD = 0, 1
 
 
 class EscoinError(RuntimeError):
@@ -97,6 +100,41 @@ class SolverDesc(C.Structure):
             rate_dev = rate_dev.data_ptr() if hasattr(rate_dev, "data_ptr") else rate_dev.ctypes.data
         return cls(int(type), int(regularization), rate, momentum, momentum2, delta, decay, diff_scale, rate_dev,
                    int(bool(diff_is_dense)), int(bool(clear_diff)))
+
+
+class PruneDesc(C.Structure):
+    """Mirror of escoin_prune_desc (include/escoin.h "Pruning")."""
+    _fields_ = [("mode", C.c_int), ("keep", C.c_long), ("threshold", C.c_double), ("score", C.c_void_p)]
+
+
+def compact_entries(entry_map, src, out=None, stream=None):
+    """escoin_compact_entries: out[entry_map[e]] = src[e] wherever entry_map[e] >= 0.  entry_map (int32) and src (4- or
+    8-byte elements) are both torch CUDA tensors (one launch on `stream`, default torch's current stream) or both numpy
+    arrays (a host loop).  out: the destination (at least as many elements as the map keeps; never src itself); None = a
+    new zeroed array of exactly the kept count, which costs a read of the map on the device route."""
+    on_device = not isinstance(entry_map, np.ndarray)
+    if on_device:
+        import torch
+        assert entry_map.is_cuda and entry_map.dtype == torch.int32 and entry_map.is_contiguous()
+        assert src.is_cuda and src.is_contiguous() and src.element_size() in (4, 8) and src.numel() == entry_map.numel()
+        if out is None:
+            out = torch.zeros(int((entry_map >= 0).sum().item()), dtype=src.dtype, device=src.device)
+        assert out.is_cuda and out.is_contiguous() and out.dtype == src.dtype
+        if stream is None:
+            stream = C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+        check(lib().escoin_compact_entries(C.c_void_p(entry_map.data_ptr()), entry_map.numel(), src.element_size(),
+                                           C.c_void_p(src.data_ptr()), C.c_void_p(out.data_ptr()), 1, stream),
+              "escoin_compact_entries")
+        return out
+    m = np.ascontiguousarray(entry_map, np.int32)
+    s = np.ascontiguousarray(src)
+    assert s.dtype.itemsize in (4, 8) and s.size == m.size
+    if out is None:
+        out = np.zeros(int((m >= 0).sum()), s.dtype)
+    assert out.dtype == s.dtype and out.flags["C_CONTIGUOUS"] and out.flags["WRITEABLE"] and out.size > (int(m.max()) if m.size else -1)
+    check(lib().escoin_compact_entries(_np_ptr(m), m.size, s.dtype.itemsize, _np_ptr(s), _np_ptr(out), 0, None),
+          "escoin_compact_entries")
+    return out
 
 
 def _solver_desc(desc, kw):
@@ -256,6 +294,13 @@ def lib():
         f.restype, f.argtypes = ip, [sp, C.c_long, vp, vp, vp, vp, vp]
         f = getattr(L, "escoin_solver_array_step_cpu" + suffix)
         f.restype, f.argtypes = ip, [sp, C.c_long, vp, vp, vp, vp]
+    pp = C.POINTER(PruneDesc)
+    L.escoin_plan_prune.restype = ip
+    L.escoin_plan_prune.argtypes = [vp, pp, vp, C.POINTER(C.c_long), vp]
+    L.escoin_plan_prune_cpu.restype = ip
+    L.escoin_plan_prune_cpu.argtypes = [vp, pp, vp, C.POINTER(C.c_long)]
+    L.escoin_compact_entries.restype = ip
+    L.escoin_compact_entries.argtypes = [vp, C.c_long, ip, vp, vp, ip, vp]
     L.escoin_cpu_kernel_name.restype = cp
     L.escoin_cpu_kernel_name.argtypes = []
     L.escoin_cpu_kernel_select.restype = ip
@@ -398,6 +443,54 @@ class Plan(object):
         assert dense_w is None or dense_w.size == self.desc.M * int(np.prod(self._grad_shapes())), "dense_w: blobs_[0]'s size"
         fn = lib().escoin_solver_step_cpu_f64 if f64 else lib().escoin_solver_step_cpu
         check(fn(self._h, C.byref(d), *ptrs), "escoin_solver_step_cpu")
+
+    # ---- pruning (include/escoin.h "Pruning") ------------------------------------------------------------------------------
+    def _prune_desc(self, keep, sparsity, threshold):
+        if sum(a is not None for a in (keep, sparsity, threshold)) != 1:
+            raise EscoinError("prune: give exactly one of keep, sparsity, threshold")
+        if sparsity is not None:
+            d = self.desc
+            keep = int(round((1.0 - float(sparsity)) * d.M * (d.C // d.group) * d.KH * d.KW))
+        if keep is not None:
+            return PruneDesc(PRUNE_KEEP, int(keep), 0.0, None)
+        return PruneDesc(PRUNE_THRESHOLD, 0, float(threshold), None)
+
+    def prune(self, keep=None, sparsity=None, threshold=None, score=None, stream=None):
+        """escoin_plan_prune: drops all but the `keep` largest-magnitude entries (or those below `threshold`) of a
+        device-aligned plan and re-aligns it on the rest.  sparsity: keep = round((1 - sparsity) * M * Cg * KH * KW).
+        score: a torch CUDA tensor of nnz elements of the plan's dtype in get_csr()'s order to rank instead of the
+        values.  Returns entry_map, an int32 torch CUDA tensor of the old nnz elements: the entry's new index, or -1.
+        Synchronises `stream` (default torch's current stream); not capturable."""
+        import torch
+        d = self._prune_desc(keep, sparsity, threshold)
+        n = self.nnz()
+        dev = torch.device("cuda", torch.cuda.current_device()) if score is None else score.device
+        if score is not None:
+            want = torch.float64 if self.stat("is_f64") == 1 else torch.float32
+            assert score.is_cuda and score.is_contiguous() and score.dtype == want and score.numel() == n, "score: nnz elements of the plan's dtype"
+            d.score = score.data_ptr()
+        entry_map = torch.empty(n, dtype=torch.int32, device=dev)
+        if stream is None:
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        new_nnz = C.c_long()
+        check(lib().escoin_plan_prune(self._h, C.byref(d), C.c_void_p(entry_map.data_ptr()) if n else None, C.byref(new_nnz), stream),
+              "escoin_plan_prune")
+        return entry_map
+
+    def prune_cpu(self, keep=None, sparsity=None, threshold=None, score=None):
+        """escoin_plan_prune_cpu: the same for a plan aligned by weight_align_cpu; score and the returned entry_map are
+        numpy arrays."""
+        d = self._prune_desc(keep, sparsity, threshold)
+        n = self.nnz()
+        s = None
+        if score is not None:
+            s = np.ascontiguousarray(score, np.float64 if self.stat("is_f64") == 1 else np.float32)
+            assert s.size == n, "score: nnz elements"
+            d.score = s.ctypes.data
+        entry_map = np.empty(n, np.int32)
+        new_nnz = C.c_long()
+        check(lib().escoin_plan_prune_cpu(self._h, C.byref(d), _np_ptr(entry_map), C.byref(new_nnz)), "escoin_plan_prune_cpu")
+        return entry_map
 
     # ---- Caffe::CPU mode (no device needed) ----------------------------------------------------
     def weight_align_cpu(self, dense_w):

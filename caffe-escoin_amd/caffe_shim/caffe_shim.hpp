@@ -282,6 +282,9 @@ class Layer {   // layer.hpp:33-475
   // SGDSolver::ApplyUpdate's per-parameter work (Normalize, Regularize, ComputeUpdateValue) and Net::Update for this
   // layer's learnable blobs in one call (include/escoin.h, "Solver step"); a layer without learnable blobs does nothing.
   virtual void SolverUpdate(const escoin_solver_desc &) {}
+  // Magnitude pruning of this layer's weights (include/escoin.h, "Pruning"): what a solver with a pruning schedule calls
+  // between two iterations; a layer without a sparse plan does nothing.
+  virtual void Prune(const escoin_prune_desc &) {}
   // layer.hpp:435-475: Reshape every call, mode switch, per-layer forward time in microseconds
   inline Dtype Forward(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &top) {
     Reshape(bottom, top);
@@ -460,8 +463,9 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
   // -- and blobs_[1] through the array step.  `rule` is the solver's rule for both blobs; its diff_is_dense and
   // clear_diff are set here.  The histories are layer-owned: for blobs_[0] compact (nnz elements in the plan's CSR order),
   // created zeroed on first use and dropped by every WeightAlign / WeightAlignFrom (the entries of a new alignment are
-  // other weights, whether or not nnz changed; a solver that re-aligns mid-training restarts this layer's momentum).  The brew picks host or device pointers (a
-  // rule.rate_dev must match it); a plan that has a device side is stepped on the device in either brew, which keeps
+  // other weights, whether or not nnz changed; a solver that re-aligns mid-training restarts this layer's momentum --
+  // Prune() below shrinks the pattern WITHOUT that: it carries the histories over through the entry map).  The brew
+  // picks host or device pointers (a rule.rate_dev must match it); a plan that has a device side is stepped on the device in either brew, which keeps
   // both sides current.  A layer that is not aligned yet aligns first.
   virtual void SolverUpdate(const escoin_solver_desc &rule) {
     ESC_CHECK(plan_ != nullptr);
@@ -494,6 +498,58 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       }
     }
   }
+
+  // Prunes the aligned plan in place (include/escoin.h, "Pruning") and keeps everything that is indexed by CSR entry in
+  // step: the weights' histories are compacted through the entry map instead of being cleared (momentum survives a
+  // pruning step), and the dropped positions of blobs_[0] -- data and diff -- become +0, so that the blob and the plan
+  // agree and a later WeightAlign from the blob reproduces the pattern.  The bias histories are not touched.  A plan that
+  // has a device side is pruned on the device in either brew (rule.score, if any, must then be a device pointer;
+  // otherwise a host pointer).  Synchronises; not for a captured graph.  A layer that is not aligned yet aligns first.
+  virtual void Prune(const escoin_prune_desc &rule) {
+    ESC_CHECK(plan_ != nullptr);
+    if (!aligned_ || (Caffe::mode() == Caffe::GPU && !aligned_on_device_)) WeightAlign();
+    const long n = nnz();
+    if (n == 0) return;
+    const int mg = num_output_ / group_, kdim = (channels_ / group_) * desc_.KH * desc_.KW;
+    vector<int> rowptr((size_t)group_ * (mg + 1)), colidx((size_t)n);
+    ESCOIN_CHECK(escoin_plan_get_csr(plan_, rowptr.data(), colidx.data(), nullptr, 0));    // the OLD pattern
+    vector<long> per_group(group_);
+    for (int g = 0; g < group_; ++g) per_group[g] = escoin_plan_nnz(plan_, g);
+    Blob<int> map(vector<int>(1, (int)n));
+    long kept = 0;
+    if (aligned_on_device_)
+      ESCOIN_CHECK(escoin_plan_prune(plan_, &rule, map.mutable_gpu_data(), &kept, Caffe::stream()));
+    else
+      ESCOIN_CHECK(escoin_plan_prune_cpu(plan_, &rule, map.mutable_cpu_data(), &kept));
+    if (kept == n) return;
+    const int *m = map.cpu_data();
+    for (size_t k = 0; k < history_.size() && k < 2; ++k) {
+      shared_ptr<Blob<Dtype> > fresh(new Blob<Dtype>(vector<int>(1, (int)kept)));
+      if (aligned_on_device_)
+        ESCOIN_CHECK(escoin_compact_entries(map.gpu_data(), n, (int)sizeof(Dtype), history_[k]->gpu_data(), fresh->mutable_gpu_data(), 1, Caffe::stream()));
+      else
+        ESCOIN_CHECK(escoin_compact_entries(m, n, (int)sizeof(Dtype), history_[k]->cpu_data(), fresh->mutable_cpu_data(), 0, nullptr));
+      history_[k] = fresh;     // (the old blob's release waits for the device)
+    }
+    Blob<Dtype> &w = *this->blobs_[0];
+    Dtype *data = w.mutable_cpu_data(), *diff = w.mutable_cpu_diff();
+    long e = 0;
+    for (int g = 0; g < group_; ++g) {
+      const int *rp = rowptr.data() + (size_t)g * (mg + 1);
+      const long base = e;
+      for (int r = 0; r < mg; ++r)
+        for (int j = rp[r]; j < rp[r + 1]; ++j, ++e)
+          if (m[e] < 0) {
+            const size_t at = ((size_t)g * mg + r) * kdim + (size_t)colidx[(size_t)(base + j)];
+            data[at] = (Dtype)0;
+            diff[at] = (Dtype)0;
+          }
+      ESC_CHECK(e - base == per_group[g]);
+    }
+  }
+  // SolverUpdate's histories, for snapshots and tests: {weights' h / m, weights' v, bias' h / m, bias' v}; empty before the
+  // first SolverUpdate on an alignment
+  const vector<shared_ptr<Blob<Dtype> > > &solver_history() const { return history_; }
 
   // The aligned form as one byte blob (CSR + channel deal + unit table + code object), and WeightAlign from such
   // a blob instead of from blobs_[0]: what a Net::CopyTrainedLayersFrom that finds "<model>.escoin/<layer>.bin"

@@ -11,6 +11,7 @@
 #include "align_rules.h"
 #include "aligned_form.h"
 #include "escoin_plan.h"
+#include "prune_rules.h"
 
 namespace escoin {
 
@@ -657,6 +658,12 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "streamk")) return p->dense.sk_used ? 1 : 0;
   if (!strncmp(key, "bwd_", 4) || !strncmp(key, "wgrad_", 6) || !strncmp(key, "dgrad_", 6)) return bwd_stat(p, key);
   if (!strncmp(key, "upd", 3)) return upd_stat(p, key);
+  if (!strcmp(key, "prune_count")) return p->prune_count;
+  if (!strcmp(key, "prune_last_dropped")) return p->prune_last_dropped;
+  if (!strcmp(key, "prune_tile_entries")) return prune::kTileEntries;
+  if (!strcmp(key, "prune_kernels_us")) return (long)(p->prune_kernels_ms * 1e3);
+  if (!strcmp(key, "prune_map_us")) return (long)(p->prune_map_ms * 1e3);
+  if (!strcmp(key, "prune_realign_us")) return (long)(p->prune_realign_ms * 1e3);
   if (!strcmp(key, "is_f64")) return p->is_f64 ? 1 : 0;
   if (!strcmp(key, "host_aligned")) return p->host_aligned ? 1 : 0;
   if (!strcmp(key, "kernel_choice")) {

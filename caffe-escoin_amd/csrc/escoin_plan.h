@@ -260,6 +260,12 @@ struct escoin_plan {
   hipStream_t upd_stream = nullptr;   // the stream of the last device-source update
   int upd_last_fast = 0;              // stat "update_fast"
   long upd_count = 0;                 // stat "update_count": updates since the plan was created
+
+  // Pruning (prune_select.hip): stats "prune_count" (prunes since the plan was created) and "prune_last_dropped"
+  long prune_count = 0, prune_last_dropped = 0;
+  // the last escoin_plan_prune's phases: the selection / scan / map launches (device events), the call's wall time until
+  // the host holds the map, and from there to the end of the re-align
+  double prune_kernels_ms = 0.0, prune_map_ms = 0.0, prune_realign_ms = 0.0;
 };
 
 namespace escoin {
@@ -288,6 +294,10 @@ struct DeviceBytes { size_t fwd, bwd, upd; };
 DeviceBytes device_bytes(const escoin_plan *p);
 // escoin_capi.hip: the shared tail of weight_align / set_csr -- rebuilds the device side from the host CSR
 int realign_from_host_csr(escoin_plan *p, hipStream_t stream);
+// escoin_capi.hip: the first half of set_csr -- validates a CSR (flat, as escoin_plan_set_csr takes it) and copies it into
+// the plan's host vectors; a refused CSR leaves the plan as it was.  T = float | double.
+template <typename T>
+int set_csr_host(escoin_plan *p, const int *rowptr, const int *colidx, const T *values, const int *nnz_per_group);
 // escoin_capi.hip: brings the host mirrors (CSR values, the kept copy of the generated code, the transposed plan's) up
 // to date after device-source updates -- through escoin_plan::sync_host_fn, which the update that made the device
 // authoritative left (the host-only translation units do not depend on update_values.hip); a no-op otherwise.  Waits

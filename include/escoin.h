@@ -648,6 +648,63 @@ ESCOIN_API int escoin_solver_array_step_cpu(const escoin_solver_desc *desc, long
 ESCOIN_API int escoin_solver_array_step_cpu_f64(const escoin_solver_desc *desc, long n, double *data, double *diff,
                                      double *history, double *history2);
 
+/* ---- Pruning: magnitude pruning of an aligned plan, in place, with the entry map that carries the solver state over ----
+ * Gradual pruning is train, drop the smallest weights, train on.  Everything above keeps the pattern; this is the verb
+ * that SHRINKS it, and it hands back what a caller needs to keep its compact arrays (history, history2, a pending
+ * values_diff: nnz elements in escoin_plan_get_csr's order) in step: the old-entry -> new-entry map.
+ * One entry point for both Dtypes: the plan knows its Dtype, and `score` is read as that type.
+ * The rule, exact and the same on device and host:
+ *   key(s) = the bits of s with the sign bit cleared, compared as an unsigned integer (float: 32 bits, double: 64).  No
+ *   floating-point comparison is made anywhere: -0.0 == +0.0, denormals rank exactly, inf ranks above every finite value
+ *   and NaN above inf (a NaN weight is never silently pruned away).
+ *   KEEP orders the entries by (key descending, entry index ascending) over the whole layer, all conv groups together, and
+ *   keeps the first min(keep, nnz): among equal keys the lower entry index stays.
+ *   THRESHOLD keeps an entry iff key(s) >= key(threshold); the threshold is converted to the plan's Dtype once.
+ *   Explicit zeros of the pattern are ordinary entries with key 0.
+ *   score == NULL ranks the plan's current values; after a device-source update or solver step those are the DEVICE's, and
+ *   the caller does not synchronise first: the plan orders itself behind the stream of that update, as the read-back does.
+ * Effect: entry_map[e], e in [0, old nnz), is entry e's index in the new CSR, or -1 if it was dropped; the kept entries
+ * keep their order, so the map ascends over them.  entry_map and new_nnz may each be NULL.  Afterwards every consumer of
+ * the plan -- forward in all four conv_modes, backward, get_csr, export_aligned, updates, the solver step, the CPU entry
+ * points -- behaves BIT FOR BIT like a fresh plan with the same options aligned by escoin_plan_set_csr on the kept entries:
+ * the dense / sparse split, the kernel choice and the tiling are decided anew (sync_host_values, a new host CSR,
+ * realign_from_host_csr); the backward state and the update state are dropped, as on any align.  Dropping every entry
+ * leaves what escoin_plan_set_csr leaves on an empty CSR: an aligned plan with nnz 0 whose forward writes the bias (or 0).
+ * When nothing is dropped (keep >= nnz, every key passes the threshold, nnz == 0) the plan is untouched: no re-align, the
+ * states stay, the map is the identity, ESCOIN_OK, "prune_last_dropped" = 0.
+ * The call synchronises (`stream`, and the last update's stream) and allocates: it is NOT CAPTURABLE.
+ * Device side (prune_select.hip): a radix select of the keep-th largest key, 8 bits a pass (4 histogram launches for float,
+ * 8 for double; the digit is chosen on the device, no host round trip between passes), then per-tile counts, one
+ * workgroup's scan of the tile counts and the map -- integer atomics only, and no workgroup waits for another one.
+ * escoin_plan_prune_cpu: the same rule as plain host code, for plans aligned by escoin_weight_align_cpu; no HIP call.
+ * escoin_compact_entries: dst[entry_map[e]] = src[e] wherever entry_map[e] >= 0 -- what the caller runs over history,
+ * history2, a pending values_diff or its own copy of the values.  dst holds the new nnz elements; src and dst must NOT
+ * overlap (only an equal pointer is detected: ESCOIN_EINVAL).  on_device != 0: device pointers, one launch of
+ * escoin_compact_kernel (one lane per old entry, one plain store), asynchronous on `stream`, capturable.  on_device == 0:
+ * host pointers, a plain loop, no HIP call.
+ * Errors: ESCOIN_EINVAL for a NULL desc, an unknown mode, keep < 0, a negative or NaN threshold, elem_bytes not 4 or 8,
+ * old_nnz < 0; ESCOIN_ENODEVICE for the device entry points without a device; ESCOIN_ESTATE before an align, on another
+ * device, for escoin_plan_prune_cpu on a device-aligned plan and for escoin_plan_prune on a CPU-aligned one.
+ * Stats: "prune_count" (prunes since the plan was created), "prune_last_dropped" (entries the last prune dropped),
+ * "prune_tile_entries" (the entries one workgroup of the count / map kernels covers per step: a constant of the build);
+ * of the last escoin_plan_prune: "prune_kernels_us" (the selection, scan and map launches, by device events),
+ * "prune_map_us" (the call's wall time until the host holds the map), "prune_realign_us" (from there to the end of the
+ * re-align; 0 when nothing was dropped); "align_us" is then the whole call. */
+#define ESCOIN_PRUNE_KEEP 0       /* keep exactly min(keep, nnz) entries: the largest |s| */
+#define ESCOIN_PRUNE_THRESHOLD 1  /* keep the entries with |s| >= threshold */
+typedef struct escoin_prune_desc {
+  int mode;
+  long keep;            /* KEEP */
+  double threshold;     /* THRESHOLD; converted to the plan's Dtype once; >= 0, not NaN */
+  const void *score;    /* NULL: s = the plan's current values.  Otherwise nnz elements of the plan's Dtype in
+                           get_csr's order (device pointer; host pointer for _cpu), e.g. |w * g| */
+} escoin_prune_desc;
+ESCOIN_API int escoin_plan_prune(escoin_plan *plan, const escoin_prune_desc *desc, int *entry_map_dev, long *new_nnz,
+                      void *stream);
+ESCOIN_API int escoin_plan_prune_cpu(escoin_plan *plan, const escoin_prune_desc *desc, int *entry_map, long *new_nnz);
+ESCOIN_API int escoin_compact_entries(const int *entry_map, long old_nnz, int elem_bytes /* 4 | 8 */, const void *src,
+                           void *dst, int on_device, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
