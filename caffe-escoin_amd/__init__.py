@@ -55,6 +55,8 @@ API_SYMBOLS = [
     "escoin_solver_array_step", "escoin_solver_array_step_f64", "escoin_solver_array_step_cpu", "escoin_solver_array_step_cpu_f64",
     # Pruning
     "escoin_plan_prune", "escoin_plan_prune_cpu", "escoin_compact_entries",
+    # Rewiring
+    "escoin_plan_rewire", "escoin_plan_rewire_cpu",
 ]
 SOLVER_SGD, SOLVER_NESTEROV, SOLVER_ADAM = 0, 1, 2
 REG_NONE, REG_L2, REG_L1 = 0, 1, 2
@@ -105,6 +107,11 @@ class SolverDesc(C.Structure):
 class PruneDesc(C.Structure):
     """Mirror of escoin_prune_desc (include/escoin.h "Pruning")."""
     _fields_ = [("mode", C.c_int), ("keep", C.c_long), ("threshold", C.c_double), ("score", C.c_void_p)]
+
+
+class RewireDesc(C.Structure):
+    """Mirror of escoin_rewire_desc (include/escoin.h "Rewiring")."""
+    _fields_ = [("drop", C.POINTER(PruneDesc)), ("grow", C.c_long), ("score", C.c_void_p), ("init", C.c_void_p)]
 
 
 def compact_entries(entry_map, src, out=None, stream=None):
@@ -299,6 +306,11 @@ def lib():
     L.escoin_plan_prune.argtypes = [vp, pp, vp, C.POINTER(C.c_long), vp]
     L.escoin_plan_prune_cpu.restype = ip
     L.escoin_plan_prune_cpu.argtypes = [vp, pp, vp, C.POINTER(C.c_long)]
+    rp = C.POINTER(RewireDesc)
+    L.escoin_plan_rewire.restype = ip
+    L.escoin_plan_rewire.argtypes = [vp, rp, vp, vp, C.POINTER(C.c_long), C.POINTER(C.c_long), vp]
+    L.escoin_plan_rewire_cpu.restype = ip
+    L.escoin_plan_rewire_cpu.argtypes = [vp, rp, vp, vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
     L.escoin_compact_entries.restype = ip
     L.escoin_compact_entries.argtypes = [vp, C.c_long, ip, vp, vp, ip, vp]
     L.escoin_cpu_kernel_name.restype = cp
@@ -491,6 +503,76 @@ class Plan(object):
         new_nnz = C.c_long()
         check(lib().escoin_plan_prune_cpu(self._h, C.byref(d), _np_ptr(entry_map), C.byref(new_nnz)), "escoin_plan_prune_cpu")
         return entry_map
+
+    # ---- rewiring (include/escoin.h "Rewiring") ---------------------------------------------------------------------------
+    def _dense_size(self):
+        d = self.desc
+        return d.M * (d.C // d.group) * d.KH * d.KW
+
+    def _rewire_drop(self, drop_keep, drop_sparsity, drop_threshold, drop_score):
+        if drop_keep is None and drop_sparsity is None and drop_threshold is None:
+            if drop_score is not None:
+                raise EscoinError("rewire: drop_score needs one of drop_keep, drop_sparsity, drop_threshold")
+            return None
+        return self._prune_desc(drop_keep, drop_sparsity, drop_threshold)
+
+    def rewire(self, grow, score, init=None, drop_keep=None, drop_sparsity=None, drop_threshold=None, drop_score=None, stream=None):
+        """escoin_plan_rewire: drops entries by escoin_plan_prune's rule (drop_keep / drop_sparsity / drop_threshold, ranked
+        on the values or on drop_score, nnz elements; none given: nothing is dropped), grows the `grow` positions outside
+        the pattern where |score| is largest, and re-aligns the device-aligned plan ONCE.  score, init: torch CUDA tensors
+        of M * Cg * KH * KW elements of the plan's dtype (score may be None iff grow == 0; init None: grown entries are
+        +0.0).  Returns (entry_map, grown): int32 torch CUDA tensors of the old nnz (new index, or -1) and of n_grown
+        elements (the new indices of the grown positions, ascending).  Synchronises `stream` (default torch's current
+        stream); not capturable."""
+        import torch
+        want = torch.float64 if self.stat("is_f64") == 1 else torch.float32
+        n, D = self.nnz(), self._dense_size()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        drop = self._rewire_drop(drop_keep, drop_sparsity, drop_threshold, drop_score)
+        if drop_score is not None:
+            assert drop_score.is_cuda and drop_score.is_contiguous() and drop_score.dtype == want and drop_score.numel() == n, "drop_score: nnz elements of the plan's dtype"
+            drop.score = drop_score.data_ptr()
+        d = RewireDesc(C.pointer(drop) if drop is not None else None, int(grow), None, None)
+        for name, t in (("score", score), ("init", init)):
+            if t is not None:
+                assert t.is_cuda and t.is_contiguous() and t.dtype == want and t.numel() == D, name + ": M * Cg * KH * KW elements of the plan's dtype"
+                setattr(d, name, t.data_ptr())
+                dev = t.device
+        entry_map = torch.empty(n, dtype=torch.int32, device=dev)
+        grown = torch.empty(max(min(int(grow), D - n), 0), dtype=torch.int32, device=dev)      # n_grown = min(grow, D - nnz)
+        if stream is None:
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        new_nnz, n_grown = C.c_long(), C.c_long()
+        check(lib().escoin_plan_rewire(self._h, C.byref(d), C.c_void_p(entry_map.data_ptr()) if n else None,
+                                       C.c_void_p(grown.data_ptr()) if grown.numel() else None, C.byref(new_nnz), C.byref(n_grown), stream),
+              "escoin_plan_rewire")
+        return entry_map, grown[:n_grown.value]
+
+    def rewire_cpu(self, grow, score, init=None, drop_keep=None, drop_sparsity=None, drop_threshold=None, drop_score=None):
+        """escoin_plan_rewire_cpu: the same for a plan aligned by weight_align_cpu; score, init, drop_score and the
+        returned (entry_map, grown) are numpy arrays."""
+        dt = np.float64 if self.stat("is_f64") == 1 else np.float32
+        n, D = self.nnz(), self._dense_size()
+        drop = self._rewire_drop(drop_keep, drop_sparsity, drop_threshold, drop_score)
+        keep_alive = []
+        if drop_score is not None:
+            ds = np.ascontiguousarray(drop_score, dt)
+            assert ds.size == n, "drop_score: nnz elements"
+            keep_alive.append(ds)
+            drop.score = ds.ctypes.data
+        d = RewireDesc(C.pointer(drop) if drop is not None else None, int(grow), None, None)
+        for name, a in (("score", score), ("init", init)):
+            if a is not None:
+                a = np.ascontiguousarray(a, dt)
+                assert a.size == D, name + ": M * Cg * KH * KW elements"
+                keep_alive.append(a)
+                setattr(d, name, a.ctypes.data)
+        entry_map = np.empty(n, np.int32)
+        grown = np.empty(max(min(int(grow), D - n), 0), np.int32)      # n_grown = min(grow, D - nnz)
+        new_nnz, n_grown = C.c_long(), C.c_long()
+        check(lib().escoin_plan_rewire_cpu(self._h, C.byref(d), _np_ptr(entry_map), _np_ptr(grown), C.byref(new_nnz), C.byref(n_grown)),
+              "escoin_plan_rewire_cpu")
+        return entry_map, grown[:n_grown.value]
 
     # ---- Caffe::CPU mode (no device needed) ----------------------------------------------------
     def weight_align_cpu(self, dense_w):

@@ -115,6 +115,7 @@ class Caffe {
 template <typename Dtype> struct EscApi;
 template <> struct EscApi<float> {
   static int weight_align(escoin_plan *p, const float *w, int on_dev, void *s) { return escoin_weight_align(p, w, on_dev, s); }
+  static int get_csr(const escoin_plan *p, int *rp, int *ci, float *v) { return escoin_plan_get_csr(p, rp, ci, v, 0); }
   static int weight_align_cpu(escoin_plan *p, const float *w) { return escoin_weight_align_cpu(p, w); }
   static int forward(escoin_plan *p, const float *b, const float *bias, float *t, int n, void *s) { return escoin_forward(p, b, bias, t, n, s); }
   static int forward_cpu(escoin_plan *p, const float *b, const float *bias, float *t, int n, int threads) { return escoin_forward_cpu(p, b, bias, t, n, threads); }
@@ -129,6 +130,7 @@ template <> struct EscApi<float> {
 };
 template <> struct EscApi<double> {
   static int weight_align(escoin_plan *p, const double *w, int on_dev, void *s) { return escoin_weight_align_f64(p, w, on_dev, s); }
+  static int get_csr(const escoin_plan *p, int *rp, int *ci, double *v) { return escoin_plan_get_csr_f64(p, rp, ci, v, 0); }
   static int weight_align_cpu(escoin_plan *p, const double *w) { return escoin_weight_align_cpu_f64(p, w); }
   static int forward(escoin_plan *p, const double *b, const double *bias, double *t, int n, void *s) { return escoin_forward_f64(p, b, bias, t, n, s); }
   static int forward_cpu(escoin_plan *p, const double *b, const double *bias, double *t, int n, int threads) { return escoin_forward_cpu_f64(p, b, bias, t, n, threads); }
@@ -285,6 +287,9 @@ class Layer {   // layer.hpp:33-475
   // Magnitude pruning of this layer's weights (include/escoin.h, "Pruning"): what a solver with a pruning schedule calls
   // between two iterations; a layer without a sparse plan does nothing.
   virtual void Prune(const escoin_prune_desc &) {}
+  // Drop-and-grow rewiring of this layer's weights (include/escoin.h, "Rewiring"): what a solver with a dynamic-sparse
+  // schedule (RigL, SET) calls between two iterations; a layer without a sparse plan does nothing.
+  virtual void Rewire(const escoin_rewire_desc &) {}
   // layer.hpp:435-475: Reshape every call, mode switch, per-layer forward time in microseconds
   inline Dtype Forward(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &top) {
     Reshape(bottom, top);
@@ -545,6 +550,68 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
             diff[at] = (Dtype)0;
           }
       ESC_CHECK(e - base == per_group[g]);
+    }
+  }
+  // Rewires the aligned plan in place (include/escoin.h, "Rewiring") -- drop and grow with ONE re-align -- and keeps
+  // everything that is indexed by CSR entry in step: the weights' histories travel through the entry map into zeroed
+  // arrays of the new size (kept entries keep their momentum, grown entries start at zero), the dropped positions of
+  // blobs_[0] -- data and diff -- become +0, and the grown positions of blobs_[0]'s data take the grown values (+0, or
+  // rule.init's), so that the blob and the plan agree; with nonzero grown values a later WeightAlign from the blob
+  // reproduces the pattern.  The bias histories are not touched.  A plan that has a device side is rewired on the
+  // device in either brew (rule.score, rule.init and rule.drop->score, if any, must then be device pointers; otherwise
+  // host pointers).  Synchronises; not for a captured graph.  A layer that is not aligned yet aligns first.
+  virtual void Rewire(const escoin_rewire_desc &rule) {
+    ESC_CHECK(plan_ != nullptr);
+    if (!aligned_ || (Caffe::mode() == Caffe::GPU && !aligned_on_device_)) WeightAlign();
+    const long n = nnz();
+    const int mg = num_output_ / group_, kdim = (channels_ / group_) * desc_.KH * desc_.KW;
+    // the positions in blobs_[0] of a CSR's entries, in its order
+    auto positions = [&](long count, vector<Dtype> *values) {
+      vector<int> rowptr((size_t)group_ * (mg + 1)), colidx((size_t)count);
+      if (values) values->resize((size_t)count);
+      ESCOIN_CHECK(EscApi<Dtype>::get_csr(plan_, rowptr.data(), colidx.data(), values ? values->data() : nullptr));
+      vector<size_t> pos;
+      long base = 0;
+      for (int g = 0; g < group_; ++g) {
+        const int *rp = rowptr.data() + (size_t)g * (mg + 1);
+        for (int r = 0; r < mg; ++r)
+          for (int j = rp[r]; j < rp[r + 1]; ++j) pos.push_back(((size_t)g * mg + r) * kdim + (size_t)colidx[(size_t)(base + j)]);
+        base += rp[mg];
+      }
+      ESC_CHECK((long)pos.size() == count);
+      return pos;
+    };
+    const vector<size_t> old_pos = positions(n, nullptr);       // the OLD pattern
+    Blob<int> map(vector<int>(1, (int)std::max<long>(n, 1))), grown(vector<int>(1, (int)std::max<long>(rule.grow, 1)));
+    long new_nnz = 0, n_grown = 0;
+    if (aligned_on_device_)
+      ESCOIN_CHECK(escoin_plan_rewire(plan_, &rule, map.mutable_gpu_data(), grown.mutable_gpu_data(), &new_nnz, &n_grown, Caffe::stream()));
+    else
+      ESCOIN_CHECK(escoin_plan_rewire_cpu(plan_, &rule, map.mutable_cpu_data(), grown.mutable_cpu_data(), &new_nnz, &n_grown));
+    if (escoin_plan_stat(plan_, "rewire_last_dropped") == 0 && n_grown == 0) return;       // the plan was left untouched
+    for (size_t k = 0; k < history_.size() && k < 2; ++k) {
+      shared_ptr<Blob<Dtype> > fresh(new Blob<Dtype>(vector<int>(1, (int)new_nnz)));       // (a new blob is zero-filled)
+      if (n > 0 && new_nnz > 0) {
+        if (aligned_on_device_)
+          ESCOIN_CHECK(escoin_compact_entries(map.gpu_data(), n, (int)sizeof(Dtype), history_[k]->gpu_data(), fresh->mutable_gpu_data(), 1, Caffe::stream()));
+        else
+          ESCOIN_CHECK(escoin_compact_entries(map.cpu_data(), n, (int)sizeof(Dtype), history_[k]->cpu_data(), fresh->mutable_cpu_data(), 0, nullptr));
+      }
+      history_[k] = fresh;     // (the old blob's release waits for the device)
+    }
+    Blob<Dtype> &w = *this->blobs_[0];
+    Dtype *data = w.mutable_cpu_data(), *diff = w.mutable_cpu_diff();
+    const int *m = map.cpu_data();
+    for (long e = 0; e < n; ++e)
+      if (m[e] < 0) data[old_pos[(size_t)e]] = (Dtype)0, diff[old_pos[(size_t)e]] = (Dtype)0;
+    if (n_grown > 0) {
+      vector<Dtype> values;
+      const vector<size_t> new_pos = positions(new_nnz, &values);
+      const int *gr = grown.cpu_data();
+      for (long i = 0; i < n_grown; ++i) {
+        ESC_CHECK(gr[i] >= 0 && gr[i] < new_nnz);
+        data[new_pos[(size_t)gr[i]]] = values[(size_t)gr[i]];
+      }
     }
   }
   // SolverUpdate's histories, for snapshots and tests: {weights' h / m, weights' v, bias' h / m, bias' v}; empty before the

@@ -664,6 +664,12 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "prune_kernels_us")) return (long)(p->prune_kernels_ms * 1e3);
   if (!strcmp(key, "prune_map_us")) return (long)(p->prune_map_ms * 1e3);
   if (!strcmp(key, "prune_realign_us")) return (long)(p->prune_realign_ms * 1e3);
+  if (!strcmp(key, "rewire_count")) return p->rewire_count;
+  if (!strcmp(key, "rewire_last_dropped")) return p->rewire_last_dropped;
+  if (!strcmp(key, "rewire_last_grown")) return p->rewire_last_grown;
+  if (!strcmp(key, "rewire_kernels_us")) return (long)(p->rewire_kernels_ms * 1e3);
+  if (!strcmp(key, "rewire_map_us")) return (long)(p->rewire_map_ms * 1e3);
+  if (!strcmp(key, "rewire_realign_us")) return (long)(p->rewire_realign_ms * 1e3);
   if (!strcmp(key, "is_f64")) return p->is_f64 ? 1 : 0;
   if (!strcmp(key, "host_aligned")) return p->host_aligned ? 1 : 0;
   if (!strcmp(key, "kernel_choice")) {

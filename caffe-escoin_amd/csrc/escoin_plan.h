@@ -266,6 +266,11 @@ struct escoin_plan {
   // the last escoin_plan_prune's phases: the selection / scan / map launches (device events), the call's wall time until
   // the host holds the map, and from there to the end of the re-align
   double prune_kernels_ms = 0.0, prune_map_ms = 0.0, prune_realign_ms = 0.0;
+
+  // Rewiring (rewire_select.hip): stats "rewire_count" (rewires since the plan was created), "rewire_last_dropped",
+  // "rewire_last_grown", and the last escoin_plan_rewire's phases, as for a prune
+  long rewire_count = 0, rewire_last_dropped = 0, rewire_last_grown = 0;
+  double rewire_kernels_ms = 0.0, rewire_map_ms = 0.0, rewire_realign_ms = 0.0;
 };
 
 namespace escoin {

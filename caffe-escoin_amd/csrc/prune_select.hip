@@ -23,6 +23,7 @@
 //                                 entry_map[e] = kept-strictly before e + min(ties before e, ties that fit), or -1
 //   escoin_compact_kernel         dst[entry_map[e]] = src[e], one lane per old entry, one plain store
 // No host round trip between them; THRESHOLD mode and the trivial KEEP cases skip the select.
+// The launch sequence, the descriptor check and the host form of the map are shared with rewire_select.hip (prune_select.h).
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -35,6 +36,7 @@
 
 #include "escoin_plan.h"
 #include "prune_rules.h"
+#include "prune_select.h"
 
 namespace escoin {
 namespace {
@@ -42,15 +44,7 @@ namespace {
 using prune::kItems;
 using prune::kThreads;
 using prune::kTileEntries;
-
-// The head of the workspace (prune::kStateBytes).  During the select: prefix = the key bytes chosen so far, remaining =
-// entries still to take among the keys that match it.  Afterwards: prefix = T, remaining = the ties that fit.
-struct SelState {
-  unsigned long long prefix, remaining;
-  unsigned ge, pad;
-  unsigned long long total_gt, total_eq;
-};
-static_assert(sizeof(SelState) <= prune::kStateBytes, "selection state outgrew its slot");
+using prune::SelState;   // the head of the workspace (prune_select.h)
 
 template <typename K> __device__ inline K key_mask() { return (K)(~(K)0 >> 1); }
 
@@ -219,19 +213,87 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// What both entry points check of the descriptor; thr_key: key(threshold) in the plan's Dtype.
+}  // namespace
+
+namespace prune {
+
+// What every entry point checks of the descriptor; thr_key: key(threshold) in the plan's Dtype.
 template <typename T>
-int check_desc(const escoin_prune_desc *d, typename prune::KeyOf<T>::type *thr_key) {
+int check_desc(const escoin_prune_desc *d, typename KeyOf<T>::type *thr_key) {
   if (!d) return fail(ESCOIN_EINVAL, "prune: null descriptor");
   if (d->mode != ESCOIN_PRUNE_KEEP && d->mode != ESCOIN_PRUNE_THRESHOLD) return fail(ESCOIN_EINVAL, "prune: unknown mode");
   if (d->mode == ESCOIN_PRUNE_KEEP && d->keep < 0) return fail(ESCOIN_EINVAL, "prune: keep must be >= 0");
   *thr_key = 0;
   if (d->mode == ESCOIN_PRUNE_THRESHOLD) {
     if (std::isnan(d->threshold) || std::signbit(d->threshold)) return fail(ESCOIN_EINVAL, "prune: threshold must be >= 0 and not NaN");
-    *thr_key = prune::key_bits((T)d->threshold);
+    *thr_key = key_bits((T)d->threshold);
   }
   return ESCOIN_OK;
 }
+template int check_desc<float>(const escoin_prune_desc *, uint32_t *);
+template int check_desc<double>(const escoin_prune_desc *, uint64_t *);
+
+void launch_select_init(SelState *st, unsigned *hist, int hist_words, unsigned long long prefix, unsigned long long remaining,
+                        unsigned ge, hipStream_t stream) {
+  hipLaunchKernelGGL(escoin_prune_init_kernel, dim3(1), dim3(kThreads), 0, stream, st, hist, hist_words, prefix, remaining, ge);
+}
+
+void launch_select_choose(SelState *st, const unsigned *hist, hipStream_t stream) {
+  hipLaunchKernelGGL(escoin_prune_choose_kernel, dim3(1), dim3(64), 0, stream, st, hist);
+}
+
+template <typename K>
+int launch_selection(const K *keys, long nnz, const LaunchPlan &lp, const escoin_prune_desc *d, K thr_key, void *ws,
+                     int *entry_map_dev, hipStream_t stream) {
+  SelState *st = static_cast<SelState *>(ws);
+  unsigned *hist = reinterpret_cast<unsigned *>(static_cast<char *>(ws) + kStateBytes);
+  unsigned *tile_cnt = hist + (size_t)lp.passes * 256;
+  const bool select = d->mode == ESCOIN_PRUNE_KEEP && d->keep > 0 && d->keep < nnz;
+  Boundary<K> b{0, 0, 1};                                  // keep >= nnz: everything stays
+  if (d->mode == ESCOIN_PRUNE_THRESHOLD) b = select_threshold<K>(thr_key);
+  else if (d->keep == 0) b = Boundary<K>{std::numeric_limits<K>::max(), 0, 0};
+  const dim3 block(kThreads);
+  launch_select_init(st, hist, lp.passes * 256, (unsigned long long)(select ? 0 : b.T), (unsigned long long)(select ? d->keep : 0),
+                     (unsigned)(select ? 0 : b.ge), stream);
+  if (select) {
+    for (int pass = 0; pass < lp.passes; ++pass) {
+      hipLaunchKernelGGL((escoin_prune_hist_kernel<K>), dim3(lp.hist_grid), block, 0, stream, keys, nnz, pass, lp.passes,
+                         (const SelState *)st, hist + (size_t)pass * 256);
+      launch_select_choose(st, hist + (size_t)pass * 256, stream);
+    }
+  }
+  hipLaunchKernelGGL((escoin_prune_count_kernel<K>), dim3(lp.tile_grid), block, 0, stream, keys, nnz, lp.tiles, (const SelState *)st, tile_cnt);
+  hipLaunchKernelGGL(escoin_prune_scan_kernel, dim3(1), block, 0, stream, lp.tiles, st, tile_cnt);
+  hipLaunchKernelGGL((escoin_prune_apply_kernel<K>), dim3(lp.tile_grid), block, 0, stream, keys, nnz, lp.tiles, (const SelState *)st,
+                     (const unsigned *)tile_cnt, entry_map_dev);
+  ESCOIN_HIP_TRY(hipGetLastError());
+  return ESCOIN_OK;
+}
+template int launch_selection<uint32_t>(const uint32_t *, long, const LaunchPlan &, const escoin_prune_desc *, uint32_t, void *, int *, hipStream_t);
+template int launch_selection<uint64_t>(const uint64_t *, long, const LaunchPlan &, const escoin_prune_desc *, uint64_t, void *, int *, hipStream_t);
+
+template <typename T>
+long host_entry_map(escoin_plan *p, const escoin_prune_desc *d, typename KeyOf<T>::type thr_key, int *map) {
+  typedef typename KeyOf<T>::type K;
+  const long nnz = plan_nnz(p);
+  std::vector<T> flat;
+  const T *score = static_cast<const T *>(d->score);
+  if (!score) {
+    flat = flat_entries(plan_vals<T>(p));
+    score = flat.data();
+  }
+  const std::vector<K> keys = keys_of<T>(score, nnz);
+  const Boundary<K> b = d->mode == ESCOIN_PRUNE_KEEP ? select_keep<K>(keys.data(), nnz, d->keep) : select_threshold<K>(thr_key);
+  return build_map<K>(keys.data(), nnz, b, map);
+}
+template long host_entry_map<float>(escoin_plan *, const escoin_prune_desc *, uint32_t, int *);
+template long host_entry_map<double>(escoin_plan *, const escoin_prune_desc *, uint64_t, int *);
+
+}  // namespace prune
+
+namespace {
+
+using prune::check_desc;
 
 // The plan re-aligned on the kept entries of `map` (host, old nnz elements): a new host CSR through set_csr's own checks,
 // then -- for a device-aligned plan -- the device side rebuilt from it, as escoin_plan_set_csr does.
@@ -274,14 +336,6 @@ int prune_device(escoin_plan *p, const escoin_prune_desc *d, int *entry_map_dev,
       ESCOIN_HIP_TRY(own_map.alloc(sizeof(int) * (size_t)nnz));
       entry_map_dev = own_map.get<int>();
     }
-    SelState *st = ws.get<SelState>();
-    unsigned *hist = reinterpret_cast<unsigned *>(ws.get<char>() + prune::kStateBytes);
-    unsigned *tile_cnt = hist + (size_t)lp.passes * 256;
-    const bool select = d->mode == ESCOIN_PRUNE_KEEP && d->keep > 0 && d->keep < nnz;
-    prune::Boundary<K> b{0, 0, 1};                                  // keep >= nnz: everything stays
-    if (d->mode == ESCOIN_PRUNE_THRESHOLD) b = prune::select_threshold<K>(thr_key);
-    else if (d->keep == 0) b = prune::Boundary<K>{std::numeric_limits<K>::max(), 0, 0};
-    const dim3 block(kThreads);
     // (events around the launches: stat "prune_kernels_us"; this call synchronises and allocates anyway)
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     ESCOIN_HIP_TRY(hipEventCreate(&ev0));
@@ -294,20 +348,7 @@ int prune_device(escoin_plan *p, const escoin_prune_desc *d, int *entry_map_dev,
       ~EventGuard() { (void)hipEventDestroy(a), (void)hipEventDestroy(b); }
     } guard{ev0, ev1};
     ESCOIN_HIP_TRY(hipEventRecord(ev0, stream));
-    hipLaunchKernelGGL(escoin_prune_init_kernel, dim3(1), block, 0, stream, st, hist, lp.passes * 256,
-                       (unsigned long long)(select ? 0 : b.T), (unsigned long long)(select ? d->keep : 0), (unsigned)(select ? 0 : b.ge));
-    if (select) {
-      for (int pass = 0; pass < lp.passes; ++pass) {
-        hipLaunchKernelGGL((escoin_prune_hist_kernel<K>), dim3(lp.hist_grid), block, 0, stream, keys, nnz, pass, lp.passes,
-                           (const SelState *)st, hist + (size_t)pass * 256);
-        hipLaunchKernelGGL(escoin_prune_choose_kernel, dim3(1), dim3(64), 0, stream, st, (const unsigned *)(hist + (size_t)pass * 256));
-      }
-    }
-    hipLaunchKernelGGL((escoin_prune_count_kernel<K>), dim3(lp.tile_grid), block, 0, stream, keys, nnz, lp.tiles, (const SelState *)st, tile_cnt);
-    hipLaunchKernelGGL(escoin_prune_scan_kernel, dim3(1), block, 0, stream, lp.tiles, st, tile_cnt);
-    hipLaunchKernelGGL((escoin_prune_apply_kernel<K>), dim3(lp.tile_grid), block, 0, stream, keys, nnz, lp.tiles, (const SelState *)st,
-                       (const unsigned *)tile_cnt, entry_map_dev);
-    ESCOIN_HIP_TRY(hipGetLastError());
+    if (const int rc = prune::launch_selection<K>(keys, nnz, lp, d, thr_key, ws.get<void>(), entry_map_dev, stream)) return rc;
     ESCOIN_HIP_TRY(hipEventRecord(ev1, stream));
     // the plan is about to re-align, which synchronises anyway: the map comes to the host here
     ESCOIN_HIP_TRY(hipMemcpyAsync(map.data(), entry_map_dev, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToHost, stream));
@@ -340,21 +381,12 @@ int prune_host(escoin_plan *p, const escoin_prune_desc *d, int *entry_map, long 
   K thr_key = 0;
   if (const int rc = check_desc<T>(d, &thr_key)) return rc;
   const long nnz = plan_nnz(p);
-  std::vector<T> flat;
-  const T *score = static_cast<const T *>(d->score);
-  if (!score) {
-    flat = flat_entries(plan_vals<T>(p));
-    score = flat.data();
-  }
-  const std::vector<K> keys = prune::keys_of<T>(score, nnz);
-  const prune::Boundary<K> b = d->mode == ESCOIN_PRUNE_KEEP ? prune::select_keep<K>(keys.data(), nnz, d->keep)
-                                                             : prune::select_threshold<K>(thr_key);
   std::vector<int> own_map;
   if (!entry_map) {
     own_map.resize((size_t)nnz);
     entry_map = own_map.data();
   }
-  const long kept = prune::build_map<K>(keys.data(), nnz, b, entry_map);
+  const long kept = prune::host_entry_map<T>(p, d, thr_key, entry_map);
   ++p->prune_count;
   p->prune_last_dropped = nnz - kept;
   if (new_nnz) *new_nnz = kept;

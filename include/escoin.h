@@ -520,7 +520,7 @@ ESCOIN_API int escoin_backward_values_cpu_f64(escoin_plan *plan, const double *b
  * These entry points write the new values into every copy, in place.
  *   dense_w  blobs_[0] (M x C/g x KH x KW).  Only the elements at the plan's CSR positions are read; every other element
  *            is ignored (it is 0 under the masked gradient; a NaN there does no harm).  A caller that GREW the pattern
- *            must call escoin_weight_align.  A kept weight whose new value is exactly 0 stays in the CSR as an explicit
+ *            must call escoin_weight_align (or grow it with escoin_plan_rewire, "Rewiring" below).  A kept weight whose new value is exactly 0 stays in the CSR as an explicit
  *            zero (-0.0 stays -0.0).
  *   values   (escoin_plan_set_values) the compact array, nnz elements in the order of escoin_plan_get_csr -- what rank 0
  *            would broadcast after a step instead of a blob.  escoin_backward_values writes its values_diff in the same
@@ -704,6 +704,67 @@ ESCOIN_API int escoin_plan_prune(escoin_plan *plan, const escoin_prune_desc *des
 ESCOIN_API int escoin_plan_prune_cpu(escoin_plan *plan, const escoin_prune_desc *desc, int *entry_map, long *new_nnz);
 ESCOIN_API int escoin_compact_entries(const int *entry_map, long old_nnz, int elem_bytes /* 4 | 8 */, const void *src,
                            void *dst, int on_device, void *stream);
+
+/* ---- Rewiring: drop and grow in one call, with one re-align, and the map that carries the solver state over ----
+ * Dynamic sparse training (RigL, SET, any prune-and-regrow schedule) drops the k smallest weights and grows k positions
+ * where a dense score -- usually the dense gradient's magnitude -- is largest.  escoin_plan_prune shrinks the pattern;
+ * this is the verb that GROWS it, and it does both at once.
+ * Notation: kdim = Cg * KH * KW, D = M * kdim; a position is p = oc * kdim + colidx with oc counted over all conv
+ * groups, i.e. an element of blobs_[0]; ascending p over a pattern is escoin_plan_get_csr's order; P is the plan's
+ * current pattern with nnz entries.  The rule, exact and the same on device and host:
+ *   Drop (optional): `drop` is an escoin_prune_desc whose rule is exactly escoin_plan_prune's, over the plan's entries:
+ *   KEEP or THRESHOLD, score NULL (the current values, the device's if it is authoritative) or a per-entry score.  It
+ *   yields the kept set K, a subset of P; drop == NULL gives K = P.
+ *   Grow: the candidates are the positions NOT in P.  A position this call drops is not a candidate in the same call, so
+ *   the two selections are independent and each equals its stand-alone rule (a caller who wants to regrow a weight it
+ *   just dropped calls escoin_plan_prune first).  key(s) is prune's key: the bits of s without the sign bit, as an
+ *   unsigned integer; no floating-point comparison is made anywhere.  A NaN score ranks HIGHEST and is grown first; a zero
+ *   score is an ordinary candidate.  The candidates are ordered by (key(score[p]) descending, p ascending) and the first
+ *   n_grown = min(grow, D - nnz) are grown.  `score` is a dense array of D elements of the plan's Dtype, shaped like
+ *   blobs_[0]; it is read only at candidate positions (a NaN inside the pattern does no harm).
+ *   Result: the new pattern is K united with the grown set G, in ascending p.  Kept entries keep their value bits.  A
+ *   grown entry is an explicit +0.0; with init != NULL it takes the bits of init[p] instead (init: a dense D-element
+ *   array, read only at grown positions).  entry_map[e], e in [0, old nnz), is the entry's new index, or -1 if it was
+ *   dropped.  grown[i], i in [0, n_grown), is the new entry index of the i-th grown position, in ascending position order
+ *   (grown_dev holds `grow` ints; only the first n_grown are written).  entry_map, grown, new_nnz and n_grown may each be
+ *   NULL.
+ * Afterwards every consumer of the plan behaves BIT FOR BIT like a fresh plan with the same options aligned by
+ * escoin_plan_set_csr on the new CSR, and only ONE re-align happened.  The backward state and the update state are
+ * dropped, as on any align.  When nothing is dropped and nothing is grown (grow == 0 or no candidates, and no drop or a
+ * drop that keeps everything) the plan is untouched and the map is the identity.  With grow == 0 the map and the plan equal
+ * escoin_plan_prune's with the same descriptor, bit for bit.  An aligned plan with nnz 0 can be grown.
+ * The call synchronises and allocates, like a prune: it is NOT CAPTURABLE.  It orders itself behind the last update's
+ * stream, as a prune does.
+ * Carrying momentum over -- the recipe.  The compact per-entry arrays (history, history2, a pending values_diff) move with
+ * the existing escoin_compact_entries into a ZERO-FILLED array of the new nnz:
+ *     new_h = zeros(new_nnz);  escoin_compact_entries(entry_map, old_nnz, elem_bytes, h, new_h, on_device, stream);
+ * kept entries keep their history, grown entries (the indices in `grown`) start with zero momentum, and the next
+ * escoin_solver_step runs on (new values_diff, new_h, new_h2) as if nothing had happened to the kept entries.
+ * A dense score is available today from a dense weight gradient computed outside the plan, or from a shadow plan aligned
+ * by escoin_plan_set_csr on the full pattern with option wgrad_kernel = ESCOIN_WGRAD_MFMA.
+ * Device side (rewire_select.hip): the drop is prune's launch sequence; over the D positions a mark launch (the host
+ * CSR's entry positions -> an int per position: candidate, dropped, or the kept entry's index), a radix select over the
+ * candidates' keys (one histogram launch per key byte, the digit chosen on the device), per-tile counts, one workgroup's
+ * scan, one launch that writes entry_map through the entries' positions and one that writes grown and the grown
+ * values -- integer atomics only, and no workgroup waits for another one.
+ * escoin_plan_rewire_cpu: the same rule as plain host code (rewire_rules), for plans aligned by escoin_weight_align_cpu;
+ * score, init, entry_map and grown are then host pointers; no HIP call.
+ * Errors follow escoin_plan_prune's (ESCOIN_EINVAL for a NULL desc or a bad `drop`, ESCOIN_ENODEVICE, ESCOIN_ESTATE);
+ * ESCOIN_EINVAL also for grow < 0, for score == NULL with grow > 0, and for D >= 2^31.
+ * Stats: "rewire_count", "rewire_last_dropped", "rewire_last_grown"; of the last escoin_plan_rewire "rewire_kernels_us"
+ * (every launch, the drop's included, by device events), "rewire_map_us" (the call's wall time until the host holds the
+ * map and the grown list), "rewire_realign_us" (from there to the end of the re-align; 0 when the plan was left
+ * untouched).  The "prune_*" stats are not touched by a rewire. */
+typedef struct escoin_rewire_desc {
+  const escoin_prune_desc *drop;  /* NULL: nothing dropped */
+  long grow;                      /* >= 0 */
+  const void *score;              /* D elements, plan's Dtype; device (host for _cpu); may be NULL iff grow == 0 */
+  const void *init;               /* NULL: grown entries are +0.0 */
+} escoin_rewire_desc;
+ESCOIN_API int escoin_plan_rewire(escoin_plan *plan, const escoin_rewire_desc *desc, int *entry_map_dev, int *grown_dev,
+                       long *new_nnz, long *n_grown, void *stream);
+ESCOIN_API int escoin_plan_rewire_cpu(escoin_plan *plan, const escoin_rewire_desc *desc, int *entry_map, int *grown,
+                           long *new_nnz, long *n_grown);
 
 #ifdef __cplusplus
 }
