@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <memory>
 #include <new>
 #include <stdexcept>
@@ -29,6 +30,11 @@ int fail(int code, const std::string &msg);
     if (e__ != hipSuccess)                                                            \
       return ::escoin::fail(ESCOIN_EHIP, std::string(#expr) + ": " + hipGetErrorString(e__)); \
   } while (0)
+
+// Milliseconds of wall time since t0 (the "*_ms" fields of a plan)
+inline double ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 
 // No exception may cross the C ABI (std::bad_alloc from the host vectors, std::system_error from a thread team):
 // every entry point that allocates runs its body through this.

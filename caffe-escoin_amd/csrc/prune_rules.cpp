@@ -94,7 +94,7 @@ bool apply_entry_map(int Mg, const std::vector<std::vector<int>> &rowptr, const 
   return e == map_len;
 }
 
-LaunchPlan launch_plan(long nnz, int elem_bytes) {
+LaunchPlan launch_plan(long nnz, int elem_bytes, int counts) {
   LaunchPlan lp;
   const long n = std::max<long>(nnz, 0);
   lp.passes = elem_bytes == 8 ? 8 : 4;
@@ -102,7 +102,7 @@ LaunchPlan launch_plan(long nnz, int elem_bytes) {
   lp.hist_grid = (int)std::max<long>(1, std::min<long>((n + kThreads - 1) / kThreads, kMaxGrid));
   lp.tile_grid = (int)std::max<long>(1, std::min<long>(lp.tiles, kMaxGrid));
   lp.scan_steps = (int)((lp.tiles + kScanWidth - 1) / kScanWidth);
-  lp.ws_bytes = kStateBytes + (size_t)lp.passes * 256 * sizeof(uint32_t) + (size_t)std::max<long>(lp.tiles, 1) * 2 * sizeof(uint32_t);
+  lp.ws_bytes = kStateBytes + (size_t)lp.passes * 256 * sizeof(uint32_t) + (size_t)std::max<long>(lp.tiles, 1) * (size_t)counts * sizeof(uint32_t);
   return lp;
 }
 

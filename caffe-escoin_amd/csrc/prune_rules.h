@@ -62,7 +62,8 @@ template <typename T>
 bool apply_entry_map(int Mg, const std::vector<std::vector<int>> &rowptr, const std::vector<std::vector<int>> &colidx,
                      const std::vector<std::vector<T>> &values, const int *map, long map_len, FlatCsr<T> *out);
 
-// The launch plan of the device kernels, a function of nnz and the element size alone.
+// The launch plan of the device kernels (radix_select.h), a function of the number of indices the select ranges over (a
+// prune: nnz), the element size and the counts a tile carries alone.
 constexpr int kThreads = 256;                       // lanes of every workgroup (four full waves of 64)
 constexpr int kItems = 4;                           // entries per lane of a tile
 constexpr int kTileEntries = kThreads * kItems;     // entries one workgroup of the count / apply kernels covers per step
@@ -74,10 +75,10 @@ struct LaunchPlan {
   int hist_grid;    // workgroups of a histogram launch (grid stride over the entries)
   int tile_grid;    // workgroups of the count / apply launches (grid stride over the tiles)
   int scan_steps;   // loop steps of the one scanning workgroup: ceil(tiles / kScanWidth)
-  size_t ws_bytes;  // the device workspace: selection state, sizeof(K) histograms, two counts per tile
+  size_t ws_bytes;  // the device workspace: selection state, sizeof(K) histograms, `counts` counts per tile
 };
 constexpr size_t kStateBytes = 64;                  // the selection state at the head of the workspace
-LaunchPlan launch_plan(long nnz, int elem_bytes);
+LaunchPlan launch_plan(long nnz, int elem_bytes, int counts = 2);   // (a prune's two: kept strictly, tie)
 
 }  // namespace prune
 }  // namespace escoin

@@ -7,12 +7,6 @@
 namespace escoin {
 namespace rewire {
 
-using prune::kMaxGrid;
-using prune::kScanWidth;
-using prune::kStateBytes;
-using prune::kThreads;
-using prune::kTileEntries;
-
 std::vector<int> entry_positions(int Mg, int kdim, const std::vector<std::vector<int>> &rowptr,
                                  const std::vector<std::vector<int>> &colidx) {
   std::vector<int> pos;
@@ -95,15 +89,9 @@ bool merge(int Mg, int kdim, const std::vector<std::vector<int>> &rowptr, const 
 
 LaunchPlan launch_plan(long D, long nnz, int elem_bytes) {
   LaunchPlan lp;
-  const long d = std::max<long>(D, 0), n = std::max<long>(nnz, 0);
-  lp.passes = elem_bytes == 8 ? 8 : 4;
-  lp.tiles = (d + kTileEntries - 1) / kTileEntries;
-  lp.hist_grid = (int)std::max<long>(1, std::min<long>((d + kThreads - 1) / kThreads, kMaxGrid));
-  lp.tile_grid = (int)std::max<long>(1, std::min<long>(lp.tiles, kMaxGrid));
-  lp.mark_grid = (int)std::max<long>(1, std::min<long>((n + kThreads - 1) / kThreads, kMaxGrid));
-  lp.scan_steps = (int)((lp.tiles + kScanWidth - 1) / kScanWidth);
-  lp.ws_bytes = kStateBytes + (size_t)lp.passes * 256 * sizeof(uint32_t) + (size_t)std::max<long>(lp.tiles, 1) * kCounts * sizeof(uint32_t);
-  lp.slot_bytes = (size_t)std::max<long>(d, 1) * sizeof(int);
+  static_cast<prune::LaunchPlan &>(lp) = prune::launch_plan(D, elem_bytes, kCounts);
+  lp.mark_grid = prune::launch_plan(nnz, elem_bytes).hist_grid;   // a grid stride over the entries, as a prune's histogram
+  lp.slot_bytes = (size_t)std::max<long>(D, 1) * sizeof(int);
   return lp;
 }
 

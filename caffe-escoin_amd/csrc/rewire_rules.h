@@ -42,14 +42,8 @@ bool merge(int Mg, int kdim, const std::vector<std::vector<int>> &rowptr, const 
 constexpr int kCounts = 3;                  // per tile: kept entries, candidates grown strictly, candidates that tie
 constexpr int kSlotCandidate = -1;          // slot[p]: not in the pattern (what a byte fill of 0xff leaves)
 constexpr int kSlotDropped = -2;            // slot[p]: an entry this call drops; slot[p] >= 0: the kept entry's old index
-struct LaunchPlan {
-  int passes;        // histogram passes of the radix select over the candidates: one per key byte
-  long tiles;        // ceil(D / kTileEntries)
-  int hist_grid;     // workgroups of a histogram launch (grid stride over the positions)
-  int tile_grid;     // workgroups of the count / map / grown launches (grid stride over the tiles)
+struct LaunchPlan : prune::LaunchPlan {   // prune's plan over the D positions with kCounts counts per tile, and
   int mark_grid;     // workgroups of the launch that marks the entries' positions (grid stride over the entries)
-  int scan_steps;    // loop steps of the one scanning workgroup: ceil(tiles / kScanWidth)
-  size_t ws_bytes;   // selection state, sizeof(K) histograms, kCounts counts per tile
   size_t slot_bytes; // one int per position
 };
 LaunchPlan launch_plan(long D, long nnz, int elem_bytes);

@@ -8,32 +8,22 @@
 // never a value of the key itself, so a zero score (key 0) and a NaN with every mantissa bit set (the largest key) are
 // ordinary candidates.
 //
-// What keeps these kernels from hanging a machine: plain C++ (no inline assembly); integer atomics only, whose result does
-// not depend on their order (no float atomics); NO WORKGROUP EVER WAITS FOR ANOTHER WORKGROUP -- no decoupled look-back, no
-// spin loop, no cooperative launch: a value one workgroup needs from another crosses a kernel boundary; every loop is
-// bounded by D or nnz (grid strides over positions, entries or tiles, 256 bins, ceil(tiles / 256) scan steps); grids are
-// capped (prune_rules.h kMaxGrid).  Every workgroup is 256 lanes, four full waves of 64: no lane leaves before the last
-// ballot or barrier of its kernel, predicates are folded into the flags.  Every store is bounds-checked against the
-// length of the array it goes to.
+// The select, count and scan kernels and the rank arithmetic are radix_select.h's, over SlotSource with kCounts counts per
+// tile; the contract that keeps these kernels from hanging a machine is written there and holds for the two kernels here,
+// whose loops are bounded by D or nnz.  Every store is bounds-checked against the length of the array it goes to.
 //
 //   (hipMemsetAsync)              slot[p] = -1 for every position: a candidate
 //   escoin_rewire_mark_kernel     per entry e at position pos[e]: slot = e if the drop keeps it, -2 if not (and then
 //                                 entry_map[e] = -1)
-//   escoin_prune_init_kernel      (prune_select.hip) zeroes the histograms, writes the selection state
-//   escoin_rewire_hist_kernel     one launch per key byte, top byte first: the digit's histogram over the candidates' keys
-//                                 that match the prefix chosen so far -- 256 LDS bins, then one global atomic per bin
-//   escoin_prune_choose_kernel    (prune_select.hip) one workgroup: the digit whose suffix sum reaches the remaining count
-//   escoin_rewire_count_kernel    per tile of 1024 positions: kept entries, candidates above the boundary key T, ties
-//   escoin_rewire_scan_kernel     one workgroup: exclusive scan of the three counts over the tiles, 256 tiles a step
-//   escoin_rewire_apply_kernel    per tile: ballot / popcount ranks inside the tile plus the tile's offsets give every
-//                                 flagged position its new entry index = kept before + grown before.  <0>: entry_map
-//                                 through slot[p]; <1>: grown, the grown positions and the grown values
+//   (launch_select)               the boundary key T among the candidates; per tile of 1024 positions the kept entries,
+//                                 the candidates above T and the ties, scanned over the tiles
+//   escoin_rewire_apply_kernel    per tile: tile_ranks gives every flagged position its new entry index = kept before +
+//                                 grown before.  <0>: entry_map through slot[p]; <1>: grown, the grown positions and the
+//                                 grown values
 // No host round trip between them; the trivial grow counts (0, every candidate) skip the select.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <limits>
 #include <string>
@@ -42,20 +32,15 @@
 #include "escoin_plan.h"
 #include "prune_rules.h"
 #include "prune_select.h"
+#include "radix_select.h"
 #include "rewire_rules.h"
 
 namespace escoin {
 namespace {
 
-using prune::kItems;
-using prune::kThreads;
-using prune::kTileEntries;
-using prune::SelState;
 using rewire::kCounts;
 using rewire::kSlotCandidate;
 using rewire::kSlotDropped;
-
-template <typename K> __device__ inline K key_mask() { return (K)(~(K)0 >> 1); }
 
 __global__ void __launch_bounds__(256) escoin_rewire_mark_kernel(const int *__restrict__ pos, const int *__restrict__ drop_map,
                                                                   long nnz, long D, int *slot, int *entry_map) {
@@ -67,151 +52,54 @@ __global__ void __launch_bounds__(256) escoin_rewire_mark_kernel(const int *__re
   }
 }
 
+// The D positions; the candidates are those slot[p] marks as outside the pattern.  Flags: bit 0 a kept entry, bit 1 a
+// candidate grown strictly, bit 2 a candidate that ties; score == NULL (nothing is grown): no candidate is flagged and no
+// score is read.
 template <typename K>
-__global__ void __launch_bounds__(256) escoin_rewire_hist_kernel(const K *__restrict__ score, const int *__restrict__ slot, long D,
-                                                                  int pass, int passes, const SelState *__restrict__ st,
-                                                                  unsigned *hist) {
-  __shared__ unsigned bins[256];
-  bins[threadIdx.x] = 0u;
-  __syncthreads();
-  const int shift = 8 * (passes - 1 - pass);
-  const K prefix = (K)st->prefix;
-  for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < D; p += (long)gridDim.x * 256) {
-    if (slot[p] != kSlotCandidate) continue;
-    const K k = score[p] & key_mask<K>();
-    if (pass == 0 || (k >> (shift + 8)) == prefix) atomicAdd(&bins[(unsigned)(k >> shift) & 0xffu], 1u);
+struct SlotSource {
+  const K *__restrict__ score;
+  const int *__restrict__ slot;
+  __device__ bool candidate(long p) const { return slot[p] == kSlotCandidate; }
+  __device__ K key(long p) const { return score[p] & key_mask<K>(); }
+  __device__ unsigned flags(long p, K T, unsigned ge) const {
+    const int s = slot[p];
+    if (s >= 0) return 1u;
+    if (s != kSlotCandidate || !score) return 0u;
+    const K k = key(p);
+    if (ge) return k >= T ? 2u : 0u;
+    return (k > T ? 2u : 0u) | (k == T ? 4u : 0u);
   }
-  __syncthreads();
-  const unsigned c = bins[threadIdx.x];
-  if (c) atomicAdd(&hist[threadIdx.x], c);
-}
-
-// the flags of position p under the state's rule: bit 0 a kept entry, bit 1 a candidate grown strictly, bit 2 a candidate
-// that ties; score == NULL (nothing is grown): no candidate is flagged and no score is read
-template <typename K>
-__device__ inline unsigned pos_flags(const K *__restrict__ score, const int *__restrict__ slot, long p, long D, K T, unsigned ge) {
-  if (p >= D) return 0u;
-  const int s = slot[p];
-  if (s >= 0) return 1u;
-  if (s != kSlotCandidate || !score) return 0u;
-  const K k = score[p] & key_mask<K>();
-  if (ge) return k >= T ? 2u : 0u;
-  return (k > T ? 2u : 0u) | (k == T ? 4u : 0u);
-}
-
-template <typename K>
-__global__ void __launch_bounds__(256) escoin_rewire_count_kernel(const K *__restrict__ score, const int *__restrict__ slot, long D,
-                                                                   long tiles, const SelState *__restrict__ st, unsigned *tile_cnt) {
-  __shared__ unsigned cnt[kCounts];
-  const K T = (K)st->prefix;
-  const unsigned ge = st->ge;
-  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    if (threadIdx.x < kCounts) cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    unsigned c[kCounts] = {0u, 0u, 0u};
-    for (int i = 0; i < kItems; ++i) {
-      const unsigned f = pos_flags<K>(score, slot, tile * kTileEntries + i * kThreads + threadIdx.x, D, T, ge);
-      for (int k = 0; k < kCounts; ++k) c[k] += __popcll(__ballot(f & (1u << k)));
-    }
-    if ((threadIdx.x & 63) == 0)
-      for (int k = 0; k < kCounts; ++k) atomicAdd(&cnt[k], c[k]);
-    __syncthreads();
-    if (threadIdx.x < kCounts) tile_cnt[tile * kCounts + threadIdx.x] = cnt[threadIdx.x];
-    __syncthreads();
-  }
-}
-
-// In place: tile_cnt[kCounts t + k] becomes the number of flag-k positions in the tiles before t.
-__global__ void __launch_bounds__(256) escoin_rewire_scan_kernel(long tiles, unsigned *tile_cnt) {
-  __shared__ unsigned wsum[4][kCounts];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned long long carry[kCounts] = {0ull, 0ull, 0ull};
-  for (long base = 0; base < tiles; base += 256) {
-    const long t = base + threadIdx.x;
-    unsigned c[kCounts], s[kCounts];
-    for (int k = 0; k < kCounts; ++k) s[k] = c[k] = t < tiles ? tile_cnt[t * kCounts + k] : 0u;
-    for (int d = 1; d < 64; d <<= 1)      // inclusive scan inside the wave
-      for (int k = 0; k < kCounts; ++k) {
-        const unsigned u = __shfl_up(s[k], d, 64);
-        if (lane >= d) s[k] += u;
-      }
-    if (lane == 63)
-      for (int k = 0; k < kCounts; ++k) wsum[wave][k] = s[k];
-    __syncthreads();
-    for (int k = 0; k < kCounts; ++k) {
-      unsigned before = 0, all = 0;
-      for (int w = 0; w < 4; ++w) {
-        if (w < wave) before += wsum[w][k];
-        all += wsum[w][k];
-      }
-      if (t < tiles) tile_cnt[t * kCounts + k] = (unsigned)(carry[k] + before + s[k] - c[k]);
-      carry[k] += all;
-    }
-    __syncthreads();   // wsum is rewritten by the next step
-  }
-}
+};
 
 // WHAT == 0: entry_map[slot[p]] = the new index of every kept entry.  WHAT == 1: for the i-th grown position (ascending):
 // grown[i] = its new index, grown_pos[i] = p, grown_val[i] = the bits of init[p], or +0.0.
 template <typename K, int WHAT>
-__global__ void __launch_bounds__(256) escoin_rewire_apply_kernel(const K *__restrict__ score, const int *__restrict__ slot, long D,
-                                                                   long tiles, const SelState *__restrict__ st,
+__global__ void __launch_bounds__(256) escoin_rewire_apply_kernel(const SlotSource<K> src, long D, long tiles,
+                                                                   const SelState *__restrict__ st,
                                                                    const unsigned *__restrict__ tile_off, long nnz, int *entry_map,
                                                                    long n_grown, int *grown, int *grown_pos, K *grown_val,
                                                                    const K *__restrict__ init) {
-  __shared__ unsigned wsum[kItems][4][kCounts];
   const K T = (K)st->prefix;
   const unsigned ge = st->ge;
   const unsigned long long ties = st->remaining;
-  const int wave = threadIdx.x >> 6;
-  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    unsigned f[kItems], in[kItems][kCounts];   // flags; flag-k positions before this lane in its wave
-    for (int i = 0; i < kItems; ++i) {
-      f[i] = pos_flags<K>(score, slot, tile * kTileEntries + i * kThreads + threadIdx.x, D, T, ge);
-      for (int k = 0; k < kCounts; ++k) {
-        const unsigned long long b = __ballot(f[i] & (1u << k));
-        in[i][k] = __builtin_amdgcn_mbcnt_hi((unsigned)(b >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)b, 0u));
-        if ((threadIdx.x & 63) == 0) wsum[i][wave][k] = __popcll(b);
-      }
-    }
-    __syncthreads();
-    // a tile's order is item-major: position (i, lane) follows every position of items < i and of earlier waves of item i
-    unsigned long long run[kCounts];
-    for (int k = 0; k < kCounts; ++k) run[k] = tile_off[tile * kCounts + k];
-    for (int i = 0; i < kItems; ++i) {
-      unsigned long long r[kCounts];
-      for (int k = 0; k < kCounts; ++k) {
-        unsigned before = 0, all = 0;
-        for (int w = 0; w < 4; ++w) {
-          if (w < wave) before += wsum[i][w][k];
-          all += wsum[i][w][k];
-        }
-        r[k] = run[k] + before + in[i][k];
-        run[k] += all;
-      }
-      const long p = tile * kTileEntries + i * kThreads + threadIdx.x;
+  for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x)
+    tile_ranks<kCounts>(src, D, tile, T, ge, tile_off, [=](long p, unsigned f, const unsigned long long (&r)[kCounts]) {
       const unsigned long long grown_before = r[1] + (r[2] < ties ? r[2] : ties);
       const unsigned long long index = r[0] + grown_before;
       if (WHAT == 0) {
-        if (f[i] & 1u) {
-          const long e = slot[p];
+        if (f & 1u) {
+          const long e = src.slot[p];
           if (e >= 0 && e < nnz) entry_map[e] = (int)index;
         }
       } else {
-        const bool is_grown = (f[i] & 2u) || ((f[i] & 4u) && r[2] < ties);
+        const bool is_grown = (f & 2u) || ((f & 4u) && r[2] < ties);
         if (is_grown && grown_before < (unsigned long long)n_grown) {
           grown[grown_before] = (int)index;
           grown_pos[grown_before] = (int)p;
           grown_val[grown_before] = init ? init[p] : (K)0;
         }
       }
-    }
-    __syncthreads();   // wsum is rewritten by the next tile
-  }
-}
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    });
 }
 
 // What both entry points check of the descriptor beyond the plan's state.
@@ -238,14 +126,8 @@ int realign_rewired(escoin_plan *p, const int *keep_map, const std::vector<int> 
     return fail(ESCOIN_EINVAL, "rewire: the grown positions do not fit the plan's CSR");
   if (expect_map && entry_map && std::memcmp(expect_map, entry_map, sizeof(int) * (size_t)plan_nnz(p)) != 0)
     return fail(ESCOIN_EINVAL, "rewire: the device's entry map is not the merged CSR's");
-  const int rc = set_csr_host<T>(p, csr.rowptr.data(), csr.colidx.data(), csr.values.data(), csr.nnz_per_group.data());
-  if (rc != ESCOIN_OK) return rc;
-  const double ms_csr = ms_since(t0);
-  const int rc2 = device ? realign_from_host_csr(p, stream) : ESCOIN_OK;
-  if (getenv("ESCOIN_VERBOSE"))
-    fprintf(stderr, "[escoin] rewire: %zu entries, %zu of them grown: new host CSR %.2f ms, device side rebuilt in %.2f ms\n",
-            csr.colidx.size(), grown_pos.size(), ms_csr, ms_since(t0) - ms_csr);
-  return rc2;
+  return prune::realign_on<T>(p, csr, device, stream, t0,
+                              "rewire: " + std::to_string(csr.colidx.size()) + " entries, " + std::to_string(grown_pos.size()) + " of them grown");
 }
 
 void note_stats(escoin_plan *p, long dropped, long grown) {
@@ -301,18 +183,8 @@ int rewire_device(escoin_plan *p, const escoin_rewire_desc *d, int *entry_map_de
       ESCOIN_HIP_TRY(gval_dev.alloc(sizeof(T) * (size_t)n_grown));
     }
     const dim3 block(kThreads);
-    // (events around the launches: stat "rewire_kernels_us"; this call synchronises and allocates anyway)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    ESCOIN_HIP_TRY(hipEventCreate(&ev0));
-    if (hipEventCreate(&ev1) != hipSuccess) {
-      (void)hipEventDestroy(ev0);
-      return fail(ESCOIN_EHIP, "rewire: hipEventCreate failed");
-    }
-    struct EventGuard {
-      hipEvent_t a, b;
-      ~EventGuard() { (void)hipEventDestroy(a), (void)hipEventDestroy(b); }
-    } guard{ev0, ev1};
-    ESCOIN_HIP_TRY(hipEventRecord(ev0, stream));
+    prune::EventTimer timer;   // stat "rewire_kernels_us"
+    if (const int rc = timer.start("rewire", stream)) return rc;
     if (nnz > 0 && d->drop) {
       const K *keys = d->drop->score ? static_cast<const K *>(d->drop->score) : p->gen.vals.get<const K>();
       const prune::LaunchPlan dlp = prune::launch_plan(nnz, (int)sizeof(T));
@@ -324,35 +196,21 @@ int rewire_device(escoin_plan *p, const escoin_rewire_desc *d, int *entry_map_de
     if (nnz > 0)
       hipLaunchKernelGGL(escoin_rewire_mark_kernel, dim3(lp.mark_grid), block, 0, stream, pos_dev.get<const int>(),
                          (const int *)drop_map.get<int>(), nnz, D, slot.get<int>(), entry_map_dev);
-    SelState *st = ws.get<SelState>();
-    unsigned *hist = reinterpret_cast<unsigned *>(ws.get<char>() + prune::kStateBytes);
-    unsigned *tile_cnt = hist + (size_t)lp.passes * 256;
-    const K *score = n_grown > 0 ? static_cast<const K *>(d->score) : nullptr;
-    const bool select = n_grown > 0 && n_grown < n_cand;
+    const SelectWorkspace w(ws.get<void>(), lp);
+    const SlotSource<K> src{n_grown > 0 ? static_cast<const K *>(d->score) : nullptr, slot.get<const int>()};
     // n_grown == n_cand: every candidate (key >= 0); n_grown == 0: none (no key exceeds or equals the largest K)
     const prune::Boundary<K> b = n_grown > 0 ? prune::Boundary<K>{0, 0, 1} : prune::Boundary<K>{std::numeric_limits<K>::max(), 0, 0};
-    prune::launch_select_init(st, hist, lp.passes * 256, (unsigned long long)(select ? 0 : b.T), (unsigned long long)(select ? n_grown : 0),
-                              (unsigned)(select ? 0 : b.ge), stream);
-    if (select) {
-      for (int pass = 0; pass < lp.passes; ++pass) {
-        hipLaunchKernelGGL((escoin_rewire_hist_kernel<K>), dim3(lp.hist_grid), block, 0, stream, score, slot.get<const int>(), D, pass,
-                           lp.passes, (const SelState *)st, hist + (size_t)pass * 256);
-        prune::launch_select_choose(st, hist + (size_t)pass * 256, stream);
-      }
-    }
-    hipLaunchKernelGGL((escoin_rewire_count_kernel<K>), dim3(lp.tile_grid), block, 0, stream, score, slot.get<const int>(), D, lp.tiles,
-                       (const SelState *)st, tile_cnt);
-    hipLaunchKernelGGL(escoin_rewire_scan_kernel, dim3(1), block, 0, stream, lp.tiles, tile_cnt);
+    launch_select<kCounts>(src, D, lp, w, b, n_grown < n_cand ? n_grown : 0, stream);
     if (nnz > 0)
-      hipLaunchKernelGGL((escoin_rewire_apply_kernel<K, 0>), dim3(lp.tile_grid), block, 0, stream, score, slot.get<const int>(), D, lp.tiles,
-                         (const SelState *)st, (const unsigned *)tile_cnt, nnz, entry_map_dev, n_grown, (int *)nullptr, (int *)nullptr,
-                         (K *)nullptr, (const K *)nullptr);
+      hipLaunchKernelGGL((escoin_rewire_apply_kernel<K, 0>), dim3(lp.tile_grid), block, 0, stream, src, D, lp.tiles, (const SelState *)w.st,
+                         (const unsigned *)w.tile_cnt, nnz, entry_map_dev, n_grown, (int *)nullptr, (int *)nullptr, (K *)nullptr,
+                         (const K *)nullptr);
     if (n_grown > 0)
-      hipLaunchKernelGGL((escoin_rewire_apply_kernel<K, 1>), dim3(lp.tile_grid), block, 0, stream, score, slot.get<const int>(), D, lp.tiles,
-                         (const SelState *)st, (const unsigned *)tile_cnt, nnz, (int *)nullptr, n_grown, grown_dev, gpos_dev.get<int>(),
-                         gval_dev.get<K>(), static_cast<const K *>(d->init));
+      hipLaunchKernelGGL((escoin_rewire_apply_kernel<K, 1>), dim3(lp.tile_grid), block, 0, stream, src, D, lp.tiles, (const SelState *)w.st,
+                         (const unsigned *)w.tile_cnt, nnz, (int *)nullptr, n_grown, grown_dev, gpos_dev.get<int>(), gval_dev.get<K>(),
+                         static_cast<const K *>(d->init));
     ESCOIN_HIP_TRY(hipGetLastError());
-    ESCOIN_HIP_TRY(hipEventRecord(ev1, stream));
+    if (const int rc = timer.stop(stream)) return rc;
     // the plan is about to re-align, which synchronises anyway: the map and the grown list come to the host here
     if (nnz > 0) ESCOIN_HIP_TRY(hipMemcpyAsync(map.data(), entry_map_dev, sizeof(int) * (size_t)nnz, hipMemcpyDeviceToHost, stream));
     if (n_grown > 0) {
@@ -360,9 +218,7 @@ int rewire_device(escoin_plan *p, const escoin_rewire_desc *d, int *entry_map_de
       ESCOIN_HIP_TRY(hipMemcpyAsync(gval.data(), gval_dev.get<T>(), sizeof(T) * (size_t)n_grown, hipMemcpyDeviceToHost, stream));
     }
     ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
-    float kernels_ms = 0.f;
-    ESCOIN_HIP_TRY(hipEventElapsedTime(&kernels_ms, ev0, ev1));
-    p->rewire_kernels_ms = kernels_ms;
+    if (const int rc = timer.elapsed_ms(&p->rewire_kernels_ms)) return rc;
   }
   p->rewire_map_ms = ms_since(t_start);
   long kept = 0;
@@ -437,15 +293,7 @@ int escoin_plan_rewire(escoin_plan *p, const escoin_rewire_desc *desc, int *entr
                        long *n_grown, void *stream) {
   return guarded([&]() -> int {
     if (const int rc = check_args(p, desc)) return rc;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
-      return fail(ESCOIN_ENODEVICE, "rewire: no HIP device (a plan aligned by escoin_weight_align_cpu is rewired by escoin_plan_rewire_cpu)");
-    if (!p->aligned)
-      return fail(ESCOIN_ESTATE, p->host_aligned ? "rewire: the plan is aligned on the host only (use escoin_plan_rewire_cpu)"
-                                                 : "rewire called before weight_align / set_csr");
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
-      return fail(ESCOIN_ESTATE, "rewire: the current device is not the device the plan was aligned on");
+    if (const int rc = prune::check_device_plan(p, "rewire")) return rc;
     return p->is_f64 ? rewire_device<double>(p, desc, entry_map_dev, grown_dev, new_nnz, n_grown, (hipStream_t)stream)
                      : rewire_device<float>(p, desc, entry_map_dev, grown_dev, new_nnz, n_grown, (hipStream_t)stream);
   });

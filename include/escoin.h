@@ -673,9 +673,11 @@ ESCOIN_API int escoin_solver_array_step_cpu_f64(const escoin_solver_desc *desc, 
  * When nothing is dropped (keep >= nnz, every key passes the threshold, nnz == 0) the plan is untouched: no re-align, the
  * states stay, the map is the identity, ESCOIN_OK, "prune_last_dropped" = 0.
  * The call synchronises (`stream`, and the last update's stream) and allocates: it is NOT CAPTURABLE.
- * Device side (prune_select.hip): a radix select of the keep-th largest key, 8 bits a pass (4 histogram launches for float,
- * 8 for double; the digit is chosen on the device, no host round trip between passes), then per-tile counts, one
- * workgroup's scan of the tile counts and the map -- integer atomics only, and no workgroup waits for another one.
+ * Device side (prune_select.hip, on the kernels of radix_select.h that escoin_plan_rewire shares): a radix select of the
+ * keep-th largest key, 8 bits a pass (select_hist_kernel: 4 histogram launches for float, 8 for double; the digit is chosen
+ * on the device by select_choose_kernel, no host round trip between passes), then per-tile counts (select_count_kernel),
+ * one workgroup's scan of the tile counts (select_scan_kernel) and the map (escoin_prune_apply_kernel) -- integer atomics
+ * only, and no workgroup waits for another one.
  * escoin_plan_prune_cpu: the same rule as plain host code, for plans aligned by escoin_weight_align_cpu; no HIP call.
  * escoin_compact_entries: dst[entry_map[e]] = src[e] wherever entry_map[e] >= 0 -- what the caller runs over history,
  * history2, a pending values_diff or its own copy of the values.  dst holds the new nnz elements; src and dst must NOT

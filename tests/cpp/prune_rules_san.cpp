@@ -155,14 +155,16 @@ static void check_launch_plan() {
   const long sizes[] = {0, 1, 255, 256, 257, kTileEntries - 1, kTileEntries, kTileEntries + 1, 3L * kTileEntries + 1,
                         512L * 512 * 9, (long)kTileEntries * kScanWidth + 1, 2147483647L};
   for (int elem : {4, 8})
-    for (long n : sizes) {
-      const LaunchPlan lp = launch_plan(n, elem);
-      if (lp.passes != elem) die("passes");
-      if (lp.tiles * kTileEntries < n || (lp.tiles > 0 && (lp.tiles - 1) * kTileEntries >= n)) die("tiles");
-      if (lp.hist_grid < 1 || lp.hist_grid > kMaxGrid || lp.tile_grid < 1 || lp.tile_grid > kMaxGrid) die("grid cap");
-      if ((long)lp.scan_steps * kScanWidth < lp.tiles) die("scan steps");
-      if (lp.ws_bytes < kStateBytes + (size_t)elem * 1024 + (size_t)lp.tiles * 8) die("workspace");
-    }
+    for (long n : sizes)
+      for (int counts : {2, 3}) {
+        const LaunchPlan lp = launch_plan(n, elem, counts);
+        if (lp.passes != elem) die("passes");
+        if (lp.tiles * kTileEntries < n || (lp.tiles > 0 && (lp.tiles - 1) * kTileEntries >= n)) die("tiles");
+        if (lp.hist_grid < 1 || lp.hist_grid > kMaxGrid || lp.tile_grid < 1 || lp.tile_grid > kMaxGrid) die("grid cap");
+        if ((long)lp.scan_steps * kScanWidth < lp.tiles) die("scan steps");
+        if (lp.ws_bytes < kStateBytes + (size_t)elem * 1024 + (size_t)lp.tiles * counts * 4) die("workspace");
+        if (counts == 2 && lp.ws_bytes != launch_plan(n, elem).ws_bytes) die("default counts");
+      }
   if (kTileEntries % 64 != 0 || kThreads % 64 != 0) die("tile is not whole waves");
   std::printf("OK launch_plan\n");
 }
