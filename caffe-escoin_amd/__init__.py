@@ -57,6 +57,8 @@ API_SYMBOLS = [
     "escoin_plan_prune", "escoin_plan_prune_cpu", "escoin_compact_entries",
     # Rewiring
     "escoin_plan_rewire", "escoin_plan_rewire_cpu",
+    # Dense weight gradient (rewire's grow score)
+    "escoin_dense_wgrad", "escoin_dense_wgrad_f64", "escoin_dense_wgrad_cpu", "escoin_dense_wgrad_cpu_f64",
 ]
 SOLVER_SGD, SOLVER_NESTEROV, SOLVER_ADAM = 0, 1, 2
 REG_NONE, REG_L2, REG_L1 = 0, 1, 2
@@ -311,6 +313,9 @@ def lib():
     L.escoin_plan_rewire.argtypes = [vp, rp, vp, vp, C.POINTER(C.c_long), C.POINTER(C.c_long), vp]
     L.escoin_plan_rewire_cpu.restype = ip
     L.escoin_plan_rewire_cpu.argtypes = [vp, rp, vp, vp, C.POINTER(C.c_long), C.POINTER(C.c_long)]
+    for name in ("escoin_dense_wgrad", "escoin_dense_wgrad_f64", "escoin_dense_wgrad_cpu", "escoin_dense_wgrad_cpu_f64"):
+        f = getattr(L, name)
+        f.restype, f.argtypes = ip, [vp] * 5 + [ip, ip, vp if "cpu" not in name else ip]
     L.escoin_compact_entries.restype = ip
     L.escoin_compact_entries.argtypes = [vp, C.c_long, ip, vp, vp, ip, vp]
     L.escoin_cpu_kernel_name.restype = cp
@@ -573,6 +578,64 @@ class Plan(object):
         check(lib().escoin_plan_rewire_cpu(self._h, C.byref(d), _np_ptr(entry_map), _np_ptr(grown), C.byref(new_nnz), C.byref(n_grown)),
               "escoin_plan_rewire_cpu")
         return entry_map, grown[:n_grown.value]
+
+    # ---- dense weight gradient (include/escoin.h "Dense weight gradient") -------------------------------------------------
+    def dense_wgrad(self, top_diff, bottom, top=None, out=None, accumulate=False, n_images=None, stream=None):
+        """escoin_dense_wgrad: the dense M x Cg x KH x KW weight gradient -- every position of blobs_[0], inside and
+        outside the pattern -- on torch CUDA tensors, asynchronous on `stream` (default torch's current stream).  top: the
+        forward's top blob (fuse_relu plans).  out: the tensor to write (accumulate=True: to add onto); None = a new one.
+        n_images: the leading images to reduce over (default all of top_diff's).  The result is what rewire() takes as
+        score=."""
+        import torch
+        d = self.desc
+        g = top_diff
+        dt = g.dtype
+        assert g.is_cuda and dt in (torch.float32, torch.float64) and g.is_contiguous()
+        assert tuple(g.shape[1:]) == (d.M,) + tuple(self.out_hw), "top_diff shape mismatch"
+        n = g.shape[0] if n_images is None else int(n_images)
+        for t in (bottom, top):
+            if t is not None:
+                assert t.is_cuda and t.dtype == dt and t.is_contiguous() and t.shape[0] >= min(n, g.shape[0])
+        shape = (d.M,) + self._grad_shapes()
+        if out is None:
+            if accumulate:
+                raise EscoinError("dense_wgrad: accumulate needs the blob to add onto (out=)")
+            out = torch.empty(shape, device=g.device, dtype=dt)
+        assert out.is_cuda and out.dtype == dt and out.is_contiguous() and tuple(out.shape) == shape, "out: wrong dtype / shape / layout"
+
+        def _p(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+
+        if stream is None:
+            stream = C.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
+        fn = lib().escoin_dense_wgrad_f64 if dt == torch.float64 else lib().escoin_dense_wgrad
+        check(fn(self._h, _p(bottom), _p(top), _p(g), _p(out), n, int(bool(accumulate)), stream), "escoin_dense_wgrad")
+        return out
+
+    def dense_wgrad_cpu(self, top_diff, bottom, top=None, out=None, accumulate=False, n_images=None, n_threads=0):
+        """escoin_dense_wgrad_cpu: the same on numpy arrays (float32 or float64, matching the aligned weights), on any plan
+        with a host CSR."""
+        d = self.desc
+        f64 = top_diff.dtype == np.float64
+        dt = np.float64 if f64 else np.float32
+        g = np.ascontiguousarray(top_diff, dt)
+        assert tuple(g.shape[1:]) == (d.M,) + tuple(self.out_hw), "top_diff shape mismatch"
+        n = g.shape[0] if n_images is None else int(n_images)
+        x = None if bottom is None else np.ascontiguousarray(bottom, dt)
+        t = None if top is None else np.ascontiguousarray(top, dt)
+        shape = (d.M,) + self._grad_shapes()
+        if out is None:
+            if accumulate:
+                raise EscoinError("dense_wgrad_cpu: accumulate needs the blob to add onto (out=)")
+            out = np.empty(shape, dt)
+        assert out.dtype == dt and out.flags["C_CONTIGUOUS"] and tuple(out.shape) == shape, "out: wrong dtype / shape / layout"
+
+        def _p(a):
+            return _np_ptr(a) if a is not None else None
+
+        fn = lib().escoin_dense_wgrad_cpu_f64 if f64 else lib().escoin_dense_wgrad_cpu
+        check(fn(self._h, _p(x), _p(t), _p(g), _p(out), n, int(bool(accumulate)), int(n_threads)), "escoin_dense_wgrad_cpu")
+        return out
 
     # ---- Caffe::CPU mode (no device needed) ----------------------------------------------------
     def weight_align_cpu(self, dense_w):

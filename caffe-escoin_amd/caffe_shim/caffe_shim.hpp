@@ -127,6 +127,8 @@ template <> struct EscApi<float> {
   static int solver_step_cpu(escoin_plan *p, const escoin_solver_desc *d, float *g, float *h, float *h2, float *w) { return escoin_solver_step_cpu(p, d, g, h, h2, w); }
   static int solver_array_step(const escoin_solver_desc *d, long n, float *w, float *g, float *h, float *h2, void *s) { return escoin_solver_array_step(d, n, w, g, h, h2, s); }
   static int solver_array_step_cpu(const escoin_solver_desc *d, long n, float *w, float *g, float *h, float *h2) { return escoin_solver_array_step_cpu(d, n, w, g, h, h2); }
+  static int dense_wgrad(escoin_plan *p, const float *b, const float *t, const float *td, float *dd, int n, int acc, void *s) { return escoin_dense_wgrad(p, b, t, td, dd, n, acc, s); }
+  static int dense_wgrad_cpu(escoin_plan *p, const float *b, const float *t, const float *td, float *dd, int n, int acc, int threads) { return escoin_dense_wgrad_cpu(p, b, t, td, dd, n, acc, threads); }
 };
 template <> struct EscApi<double> {
   static int weight_align(escoin_plan *p, const double *w, int on_dev, void *s) { return escoin_weight_align_f64(p, w, on_dev, s); }
@@ -142,6 +144,8 @@ template <> struct EscApi<double> {
   static int solver_step_cpu(escoin_plan *p, const escoin_solver_desc *d, double *g, double *h, double *h2, double *w) { return escoin_solver_step_cpu_f64(p, d, g, h, h2, w); }
   static int solver_array_step(const escoin_solver_desc *d, long n, double *w, double *g, double *h, double *h2, void *s) { return escoin_solver_array_step_f64(d, n, w, g, h, h2, s); }
   static int solver_array_step_cpu(const escoin_solver_desc *d, long n, double *w, double *g, double *h, double *h2) { return escoin_solver_array_step_cpu_f64(d, n, w, g, h, h2); }
+  static int dense_wgrad(escoin_plan *p, const double *b, const double *t, const double *td, double *dd, int n, int acc, void *s) { return escoin_dense_wgrad_f64(p, b, t, td, dd, n, acc, s); }
+  static int dense_wgrad_cpu(escoin_plan *p, const double *b, const double *t, const double *td, double *dd, int n, int acc, int threads) { return escoin_dense_wgrad_cpu_f64(p, b, t, td, dd, n, acc, threads); }
 };
 
 // syncedmem.hpp:56-91: lazily mirrored host/device buffer with a head state.
@@ -612,6 +616,31 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
         ESC_CHECK(gr[i] >= 0 && gr[i] < new_nnz);
         data[new_pos[(size_t)gr[i]]] = values[(size_t)gr[i]];
       }
+    }
+  }
+  // The DENSE weight gradient of the layer's bottom / top pairs (include/escoin.h, "Dense weight gradient"; the
+  // reference's weight_gpu_gemm result, base_conv_layer.cpp:877-889): `out` is reshaped like blobs_[0] and its DATA is
+  // overwritten with the gradient at every position, inside and outside the pattern -- what escoin_rewire_desc.score
+  // reads (out->gpu_data() for a plan with a device side, out->cpu_data() otherwise).  blobs_[0]'s diff is not touched.
+  // Caffe::GPU, float: the matrix-core kernel on the device, asynchronous on Caffe::stream().  Caffe::GPU, double: the
+  // library has no double kernel on the device, so this falls back to the CPU entry point on the blobs' cpu_data (a copy
+  // of bottom, top and top's diff to the host).  Caffe::CPU: the CPU entry point.  A layer that is not aligned yet aligns
+  // first.
+  void DenseWeightDiff(const vector<Blob<Dtype> *> &top, const vector<Blob<Dtype> *> &bottom, Blob<Dtype> *out) {
+    ESC_CHECK(plan_ != nullptr && out != nullptr);
+    const bool gpu = Caffe::mode() == Caffe::GPU;
+    if (!aligned_ || (gpu && !aligned_on_device_)) WeightAlign();
+    out->Reshape(this->blobs_[0]->shape());
+    const bool device = gpu && sizeof(Dtype) == 4;
+    ESC_CHECK(!top.empty() && top.size() == bottom.size());
+    for (size_t i = 0; i < top.size(); ++i) {
+      if (device)
+        ESCOIN_CHECK(EscApi<Dtype>::dense_wgrad(plan_, bottom[i]->gpu_data(), fuse_relu_ ? top[i]->gpu_data() : nullptr,
+                                                top[i]->gpu_diff(), out->mutable_gpu_data(), num_, i > 0, Caffe::stream()));
+      else
+        ESCOIN_CHECK(EscApi<Dtype>::dense_wgrad_cpu(plan_, bottom[i]->cpu_data(), fuse_relu_ ? top[i]->cpu_data() : nullptr,
+                                                    top[i]->cpu_diff(), out->mutable_cpu_data(), num_, i > 0,
+                                                    Caffe::cpu_threads()));
     }
   }
   // SolverUpdate's histories, for snapshots and tests: {weights' h / m, weights' v, bias' h / m, bias' v}; empty before the

@@ -509,6 +509,31 @@ bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp) {
   return true;
 }
 
+bool dwg_plan(const Geometry &g, bool is_f64, int n_cu, int max_splits, DwgPlan *dp) {
+  DwgPlan p;
+  if (!wgm_plan(g, is_f64, &p.tile)) return false;
+  const long chunks = p.tile.chunks;      // >= 1: N, OH, OW >= 1
+  const long tiles = (long)g.d.group * p.tile.mtiles * p.tile.ktiles;
+  // every span length once, the longest (fewest splits) first: a later one must be strictly cheaper to win
+  const long resident = (long)kDwgResidentPerCu * std::max(n_cu, 1);
+  long best_span = chunks, best_cost = -1;
+  for (long span = chunks; span >= 1; --span) {
+    const long s = (chunks + span - 1) / span;
+    if (s > 1 && ((max_splits > 0 && s > max_splits) || tiles * s > kDwgMaxRounds * resident)) break;   // (s only grows from here)
+    // rounds in 1/1024: what the workgroups fill, and half of what the last round leaves empty; one round at least
+    const long filled = tiles * s * 1024 / resident, whole = (tiles * s + resident - 1) / resident * 1024;
+    const long rounds = std::max(1024L, (filled + whole) / 2);
+    const long cost = rounds * span + (1024 / kDwgSplitsPerChunkCost) * s;
+    if (best_cost < 0 || cost < best_cost) best_cost = cost, best_span = span;
+  }
+  p.span = (int)best_span;
+  p.splits = (int)((chunks + best_span - 1) / best_span);
+  p.positions = (long)g.d.M * g.kdim;
+  p.slab_bytes = sizeof(float) * (size_t)p.splits * (size_t)p.positions;
+  *dp = p;
+  return true;
+}
+
 bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp) {
   const escoin_conv_desc &d = g.d;
   if (is_f64) return false;

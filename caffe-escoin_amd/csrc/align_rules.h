@@ -153,6 +153,32 @@ struct WgmPlan {
 // column tiles: the grid).
 bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp);
 
+// ---- the dense weight gradient on the matrix cores (dense_wgrad.hip) ------------------------------------------------
+// wgm_plan's predicate and tiles; the pixel axis is split over `splits` workgroups per tile, each walking `span` whole
+// chunks with one accumulator set, so that a layer with few tiles still fills the device.  With tiles = group * mtiles *
+// ktiles and resident = kDwgResidentPerCu * n_cu workgroups on the device at once (four per CU: what the kernel's 70
+// VGPRs + 16 AGPRs and 33 KB of LDS allow), a split into S = ceil(chunks / span) spans costs
+//     max(1, (r + ceil(r)) / 2) * span       r = tiles * S / resident rounds of resident workgroups (a partly filled last
+//                                            round counts half of what it leaves empty: its workgroups start as slots
+//                                            free up) x the chunks each workgroup walks
+//   + S / kDwgSplitsPerChunkCost             the sum kernel's serial walk over the splits,
+// in integer arithmetic (rounds in 1/1024, floor), and the plan takes the cheapest span (ties: the fewest splits) among
+// those with S <= max_splits (when > 0) and at most kDwgMaxRounds rounds -- or S = 1 where nothing else qualifies.  A
+// model of the launch's shape, never a timing; what was tried on the MI355X is in profiles/grow_score_mi355x.md.  Split s covers chunks [s * span, min((s + 1) * span, chunks)):
+// every chunk once, none of them empty.  The partial slab is splits x M*Cg*KH*KW floats: at most about kDwgMaxRounds *
+// resident tiles of 16 KB, whatever the batch size.
+constexpr int kDwgResidentPerCu = 4;
+constexpr long kDwgMaxRounds = 4;
+constexpr long kDwgSplitsPerChunkCost = 512;
+struct DwgPlan {
+  WgmPlan tile;              // tile.chunks = chunks of the full batch
+  int span = 0;              // chunks per split
+  int splits = 0;            // workgroups per tile at the full batch (grid x)
+  long positions = 0;        // D = M * Cg * KH * KW
+  size_t slab_bytes = 0;     // sizeof(float) * splits * positions
+};
+bool dwg_plan(const Geometry &g, bool is_f64, int n_cu, int max_splits, DwgPlan *dp);
+
 // ---- the fp32-MFMA data-gradient kernel (dgrad_mfma.hip) -----------------------------------------------------------
 // The bottom pixels split into stride_h x stride_w phases ((h + pad_h) % stride_h, (w + pad_w) % stride_w); inside a phase
 // every pixel has the same contributing taps, so a phase is a stride-1 implicit GEMM.  One workgroup of four waves per

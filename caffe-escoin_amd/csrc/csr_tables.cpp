@@ -125,16 +125,23 @@ WgmTables wgrad_mfma_tables(const CsrView &v, int tile_m, int tile_k) {
     t.ent[((size_t)c.grp * g.Mg + c.m) * g.kdim + c.col] = (int)c.e;
     ++t.tile_cnt[((size_t)c.grp * mtiles + c.m / tile_m) * ktiles + c.col / tile_k];
   });
-  t.ktab.assign(at_least_one(4L * ktiles * tile_k), 0);
+  t.ktab = im2col_ktab(g, tile_k);
+  return t;
+}
+
+std::vector<int> im2col_ktab(const Geometry &g, int tile_k) {
+  const escoin_conv_desc &d = g.d;
+  const int ktiles = (g.kdim + tile_k - 1) / tile_k;
+  std::vector<int> ktab(at_least_one(4L * ktiles * tile_k), 0);
   for (int k = 0; k < g.kdim; ++k) {
     const Tap tap = decode_tap(k, d.KH, d.KW);
     const int dy = tap.kr * d.dil_h, dx = tap.kc * d.dil_w;
-    t.ktab[4 * (size_t)k] = (tap.ic * d.H + dy) * d.W + dx;
-    t.ktab[4 * (size_t)k + 1] = dy;
-    t.ktab[4 * (size_t)k + 2] = dx;
-    t.ktab[4 * (size_t)k + 3] = 1;
+    ktab[4 * (size_t)k] = (tap.ic * d.H + dy) * d.W + dx;
+    ktab[4 * (size_t)k + 1] = dy;
+    ktab[4 * (size_t)k + 2] = dx;
+    ktab[4 * (size_t)k + 3] = 1;
   }
-  return t;
+  return ktab;
 }
 
 DgmTables dgrad_mfma_tables(const CsrView &v, const DgmPlan &plan) {

@@ -103,6 +103,8 @@ StagedTables staged_tables(const CsrView &v, int icb, int nblk, int cs, int Wp);
 // past kdim (the last tile's padding) carry {0, 0, 0, 0}: "no such column".
 struct WgmTables { std::vector<int> ent, tile_cnt, ktab; };
 WgmTables wgrad_mfma_tables(const CsrView &v, int tile_m, int tile_k);
+// That ktab alone: a function of the geometry, no CSR (the dense weight gradient's state, dense_wgrad.hip, needs no more).
+std::vector<int> im2col_ktab(const Geometry &g, int tile_k);
 
 // The MFMA data-gradient kernel's tables for a tile plan of align_rules.h dgm_plan (P phases, phase index = row residue *
 // stride_w + column residue; ctiles channel tiles of tile_c per conv group; steps of step_k columns):

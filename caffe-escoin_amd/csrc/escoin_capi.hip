@@ -63,7 +63,8 @@ DeviceBytes device_bytes(const escoin_plan *p) {
   const DenseArrays &dn = p->dense;
   DeviceBytes b{p->gen.rowptr.bytes() + p->gen.taps.bytes() + p->gen.vals.bytes() + t.stream.bytes() + t.unit_hdr.bytes() +
                     t.chan.bytes() + t.jit.code_bytes + dn.w.bytes() + dn.ktab.bytes() + dn.sk_ws.bytes() + p->col.bytes(),
-                0, 0};
+                0, 0, 0};
+  if (const DenseWgradState *w = p->dwg.get()) b.dwg = w->ktab.bytes() + w->part.bytes();
   if (const UpdState *u = p->upd.get())
     b.upd = u->src.bytes() + u->off.bytes() + u->buf.bytes() + u->wpos.bytes() + u->stage.bytes() + u->e_ptr.bytes() + u->e_off.bytes() + u->e_buf.bytes();
   if (const BwdState *s = p->bwd.get())
@@ -108,6 +109,16 @@ long upd_stat(const escoin_plan *p, const char *key) {
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
 
+long dwg_stat(const escoin_plan *p, const char *key) {
+  const DenseWgradState *w = p->dwg.get();
+  if (!strcmp(key, "dwg_device_bytes")) return (long)device_bytes(p).dwg;
+  if (!strcmp(key, "dwg_splits")) return w ? w->splits : 0;
+  if (!strcmp(key, "dwg_lds_bytes")) return w ? (long)w->lds_bytes : 0;
+  if (!strcmp(key, "dwg_count")) return p->dwg_count;
+  return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
+}
+
+// (the dense weight gradient's state, p->dwg, is a function of the descriptor alone: no align frees it)
 static void free_device(escoin_plan *p) {
   p->upd.reset();
   p->dev_authoritative = false;
@@ -443,6 +454,11 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->wgrad_channel_block = value;
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "dense_wgrad_splits")) {
+      if (value < 0) return fail(ESCOIN_EINVAL, "dense_wgrad_splits must be >= 0");
+      p->dense_wgrad_splits = value;
+      return ESCOIN_OK;
+    }
     if (!strcmp(key, "body_variant")) {
       if (value < -1 || value > 0) return fail(ESCOIN_EINVAL, "body_variant must be -1 (automatic) or 0 (generic)");
       p->body_variant = value;
@@ -654,6 +670,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "streamk")) return p->dense.sk_used ? 1 : 0;
   if (!strncmp(key, "bwd_", 4) || !strncmp(key, "wgrad_", 6) || !strncmp(key, "dgrad_", 6)) return bwd_stat(p, key);
   if (!strncmp(key, "upd", 3)) return upd_stat(p, key);
+  if (!strncmp(key, "dwg_", 4)) return dwg_stat(p, key);
   if (!strcmp(key, "prune_count")) return p->prune_count;
   if (!strcmp(key, "prune_last_dropped")) return p->prune_last_dropped;
   if (!strcmp(key, "prune_tile_entries")) return prune::kTileEntries;
@@ -696,7 +713,7 @@ int escoin_plan_get_csr_f64(const escoin_plan *p, int *rowptr, int *colidx, doub
 size_t escoin_plan_workspace_bytes(const escoin_plan *p) {
   if (!p) return 0;
   const DeviceBytes b = device_bytes(p);
-  return b.fwd + b.bwd + b.upd;
+  return b.fwd + b.bwd + b.upd + b.dwg;
 }
 
 const char *escoin_plan_kernel_name(const escoin_plan *p) {

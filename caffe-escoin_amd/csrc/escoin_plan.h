@@ -124,6 +124,19 @@ struct BwdState {
   std::vector<int> tsrc;
 };
 
+// What the first escoin_dense_wgrad on a plan builds (dense_wgrad.hip).  A function of the descriptor, the device's CU
+// count and option "dense_wgrad_splits" alone -- not of the pattern or the values -- so no align resets it: it lives until
+// the plan is destroyed (or until a call finds the plan aligned on another device, which builds it anew there).
+struct DenseWgradState {
+  int device = -1;
+  int mtiles = 0, ktiles = 0;          // tiles per conv group along the output channels / the columns
+  int span = 0, splits = 0;            // chunks per split, splits of the full batch (align_rules.h dwg_plan)
+  long positions = 0;                  // D = M * Cg * KH * KW
+  size_t lds_bytes = 0;
+  DeviceBuffer ktab;                   // [4 * ktiles * tile_k] the im2col decode of a column (csr_tables.h im2col_ktab)
+  DeviceBuffer part;                   // [splits][D] partial sums
+};
+
 // What the first escoin_update_values on an alignment builds (update_values.hip); reset with the device side.  One flat
 // scatter list over every device word that holds a weight of this alignment: destination k receives the value of CSR
 // entry src[k] at element off[k] (elements of the plan's Dtype) of buffer buf[k].
@@ -277,6 +290,13 @@ struct escoin_plan {
   // "rewire_last_grown", and the last escoin_plan_rewire's phases, as for a prune
   long rewire_count = 0, rewire_last_dropped = 0, rewire_last_grown = 0;
   double rewire_kernels_ms = 0.0, rewire_map_ms = 0.0, rewire_realign_ms = 0.0;
+
+  // Dense weight gradient (dense_wgrad.hip): option "dense_wgrad_splits" (0: the rule decides, n: at most n splits of the
+  // pixel axis), the state the first escoin_dense_wgrad builds -- kept across aligns -- and stat "dwg_count" (device
+  // calls since the plan was created)
+  int dense_wgrad_splits = 0;
+  std::unique_ptr<escoin::DenseWgradState> dwg;
+  long dwg_count = 0;
 };
 
 namespace escoin {
@@ -301,8 +321,10 @@ template <> inline std::vector<std::vector<double>> &plan_vals<double>(escoin_pl
 
 // escoin_capi.hip: the device bytes a plan's owners hold -- the forward's (stat "device_bytes") and the backward
 // state's, its transposed plan's included (stat "bwd_device_bytes"); escoin_plan_workspace_bytes is their sum.
-struct DeviceBytes { size_t fwd, bwd, upd; };
+struct DeviceBytes { size_t fwd, bwd, upd, dwg; };   // dwg: the dense weight gradient's state (stat "dwg_device_bytes")
 DeviceBytes device_bytes(const escoin_plan *p);
+// dense_wgrad.hip builds the dense weight gradient's state; escoin_capi.hip answers its "dwg_*" stats
+long dwg_stat(const escoin_plan *p, const char *key);
 // escoin_capi.hip: the shared tail of weight_align / set_csr -- rebuilds the device side from the host CSR
 int realign_from_host_csr(escoin_plan *p, hipStream_t stream);
 // escoin_capi.hip: the first half of set_csr -- validates a CSR (flat, as escoin_plan_set_csr takes it) and copies it into

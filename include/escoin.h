@@ -742,8 +742,8 @@ ESCOIN_API int escoin_compact_entries(const int *entry_map, long old_nnz, int el
  *     new_h = zeros(new_nnz);  escoin_compact_entries(entry_map, old_nnz, elem_bytes, h, new_h, on_device, stream);
  * kept entries keep their history, grown entries (the indices in `grown`) start with zero momentum, and the next
  * escoin_solver_step runs on (new values_diff, new_h, new_h2) as if nothing had happened to the kept entries.
- * A dense score is available today from a dense weight gradient computed outside the plan, or from a shadow plan aligned
- * by escoin_plan_set_csr on the full pattern with option wgrad_kernel = ESCOIN_WGRAD_MFMA.
+ * The dense score comes from the plan itself: escoin_dense_wgrad ("Dense weight gradient" below) writes the D-element
+ * dense weight gradient that `score` reads, no abs needed.
  * Device side (rewire_select.hip): the drop is prune's launch sequence; over the D positions a mark launch (the host
  * CSR's entry positions -> an int per position: candidate, dropped, or the kept entry's index), a radix select over the
  * candidates' keys (one histogram launch per key byte, the digit chosen on the device), per-tile counts, one workgroup's
@@ -767,6 +767,58 @@ ESCOIN_API int escoin_plan_rewire(escoin_plan *plan, const escoin_rewire_desc *d
                        long *new_nnz, long *n_grown, void *stream);
 ESCOIN_API int escoin_plan_rewire_cpu(escoin_plan *plan, const escoin_rewire_desc *desc, int *entry_map, int *grown,
                            long *new_nnz, long *n_grown);
+
+/* ---- Dense weight gradient: the grow score of a rewire, from the sparse plan itself ------------------------------------
+ *   weight_gpu_gemm (base_conv_layer.cpp:877-889): the reference's weight gradient is dense.
+ * Every weight-gradient path of escoin_backward writes the CSR positions only; a RigL step needs the gradient OUTSIDE the
+ * pattern.  With G = top_diff (x [top > 0] on fuse_relu plans),
+ *   dense_diff[oc*kdim + k] = sum over (n < n_images, oh, ow) of G[n][oc][oh][ow] x bottom at column k's tap (0 outside the
+ *   image), for ALL D = M*kdim positions of blobs_[0], inside and outside the pattern -- exactly the array
+ *   escoin_rewire_desc.score reads.
+ * accumulate == 0 overwrites every element; accumulate != 0 adds the gradient with one rounding.  n_images == 0 writes
+ * zeros (nothing when accumulating); images at or past n_images are never read.  The result depends on the plan's geometry
+ * and fuse_relu only, not on the pattern or the values; the call still requires an aligned plan (ESCOIN_ESTATE before) on
+ * the current device.  A RigL step is  escoin_dense_wgrad -> escoin_plan_rewire(score = dense_diff) ->
+ * escoin_compact_entries.
+ * Device: float plans within the MFMA weight-gradient kernel's index limits (N*OH*OW, M*Cg*KH*KW and Cg*H*W below 2^31; H,
+ * W, pads and dilated kernel extents below 2^28; at most 65535 (group, 64-channel tile) pairs and column tiles); a double
+ * plan or one outside the limits gets ESCOIN_EINVAL, and escoin_dense_wgrad_f64 always does ("no double kernel: use
+ * escoin_dense_wgrad_cpu_f64").  escoin_dense_wgrad_mfma_kernel: one workgroup of four waves per (split of the pixel axis,
+ * 64 output channels of a conv group, 64 columns) multiplies G[64 x pixels] by the im2col view of the bottom on the fp32
+ * matrix cores (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 sums), 32 pixels per LDS step -- the step loop of
+ * escoin_sconv_wgrad_mfma_kernel -- over its whole span of 1024-pixel chunks with one accumulator set, and writes its tile
+ * to a partial slab; escoin_dense_wgrad_sum_kernel then sums the splits ascending, one lane per position.  The split:
+ * with tiles = group x M-tiles x column tiles and resident = 4 x CUs workgroups on the device at once, cutting the chunks
+ * into S = ceil(chunks / span) spans costs max(1, (r + ceil(r)) / 2) x span with r = tiles x S / resident (rounds of resident
+ * workgroups, a partly filled last round counting half of what it leaves empty, x the chunks each workgroup walks) + S / 512
+ * (the sum's serial walk); the plan takes the cheapest span among those of at most four rounds (ties:
+ * the fewest splits; S = 1 where none qualifies).  A layer with few tiles still fills the device, and the slab is S x D
+ * floats -- at most about 16 x CUs tiles of 16 KB, whatever the batch (csrc/align_rules.h dwg_plan; what was measured:
+ * profiles/grow_score_mi355x.md).  Spans without a live pixel are not launched.
+ * Deterministic: the sum order is a function of the geometry, n_images, the device's CU count and option
+ * "dense_wgrad_splits" only; no atomics, no workgroup waits for another.  Zeros are staged by select: a non-finite bottom
+ * element reaches only the columns whose tap reads it, a non-finite G only its own row.
+ * State: the first device call builds the column decode table and the slab (allocations, a synchronisation).  They are a
+ * function of the descriptor alone, so weight_align, set_csr, prune and rewire KEEP them; only escoin_plan_destroy frees
+ * them (a call that finds the plan aligned on another device builds them anew there).  Later calls allocate nothing and
+ * synchronise nothing: capturable in a graph after escoin_forward and escoin_backward.
+ * The _cpu twins: plain host loops on any plan with a host CSR, both Dtypes; every element's sum runs over its pixels
+ * ascending, whatever n_threads (as in escoin_forward_cpu); n_images is not bounded by desc.N.
+ * Errors: ESCOIN_EINVAL for a NULL top_diff, bottom or dense_diff, fuse_relu without top, n_images outside [0, desc.N]
+ * (GPU) / < 0 (CPU); ESCOIN_ESTATE before an align, on another device, on the other Dtype's _cpu entry point.
+ * Option "dense_wgrad_splits" (test option, before the align): 0 = the rule above, n = at most n splits.  Results stay
+ * within the same error bound for any value (the low bits differ: another sum order).
+ * Stats: "dwg_device_bytes" (the state's device memory: 0 until the first call; part of escoin_plan_workspace_bytes),
+ * "dwg_splits" (splits of the full batch; 0 until the first call), "dwg_lds_bytes" (LDS of a workgroup; 0 until the
+ * first call), "dwg_count" (device calls since the plan was created). */
+ESCOIN_API int escoin_dense_wgrad(escoin_plan *plan, const float *bottom_dev, const float *top_dev, const float *top_diff_dev,
+                       float *dense_diff_dev, int n_images, int accumulate, void *stream);
+ESCOIN_API int escoin_dense_wgrad_f64(escoin_plan *plan, const double *bottom_dev, const double *top_dev,
+                           const double *top_diff_dev, double *dense_diff_dev, int n_images, int accumulate, void *stream);
+ESCOIN_API int escoin_dense_wgrad_cpu(escoin_plan *plan, const float *bottom, const float *top, const float *top_diff,
+                           float *dense_diff, int n_images, int accumulate, int n_threads);
+ESCOIN_API int escoin_dense_wgrad_cpu_f64(escoin_plan *plan, const double *bottom, const double *top, const double *top_diff,
+                               double *dense_diff, int n_images, int accumulate, int n_threads);
 
 #ifdef __cplusplus
 }
