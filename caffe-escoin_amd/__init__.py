@@ -59,6 +59,8 @@ API_SYMBOLS = [
     "escoin_plan_rewire", "escoin_plan_rewire_cpu",
     # Dense weight gradient (rewire's grow score)
     "escoin_dense_wgrad", "escoin_dense_wgrad_f64", "escoin_dense_wgrad_cpu", "escoin_dense_wgrad_cpu_f64",
+    # Space-to-depth (option "s2d")
+    "escoin_plan_s2d_pack",
 ]
 SOLVER_SGD, SOLVER_NESTEROV, SOLVER_ADAM = 0, 1, 2
 REG_NONE, REG_L2, REG_L1 = 0, 1, 2
@@ -235,6 +237,8 @@ def lib():
     L.escoin_plan_kernel_name.argtypes = [vp]
     L.escoin_plan_tiling_info.restype = cp
     L.escoin_plan_tiling_info.argtypes = [vp]
+    L.escoin_plan_s2d_pack.restype = ip
+    L.escoin_plan_s2d_pack.argtypes = [vp, vp, ip, vp]
     L.escoin_forward.restype = ip
     L.escoin_forward.argtypes = [vp, vp, vp, vp, ip, vp]
     L.escoin_plan_export_aligned.restype = ip
@@ -744,6 +748,16 @@ class Plan(object):
         check(lib().escoin_forward(self._h, C.c_void_p(bottom_ptr),
                                    C.c_void_p(bias_ptr) if bias_ptr else None,
                                    C.c_void_p(top_ptr), int(n_images), stream), "escoin_forward")
+
+    def s2d_pack(self, bottom):
+        """The space-to-depth rearrangement of an "s2d" plan alone, into the plan's scratch, on torch's current stream
+        (what forward() runs before the inner plan; for measuring it)."""
+        import torch
+        d = self.desc
+        assert bottom.is_cuda and bottom.dtype == torch.float32 and bottom.is_contiguous()
+        assert tuple(bottom.shape[1:]) == (d.C, d.H, d.W), "bottom shape mismatch"
+        stream = C.c_void_p(torch.cuda.current_stream(bottom.device).cuda_stream)
+        check(lib().escoin_plan_s2d_pack(self._h, C.c_void_p(bottom.data_ptr()), int(bottom.shape[0]), stream), "escoin_plan_s2d_pack")
 
     def forward(self, bottom, bias=None, top=None):
         """Forward_gpu on torch CUDA tensors (float32, or float64 for a double plan), on torch's current stream."""

@@ -100,15 +100,20 @@ class Caffe {
   // plans layers create from now on; CPU mode has one data gradient and ignores it
   static int backward_kernel() { return Get().backward_kernel_; }
   static void set_backward_kernel(int k) { Get().backward_kernel_ = k; }
+  // whether the plans layers create from now on run strided layers on the stride-1 kernels via space-to-depth
+  // (include/escoin.h option "s2d"); a layer the option does not serve, and CPU mode, run as without it
+  static bool s2d() { return Get().s2d_; }
+  static void set_s2d(bool on) { Get().s2d_ = on; }
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
   int wgrad_kernel_;
   int backward_kernel_;
+  bool s2d_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -416,6 +421,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_create(&d, &fresh));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_kernel", Caffe::wgrad_kernel()));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "backward_kernel", Caffe::backward_kernel()));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2d", Caffe::s2d() ? 1 : 0));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;

@@ -576,4 +576,34 @@ bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp) {
   return true;
 }
 
+bool s2d_plan(const Geometry &g, bool is_f64, S2dPlan *sp) {
+  const escoin_conv_desc &d = g.d;
+  if (is_f64) return false;
+  if (d.stride_h == 1 && d.stride_w == 1) return false;
+  if (d.dil_h != 1 || d.dil_w != 1) return false;
+  const long lim28 = 1L << 28;
+  if ((long)d.H + 2L * d.pad_h >= lim28 || (long)d.W + 2L * d.pad_w >= lim28 || d.stride_h >= lim28 || d.stride_w >= lim28) return false;
+  S2dPlan p;
+  p.PH = std::min(d.stride_h, d.KH);
+  p.PW = std::min(d.stride_w, d.KW);
+  escoin_conv_desc &in = p.inner;
+  in = d;
+  in.KH = (d.KH + d.stride_h - 1) / d.stride_h;
+  in.KW = (d.KW + d.stride_w - 1) / d.stride_w;
+  in.H = g.OH + in.KH - 1;
+  in.W = g.OW + in.KW - 1;
+  in.pad_h = in.pad_w = 0;
+  in.stride_h = in.stride_w = 1;
+  const double two31 = 2147483648.0;
+  const double c_in = (double)d.C * p.PH * p.PW, cg_in = (double)g.Cg * p.PH * p.PW;
+  if (cg_in > 32767.0) return false;
+  const double x_floats = (double)d.N * c_in * in.H * (double)in.W;
+  if (x_floats >= two31 || (double)d.N * d.C * d.H * (double)d.W >= two31) return false;
+  if ((double)d.M * cg_in * in.KH * (double)in.KW >= two31) return false;
+  in.C = d.C * p.PH * p.PW;
+  p.x_floats = (long)x_floats;
+  *sp = p;
+  return true;
+}
+
 }  // namespace escoin

@@ -215,5 +215,38 @@ struct DgmPlan {
 // 65535 (group, channel tile) pairs: the grid's y and z; fewer than 2^31 (group, phase, channel tile) triples).
 bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp);
 
+// ---- strided layers on the stride-1 kernels via space-to-depth (s2d.hip, plan option "s2d") ------------------------
+// A strided convolution is a stride-1 convolution of the padded bottom split into its stride_h x stride_w pixel phases,
+// each phase a channel (include/escoin.h "Space-to-depth"): PH = min(stride_h, KH) x PW = min(stride_w, KW) phases own a
+// tap; channel c' = (c * PH + ph) * PW + pw; tap (kr, kc) becomes tap (kr / stride_h, kc / stride_w) of phase
+// (kr % stride_h, kc % stride_w); the inner image is H' x W' = (OH + KH' - 1) x (OW + KW' - 1), pad 0, stride 1.
+// The pack / unpack kernels divide by constants of the launch (rows per plane, PH, the strides).  floor(n / d) for
+// 0 <= n < 2^31 and d >= 1 as one multiplication (Granlund & Montgomery, "Division by invariant integers using
+// multiplication", theorem 4.2 with N = 31): mul = floor(2^(31 + l) / d) + 1, l = ceil(log2 d), which fits 32 bits because
+// d > 2^(l - 1); then floor(mul * n / 2^(31 + l)) = floor(n / d).
+struct S2dDiv { unsigned mul, shift; };
+constexpr S2dDiv s2d_div_make(unsigned d) {
+  unsigned l = 0;
+  while ((1ull << l) < d) ++l;
+  return S2dDiv{(unsigned)((1ull << (31 + l)) / d + 1), 31 + l};
+}
+constexpr unsigned s2d_div(unsigned n, S2dDiv f) { return (unsigned)(((unsigned long long)f.mul * n) >> f.shift); }
+// log2 of the lanes a row of `span` elements gets: the smallest power of two that covers it, a wave at most
+constexpr unsigned s2d_lane_shift(unsigned span) {
+  unsigned k = 0;
+  while (k < 6 && (1u << k) < span) ++k;
+  return k;
+}
+struct S2dPlan {
+  int PH = 0, PW = 0;             // phases that own at least one tap
+  escoin_conv_desc inner = {};    // the inner plan's descriptor
+  long x_floats = 0;              // N * C' * H' * W': the rearranged bottom X' (and its gradient dX')
+};
+// Whether option "s2d" serves this plan, and the inner descriptor where it does: float plans with a stride above 1 in at
+// least one axis and dilation 1, whose bottom, X' and inner weight matrix (N*C*H*W, N*C'*H'*W', M*Cg'*KH'*KW') stay below
+// 2^31 elements (the pack / unpack kernels' 32-bit offsets; every workgroup count is below them), whose padded extents
+// (H + 2 pad_h, W + 2 pad_w) stay below 2^28 and whose Cg' is a channel count a plan accepts (at most 32767).
+bool s2d_plan(const Geometry &g, bool is_f64, S2dPlan *sp);
+
 }  // namespace escoin
 #endif  // ESCOIN_ALIGN_RULES_H_

@@ -212,6 +212,42 @@ DgmTables dgrad_mfma_tables(const CsrView &v, const DgmPlan &plan) {
   return t;
 }
 
+S2dCsr s2d_csr(const CsrView &v, const S2dPlan &sp) {
+  const Geometry &g = *v.g;
+  const escoin_conv_desc &d = g.d;
+  const int kh = sp.inner.KH, kw = sp.inner.KW;
+  S2dCsr t;
+  t.rowptr.assign((size_t)d.group * (g.Mg + 1), 0);
+  t.nnz_g.assign(d.group, 0);
+  t.colidx.reserve((size_t)v.nnz());
+  t.src.reserve((size_t)v.nnz());
+  // per row: (inner column, flat index of the outer entry), sorted -- the columns of a row are distinct, so the order is
+  // a function of the pattern alone
+  std::vector<std::pair<int, int>> row;
+  long base = 0;
+  for (int grp = 0; grp < d.group; ++grp) {
+    const std::vector<int> &rp = (*v.rowptr)[grp], &ci = (*v.colidx)[grp];
+    int *irp = t.rowptr.data() + (size_t)grp * (g.Mg + 1);
+    for (int m = 0; m < g.Mg; ++m) {
+      row.clear();
+      for (int j = rp[m]; j < rp[m + 1]; ++j) {
+        const Tap tap = decode_tap(ci[j], d.KH, d.KW);
+        const int c_in = (tap.ic * sp.PH + tap.kr % d.stride_h) * sp.PW + tap.kc % d.stride_w;
+        row.emplace_back((c_in * kh + tap.kr / d.stride_h) * kw + tap.kc / d.stride_w, (int)(base + j));
+      }
+      std::sort(row.begin(), row.end());
+      for (const auto &e : row) {
+        t.colidx.push_back(e.first);
+        t.src.push_back(e.second);
+      }
+      irp[m + 1] = irp[m] + (int)row.size();
+    }
+    t.nnz_g[grp] = irp[g.Mg];
+    base += (long)ci.size();
+  }
+  return t;
+}
+
 bool entry_major(const std::vector<int> &src, const std::vector<unsigned> &off, const std::vector<unsigned char> &buf,
                  long nnz, EntryMajor *out) {
   const size_t n = src.size(), nz = at_least_one(nnz);

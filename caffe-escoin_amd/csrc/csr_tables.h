@@ -127,6 +127,16 @@ struct DgmPlan;
 struct DgmTables { std::vector<int> phase, tap_ptr, taps, col, pos, live_ptr, live; };
 DgmTables dgrad_mfma_tables(const CsrView &v, const DgmPlan &plan);
 
+// The CSR of the inner stride-1 plan of option "s2d" (align_rules.h s2d_plan), in set_csr's form: per group, row = output
+// channel ocl, entry (ocl, ic, kr, kc) at column (c' * KH' + kr / stride_h) * KW' + kc / stride_w with c' = (ic * PH +
+// kr % stride_h) * PW + kc % stride_w (group-local), ascending within the row -- a permutation of the outer order inside
+// each row.  rowptr [group * (Mg + 1)] group-relative, colidx [nnz], nnz_g [group], src [nnz]: inner entry k holds the
+// value of outer entry src[k] (flat index, groups concatenated).  The map is injective; an inner position without a
+// preimage is never an entry.
+struct S2dPlan;
+struct S2dCsr { std::vector<int> rowptr, colidx, nnz_g, src; };
+S2dCsr s2d_csr(const CsrView &v, const S2dPlan &sp);
+
 // A scatter list (destination k: CSR entry src[k], element off[k] of buffer buf[k]) entry-major: entry e's destinations
 // are e_off[k] / e_buf[k] for k in [e_ptr[e], e_ptr[e + 1]), in the order of the list.  e_ptr [max(nnz, 1) + 1], e_off
 // and e_buf [max(n, 1)] for a list of n.  false (and nothing built): a destination names no CSR entry.

@@ -2,6 +2,7 @@
 // plan life cycle, WeightAlign (dense -> CSR -> device weight streams), dispatch.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <new>
@@ -16,6 +17,8 @@
 namespace escoin {
 
 static thread_local std::string g_last_error;
+
+S2dHooks g_s2d_hooks = {nullptr, nullptr, nullptr};
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 
@@ -72,6 +75,12 @@ DeviceBytes device_bytes(const escoin_plan *p) {
             s->wgm_ent.bytes() + s->wgm_cnt.bytes() + s->wgm_ktab.bytes() +
             s->dgm_mat.bytes() + s->dgm_phase.bytes() + s->dgm_col.bytes() + s->dgm_lptr.bytes() + s->dgm_live.bytes() +
             (s->tplan ? device_bytes(s->tplan.get()).fwd : 0);
+  if (const S2dState *sd = p->s2d_state.get()) {
+    // the X' / dX' scratch and the inner plan's own owners (its update state is never built: the plan's list reaches its copies)
+    const DeviceBytes in = device_bytes(sd->inner.get());
+    b.fwd += sd->x.bytes() + in.fwd;
+    b.bwd += in.bwd;
+  }
   return b;
 }
 
@@ -79,6 +88,7 @@ long bwd_stat(const escoin_plan *p, const char *key) {
   const BwdState *s = p->bwd.get();
   if (!strcmp(key, "bwd_data_kernel")) {
     if (!s) return fail(ESCOIN_ESTATE, "bwd_data_kernel: no backward has run on this alignment");
+    if (s->s2d_inner && p->s2d_state) return bwd_stat(p->s2d_state->inner.get(), key);
     return s->data_kernel;
   }
   if (!strcmp(key, "bwd_device_bytes")) return (long)device_bytes(p).bwd;
@@ -123,6 +133,7 @@ static void free_device(escoin_plan *p) {
   p->upd.reset();
   p->dev_authoritative = false;
   p->bwd.reset();
+  p->s2d_state.reset();
   p->gen = GenericArrays();
   tiled_release(p);
   p->col.reset();
@@ -138,6 +149,42 @@ static int upload_generic(escoin_plan *p, hipStream_t stream) {
   ESCOIN_HIP_TRY(p->gen.taps.upload(t.taps, stream));
   ESCOIN_HIP_TRY(p->gen.vals.upload(vals, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));  // host vectors die at scope exit
+  return ESCOIN_OK;
+}
+
+// Option "s2d" (include/escoin.h "Space-to-depth"): the inner stride-1 plan with the plan's kernel options, aligned on the
+// inner CSR, and the X' scratch.  The plan itself keeps the generic arrays alone (the weight gradient walks them, and
+// gen.vals is the value array of the in-place updates).
+static int s2d_build(escoin_plan *p, const S2dPlan &sp, hipStream_t stream) {
+  if (!g_s2d_hooks.pack || !g_s2d_hooks.unpack) return fail(ESCOIN_EINVAL, "option \"s2d\": this build does not carry the space-to-depth kernels");
+  p->s2d_state.reset(new S2dState());
+  S2dState *sd = p->s2d_state.get();
+  sd->sp = sp;
+  escoin_plan *ip = nullptr;
+  int rc = escoin_plan_create(&sp.inner, &ip);
+  sd->inner.reset(ip);
+  if (rc != ESCOIN_OK) return rc;
+  // the data gradient's kernel: GENERIC and BWD_MFMA stay with this plan (its gather / MFMA kernels), the others go to the inner plan
+  const int ibwd = p->bwd_kernel == ESCOIN_KERNEL_GENERIC || p->bwd_kernel == ESCOIN_BWD_MFMA ? ESCOIN_KERNEL_AUTO : p->bwd_kernel;
+  if ((rc = escoin_plan_set_option(ip, "kernel", p->kernel_choice)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(ip, "backward_kernel", ibwd)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(ip, "tiling_batch", p->tiling_batch)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(ip, "max_launch_bytes", (int)std::min<long>(p->max_launch_bytes, 0x7fffffff))) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(ip, "dense_threshold_pct", p->dense_threshold_pct)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(ip, "dense_gate", p->dense_gate)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(ip, "code_loader", p->code_loader)) != ESCOIN_OK) return rc;
+  S2dCsr ic = s2d_csr(csr_view(p), sp);
+  const std::vector<float> flat = flat_entries(p->values);
+  std::vector<float> vals(ic.src.size());
+  for (size_t k = 0; k < vals.size(); ++k) vals[k] = flat[(size_t)ic.src[k]];
+  sd->src = std::move(ic.src);
+  rc = escoin_plan_set_csr(ip, ic.rowptr.data(), ic.colidx.data(), vals.data(), ic.nnz_g.data(), stream);
+  if (rc != ESCOIN_OK) return rc;
+  ESCOIN_HIP_TRY(sd->x.alloc(sizeof(float) * (size_t)sp.x_floats));
+  p->n_dense_groups = 0; p->n_sparse_groups = p->g.d.group; p->use_dense = false;
+  p->dense_mask = 0; p->sparse_mask = ~0ull; p->small_rule = 0; p->import_fast = false;
+  p->kernel_name = std::string(g_s2d_hooks.pack_kernel_name) + " + " + escoin_plan_kernel_name(ip);
+  p->aligned = true;
   return ESCOIN_OK;
 }
 
@@ -163,6 +210,14 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     p->kernel_name = generic_kernel_name_f64(g.d.fuse_relu != 0);
     p->aligned = true;
     return ESCOIN_OK;
+  }
+  // option "s2d": the layer runs through a stride-1 inner plan, which alone decides dense or sparse, tiled or generic,
+  // on its own geometry (the 4 % rule of dense_groups() for layers without a fast kernel is what the option removes)
+  S2dPlan s2p;
+  if (p->s2d && (p->conv_mode == ESCOIN_CONV_MODE_SCONV || p->conv_mode == ESCOIN_CONV_MODE_SCONV_PAR) && s2d_plan(g, false, &s2p)) {
+    const int rc = s2d_build(p, s2p, stream);
+    if (rc != ESCOIN_OK) p->s2d_state.reset();
+    return rc;
   }
   // which conv groups go to the dense (fp32 MFMA) kernel (align_rules.h)
   const int G = g.d.group;
@@ -405,6 +460,12 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
     if (!p || !key) return fail(ESCOIN_EINVAL, "null argument");
     // ("wgrad_kernel" on an aligned plan: read when the next backward state is built -- after a refused forced kernel, or
     //  after the next align; a state that exists keeps its kernel)
+    if (!strcmp(key, "s2d")) {
+      if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "s2d must be 0 or 1");
+      if (p->aligned || p->host_aligned) return fail(ESCOIN_ESTATE, "s2d must be set before weight_align / weight_align_cpu / set_csr");
+      p->s2d = value;
+      return ESCOIN_OK;
+    }
     if (p->aligned && strcmp(key, "conv_mode") != 0 && strcmp(key, "cpu_channel_block") != 0 && strcmp(key, "cpu_images_per_job") != 0 &&
         strcmp(key, "wgrad_kernel") != 0)
       return fail(ESCOIN_ESTATE, "this option must be set before weight_align/set_csr");
@@ -476,8 +537,10 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
     } else if (!strcmp(key, "conv_mode")) {
       if (value < ESCOIN_CONV_MODE_LOWERED_GEMM || value > ESCOIN_CONV_MODE_SCONV_PAR)
         return fail(ESCOIN_EINVAL, "conv_mode must be one of Caffe::ConvMode's four values (0..3)");
-      const bool regroup = p->aligned && (value == ESCOIN_CONV_MODE_LOWERED_GEMM) !=
-                                             (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_GEMM);
+      // (an "s2d" plan also rebuilds between the lowered modes, which run on the original geometry, and SCONV / SCONV_PAR)
+      auto direct = [](int m) { return m == ESCOIN_CONV_MODE_SCONV || m == ESCOIN_CONV_MODE_SCONV_PAR; };
+      const bool regroup = p->aligned && ((value == ESCOIN_CONV_MODE_LOWERED_GEMM) != (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_GEMM) ||
+                                          (p->s2d && !p->is_f64 && direct(value) != direct(p->conv_mode)));
       p->conv_mode = value;
       // to or from LOWERED_GEMM on an aligned plan: the dense / sparse device structures are rebuilt
       // from the CSR the plan holds (the other three modes share theirs).  The plan is not aligned
@@ -639,6 +702,16 @@ int escoin_plan_import_aligned_dev(escoin_plan *p, const void *dev_buf, size_t b
 
 long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!p || !key) return fail(ESCOIN_EINVAL, "null argument");
+  if (!strcmp(key, "s2d")) return p->s2d_state ? 1 : 0;
+  if (!strcmp(key, "s2d_scratch_bytes")) return p->s2d_state ? (long)p->s2d_state->x.bytes() : 0;
+  if (p->s2d_state) {
+    // what describes the forward's kernel is the inner plan's
+    static const char *const inner_keys[] = {"kernel_choice", "code_bytes", "code_direct", "small_launch_rule", "jit_rows", "jit_records",
+                                             "deal_slowest_over_mean_x1000", "deal_worst_block_x1000", "lds_bytes", "body_variant",
+                                             "workgroup_columns", "streamk_gave_up", "streamk"};
+    for (const char *k : inner_keys)
+      if (!strcmp(key, k)) return escoin_plan_stat(p->s2d_state->inner.get(), key);
+  }
   if (!strcmp(key, "align_us")) return (long)(p->align_ms * 1e3);
   if (!strcmp(key, "code_bytes")) return (long)(p->tiled.enabled && p->tiled.jit ? p->tiled_dev.jit.code_bytes : 0);
   if (!strcmp(key, "device_bytes")) return (long)device_bytes(p).fwd;
@@ -724,7 +797,21 @@ const char *escoin_plan_kernel_name(const escoin_plan *p) {
 }
 
 const char *escoin_plan_tiling_info(const escoin_plan *p) {
+  if (p && p->aligned && p->s2d_state) return escoin_plan_tiling_info(p->s2d_state->inner.get());
   return (p && p->aligned && p->tiled.enabled) ? p->tiled.info.c_str() : "";
+}
+
+int escoin_plan_s2d_pack(escoin_plan *p, const float *bottom_dev, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    if (!p || !bottom_dev) return fail(ESCOIN_EINVAL, "null argument");
+    if (!p->aligned || !p->s2d_state) return fail(ESCOIN_ESTATE, "s2d_pack: option \"s2d\" is not active on this plan");
+    if (n_images < 0 || n_images > p->g.d.N) return fail(ESCOIN_EINVAL, "n_images outside [0, desc.N]");
+    if (n_images == 0) return ESCOIN_OK;
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
+      return fail(ESCOIN_ESTATE, "s2d_pack: the current device is not the device the plan was aligned on");
+    return g_s2d_hooks.pack(p, bottom_dev, p->s2d_state->x.get<float>(), n_images, (hipStream_t)stream);
+  });
 }
 
 int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_dev, float *top_dev,
@@ -748,6 +835,12 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
       return fail(ESCOIN_EHIP, "dense kernel (stream-K): a workgroup gave up waiting for another one's partial sums in an "
                                "earlier launch of this plan; that launch's results are wrong");
     hipStream_t s = (hipStream_t)stream;
+    // option "s2d": the bottom's stride phases become channels of X', then the inner stride-1 plan (bias and ReLU in its epilogue)
+    if (S2dState *sd = p->s2d_state.get()) {
+      const int rc = g_s2d_hooks.pack(p, bottom_dev, sd->x.get<float>(), n_images, s);
+      if (rc != ESCOIN_OK) return rc;
+      return escoin_forward(sd->inner.get(), sd->x.get<const float>(), bias_dev, top_dev, n_images, stream);
+    }
     // LOWERED_SPARSE lowers every group, whatever AUTO decided for the direct path
     if (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE && p->kernel_choice != ESCOIN_KERNEL_DENSE)
       return launch_lowered(p, bottom_dev, bias_dev, top_dev, n_images, s);

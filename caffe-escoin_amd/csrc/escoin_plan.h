@@ -13,6 +13,7 @@
 
 #include "csr_tables.h"
 #include "device_buffer.h"
+#include "align_rules.h"
 #include "escoin.h"
 #include "geometry.h"
 #include "jit_module.h"
@@ -122,6 +123,18 @@ struct BwdState {
   // host: per entry of the transposed order (tplan's CSR, or ttap / tval) the index of the plan's CSR entry (groups
   // concatenated) it is a copy of -- how escoin_update_values reaches the backward state's values (update_values.hip)
   std::vector<int> tsrc;
+  // option "s2d": the data gradient is the inner plan's backward followed by the unpack kernel (S2dState); this state
+  // then holds the weight gradient's side only
+  bool s2d_inner = false;
+};
+
+// What upload() builds for a plan that option "s2d" serves (escoin_capi.hip; the rules: align_rules.h s2d_plan, csr_tables.h
+// s2d_csr; the kernels: s2d.hip); reset with the device side.
+struct S2dState {
+  S2dPlan sp;
+  std::unique_ptr<escoin_plan, int (*)(escoin_plan *)> inner{nullptr, escoin_plan_destroy};   // the stride-1 plan
+  DeviceBuffer x;              // X' for the forward, dX' for the data gradient: sp.x_floats floats
+  std::vector<int> src;        // host: inner CSR entry k holds the value of the plan's CSR entry src[k]
 };
 
 // What the first escoin_dense_wgrad on a plan builds (dense_wgrad.hip).  A function of the descriptor, the device's CU
@@ -291,6 +304,10 @@ struct escoin_plan {
   long rewire_count = 0, rewire_last_dropped = 0, rewire_last_grown = 0;
   double rewire_kernels_ms = 0.0, rewire_map_ms = 0.0, rewire_realign_ms = 0.0;
 
+  // Space-to-depth (s2d.hip): option "s2d" and what upload() builds where it applies; reset with the device side
+  int s2d = 0;
+  std::unique_ptr<escoin::S2dState> s2d_state;
+
   // Dense weight gradient (dense_wgrad.hip): option "dense_wgrad_splits" (0: the rule decides, n: at most n splits of the
   // pixel axis), the state the first escoin_dense_wgrad builds -- kept across aligns -- and stat "dwg_count" (device
   // calls since the plan was created)
@@ -396,6 +413,17 @@ int launch_wgrad_mfma(const escoin_plan *p, const BwdState *s, const float *bott
 int dgm_build(escoin_plan *p, BwdState *s, hipStream_t stream);
 int launch_dgrad_mfma(const escoin_plan *p, const BwdState *s, const float *top, const float *top_diff,
                       float *bottom_diff, int n_images, hipStream_t stream);
+
+// s2d.hip (option "s2d"): X' of the first n_images images from the bottom blob (pack), bottom_diff of the first n_images
+// images from dX' (unpack), and the pack kernel's name.  s2d.hip registers them when the library is loaded; the plan's core
+// (escoin_capi.hip, sconv_backward.hip) calls through the table, like escoin_plan::sync_host_fn, so that a program linking
+// the core's objects alone still links -- there the table is empty and option "s2d" is refused at the align.
+struct S2dHooks {
+  int (*pack)(const escoin_plan *p, const float *bottom, float *x, int n_images, hipStream_t stream);
+  int (*unpack)(const escoin_plan *p, const float *dx, float *bottom_diff, int n_images, hipStream_t stream);
+  const char *pack_kernel_name;
+};
+extern S2dHooks g_s2d_hooks;   // escoin_capi.hip
 
 // Index of the k-th set bit of `mask` (k < popcount): blockIdx -> conv group when only some groups
 // of a layer run in a launch.  Wave-uniform scalar code on the device.

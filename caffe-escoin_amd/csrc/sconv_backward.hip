@@ -559,7 +559,10 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   const bool transposable = bwd_transposable(p);
   const bool forced = p->bwd_kernel == ESCOIN_KERNEL_TILED || p->bwd_kernel == ESCOIN_KERNEL_JIT ||
                       p->bwd_kernel == ESCOIN_KERNEL_DENSE;
-  if (forced && !transposable)
+  // option "s2d": AUTO, TILED, JIT and DENSE are the inner plan's backward (which refuses what it cannot serve); GENERIC
+  // and BWD_MFMA keep this plan's gather / MFMA kernel
+  const bool s2d_inner = p->s2d_state && p->bwd_kernel != ESCOIN_KERNEL_GENERIC && p->bwd_kernel != ESCOIN_BWD_MFMA;
+  if (forced && !transposable && !s2d_inner)
     return fail(ESCOIN_EINVAL, "backward_kernel: this plan has no transposed forward plan (needs a float plan, stride 1, "
                                "pad <= dilation * (kernel - 1)); only the gather kernel serves it");
   StgPlan sp;
@@ -580,7 +583,16 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   s->nnz = plan_nnz(p);
   if (s->nnz > 0x7fffffffL) return fail(ESCOIN_EINVAL, "backward: more than 2^31 nonzeros");
   int rc = ESCOIN_OK;
-  if (p->bwd_kernel == ESCOIN_BWD_MFMA) {
+  if (s2d_inner) {
+    // the inner plan's backward state is built here, with this one: the update list is rebuilt once for both, and no
+    // later call allocates (dX' is the X' scratch)
+    if constexpr (sizeof(T) == 4) {
+      escoin_plan *ip = p->s2d_state->inner.get();
+      s->s2d_inner = true;
+      if (!ip->bwd && (rc = bwd_build<float>(ip, stream)) != ESCOIN_OK) ip->bwd.reset();
+      if (rc == ESCOIN_OK) s->data_kernel = ip->bwd->data_kernel;
+    }
+  } else if (p->bwd_kernel == ESCOIN_BWD_MFMA) {
     if constexpr (sizeof(T) == 4) {
       s->data_kernel = ESCOIN_BWD_MFMA;
       rc = dgm_build(p, s, stream);
@@ -648,7 +660,15 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
   if (n_images == 0) return ESCOIN_OK;
   const bool relu = d.fuse_relu != 0;
   if (bottom_diff) {
-    if (s->tplan) {
+    if (s->s2d_inner) {
+      // option "s2d": dX' = the inner plan's data gradient of top_diff (the ReLU mask is its own), then depth-to-space
+      if constexpr (sizeof(T) == 4) {
+        S2dState *sd = p->s2d_state.get();
+        int rc = escoin_backward(sd->inner.get(), nullptr, top, top_diff, sd->x.get<float>(), nullptr, nullptr, n_images, stream);
+        if (rc == ESCOIN_OK) rc = g_s2d_hooks.unpack(p, sd->x.get<const float>(), bottom_diff, n_images, stream);
+        if (rc != ESCOIN_OK) return rc;
+      }
+    } else if (s->tplan) {
       const float *src = reinterpret_cast<const float *>(top_diff);
       if (relu) {
         const size_t count = (size_t)n_images * d.M * g.OH * g.OW;

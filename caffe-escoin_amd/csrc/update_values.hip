@@ -9,6 +9,8 @@
 //   dense.w                                    the MFMA kernel's padded matrix
 //   bwd: tval, or the transposed plan's own    the backward state's copies, through BwdState::tsrc
 //   bwd: dgm_mat                               the MFMA data gradient's phase matrices, through BwdState::dgm_pos
+//   s2d: the inner plan's copies               option "s2d": everything above once more for the inner stride-1 plan, through
+//                                              S2dState::src (and for ITS backward state: src composed with its tsrc)
 // The first update on an alignment builds that list (UpdState); later updates launch one kernel and nothing else.
 // The list's device facts (buffers, their sizes, the bounds checks) are collected here; the indices derived from the CSR
 // alone -- dense positions, the entry-major view -- come from the host-only builders of csr_tables.h.
@@ -126,10 +128,33 @@ int build_state(escoin_plan *p, hipStream_t stream, bool entry_view, bool vals_o
     rc = collect<T>(p, nullptr, u.get(), &dst);
   }
   if (rc != ESCOIN_OK) return rc;
+  const S2dState *sd = vals_only ? nullptr : p->s2d_state.get();
+  if (sd) {
+    // option "s2d": the inner plan's forward side -- inner entry k is a copy of entry sd->src[k]
+    if ((long)sd->src.size() != u->nnz) return fail(ESCOIN_EINVAL, "update_values: the inner plan does not match the CSR");
+    rc = collect<T>(sd->inner.get(), sd->src.data(), u.get(), &dst);
+    if (rc != ESCOIN_OK) return rc;
+  }
   if (const BwdState *s = vals_only ? nullptr : p->bwd.get()) {
-    const bool dgm = s->data_kernel == ESCOIN_BWD_MFMA;
-    if ((long)(dgm ? s->dgm_pos.size() : s->tsrc.size()) != u->nnz) return fail(ESCOIN_EINVAL, "update_values: the backward state does not match the CSR");
-    if (dgm) {
+    const bool dgm = s->data_kernel == ESCOIN_BWD_MFMA && !s->s2d_inner;
+    if (s->s2d_inner) {
+      // ... and its backward state's copies: outer entry -> inner entry -> the inner transposed order
+      const BwdState *is = sd ? sd->inner->bwd.get() : nullptr;
+      if (!is || (long)is->tsrc.size() != u->nnz) return fail(ESCOIN_EINVAL, "update_values: the inner backward state does not match the CSR");
+      std::vector<int> via((size_t)u->nnz);
+      for (long k = 0; k < u->nnz; ++k) via[(size_t)k] = sd->src[(size_t)is->tsrc[(size_t)k]];
+      if (is->tplan) {
+        rc = collect<T>(is->tplan.get(), via.data(), u.get(), &dst);
+        if (rc != ESCOIN_OK) return rc;
+      } else if (u->nnz > 0) {
+        if (u->n_buffers >= kUpdMaxBuffers || is->tval.bytes() < sizeof(T) * (size_t)u->nnz) return fail(ESCOIN_EINVAL, "update_values: bad inner backward value array");
+        const int b = u->n_buffers++;
+        u->base[b] = is->tval.get<void>();
+        for (long k = 0; k < u->nnz; ++k) dst.push_back({(unsigned char)b, via[(size_t)k], (unsigned)k});
+      }
+    } else if ((long)(dgm ? s->dgm_pos.size() : s->tsrc.size()) != u->nnz) {
+      return fail(ESCOIN_EINVAL, "update_values: the backward state does not match the CSR");
+    } else if (dgm) {
       // the MFMA data gradient's phase matrices: one element per CSR entry (csr_tables.h dgrad_mfma_tables)
       if (u->nnz > 0) {
         if (u->n_buffers >= kUpdMaxBuffers || sizeof(T) != 4) return fail(ESCOIN_EINVAL, "update_values: bad backward phase matrices");
@@ -202,8 +227,19 @@ void patch_host(escoin_plan *q, const T *vals, const int *src_of) {
 template <typename T>
 void patch_host_all(escoin_plan *p, const T *vals) {
   patch_host<T>(p, vals, nullptr);
-  if constexpr (sizeof(T) == 4)
+  if constexpr (sizeof(T) == 4) {
     if (p->bwd && p->bwd->tplan) patch_host<float>(p->bwd->tplan.get(), vals, p->bwd->tsrc.data());
+    if (const S2dState *sd = p->s2d_state.get()) {
+      escoin_plan *ip = sd->inner.get();
+      patch_host<float>(ip, vals, sd->src.data());
+      if (ip->bwd && ip->bwd->tplan) {
+        const std::vector<int> &ts = ip->bwd->tsrc;
+        std::vector<int> via(ts.size());
+        for (size_t k = 0; k < ts.size(); ++k) via[k] = sd->src[(size_t)ts[k]];
+        patch_host<float>(ip->bwd->tplan.get(), vals, via.data());
+      }
+    }
+  }
 }
 
 // The fallback: the device side rebuilt from the host CSR with the new values, exactly as set_csr would.
@@ -250,6 +286,8 @@ int check_updatable(const escoin_plan *p, const char *name) {
 
 bool plan_in_place_ok(const escoin_plan *p) {
   const BwdState *bs = p->bwd.get();
+  if (const S2dState *sd = p->s2d_state.get())
+    if (!plan_in_place_ok(sd->inner.get())) return false;
   return in_place_ok(p) && !(bs && bs->tplan && !in_place_ok(bs->tplan.get()));
 }
 

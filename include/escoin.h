@@ -162,6 +162,8 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  body_variant), the generic body otherwise; 0: always the generic body.  Both call the same code
  *                  and run the same epilogue: results are bit-identical; tests and same-call A/B runs use 0.  May be
  *                  set on an aligned plan; stat "body_variant" = what the last forward ran (0 generic, 1 chained).
+ *   "s2d"        = 0 (default) / 1: run a strided layer on the stride-1 kernels via space-to-depth ("Space-to-depth"
+ *                  below).  1 changes nothing for a layer the option does not serve; KERNEL_AUTO never picks it by itself.
  * Environment: the product build reads ESCOIN_VERBOSE (diagnostics on stderr) and TMPDIR (temporary file of the
  * code object manager's fallback path) and nothing else -- no environment variable can change a result
  * ("Environment"; csrc/knobs.h for the non-product flavours built by tools/mkabl.sh exp / stamps). */
@@ -217,6 +219,48 @@ ESCOIN_API int escoin_plan_import_aligned(escoin_plan *plan, const void *buf, si
 /* The same from a DEVICE buffer -- where an RCCL broadcast leaves the blob (NCCL<Dtype>::Broadcast, parallel.cpp:189-200):
  * one copy into a pinned staging area the calling thread keeps between calls, then the import above. */
 ESCOIN_API int escoin_plan_import_aligned_dev(escoin_plan *plan, const void *dev_buf, size_t bytes, void *stream);
+
+/* ---- Space-to-depth: strided layers on the stride-1 kernels (option "s2d") --------------------------------------------
+ * Every fast sparse kernel is a stride-1 kernel; a strided convolution is a stride-1 convolution of a rearranged input.
+ * For a descriptor with dil_h = dil_w = 1 let PH = min(stride_h, KH), PW = min(stride_w, KW) (the phases that own a tap),
+ * KH' = ceil(KH / stride_h), KW' = ceil(KW / stride_w), H' = OH + KH' - 1, W' = OW + KW' - 1.  The INNER plan has
+ *   C' = C * PH * PW channels, c' = (c * PH + ph) * PW + pw (a conv group's channels stay contiguous: group' = group,
+ *   Cg' = Cg * PH * PW), M' = M, an H' x W' image, a KH' x KW' kernel, pad 0, stride 1, dilation 1, and the outer
+ *   plan's N, has_bias and fuse_relu;
+ *   input   X'[n][c'][i][j] = X[n][c][i * stride_h + ph - pad_h][j * stride_w + pw - pad_w] inside the image, +0 outside;
+ *   weights CSR entry (oc, c, kr, kc) -> (oc, c', kr / stride_h, kc / stride_w) with ph = kr % stride_h, pw = kc %
+ *           stride_w: injective, the nonzero count and the FLOPs of the sparse walk do not change; inner positions
+ *           without a preimage are never entries;
+ *   top = inner_forward(X'), bias and ReLU in the inner epilogue;
+ *   data gradient dX' = inner_data_gradient(top_diff), and with hp = h + pad_h, wp = w + pad_w
+ *           bottom_diff[n][c][h][w] = dX'[n][c'(c, hp % stride_h, wp % stride_w)][hp / stride_h][wp / stride_w] where the
+ *           phase is below (PH, PW) and the index below (H', W'), +0 otherwise: every element of the first n_images
+ *           images is written exactly once.
+ * With "s2d" = 1 a FLOAT plan in conv_mode SCONV / SCONV_PAR with a stride above 1 in at least one axis and dilation 1,
+ * whose bottom, X' and inner weight matrix stay below 2^31 elements and whose Cg' is at most 32767, runs this way:
+ * escoin_forward = escoin_s2d_pack_kernel (one pass, zeros included) + the inner plan's forward; the data gradient = the
+ * inner plan's backward + escoin_s2d_unpack_kernel.  The inner plan and the X' scratch (also dX') are built by the
+ * align; the forward never allocates.  The inner plan gets the options "kernel", "backward_kernel", "tiling_batch",
+ * "max_launch_bytes", "dense_threshold_pct", "dense_gate" and "code_loader" and ALONE decides dense or sparse per group,
+ * on its own geometry: forcing TILED / JIT fails with ESCOIN_EINVAL where the inner layer does not fit them (KW' > 5,
+ * W' > 256, ...).  "backward_kernel" = GENERIC keeps the outer gather kernel, ESCOIN_BWD_MFMA the outer MFMA data
+ * gradient; AUTO, TILED, JIT and DENSE go to the inner plan's backward.  The weight, bias and compact gradients and
+ * escoin_dense_wgrad read the original bottom and are untouched (the same bits as without the option).  In-place
+ * updates (escoin_update_values, escoin_plan_set_values, escoin_solver_step) reach the inner plan's copies and stay in
+ * place wherever the inner plan is in-place capable; prune, rewire, set_csr and weight_align rebuild the inner plan.
+ * escoin_plan_export_aligned writes the outer CSR and no code section; escoin_plan_import_aligned aligns from it.
+ * Everywhere else -- stride 1 in both axes, a dilation, a size limit, a double plan, LOWERED_GEMM / LOWERED_SPARSE (a flip
+ * of the conv mode rebuilds) -- the plan behaves exactly as with "s2d" = 0.
+ * Stats: "s2d" (1 when active), "s2d_scratch_bytes"; "kernel_choice", "bwd_data_kernel", escoin_plan_tiling_info and the
+ * other facts about the forward's kernel report the inner plan's; escoin_plan_kernel_name returns
+ * "escoin_s2d_pack_kernel + <inner name>".  "device_bytes" and escoin_plan_workspace_bytes count the scratch and the
+ * inner plan.  Ordering across streams is the caller's, as for any plan: forward and backward share the scratch.
+ * Non-finite input: a non-finite bottom element reaches a zero weight (0 x inf = NaN) only where the inner plan chose
+ * its DENSE kernel -- the property the DENSE kernel has without the option; the sparse inner kernels never multiply by a
+ * pruned weight, and the padding the pack kernel writes is +0, never a bottom element.
+ * escoin_plan_s2d_pack runs the rearrangement alone into the plan's scratch (what escoin_forward runs first), for
+ * measuring it; ESCOIN_ESTATE unless stat "s2d" is 1. */
+ESCOIN_API int escoin_plan_s2d_pack(escoin_plan *plan, const float *bottom_dev, int n_images, void *stream);
 
 /* Integer facts about an aligned plan (negative = error): "align_us" wall time of the last
  * weight_align / set_csr / import_aligned, "code_bytes" generated machine code on the device,
