@@ -55,11 +55,11 @@ GatherTables gather_transpose(const CsrView &v) {
   return t;
 }
 
-ForwardTranspose forward_transpose(const CsrView &v) {
+DerivedCsr forward_transpose(const CsrView &v) {
   const Geometry &g = *v.g;
   const escoin_conv_desc &d = g.d;
   const int kk = d.KH * d.KW;
-  ForwardTranspose t;
+  DerivedCsr t;
   t.rowptr.assign((size_t)d.group * (g.Cg + 1), 0);
   t.nnz_g.assign(d.group, 0);
   // per row of a group: (column', flat index of the entry).  The columns of a row are distinct, so the sorted order is a
@@ -76,7 +76,7 @@ ForwardTranspose forward_transpose(const CsrView &v) {
       std::sort(row.begin(), row.end());
       for (const auto &e : row) {
         t.colidx.push_back(e.first);
-        t.tsrc.push_back(e.second);
+        t.src.push_back(e.second);
       }
       trp[c + 1] = trp[c] + (int)row.size();
     }
@@ -212,11 +212,11 @@ DgmTables dgrad_mfma_tables(const CsrView &v, const DgmPlan &plan) {
   return t;
 }
 
-S2dCsr s2d_csr(const CsrView &v, const S2dPlan &sp) {
+DerivedCsr s2d_csr(const CsrView &v, const S2dPlan &sp) {
   const Geometry &g = *v.g;
   const escoin_conv_desc &d = g.d;
   const int kh = sp.inner.KH, kw = sp.inner.KW;
-  S2dCsr t;
+  DerivedCsr t;
   t.rowptr.assign((size_t)d.group * (g.Mg + 1), 0);
   t.nnz_g.assign(d.group, 0);
   t.colidx.reserve((size_t)v.nnz());
@@ -246,6 +246,18 @@ S2dCsr s2d_csr(const CsrView &v, const S2dPlan &sp) {
     base += (long)ci.size();
   }
   return t;
+}
+
+bool compose_maps(const std::vector<int> *outer, const std::vector<int> *inner, long n, std::vector<int> *out) {
+  if (n < 0 || (outer && (long)outer->size() != n)) return false;
+  std::vector<int> r(inner ? inner->size() : (size_t)n);
+  for (size_t k = 0; k < r.size(); ++k) {
+    const int j = inner ? (*inner)[k] : (int)k;
+    if (j < 0 || (long)j >= n) return false;
+    r[k] = outer ? (*outer)[(size_t)j] : j;
+  }
+  out->swap(r);
+  return true;
 }
 
 bool entry_major(const std::vector<int> &src, const std::vector<unsigned> &off, const std::vector<unsigned char> &buf,

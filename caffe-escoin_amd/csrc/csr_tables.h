@@ -81,11 +81,14 @@ std::vector<int> dense_positions(const CsrView &v, int row_stride);
 struct GatherTables { std::vector<int> trow, ttap, tsrc; };
 GatherTables gather_transpose(const CsrView &v);
 
+// The CSR of a derived plan (escoin_plan.h DerivedPlan) in set_csr's form -- rowptr group-relative, colidx [nnz], nnz_g
+// [group] -- and its entry map src [nnz]: entry k holds the value of this CSR's entry src[k] (values_flat[src[k]]).
+struct DerivedCsr { std::vector<int> rowptr, colidx, nnz_g, src; };
+
 // The CSR of the transposed forward plan (the data gradient as a stride-1 forward of top_diff), in set_csr's form:
 // per group, row = input channel icl, entry (ocl, icl, kr, kc) at column ocl*KH*KW + (KH-1-kr)*KW + (KW-1-kc), ascending
-// within the row.  rowptr [group * (Cg + 1)] group-relative, colidx [nnz], nnz_g [group], tsrc [nnz] as above.
-struct ForwardTranspose { std::vector<int> rowptr, colidx, tsrc, nnz_g; };
-ForwardTranspose forward_transpose(const CsrView &v);
+// within the row.  rowptr [group * (Cg + 1)]; src [nnz]: the flat index of the entry at that place.
+DerivedCsr forward_transpose(const CsrView &v);
 
 // The staged weight-gradient kernel's tables for blocks of icb input channels, nblk per conv group, cs floats per staged
 // channel, rows of Wp floats: blk [M * (nblk + 1)], blk[oc * (nblk + 1) + b] = the flat index where output channel oc's
@@ -134,8 +137,12 @@ DgmTables dgrad_mfma_tables(const CsrView &v, const DgmPlan &plan);
 // value of outer entry src[k] (flat index, groups concatenated).  The map is injective; an inner position without a
 // preimage is never an entry.
 struct S2dPlan;
-struct S2dCsr { std::vector<int> rowptr, colidx, nnz_g, src; };
-S2dCsr s2d_csr(const CsrView &v, const S2dPlan &sp);
+DerivedCsr s2d_csr(const CsrView &v, const S2dPlan &sp);
+
+// Two entry maps in a row, out[k] = outer[inner[k]]: entry k holds the value of entry inner[k] of a plan of n entries, whose
+// entry j holds that of entry outer[j].  A null side is the identity over [0, n).  false, and *out as it was: `outer` has
+// not n elements, or an index of `inner` lies outside [0, n).
+bool compose_maps(const std::vector<int> *outer, const std::vector<int> *inner, long n, std::vector<int> *out);
 
 // A scatter list (destination k: CSR entry src[k], element off[k] of buffer buf[k]) entry-major: entry e's destinations
 // are e_off[k] / e_buf[k] for k in [e_ptr[e], e_ptr[e + 1]), in the order of the list.  e_ptr [max(nnz, 1) + 1], e_off

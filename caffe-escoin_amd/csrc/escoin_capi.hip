@@ -74,10 +74,10 @@ DeviceBytes device_bytes(const escoin_plan *p) {
     b.bwd = s->trow.bytes() + s->ttap.bytes() + s->tval.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() + s->stg_blk.bytes() + s->stg_off.bytes() +
             s->wgm_ent.bytes() + s->wgm_cnt.bytes() + s->wgm_ktab.bytes() +
             s->dgm_mat.bytes() + s->dgm_phase.bytes() + s->dgm_col.bytes() + s->dgm_lptr.bytes() + s->dgm_live.bytes() +
-            (s->tplan ? device_bytes(s->tplan.get()).fwd : 0);
+            (s->transposed.plan ? device_bytes(s->transposed.plan.get()).fwd : 0);
   if (const S2dState *sd = p->s2d_state.get()) {
     // the X' / dX' scratch and the inner plan's own owners (its update state is never built: the plan's list reaches its copies)
-    const DeviceBytes in = device_bytes(sd->inner.get());
+    const DeviceBytes in = device_bytes(sd->inner.plan.get());
     b.fwd += sd->x.bytes() + in.fwd;
     b.bwd += in.bwd;
   }
@@ -88,7 +88,7 @@ long bwd_stat(const escoin_plan *p, const char *key) {
   const BwdState *s = p->bwd.get();
   if (!strcmp(key, "bwd_data_kernel")) {
     if (!s) return fail(ESCOIN_ESTATE, "bwd_data_kernel: no backward has run on this alignment");
-    if (s->s2d_inner && p->s2d_state) return bwd_stat(p->s2d_state->inner.get(), key);
+    if (s->s2d_inner && p->s2d_state) return bwd_stat(p->s2d_state->inner.plan.get(), key);
     return s->data_kernel;
   }
   if (!strcmp(key, "bwd_device_bytes")) return (long)device_bytes(p).bwd;
@@ -152,6 +152,28 @@ static int upload_generic(escoin_plan *p, hipStream_t stream) {
   return ESCOIN_OK;
 }
 
+int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, int kernel, int backward_kernel,
+                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out) {
+  escoin_plan *q = nullptr;
+  int rc = escoin_plan_create(&desc, &q);
+  out->plan.reset(q);
+  if (rc != ESCOIN_OK) return rc;
+  // what a derived plan inherits, and all of it ("body_variant", "stream_stores" and the "wgrad_*" options are not handed down)
+  if ((rc = escoin_plan_set_option(q, "kernel", kernel)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "backward_kernel", backward_kernel)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "tiling_batch", owner->tiling_batch)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "max_launch_bytes", (int)std::min<long>(owner->max_launch_bytes, 0x7fffffff))) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "dense_threshold_pct", owner->dense_threshold_pct)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "dense_gate", owner->dense_gate)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "code_loader", owner->code_loader)) != ESCOIN_OK) return rc;
+  const std::vector<float> flat = flat_entries(owner->values);
+  std::vector<float> vals(csr.src.size());
+  for (size_t k = 0; k < vals.size(); ++k) vals[k] = flat[(size_t)csr.src[k]];
+  if ((rc = escoin_plan_set_csr(q, csr.rowptr.data(), csr.colidx.data(), vals.data(), csr.nnz_g.data(), stream)) != ESCOIN_OK) return rc;
+  out->src = std::move(csr.src);
+  return ESCOIN_OK;
+}
+
 // Option "s2d" (include/escoin.h "Space-to-depth"): the inner stride-1 plan with the plan's kernel options, aligned on the
 // inner CSR, and the X' scratch.  The plan itself keeps the generic arrays alone (the weight gradient walks them, and
 // gen.vals is the value array of the in-place updates).
@@ -160,26 +182,11 @@ static int s2d_build(escoin_plan *p, const S2dPlan &sp, hipStream_t stream) {
   p->s2d_state.reset(new S2dState());
   S2dState *sd = p->s2d_state.get();
   sd->sp = sp;
-  escoin_plan *ip = nullptr;
-  int rc = escoin_plan_create(&sp.inner, &ip);
-  sd->inner.reset(ip);
-  if (rc != ESCOIN_OK) return rc;
   // the data gradient's kernel: GENERIC and BWD_MFMA stay with this plan (its gather / MFMA kernels), the others go to the inner plan
   const int ibwd = p->bwd_kernel == ESCOIN_KERNEL_GENERIC || p->bwd_kernel == ESCOIN_BWD_MFMA ? ESCOIN_KERNEL_AUTO : p->bwd_kernel;
-  if ((rc = escoin_plan_set_option(ip, "kernel", p->kernel_choice)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(ip, "backward_kernel", ibwd)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(ip, "tiling_batch", p->tiling_batch)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(ip, "max_launch_bytes", (int)std::min<long>(p->max_launch_bytes, 0x7fffffff))) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(ip, "dense_threshold_pct", p->dense_threshold_pct)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(ip, "dense_gate", p->dense_gate)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(ip, "code_loader", p->code_loader)) != ESCOIN_OK) return rc;
-  S2dCsr ic = s2d_csr(csr_view(p), sp);
-  const std::vector<float> flat = flat_entries(p->values);
-  std::vector<float> vals(ic.src.size());
-  for (size_t k = 0; k < vals.size(); ++k) vals[k] = flat[(size_t)ic.src[k]];
-  sd->src = std::move(ic.src);
-  rc = escoin_plan_set_csr(ip, ic.rowptr.data(), ic.colidx.data(), vals.data(), ic.nnz_g.data(), stream);
+  const int rc = build_derived_plan(p, sp.inner, p->kernel_choice, ibwd, s2d_csr(csr_view(p), sp), stream, &sd->inner);
   if (rc != ESCOIN_OK) return rc;
+  escoin_plan *ip = sd->inner.plan.get();
   ESCOIN_HIP_TRY(sd->x.alloc(sizeof(float) * (size_t)sp.x_floats));
   p->n_dense_groups = 0; p->n_sparse_groups = p->g.d.group; p->use_dense = false;
   p->dense_mask = 0; p->sparse_mask = ~0ull; p->small_rule = 0; p->import_fast = false;
@@ -710,7 +717,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
                                              "deal_slowest_over_mean_x1000", "deal_worst_block_x1000", "lds_bytes", "body_variant",
                                              "workgroup_columns", "streamk_gave_up", "streamk"};
     for (const char *k : inner_keys)
-      if (!strcmp(key, k)) return escoin_plan_stat(p->s2d_state->inner.get(), key);
+      if (!strcmp(key, k)) return escoin_plan_stat(p->s2d_state->inner.plan.get(), key);
   }
   if (!strcmp(key, "align_us")) return (long)(p->align_ms * 1e3);
   if (!strcmp(key, "code_bytes")) return (long)(p->tiled.enabled && p->tiled.jit ? p->tiled_dev.jit.code_bytes : 0);
@@ -797,7 +804,7 @@ const char *escoin_plan_kernel_name(const escoin_plan *p) {
 }
 
 const char *escoin_plan_tiling_info(const escoin_plan *p) {
-  if (p && p->aligned && p->s2d_state) return escoin_plan_tiling_info(p->s2d_state->inner.get());
+  if (p && p->aligned && p->s2d_state) return escoin_plan_tiling_info(p->s2d_state->inner.plan.get());
   return (p && p->aligned && p->tiled.enabled) ? p->tiled.info.c_str() : "";
 }
 
@@ -839,7 +846,7 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
     if (S2dState *sd = p->s2d_state.get()) {
       const int rc = g_s2d_hooks.pack(p, bottom_dev, sd->x.get<float>(), n_images, s);
       if (rc != ESCOIN_OK) return rc;
-      return escoin_forward(sd->inner.get(), sd->x.get<const float>(), bias_dev, top_dev, n_images, stream);
+      return escoin_forward(sd->inner.plan.get(), sd->x.get<const float>(), bias_dev, top_dev, n_images, stream);
     }
     // LOWERED_SPARSE lowers every group, whatever AUTO decided for the direct path
     if (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE && p->kernel_choice != ESCOIN_KERNEL_DENSE)

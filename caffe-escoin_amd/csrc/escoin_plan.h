@@ -79,11 +79,19 @@ struct CpuWorkspace {
   unsigned long call = 0;        // ... as of this escoin_forward_cpu call
 };
 
-// What the first escoin_backward on an alignment builds (sconv_backward.hip); reset with the device side.
+// A derived plan: a second plan that its owner builds for itself (build_derived_plan), whose CSR entries are copies of
+// the owner's.  A change of the owner's values reaches them through the map (update_values.hip for_each_copy); a change of
+// its pattern drops the state that holds the derived plan (free_device).
+struct DerivedPlan {
+  std::unique_ptr<escoin_plan, int (*)(escoin_plan *)> plan{nullptr, escoin_plan_destroy};
+  std::vector<int> src;   // host: this plan's entry k holds the value of the owner's entry src[k] (flat index, groups concatenated)
+};
+
+// What the first escoin_backward on an alignment builds (sconv_backward.hip); reset with the device side.  It holds at
+// most one copy of the plan's values for the data gradient, and data_kernel says which: the transposed forward plan
+// (path a), the gather kernel's tval (path b), the MFMA kernel's dgm_mat (path c) -- or none (s2d_inner).
 struct BwdState {
-  // transposed forward plan (path a), or null: the gather kernel (path b) or the MFMA data-gradient kernel (path c);
-  // data_kernel says which
-  std::unique_ptr<escoin_plan, int (*)(escoin_plan *)> tplan{nullptr, escoin_plan_destroy};
+  DerivedPlan transposed;   // path (a): the data gradient as a stride-1 forward of top_diff; plan null on the other paths
   int data_kernel = ESCOIN_KERNEL_GENERIC;
   DeviceBuffer trow;   // [C + 1] absolute offsets into ttap / tval (gather kernel)
   DeviceBuffer ttap;   // per transposed entry: ocl << 16 | kr << 8 | kc
@@ -120,11 +128,11 @@ struct BwdState {
   std::vector<int> dgm_ppix;   // host: [phases] a phase's pixels per image (the launch's grid)
   std::vector<int> dgm_pos;    // host: [nnz] the element of dgm_mat that holds CSR entry e -- how weight updates reach it
   double align_ms = 0.0;
-  // host: per entry of the transposed order (tplan's CSR, or ttap / tval) the index of the plan's CSR entry (groups
-  // concatenated) it is a copy of -- how escoin_update_values reaches the backward state's values (update_values.hip)
+  // host, path (b): element k of tval (and of ttap) holds the value of the plan's CSR entry tsrc[k] (flat index, groups
+  // concatenated).  Not transposed.src: the gather kernel's order is another than the transposed plan's.
   std::vector<int> tsrc;
   // option "s2d": the data gradient is the inner plan's backward followed by the unpack kernel (S2dState); this state
-  // then holds the weight gradient's side only
+  // then holds the weight gradient's side only and no copy of the values -- those are the inner plan's backward state's
   bool s2d_inner = false;
 };
 
@@ -132,9 +140,8 @@ struct BwdState {
 // s2d_csr; the kernels: s2d.hip); reset with the device side.
 struct S2dState {
   S2dPlan sp;
-  std::unique_ptr<escoin_plan, int (*)(escoin_plan *)> inner{nullptr, escoin_plan_destroy};   // the stride-1 plan
+  DerivedPlan inner;           // the stride-1 plan; its own backward state may hold a derived plan of this derived plan
   DeviceBuffer x;              // X' for the forward, dX' for the data gradient: sp.x_floats floats
-  std::vector<int> src;        // host: inner CSR entry k holds the value of the plan's CSR entry src[k]
 };
 
 // What the first escoin_dense_wgrad on a plan builds (dense_wgrad.hip).  A function of the descriptor, the device's CU
@@ -161,7 +168,9 @@ struct UpdState {
   void *base[kUpdMaxBuffers] = {};
   int n_buffers = 0;
   long n_dst = 0, nnz = 0;
-  bool has_bwd = false;         // the list covers the backward state's copies (rebuilt once when that state appears later)
+  // the list was built after the backward state (the plan's, and with it its derived plans'), so the walk found those
+  // states' copies; a list without is rebuilt once when the state appears
+  bool has_bwd = false;
   std::vector<char> h_stage;    // host side of `stage`
   std::vector<int> h_wpos;      // host side of `wpos`: where a host-source update finds entry e in a dense blobs_[0]
   // The same list entry-major, for the solver step (solver_step.hip), which computes a value once per CSR entry: entry e
@@ -344,6 +353,11 @@ DeviceBytes device_bytes(const escoin_plan *p);
 long dwg_stat(const escoin_plan *p, const char *key);
 // escoin_capi.hip: the shared tail of weight_align / set_csr -- rebuilds the device side from the host CSR
 int realign_from_host_csr(escoin_plan *p, hipStream_t stream);
+// escoin_capi.hip (in the core for the reason S2dHooks gives below): a derived plan of the float plan `owner` into *out --
+// descriptor `desc`, the owner's options and these two kernel options, aligned on `csr` with the owner's values permuted
+// through csr.src, which becomes out->src.  A failure returns the failed call's code; the caller drops *out with its state.
+int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, int kernel, int backward_kernel,
+                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out);
 // escoin_capi.hip: the first half of set_csr -- validates a CSR (flat, as escoin_plan_set_csr takes it) and copies it into
 // the plan's host vectors; a refused CSR leaves the plan as it was.  T = float | double.
 template <typename T>

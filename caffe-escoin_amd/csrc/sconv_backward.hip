@@ -497,25 +497,10 @@ static int build_transposed_plan(escoin_plan *p, BwdState *s, hipStream_t stream
   t.stride_h = t.stride_w = 1;
   t.has_bias = 0;
   t.fuse_relu = 0;
-  escoin_plan *tp = nullptr;
-  int rc = escoin_plan_create(&t, &tp);
-  s->tplan.reset(tp);
+  // the forced data-gradient kernel is this plan's forward kernel; it has no backward of its own
+  const int rc = build_derived_plan(p, t, p->bwd_kernel, ESCOIN_KERNEL_AUTO, forward_transpose(csr_view(p)), stream, &s->transposed);
   if (rc != ESCOIN_OK) return rc;
-  if (p->bwd_kernel != ESCOIN_KERNEL_AUTO && (rc = escoin_plan_set_option(tp, "kernel", p->bwd_kernel)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(tp, "tiling_batch", p->tiling_batch)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(tp, "max_launch_bytes", (int)std::min<long>(p->max_launch_bytes, 0x7fffffff))) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(tp, "dense_threshold_pct", p->dense_threshold_pct)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(tp, "dense_gate", p->dense_gate)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(tp, "code_loader", p->code_loader)) != ESCOIN_OK) return rc;
-  // (s->tsrc records the transposed order for escoin_update_values)
-  ForwardTranspose ft = forward_transpose(csr_view(p));
-  const std::vector<float> flat = flat_entries(p->values);
-  std::vector<float> vals(ft.tsrc.size());
-  for (size_t k = 0; k < vals.size(); ++k) vals[k] = flat[(size_t)ft.tsrc[k]];
-  s->tsrc = std::move(ft.tsrc);
-  rc = escoin_plan_set_csr(tp, ft.rowptr.data(), ft.colidx.data(), vals.data(), ft.nnz_g.data(), stream);
-  if (rc != ESCOIN_OK) return rc;
-  s->data_kernel = (int)escoin_plan_stat(tp, "kernel_choice");
+  s->data_kernel = (int)escoin_plan_stat(s->transposed.plan.get(), "kernel_choice");
   return ESCOIN_OK;
 }
 
@@ -587,7 +572,7 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
     // the inner plan's backward state is built here, with this one: the update list is rebuilt once for both, and no
     // later call allocates (dX' is the X' scratch)
     if constexpr (sizeof(T) == 4) {
-      escoin_plan *ip = p->s2d_state->inner.get();
+      escoin_plan *ip = p->s2d_state->inner.plan.get();
       s->s2d_inner = true;
       if (!ip->bwd && (rc = bwd_build<float>(ip, stream)) != ESCOIN_OK) ip->bwd.reset();
       if (rc == ESCOIN_OK) s->data_kernel = ip->bwd->data_kernel;
@@ -664,11 +649,11 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
       // option "s2d": dX' = the inner plan's data gradient of top_diff (the ReLU mask is its own), then depth-to-space
       if constexpr (sizeof(T) == 4) {
         S2dState *sd = p->s2d_state.get();
-        int rc = escoin_backward(sd->inner.get(), nullptr, top, top_diff, sd->x.get<float>(), nullptr, nullptr, n_images, stream);
+        int rc = escoin_backward(sd->inner.plan.get(), nullptr, top, top_diff, sd->x.get<float>(), nullptr, nullptr, n_images, stream);
         if (rc == ESCOIN_OK) rc = g_s2d_hooks.unpack(p, sd->x.get<const float>(), bottom_diff, n_images, stream);
         if (rc != ESCOIN_OK) return rc;
       }
-    } else if (s->tplan) {
+    } else if (s->transposed.plan) {
       const float *src = reinterpret_cast<const float *>(top_diff);
       if (relu) {
         const size_t count = (size_t)n_images * d.M * g.OH * g.OW;
@@ -679,7 +664,7 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
         ESCOIN_HIP_TRY(hipGetLastError());
         src = s->g.get<const float>();
       }
-      const int rc = escoin_forward(s->tplan.get(), src, nullptr, reinterpret_cast<float *>(bottom_diff), n_images, stream);
+      const int rc = escoin_forward(s->transposed.plan.get(), src, nullptr, reinterpret_cast<float *>(bottom_diff), n_images, stream);
       if (rc != ESCOIN_OK) return rc;
     } else if (s->data_kernel == ESCOIN_BWD_MFMA) {
       if constexpr (sizeof(T) == 4) {

@@ -3,14 +3,13 @@
 // Everything WeightAlign decides is a function of the sparsity PATTERN and the options; a value enters the device side
 // as a full 32-bit (64-bit: double plans) word at a position the builders record (jit::Program::val_word,
 // WeightStream::val_word; tests/cpp/value_map_check.cpp proves that nothing else depends on a value).  For an unchanged
-// pattern a weight update is therefore a scatter of the nnz values into every device word that holds one:
-//   gen.vals                                   the generic kernel's and the LOWERED_SPARSE comparator's values
-//   the generated code / the weight stream     sparse conv groups of a tiled plan
-//   dense.w                                    the MFMA kernel's padded matrix
-//   bwd: tval, or the transposed plan's own    the backward state's copies, through BwdState::tsrc
-//   bwd: dgm_mat                               the MFMA data gradient's phase matrices, through BwdState::dgm_pos
-//   s2d: the inner plan's copies               option "s2d": everything above once more for the inner stride-1 plan, through
-//                                              S2dState::src (and for ITS backward state: src composed with its tsrc)
+// pattern a weight update is therefore a scatter of the nnz values into every device word that holds one.  One rule
+// (for_each_copy) finds them: a plan, its backward state's copy and its derived plans, recursively.
+//   a plan's forward side       gen.vals (the generic kernel's and the LOWERED_SPARSE comparator's values), dense.w (the MFMA
+//                               kernel's padded matrix), the generated code / the weight stream of a tiled plan's sparse groups
+//   its backward state's copy   one of: the transposed plan (a derived plan), tval through tsrc, dgm_mat through dgm_pos
+//   its derived plans           (escoin_plan.h DerivedPlan: the transposed plan, the inner plan of option "s2d") plans like
+//                               any other, whose copies are reached through the maps on the way composed (compose_maps)
 // The first update on an alignment builds that list (UpdState); later updates launch one kernel and nothing else.
 // The list's device facts (buffers, their sizes, the bounds checks) are collected here; the indices derived from the CSR
 // alone -- dense positions, the entry-major view -- come from the host-only builders of csr_tables.h.
@@ -55,11 +54,12 @@ namespace {
 
 struct Dst { unsigned char buf; int src; unsigned off; };
 
-// The destinations of one plan's forward side (the plan itself, or the backward state's transposed plan): entry e of q's
+// The destinations of one plan's forward side (the plan itself or a derived plan at any level): entry e of q's
 // CSR (groups concatenated) is a copy of entry src_of[e] of the updated plan's (nullptr: the identity).  Every offset is
 // checked against the size of the buffer it indexes: a list that would write out of bounds is refused, never launched.
+// (Out of line: inlined into the walk below, the per-entry loop came out 2 % slower on the first update of a 3x3 layer.)
 template <typename T>
-int collect(const escoin_plan *q, const int *src_of, UpdState *u, std::vector<Dst> *out) {
+__attribute__((noinline)) int collect(const escoin_plan *q, const int *src_of, UpdState *u, std::vector<Dst> *out) {
   const Geometry &g = q->g;
   auto add_buffer = [&](void *ptr) -> int {
     if (u->n_buffers >= kUpdMaxBuffers) return -1;
@@ -111,13 +111,63 @@ bool in_place_ok(const escoin_plan *q) {
   return q->tiled_dev.jit.direct != nullptr && !q->tiled_dev.val_word.empty();
 }
 
+// The walk: every copy of the values of the plan the walk began at (the root), as reached from plan q, whose entry j
+// holds the value of the root's entry (*outer)[j] (null: q is the root).  In this order:
+//   q's own forward side                  on_plan(q, map)
+//   q's derived plan of option "s2d"      this walk, through its map
+//   the copy of q's backward state        its derived plan: this walk; an array: on_array(buf, elem_size, elem, map, n) -- for
+//                                         k < n, element (elem ? elem[k] : k) of buf, elem_size bytes each, is a copy
+// map[k] is the root's entry whose value the visited plan's entry k, or the array copy's k, holds (null: the identity).
+// with_maps = false visits the plans alone: nothing is checked or composed, every map is null.  A visitor's nonzero
+// return ends the walk and is returned; so is the refusal of a map that does not fit the CSR it indexes.
+// (The "s2d" plan comes before the backward state's copy so that the list's buffers keep the order they always had: the
+// plan, the inner plan, then the data gradient's copy, which either of the two may hold.)
+template <typename Plan, typename OnPlan, typename OnArray>
+int for_each_copy(Plan *q, const std::vector<int> *outer, bool with_maps, OnPlan &on_plan, OnArray &on_array) {
+  const long nnz = plan_nnz(q);
+  auto mismatch = [&](const char *what) {   // (outer: q is a derived plan)
+    return fail(ESCOIN_EINVAL, std::string("update_values: ") + what + (outer ? " of a derived plan" : "") + " does not match the CSR");
+  };
+  if (outer && (long)outer->size() != nnz) return mismatch("the entry map");
+  int rc = on_plan(q, outer ? outer->data() : nullptr);
+  if (rc != ESCOIN_OK) return rc;
+  std::vector<int> composed;
+  // the map of a copy that holds q's entries in the order m (null, and nothing checked, without maps)
+  auto through = [&](const std::vector<int> &m, const std::vector<int> **out) {
+    *out = !with_maps ? nullptr : !outer ? &m : &composed;
+    return !with_maps || ((long)m.size() == nnz && (!outer || compose_maps(outer, &m, nnz, &composed)));
+  };
+  const std::vector<int> *map = nullptr;
+  if (const S2dState *sd = q->s2d_state.get()) {
+    if (!through(sd->inner.src, &map)) return mismatch("the inner plan");
+    if ((rc = for_each_copy<Plan>(sd->inner.plan.get(), map, with_maps, on_plan, on_array)) != ESCOIN_OK) return rc;
+  }
+  const BwdState *s = q->bwd.get();
+  // (s2d_inner: the data gradient is the inner plan's, whose backward state the walk has just visited; this state holds
+  //  no copy -- no transposed plan, tsrc and dgm_pos empty -- and its data_kernel names the inner plan's kernel)
+  if (!s || s->s2d_inner) return ESCOIN_OK;
+  if (s->transposed.plan) {
+    if (!through(s->transposed.src, &map)) return mismatch("the backward state");
+    return for_each_copy<Plan>(s->transposed.plan.get(), map, with_maps, on_plan, on_array);
+  }
+  if (!with_maps) return ESCOIN_OK;
+  if (s->data_kernel == ESCOIN_BWD_MFMA) {
+    // the phase matrices, always float: element dgm_pos[e] holds the value of q's entry e (csr_tables.h dgrad_mfma_tables)
+    if ((long)s->dgm_pos.size() != nnz) return mismatch("the backward state");
+    return on_array(s->dgm_mat, sizeof(float), s->dgm_pos.data(), outer ? outer->data() : nullptr, nnz);
+  }
+  if (!through(s->tsrc, &map)) return mismatch("the backward state");
+  return on_array(s->tval, q->is_f64 ? sizeof(double) : sizeof(float), nullptr, map->data(), nnz);
+}
+
+const auto skip_arrays = [](const DeviceBuffer &, size_t, const int *, const int *, long) { return ESCOIN_OK; };
+
 // entry_view: also the entry-major form of the list (UpdState::e_ptr), for the solver step.  vals_only: the plan has no
 // in-place path -- the list is the value array alone, which a solver step writes before the plan is rebuilt from it.
 template <typename T>
 int build_state(escoin_plan *p, hipStream_t stream, bool entry_view, bool vals_only = false) {
   std::unique_ptr<UpdState> u(new UpdState());
   std::vector<Dst> dst;
-  int rc = ESCOIN_OK;
   u->nnz = plan_nnz(p);
   if (vals_only) {
     if (u->nnz > 0 && p->gen.vals.bytes() < sizeof(T) * (size_t)u->nnz) return fail(ESCOIN_EINVAL, "solver_step: the plan's value array is shorter than its CSR");
@@ -125,57 +175,23 @@ int build_state(escoin_plan *p, hipStream_t stream, bool entry_view, bool vals_o
     for (long k = 0; k < u->nnz; ++k) dst.push_back({(unsigned char)0, (int)k, (unsigned)k});
     u->vals_only = true;
   } else {
-    rc = collect<T>(p, nullptr, u.get(), &dst);
-  }
-  if (rc != ESCOIN_OK) return rc;
-  const S2dState *sd = vals_only ? nullptr : p->s2d_state.get();
-  if (sd) {
-    // option "s2d": the inner plan's forward side -- inner entry k is a copy of entry sd->src[k]
-    if ((long)sd->src.size() != u->nnz) return fail(ESCOIN_EINVAL, "update_values: the inner plan does not match the CSR");
-    rc = collect<T>(sd->inner.get(), sd->src.data(), u.get(), &dst);
-    if (rc != ESCOIN_OK) return rc;
-  }
-  if (const BwdState *s = vals_only ? nullptr : p->bwd.get()) {
-    const bool dgm = s->data_kernel == ESCOIN_BWD_MFMA && !s->s2d_inner;
-    if (s->s2d_inner) {
-      // ... and its backward state's copies: outer entry -> inner entry -> the inner transposed order
-      const BwdState *is = sd ? sd->inner->bwd.get() : nullptr;
-      if (!is || (long)is->tsrc.size() != u->nnz) return fail(ESCOIN_EINVAL, "update_values: the inner backward state does not match the CSR");
-      std::vector<int> via((size_t)u->nnz);
-      for (long k = 0; k < u->nnz; ++k) via[(size_t)k] = sd->src[(size_t)is->tsrc[(size_t)k]];
-      if (is->tplan) {
-        rc = collect<T>(is->tplan.get(), via.data(), u.get(), &dst);
-        if (rc != ESCOIN_OK) return rc;
-      } else if (u->nnz > 0) {
-        if (u->n_buffers >= kUpdMaxBuffers || is->tval.bytes() < sizeof(T) * (size_t)u->nnz) return fail(ESCOIN_EINVAL, "update_values: bad inner backward value array");
-        const int b = u->n_buffers++;
-        u->base[b] = is->tval.get<void>();
-        for (long k = 0; k < u->nnz; ++k) dst.push_back({(unsigned char)b, via[(size_t)k], (unsigned)k});
-      }
-    } else if ((long)(dgm ? s->dgm_pos.size() : s->tsrc.size()) != u->nnz) {
-      return fail(ESCOIN_EINVAL, "update_values: the backward state does not match the CSR");
-    } else if (dgm) {
-      // the MFMA data gradient's phase matrices: one element per CSR entry (csr_tables.h dgrad_mfma_tables)
-      if (u->nnz > 0) {
-        if (u->n_buffers >= kUpdMaxBuffers || sizeof(T) != 4) return fail(ESCOIN_EINVAL, "update_values: bad backward phase matrices");
-        const int b = u->n_buffers++;
-        u->base[b] = s->dgm_mat.get<void>();
-        for (long k = 0; k < u->nnz; ++k) {
-          const size_t at = (size_t)s->dgm_pos[(size_t)k];
-          if ((at + 1) * sizeof(T) > s->dgm_mat.bytes()) return fail(ESCOIN_EINVAL, "update_values: phase-matrix destination out of range");
-          dst.push_back({(unsigned char)b, (int)k, (unsigned)at});
-        }
-      }
-    } else if (s->tplan) {
-      rc = collect<T>(s->tplan.get(), s->tsrc.data(), u.get(), &dst);
-      if (rc != ESCOIN_OK) return rc;
-    } else if (u->nnz > 0) {
-      if (u->n_buffers >= kUpdMaxBuffers || s->tval.bytes() < sizeof(T) * (size_t)u->nnz) return fail(ESCOIN_EINVAL, "update_values: bad backward value array");
+    auto on_plan = [&](const escoin_plan *q, const int *map) { return collect<T>(q, map, u.get(), &dst); };
+    // an array copy: one buffer, one destination per element, each checked against the array's size
+    auto on_array = [&](const DeviceBuffer &buf, size_t elem_size, const int *elem, const int *map, long n) -> int {
+      if (n == 0) return ESCOIN_OK;
+      if (u->n_buffers >= kUpdMaxBuffers || elem_size != sizeof(T)) return fail(ESCOIN_EINVAL, "update_values: bad backward value array");
       const int b = u->n_buffers++;
-      u->base[b] = s->tval.get<void>();
-      for (long k = 0; k < u->nnz; ++k) dst.push_back({(unsigned char)b, s->tsrc[(size_t)k], (unsigned)k});
-    }
-    u->has_bwd = true;
+      u->base[b] = buf.get<void>();
+      for (long k = 0; k < n; ++k) {
+        const size_t at = (size_t)(elem ? elem[k] : k);
+        if ((at + 1) * sizeof(T) > buf.bytes()) return fail(ESCOIN_EINVAL, "update_values: backward destination out of range");
+        dst.push_back({(unsigned char)b, map ? map[k] : (int)k, (unsigned)at});
+      }
+      return ESCOIN_OK;
+    };
+    const int rc = for_each_copy(p, nullptr, true, on_plan, on_array);
+    if (rc != ESCOIN_OK) return rc;
+    u->has_bwd = p->bwd != nullptr;
   }
   std::stable_sort(dst.begin(), dst.end(), [](const Dst &a, const Dst &b) { return a.buf != b.buf ? a.buf < b.buf : a.src < b.src; });
   u->n_dst = (long)dst.size();
@@ -224,22 +240,12 @@ void patch_host(escoin_plan *q, const T *vals, const int *src_of) {
   }
 }
 
+// ... into every plan copy of the walk; the array copies have no host mirror.  (A double plan has neither a backward
+// state's derived plan nor an inner plan: the walk visits p alone.)
 template <typename T>
 void patch_host_all(escoin_plan *p, const T *vals) {
-  patch_host<T>(p, vals, nullptr);
-  if constexpr (sizeof(T) == 4) {
-    if (p->bwd && p->bwd->tplan) patch_host<float>(p->bwd->tplan.get(), vals, p->bwd->tsrc.data());
-    if (const S2dState *sd = p->s2d_state.get()) {
-      escoin_plan *ip = sd->inner.get();
-      patch_host<float>(ip, vals, sd->src.data());
-      if (ip->bwd && ip->bwd->tplan) {
-        const std::vector<int> &ts = ip->bwd->tsrc;
-        std::vector<int> via(ts.size());
-        for (size_t k = 0; k < ts.size(); ++k) via[k] = sd->src[(size_t)ts[k]];
-        patch_host<float>(ip->bwd->tplan.get(), vals, via.data());
-      }
-    }
-  }
+  auto on_plan = [&](escoin_plan *q, const int *map) { patch_host<T>(q, vals, map); return ESCOIN_OK; };
+  for_each_copy(p, nullptr, true, on_plan, skip_arrays);   // (a map that does not fit was refused when the list was built)
 }
 
 // The fallback: the device side rebuilt from the host CSR with the new values, exactly as set_csr would.
@@ -284,11 +290,10 @@ int check_updatable(const escoin_plan *p, const char *name) {
   return ESCOIN_OK;
 }
 
+// Whether the in-place path exists for p: in_place_ok of every plan copy of the walk.
 bool plan_in_place_ok(const escoin_plan *p) {
-  const BwdState *bs = p->bwd.get();
-  if (const S2dState *sd = p->s2d_state.get())
-    if (!plan_in_place_ok(sd->inner.get())) return false;
-  return in_place_ok(p) && !(bs && bs->tplan && !in_place_ok(bs->tplan.get()));
+  auto on_plan = [](const escoin_plan *q, const int *) { return in_place_ok(q) ? ESCOIN_OK : 1; };
+  return for_each_copy(p, nullptr, false, on_plan, skip_arrays) == ESCOIN_OK;
 }
 
 template <typename T>

@@ -140,10 +140,10 @@ void check_forward_transpose(const Case &c) {
     }
     nnz_g.push_back(in_group);
   }
-  const ForwardTranspose t = forward_transpose(c.view());
+  const DerivedCsr t = forward_transpose(c.view());
   k.same(t.rowptr, rowptr, "rowptr'");
   k.same(t.colidx, colidx, "colidx'");
-  k.same(t.tsrc, tsrc, "tsrc");
+  k.same(t.src, tsrc, "tsrc");
   k.same(t.nnz_g, nnz_g, "nnz_g");
 }
 
@@ -279,6 +279,66 @@ void check_entry_major(const Case &c, unsigned seed) {
   k.expect(!entry_major(src, off, buf, c.nnz(), &none), "src = -1 was accepted");
 }
 
+// The case's two real entry maps in a row (the transposed plan's order read through the gather order): values copied twice,
+// once per map, equal the values read once through the composed map.  Then the identity on either side, and the refusals.
+void check_compose(const Case &c) {
+  Checker k{c.name + " compose_maps"};
+  const long n = c.nnz();
+  const std::vector<int> outer = forward_transpose(c.view()).src, inner = gather_transpose(c.view()).tsrc;
+  std::vector<long> vals((size_t)n), once((size_t)n), twice((size_t)n);
+  for (long e = 0; e < n; ++e) vals[(size_t)e] = 7 * e + 3;
+  for (long j = 0; j < n; ++j) once[(size_t)j] = vals[(size_t)outer[(size_t)j]];
+  for (long i = 0; i < n; ++i) twice[(size_t)i] = once[(size_t)inner[(size_t)i]];
+  std::vector<int> out{-7};
+  k.expect(compose_maps(&outer, &inner, n, &out), "two good maps were refused");
+  k.expect((long)out.size() == n, "length", (long)out.size(), n);
+  if (!k.ok) return;
+  for (long i = 0; i < n; ++i) {
+    k.expect(out[(size_t)i] >= 0 && out[(size_t)i] < n, "composed index outside the CSR", i, out[(size_t)i]);
+    if (!k.ok) return;
+    k.expect(vals[(size_t)out[(size_t)i]] == twice[(size_t)i], "the composed map reads another value", i, out[(size_t)i]);
+  }
+  k.expect(compose_maps(nullptr, &inner, n, &out), "identity outside was refused");
+  k.same(out, inner, "identity outside");
+  k.expect(compose_maps(&outer, nullptr, n, &out), "identity inside was refused");
+  k.same(out, outer, "identity inside");
+  k.expect(compose_maps(nullptr, nullptr, n, &out), "two identities were refused");
+  k.expect((long)out.size() == n, "two identities: length", (long)out.size(), n);
+  for (size_t i = 0; i < out.size(); ++i) k.expect(out[i] == (int)i, "two identities", (long)i, out[i]);
+  // refused, and nothing written: an index of the inner map at n or below 0 (with and without an outer map), an outer
+  // map of another length
+  const std::vector<int> untouched{-7, -7, -7};
+  std::vector<int> bad = inner;
+  for (const int index : {(int)n, -1}) {
+    bad.push_back(index);
+    out = untouched;
+    k.expect(!compose_maps(&outer, &bad, n, &out) && out == untouched, "a bad index was accepted, or something was written", index);
+    k.expect(!compose_maps(nullptr, &bad, n, &out) && out == untouched, "a bad index under the identity was accepted", index);
+    bad.pop_back();
+  }
+  bad = outer;
+  bad.push_back(0);
+  out = untouched;
+  k.expect(!compose_maps(&bad, &inner, n, &out) && out == untouched, "an outer map of n + 1 elements was accepted");
+}
+
+void check_compose_by_hand() {
+  Checker k{"by_hand compose_maps"};
+  // four entries; a first-level plan that holds them in the order 2 0 3 1; a second-level copy of three of ITS entries
+  const std::vector<int> outer{2, 0, 3, 1}, inner{3, 3, 0};
+  std::vector<int> out;
+  k.expect(compose_maps(&outer, &inner, 4, &out), "refused");
+  k.same(out, std::vector<int>{1, 1, 2}, "outer[inner[k]]");
+  // no entries at all: empty maps compose to an empty map, and the only index there is, 0, is already out of range
+  const std::vector<int> none, zero{0};
+  out = {5};
+  k.expect(compose_maps(&none, &none, 0, &out) && out.empty(), "empty maps");
+  out = {5};
+  k.expect(compose_maps(nullptr, nullptr, 0, &out) && out.empty(), "empty identities");
+  out = {5};
+  k.expect(!compose_maps(&none, &zero, 0, &out) && out == std::vector<int>{5}, "index 0 of an empty map was accepted");
+}
+
 void check_stretched(const Case &c) {
   Checker k{c.name + " stretched_col"};
   const escoin_conv_desc &d = c.g.d;
@@ -295,6 +355,7 @@ void check_case(const Case &c, unsigned seed) {
   check_generic(c);
   check_staged(c);
   check_entry_major(c, seed ^ 0x9e3779b9u);
+  check_compose(c);
   check_stretched(c);
 }
 
@@ -321,6 +382,7 @@ int main() {
   check_case(make_case("lone", geometry(1, 3, 4, 3, 3, 5, 5, 1, 1, 1, 1), 2, [](int, int, int, int, int, bool last) { return last; }), 606u);
   // (g) fully dense
   check_case(make_case("dense", geometry(1, 2, 2, 3, 3, 5, 5, 1, 1, 1, 1), 1, [](int, int, int, int, int, bool) { return true; }), 707u);
+  check_compose_by_hand();
   if (g_failed) std::printf("%d checks FAILED\n", g_failed);
   return g_failed ? 1 : 0;
 }

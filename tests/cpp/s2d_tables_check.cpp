@@ -112,7 +112,7 @@ int main(int argc, char **argv) {
   const escoin_conv_desc &in = sp.inner;
   printf("inner %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d %d\n", in.N, in.C, in.H, in.W, in.M, in.KH, in.KW, in.pad_h, in.pad_w,
          in.stride_h, in.stride_w, in.dil_h, in.dil_w, in.group, in.has_bias, in.fuse_relu);
-  const S2dCsr t = s2d_csr(CsrView{&g, &rowptr, &colidx}, sp);
+  const DerivedCsr t = s2d_csr(CsrView{&g, &rowptr, &colidx}, sp);
   print_row("rowptr", t.rowptr);
   print_row("colidx", t.colidx);
   print_row("nnz_g", t.nnz_g);

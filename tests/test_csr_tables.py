@@ -2,14 +2,15 @@
 compiled with plain g++ against csr_tables.cpp alone and no ROCm include path -- that compile is the proof that the unit
 is host-only -- every builder's output equals a brute-force restatement (dense scatter and scan, stable sort, the defining
 formula) on seven small patterns: grouped with an asymmetric kernel, dilated with a short last channel block, strided,
-with empty rows and channels, empty, one entry per row in the last column, fully dense."""
+with empty rows and channels, empty, one entry per row in the last column, fully dense.  The composition of two entry
+maps (compose_maps) is checked on every pattern's own two maps, and once more against a result written out by hand."""
 import os
 import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = ("grouped", "dilated", "strided", "empty_rows", "empty", "lone", "dense")
 BUILDERS = ("for_each_entry", "forward_transpose", "gather_transpose", "dense_positions kdim", "dense_positions padded",
-            "generic_tables", "staged_tables", "entry_major", "stretched_col")
+            "generic_tables", "staged_tables", "entry_major", "compose_maps", "stretched_col")
 
 
 def test_every_builder_equals_its_brute_force_restatement(tmp_path):
@@ -25,4 +26,5 @@ def test_every_builder_equals_its_brute_force_restatement(tmp_path):
     for case in CASES:
         for builder in BUILDERS:
             assert lines.count("OK %s %s" % (case, builder)) == 1, (case, builder, text)
-    assert len(lines) == len(CASES) * len(BUILDERS), text
+    assert lines.count("OK by_hand compose_maps") == 1, text
+    assert len(lines) == len(CASES) * len(BUILDERS) + 1, text

@@ -299,6 +299,28 @@ def test_updates_reach_the_inner_plan_in_place(pkg, synth, dev, name, kernel):
     plan.close()
 
 
+@pytest.mark.parametrize("bk", ["GENERIC", "BWD_MFMA"])
+def test_updates_reach_an_outer_backward_copy_and_the_inner_plan(pkg, synth, dev, bk):
+    """The data gradient stays with the outer plan (the gather kernel's value array, the MFMA kernel's phase matrices):
+    one update list then holds that array and the inner plan's forward copies, and a set_values from the device after the
+    first backward reaches both in place."""
+    s, sk = _case(synth, make(synth, "3x3_s2x3_g2"))
+    code = pkg.KERNEL_GENERIC if bk == "GENERIC" else pkg.BWD_MFMA
+    plan = _plan(pkg, s, sk.w, backward_kernel=code)
+    plan.set_values(_up(values_at(plan, new_weights(sk.w, 41)[0])[2], dev))     # before the backward state exists
+    assert plan.stat("update_fast") == 1 and plan.stat("s2d") == 1
+    before = plan.stat("update_destinations")
+    plan.backward(_up(sk.top_diff, dev), bottom_diff=_nan_like(s, dev))
+    assert plan.stat("bwd_data_kernel") == code
+    v2 = values_at(plan, new_weights(sk.w, 42)[0])[2]
+    plan.set_values(_up(v2, dev))
+    assert plan.stat("update_fast") == 1
+    assert plan.stat("update_destinations") > before    # the outer backward state's array joined the list
+    assert same_bits(plan.get_csr()[2], v2)
+    _fresh_equals(pkg, synth, dev, s, sk, plan, "set_values after the outer backward", backward_kernel=code)
+    plan.close()
+
+
 def test_a_pruned_and_a_rewired_plan_equal_fresh_plans(pkg, synth, dev):
     s, sk = _case(synth, make(synth, "3x3_s2x3_g2"))
     plan = _plan(pkg, s, sk.w)
