@@ -258,7 +258,15 @@ int escoin_compact_entries(const int *entry_map, long old_nnz, int elem_bytes, c
                            void *stream) {
   if (elem_bytes != 4 && elem_bytes != 8) return fail(ESCOIN_EINVAL, "compact_entries: elem_bytes must be 4 or 8");
   if (old_nnz < 0) return fail(ESCOIN_EINVAL, "compact_entries: old_nnz must be >= 0");
-  if (old_nnz > 0 && (!entry_map || !src || !dst)) return fail(ESCOIN_EINVAL, "compact_entries: null argument");
+  if (old_nnz > 0 && (!entry_map || !src)) return fail(ESCOIN_EINVAL, "compact_entries: null argument");
+  if (old_nnz > 0 && !dst) {
+    // a NULL dst is a destination of 0 elements (the new nnz is 0; an empty tensor's pointer): nothing is stored, nothing
+    // launched.  The host route can see a map that keeps an entry all the same, and refuses it.
+    if (!on_device)
+      for (long e = 0; e < old_nnz; ++e)
+        if (entry_map[e] >= 0) return fail(ESCOIN_EINVAL, "compact_entries: the map keeps an entry but dst is NULL");
+    return ESCOIN_OK;
+  }
   if (old_nnz > 0 && src == dst) return fail(ESCOIN_EINVAL, "compact_entries: src and dst must not overlap");
   if (!on_device) {
     // a plain host loop, no HIP call

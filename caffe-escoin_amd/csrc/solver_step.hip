@@ -72,8 +72,11 @@ int require_device(const char *name) {
 template <typename T>
 int solver_step_t(escoin_plan *p, const escoin_solver_desc *d, T *diff, T *h, T *h2, T *dense_w, void *stream_v) {
   const char *name = "solver_step";     // (both Dtypes, as update_values.hip names its entry points in messages)
-  if (!p || !diff || !h) return fail(ESCOIN_EINVAL, std::string(name) + ": null argument");
-  if (const char *why = solver_desc_error(d, h2)) return fail(ESCOIN_EINVAL, std::string(name) + ": " + why);
+  if (!p) return fail(ESCOIN_EINVAL, std::string(name) + ": null argument");
+  // a plan of 0 entries reads and writes nothing: its arrays (of 0 elements) may be NULL, as an empty tensor's pointer is
+  const bool empty = plan_nnz(p) == 0;
+  if (!empty && (!diff || !h)) return fail(ESCOIN_EINVAL, std::string(name) + ": null argument");
+  if (const char *why = solver_desc_error(d, empty ? static_cast<const void *>(p) : h2)) return fail(ESCOIN_EINVAL, std::string(name) + ": " + why);
   hipStream_t stream = (hipStream_t)stream_v;
   SolverTargets t;
   if (const int rc = solver_begin<T>(p, name, stream, &t)) return rc;

@@ -49,8 +49,10 @@ struct ArrayLoop {
 template <typename T>
 int solver_step_cpu(escoin_plan *p, const escoin_solver_desc *d, T *diff, T *h, T *h2, T *dense_w) {
   const std::string name = "solver_step_cpu";
-  if (!p || !diff || !h) return fail(ESCOIN_EINVAL, name + ": null argument");
-  if (const char *why = solver_desc_error(d, h2)) return fail(ESCOIN_EINVAL, name + ": " + why);
+  if (!p) return fail(ESCOIN_EINVAL, name + ": null argument");
+  const bool empty = plan_nnz(p) == 0;      // (0 entries: nothing is read or written, the arrays may be NULL)
+  if (!empty && (!diff || !h)) return fail(ESCOIN_EINVAL, name + ": null argument");
+  if (const char *why = solver_desc_error(d, empty ? static_cast<const void *>(p) : h2)) return fail(ESCOIN_EINVAL, name + ": " + why);
   if (!p->host_aligned) return fail(ESCOIN_ESTATE, name + " called before weight_align_cpu");
   if (p->aligned)
     return fail(ESCOIN_ESTATE, name + ": the plan has a device side, which this entry point would leave behind; escoin_solver_step updates both sides");

@@ -638,7 +638,8 @@ ESCOIN_API int escoin_update_values_cpu_f64(escoin_plan *plan, const double *den
  * like a fresh plan aligned by escoin_plan_set_csr on w' at the old pattern, in all four conv_modes and for the backward
  * state's copies; the device is authoritative afterwards and the host mirrors follow as after a device-source update;
  * "update_count" increments, "update_fast" reports the path.  An explicit zero of the pattern is updated like any entry.
- * With nnz == 0 the call returns ESCOIN_OK without a launch.
+ * With nnz == 0 the call returns ESCOIN_OK without a launch; diff, history and history2 (arrays of 0 elements) may then
+ * be NULL.
  * One launch of escoin_solver_step_kernel, one lane per CSR ENTRY: the lane reads w, diff, h (h2), computes the rule once,
  * writes h (h2), dense_w, the cleared diff, and stores w' to each of the entry's destinations (the value array, the code
  * word or stream quad, the dense matrix, the backward state's copies) through an entry-major view of the update state's
@@ -650,8 +651,8 @@ ESCOIN_API int escoin_update_values_cpu_f64(escoin_plan *plan, const double *den
  * escoin_solver_array_step: the same rule on a plain array (`data` is w and the only destination): the bias, any blob.
  * The _cpu entry points are plain host loops with the same bits: escoin_solver_step_cpu for plans aligned by
  * escoin_weight_align_cpu only (as escoin_update_values_cpu), all pointers host pointers, rate_dev included.
- * Errors: ESCOIN_EINVAL for a NULL desc / diff / history (array step: data, or n < 0), an unknown type or regularization,
- * Adam without history2; ESCOIN_ENODEVICE for the device entry points without a device; ESCOIN_ESTATE before an align, on
+ * Errors: ESCOIN_EINVAL for a NULL desc, a NULL diff / history on a plan with entries (array step: data, or n < 0), an
+ * unknown type or regularization, Adam without history2 on a plan with entries; ESCOIN_ENODEVICE for the device entry points without a device; ESCOIN_ESTATE before an align, on
  * the other Dtype's entry point, on another device, and for escoin_solver_step_cpu on a device-aligned plan. */
 #define ESCOIN_SOLVER_SGD 0        /* sgd_solver.cu:7-12      */
 #define ESCOIN_SOLVER_NESTEROV 1   /* nesterov_solver.cu:7-14 */
@@ -725,7 +726,8 @@ ESCOIN_API int escoin_solver_array_step_cpu_f64(const escoin_solver_desc *desc, 
  * escoin_plan_prune_cpu: the same rule as plain host code, for plans aligned by escoin_weight_align_cpu; no HIP call.
  * escoin_compact_entries: dst[entry_map[e]] = src[e] wherever entry_map[e] >= 0 -- what the caller runs over history,
  * history2, a pending values_diff or its own copy of the values.  dst holds the new nnz elements; src and dst must NOT
- * overlap (only an equal pointer is detected: ESCOIN_EINVAL).  on_device != 0: device pointers, one launch of
+ * overlap (only an equal pointer is detected: ESCOIN_EINVAL).  dst == NULL is a destination of 0 elements (every entry was
+ * dropped): nothing is stored or launched; the host route refuses it (ESCOIN_EINVAL) if the map keeps an entry.  on_device != 0: device pointers, one launch of
  * escoin_compact_kernel (one lane per old entry, one plain store), asynchronous on `stream`, capturable.  on_device == 0:
  * host pointers, a plain loop, no HIP call.
  * Errors: ESCOIN_EINVAL for a NULL desc, an unknown mode, keep < 0, a negative or NaN threshold, elem_bytes not 4 or 8,

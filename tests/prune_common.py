@@ -52,6 +52,21 @@ def ref_csr(desc, rowptr, colidx, values, nnz_per_group, entry_map):
     return rp, colidx[kept], values[kept], ng
 
 
+def positions(desc, rowptr, colidx, nnz_per_group):
+    """The flat index into blobs_[0] of every entry of a CSR in get_csr()'s form, in its order (ascending)."""
+    mg, kdim = desc.M // desc.group, (desc.C // desc.group) * desc.KH * desc.KW
+    out, base = [], 0
+    for grp in range(desc.group):
+        r = np.asarray(rowptr[grp * (mg + 1):(grp + 1) * (mg + 1)])
+        n = int(nnz_per_group[grp])
+        rows = np.repeat(np.arange(mg, dtype=np.int64), np.diff(r)) + grp * mg
+        out.append(rows * kdim + np.asarray(colidx[base:base + n], np.int64))
+        base += n
+    pos = np.concatenate(out) if out else np.zeros(0, np.int64)
+    assert np.all(np.diff(pos) > 0), "a CSR's positions ascend"
+    return pos
+
+
 def pattern_csr(desc, positions):
     """rowptr, colidx, nnz_per_group of the pattern that holds the given flat positions of blobs_[0] (ascending)."""
     mg, kdim = desc.M // desc.group, (desc.C // desc.group) * desc.KH * desc.KW

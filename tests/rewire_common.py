@@ -36,21 +36,6 @@ def dense_size(desc):
     return desc.M * (desc.C // desc.group) * desc.KH * desc.KW
 
 
-def positions(desc, rowptr, nnz_per_group, colidx):
-    """The position of every entry of a CSR in get_csr()'s flat form (ascending)."""
-    mg, kdim = desc.M // desc.group, (desc.C // desc.group) * desc.KH * desc.KW
-    out, base = [], 0
-    for grp in range(desc.group):
-        r = rowptr[grp * (mg + 1):(grp + 1) * (mg + 1)]
-        n = int(nnz_per_group[grp])
-        rows = np.repeat(np.arange(mg, dtype=np.int64), np.diff(r)) + grp * mg
-        out.append(rows * kdim + colidx[base:base + n])
-        base += n
-    pos = np.concatenate(out) if out else np.zeros(0, np.int64)
-    assert np.all(np.diff(pos) > 0)
-    return pos
-
-
 def candidates(D, pos):
     free = np.ones(D, bool)
     free[pos] = False
@@ -70,7 +55,7 @@ def ref_rewire(desc, csr, grow, score, init=None, drop_keep=None, drop_threshold
     """csr: get_csr()'s (rowptr, colidx, values, nnz_per_group).  Returns a dict: entry_map, grown (int32), grown_pos,
     csr (the new CSR in the same form), pos (the new pattern's positions)."""
     rp, ci, va, ng = csr
-    pos = positions(desc, rp, ng, ci)
+    pos = pc.positions(desc, rp, ci, ng)
     D = dense_size(desc)
     kept = np.ones(pos.size, bool)
     if drop_keep is not None or drop_threshold is not None:

@@ -76,21 +76,6 @@ def bits_equal(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
-def positions(plan_desc, rowptr, colidx, nnz_per_group):
-    """The flat index into blobs_[0] of every CSR entry, in get_csr()'s order."""
-    d = plan_desc
-    mg, kdim = d.M // d.group, (d.C // d.group) * d.KH * d.KW
-    out = np.empty(colidx.size, np.int64)
-    base = 0
-    for grp in range(d.group):
-        r = rowptr[grp * (mg + 1):(grp + 1) * (mg + 1)]
-        rows = np.repeat(np.arange(mg), np.diff(r)) + grp * mg
-        n = int(nnz_per_group[grp])
-        out[base:base + n] = rows * kdim + colidx[base:base + n]
-        base += n
-    return out
-
-
 def seeded_values(n, seed, dt, zeros=True):
     """n seeded values in (-1, 1); with `zeros` (and n >= 8) a few exactly 0 and one -0.0."""
     rs = np.random.RandomState(seed)

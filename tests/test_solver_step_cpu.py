@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import solver_common as sc
+from plan_model import positions
 from upd_common import new_weights, values_at
 
 HYPER = dict(rate=0.01, momentum=0.9, momentum2=0.999, delta=1e-8, decay=5e-4)
@@ -37,7 +38,7 @@ class Twin(object):
             p.weight_align_cpu(w0)
             p.update_values_cpu(w1)
         rp, ci, va, ng = self.plan.get_csr()
-        self.pos = sc.positions(self.desc, rp, ci, ng)
+        self.pos = positions(self.desc, rp, ci, ng)
         self.w = va.copy()
         assert sc.bits_equal(self.w, values_at(self.plan, w1)[2])
         assert np.count_nonzero(self.w == 0) >= 4 and np.any(np.signbit(self.w) & (self.w == 0))

@@ -10,6 +10,7 @@ import pytest
 
 import solver_common as sc
 from conftest import rel_err
+from plan_model import positions
 from test_update_values_gpu import Layer, _mixed_weights, _oracle_forward, _seeded
 from upd_common import new_weights, values_at
 
@@ -41,7 +42,7 @@ class Stepper(object):
             plan.update_values(torch.from_numpy(w_nan).to(dev))
             layer.w = w_new
         rp, ci, va, ng = plan.get_csr()
-        self.pos = sc.positions(plan.desc, rp, ci, ng)
+        self.pos = positions(plan.desc, rp, ci, ng)
         self.w = va.copy()
         assert sc.bits_equal(self.w, values_at(plan, layer.w)[2])
         n = self.w.size

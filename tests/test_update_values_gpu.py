@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import rel_err
+from seq_common import mixed_weights as _mixed_weights
 from upd_common import new_weights, same_bits, values_at
 
 torch = pytest.importorskip("torch")
@@ -92,18 +93,6 @@ class Layer(object):
         assert err <= (1e-12 if self.dt == np.float64 else TOL)
         self.w = w_new
         return ref, w_new
-
-
-def _mixed_weights(s, seed):
-    """A grouped layer whose first conv group is 60 % dense and whose others keep 8 %."""
-    rs = np.random.RandomState(seed)
-    w = rs.uniform(-1, 1, (s.M, s.C // s.group, s.KH, s.KW)).astype(np.float32)
-    w[w == 0] = 0.5
-    mg = s.M // s.group
-    keep = rs.uniform(0, 1, w.shape)
-    w[:mg][keep[:mg] >= 0.6] = 0
-    w[mg:][keep[mg:] >= 0.08] = 0
-    return w
 
 
 def _kinds(pkg, synth):
