@@ -451,6 +451,7 @@ bool stg_plan(const Geometry &g, bool is_f64, int wgrad_channel_block, int n_cu,
   sp->cs = (int)(rows * Wp);
   sp->icb = (int)std::min<size_t>((size_t)g.Cg, kStgLdsBudget / (sizeof(float) * (size_t)sp->cs));
   if (wgrad_channel_block > 0) sp->icb = std::min(sp->icb, wgrad_channel_block);
+  sp->lds_bytes = sizeof(float) * (size_t)sp->icb * (size_t)sp->cs;
   sp->nblk = (g.Cg + sp->icb - 1) / sp->icb;
   sp->chunks = (int)((total + kBwdChunkPixels - 1) / kBwdChunkPixels);
   // enough workgroups for two per CU where the chunks and blocks alone do not give them: deal the output channels
@@ -574,6 +575,48 @@ bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp) {
   p.lds_bytes = kDgmLdsBytes;
   *dp = p;
   return true;
+}
+
+bool bwd_transposable(const Geometry &g, bool is_f64) {
+  const escoin_conv_desc &d = g.d;
+  return !is_f64 && d.stride_h == 1 && d.stride_w == 1 && d.pad_h <= d.dil_h * (d.KH - 1) &&
+         d.pad_w <= d.dil_w * (d.KW - 1) && g.Mg <= 32767;
+}
+
+BwdChoice bwd_choice(const Geometry &g, bool is_f64, long nnz, const BwdOptions &o, int n_cu) {
+  const escoin_conv_desc &d = g.d;
+  BwdChoice c;
+  auto refuse = [&c](const char *why) { c.rc = ESCOIN_EINVAL; c.error = why; return c; };
+  if (g.Mg > 65535) return refuse("backward: more than 65535 output channels per group");
+  if (d.C > 4 * 65535 || d.N > 65535) return refuse("backward: grid dimension exceeds 65535");
+  const bool transposable = bwd_transposable(g, is_f64);
+  const bool forced = o.backward_kernel == ESCOIN_KERNEL_TILED || o.backward_kernel == ESCOIN_KERNEL_JIT ||
+                      o.backward_kernel == ESCOIN_KERNEL_DENSE;
+  // option "s2d": GENERIC and BWD_MFMA keep the plan's own gather / MFMA kernel, the others go to the inner plan
+  const bool inner = o.s2d && o.backward_kernel != ESCOIN_KERNEL_GENERIC && o.backward_kernel != ESCOIN_BWD_MFMA;
+  if (forced && !transposable && !inner)
+    return refuse("backward_kernel: this plan has no transposed forward plan (needs a float plan, stride 1, "
+                  "pad <= dilation * (kernel - 1)); only the gather kernel serves it");
+  const bool staged_ok = stg_plan(g, is_f64, o.wgrad_channel_block, n_cu, &c.stg);
+  if (o.wgrad_kernel == ESCOIN_WGRAD_STAGED && !staged_ok)
+    return refuse("wgrad_kernel: the staged weight-gradient kernel needs a float plan with stride 1 whose "
+                  "chunk tile of one input channel fits the LDS budget; only the entry kernel serves this plan");
+  if (o.wgrad_kernel == ESCOIN_WGRAD_MFMA && !wgm_plan(g, is_f64, &c.wgm))
+    return refuse("wgrad_kernel: the MFMA weight-gradient kernel needs a float plan whose pixel, weight and "
+                  "image indices fit 31 bits; the entry kernel serves this plan");
+  if (o.backward_kernel == ESCOIN_BWD_MFMA && !dgm_plan(g, is_f64, &c.dgm))
+    return refuse("backward_kernel: the MFMA data-gradient kernel needs a float plan whose pixel, top and "
+                  "matrix indices fit 31 bits; the gather kernel serves this plan");
+  if (nnz > 0x7fffffffL) return refuse("backward: more than 2^31 nonzeros");
+  c.data = inner ? kBwdInner
+           : o.backward_kernel == ESCOIN_BWD_MFMA ? kBwdMfma
+           : transposable && o.backward_kernel != ESCOIN_KERNEL_GENERIC ? kBwdTransposed : kBwdGather;
+  if (o.wgrad_kernel == ESCOIN_WGRAD_MFMA) c.wgrad = ESCOIN_WGRAD_MFMA;
+  else if (staged_ok && (o.wgrad_kernel == ESCOIN_WGRAD_STAGED ||
+                         (o.wgrad_kernel == ESCOIN_WGRAD_AUTO && stg_auto_prefers(g, nnz, c.stg, n_cu))))
+    c.wgrad = ESCOIN_WGRAD_STAGED;
+  c.chunks_max = (int)(((long)d.N * g.OH * g.OW + kBwdChunkPixels - 1) / kBwdChunkPixels);
+  return c;
 }
 
 bool s2d_plan(const Geometry &g, bool is_f64, S2dPlan *sp) {

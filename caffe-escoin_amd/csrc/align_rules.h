@@ -1,8 +1,8 @@
 // align_rules.h -- WeightAlign's decisions: which conv groups go to the dense kernel, which kernel and layout the sparse
-// ones get, which weight-gradient kernel the backward runs.  Pure C++ (no HIP, no escoin_plan): every rule is a function
-// of values -- geometry, nonzero counts, option values and the device's CU count -- so that it runs, and is tested, on
-// a machine without a GPU (tests/test_align_rules.py).  The .hip files call these and do the device work: uploads,
-// code loads, launches.
+// ones get, which data-gradient and weight-gradient kernels the backward runs or why it refuses (bwd_choice).  Pure C++
+// (no HIP, no escoin_plan): every rule is a function of values -- geometry, nonzero counts, option values and the device's
+// CU count -- so that it runs, and is tested, on a machine without a GPU (tests/test_align_rules.py,
+// tests/test_bwd_choice.py).  The .hip files call these and do the device work: uploads, code loads, launches.
 #ifndef ESCOIN_ALIGN_RULES_H_
 #define ESCOIN_ALIGN_RULES_H_
 
@@ -124,6 +124,7 @@ struct StgPlan {
   int nblk = 0;       // blocks per conv group (grid z)
   int chunks = 0;     // chunks of the full batch
   int osplit = 1;     // workgroups a conv group's output channels are dealt over
+  size_t lds_bytes = 0;   // the tile: sizeof(float) * icb * cs
 };
 // Whether the staged kernel serves this plan, and its block plan where it does.
 bool stg_plan(const Geometry &g, bool is_f64, int wgrad_channel_block, int n_cu, StgPlan *sp);
@@ -214,6 +215,29 @@ struct DgmPlan {
 // phase matrices' floats below 2^31; H, W, the pads and the dilated kernel extent below 2^28; at most 65535 phases and
 // 65535 (group, channel tile) pairs: the grid's y and z; fewer than 2^31 (group, phase, channel tile) triples).
 bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp);
+
+// ---- the backward's kernels (sconv_backward.hip) -------------------------------------------------------------------
+// Whether the data gradient can run as a stride-1 forward of top_diff with the transposed, flipped weights: float plans,
+// stride 1, pad <= dilation * (kernel - 1), at most 32767 output channels per group (a plan's channel limit).
+bool bwd_transposable(const Geometry &g, bool is_f64);
+// The plan options the backward reads (escoin_plan_set_option), and s2d: option "s2d" serves the plan (it has an S2dState).
+struct BwdOptions { int backward_kernel, wgrad_kernel, wgrad_channel_block; bool s2d; };
+// Who computes the data gradient: the inner plan of option "s2d" (AUTO, TILED, JIT and DENSE on such a plan; the inner
+// plan refuses what it cannot serve), the transposed forward plan, the gather kernel, the MFMA kernel of dgrad_mfma.hip.
+enum BwdDataPath { kBwdInner, kBwdTransposed, kBwdGather, kBwdMfma };
+// What the first backward on an alignment builds, or why it builds nothing: rc != ESCOIN_OK is a refusal with its message
+// (the first of the ladder's that applies).  stg / wgm / dgm are filled for the kernel that wgrad / data names.
+struct BwdChoice {
+  int rc = ESCOIN_OK;
+  const char *error = "";
+  BwdDataPath data = kBwdGather;
+  int wgrad = ESCOIN_WGRAD_ENTRY;   // ESCOIN_WGRAD_ENTRY / STAGED / MFMA: what option "wgrad_kernel" resolves to
+  StgPlan stg;
+  WgmPlan wgm;
+  DgmPlan dgm;
+  int chunks_max = 0;               // chunks of the full batch: the slab's rows
+};
+BwdChoice bwd_choice(const Geometry &g, bool is_f64, long nnz, const BwdOptions &o, int n_cu);
 
 // ---- strided layers on the stride-1 kernels via space-to-depth (s2d.hip, plan option "s2d") ------------------------
 // A strided convolution is a stride-1 convolution of the padded bottom split into its stride_h x stride_w pixel phases,

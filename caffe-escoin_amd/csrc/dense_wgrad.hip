@@ -115,18 +115,14 @@ static int dense_wgrad_gpu(escoin_plan *p, const float *bottom, const float *top
   if (!p) return fail(ESCOIN_EINVAL, "null plan");
   if (!p->aligned) return fail(ESCOIN_ESTATE, "dense_wgrad called before weight_align / set_csr");
   if (p->is_f64) return fail(ESCOIN_EINVAL, kNoDouble);
-  {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
-      return fail(ESCOIN_ESTATE, "dense_wgrad: the current device is not the device the plan was aligned on");
-  }
+  if (const int rc = check_plan_device(p, "dense_wgrad")) return rc;
   const Geometry &g = p->g;
   const escoin_conv_desc &d = g.d;
   if (!top_diff) return fail(ESCOIN_EINVAL, "dense_wgrad: top_diff is required");
   if (!bottom) return fail(ESCOIN_EINVAL, "dense_wgrad: bottom is required");
   if (!dense_diff) return fail(ESCOIN_EINVAL, "dense_wgrad: dense_diff is required");
   if (d.fuse_relu && !top) return fail(ESCOIN_EINVAL, "dense_wgrad: a fuse_relu plan needs the forward's top");
-  if (n_images < 0 || n_images > d.N) return fail(ESCOIN_EINVAL, "n_images outside [0, desc.N]");
+  if (const int rc = check_n_images(p, n_images)) return rc;
   hipStream_t stream = (hipStream_t)stream_v;
   if (!p->dwg || p->dwg->device != p->device) {
     const int rc = dwg_build(p, stream);

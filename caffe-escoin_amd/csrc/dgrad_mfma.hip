@@ -153,9 +153,7 @@ escoin_sconv_dgrad_mfma_kernel(DgmArgs a) {
   }
 }
 
-int dgm_build(escoin_plan *p, BwdState *s, hipStream_t stream) {
-  DgmPlan dp;
-  if (!dgm_plan(p->g, p->is_f64, &dp)) return fail(ESCOIN_EINVAL, "backward_kernel: the MFMA data-gradient kernel does not serve this plan");
+int dgm_build(const escoin_plan *p, const DgmPlan &dp, DgmState *m, hipStream_t stream) {
   DgmTables t = dgrad_mfma_tables(csr_view(p), dp);
   std::vector<float> mat((size_t)std::max<long>(dp.mat_floats, 1), 0.f);
   const std::vector<float> flat = flat_entries(p->values);
@@ -163,42 +161,41 @@ int dgm_build(escoin_plan *p, BwdState *s, hipStream_t stream) {
     if ((long)t.pos[e] < 0 || (long)t.pos[e] >= dp.mat_floats) return fail(ESCOIN_EINVAL, "backward_kernel: an entry's place lies outside the phase matrices");
     mat[(size_t)t.pos[e]] = flat[e];
   }
-  s->dgm_phases = dp.phases_h * dp.phases_w;
-  s->dgm_ctiles = dp.ctiles;
-  s->dgm_cols_total = (int)dp.cols_total;
-  s->dgm_lds_bytes = dp.lds_bytes;
-  s->dgm_ppix.resize(dp.phase.size());
-  for (size_t k = 0; k < dp.phase.size(); ++k) s->dgm_ppix[k] = dp.phase[k].rows * dp.phase[k].cols;
-  ESCOIN_HIP_TRY(s->dgm_mat.upload(mat, stream));
-  ESCOIN_HIP_TRY(s->dgm_phase.upload(t.phase, stream));
-  ESCOIN_HIP_TRY(s->dgm_col.upload(t.col, stream));
-  ESCOIN_HIP_TRY(s->dgm_lptr.upload(t.live_ptr, stream));
-  ESCOIN_HIP_TRY(s->dgm_live.upload(t.live, stream));
+  m->phases = dp.phases_h * dp.phases_w;
+  m->ctiles = dp.ctiles;
+  m->cols_total = (int)dp.cols_total;
+  m->lds_bytes = dp.lds_bytes;
+  m->ppix.resize(dp.phase.size());
+  for (size_t k = 0; k < dp.phase.size(); ++k) m->ppix[k] = dp.phase[k].rows * dp.phase[k].cols;
+  ESCOIN_HIP_TRY(m->mat.upload(mat, stream));
+  ESCOIN_HIP_TRY(m->phase.upload(t.phase, stream));
+  ESCOIN_HIP_TRY(m->col.upload(t.col, stream));
+  ESCOIN_HIP_TRY(m->lptr.upload(t.live_ptr, stream));
+  ESCOIN_HIP_TRY(m->live.upload(t.live, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
   t.pos.resize(flat.size());
-  s->dgm_pos = std::move(t.pos);
+  m->pos = std::move(t.pos);
   return ESCOIN_OK;
 }
 
-int launch_dgrad_mfma(const escoin_plan *p, const BwdState *s, const float *top, const float *top_diff,
+int launch_dgrad_mfma(const escoin_plan *p, const DgmState &m, const float *top, const float *top_diff,
                       float *bottom_diff, int n_images, hipStream_t stream) {
   const Geometry &g = p->g;
   const escoin_conv_desc &d = g.d;
-  if (!s->dgm_mat.get<void>() || !s->dgm_phase.get<void>() || !s->dgm_col.get<void>() || !s->dgm_lptr.get<void>() ||
-      !s->dgm_live.get<void>())
+  if (!m.mat.get<void>() || !m.phase.get<void>() || !m.col.get<void>() || !m.lptr.get<void>() || !m.live.get<void>())
     return fail(ESCOIN_ESTATE, "MFMA data-gradient kernel: the backward state has no tables for it");
   long tiles = 0;
-  for (const int ppix : s->dgm_ppix) tiles = std::max(tiles, ((long)n_images * ppix + kDgmTileP - 1) / kDgmTileP);
+  for (const int ppix : m.ppix) tiles = std::max(tiles, ((long)n_images * ppix + kDgmTileP - 1) / kDgmTileP);
   if (tiles == 0) return ESCOIN_OK;                        // nothing to write: no launch
   DgmArgs a;
   a.top_diff = top_diff; a.top = top; a.bottom_diff = bottom_diff;
-  a.mat = s->dgm_mat.get<const float>(); a.col = s->dgm_col.get<const int4>(); a.phase = s->dgm_phase.get<const int>();
-  a.live_ptr = s->dgm_lptr.get<const int>(); a.live = s->dgm_live.get<const int>();
+  a.mat = m.mat.get<const float>(); a.col = m.col.get<const int4>(); a.phase = m.phase.get<const int>();
+  a.live_ptr = m.lptr.get<const int>(); a.live = m.live.get<const int>();
   a.n_images = n_images;
   a.C = d.C; a.H = d.H; a.W = d.W; a.M = d.M; a.OH = g.OH; a.OW = g.OW;
   a.stride_h = d.stride_h; a.stride_w = d.stride_w;
-  a.Cg = g.Cg; a.Mg = g.Mg; a.ctiles = s->dgm_ctiles; a.phases = s->dgm_phases; a.cols_total = s->dgm_cols_total;
-  const dim3 grid((unsigned)tiles, (unsigned)s->dgm_phases, (unsigned)(d.group * s->dgm_ctiles)), block(kDgmThreads);
+  a.Cg = g.Cg; a.Mg = g.Mg; a.ctiles = m.ctiles; a.phases = m.phases; a.cols_total = m.cols_total;
+  const dim3 grid((unsigned)tiles, (unsigned)m.phases, (unsigned)(d.group * m.ctiles)), block(kDgmThreads);
   if (d.fuse_relu) hipLaunchKernelGGL(escoin_sconv_dgrad_mfma_kernel<true>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(escoin_sconv_dgrad_mfma_kernel<false>, grid, block, 0, stream, a);
   ESCOIN_HIP_TRY(hipGetLastError());

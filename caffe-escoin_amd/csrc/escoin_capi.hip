@@ -27,6 +27,18 @@ int fail(int code, const std::string &msg) {
   return code;
 }
 
+int check_plan_device(const escoin_plan *p, const std::string &who) {
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
+    return fail(ESCOIN_ESTATE, who + ": the current device is not the device the plan was aligned on");
+  return ESCOIN_OK;
+}
+
+int check_n_images(const escoin_plan *p, int n_images) {
+  if (n_images < 0 || n_images > p->g.d.N) return fail(ESCOIN_EINVAL, "n_images outside [0, desc.N]");
+  return ESCOIN_OK;
+}
+
 template <typename T>
 int set_csr_host(escoin_plan *p, const int *rowptr, const int *colidx, const T *values, const int *nnz_per_group);
 
@@ -71,9 +83,7 @@ DeviceBytes device_bytes(const escoin_plan *p) {
   if (const UpdState *u = p->upd.get())
     b.upd = u->src.bytes() + u->off.bytes() + u->buf.bytes() + u->wpos.bytes() + u->stage.bytes() + u->e_ptr.bytes() + u->e_off.bytes() + u->e_buf.bytes();
   if (const BwdState *s = p->bwd.get())
-    b.bwd = s->trow.bytes() + s->ttap.bytes() + s->tval.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() + s->stg_blk.bytes() + s->stg_off.bytes() +
-            s->wgm_ent.bytes() + s->wgm_cnt.bytes() + s->wgm_ktab.bytes() +
-            s->dgm_mat.bytes() + s->dgm_phase.bytes() + s->dgm_col.bytes() + s->dgm_lptr.bytes() + s->dgm_live.bytes() +
+    b.bwd = s->gather.bytes() + s->stg.bytes() + s->wgm.bytes() + s->dgm.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() +
             (s->transposed.plan ? device_bytes(s->transposed.plan.get()).fwd : 0);
   if (const S2dState *sd = p->s2d_state.get()) {
     // the X' / dX' scratch and the inner plan's own owners (its update state is never built: the plan's list reaches its copies)
@@ -88,8 +98,9 @@ long bwd_stat(const escoin_plan *p, const char *key) {
   const BwdState *s = p->bwd.get();
   if (!strcmp(key, "bwd_data_kernel")) {
     if (!s) return fail(ESCOIN_ESTATE, "bwd_data_kernel: no backward has run on this alignment");
-    if (s->s2d_inner && p->s2d_state) return bwd_stat(p->s2d_state->inner.plan.get(), key);
-    return s->data_kernel;
+    if (s->data == kBwdInner) return bwd_stat(p->s2d_state->inner.plan.get(), key);
+    if (s->data == kBwdTransposed) return escoin_plan_stat(s->transposed.plan.get(), "kernel_choice");
+    return s->data == kBwdMfma ? ESCOIN_BWD_MFMA : ESCOIN_KERNEL_GENERIC;
   }
   if (!strcmp(key, "bwd_device_bytes")) return (long)device_bytes(p).bwd;
   if (!strcmp(key, "bwd_chunks")) return s ? s->last_chunks : 0;
@@ -98,10 +109,10 @@ long bwd_stat(const escoin_plan *p, const char *key) {
     return s->last_wgrad;
   }
   if (!strcmp(key, "wgrad_lds_bytes")) {
-    if (s && s->wgrad == ESCOIN_WGRAD_MFMA) return (long)s->wgm_lds_bytes;
-    return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg_lds_bytes : 0;
+    if (s && s->wgrad == ESCOIN_WGRAD_MFMA) return (long)s->wgm.lds_bytes;
+    return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg.lds_bytes : 0;
   }
-  if (!strcmp(key, "dgrad_lds_bytes")) return s && s->data_kernel == ESCOIN_BWD_MFMA ? (long)s->dgm_lds_bytes : 0;
+  if (!strcmp(key, "dgrad_lds_bytes")) return s && s->data == kBwdMfma ? (long)s->dgm.lds_bytes : 0;
   if (!strcmp(key, "bwd_align_us")) return s ? (long)(s->align_ms * 1e3) : 0;
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
@@ -812,11 +823,9 @@ int escoin_plan_s2d_pack(escoin_plan *p, const float *bottom_dev, int n_images, 
   return guarded([&]() -> int {
     if (!p || !bottom_dev) return fail(ESCOIN_EINVAL, "null argument");
     if (!p->aligned || !p->s2d_state) return fail(ESCOIN_ESTATE, "s2d_pack: option \"s2d\" is not active on this plan");
-    if (n_images < 0 || n_images > p->g.d.N) return fail(ESCOIN_EINVAL, "n_images outside [0, desc.N]");
+    if (const int rc = check_n_images(p, n_images)) return rc;
     if (n_images == 0) return ESCOIN_OK;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
-      return fail(ESCOIN_ESTATE, "s2d_pack: the current device is not the device the plan was aligned on");
+    if (const int rc = check_plan_device(p, "s2d_pack")) return rc;
     return g_s2d_hooks.pack(p, bottom_dev, p->s2d_state->x.get<float>(), n_images, (hipStream_t)stream);
   });
 }
@@ -827,14 +836,9 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
     if (!p || !bottom_dev || !top_dev) return fail(ESCOIN_EINVAL, "null argument");
     if (!p->aligned) return fail(ESCOIN_ESTATE, "forward called before weight_align / set_csr");
     if (p->is_f64) return fail(ESCOIN_ESTATE, "forward: the plan holds double weights (use escoin_forward_f64)");
-    if (n_images < 0 || n_images > p->g.d.N)
-      return fail(ESCOIN_EINVAL, "n_images outside [0, desc.N]");
+    if (const int rc = check_n_images(p, n_images)) return rc;
     if (n_images == 0) return ESCOIN_OK;
-    {
-      int dev = -1;
-      if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
-        return fail(ESCOIN_ESTATE, "forward: the current device is not the device the plan was aligned on");
-    }
+    if (const int rc = check_plan_device(p, "forward")) return rc;
     // dense kernel, stream-K: a fix-up wait that ran out in an EARLIER launch of this plan left wrong results in that
     // launch's top blob.  The word lives in pinned host memory (no synchronisation here) and stays set until the
     // next WeightAlign: the caller hears about it at the next call at the latest (dense_mfma.hip).
@@ -868,11 +872,9 @@ int escoin_forward_f64(escoin_plan *p, const double *bottom_dev, const double *b
     if (!p || !bottom_dev || !top_dev) return fail(ESCOIN_EINVAL, "null argument");
     if (!p->aligned) return fail(ESCOIN_ESTATE, "forward called before weight_align / set_csr");
     if (!p->is_f64) return fail(ESCOIN_ESTATE, "forward_f64: the plan holds float weights (use escoin_forward)");
-    if (n_images < 0 || n_images > p->g.d.N) return fail(ESCOIN_EINVAL, "n_images outside [0, desc.N]");
+    if (const int rc = check_n_images(p, n_images)) return rc;
     if (n_images == 0) return ESCOIN_OK;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
-      return fail(ESCOIN_ESTATE, "forward: the current device is not the device the plan was aligned on");
+    if (const int rc = check_plan_device(p, "forward")) return rc;
     return launch_generic_f64(p, bottom_dev, bias_dev, top_dev, n_images, (hipStream_t)stream);
   });
 }

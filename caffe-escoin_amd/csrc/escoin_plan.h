@@ -24,6 +24,10 @@ namespace escoin {
 // Thread-local error message behind escoin_last_error().
 void set_error(const std::string &msg);
 int fail(int code, const std::string &msg);
+// Two checks of the device entry points (escoin_capi.hip): the current device is the one the plan was aligned on (`who`
+// begins the message), and n_images lies in [0, desc.N].  ESCOIN_OK or the failure's code, the message set.
+int check_plan_device(const escoin_plan *p, const std::string &who);
+int check_n_images(const escoin_plan *p, int n_images);
 
 #define ESCOIN_HIP_TRY(expr)                                                          \
   do {                                                                                \
@@ -87,53 +91,75 @@ struct DerivedPlan {
   std::vector<int> src;   // host: this plan's entry k holds the value of the owner's entry src[k] (flat index, groups concatenated)
 };
 
-// What the first escoin_backward on an alignment builds (sconv_backward.hip); reset with the device side.  It holds at
-// most one copy of the plan's values for the data gradient, and data_kernel says which: the transposed forward plan
-// (path a), the gather kernel's tval (path b), the MFMA kernel's dgm_mat (path c) -- or none (s2d_inner).
-struct BwdState {
-  DerivedPlan transposed;   // path (a): the data gradient as a stride-1 forward of top_diff; plan null on the other paths
-  int data_kernel = ESCOIN_KERNEL_GENERIC;
-  DeviceBuffer trow;   // [C + 1] absolute offsets into ttap / tval (gather kernel)
+// What the first escoin_backward on an alignment builds (sconv_backward.hip, as align_rules.h bwd_choice decides); reset
+// with the device side.  One sub-struct per kernel, each with the device bytes of its own buffers, and what the kernels
+// share.  The state holds at most one copy of the plan's values for the data gradient, and `data` says which.
+
+// The gather kernel (kBwdGather): the transposed CSR (csr_tables.h gather_transpose)
+struct GatherDgrad {
+  DeviceBuffer trow;   // [C + 1] absolute offsets into ttap / tval
   DeviceBuffer ttap;   // per transposed entry: ocl << 16 | kr << 8 | kc
   DeviceBuffer tval;   // float or double values, in the transposed order
-  DeviceBuffer wpos;   // per CSR entry: oc * kdim + colidx (its position in weight_diff)
-  DeviceBuffer slab;   // [chunks_max][nnz] weight partials, then [chunks_max][M] bias partials
-  DeviceBuffer g;      // fuse_relu + path (a): top_diff * [top > 0], desc.N x M x OH x OW
-  long nnz = 0;
-  int chunks_max = 0, last_chunks = 0;
-  // weight gradient, LDS-staged kernel (option "wgrad_kernel"): wgrad = what the option resolved to on this alignment,
-  // last_wgrad = what the last weight / bias gradient ran (0: none yet)
-  int wgrad = ESCOIN_WGRAD_ENTRY, last_wgrad = 0;
-  int stg_icb = 0, stg_nblk = 0;       // input channels per staged block, blocks per conv group
-  int stg_rows = 0;                    // padded rows of the LDS tile (the longest chunk's span)
-  int stg_osplit = 1;                  // workgroups a conv group's output channels are dealt over
-  size_t stg_lds_bytes = 0;
-  DeviceBuffer stg_blk;  // [M][stg_nblk + 1] absolute entry index where output channel oc's entries of block b begin
-  DeviceBuffer stg_off;  // [nnz] per CSR entry: its tap's float offset inside the staged block's LDS tile
-  // weight gradient, fp32-MFMA kernel (wgrad_mfma.hip; the tables: csr_tables.h wgrad_mfma_tables)
-  int wgm_mtiles = 0, wgm_ktiles = 0;  // tiles per conv group along the output channels / the columns
-  size_t wgm_lds_bytes = 0;
-  DeviceBuffer wgm_ent;   // [M * kdim] (row, column) -> CSR entry, -1: none
-  DeviceBuffer wgm_cnt;   // [group * mtiles * ktiles] entries per tile
-  DeviceBuffer wgm_ktab;  // [4 * ktiles * tile_k] the im2col decode of a column
-  // data gradient, fp32-MFMA kernel (dgrad_mfma.hip, option "backward_kernel" = ESCOIN_BWD_MFMA; the tables: csr_tables.h
-  // dgrad_mfma_tables)
-  int dgm_phases = 0, dgm_ctiles = 0, dgm_cols_total = 0;
-  size_t dgm_lds_bytes = 0;
-  DeviceBuffer dgm_mat;    // the phase matrices: the weights transposed, columns permuted by phase, zero outside the pattern
-  DeviceBuffer dgm_phase;  // [phases][8] a phase's pixels, columns and place in dgm_col / dgm_mat
-  DeviceBuffer dgm_col;    // [4 * cols_total] the decode of a column: {G offset of ocl, dh, dw, valid}
-  DeviceBuffer dgm_lptr;   // [group * phases * ctiles + 1] into dgm_live
-  DeviceBuffer dgm_live;   // the live steps of every (group, phase, channel tile), ascending
-  std::vector<int> dgm_ppix;   // host: [phases] a phase's pixels per image (the launch's grid)
-  std::vector<int> dgm_pos;    // host: [nnz] the element of dgm_mat that holds CSR entry e -- how weight updates reach it
-  double align_ms = 0.0;
-  // host, path (b): element k of tval (and of ttap) holds the value of the plan's CSR entry tsrc[k] (flat index, groups
+  // host: element k of tval (and of ttap) holds the value of the plan's CSR entry tsrc[k] (flat index, groups
   // concatenated).  Not transposed.src: the gather kernel's order is another than the transposed plan's.
   std::vector<int> tsrc;
-  // option "s2d": the data gradient is the inner plan's backward followed by the unpack kernel (S2dState); this state
-  // then holds the weight gradient's side only and no copy of the values -- those are the inner plan's backward state's
-  bool s2d_inner = false;
+  size_t bytes() const { return trow.bytes() + ttap.bytes() + tval.bytes(); }
+};
+
+// The LDS-staged weight-gradient kernel (ESCOIN_WGRAD_STAGED; align_rules.h StgPlan, csr_tables.h staged_tables)
+struct StagedWgrad {
+  int icb = 0, nblk = 0;       // input channels per staged block, blocks per conv group
+  int rows = 0;                // padded rows of the LDS tile (the longest chunk's span)
+  int osplit = 1;              // workgroups a conv group's output channels are dealt over
+  size_t lds_bytes = 0;
+  DeviceBuffer blk;  // [M][nblk + 1] absolute entry index where output channel oc's entries of block b begin
+  DeviceBuffer off;  // [nnz] per CSR entry: its tap's float offset inside the staged block's LDS tile
+  size_t bytes() const { return blk.bytes() + off.bytes(); }
+};
+
+// The fp32-MFMA weight-gradient kernel (ESCOIN_WGRAD_MFMA; wgrad_mfma.hip; the tables: csr_tables.h wgrad_mfma_tables)
+struct WgmState {
+  int mtiles = 0, ktiles = 0;  // tiles per conv group along the output channels / the columns
+  size_t lds_bytes = 0;
+  DeviceBuffer ent;   // [M * kdim] (row, column) -> CSR entry, -1: none
+  DeviceBuffer cnt;   // [group * mtiles * ktiles] entries per tile
+  DeviceBuffer ktab;  // [4 * ktiles * tile_k] the im2col decode of a column
+  size_t bytes() const { return ent.bytes() + cnt.bytes() + ktab.bytes(); }
+};
+
+// The fp32-MFMA data-gradient kernel (kBwdMfma; dgrad_mfma.hip; the tables: csr_tables.h dgrad_mfma_tables)
+struct DgmState {
+  int phases = 0, ctiles = 0, cols_total = 0;
+  size_t lds_bytes = 0;
+  DeviceBuffer mat;    // the phase matrices: the weights transposed, columns permuted by phase, zero outside the pattern
+  DeviceBuffer phase;  // [phases][8] a phase's pixels, columns and place in col / mat
+  DeviceBuffer col;    // [4 * cols_total] the decode of a column: {G offset of ocl, dh, dw, valid}
+  DeviceBuffer lptr;   // [group * phases * ctiles + 1] into live
+  DeviceBuffer live;   // the live steps of every (group, phase, channel tile), ascending
+  std::vector<int> ppix;   // host: [phases] a phase's pixels per image (the launch's grid)
+  std::vector<int> pos;    // host: [nnz] the element of mat that holds CSR entry e -- how weight updates reach it
+  size_t bytes() const { return mat.bytes() + phase.bytes() + col.bytes() + lptr.bytes() + live.bytes(); }
+};
+
+struct BwdState {
+  // who computes the data gradient, and with it where the state's copy of the values is: the inner plan's backward state
+  // (kBwdInner: option "s2d", the inner plan's backward followed by the unpack kernel -- this state then holds the weight
+  // gradient's side only), `transposed`, gather.tval, dgm.mat
+  BwdDataPath data = kBwdGather;
+  DerivedPlan transposed;   // kBwdTransposed: the data gradient as a stride-1 forward of top_diff; plan null on the other paths
+  GatherDgrad gather;
+  DgmState dgm;
+  DeviceBuffer wpos;   // per CSR entry: oc * kdim + colidx (its position in weight_diff)
+  DeviceBuffer slab;   // [chunks_max][nnz] weight partials, then [chunks_max][M] bias partials
+  DeviceBuffer g;      // fuse_relu + kBwdTransposed: top_diff * [top > 0], desc.N x M x OH x OW
+  long nnz = 0;
+  int chunks_max = 0, last_chunks = 0;
+  // weight gradient (option "wgrad_kernel"): wgrad = what the option resolved to on this alignment, last_wgrad = what the
+  // last weight / bias gradient ran (0: none yet)
+  int wgrad = ESCOIN_WGRAD_ENTRY, last_wgrad = 0;
+  StagedWgrad stg;
+  WgmState wgm;
+  double align_ms = 0.0;
 };
 
 // What upload() builds for a plan that option "s2d" serves (escoin_capi.hip; the rules: align_rules.h s2d_plan, csr_tables.h
@@ -416,16 +442,16 @@ int dense_build_ktab(escoin_plan *p, hipStream_t stream);
 int dense_lda(int K);          // floats per row of d_dense_w (K rounded up to whole k-steps)
 int dense_spare_rows();       // zero rows after row M - 1
 
-// wgrad_mfma.hip (option "wgrad_kernel" = MFMA): builds the kernel's tables into the backward state; stage 1 of the
-// weight gradient over `chunks` chunks of n_images images into slab_w [chunks][nnz]
-int wgm_build(escoin_plan *p, BwdState *s, hipStream_t stream);
-int launch_wgrad_mfma(const escoin_plan *p, const BwdState *s, const float *bottom, const float *top,
+// wgrad_mfma.hip (option "wgrad_kernel" = MFMA): builds the kernel's tables for the tile plan bwd_choice made; stage 1 of
+// the weight gradient of the plan's nnz entries over `chunks` chunks of n_images images into slab_w [chunks][nnz]
+int wgm_build(const escoin_plan *p, const WgmPlan &wp, WgmState *w, hipStream_t stream);
+int launch_wgrad_mfma(const escoin_plan *p, const WgmState &w, long nnz, const float *bottom, const float *top,
                       const float *top_diff, float *slab_w, int n_images, int chunks, hipStream_t stream);
 
-// dgrad_mfma.hip (option "backward_kernel" = ESCOIN_BWD_MFMA): builds the phase matrices and the kernel's tables into the
-// backward state; the data gradient of n_images images
-int dgm_build(escoin_plan *p, BwdState *s, hipStream_t stream);
-int launch_dgrad_mfma(const escoin_plan *p, const BwdState *s, const float *top, const float *top_diff,
+// dgrad_mfma.hip (option "backward_kernel" = ESCOIN_BWD_MFMA): builds the phase matrices and the kernel's tables for the
+// tile plan bwd_choice made; the data gradient of n_images images
+int dgm_build(const escoin_plan *p, const DgmPlan &dp, DgmState *m, hipStream_t stream);
+int launch_dgrad_mfma(const escoin_plan *p, const DgmState &m, const float *top, const float *top_diff,
                       float *bottom_diff, int n_images, hipStream_t stream);
 
 // s2d.hip (option "s2d"): X' of the first n_images images from the bottom blob (pack), bottom_diff of the first n_images

@@ -131,10 +131,7 @@ int check_device_plan(const escoin_plan *p, const char *name) {
   if (!p->aligned)
     return fail(ESCOIN_ESTATE, p->host_aligned ? n + ": the plan is aligned on the host only (use escoin_plan_" + n + "_cpu)"
                                                : n + " called before weight_align / set_csr");
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
-    return fail(ESCOIN_ESTATE, n + ": the current device is not the device the plan was aligned on");
-  return ESCOIN_OK;
+  return check_plan_device(p, n);
 }
 
 }  // namespace prune

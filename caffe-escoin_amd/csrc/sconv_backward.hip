@@ -29,9 +29,14 @@
 //     (option "wgrad_kernel": stage 1 by the LDS-staged kernel below, or by the fp32-MFMA kernel of wgrad_mfma.hip -- same
 //     chunks, same slab; the MFMA kernel's bias gradient is the entry kernel's, launched for the bias alone)
 //
-// The backward state (transposed CSR or transposed plan, slab, ReLU scratch) is built by the first backward on an
-// aligned plan -- its index tables by the host-only builders of csr_tables.h, this file uploads them -- and dropped with the device side (free_device: weight_align / set_csr / import_aligned; destroy); later
-// calls allocate nothing and synchronise nothing, so they can be captured into a graph.
+// Which of these kernels a plan gets, and what it refuses, is decided by the host-only rule bwd_choice (align_rules.h);
+// bwd_build here calls it once and does the device work.  The backward state (BwdState, escoin_plan.h: one sub-struct per
+// kernel -- GatherDgrad, DgmState, StagedWgrad, WgmState -- next to the transposed plan, the slab and the ReLU scratch) is
+// built by the first backward on an aligned plan -- its index tables by the host-only builders of csr_tables.h, this file
+// uploads them -- and dropped with the device side (free_device: weight_align / set_csr / import_aligned; destroy); later
+// calls allocate nothing and synchronise nothing, so they can be captured into a graph.  backward_gpu is the driver:
+// checks, state, then data_gradient (a switch over BwdState::data, one function per path) and weight_gradient
+// (wgrad_entry / wgrad_staged / wgrad_mfma over the shared stage-1 and stage-2 launch helpers).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -269,7 +274,7 @@ escoin_sconv_wgrad_sum_f64_kernel(const double *slab_w, const double *slab_b, co
 //   staging   the padded rows the chunk's pixels touch (images stacked Hp rows apart, the halo and images past n_images
 //             as zeros), for the block's channels, into LDS -- once;
 //   walk      each wave takes whole output channels: G for all 1024 pixels of the chunk in registers (16 per lane), then
-//             the channel's CSR entries of this block (the host table stg_blk: rows are sorted by input channel); per
+//             the channel's CSR entries of this block (the host table blk: rows are sorted by input channel); per
 //             entry 16 LDS reads and 16 FMAs into the lane's own partial, no cross-lane step;
 //   reduce    eight entries at a time: three halving exchanges (a lane keeps half the entries and receives its partner's
 //             partials for them), then a butterfly over the last three lane bits -- per entry the pairing (lane ^ 32,
@@ -372,7 +377,7 @@ __device__ inline void stg_walk(const StagedArgs &a, const float *tile, int chun
       sb = wave_sum(sb);
       if (lane == 0) a.slab_b[(size_t)chunk * a.M + oc] = sb;
     }
-    // the tap offsets of a batch are fetched one batch ahead (stg_off is padded by two batches): a scalar load shares
+    // the tap offsets of a batch are fetched one batch ahead (off is padded by two batches): a scalar load shares
     // its counter with the LDS reads, so waiting for one inside the walk would drain the other
     int o[kStgBatch], o_next[kStgBatch] = {};
     if (jb != je) {   // (a bias-only walk fetches nothing)
@@ -479,14 +484,9 @@ escoin_sconv_wgrad_tree_sum_kernel(const float *__restrict__ slab_w, const float
   }
 }
 
-// ---- backward state ---------------------------------------------------------------------------------------------
-bool bwd_transposable(const escoin_plan *p) {
-  const escoin_conv_desc &d = p->g.d;
-  return !p->is_f64 && d.stride_h == 1 && d.stride_w == 1 && d.pad_h <= d.dil_h * (d.KH - 1) &&
-         d.pad_w <= d.dil_w * (d.KW - 1) && p->g.Mg <= 32767;
-}
-
-// The transposed forward plan of path (a): geometry of the data gradient as a stride-1 forward of G.
+// ---- backward state: the device work for what align_rules.h bwd_choice decided ------------------------------------
+// The transposed forward plan of path (a): geometry of the data gradient as a stride-1 forward of G; for fuse_relu plans
+// also the scratch that holds G.
 static int build_transposed_plan(escoin_plan *p, BwdState *s, hipStream_t stream) {
   const Geometry &g = p->g;
   const escoin_conv_desc &d = g.d;
@@ -499,121 +499,282 @@ static int build_transposed_plan(escoin_plan *p, BwdState *s, hipStream_t stream
   t.fuse_relu = 0;
   // the forced data-gradient kernel is this plan's forward kernel; it has no backward of its own
   const int rc = build_derived_plan(p, t, p->bwd_kernel, ESCOIN_KERNEL_AUTO, forward_transpose(csr_view(p)), stream, &s->transposed);
-  if (rc != ESCOIN_OK) return rc;
-  s->data_kernel = (int)escoin_plan_stat(s->transposed.plan.get(), "kernel_choice");
+  if (rc != ESCOIN_OK || !d.fuse_relu) return rc;
+  ESCOIN_HIP_TRY(s->g.alloc(sizeof(float) * (size_t)d.N * d.M * g.OH * g.OW));
   return ESCOIN_OK;
 }
 
 // The gather kernel's transposed CSR (csr_tables.h gather_transpose), with the values in its order.
 template <typename T>
-static int build_gather(escoin_plan *p, BwdState *s, hipStream_t stream) {
+static int build_gather(escoin_plan *p, GatherDgrad *ga, hipStream_t stream) {
   GatherTables t = gather_transpose(csr_view(p));
   const std::vector<T> flat = flat_entries(plan_vals<T>(p));
   std::vector<T> tval(t.ttap.size(), T(0));
   for (size_t k = 0; k < t.tsrc.size(); ++k) tval[k] = flat[(size_t)t.tsrc[k]];
-  ESCOIN_HIP_TRY(s->trow.upload(t.trow, stream));
-  ESCOIN_HIP_TRY(s->ttap.upload(t.ttap, stream));
-  ESCOIN_HIP_TRY(s->tval.upload(tval, stream));
+  ESCOIN_HIP_TRY(ga->trow.upload(t.trow, stream));
+  ESCOIN_HIP_TRY(ga->ttap.upload(t.ttap, stream));
+  ESCOIN_HIP_TRY(ga->tval.upload(tval, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
-  s->tsrc = std::move(t.tsrc);
+  ga->tsrc = std::move(t.tsrc);
   return ESCOIN_OK;
 }
 
-static int stg_build(escoin_plan *p, BwdState *s, const StgPlan &sp, hipStream_t stream) {
-  s->stg_icb = sp.icb;
-  s->stg_nblk = sp.nblk;
-  s->stg_rows = sp.rows_max;
-  s->stg_lds_bytes = sizeof(float) * (size_t)sp.icb * (size_t)sp.cs;
-  s->stg_osplit = sp.osplit;
+static int stg_build(const escoin_plan *p, const StgPlan &sp, StagedWgrad *st, hipStream_t stream) {
+  st->icb = sp.icb;
+  st->nblk = sp.nblk;
+  st->rows = sp.rows_max;
+  st->lds_bytes = sp.lds_bytes;
+  st->osplit = sp.osplit;
   const StagedTables t = staged_tables(csr_view(p), sp.icb, sp.nblk, sp.cs, p->g.d.W + 2 * p->g.d.pad_w);
-  ESCOIN_HIP_TRY(s->stg_blk.upload(t.blk, stream));
-  ESCOIN_HIP_TRY(s->stg_off.upload(t.off, stream));
+  ESCOIN_HIP_TRY(st->blk.upload(t.blk, stream));
+  ESCOIN_HIP_TRY(st->off.upload(t.off, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
+  return ESCOIN_OK;
+}
+
+template <typename T> static int bwd_build(escoin_plan *p, hipStream_t stream);
+
+// The plan's backward state, built where this alignment has none yet; a refused or failed build leaves none behind.
+template <typename T>
+static int ensure_state(escoin_plan *p, hipStream_t stream) {
+  if (p->bwd) return ESCOIN_OK;
+  const int rc = bwd_build<T>(p, stream);
+  if (rc != ESCOIN_OK) p->bwd.reset();
+  return rc;
+}
+
+// The data gradient's side of the state.
+template <typename T>
+static int build_data(escoin_plan *p, BwdState *s, const BwdChoice &c, hipStream_t stream) {
+  switch (c.data) {
+    // the inner plan's backward state is built here, with this one: the update list is rebuilt once for both, and no
+    // later call allocates (dX' is the X' scratch)
+    case kBwdInner: return ensure_state<float>(p->s2d_state->inner.plan.get(), stream);
+    case kBwdTransposed: return build_transposed_plan(p, s, stream);
+    case kBwdMfma: return dgm_build(p, c.dgm, &s->dgm, stream);
+    case kBwdGather: break;
+  }
+  return build_gather<T>(p, &s->gather, stream);
+}
+
+// The rule decides (align_rules.h bwd_choice), this does the device work: uploads, allocations, the derived plans.
+template <typename T>
+static int bwd_build(escoin_plan *p, hipStream_t stream) {
+  const auto t0 = std::chrono::steady_clock::now();
+  // (after device-source weight updates the host CSR this state is built from is stale: the values come back first)
+  if (const int rcs = sync_host_values(p)) return rcs;
+  const Geometry &g = p->g;
+  const long nnz = plan_nnz(p);
+  const BwdOptions o{p->bwd_kernel, p->wgrad_kernel, p->wgrad_channel_block, p->s2d_state != nullptr};
+  const BwdChoice c = bwd_choice(g, p->is_f64, nnz, o, tiled_device_cus());
+  if (c.rc != ESCOIN_OK) return fail(c.rc, c.error);
+  p->bwd.reset(new BwdState());
+  BwdState *s = p->bwd.get();
+  s->nnz = nnz; s->data = c.data; s->wgrad = c.wgrad; s->chunks_max = c.chunks_max;
+  int rc = build_data<T>(p, s, c, stream);
+  if (rc != ESCOIN_OK) return rc;
+  const std::vector<int> wpos = dense_positions(csr_view(p), g.kdim);   // (lives until the synchronise below)
+  ESCOIN_HIP_TRY(s->wpos.upload(wpos, stream));
+  ESCOIN_HIP_TRY(s->slab.alloc(sizeof(T) * (size_t)s->chunks_max * (size_t)(nnz + g.d.M)));
+  if (c.wgrad == ESCOIN_WGRAD_MFMA) rc = wgm_build(p, c.wgm, &s->wgm, stream);
+  else if (c.wgrad == ESCOIN_WGRAD_STAGED) rc = stg_build(p, c.stg, &s->stg, stream);
+  if (rc != ESCOIN_OK) return rc;
+  ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
+  s->align_ms = ms_since(t0);
+  return ESCOIN_OK;
+}
+
+// ---- data gradient: one function per path ----------------------------------------------------------------------------
+// option "s2d": dX' = the inner plan's data gradient of top_diff (the ReLU mask is its own), then depth-to-space
+static int dgrad_inner(escoin_plan *p, const float *top, const float *top_diff, float *bottom_diff, int n_images,
+                       hipStream_t stream) {
+  S2dState *sd = p->s2d_state.get();
+  const int rc = escoin_backward(sd->inner.plan.get(), nullptr, top, top_diff, sd->x.get<float>(), nullptr, nullptr, n_images, stream);
+  return rc != ESCOIN_OK ? rc : g_s2d_hooks.unpack(p, sd->x.get<const float>(), bottom_diff, n_images, stream);
+}
+
+static int dgrad_transposed(escoin_plan *p, const float *top, const float *top_diff, float *bottom_diff, int n_images,
+                            hipStream_t stream) {
+  const Geometry &g = p->g;
+  const BwdState *s = p->bwd.get();
+  const float *src = top_diff;
+  if (g.d.fuse_relu) {
+    const size_t count = (size_t)n_images * g.d.M * g.OH * g.OW;
+    const unsigned blocks = (unsigned)std::min<size_t>((count + 255) / 256, 8192);
+    hipLaunchKernelGGL(escoin_sconv_bwd_relu_mask_kernel, dim3(blocks), dim3(256), 0, stream, top_diff, top, s->g.get<float>(), count);
+    ESCOIN_HIP_TRY(hipGetLastError());
+    src = s->g.get<const float>();
+  }
+  return escoin_forward(s->transposed.plan.get(), src, nullptr, bottom_diff, n_images, stream);
+}
+
+// One launch of a kernel that is compiled with and without the fuse_relu mask.
+template <typename A>
+static int launch_relu_pair(bool relu, void (*masked)(A), void (*plain)(A), dim3 grid, dim3 block, size_t lds, hipStream_t stream,
+                            const A &a) {
+  hipLaunchKernelGGL(relu ? masked : plain, grid, block, lds, stream, a);
+  ESCOIN_HIP_TRY(hipGetLastError());
   return ESCOIN_OK;
 }
 
 template <typename T>
-static int bwd_build(escoin_plan *p, hipStream_t stream) {
-  const auto t0 = std::chrono::steady_clock::now();
+static int dgrad_gather(const escoin_plan *p, const T *top, const T *top_diff, T *bottom_diff, int n_images, hipStream_t stream) {
   const Geometry &g = p->g;
   const escoin_conv_desc &d = g.d;
-  if (g.Mg > 65535) return fail(ESCOIN_EINVAL, "backward: more than 65535 output channels per group");
-  if (d.C > 4 * 65535 || d.N > 65535) return fail(ESCOIN_EINVAL, "backward: grid dimension exceeds 65535");
-  // (after device-source weight updates the host CSR this state is built from is stale: the values come back first)
-  if (const int rcs = sync_host_values(p)) return rcs;
-  const bool transposable = bwd_transposable(p);
-  const bool forced = p->bwd_kernel == ESCOIN_KERNEL_TILED || p->bwd_kernel == ESCOIN_KERNEL_JIT ||
-                      p->bwd_kernel == ESCOIN_KERNEL_DENSE;
-  // option "s2d": AUTO, TILED, JIT and DENSE are the inner plan's backward (which refuses what it cannot serve); GENERIC
-  // and BWD_MFMA keep this plan's gather / MFMA kernel
-  const bool s2d_inner = p->s2d_state && p->bwd_kernel != ESCOIN_KERNEL_GENERIC && p->bwd_kernel != ESCOIN_BWD_MFMA;
-  if (forced && !transposable && !s2d_inner)
-    return fail(ESCOIN_EINVAL, "backward_kernel: this plan has no transposed forward plan (needs a float plan, stride 1, "
-                               "pad <= dilation * (kernel - 1)); only the gather kernel serves it");
-  StgPlan sp;
-  const bool staged_ok = stg_plan(g, p->is_f64, p->wgrad_channel_block, tiled_device_cus(), &sp);
-  if (p->wgrad_kernel == ESCOIN_WGRAD_STAGED && !staged_ok)
-    return fail(ESCOIN_EINVAL, "wgrad_kernel: the staged weight-gradient kernel needs a float plan with stride 1 whose "
-                               "chunk tile of one input channel fits the LDS budget; only the entry kernel serves this plan");
-  WgmPlan wp;
-  if (p->wgrad_kernel == ESCOIN_WGRAD_MFMA && !wgm_plan(g, p->is_f64, &wp))
-    return fail(ESCOIN_EINVAL, "wgrad_kernel: the MFMA weight-gradient kernel needs a float plan whose pixel, weight and "
-                               "image indices fit 31 bits; the entry kernel serves this plan");
-  DgmPlan dp;
-  if (p->bwd_kernel == ESCOIN_BWD_MFMA && !dgm_plan(g, p->is_f64, &dp))
-    return fail(ESCOIN_EINVAL, "backward_kernel: the MFMA data-gradient kernel needs a float plan whose pixel, top and "
-                               "matrix indices fit 31 bits; the gather kernel serves this plan");
-  p->bwd.reset(new BwdState());
-  BwdState *s = p->bwd.get();
-  s->nnz = plan_nnz(p);
-  if (s->nnz > 0x7fffffffL) return fail(ESCOIN_EINVAL, "backward: more than 2^31 nonzeros");
-  int rc = ESCOIN_OK;
-  if (s2d_inner) {
-    // the inner plan's backward state is built here, with this one: the update list is rebuilt once for both, and no
-    // later call allocates (dX' is the X' scratch)
-    if constexpr (sizeof(T) == 4) {
-      escoin_plan *ip = p->s2d_state->inner.plan.get();
-      s->s2d_inner = true;
-      if (!ip->bwd && (rc = bwd_build<float>(ip, stream)) != ESCOIN_OK) ip->bwd.reset();
-      if (rc == ESCOIN_OK) s->data_kernel = ip->bwd->data_kernel;
+  const GatherDgrad &ga = p->bwd->gather;
+  BwdDataArgs<T> a;
+  a.top_diff = top_diff; a.top = top; a.bottom_diff = bottom_diff;
+  a.trow = ga.trow.get<int>(); a.ttap = ga.ttap.get<int>(); a.tval = ga.tval.get<T>();
+  a.C = d.C; a.H = d.H; a.W = d.W; a.M = d.M; a.OH = g.OH; a.OW = g.OW;
+  a.pad_h = d.pad_h; a.pad_w = d.pad_w; a.stride_h = d.stride_h; a.stride_w = d.stride_w;
+  a.dil_h = d.dil_h; a.dil_w = d.dil_w; a.Cg = g.Cg; a.Mg = g.Mg;
+  const dim3 grid((d.H * d.W + 63) / 64, (d.C + kBwdWaves - 1) / kBwdWaves, n_images), block(64, kBwdWaves);
+  if constexpr (sizeof(T) == 8)
+    return launch_relu_pair(d.fuse_relu, escoin_sconv_bwd_data_f64_kernel<true>, escoin_sconv_bwd_data_f64_kernel<false>, grid, block, 0, stream, a);
+  else
+    return launch_relu_pair(d.fuse_relu, escoin_sconv_bwd_data_kernel<true>, escoin_sconv_bwd_data_kernel<false>, grid, block, 0, stream, a);
+}
+
+template <typename T>
+static int data_gradient(escoin_plan *p, const T *top, const T *top_diff, T *bottom_diff, int n_images, hipStream_t stream) {
+  if constexpr (sizeof(T) == 4) {   // (a double plan's data gradient is the gather kernel's: bwd_choice)
+    switch (p->bwd->data) {
+      case kBwdInner: return dgrad_inner(p, top, top_diff, bottom_diff, n_images, stream);
+      case kBwdTransposed: return dgrad_transposed(p, top, top_diff, bottom_diff, n_images, stream);
+      case kBwdMfma: return launch_dgrad_mfma(p, p->bwd->dgm, top, top_diff, bottom_diff, n_images, stream);
+      case kBwdGather: break;
     }
-  } else if (p->bwd_kernel == ESCOIN_BWD_MFMA) {
-    if constexpr (sizeof(T) == 4) {
-      s->data_kernel = ESCOIN_BWD_MFMA;
-      rc = dgm_build(p, s, stream);
-    }
-  } else if (transposable && p->bwd_kernel != ESCOIN_KERNEL_GENERIC) {
-    rc = build_transposed_plan(p, s, stream);
-    if (rc == ESCOIN_OK && d.fuse_relu) {
-      const size_t bytes = sizeof(float) * (size_t)d.N * d.M * g.OH * g.OW;
-      ESCOIN_HIP_TRY(s->g.alloc(bytes));
-    }
-  } else {
-    s->data_kernel = ESCOIN_KERNEL_GENERIC;
-    rc = build_gather<T>(p, s, stream);
   }
-  if (rc != ESCOIN_OK) return rc;
-  const std::vector<int> wpos = dense_positions(csr_view(p), g.kdim);   // (lives until the synchronise below)
-  ESCOIN_HIP_TRY(s->wpos.upload(wpos, stream));
-  s->chunks_max = (int)(((long)d.N * g.OH * g.OW + kChunkPixels - 1) / kChunkPixels);
-  const size_t slab = sizeof(T) * (size_t)s->chunks_max * (size_t)(s->nnz + d.M);
-  ESCOIN_HIP_TRY(s->slab.alloc(slab));
-  s->wgrad = ESCOIN_WGRAD_ENTRY;
-  if (p->wgrad_kernel == ESCOIN_WGRAD_MFMA) {
-    if constexpr (sizeof(T) == 4) {
-      if ((rc = wgm_build(p, s, stream)) != ESCOIN_OK) return rc;
-      s->wgrad = ESCOIN_WGRAD_MFMA;
-    }
-  } else if (staged_ok && (p->wgrad_kernel == ESCOIN_WGRAD_STAGED ||
-                    (p->wgrad_kernel == ESCOIN_WGRAD_AUTO && stg_auto_prefers(g, s->nnz, sp, tiled_device_cus())))) {
-    if ((rc = stg_build(p, s, sp, stream)) != ESCOIN_OK) return rc;
-    s->wgrad = ESCOIN_WGRAD_STAGED;
-  }
-  ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
-  s->align_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return dgrad_gather<T>(p, top, top_diff, bottom_diff, n_images, stream);
+}
+
+// ---- weight / bias gradient: stage 1 by one of three kernels, stage 2 by one of two sums -----------------------------
+// One call's blobs, outputs (either may be null), slab and chunks.
+template <typename T>
+struct WgradCall {
+  const T *bottom, *top, *top_diff;
+  T *weight_diff, *bias_diff;
+  T *slab_w, *slab_b;
+  const int *wpos;       // null: compact output (escoin_backward_values), stage 2 writes entry e to weight_diff[e]
+  int n_images, chunks;
+  hipStream_t stream;
+};
+
+// Stage 1 by the entry kernel, for the weights and / or the bias.
+template <typename T>
+static int launch_partial(const escoin_plan *p, const WgradCall<T> &c, bool want_w, bool want_b) {
+  const Geometry &g = p->g;
+  const escoin_conv_desc &d = g.d;
+  if (d.M > 65535) return fail(ESCOIN_EINVAL, "backward: more than 65535 output channels");
+  WgradArgs<T> a;
+  a.bottom = c.bottom; a.top_diff = c.top_diff; a.top = c.top;
+  a.rowptr = p->gen.rowptr.get<int>(); a.taps = p->gen.taps.get<int>();
+  a.slab_w = c.slab_w; a.slab_b = c.slab_b;
+  a.total = (long)c.n_images * g.OH * g.OW; a.nnz = (int)p->bwd->nnz;
+  a.C = d.C; a.H = d.H; a.W = d.W; a.M = d.M; a.OH = g.OH; a.OW = g.OW;
+  a.pad_h = d.pad_h; a.pad_w = d.pad_w; a.stride_h = d.stride_h; a.stride_w = d.stride_w;
+  a.dil_h = d.dil_h; a.dil_w = d.dil_w; a.Cg = g.Cg; a.Mg = g.Mg;
+  a.want_w = want_w; a.want_b = want_b;
+  const dim3 grid(c.chunks, d.M), block(64 * kBwdWaves);
+  if constexpr (sizeof(T) == 8)
+    return launch_relu_pair(d.fuse_relu, escoin_sconv_wgrad_partial_f64_kernel<true>, escoin_sconv_wgrad_partial_f64_kernel<false>, grid, block, 0, c.stream, a);
+  else
+    return launch_relu_pair(d.fuse_relu, escoin_sconv_wgrad_partial_kernel<true>, escoin_sconv_wgrad_partial_kernel<false>, grid, block, 0, c.stream, a);
+}
+
+// Stage 2, one lane per item: the slab's columns into weight_diff and / or bias_diff (a null one is left out).
+template <typename T>
+static int launch_sum(const escoin_plan *p, const WgradCall<T> &c, T *weight_diff, T *bias_diff) {
+  const int nnz = (int)p->bwd->nnz, M = p->g.d.M;
+  const long lanes = (weight_diff ? nnz : 0) + (bias_diff ? M : 0);
+  if (lanes == 0) return ESCOIN_OK;
+  const dim3 grid((unsigned)((lanes + 255) / 256));
+  if constexpr (sizeof(T) == 8)
+    hipLaunchKernelGGL(escoin_sconv_wgrad_sum_f64_kernel, grid, dim3(256), 0, c.stream, c.slab_w, c.slab_b, c.wpos, weight_diff,
+                       bias_diff, nnz, M, c.chunks);
+  else
+    hipLaunchKernelGGL(escoin_sconv_wgrad_sum_kernel, grid, dim3(256), 0, c.stream, c.slab_w, c.slab_b, c.wpos, weight_diff,
+                       bias_diff, nnz, M, c.chunks);
+  ESCOIN_HIP_TRY(hipGetLastError());
   return ESCOIN_OK;
 }
 
+// Stage 2 of the staged and the MFMA kernel, 16 lanes per item.
+static int launch_tree_sum(const escoin_plan *p, const WgradCall<float> &c, float *weight_diff, float *bias_diff) {
+  const int nnz = (int)p->bwd->nnz, M = p->g.d.M;
+  const long items = (weight_diff ? nnz : 0) + (bias_diff ? M : 0);
+  if (items == 0) return ESCOIN_OK;
+  hipLaunchKernelGGL(escoin_sconv_wgrad_tree_sum_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, c.stream, c.slab_w,
+                     c.slab_b, c.wpos, weight_diff, bias_diff, nnz, M, c.chunks);
+  ESCOIN_HIP_TRY(hipGetLastError());
+  return ESCOIN_OK;
+}
+
+template <typename T>
+static int wgrad_entry(const escoin_plan *p, const WgradCall<T> &c) {
+  const int rc = launch_partial<T>(p, c, c.weight_diff != nullptr, c.bias_diff != nullptr);
+  return rc != ESCOIN_OK ? rc : launch_sum<T>(p, c, c.weight_diff, c.bias_diff);
+}
+
+static int wgrad_staged(const escoin_plan *p, const WgradCall<float> &c) {
+  const Geometry &g = p->g;
+  const escoin_conv_desc &d = g.d;
+  const BwdState *s = p->bwd.get();
+  const StagedWgrad &st = s->stg;
+  StagedArgs sa;
+  sa.bottom = c.bottom; sa.top_diff = c.top_diff; sa.top = c.top;
+  sa.blk = st.blk.get<int>(); sa.off = st.off.get<int>();
+  sa.slab_w = c.slab_w; sa.slab_b = c.slab_b;
+  sa.total = (long)c.n_images * g.OH * g.OW; sa.nnz = (int)s->nnz; sa.n_images = c.n_images;
+  sa.C = d.C; sa.H = d.H; sa.W = d.W; sa.M = d.M; sa.OH = g.OH; sa.OW = g.OW;
+  sa.pad_h = d.pad_h; sa.pad_w = d.pad_w; sa.span_h = d.dil_h * (d.KH - 1);
+  sa.Cg = g.Cg; sa.Mg = g.Mg; sa.Hp = d.H + 2 * d.pad_h; sa.Wp = d.W + 2 * d.pad_w;
+  sa.icb = st.icb; sa.nblk = st.nblk; sa.rows_max = st.rows; sa.cs = st.rows * sa.Wp;
+  sa.osplit = st.osplit; sa.mper = (g.Mg + st.osplit - 1) / st.osplit;
+  sa.want_w = c.weight_diff != nullptr; sa.want_b = c.bias_diff != nullptr;
+  sa.inv_opix = 1.0f / (float)(g.OH * g.OW); sa.inv_ow = 1.0f / (float)g.OW;
+  sa.inv_wp = 1.0f / (float)sa.Wp; sa.inv_hp = 1.0f / (float)sa.Hp;
+  const dim3 grid(c.chunks, d.group * st.osplit, sa.want_w ? st.nblk : 1), block(64 * kStgWaves);
+  const size_t lds = sa.want_w ? st.lds_bytes : 0;
+  const int rc = launch_relu_pair(d.fuse_relu, escoin_sconv_wgrad_staged_kernel<true>, escoin_sconv_wgrad_staged_kernel<false>, grid, block, lds, c.stream, sa);
+  return rc != ESCOIN_OK ? rc : launch_tree_sum(p, c, c.weight_diff, c.bias_diff);
+}
+
+// weights: the MFMA kernel's partials, then the tree sum; bias: the entry kernel's bias-only stage 1 and its serial
+// stage 2 -- the entry kernel's bias bits
+static int wgrad_mfma(const escoin_plan *p, const WgradCall<float> &c) {
+  const BwdState *s = p->bwd.get();
+  int rc = ESCOIN_OK;
+  if (c.weight_diff) {
+    rc = launch_wgrad_mfma(p, s->wgm, s->nnz, c.bottom, c.top, c.top_diff, c.slab_w, c.n_images, c.chunks, c.stream);
+    if (rc == ESCOIN_OK) rc = launch_tree_sum(p, c, c.weight_diff, nullptr);
+  }
+  if (rc == ESCOIN_OK && c.bias_diff) {
+    rc = launch_partial<float>(p, c, false, true);
+    if (rc == ESCOIN_OK) rc = launch_sum<float>(p, c, nullptr, c.bias_diff);
+  }
+  return rc;
+}
+
+template <typename T>
+static int weight_gradient(escoin_plan *p, const T *bottom, const T *top, const T *top_diff, T *weight_diff, T *bias_diff,
+                           int n_images, hipStream_t stream, bool compact) {
+  BwdState *s = p->bwd.get();
+  const long total = (long)n_images * p->g.OH * p->g.OW;
+  T *slab_w = s->slab.get<T>();
+  const WgradCall<T> c{bottom, top, top_diff, weight_diff, bias_diff, slab_w, slab_w + (size_t)s->chunks_max * (size_t)s->nnz,
+                       compact ? nullptr : s->wpos.get<int>(), n_images, (int)((total + kChunkPixels - 1) / kChunkPixels), stream};
+  s->last_chunks = c.chunks;
+  s->last_wgrad = s->wgrad;
+  if constexpr (sizeof(T) == 4) {   // (a double plan's weight gradient is the entry kernel's: bwd_choice)
+    if (s->wgrad == ESCOIN_WGRAD_STAGED) return wgrad_staged(p, c);
+    if (s->wgrad == ESCOIN_WGRAD_MFMA) return wgrad_mfma(p, c);
+  }
+  return wgrad_entry<T>(p, c);
+}
+
+// The driver: the checks, the state where this alignment has none yet, then the two gradients.  With the state built a
+// call allocates nothing and synchronises nothing.
 template <typename T>
 static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *top_diff, T *bottom_diff,
                         T *weight_diff, T *bias_diff, int n_images, void *stream_v, bool compact) {
@@ -622,168 +783,19 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
   if (p->is_f64 != (sizeof(T) == 8))
     return fail(ESCOIN_ESTATE, p->is_f64 ? "backward: the plan holds double weights (use the _f64 entry point)"
                                          : "backward_f64: the plan holds float weights");
-  {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
-      return fail(ESCOIN_ESTATE, "backward: the current device is not the device the plan was aligned on");
-  }
-  const Geometry &g = p->g;
-  const escoin_conv_desc &d = g.d;
+  if (const int rc = check_plan_device(p, "backward")) return rc;
   if (!top_diff) return fail(ESCOIN_EINVAL, "backward: top_diff is required");
-  if (d.fuse_relu && !top) return fail(ESCOIN_EINVAL, "backward: a fuse_relu plan needs the forward's top");
+  if (p->g.d.fuse_relu && !top) return fail(ESCOIN_EINVAL, "backward: a fuse_relu plan needs the forward's top");
   if (weight_diff && !bottom) return fail(ESCOIN_EINVAL, "backward: the weight gradient needs bottom");
-  if (n_images < 0 || n_images > d.N) return fail(ESCOIN_EINVAL, "n_images outside [0, desc.N]");
+  if (const int rc = check_n_images(p, n_images)) return rc;
   hipStream_t stream = (hipStream_t)stream_v;
-  if (!p->bwd) {
-    const int rc = bwd_build<T>(p, stream);
-    if (rc != ESCOIN_OK) {
-      p->bwd.reset();
-      return rc;
-    }
-  }
-  BwdState *s = p->bwd.get();
+  if (const int rc = ensure_state<T>(p, stream)) return rc;
   if (n_images == 0) return ESCOIN_OK;
-  const bool relu = d.fuse_relu != 0;
   if (bottom_diff) {
-    if (s->s2d_inner) {
-      // option "s2d": dX' = the inner plan's data gradient of top_diff (the ReLU mask is its own), then depth-to-space
-      if constexpr (sizeof(T) == 4) {
-        S2dState *sd = p->s2d_state.get();
-        int rc = escoin_backward(sd->inner.plan.get(), nullptr, top, top_diff, sd->x.get<float>(), nullptr, nullptr, n_images, stream);
-        if (rc == ESCOIN_OK) rc = g_s2d_hooks.unpack(p, sd->x.get<const float>(), bottom_diff, n_images, stream);
-        if (rc != ESCOIN_OK) return rc;
-      }
-    } else if (s->transposed.plan) {
-      const float *src = reinterpret_cast<const float *>(top_diff);
-      if (relu) {
-        const size_t count = (size_t)n_images * d.M * g.OH * g.OW;
-        const unsigned blocks = (unsigned)std::min<size_t>((count + 255) / 256, 8192);
-        hipLaunchKernelGGL(escoin_sconv_bwd_relu_mask_kernel, dim3(blocks), dim3(256), 0, stream,
-                           reinterpret_cast<const float *>(top_diff), reinterpret_cast<const float *>(top),
-                           s->g.get<float>(), count);
-        ESCOIN_HIP_TRY(hipGetLastError());
-        src = s->g.get<const float>();
-      }
-      const int rc = escoin_forward(s->transposed.plan.get(), src, nullptr, reinterpret_cast<float *>(bottom_diff), n_images, stream);
-      if (rc != ESCOIN_OK) return rc;
-    } else if (s->data_kernel == ESCOIN_BWD_MFMA) {
-      if constexpr (sizeof(T) == 4) {
-        const int rc = launch_dgrad_mfma(p, s, top, top_diff, bottom_diff, n_images, stream);
-        if (rc != ESCOIN_OK) return rc;
-      }
-    } else {
-      BwdDataArgs<T> a;
-      a.top_diff = top_diff; a.top = top; a.bottom_diff = bottom_diff;
-      a.trow = s->trow.get<int>(); a.ttap = s->ttap.get<int>(); a.tval = s->tval.get<T>();
-      a.C = d.C; a.H = d.H; a.W = d.W; a.M = d.M; a.OH = g.OH; a.OW = g.OW;
-      a.pad_h = d.pad_h; a.pad_w = d.pad_w; a.stride_h = d.stride_h; a.stride_w = d.stride_w;
-      a.dil_h = d.dil_h; a.dil_w = d.dil_w; a.Cg = g.Cg; a.Mg = g.Mg;
-      const dim3 grid((d.H * d.W + 63) / 64, (d.C + kBwdWaves - 1) / kBwdWaves, n_images), block(64, kBwdWaves);
-      if constexpr (sizeof(T) == 8) {
-        if (relu) hipLaunchKernelGGL(escoin_sconv_bwd_data_f64_kernel<true>, grid, block, 0, stream, a);
-        else hipLaunchKernelGGL(escoin_sconv_bwd_data_f64_kernel<false>, grid, block, 0, stream, a);
-      } else {
-        if (relu) hipLaunchKernelGGL(escoin_sconv_bwd_data_kernel<true>, grid, block, 0, stream, a);
-        else hipLaunchKernelGGL(escoin_sconv_bwd_data_kernel<false>, grid, block, 0, stream, a);
-      }
-      ESCOIN_HIP_TRY(hipGetLastError());
-    }
+    const int rc = data_gradient<T>(p, top, top_diff, bottom_diff, n_images, stream);
+    if (rc != ESCOIN_OK) return rc;
   }
-  if (weight_diff || bias_diff) {
-    const long total = (long)n_images * g.OH * g.OW;
-    const int chunks = (int)((total + kChunkPixels - 1) / kChunkPixels);
-    s->last_chunks = chunks;
-    T *slab_w = s->slab.get<T>();
-    T *slab_b = slab_w + (size_t)s->chunks_max * (size_t)s->nnz;
-    WgradArgs<T> a;
-    a.bottom = bottom; a.top_diff = top_diff; a.top = top;
-    a.rowptr = p->gen.rowptr.get<int>(); a.taps = p->gen.taps.get<int>();
-    a.slab_w = slab_w; a.slab_b = slab_b;
-    a.total = total; a.nnz = (int)s->nnz;
-    a.C = d.C; a.H = d.H; a.W = d.W; a.M = d.M; a.OH = g.OH; a.OW = g.OW;
-    a.pad_h = d.pad_h; a.pad_w = d.pad_w; a.stride_h = d.stride_h; a.stride_w = d.stride_w;
-    a.dil_h = d.dil_h; a.dil_w = d.dil_w; a.Cg = g.Cg; a.Mg = g.Mg;
-    a.want_w = weight_diff != nullptr;
-    a.want_b = bias_diff != nullptr;
-    // compact output (escoin_backward_values): stage 2 writes entry e to weight_diff[e]
-    const int *wpos = compact ? nullptr : s->wpos.get<int>();
-    s->last_wgrad = s->wgrad;
-    if constexpr (sizeof(T) == 4) {
-      if (s->wgrad == ESCOIN_WGRAD_STAGED) {
-        StagedArgs sa;
-        sa.bottom = bottom; sa.top_diff = top_diff; sa.top = top;
-        sa.blk = s->stg_blk.get<int>(); sa.off = s->stg_off.get<int>();
-        sa.slab_w = slab_w; sa.slab_b = slab_b;
-        sa.total = total; sa.nnz = (int)s->nnz; sa.n_images = n_images;
-        sa.C = d.C; sa.H = d.H; sa.W = d.W; sa.M = d.M; sa.OH = g.OH; sa.OW = g.OW;
-        sa.pad_h = d.pad_h; sa.pad_w = d.pad_w; sa.span_h = d.dil_h * (d.KH - 1);
-        sa.Cg = g.Cg; sa.Mg = g.Mg; sa.Hp = d.H + 2 * d.pad_h; sa.Wp = d.W + 2 * d.pad_w;
-        sa.icb = s->stg_icb; sa.nblk = s->stg_nblk; sa.rows_max = s->stg_rows; sa.cs = s->stg_rows * sa.Wp;
-        sa.osplit = s->stg_osplit; sa.mper = (g.Mg + s->stg_osplit - 1) / s->stg_osplit;
-        sa.want_w = a.want_w; sa.want_b = a.want_b;
-        sa.inv_opix = 1.0f / (float)(g.OH * g.OW); sa.inv_ow = 1.0f / (float)g.OW;
-        sa.inv_wp = 1.0f / (float)sa.Wp; sa.inv_hp = 1.0f / (float)sa.Hp;
-        const dim3 sgrid(chunks, d.group * s->stg_osplit, a.want_w ? s->stg_nblk : 1), sblock(64 * kStgWaves);
-        const size_t lds = a.want_w ? s->stg_lds_bytes : 0;
-        if (relu) hipLaunchKernelGGL(escoin_sconv_wgrad_staged_kernel<true>, sgrid, sblock, lds, stream, sa);
-        else hipLaunchKernelGGL(escoin_sconv_wgrad_staged_kernel<false>, sgrid, sblock, lds, stream, sa);
-        ESCOIN_HIP_TRY(hipGetLastError());
-        const long items = (weight_diff ? s->nnz : 0) + (bias_diff ? d.M : 0);
-        if (items > 0) {
-          hipLaunchKernelGGL(escoin_sconv_wgrad_tree_sum_kernel, dim3((unsigned)((items + 15) / 16)), dim3(256), 0, stream,
-                             slab_w, slab_b, wpos, weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
-          ESCOIN_HIP_TRY(hipGetLastError());
-        }
-        return ESCOIN_OK;
-      }
-      if (s->wgrad == ESCOIN_WGRAD_MFMA) {
-        // weights: the MFMA kernel's partials, then the tree sum; bias: the entry kernel's bias-only stage 1 and its
-        // serial stage 2 -- the entry kernel's bias bits
-        if (weight_diff) {
-          const int rc = launch_wgrad_mfma(p, s, bottom, top, top_diff, slab_w, n_images, chunks, stream);
-          if (rc != ESCOIN_OK) return rc;
-          if (s->nnz > 0) {
-            hipLaunchKernelGGL(escoin_sconv_wgrad_tree_sum_kernel, dim3((unsigned)((s->nnz + 15) / 16)), dim3(256), 0, stream,
-                               slab_w, slab_b, wpos, weight_diff, (float *)nullptr, (int)s->nnz, d.M, chunks);
-            ESCOIN_HIP_TRY(hipGetLastError());
-          }
-        }
-        if (bias_diff) {
-          if (d.M > 65535) return fail(ESCOIN_EINVAL, "backward: more than 65535 output channels");
-          a.want_w = 0;
-          const dim3 bgrid(chunks, d.M), bblock(64 * kBwdWaves);
-          if (relu) hipLaunchKernelGGL(escoin_sconv_wgrad_partial_kernel<true>, bgrid, bblock, 0, stream, a);
-          else hipLaunchKernelGGL(escoin_sconv_wgrad_partial_kernel<false>, bgrid, bblock, 0, stream, a);
-          ESCOIN_HIP_TRY(hipGetLastError());
-          hipLaunchKernelGGL(escoin_sconv_wgrad_sum_kernel, dim3((unsigned)((d.M + 255) / 256)), dim3(256), 0, stream, slab_w,
-                             slab_b, wpos, (float *)nullptr, bias_diff, (int)s->nnz, d.M, chunks);
-          ESCOIN_HIP_TRY(hipGetLastError());
-        }
-        return ESCOIN_OK;
-      }
-    }
-    const dim3 grid(chunks, d.M), block(64 * kBwdWaves);
-    if (d.M > 65535) return fail(ESCOIN_EINVAL, "backward: more than 65535 output channels");
-    if constexpr (sizeof(T) == 8) {
-      if (relu) hipLaunchKernelGGL(escoin_sconv_wgrad_partial_f64_kernel<true>, grid, block, 0, stream, a);
-      else hipLaunchKernelGGL(escoin_sconv_wgrad_partial_f64_kernel<false>, grid, block, 0, stream, a);
-    } else {
-      if (relu) hipLaunchKernelGGL(escoin_sconv_wgrad_partial_kernel<true>, grid, block, 0, stream, a);
-      else hipLaunchKernelGGL(escoin_sconv_wgrad_partial_kernel<false>, grid, block, 0, stream, a);
-    }
-    ESCOIN_HIP_TRY(hipGetLastError());
-    const long lanes = (weight_diff ? s->nnz : 0) + (bias_diff ? d.M : 0);
-    if (lanes > 0) {
-      const dim3 sgrid((unsigned)((lanes + 255) / 256));
-      if constexpr (sizeof(T) == 8)
-        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_f64_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, wpos,
-                           weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
-      else
-        hipLaunchKernelGGL(escoin_sconv_wgrad_sum_kernel, sgrid, dim3(256), 0, stream, slab_w, slab_b, wpos,
-                           weight_diff, bias_diff, (int)s->nnz, d.M, chunks);
-      ESCOIN_HIP_TRY(hipGetLastError());
-    }
-  }
+  if (weight_diff || bias_diff) return weight_gradient<T>(p, bottom, top, top_diff, weight_diff, bias_diff, n_images, stream, compact);
   return ESCOIN_OK;
 }
 

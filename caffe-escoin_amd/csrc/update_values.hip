@@ -7,7 +7,8 @@
 // (for_each_copy) finds them: a plan, its backward state's copy and its derived plans, recursively.
 //   a plan's forward side       gen.vals (the generic kernel's and the LOWERED_SPARSE comparator's values), dense.w (the MFMA
 //                               kernel's padded matrix), the generated code / the weight stream of a tiled plan's sparse groups
-//   its backward state's copy   one of: the transposed plan (a derived plan), tval through tsrc, dgm_mat through dgm_pos
+//   its backward state's copy   by BwdState::data one of: the transposed plan (a derived plan), gather.tval through
+//                               gather.tsrc, dgm.mat through dgm.pos -- or none (the inner plan's state holds it)
 //   its derived plans           (escoin_plan.h DerivedPlan: the transposed plan, the inner plan of option "s2d") plans like
 //                               any other, whose copies are reached through the maps on the way composed (compose_maps)
 // The first update on an alignment builds that list (UpdState); later updates launch one kernel and nothing else.
@@ -143,21 +144,24 @@ int for_each_copy(Plan *q, const std::vector<int> *outer, bool with_maps, OnPlan
     if ((rc = for_each_copy<Plan>(sd->inner.plan.get(), map, with_maps, on_plan, on_array)) != ESCOIN_OK) return rc;
   }
   const BwdState *s = q->bwd.get();
-  // (s2d_inner: the data gradient is the inner plan's, whose backward state the walk has just visited; this state holds
-  //  no copy -- no transposed plan, tsrc and dgm_pos empty -- and its data_kernel names the inner plan's kernel)
-  if (!s || s->s2d_inner) return ESCOIN_OK;
-  if (s->transposed.plan) {
-    if (!through(s->transposed.src, &map)) return mismatch("the backward state");
-    return for_each_copy<Plan>(s->transposed.plan.get(), map, with_maps, on_plan, on_array);
+  if (!s) return ESCOIN_OK;
+  switch (s->data) {
+    case kBwdInner:   // the data gradient is the inner plan's, whose backward state the walk has just visited: no copy here
+      break;
+    case kBwdTransposed:
+      if (!through(s->transposed.src, &map)) return mismatch("the backward state");
+      return for_each_copy<Plan>(s->transposed.plan.get(), map, with_maps, on_plan, on_array);
+    case kBwdMfma:
+      if (!with_maps) break;
+      // the phase matrices, always float: element pos[e] holds the value of q's entry e (csr_tables.h dgrad_mfma_tables)
+      if ((long)s->dgm.pos.size() != nnz) return mismatch("the backward state");
+      return on_array(s->dgm.mat, sizeof(float), s->dgm.pos.data(), outer ? outer->data() : nullptr, nnz);
+    case kBwdGather:
+      if (!with_maps) break;
+      if (!through(s->gather.tsrc, &map)) return mismatch("the backward state");
+      return on_array(s->gather.tval, q->is_f64 ? sizeof(double) : sizeof(float), nullptr, map->data(), nnz);
   }
-  if (!with_maps) return ESCOIN_OK;
-  if (s->data_kernel == ESCOIN_BWD_MFMA) {
-    // the phase matrices, always float: element dgm_pos[e] holds the value of q's entry e (csr_tables.h dgrad_mfma_tables)
-    if ((long)s->dgm_pos.size() != nnz) return mismatch("the backward state");
-    return on_array(s->dgm_mat, sizeof(float), s->dgm_pos.data(), outer ? outer->data() : nullptr, nnz);
-  }
-  if (!through(s->tsrc, &map)) return mismatch("the backward state");
-  return on_array(s->tval, q->is_f64 ? sizeof(double) : sizeof(float), nullptr, map->data(), nnz);
+  return ESCOIN_OK;
 }
 
 const auto skip_arrays = [](const DeviceBuffer &, size_t, const int *, const int *, long) { return ESCOIN_OK; };
@@ -282,12 +286,7 @@ int check_updatable(const escoin_plan *p, const char *name) {
   if (!p->aligned) return fail(ESCOIN_ESTATE, std::string(name) + " called before weight_align / set_csr");
   if (p->is_f64 != (sizeof(T) == 8))
     return fail(ESCOIN_ESTATE, std::string(name) + (p->is_f64 ? ": the plan holds double weights (use the _f64 entry point)" : "_f64: the plan holds float weights"));
-  {
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess || dev != p->device)
-      return fail(ESCOIN_ESTATE, std::string(name) + ": the current device is not the device the plan was aligned on");
-  }
-  return ESCOIN_OK;
+  return check_plan_device(p, name);
 }
 
 // Whether the in-place path exists for p: in_place_ok of every plan copy of the walk.

@@ -55,37 +55,35 @@ escoin_sconv_wgrad_mfma_kernel(WgmArgs a) {
   }
 }
 
-int wgm_build(escoin_plan *p, BwdState *s, hipStream_t stream) {
-  WgmPlan wp;
-  if (!wgm_plan(p->g, p->is_f64, &wp)) return fail(ESCOIN_EINVAL, "wgrad_kernel: the MFMA weight-gradient kernel does not serve this plan");
+int wgm_build(const escoin_plan *p, const WgmPlan &wp, WgmState *w, hipStream_t stream) {
   const WgmTables t = wgrad_mfma_tables(csr_view(p), wp.tile_m, wp.tile_k);
-  s->wgm_mtiles = wp.mtiles;
-  s->wgm_ktiles = wp.ktiles;
-  s->wgm_lds_bytes = wp.lds_bytes;
-  ESCOIN_HIP_TRY(s->wgm_ent.upload(t.ent, stream));
-  ESCOIN_HIP_TRY(s->wgm_cnt.upload(t.tile_cnt, stream));
-  ESCOIN_HIP_TRY(s->wgm_ktab.upload(t.ktab, stream));
+  w->mtiles = wp.mtiles;
+  w->ktiles = wp.ktiles;
+  w->lds_bytes = wp.lds_bytes;
+  ESCOIN_HIP_TRY(w->ent.upload(t.ent, stream));
+  ESCOIN_HIP_TRY(w->cnt.upload(t.tile_cnt, stream));
+  ESCOIN_HIP_TRY(w->ktab.upload(t.ktab, stream));
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));   // host vectors die at scope exit
   return ESCOIN_OK;
 }
 
-int launch_wgrad_mfma(const escoin_plan *p, const BwdState *s, const float *bottom, const float *top,
+int launch_wgrad_mfma(const escoin_plan *p, const WgmState &w, long nnz, const float *bottom, const float *top,
                       const float *top_diff, float *slab_w, int n_images, int chunks, hipStream_t stream) {
   const Geometry &g = p->g;
   const escoin_conv_desc &d = g.d;
-  if (s->nnz == 0 || chunks == 0) return ESCOIN_OK;       // nothing to produce: no launch
-  if (!s->wgm_ent.get<void>() || !s->wgm_cnt.get<void>() || !s->wgm_ktab.get<void>())
+  if (nnz == 0 || chunks == 0) return ESCOIN_OK;       // nothing to produce: no launch
+  if (!w.ent.get<void>() || !w.cnt.get<void>() || !w.ktab.get<void>())
     return fail(ESCOIN_ESTATE, "MFMA weight-gradient kernel: the backward state has no tables for it");
   WgmArgs a;
-  a.in.bottom = bottom; a.in.top_diff = top_diff; a.in.top = top; a.in.ktab = s->wgm_ktab.get<const int4>();
-  a.ent = s->wgm_ent.get<const int>(); a.tile_cnt = s->wgm_cnt.get<const int>();
+  a.in.bottom = bottom; a.in.top_diff = top_diff; a.in.top = top; a.in.ktab = w.ktab.get<const int4>();
+  a.ent = w.ent.get<const int>(); a.tile_cnt = w.cnt.get<const int>();
   a.slab_w = slab_w;
   a.in.total = (long)n_images * g.OH * g.OW;
-  a.nnz = (int)s->nnz;
+  a.nnz = (int)nnz;
   a.in.C = d.C; a.in.H = d.H; a.in.W = d.W; a.in.M = d.M; a.in.OH = g.OH; a.in.OW = g.OW;
   a.in.pad_h = d.pad_h; a.in.pad_w = d.pad_w; a.in.stride_h = d.stride_h; a.in.stride_w = d.stride_w;
-  a.in.Cg = g.Cg; a.in.Mg = g.Mg; a.Kd = g.kdim; a.mtiles = s->wgm_mtiles; a.ktiles = s->wgm_ktiles;
-  const dim3 grid((unsigned)chunks, (unsigned)(d.group * s->wgm_mtiles), (unsigned)s->wgm_ktiles), block(kWgmThreads);
+  a.in.Cg = g.Cg; a.in.Mg = g.Mg; a.Kd = g.kdim; a.mtiles = w.mtiles; a.ktiles = w.ktiles;
+  const dim3 grid((unsigned)chunks, (unsigned)(d.group * w.mtiles), (unsigned)w.ktiles), block(kWgmThreads);
   if (d.fuse_relu) hipLaunchKernelGGL(escoin_sconv_wgrad_mfma_kernel<true>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(escoin_sconv_wgrad_mfma_kernel<false>, grid, block, 0, stream, a);
   ESCOIN_HIP_TRY(hipGetLastError());

@@ -45,13 +45,11 @@ static Result run(const Geometry &g, const SplitOptions &o, int wgrad_kernel, bo
     nnz_per_group[grp] = (long)colidx[grp].size();
     nnz_all += nnz_per_group[grp];
   }
-  // the backward's weight-gradient kernel (sconv_backward.hip bwd_build)
-  StgPlan sp;
-  if (stg_plan(g, is_f64, 0, n_cu, &sp) &&
-      (wgrad_kernel == ESCOIN_WGRAD_STAGED || (wgrad_kernel == ESCOIN_WGRAD_AUTO && stg_auto_prefers(g, nnz_all, sp, n_cu)))) {
-    r.wgrad = ESCOIN_WGRAD_STAGED;
-    r.wgrad_lds = (long)(sizeof(float) * (size_t)sp.icb * (size_t)sp.cs);
-  }
+  // the backward's weight-gradient kernel, as sconv_backward.hip bwd_build asks for it (stat "wgrad_lds_bytes")
+  const BwdChoice bc = bwd_choice(g, is_f64, nnz_all, BwdOptions{ESCOIN_KERNEL_AUTO, wgrad_kernel, 0, false}, n_cu);
+  if (bc.rc != ESCOIN_OK) { r.error = bc.error; return r; }
+  r.wgrad = bc.wgrad;
+  r.wgrad_lds = bc.wgrad == ESCOIN_WGRAD_STAGED ? (long)bc.stg.lds_bytes : bc.wgrad == ESCOIN_WGRAD_MFMA ? (long)bc.wgm.lds_bytes : 0;
   if (is_f64) return r;     // a double plan runs the generic kernel
   const GroupSplit split = group_split(dense_groups(g, nnz_per_group, o, n_cu));
   if (split.use_dense) {
