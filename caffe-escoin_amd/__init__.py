@@ -61,6 +61,9 @@ API_SYMBOLS = [
     "escoin_dense_wgrad", "escoin_dense_wgrad_f64", "escoin_dense_wgrad_cpu", "escoin_dense_wgrad_cpu_f64",
     # Space-to-depth (option "s2d")
     "escoin_plan_s2d_pack",
+    # Space-to-batch (option "s2b")
+    "escoin_plan_s2b_pack",
+    "escoin_plan_s2b_unpack",
 ]
 SOLVER_SGD, SOLVER_NESTEROV, SOLVER_ADAM = 0, 1, 2
 REG_NONE, REG_L2, REG_L1 = 0, 1, 2
@@ -239,6 +242,10 @@ def lib():
     L.escoin_plan_tiling_info.argtypes = [vp]
     L.escoin_plan_s2d_pack.restype = ip
     L.escoin_plan_s2d_pack.argtypes = [vp, vp, ip, vp]
+    L.escoin_plan_s2b_pack.restype = ip
+    L.escoin_plan_s2b_pack.argtypes = [vp, vp, ip, vp]
+    L.escoin_plan_s2b_unpack.restype = ip
+    L.escoin_plan_s2b_unpack.argtypes = [vp, vp, ip, vp]
     L.escoin_forward.restype = ip
     L.escoin_forward.argtypes = [vp, vp, vp, vp, ip, vp]
     L.escoin_plan_export_aligned.restype = ip
@@ -758,6 +765,26 @@ class Plan(object):
         assert tuple(bottom.shape[1:]) == (d.C, d.H, d.W), "bottom shape mismatch"
         stream = C.c_void_p(torch.cuda.current_stream(bottom.device).cuda_stream)
         check(lib().escoin_plan_s2d_pack(self._h, C.c_void_p(bottom.data_ptr()), int(bottom.shape[0]), stream), "escoin_plan_s2d_pack")
+
+    def s2b_pack(self, bottom):
+        """The space-to-batch rearrangement of an "s2b" plan alone, into the plan's X' scratch, on torch's current stream
+        (what forward() runs before the inner plan; for measuring it)."""
+        import torch
+        d = self.desc
+        assert bottom.is_cuda and bottom.dtype == torch.float32 and bottom.is_contiguous()
+        assert tuple(bottom.shape[1:]) == (d.C, d.H, d.W), "bottom shape mismatch"
+        stream = C.c_void_p(torch.cuda.current_stream(bottom.device).cuda_stream)
+        check(lib().escoin_plan_s2b_pack(self._h, C.c_void_p(bottom.data_ptr()), int(bottom.shape[0]), stream), "escoin_plan_s2b_pack")
+
+    def s2b_unpack(self, top):
+        """The batch-to-space rearrangement of an "s2b" plan alone, from the plan's T' scratch (whatever it holds) into `top`
+        (N x M x OH x OW), on torch's current stream (what forward() runs after the inner plan; for measuring it)."""
+        import torch
+        d = self.desc
+        assert top.is_cuda and top.dtype == torch.float32 and top.is_contiguous()
+        assert tuple(top.shape[1:]) == (d.M,) + tuple(self.out_hw), "top shape mismatch"
+        stream = C.c_void_p(torch.cuda.current_stream(top.device).cuda_stream)
+        check(lib().escoin_plan_s2b_unpack(self._h, C.c_void_p(top.data_ptr()), int(top.shape[0]), stream), "escoin_plan_s2b_unpack")
 
     def forward(self, bottom, bias=None, top=None):
         """Forward_gpu on torch CUDA tensors (float32, or float64 for a double plan), on torch's current stream."""

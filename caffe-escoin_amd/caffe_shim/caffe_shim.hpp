@@ -104,16 +104,20 @@ class Caffe {
   // (include/escoin.h option "s2d"); a layer the option does not serve, and CPU mode, run as without it
   static bool s2d() { return Get().s2d_; }
   static void set_s2d(bool on) { Get().s2d_ = on; }
+  // the same for dilated stride-1 layers via space-to-batch (include/escoin.h option "s2b")
+  static bool s2b() { return Get().s2b_; }
+  static void set_s2b(bool on) { Get().s2b_ = on; }
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
   int wgrad_kernel_;
   int backward_kernel_;
   bool s2d_;
+  bool s2b_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -422,6 +426,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_kernel", Caffe::wgrad_kernel()));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "backward_kernel", Caffe::backward_kernel()));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2d", Caffe::s2d() ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2b", Caffe::s2b() ? 1 : 0));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;

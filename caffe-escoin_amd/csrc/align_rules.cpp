@@ -592,7 +592,7 @@ BwdChoice bwd_choice(const Geometry &g, bool is_f64, long nnz, const BwdOptions 
   const bool transposable = bwd_transposable(g, is_f64);
   const bool forced = o.backward_kernel == ESCOIN_KERNEL_TILED || o.backward_kernel == ESCOIN_KERNEL_JIT ||
                       o.backward_kernel == ESCOIN_KERNEL_DENSE;
-  // option "s2d": GENERIC and BWD_MFMA keep the plan's own gather / MFMA kernel, the others go to the inner plan
+  // an inner plan (option "s2d" / "s2b"): GENERIC and BWD_MFMA keep the plan's own gather / MFMA kernel, the others go to the inner plan
   const bool inner = o.s2d && o.backward_kernel != ESCOIN_KERNEL_GENERIC && o.backward_kernel != ESCOIN_BWD_MFMA;
   if (forced && !transposable && !inner)
     return refuse("backward_kernel: this plan has no transposed forward plan (needs a float plan, stride 1, "
@@ -645,6 +645,36 @@ bool s2d_plan(const Geometry &g, bool is_f64, S2dPlan *sp) {
   if ((double)d.M * cg_in * in.KH * (double)in.KW >= two31) return false;
   in.C = d.C * p.PH * p.PW;
   p.x_floats = (long)x_floats;
+  *sp = p;
+  return true;
+}
+
+bool s2b_plan(const Geometry &g, bool is_f64, S2bPlan *sp) {
+  const escoin_conv_desc &d = g.d;
+  if (is_f64) return false;
+  if (d.stride_h != 1 || d.stride_w != 1) return false;
+  const long lim28 = 1L << 28;
+  if ((long)d.H + 2L * d.pad_h >= lim28 || (long)d.W + 2L * d.pad_w >= lim28 || d.dil_h >= lim28 || d.dil_w >= lim28) return false;
+  S2bPlan p;
+  p.eh = d.KH > 1 ? d.dil_h : 1;     // (a dilation on an axis with one tap is no dilation)
+  p.ew = d.KW > 1 ? d.dil_w : 1;
+  const long P = (long)p.eh * p.ew;
+  if (P <= 1 || (long)d.N * P > kS2bMaxInnerImages) return false;
+  escoin_conv_desc &in = p.inner;
+  in = d;
+  in.N = (int)(d.N * P);
+  in.H = (d.H + 2 * d.pad_h + p.eh - 1) / p.eh;
+  in.W = (d.W + 2 * d.pad_w + p.ew - 1) / p.ew;
+  in.pad_h = in.pad_w = 0;
+  in.dil_h = in.dil_w = 1;
+  in.fuse_relu = 0;                  // (the unpack kernel applies the outer plan's ReLU)
+  const int ohi = in.H - d.KH + 1, owi = in.W - d.KW + 1;      // = ceil(OH / eh), ceil(OW / ew)
+  const double two31 = 2147483648.0;
+  const double x_floats = (double)in.N * d.C * in.H * (double)in.W, t_floats = (double)in.N * d.M * ohi * (double)owi;
+  if (x_floats >= two31 || t_floats >= two31) return false;
+  if ((double)d.N * d.C * d.H * (double)d.W >= two31 || (double)d.N * d.M * g.OH * (double)g.OW >= two31) return false;
+  p.x_floats = (long)x_floats;
+  p.t_floats = (long)t_floats;
   *sp = p;
   return true;
 }

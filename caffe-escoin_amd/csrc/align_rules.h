@@ -220,9 +220,10 @@ bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp);
 // Whether the data gradient can run as a stride-1 forward of top_diff with the transposed, flipped weights: float plans,
 // stride 1, pad <= dilation * (kernel - 1), at most 32767 output channels per group (a plan's channel limit).
 bool bwd_transposable(const Geometry &g, bool is_f64);
-// The plan options the backward reads (escoin_plan_set_option), and s2d: option "s2d" serves the plan (it has an S2dState).
+// The plan options the backward reads (escoin_plan_set_option), and s2d: the plan has an inner plan (option "s2d" or
+// option "s2b" serves it: it has an S2dState or an S2bState).
 struct BwdOptions { int backward_kernel, wgrad_kernel, wgrad_channel_block; bool s2d; };
-// Who computes the data gradient: the inner plan of option "s2d" (AUTO, TILED, JIT and DENSE on such a plan; the inner
+// Who computes the data gradient: the inner plan of option "s2d" / "s2b" (AUTO, TILED, JIT and DENSE on such a plan; the inner
 // plan refuses what it cannot serve), the transposed forward plan, the gather kernel, the MFMA kernel of dgrad_mfma.hip.
 enum BwdDataPath { kBwdInner, kBwdTransposed, kBwdGather, kBwdMfma };
 // What the first backward on an alignment builds, or why it builds nothing: rc != ESCOIN_OK is a refusal with its message
@@ -271,6 +272,26 @@ struct S2dPlan {
 // 2^31 elements (the pack / unpack kernels' 32-bit offsets; every workgroup count is below them), whose padded extents
 // (H + 2 pad_h, W + 2 pad_w) stay below 2^28 and whose Cg' is a channel count a plan accepts (at most 32767).
 bool s2d_plan(const Geometry &g, bool is_f64, S2dPlan *sp);
+
+// ---- dilated layers on the stride-1 kernels via space-to-batch (s2b.hip, plan option "s2b") -------------------------
+// A dilated stride-1 convolution is eh x ew independent undilated convolutions: output pixel (oh, ow) reads only padded
+// input pixels of its own residue class modulo (eh, ew), eh = dil_h where KH > 1 (else 1), ew likewise (include/escoin.h
+// "Space-to-batch").  Each class is an IMAGE of the inner plan: n' = (n * eh + qh) * ew + qw, an H' x W' =
+// ceil((H + 2 pad_h) / eh) x ceil((W + 2 pad_w) / ew) image, pad 0, stride 1, dilation 1, no ReLU; the CSR is the outer one.
+struct S2bPlan {
+  int eh = 0, ew = 0;             // residue classes per axis; P = eh * ew inner images per outer image
+  escoin_conv_desc inner = {};    // the inner plan's descriptor (N' = N * P)
+  long x_floats = 0;              // N' * C * H' * W': the rearranged bottom X' (and its gradient dX')
+  long t_floats = 0;              // N' * M * OH' * OW': the inner top T' (and the rearranged top_diff G')
+};
+// The most inner images option "s2b" builds a plan for: the generic kernel's grid z and the backward's (bwd_choice refuses
+// N > 65535) are the image index.
+constexpr long kS2bMaxInnerImages = 65535;
+// Whether option "s2b" serves this plan, and the inner descriptor where it does: float plans with stride 1 in both axes
+// and P = eh * ew > 1, whose bottom, top, X' and T' each stay below 2^31 elements (the pack / unpack kernels' 32-bit
+// offsets; every row and workgroup count is below them), whose padded extents and dilations stay below 2^28 and whose
+// N * P is at most kS2bMaxInnerImages.
+bool s2b_plan(const Geometry &g, bool is_f64, S2bPlan *sp);
 
 }  // namespace escoin
 #endif  // ESCOIN_ALIGN_RULES_H_

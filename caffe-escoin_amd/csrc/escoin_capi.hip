@@ -19,6 +19,7 @@ namespace escoin {
 static thread_local std::string g_last_error;
 
 S2dHooks g_s2d_hooks = {nullptr, nullptr, nullptr};
+S2bHooks g_s2b_hooks = {nullptr, nullptr, nullptr, nullptr};
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 
@@ -91,6 +92,12 @@ DeviceBytes device_bytes(const escoin_plan *p) {
     b.fwd += sd->x.bytes() + in.fwd;
     b.bwd += in.bwd;
   }
+  if (const S2bState *sb = p->s2b_state.get()) {
+    // the X' / dX' and T' / G' scratches and the inner plan's own owners, as for "s2d"
+    const DeviceBytes in = device_bytes(sb->inner.plan.get());
+    b.fwd += sb->x.bytes() + sb->t.bytes() + in.fwd;
+    b.bwd += in.bwd;
+  }
   return b;
 }
 
@@ -98,7 +105,7 @@ long bwd_stat(const escoin_plan *p, const char *key) {
   const BwdState *s = p->bwd.get();
   if (!strcmp(key, "bwd_data_kernel")) {
     if (!s) return fail(ESCOIN_ESTATE, "bwd_data_kernel: no backward has run on this alignment");
-    if (s->data == kBwdInner) return bwd_stat(p->s2d_state->inner.plan.get(), key);
+    if (s->data == kBwdInner) return bwd_stat(p->inner_plan()->plan.get(), key);
     if (s->data == kBwdTransposed) return escoin_plan_stat(s->transposed.plan.get(), "kernel_choice");
     return s->data == kBwdMfma ? ESCOIN_BWD_MFMA : ESCOIN_KERNEL_GENERIC;
   }
@@ -145,6 +152,7 @@ static void free_device(escoin_plan *p) {
   p->dev_authoritative = false;
   p->bwd.reset();
   p->s2d_state.reset();
+  p->s2b_state.reset();
   p->gen = GenericArrays();
   tiled_release(p);
   p->col.reset();
@@ -164,7 +172,7 @@ static int upload_generic(escoin_plan *p, hipStream_t stream) {
 }
 
 int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, int kernel, int backward_kernel,
-                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out) {
+                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out, int tiling_batch) {
   escoin_plan *q = nullptr;
   int rc = escoin_plan_create(&desc, &q);
   out->plan.reset(q);
@@ -172,7 +180,7 @@ int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, i
   // what a derived plan inherits, and all of it ("body_variant", "stream_stores" and the "wgrad_*" options are not handed down)
   if ((rc = escoin_plan_set_option(q, "kernel", kernel)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "backward_kernel", backward_kernel)) != ESCOIN_OK) return rc;
-  if ((rc = escoin_plan_set_option(q, "tiling_batch", owner->tiling_batch)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "tiling_batch", tiling_batch < 0 ? owner->tiling_batch : tiling_batch)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "max_launch_bytes", (int)std::min<long>(owner->max_launch_bytes, 0x7fffffff))) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "dense_threshold_pct", owner->dense_threshold_pct)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "dense_gate", owner->dense_gate)) != ESCOIN_OK) return rc;
@@ -206,6 +214,38 @@ static int s2d_build(escoin_plan *p, const S2dPlan &sp, hipStream_t stream) {
   return ESCOIN_OK;
 }
 
+// Option "s2b" (include/escoin.h "Space-to-batch"): the inner undilated plan of N * P images with the plan's kernel options,
+// aligned on the plan's own CSR (the entry map is the identity), and the X' and T' scratches.  The plan itself keeps the
+// generic arrays alone, as under "s2d".
+static int s2b_build(escoin_plan *p, const S2bPlan &sp, hipStream_t stream) {
+  if (!g_s2b_hooks.pack || !g_s2b_hooks.unpack) return fail(ESCOIN_EINVAL, "option \"s2b\": this build does not carry the space-to-batch kernels");
+  p->s2b_state.reset(new S2bState());
+  S2bState *sb = p->s2b_state.get();
+  sb->sp = sp;
+  const int ibwd = p->bwd_kernel == ESCOIN_KERNEL_GENERIC || p->bwd_kernel == ESCOIN_BWD_MFMA ? ESCOIN_KERNEL_AUTO : p->bwd_kernel;
+  DerivedCsr csr;
+  for (int grp = 0; grp < p->g.d.group; ++grp) {
+    csr.rowptr.insert(csr.rowptr.end(), p->rowptr[grp].begin(), p->rowptr[grp].end());
+    csr.colidx.insert(csr.colidx.end(), p->colidx[grp].begin(), p->colidx[grp].end());
+    csr.nnz_g.push_back((int)p->colidx[grp].size());
+  }
+  csr.src.resize(csr.colidx.size());
+  for (size_t k = 0; k < csr.src.size(); ++k) csr.src[k] = (int)k;
+  // "tiling_batch" counts outer images: an outer image is P inner ones
+  const long tb = (long)p->tiling_batch * sp.eh * sp.ew;
+  if (tb > 0x7fffffffL) return fail(ESCOIN_EINVAL, "option \"s2b\": tiling_batch times the residue classes exceeds 2^31");
+  const int rc = build_derived_plan(p, sp.inner, p->kernel_choice, ibwd, std::move(csr), stream, &sb->inner, (int)tb);
+  if (rc != ESCOIN_OK) return rc;
+  ESCOIN_HIP_TRY(sb->x.alloc(sizeof(float) * (size_t)sp.x_floats));
+  ESCOIN_HIP_TRY(sb->t.alloc(sizeof(float) * (size_t)sp.t_floats));
+  p->n_dense_groups = 0; p->n_sparse_groups = p->g.d.group; p->use_dense = false;
+  p->dense_mask = 0; p->sparse_mask = ~0ull; p->small_rule = 0; p->import_fast = false;
+  p->kernel_name = std::string(g_s2b_hooks.pack_kernel_name) + " + " + escoin_plan_kernel_name(sb->inner.plan.get()) + " + " +
+                   g_s2b_hooks.unpack_kernel_name;
+  p->aligned = true;
+  return ESCOIN_OK;
+}
+
 // Uploads the CSR held in p->rowptr/colidx/values and builds the kernel-specific
 // streams.  Shared tail of escoin_weight_align and escoin_plan_set_csr.
 //   jit_blob: the generated-code section of a persisted aligned form (escoin_plan_import_aligned), tried
@@ -235,6 +275,13 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
   if (p->s2d && (p->conv_mode == ESCOIN_CONV_MODE_SCONV || p->conv_mode == ESCOIN_CONV_MODE_SCONV_PAR) && s2d_plan(g, false, &s2p)) {
     const int rc = s2d_build(p, s2p, stream);
     if (rc != ESCOIN_OK) p->s2d_state.reset();
+    return rc;
+  }
+  // option "s2b": likewise for a dilated stride-1 layer, through an undilated inner plan of N * P images
+  S2bPlan s2bp;
+  if (p->s2b && (p->conv_mode == ESCOIN_CONV_MODE_SCONV || p->conv_mode == ESCOIN_CONV_MODE_SCONV_PAR) && s2b_plan(g, false, &s2bp)) {
+    const int rc = s2b_build(p, s2bp, stream);
+    if (rc != ESCOIN_OK) p->s2b_state.reset();
     return rc;
   }
   // which conv groups go to the dense (fp32 MFMA) kernel (align_rules.h)
@@ -484,6 +531,12 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->s2d = value;
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "s2b")) {
+      if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "s2b must be 0 or 1");
+      if (p->aligned || p->host_aligned) return fail(ESCOIN_ESTATE, "s2b must be set before weight_align / weight_align_cpu / set_csr");
+      p->s2b = value;
+      return ESCOIN_OK;
+    }
     if (p->aligned && strcmp(key, "conv_mode") != 0 && strcmp(key, "cpu_channel_block") != 0 && strcmp(key, "cpu_images_per_job") != 0 &&
         strcmp(key, "wgrad_kernel") != 0)
       return fail(ESCOIN_ESTATE, "this option must be set before weight_align/set_csr");
@@ -555,10 +608,10 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
     } else if (!strcmp(key, "conv_mode")) {
       if (value < ESCOIN_CONV_MODE_LOWERED_GEMM || value > ESCOIN_CONV_MODE_SCONV_PAR)
         return fail(ESCOIN_EINVAL, "conv_mode must be one of Caffe::ConvMode's four values (0..3)");
-      // (an "s2d" plan also rebuilds between the lowered modes, which run on the original geometry, and SCONV / SCONV_PAR)
+      // (an "s2d" / "s2b" plan also rebuilds between the lowered modes, which run on the original geometry, and SCONV / SCONV_PAR)
       auto direct = [](int m) { return m == ESCOIN_CONV_MODE_SCONV || m == ESCOIN_CONV_MODE_SCONV_PAR; };
       const bool regroup = p->aligned && ((value == ESCOIN_CONV_MODE_LOWERED_GEMM) != (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_GEMM) ||
-                                          (p->s2d && !p->is_f64 && direct(value) != direct(p->conv_mode)));
+                                          ((p->s2d || p->s2b) && !p->is_f64 && direct(value) != direct(p->conv_mode)));
       p->conv_mode = value;
       // to or from LOWERED_GEMM on an aligned plan: the dense / sparse device structures are rebuilt
       // from the CSR the plan holds (the other three modes share theirs).  The plan is not aligned
@@ -722,13 +775,15 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!p || !key) return fail(ESCOIN_EINVAL, "null argument");
   if (!strcmp(key, "s2d")) return p->s2d_state ? 1 : 0;
   if (!strcmp(key, "s2d_scratch_bytes")) return p->s2d_state ? (long)p->s2d_state->x.bytes() : 0;
-  if (p->s2d_state) {
+  if (!strcmp(key, "s2b")) return p->s2b_state ? 1 : 0;
+  if (!strcmp(key, "s2b_scratch_bytes")) return p->s2b_state ? (long)(p->s2b_state->x.bytes() + p->s2b_state->t.bytes()) : 0;
+  if (p->inner_plan()) {
     // what describes the forward's kernel is the inner plan's
     static const char *const inner_keys[] = {"kernel_choice", "code_bytes", "code_direct", "small_launch_rule", "jit_rows", "jit_records",
                                              "deal_slowest_over_mean_x1000", "deal_worst_block_x1000", "lds_bytes", "body_variant",
                                              "workgroup_columns", "streamk_gave_up", "streamk"};
     for (const char *k : inner_keys)
-      if (!strcmp(key, k)) return escoin_plan_stat(p->s2d_state->inner.plan.get(), key);
+      if (!strcmp(key, k)) return escoin_plan_stat(p->inner_plan()->plan.get(), key);
   }
   if (!strcmp(key, "align_us")) return (long)(p->align_ms * 1e3);
   if (!strcmp(key, "code_bytes")) return (long)(p->tiled.enabled && p->tiled.jit ? p->tiled_dev.jit.code_bytes : 0);
@@ -815,7 +870,7 @@ const char *escoin_plan_kernel_name(const escoin_plan *p) {
 }
 
 const char *escoin_plan_tiling_info(const escoin_plan *p) {
-  if (p && p->aligned && p->s2d_state) return escoin_plan_tiling_info(p->s2d_state->inner.plan.get());
+  if (p && p->aligned && p->inner_plan()) return escoin_plan_tiling_info(p->inner_plan()->plan.get());
   return (p && p->aligned && p->tiled.enabled) ? p->tiled.info.c_str() : "";
 }
 
@@ -827,6 +882,28 @@ int escoin_plan_s2d_pack(escoin_plan *p, const float *bottom_dev, int n_images, 
     if (n_images == 0) return ESCOIN_OK;
     if (const int rc = check_plan_device(p, "s2d_pack")) return rc;
     return g_s2d_hooks.pack(p, bottom_dev, p->s2d_state->x.get<float>(), n_images, (hipStream_t)stream);
+  });
+}
+
+int escoin_plan_s2b_pack(escoin_plan *p, const float *bottom_dev, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    if (!p || !bottom_dev) return fail(ESCOIN_EINVAL, "null argument");
+    if (!p->aligned || !p->s2b_state) return fail(ESCOIN_ESTATE, "s2b_pack: option \"s2b\" is not active on this plan");
+    if (const int rc = check_n_images(p, n_images)) return rc;
+    if (n_images == 0) return ESCOIN_OK;
+    if (const int rc = check_plan_device(p, "s2b_pack")) return rc;
+    return g_s2b_hooks.pack(p, bottom_dev, nullptr, p->s2b_state->x.get<float>(), false, n_images, (hipStream_t)stream);
+  });
+}
+
+int escoin_plan_s2b_unpack(escoin_plan *p, float *top_dev, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    if (!p || !top_dev) return fail(ESCOIN_EINVAL, "null argument");
+    if (!p->aligned || !p->s2b_state) return fail(ESCOIN_ESTATE, "s2b_unpack: option \"s2b\" is not active on this plan");
+    if (const int rc = check_n_images(p, n_images)) return rc;
+    if (n_images == 0) return ESCOIN_OK;
+    if (const int rc = check_plan_device(p, "s2b_unpack")) return rc;
+    return g_s2b_hooks.unpack(p, p->s2b_state->t.get<const float>(), top_dev, true, p->g.d.fuse_relu != 0, n_images, (hipStream_t)stream);
   });
 }
 
@@ -851,6 +928,16 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
       const int rc = g_s2d_hooks.pack(p, bottom_dev, sd->x.get<float>(), n_images, s);
       if (rc != ESCOIN_OK) return rc;
       return escoin_forward(sd->inner.plan.get(), sd->x.get<const float>(), bias_dev, top_dev, n_images, stream);
+    }
+    // option "s2b": the padded bottom's residue classes become images of X', then the inner undilated plan (bias in its
+    // epilogue) into T', then the classes' tops interleaved into the top blob (ReLU there)
+    if (S2bState *sb = p->s2b_state.get()) {
+      const int P = sb->sp.eh * sb->sp.ew;
+      int rc = g_s2b_hooks.pack(p, bottom_dev, nullptr, sb->x.get<float>(), false, n_images, s);
+      if (rc != ESCOIN_OK) return rc;
+      rc = escoin_forward(sb->inner.plan.get(), sb->x.get<const float>(), bias_dev, sb->t.get<float>(), n_images * P, stream);
+      if (rc != ESCOIN_OK) return rc;
+      return g_s2b_hooks.unpack(p, sb->t.get<const float>(), top_dev, true, p->g.d.fuse_relu != 0, n_images, s);
     }
     // LOWERED_SPARSE lowers every group, whatever AUTO decided for the direct path
     if (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE && p->kernel_choice != ESCOIN_KERNEL_DENSE)

@@ -143,7 +143,7 @@ struct DgmState {
 
 struct BwdState {
   // who computes the data gradient, and with it where the state's copy of the values is: the inner plan's backward state
-  // (kBwdInner: option "s2d", the inner plan's backward followed by the unpack kernel -- this state then holds the weight
+  // (kBwdInner: option "s2d" or "s2b", the inner plan's backward followed by the unpack kernel -- this state then holds the weight
   // gradient's side only), `transposed`, gather.tval, dgm.mat
   BwdDataPath data = kBwdGather;
   DerivedPlan transposed;   // kBwdTransposed: the data gradient as a stride-1 forward of top_diff; plan null on the other paths
@@ -168,6 +168,14 @@ struct S2dState {
   S2dPlan sp;
   DerivedPlan inner;           // the stride-1 plan; its own backward state may hold a derived plan of this derived plan
   DeviceBuffer x;              // X' for the forward, dX' for the data gradient: sp.x_floats floats
+};
+
+// What upload() builds for a plan that option "s2b" serves (escoin_capi.hip; the rule: align_rules.h s2b_plan; the kernels:
+// s2b.hip); reset with the device side.  A plan has at most one of the two states: the options serve disjoint geometries.
+struct S2bState {
+  S2bPlan sp;
+  DerivedPlan inner;           // the undilated plan of N * P images on the outer CSR (src: the identity)
+  DeviceBuffer x, t;           // X' / dX': sp.x_floats floats; T' / G': sp.t_floats floats
 };
 
 // What the first escoin_dense_wgrad on a plan builds (dense_wgrad.hip).  A function of the descriptor, the device's CU
@@ -342,6 +350,13 @@ struct escoin_plan {
   // Space-to-depth (s2d.hip): option "s2d" and what upload() builds where it applies; reset with the device side
   int s2d = 0;
   std::unique_ptr<escoin::S2dState> s2d_state;
+  // Space-to-batch (s2b.hip): option "s2b" and what upload() builds where it applies; reset with the device side
+  int s2b = 0;
+  std::unique_ptr<escoin::S2bState> s2b_state;
+  // the inner plan of whichever of the two options serves this plan (null: neither does)
+  const escoin::DerivedPlan *inner_plan() const {
+    return s2d_state ? &s2d_state->inner : s2b_state ? &s2b_state->inner : nullptr;
+  }
 
   // Dense weight gradient (dense_wgrad.hip): option "dense_wgrad_splits" (0: the rule decides, n: at most n splits of the
   // pixel axis), the state the first escoin_dense_wgrad builds -- kept across aligns -- and stat "dwg_count" (device
@@ -381,9 +396,10 @@ long dwg_stat(const escoin_plan *p, const char *key);
 int realign_from_host_csr(escoin_plan *p, hipStream_t stream);
 // escoin_capi.hip (in the core for the reason S2dHooks gives below): a derived plan of the float plan `owner` into *out --
 // descriptor `desc`, the owner's options and these two kernel options, aligned on `csr` with the owner's values permuted
-// through csr.src, which becomes out->src.  A failure returns the failed call's code; the caller drops *out with its state.
+// through csr.src, which becomes out->src; tiling_batch >= 0 replaces the owner's "tiling_batch" (option "s2b": the inner
+// plan's images are the owner's times P).  A failure returns the failed call's code; the caller drops *out with its state.
 int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, int kernel, int backward_kernel,
-                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out);
+                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out, int tiling_batch = -1);
 // escoin_capi.hip: the first half of set_csr -- validates a CSR (flat, as escoin_plan_set_csr takes it) and copies it into
 // the plan's host vectors; a refused CSR leaves the plan as it was.  T = float | double.
 template <typename T>
@@ -464,6 +480,18 @@ struct S2dHooks {
   const char *pack_kernel_name;
 };
 extern S2dHooks g_s2d_hooks;   // escoin_capi.hip
+
+// s2b.hip (option "s2b"), registered like S2dHooks.  Each kernel serves both directions; `top_side` names the blob:
+//   pack    false: X' from the bottom blob (offset = the pad); true: G' from top_diff (offset 0), times [mask > 0] where
+//           mask (the top blob) is not null
+//   unpack  false: bottom_diff from dX' (offset = the pad); true: the top blob from T' (offset 0), through ReLU if `relu`
+// always of the first n_images images.
+struct S2bHooks {
+  int (*pack)(const escoin_plan *p, const float *src, const float *mask, float *dst, bool top_side, int n_images, hipStream_t stream);
+  int (*unpack)(const escoin_plan *p, const float *src, float *dst, bool top_side, bool relu, int n_images, hipStream_t stream);
+  const char *pack_kernel_name, *unpack_kernel_name;
+};
+extern S2bHooks g_s2b_hooks;   // escoin_capi.hip
 
 // Index of the k-th set bit of `mask` (k < popcount): blockIdx -> conv group when only some groups
 // of a layer run in a launch.  Wave-uniform scalar code on the device.

@@ -549,7 +549,7 @@ static int build_data(escoin_plan *p, BwdState *s, const BwdChoice &c, hipStream
   switch (c.data) {
     // the inner plan's backward state is built here, with this one: the update list is rebuilt once for both, and no
     // later call allocates (dX' is the X' scratch)
-    case kBwdInner: return ensure_state<float>(p->s2d_state->inner.plan.get(), stream);
+    case kBwdInner: return ensure_state<float>(p->inner_plan()->plan.get(), stream);
     case kBwdTransposed: return build_transposed_plan(p, s, stream);
     case kBwdMfma: return dgm_build(p, c.dgm, &s->dgm, stream);
     case kBwdGather: break;
@@ -565,7 +565,7 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   if (const int rcs = sync_host_values(p)) return rcs;
   const Geometry &g = p->g;
   const long nnz = plan_nnz(p);
-  const BwdOptions o{p->bwd_kernel, p->wgrad_kernel, p->wgrad_channel_block, p->s2d_state != nullptr};
+  const BwdOptions o{p->bwd_kernel, p->wgrad_kernel, p->wgrad_channel_block, p->inner_plan() != nullptr};
   const BwdChoice c = bwd_choice(g, p->is_f64, nnz, o, tiled_device_cus());
   if (c.rc != ESCOIN_OK) return fail(c.rc, c.error);
   p->bwd.reset(new BwdState());
@@ -586,8 +586,17 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
 
 // ---- data gradient: one function per path ----------------------------------------------------------------------------
 // option "s2d": dX' = the inner plan's data gradient of top_diff (the ReLU mask is its own), then depth-to-space
+// option "s2b": G' = top_diff's residue classes (times [top > 0] on a fuse_relu plan), dX' = the inner plan's data
+// gradient of G' (it has no ReLU and needs no top), then the classes interleaved into bottom_diff
 static int dgrad_inner(escoin_plan *p, const float *top, const float *top_diff, float *bottom_diff, int n_images,
                        hipStream_t stream) {
+  if (S2bState *sb = p->s2b_state.get()) {
+    const int P = sb->sp.eh * sb->sp.ew;
+    int rc = g_s2b_hooks.pack(p, top_diff, p->g.d.fuse_relu ? top : nullptr, sb->t.get<float>(), true, n_images, stream);
+    if (rc != ESCOIN_OK) return rc;
+    rc = escoin_backward(sb->inner.plan.get(), nullptr, nullptr, sb->t.get<const float>(), sb->x.get<float>(), nullptr, nullptr, n_images * P, stream);
+    return rc != ESCOIN_OK ? rc : g_s2b_hooks.unpack(p, sb->x.get<const float>(), bottom_diff, false, false, n_images, stream);
+  }
   S2dState *sd = p->s2d_state.get();
   const int rc = escoin_backward(sd->inner.plan.get(), nullptr, top, top_diff, sd->x.get<float>(), nullptr, nullptr, n_images, stream);
   return rc != ESCOIN_OK ? rc : g_s2d_hooks.unpack(p, sd->x.get<const float>(), bottom_diff, n_images, stream);

@@ -9,7 +9,7 @@
 //                               kernel's padded matrix), the generated code / the weight stream of a tiled plan's sparse groups
 //   its backward state's copy   by BwdState::data one of: the transposed plan (a derived plan), gather.tval through
 //                               gather.tsrc, dgm.mat through dgm.pos -- or none (the inner plan's state holds it)
-//   its derived plans           (escoin_plan.h DerivedPlan: the transposed plan, the inner plan of option "s2d") plans like
+//   its derived plans           (escoin_plan.h DerivedPlan: the transposed plan, the inner plan of option "s2d" or "s2b") plans like
 //                               any other, whose copies are reached through the maps on the way composed (compose_maps)
 // The first update on an alignment builds that list (UpdState); later updates launch one kernel and nothing else.
 // The list's device facts (buffers, their sizes, the bounds checks) are collected here; the indices derived from the CSR
@@ -115,7 +115,7 @@ bool in_place_ok(const escoin_plan *q) {
 // The walk: every copy of the values of the plan the walk began at (the root), as reached from plan q, whose entry j
 // holds the value of the root's entry (*outer)[j] (null: q is the root).  In this order:
 //   q's own forward side                  on_plan(q, map)
-//   q's derived plan of option "s2d"      this walk, through its map
+//   q's derived plan of option "s2d" / "s2b"   this walk, through its map
 //   the copy of q's backward state        its derived plan: this walk; an array: on_array(buf, elem_size, elem, map, n) -- for
 //                                         k < n, element (elem ? elem[k] : k) of buf, elem_size bytes each, is a copy
 // map[k] is the root's entry whose value the visited plan's entry k, or the array copy's k, holds (null: the identity).
@@ -142,6 +142,10 @@ int for_each_copy(Plan *q, const std::vector<int> *outer, bool with_maps, OnPlan
   if (const S2dState *sd = q->s2d_state.get()) {
     if (!through(sd->inner.src, &map)) return mismatch("the inner plan");
     if ((rc = for_each_copy<Plan>(sd->inner.plan.get(), map, with_maps, on_plan, on_array)) != ESCOIN_OK) return rc;
+  }
+  if (const S2bState *sb = q->s2b_state.get()) {   // (the identity map; a plan has one of the two states at most)
+    if (!through(sb->inner.src, &map)) return mismatch("the inner plan");
+    if ((rc = for_each_copy<Plan>(sb->inner.plan.get(), map, with_maps, on_plan, on_array)) != ESCOIN_OK) return rc;
   }
   const BwdState *s = q->bwd.get();
   if (!s) return ESCOIN_OK;

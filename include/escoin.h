@@ -164,6 +164,9 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  set on an aligned plan; stat "body_variant" = what the last forward ran (0 generic, 1 chained).
  *   "s2d"        = 0 (default) / 1: run a strided layer on the stride-1 kernels via space-to-depth ("Space-to-depth"
  *                  below).  1 changes nothing for a layer the option does not serve; KERNEL_AUTO never picks it by itself.
+ *   "s2b"        = 0 (default) / 1: run a dilated stride-1 layer on the stride-1, dilation-1 kernels via space-to-batch
+ *                  ("Space-to-batch" below).  1 changes nothing for a layer the option does not serve; KERNEL_AUTO never
+ *                  picks it by itself.  May be set together with "s2d": the two serve disjoint geometries.
  * Environment: the product build reads ESCOIN_VERBOSE (diagnostics on stderr) and TMPDIR (temporary file of the
  * code object manager's fallback path) and nothing else -- no environment variable can change a result
  * ("Environment"; csrc/knobs.h for the non-product flavours built by tools/mkabl.sh exp / stamps). */
@@ -249,7 +252,7 @@ ESCOIN_API int escoin_plan_import_aligned_dev(escoin_plan *plan, const void *dev
  * updates (escoin_update_values, escoin_plan_set_values, escoin_solver_step) reach the inner plan's copies and stay in
  * place wherever the inner plan is in-place capable; prune, rewire, set_csr and weight_align rebuild the inner plan.
  * escoin_plan_export_aligned writes the outer CSR and no code section; escoin_plan_import_aligned aligns from it.
- * Everywhere else -- stride 1 in both axes, a dilation, a size limit, a double plan, LOWERED_GEMM / LOWERED_SPARSE (a flip
+ * Everywhere else -- stride 1 in both axes, a dilation (option "s2b" serves the stride-1 ones), a size limit, a double plan, LOWERED_GEMM / LOWERED_SPARSE (a flip
  * of the conv mode rebuilds) -- the plan behaves exactly as with "s2d" = 0.
  * Stats: "s2d" (1 when active), "s2d_scratch_bytes"; "kernel_choice", "bwd_data_kernel", escoin_plan_tiling_info and the
  * other facts about the forward's kernel report the inner plan's; escoin_plan_kernel_name returns
@@ -261,6 +264,56 @@ ESCOIN_API int escoin_plan_import_aligned_dev(escoin_plan *plan, const void *dev
  * escoin_plan_s2d_pack runs the rearrangement alone into the plan's scratch (what escoin_forward runs first), for
  * measuring it; ESCOIN_ESTATE unless stat "s2d" is 1. */
 ESCOIN_API int escoin_plan_s2d_pack(escoin_plan *plan, const float *bottom_dev, int n_images, void *stream);
+
+/* ---- Space-to-batch: dilated layers on the stride-1, dilation-1 kernels (option "s2b") -------------------------------
+ * A dilated stride-1 convolution is dil_h x dil_w independent undilated convolutions: output pixel (oh, ow) reads only
+ * padded input pixels of its own residue class modulo (dil_h, dil_w).  For a descriptor with stride_h = stride_w = 1 let
+ * eh = dil_h if KH > 1 else 1, ew = dil_w if KW > 1 else 1 (a dilation on an axis with one tap is no dilation), P = eh * ew,
+ * Hp = H + 2 pad_h, Wp = W + 2 pad_w, H' = ceil(Hp / eh), W' = ceil(Wp / ew), OH' = H' - KH + 1 = ceil(OH / eh),
+ * OW' = W' - KW + 1 = ceil(OW / ew).  The INNER plan has
+ *   N' = N * P images, n' = (n * eh + qh) * ew + qw (the first n_images outer images are the first n_images * P inner
+ *   ones), the outer plan's C, M, group, KH x KW and has_bias, an H' x W' image, pad 0, stride 1, dilation 1, fuse_relu = 0;
+ *   weights the outer CSR verbatim: same rows, same columns, same value order;
+ *   input   X'[n'][c][i][j] = X[n][c][i * eh + qh - pad_h][j * ew + qw - pad_w] inside the image, +0 outside -- the rows
+ *           and columns of short residue classes past Hp / Wp included;
+ *   T' = inner_forward(X'), the bias in the inner epilogue;
+ *   top[n][m][oh][ow] = T'[n'(n, oh % eh, ow % ew)][m][oh / eh][ow / ew], then v > 0 ? v : 0 on a fuse_relu plan (the
+ *           epilogues' expression: a NaN becomes 0 as it does there);
+ *   G'[n'][m][i][j] = top_diff[n][m][i * eh + qh][j * ew + qw] inside OH x OW, +0 outside; on a fuse_relu plan
+ *           top > 0 ? top_diff : 0 there (the expression of the transposed data-gradient path);
+ *   dX' = inner_data_gradient(G') (the inner plan has no ReLU and needs no top), and with hp = h + pad_h, wp = w + pad_w
+ *           bottom_diff[n][c][h][w] = dX'[n'(n, hp % eh, wp % ew)][c][hp / eh][wp / ew]: every element of the first
+ *           n_images images is written exactly once.
+ * All P residue classes are always inner images, also where OH < eh leaves some without a top pixel: their G' is all
+ * zeros, so bottom pixels no window reads get a zero gradient.
+ * With "s2b" = 1 a FLOAT plan in conv_mode SCONV / SCONV_PAR with stride 1 in both axes and P > 1, whose bottom, top, X'
+ * and T' each stay below 2^31 elements and whose N * P is at most 65535 (the image index is a grid dimension of the
+ * generic kernel and of the backward's kernels), runs this way: escoin_forward = escoin_s2b_pack_kernel (one pass, zeros
+ * included) + the inner plan's forward + escoin_s2b_unpack_kernel; the data gradient = escoin_s2b_pack_kernel of top_diff +
+ * the inner plan's backward + escoin_s2b_unpack_kernel.  The inner plan and the two scratches (X' / dX' and T' / G') are
+ * built by the align; forward and backward never allocate.  The inner plan gets the options "kernel", "backward_kernel",
+ * "max_launch_bytes", "dense_threshold_pct", "dense_gate" and "code_loader", and "tiling_batch" times P, and ALONE
+ * decides dense or sparse per group, on its own geometry: forcing TILED / JIT fails with ESCOIN_EINVAL where the inner
+ * layer does not fit them (KW > 5, W' > 256, ...).  "backward_kernel" = GENERIC keeps the outer gather kernel,
+ * ESCOIN_BWD_MFMA the outer MFMA data gradient; AUTO, TILED, JIT and DENSE go to the inner plan's backward.  The weight,
+ * bias and compact gradients and escoin_dense_wgrad read the original bottom and are untouched (the same bits as without
+ * the option).  In-place updates (escoin_update_values, escoin_plan_set_values, escoin_solver_step) reach the inner plan's
+ * copies and stay in place wherever the inner plan is in-place capable; prune, rewire, set_csr and weight_align rebuild
+ * the inner plan.  escoin_plan_export_aligned writes the outer CSR and no code section; escoin_plan_import_aligned aligns
+ * from it.  Everywhere else -- a stride above 1, P == 1 (dilation 1, a 1x1 kernel), a size limit, a double plan,
+ * LOWERED_GEMM / LOWERED_SPARSE (a flip of the conv mode rebuilds) -- the plan behaves exactly as with "s2b" = 0.
+ * Stats: "s2b" (1 when active), "s2b_scratch_bytes" (both scratches); "kernel_choice", "bwd_data_kernel",
+ * escoin_plan_tiling_info and the other facts about the forward's kernel report the inner plan's; escoin_plan_kernel_name
+ * returns "escoin_s2b_pack_kernel + <inner name> + escoin_s2b_unpack_kernel".  "device_bytes" and
+ * escoin_plan_workspace_bytes count the scratches and the inner plan.  Ordering across streams is the caller's, as for
+ * any plan: forward and backward share the scratches.
+ * Non-finite input: a non-finite bottom element reaches a zero weight (0 x inf = NaN) only where the inner plan chose
+ * its DENSE kernel -- the property the DENSE kernel has without the option; the sparse inner kernels never multiply by a
+ * pruned weight, and the padding the pack kernel writes is +0, never a bottom element.
+ * escoin_plan_s2b_pack runs the forward's first rearrangement alone (the bottom into the X' scratch), escoin_plan_s2b_unpack
+ * its last (the T' scratch, whatever it holds, into the top blob), for measuring them; ESCOIN_ESTATE unless stat "s2b" is 1. */
+ESCOIN_API int escoin_plan_s2b_pack(escoin_plan *plan, const float *bottom_dev, int n_images, void *stream);
+ESCOIN_API int escoin_plan_s2b_unpack(escoin_plan *plan, float *top_dev, int n_images, void *stream);
 
 /* Integer facts about an aligned plan (negative = error): "align_us" wall time of the last
  * weight_align / set_csr / import_aligned, "code_bytes" generated machine code on the device,
