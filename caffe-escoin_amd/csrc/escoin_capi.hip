@@ -284,12 +284,19 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     if (rc != ESCOIN_OK) p->s2b_state.reset();
     return rc;
   }
+  // A forced TILED / JIT on a layer that "s2d" / "s2b" serves in the direct modes names the INNER plan's kernel: the layer's own
+  // geometry (a stride, a dilation) has no tiled kernel.  Here the plan stands in a lowered mode, which runs on that geometry
+  // without the inner plan, and aligns as under KERNEL_AUTO instead of refusing -- a conv_mode flip left such a plan unaligned.
+  int kernel = p->kernel_choice;
+  if ((kernel == ESCOIN_KERNEL_TILED || kernel == ESCOIN_KERNEL_JIT) && !tiled_supported(g) &&
+      ((p->s2d && s2d_plan(g, false, &s2p)) || (p->s2b && s2b_plan(g, false, &s2bp))))
+    kernel = ESCOIN_KERNEL_AUTO;
   // which conv groups go to the dense (fp32 MFMA) kernel (align_rules.h)
   const int G = g.d.group;
   std::vector<long> nnz_per_group(G);
   for (int grp = 0; grp < G; ++grp) nnz_per_group[grp] = (long)p->colidx[grp].size();
   const GroupSplit split = group_split(dense_groups(
-      g, nnz_per_group, SplitOptions{p->kernel_choice, p->conv_mode, p->dense_gate, p->dense_threshold_pct, p->tiling_batch},
+      g, nnz_per_group, SplitOptions{kernel, p->conv_mode, p->dense_gate, p->dense_threshold_pct, p->tiling_batch},
       tiled_device_cus()));
   p->n_dense_groups = split.n_dense;
   p->n_sparse_groups = split.n_sparse;
@@ -313,8 +320,8 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     return ESCOIN_OK;
   }
   p->small_rule = 0;
-  const bool explicit_tiled = p->kernel_choice == ESCOIN_KERNEL_TILED || p->kernel_choice == ESCOIN_KERNEL_JIT;
-  const bool want_tiled = explicit_tiled || (p->kernel_choice == ESCOIN_KERNEL_AUTO && tiled_supported(g));
+  const bool explicit_tiled = kernel == ESCOIN_KERNEL_TILED || kernel == ESCOIN_KERNEL_JIT;
+  const bool want_tiled = explicit_tiled || (kernel == ESCOIN_KERNEL_AUTO && tiled_supported(g));
   if (want_tiled) {
     if (!tiled_supported(g))
       return fail(ESCOIN_EINVAL, "tiled kernel requested for a geometry it does not support");
@@ -325,7 +332,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     // over 50-95 % sparsity on every BASELINE 3x3 / 5x5 / 1x1 shape generated code is now ahead of the
     // stream kernel at every point (profiles/r04_crossover.md; the worst point, alex_conv2 @50 %, by 14 %).
     // Code beyond kMaxJitBytes (geometry.h) falls back to the stream kernel by itself.
-    const bool try_jit = p->kernel_choice == ESCOIN_KERNEL_JIT || p->kernel_choice == ESCOIN_KERNEL_AUTO;
+    const bool try_jit = kernel == ESCOIN_KERNEL_JIT || kernel == ESCOIN_KERNEL_AUTO;
     int rc = ESCOIN_OK;
     p->import_fast = false;
     p->small_rule = 0;     // (set by tiled_build / tiled_import from the tiling, before any code is generated or loaded)
@@ -336,8 +343,8 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     }
     if (try_jit && !p->tiled.enabled && p->small_rule != 2) {
       rc = tiled_build(p, stream, true);
-      if (rc != ESCOIN_OK && p->kernel_choice == ESCOIN_KERNEL_JIT) return rc;
-      if (!p->tiled.enabled && p->kernel_choice == ESCOIN_KERNEL_JIT)
+      if (rc != ESCOIN_OK && kernel == ESCOIN_KERNEL_JIT) return rc;
+      if (!p->tiled.enabled && kernel == ESCOIN_KERNEL_JIT)
         return fail(ESCOIN_EINVAL, "generated-code kernel requested but the layer does not fit it");
       if (rc != ESCOIN_OK) {
         // KERNEL_AUTO: a failure of the code path (code object manager, module load, an allocation)
@@ -356,7 +363,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
       rc = tiled_build(p, stream, false);   // leaves tiled.enabled false when the stream does not fit LDS
       if (rc != ESCOIN_OK) return rc;
     }
-    if (!p->tiled.enabled && p->kernel_choice == ESCOIN_KERNEL_TILED)
+    if (!p->tiled.enabled && kernel == ESCOIN_KERNEL_TILED)
       return fail(ESCOIN_EINVAL, "tiled kernel requested but its weight stream does not fit the LDS budget");
   }
   p->kernel_name = p->tiled.enabled ? tiled_kernel_name(p) : generic_kernel_name(g.d.fuse_relu != 0);

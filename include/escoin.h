@@ -253,7 +253,10 @@ ESCOIN_API int escoin_plan_import_aligned_dev(escoin_plan *plan, const void *dev
  * place wherever the inner plan is in-place capable; prune, rewire, set_csr and weight_align rebuild the inner plan.
  * escoin_plan_export_aligned writes the outer CSR and no code section; escoin_plan_import_aligned aligns from it.
  * Everywhere else -- stride 1 in both axes, a dilation (option "s2b" serves the stride-1 ones), a size limit, a double plan, LOWERED_GEMM / LOWERED_SPARSE (a flip
- * of the conv mode rebuilds) -- the plan behaves exactly as with "s2d" = 0.
+ * of the conv mode rebuilds) -- the plan behaves exactly as with "s2d" = 0, with one exception: in LOWERED_GEMM /
+ * LOWERED_SPARSE a layer the option serves in the direct modes, whose own geometry has no tiled kernel, reads a forced
+ * "kernel" = TILED / JIT -- the inner plan's kernel -- as AUTO instead of refusing the align, so that a conv_mode flip
+ * never leaves the plan unaligned ("backward_kernel" is read as it stands, as with "s2d" = 0).
  * Stats: "s2d" (1 when active), "s2d_scratch_bytes"; "kernel_choice", "bwd_data_kernel", escoin_plan_tiling_info and the
  * other facts about the forward's kernel report the inner plan's; escoin_plan_kernel_name returns
  * "escoin_s2d_pack_kernel + <inner name>".  "device_bytes" and escoin_plan_workspace_bytes count the scratch and the
@@ -301,7 +304,9 @@ ESCOIN_API int escoin_plan_s2d_pack(escoin_plan *plan, const float *bottom_dev, 
  * copies and stay in place wherever the inner plan is in-place capable; prune, rewire, set_csr and weight_align rebuild
  * the inner plan.  escoin_plan_export_aligned writes the outer CSR and no code section; escoin_plan_import_aligned aligns
  * from it.  Everywhere else -- a stride above 1, P == 1 (dilation 1, a 1x1 kernel), a size limit, a double plan,
- * LOWERED_GEMM / LOWERED_SPARSE (a flip of the conv mode rebuilds) -- the plan behaves exactly as with "s2b" = 0.
+ * LOWERED_GEMM / LOWERED_SPARSE (a flip of the conv mode rebuilds) -- the plan behaves exactly as with "s2b" = 0, with the
+ * exception "Space-to-depth" states: in the lowered modes a forced "kernel" = TILED / JIT on a layer the option serves
+ * in the direct modes is read as AUTO (the dilated geometry has no tiled kernel; the flip must not leave the plan unaligned).
  * Stats: "s2b" (1 when active), "s2b_scratch_bytes" (both scratches); "kernel_choice", "bwd_data_kernel",
  * escoin_plan_tiling_info and the other facts about the forward's kernel report the inner plan's; escoin_plan_kernel_name
  * returns "escoin_s2b_pack_kernel + <inner name> + escoin_s2b_unpack_kernel".  "device_bytes" and

@@ -35,6 +35,15 @@ LAYERS = {
     "PW_B": ("ebpw_b", (4, 60, 5, 5, 150, 1), dict(sparsity=0.95)),
     "G5X5": ("ebg5x5", (2, 16, 12, 10, 12, 5), dict(pad=2, group=2, sparsity=0.8)),
     "STR2": ("ebs2", (3, 8, 31, 31, 8, 3), dict(pad=1, stride=2, sparsity=0.6)),
+    # The dilated layer of option "s2b".  Dilation 2 x 3: the smallest pair with dil_h != dil_w, both above 1 (P = 6 residue
+    # classes).  13 x 16 with pad 2 x 3 is a padded frame of 17 x 22: neither a multiple of its dilation, so the row classes
+    # hold 9 and 8 rows and the column classes 8, 7 and 7 (short classes on both axes); pad <= dil * (K - 1) on both axes
+    # (4 and 6), so the outer transposed plan exists.  The inner layer is 18 images of 24 x 9 x 8, pad 0, with a 7 x 6 top, on
+    # L3X3's channel counts; forced KERNEL_TILED and KERNEL_JIT take it, and its transposed layer, as it is (align_rules'
+    # host rules say so, test_errbound_gpu.py runs both), so nothing had to grow beyond what the
+    # residue classes need (17 = 2 * 8 + 1, 22 = 3 * 7 + 1: one long class per axis, the others short).  N = 3: n_part = N // 2
+    # = 1 is a partial batch, of 6 inner images, with two images past it that must stay untouched.
+    "DIL": ("ebdil", (3, 24, 13, 16, 20, 3), dict(pad=2, pad_w=3, dil=2, dil_w=3, sparsity=0.9)),
 }
 
 # ---- the configurations ---------------------------------------------------------------------------------------------------------
@@ -64,6 +73,15 @@ CONFIGS = [
            dict(s2d=1, bwd_data_kernel="BWD_MFMA"), {}),
     Config("s2d_outer_generic", "STR2", dict(s2d=1, backward_kernel="KERNEL_GENERIC", wgrad_kernel="WGRAD_ENTRY"), False, False, "pruned",
            dict(s2d=1, bwd_data_kernel="KERNEL_GENERIC", wgrad_kernel="WGRAD_ENTRY"), {}),
+    # option "s2b": the weights also live in every copy of the inner plan of N * P images, which a prune, rewire, set_csr or
+    # conv_mode flip tears down and rebuilds.  Float plans: every op of the vocabulary applies
+    Config("s2b_inner", "DIL", dict(s2b=1), False, False, "pruned", dict(s2b=1), {}),
+    Config("s2b_inner_jit", "DIL", dict(s2b=1, kernel="KERNEL_JIT", backward_kernel="KERNEL_JIT", tiling_batch=256), True, False, "pruned",
+           dict(s2b=1, name=("jit",), bwd_data_kernel="KERNEL_JIT"), {}),      # the ReLU mask through the pack kernel, generated code inside
+    Config("s2b_outer_mfma", "DIL", dict(s2b=1, backward_kernel="BWD_MFMA"), False, False, "pruned",
+           dict(s2b=1, bwd_data_kernel="BWD_MFMA"), {}),
+    Config("s2b_outer_generic", "DIL", dict(s2b=1, backward_kernel="KERNEL_GENERIC", wgrad_kernel="WGRAD_ENTRY"), False, False, "pruned",
+           dict(s2b=1, bwd_data_kernel="KERNEL_GENERIC", wgrad_kernel="WGRAD_ENTRY"), {}),
     Config("double", "L3X3", dict(wgrad_kernel="WGRAD_ENTRY"), False, True, "pruned",
            dict(name=("f64",), bwd_data_kernel="KERNEL_GENERIC", wgrad_kernel="WGRAD_ENTRY"),
            {"dense_wgrad": _NO_F64_WGRAD, "import_same": _NO_F64_FORM, "import_fresh": _NO_F64_FORM}),
@@ -73,17 +91,20 @@ CPU_CONFIGS = [
     Config("cpu_3x3_f32", "L3X3", {}, True, False, "pruned", {}, _CPU_EXCLUDE),
     Config("cpu_groups_f64", "G5X5", {}, False, True, "mixed", {}, _CPU_EXCLUDE),
     Config("cpu_stride2_f32", "STR2", {}, False, False, "pruned", {}, _CPU_EXCLUDE),
+    Config("cpu_dilated_f32", "DIL", {}, False, False, "pruned", {}, _CPU_EXCLUDE),
 ]
 BY_ID = {c.id: c for c in CONFIGS + CPU_CONFIGS}
 
 # Seeds and length: chosen so that test_generator_coverage holds (every op of a configuration's vocabulary at least twice
-# over its seeds; every ordered pair of distinct mutating classes adjacent somewhere in the device suite).
+# over its seeds; every ordered pair of distinct mutating classes adjacent somewhere in the device suite).  The "s2b" and
+# cpu_dilated_f32 rows: the first three consecutive seeds, counted from 1, that coverage() accepts for the configuration.
 LENGTH = 20
 SEEDS = {
     "jit_3x3": (6, 7, 8), "tiled_3x3": (2, 3, 4), "generic_3x3": (13, 14, 15), "dense_mfma": (4, 5, 6), "mixed_groups": (1, 2, 3),
     "pointwise": (9, 10, 11), "jit_loader": (3, 4, 5), "s2d_inner": (6, 7, 8), "s2d_outer_mfma": (12, 13, 14),
     "s2d_outer_generic": (5, 6, 7), "double": (1, 2, 3),
-    "cpu_3x3_f32": (1, 2, 3), "cpu_groups_f64": (2, 3, 4), "cpu_stride2_f32": (1, 2, 3),
+    "s2b_inner": (5, 6, 7), "s2b_inner_jit": (11, 12, 13), "s2b_outer_mfma": (1, 2, 3), "s2b_outer_generic": (5, 6, 7),
+    "cpu_3x3_f32": (1, 2, 3), "cpu_groups_f64": (2, 3, 4), "cpu_stride2_f32": (1, 2, 3), "cpu_dilated_f32": (2, 3, 4),
 }
 
 
@@ -578,6 +599,29 @@ def fast_import(is_fast, fast0, fast1):
             STEP, chk(fast0), STEP, chk(fast1), BWD, ("import_same", {}), chk(is_fast), ("prune", dict(mode="keep", frac=0.8, seed=2)),
             _upd("set_values", "device", 3), chk(fast1),
             BWD, ("get_csr", {})]
+
+
+def derived_plan_lifecycle(check):
+    """What only a plan with an inner plan (option "s2d" / "s2b") has: every point at which the inner plan is torn down and
+    rebuilt, an update or a backward on either side of it, and check(driver) after each op.  The points: the first backward
+    (the inner or the outer backward copy appears), prune, the conv_mode flips (the lowered modes run without the inner
+    plan; an update between two of them), rewire on the checked dense weight gradient, both imports, a prune to nothing and
+    a rewire that grows from nothing."""
+    ops = [_upd("set_values", "device", 1), BWD, ("prune", dict(mode="keep", frac=0.8, seed=2)), _upd("set_values", "host", 3),
+           ("flip", dict(mode="sparse")), _upd("update_values", "device", 4), ("flip", dict(mode="gemm")), ("flip", dict(mode="both")),
+           ("rewire", dict(drop="keep", drop_frac=0.8, grow_frac=0.2, init=False, score="dense_wgrad", seed=5)),
+           ("import_same", {}), STEP, ("import_fresh", {}), _upd("set_values", "device", 6),
+           ("prune", dict(mode="keep", frac=0.0, seed=7)),
+           ("rewire", dict(drop=None, drop_frac=1.0, grow_frac=4.0, init=False, score="ties", seed=8)), BWD]
+    out = []
+    for op in ops:
+        out += [op, ("check", dict(fn=check))]
+    return out
+
+
+# The shortest sequence on which a plan of option "s2b" with a forced KERNEL_JIT / KERNEL_TILED was left unaligned: the flip to
+# LOWERED_SPARSE rebuilds the plan on the dilated geometry itself, where the forced kernel -- the inner plan's -- does not exist
+FLIP_UNDER_A_FORCED_INNER_KERNEL = [("flip", dict(mode="sparse"))]
 
 
 # The shortest sequence that the device binding refused before solver_step and compact_entries took arrays of 0 elements

@@ -21,6 +21,9 @@ PW_A = ("ebpw_a", (9, 96, 7, 9, 33, 1), dict(sparsity=0.95))
 PW_B = ("ebpw_b", (4, 60, 5, 5, 150, 1), dict(sparsity=0.95))
 G5X5 = ("ebg5x5", (2, 16, 12, 10, 12, 5), dict(pad=2, group=2, sparsity=0.8))
 STR2 = ("ebs2", (3, 8, 31, 31, 8, 3), dict(pad=1, stride=2, sparsity=0.6))
+# dilation 2 x 3 on a padded frame of 17 x 22 (row classes of 9 and 8 rows, column classes of 8, 7 and 7 columns); under option
+# "s2b" 18 inner images of 24 x 9 x 8 with a 7 x 6 top, which forced TILED and JIT accept (seq_common.LAYERS has the reasons)
+DIL = ("ebdil", (3, 24, 13, 16, 20, 3), dict(pad=2, pad_w=3, dil=2, dil_w=3, sparsity=0.9))
 GK = ("gk", (64, 1024, 7, 7, 512, 1), dict(sparsity=0.0))       # test_gpu_parity.py's stream-K layer
 
 
@@ -135,6 +138,32 @@ def test_forward_stride_2(pkg, synth, dev, kn):
     _run_forward(pkg, dev, s, sk, getattr(pkg, "KERNEL_" + kn), ON_OFF, partial=1)
 
 
+S2B_PACK, S2B_UNPACK = "escoin_s2b_pack_kernel", "escoin_s2b_unpack_kernel"
+DIL_RUNS = [("GENERIC", 0), ("DENSE", 0), ("AUTO", 0), ("GENERIC", 1), ("TILED", 1), ("JIT", 1), ("DENSE", 1), ("AUTO", 1)]
+
+
+@pytest.mark.parametrize("kn,s2b", DIL_RUNS, ids=["%s%s" % (k, "-s2b" if o else "") for k, o in DIL_RUNS])
+def test_forward_dilated_with_and_without_space_to_batch(pkg, synth, dev, kn, s2b):
+    """The dilated layer on its own geometry (the generic and the dense kernel: no tiled kernel takes a dilation) and under
+    option "s2b" with each kernel family as the inner plan's: pack, the inner forward of N * P images, unpack (the ReLU
+    there).  The partial batch is one image: P of the 3 * P inner images."""
+    s, sk, _ = _layer(synth, DIL)
+    kernel = getattr(pkg, "KERNEL_" + kn)
+
+    def check_name(name):
+        parts = name.split(" + ")
+        if s2b:     # pack + the inner plan's own name, which names the forced family + unpack
+            assert len(parts) >= 3 and parts[0] == S2B_PACK and parts[-1] == S2B_UNPACK, name
+            parts = parts[1:-1]
+        assert not any("s2b" in p or "s2d" in p for p in parts), name
+        _expect(pkg, kernel, " + ".join(parts))
+
+    for plan in _forward_cases(pkg, dev, s, sk, kernel, ALL4, partial=s.N // 2, check_name=check_name, **(dict(s2b=1) if s2b else {})):
+        assert plan.stat("s2b") == s2b and plan.stat("s2d") == 0, plan.kernel_name
+        if s2b and kn != "AUTO":
+            assert plan.stat("kernel_choice") == kernel, plan.kernel_name
+
+
 def test_forward_dense_stream_k_fixup(pkg, synth, dev):
     """The dense MFMA kernel with K split across workgroups: the cut tiles' partial sums are added in a fix-up (the
     split-K add of the bound's + 4)."""
@@ -179,6 +208,10 @@ FAMILIES = [
     ("tiled_pointwise", PW_B, "KERNEL_TILED", dict(tiling_batch=256), False),
     ("jit_5x5_groups", G5X5, "KERNEL_JIT", dict(tiling_batch=256), False),
     ("generic_stride2", STR2, "KERNEL_GENERIC", {}, False), ("dense_stride2", STR2, "KERNEL_DENSE", {}, False),
+    # the options that run a layer through an inner plan: pack and unpack copy values, so the property holds through them
+    ("s2d_stride2", STR2, "KERNEL_AUTO", dict(s2d=1), False),
+    ("s2b_dilated", DIL, "KERNEL_AUTO", dict(s2b=1), False), ("s2b_jit_dilated", DIL, "KERNEL_JIT", dict(s2b=1), False),
+    ("generic_dilated", DIL, "KERNEL_GENERIC", {}, False), ("dense_dilated", DIL, "KERNEL_DENSE", {}, False),
 ]
 
 
@@ -197,6 +230,9 @@ def test_row_and_image_scaling_are_exact_on_every_kernel_family(pkg, synth, dev,
         plan = pkg.Plan(pkg.ConvDesc.from_shape(s), kernel=getattr(pkg, kn), **opts)
         plan.weight_align(ww.astype(dt))
         names.append((plan.kernel_name, plan.tiling_info))
+        for option in ("s2d", "s2b"):       # the option is active on its rows, and on no other
+            assert plan.stat(option) == opts.get(option, 0) and (("escoin_%s_pack_kernel" % option) in names[-1][0]) == (option in opts), \
+                (fam, option, names[-1])
         outs[key] = plan.forward(xd, _up(bb, dev, dt)).clone()
         if key == "plain":
             outs["nobias"] = plan.forward(xd, None).clone()

@@ -14,7 +14,7 @@ import pytest
 import seq_common as sq
 import solver_common as sc
 from seq_backends import GpuBackend
-from test_errbound_gpu import G5X5, L3X3, PW_B, STR2
+from test_errbound_gpu import DIL, G5X5, L3X3, PW_B, STR2
 
 torch = pytest.importorskip("torch")
 
@@ -26,6 +26,8 @@ FLOAT_IDS = [c.id for c in sq.CONFIGS if not c.f64]
 IN_PLACE_IDS = [c.id for c in sq.CONFIGS if not c.options.get("code_loader")]
 # the configurations whose plan runs generated code and loads a persisted code object as it is (stat import_fast == 1)
 FAST_IMPORT_IDS = ["jit_3x3", "mixed_groups", "pointwise"]
+# the configurations whose plan runs through an inner plan (options "s2d" and "s2b")
+DERIVED_IDS = [c.id for c in sq.CONFIGS if c.options.get("s2d") or c.options.get("s2b")]
 
 
 @pytest.fixture(scope="module")
@@ -66,7 +68,7 @@ def _run(pkg, dev, synth, cid, hyper, ops, what, after=None):
 
 
 def test_the_layers_are_the_error_bound_suites():
-    assert [sq.LAYERS[k] for k in ("L3X3", "PW_B", "G5X5", "STR2")] == [L3X3, PW_B, G5X5, STR2]
+    assert [sq.LAYERS[k] for k in ("L3X3", "PW_B", "G5X5", "STR2", "DIL")] == [L3X3, PW_B, G5X5, STR2, DIL] and len(sq.LAYERS) == 5
 
 
 @pytest.mark.parametrize("cid", IDS)
@@ -164,6 +166,46 @@ def test_an_emptied_plan_grows_again(pkg, dev, synth, cid):
 
     _run(pkg, dev, synth, cid, dict(type=sc.NESTEROV, regularization=sc.REG_NONE, rate=1e-2, momentum=0.9),
          sq.empty_then_grow(sq.empty_forward_is_the_bias), "emptied", after)
+
+
+@pytest.mark.parametrize("cid", DERIVED_IDS)
+def test_a_derived_plan_is_rebuilt_at_every_point_that_tears_it_down(pkg, dev, synth, cid):
+    """seq_common.derived_plan_lifecycle on the plans that run through an inner plan.  After every op, in the plan's own
+    conv_mode: the option is active and kernel_name has the option's parts around the inner plan's name; the scratch is
+    the size it had at the first check (a rebuild allocates it again, never a second one); workspace_bytes is the sum of the
+    four states' bytes.  The driver's forward after every mutating op and its comparison with a fresh plan do the rest."""
+    opt = "s2b" if cid.startswith("s2b") else "s2d"
+    seen = {}
+
+    def check(drv):
+        plan = drv.b.plan
+        name = plan.kernel_name
+        assert drv.b.mode is None and plan.stat(opt) == 1 and plan.stat("s2d" if opt == "s2b" else "s2b") == 0, (cid, name)
+        parts = name.split(" + ")
+        if opt == "s2b":
+            assert len(parts) >= 3 and parts[0] == "escoin_s2b_pack_kernel" and parts[-1] == "escoin_s2b_unpack_kernel", name
+            inner = parts[1:-1]
+        else:
+            assert len(parts) >= 2 and parts[0] == "escoin_s2d_pack_kernel", name
+            inner = parts[1:]
+        assert all(p.startswith("escoin_") and "_s2" not in p for p in inner), name
+        scratch = plan.stat(opt + "_scratch_bytes")
+        assert scratch > 0 and seen.setdefault("scratch", scratch) == scratch, (cid, seen, scratch)
+        assert plan.stat("device_bytes") > scratch
+        assert plan.workspace_bytes == sum(plan.stat(k + "device_bytes") for k in ("", "bwd_", "upd_", "dwg_")), (cid, drv.b.accounting())
+
+    _run(pkg, dev, synth, cid, SGD, sq.derived_plan_lifecycle(check), "derived plan lifecycle")
+
+
+@pytest.mark.parametrize("cid", ["s2b_inner_jit"])
+def test_a_flip_to_lowered_sparse_under_a_forced_inner_kernel(pkg, dev, synth, cid):
+    """The shortest sequence of the one refusal the "s2b" configurations found (seq_common has it): the flip aligns the
+    plan on its dilated geometry, where no generated code exists, and back in its own mode the inner plan runs it again."""
+    def check(drv):
+        plan = drv.b.plan
+        assert plan.stat("s2b") == 1 and "jit" in plan.kernel_name and plan.stat("bwd_data_kernel") == pkg.KERNEL_JIT, plan.kernel_name
+
+    _run(pkg, dev, synth, cid, SGD, sq.FLIP_UNDER_A_FORCED_INNER_KERNEL + [sq.BWD, ("check", dict(fn=check))], "flip under a forced inner kernel")
 
 
 @pytest.mark.parametrize("cid", IDS)
