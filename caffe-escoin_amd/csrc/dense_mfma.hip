@@ -708,6 +708,7 @@ int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, f
                        (int)(flag_bytes / 4));
   }
   dn.sk_used = streamk;
+  dn.variant_last = (bm == 64 ? 1 : 2) + 4 * (vec_b ? 1 : 0) + 8 * (a.vec_out ? 1 : 0) + 16 * (streamk ? 1 : 0);
   dim3 grid((unsigned)n_wg, 1, 1);
 #define ESC_DENSE_LAUNCH(WR, MODE)                                                                                 \
   do {                                                                                                             \

@@ -788,7 +788,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
     // what describes the forward's kernel is the inner plan's
     static const char *const inner_keys[] = {"kernel_choice", "code_bytes", "code_direct", "small_launch_rule", "jit_rows", "jit_records",
                                              "deal_slowest_over_mean_x1000", "deal_worst_block_x1000", "lds_bytes", "body_variant",
-                                             "workgroup_columns", "streamk_gave_up", "streamk"};
+                                             "workgroup_columns", "streamk_gave_up", "streamk", "dense_variant"};
     for (const char *k : inner_keys)
       if (!strcmp(key, k)) return escoin_plan_stat(p->inner_plan()->plan.get(), key);
   }
@@ -821,6 +821,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
     return (long)v;
   }
   if (!strcmp(key, "streamk")) return p->dense.sk_used ? 1 : 0;
+  if (!strcmp(key, "dense_variant")) return p->dense.variant_last;
   if (!strncmp(key, "bwd_", 4) || !strncmp(key, "wgrad_", 6) || !strncmp(key, "dgrad_", 6)) return bwd_stat(p, key);
   if (!strncmp(key, "upd", 3)) return upd_stat(p, key);
   if (!strncmp(key, "dwg_", 4)) return dwg_stat(p, key);

@@ -254,6 +254,9 @@ struct DenseArrays {
   int sk_flag_words = 0;
   MappedWord sk_fail;      // the word the kernel sets when a fix-up wait gave up (sticky until the next WeightAlign)
   mutable bool sk_used = false;   // the last dense launch of this plan split K (escoin_plan_stat "streamk")
+  // the instantiation and store path of the last dense launch: WROWS + 4 * BMODE + 8 * vec_out + 16 * STREAMK, 0 before
+  // the first one (escoin_plan_stat "dense_variant")
+  mutable int variant_last = 0;
 };
 
 }  // namespace escoin

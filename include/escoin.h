@@ -336,7 +336,10 @@ ESCOIN_API int escoin_plan_s2b_unpack(escoin_plan *plan, float *top_dev, int n_i
  * WeightAlign dealt the output channels over the waves that meet at a block's barrier -- slowest wave / mean wave,
  * weighted over all blocks, and the worst single block, x 1000; 0 for a plan restored from a persisted code object),
  * "streamk" / "streamk_gave_up"
- * (dense kernel; a give-up also makes the next escoin_forward on the plan fail with ESCOIN_EHIP). */
+ * (dense kernel; a give-up also makes the next escoin_forward on the plan fail with ESCOIN_EHIP),
+ * "dense_variant" (which instantiation and store path the plan's last dense launch took: output-channel rows per wave
+ * (1: 64-row tiles, 2: 128-row tiles) + 4 if the pointwise operand was staged 16 bytes at a time + 8 if the top was
+ * stored 16 bytes at a time + 16 if K was split across workgroups; 0 before the first dense launch). */
 ESCOIN_API long escoin_plan_stat(const escoin_plan *plan, const char *key);
 
 /* Name of the device kernel the plan launches (the symbol rocprofv3 reports). */

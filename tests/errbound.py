@@ -8,4 +8,5 @@ _TOOLS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))
 if _TOOLS not in sys.path:
     sys.path.insert(0, _TOOLS)
 from error_bound import (ROW_EXPONENTS, TINY, U32, U64, Skewed, accumulated_bound, backward_bound, check,  # noqa: E402,F401
-                         drop_bias, forward_bound, gamma, leak_from, low_channels, row_nnz, skew, swap_images, within)
+                         corruption_target, drop_bias, forward_bound, gamma, leak_from, low_channels, row_nnz, skew,
+                         swap_images, within)

@@ -40,17 +40,9 @@ def test_the_checker_passes_the_oracle_and_fails_three_corruptions_that_rel_err_
     out = oracle.conv_forward(_geom(oracle, s), sk.x, sk.w, sk.b, gate=False)
     want, B = eb.forward_bound(s, sk.w, sk.x, sk.b)
     ratio = eb.within(out, want, B, "the fp32 oracle", sk.row_exp, what=s.name)
-    order, mag = eb.low_channels(want)
-    quarter = order[:max(1, s.M // 4)]
-    nnz = eb.row_nnz(sk.w)
-    # the lowest channel of the quarter that has nonzeros and a bias (filters_tail leaves some rows empty)
-    live = [m for m in quarter if nnz[m] > 0 and sk.b[m] != 0]
-    m = int(live[0] if live else quarter[0])
-    # its neighbour (m - 1 or m + 1) of the larger magnitude: rows that share a wave or a quad are adjacent
-    src = max((n for n in (m - 1, m + 1) if 0 <= n < s.M), key=lambda n: mag[n])
-    if mag[src] < 2.0 ** 20 * mag[m]:      # no high-scale neighbour next to this row: the pair of the quarter that has one
-        m, src = max(((a, n) for a in quarter for n in (a - 1, a + 1) if 0 <= n < s.M), key=lambda p: mag[p[1]] / max(mag[p[0]], 1e-300))
-        m, src = int(m), int(src)
+    # a low-scale channel that has nonzeros and a bias (filters_tail leaves some rows empty) and a high-scale neighbour
+    m, src = eb.corruption_target(want, sk.w, sk.b)
+    mag = eb.low_channels(want)[1]
     assert mag[src] >= 2.0 ** 20 * mag[m], (mag[m], mag[src])
     bad = {"bias dropped": eb.drop_bias(out, sk.b, m), "2^-30 of row %d" % src: eb.leak_from(out, m, src),
            "images 0 and 1 swapped": eb.swap_images(out, m)}

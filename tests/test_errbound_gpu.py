@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import errbound as eb
+from layout_cases import GK_VARIANT, N_CU, dense_variant
 from test_body_variant_gpu import CASES as BODY_CASES
 from upd_common import new_weights, values_at
 from wgrad_common import csr_positions, make_shape, seeded
@@ -53,7 +54,11 @@ def _ref(s, sk, bias, relu, f64=False):
     """The float64 forward and its bound for a skewed layer, computed once per (layer, bias, relu, dtype)."""
     key = (s.name, id(sk), bias, relu, f64)
     if key not in _REFS:
-        _REFS[key] = eb.forward_bound(s, sk.w, sk.x, sk.b if bias else None, relu=relu, f64=f64)
+        if relu:        # forward_bound's own rule: ReLU is 1-Lipschitz, max(want, 0) keeps the bound
+            want, B = _ref(s, sk, bias, False, f64)
+            _REFS[key] = (np.maximum(want, 0.0), B)
+        else:
+            _REFS[key] = eb.forward_bound(s, sk.w, sk.x, sk.b if bias else None, f64=f64)
     return _REFS[key]
 
 
@@ -70,9 +75,9 @@ def _expect(pkg, kernel, name):
         assert name == "escoin_dense_mfma_kernel", name
 
 
-def _forward_cases(pkg, dev, s, sk, kernel, combos, partial=0, f64=False, check_name=None, **opts):
+def _forward_cases(pkg, dev, s, sk, kernel, combos, partial=0, f64=False, check_name=None, worst=None, **opts):
     """One plan per ReLU setting of `combos` ((bias, relu) pairs), forwards with and without bias, every element within
-    the bound; yields each plan after its forwards, for the caller's stat assertions."""
+    the bound; yields each plan after its forwards, for the caller's stat assertions.  `worst`: errbound.within's."""
     dt = np.float64 if f64 else np.float32
     xd, bd = _up(sk.x, dev, dt), _up(sk.b, dev, dt)
     for relu in sorted(set(r for _, r in combos)):
@@ -84,13 +89,14 @@ def _forward_cases(pkg, dev, s, sk, kernel, combos, partial=0, f64=False, check_
             got = plan.forward(xd, bd if bias else None)
             torch.cuda.synchronize()
             want, B = _ref(s, sk, bias, relu, f64)
-            r = eb.within(got.cpu().numpy(), want, B, name, sk.row_exp, what=(s.name, "bias", bias, "relu", relu, opts))
+            r = eb.within(got.cpu().numpy(), want, B, name, sk.row_exp, what=(s.name, "bias", bias, "relu", relu, opts), worst=worst)
             print("errbound forward %-44s %-8s bias=%d relu=%d %s: %.3g" % (name, s.name, bias, relu, opts, r))
             if partial and bias:      # the first images of the plan's batch, into the head of a full top blob
                 top = torch.full_like(got, -7.5)
                 plan.forward(xd[:partial], bd, top[:partial])
                 torch.cuda.synchronize()
-                eb.within(top[:partial].cpu().numpy(), want[:partial], B[:partial], name, sk.row_exp, what=(s.name, "first images", partial, opts))
+                eb.within(top[:partial].cpu().numpy(), want[:partial], B[:partial], name, sk.row_exp, what=(s.name, "first images", partial, opts),
+                          worst=worst)
                 assert bool((top[partial:] == -7.5).all()), (name, "images past the call's were written")
         yield plan
         plan.close()
@@ -170,6 +176,10 @@ def test_forward_dense_stream_k_fixup(pkg, synth, dev):
     s, sk, _ = _layer(synth, GK)
     for plan in _forward_cases(pkg, dev, s, sk, pkg.KERNEL_DENSE, [(True, True)]):
         assert plan.stat("streamk") == 1 and plan.stat("streamk_gave_up") == 0
+        # 128-row tiles, gathered operand and scalar stores (49 pixels), K split: the variant launch_dense's rule gives
+        n_cu = torch.cuda.get_device_properties(0).multi_processor_count
+        assert plan.stat("dense_variant") == dense_variant(s, s.N, n_cu) and (n_cu != N_CU or plan.stat("dense_variant") == GK_VARIANT)
+        print("    dense_variant %d" % plan.stat("dense_variant"))
 
 
 def test_forward_lowered_sparse(pkg, synth, dev):

@@ -169,6 +169,30 @@ def low_channels(want):
     return np.argsort(mag, kind="stable"), mag
 
 
+def corruption_target(want, w, b, gap=2.0 ** 20):
+    """(m, src): the channel the self-check corrupts and the neighbour it leaks from.  m is the lowest-magnitude channel
+    of the lowest quarter that has nonzeros and a bias, src its neighbour (m - 1 or m + 1: rows that share a wave or a
+    quad are adjacent) of the larger magnitude.  Where that neighbour is not `gap` times larger, the pair of the quarter
+    with the largest gap -- again among channels with nonzeros and a bias only: an empty row's channel holds its bias on
+    every image (swapping two of them changes nothing), and a rule that takes the largest gap alone lands on such rows at
+    95 % sparsity.  If the quarter has no such channel, the lowest one that has is taken from the rest."""
+    order, mag = low_channels(want)
+    M = len(order)
+    nnz = row_nnz(w)
+    live = [int(m) for m in order if nnz[m] > 0 and b is not None and b[m] != 0]
+    assert live, "no output channel has both nonzeros and a bias"
+    quarter = set(int(m) for m in order[:max(1, M // 4)])
+    cand = [m for m in live if m in quarter] or live[:1]
+
+    def pairs(ms):
+        return [(m, n) for m in ms for n in (m - 1, m + 1) if 0 <= n < M]
+
+    m, src = max(pairs(cand[:1]), key=lambda p: mag[p[1]])
+    if mag[src] < gap * mag[m]:
+        m, src = max(pairs(cand), key=lambda p: mag[p[1]] / max(mag[p[0]], 1e-300))
+    return int(m), int(src)
+
+
 def drop_bias(out, b, m):
     c = out.copy()
     c[:, m] = (c[:, m].astype(np.float64) - float(b[m])).astype(out.dtype)
