@@ -334,8 +334,10 @@ def main():
     # ESC_EPI3_<tile>_<g>: 3x3 / pad 1 epilogue of output channel g of a tile, in place on the
     # accumulators: out[e] = C[e] + L[e-1] + R[e+1] (L, C, R = the kc = 0, 1, 2 classes); the two
     # elements that live in the neighbouring quad come through DPP row_shr/row_shl with
-    # bound_ctrl (0 at the row edge).  %4..%7 are per-lane 0/1 masks applied first when the
-    # MASKED variant is used (columns >= W hold garbage when W is not a multiple of 4).
+    # bound_ctrl (0 at the row edge).  %4..%7 are per-lane bit masks (0 or ~0) ANDed in first when
+    # the MASKED variant is used (columns >= W hold garbage when W is not a multiple of 4).  A
+    # select, not a multiplication: the garbage is a neighbouring row's data, and 0 x NaN or
+    # 0 x inf would carry a non-finite bottom element into outputs that no nonzero reads it for.
     for tile, base in ((0, ACC_A), (1, ACC_B)):
         for g in range(NACC_TILE // 12):
             L0 = base + 12 * g
@@ -346,7 +348,7 @@ def main():
                 if masked:
                     for cls in (L0, C0, R0):
                         for e in range(4):
-                            lines.append("v_mul_f32 v%d, v%d, %%%d" % (cls + e, cls + e, 4 + e))
+                            lines.append("v_and_b32 v%d, v%d, %%%d" % (cls + e, cls + e, 4 + e))
                 lines += [
                     "v_add_f32 v%d, v%d, v%d" % (C0 + 0, C0 + 0, R0 + 1),
                     "v_add_f32 v%d, v%d, v%d" % (C0 + 1, C0 + 1, L0 + 0),
@@ -371,8 +373,9 @@ def main():
     # r != 0 the lanes in %[okp] own the row's last, partial quad: they store r elements, and the
     # two class values of theirs that a STORED output takes from beyond the row (kc = 2 at column
     # OW for their own last output, kc = 0 at the quad's last column for the first output of the
-    # row that follows in the lane order: neighbouring rows' data, not padding) are multiplied by
-    # %[pm] (0 in those lanes, 1 elsewhere) first.  %[voff] = the lane's byte offset from %[base] (channel m0 of
+    # row that follows in the lane order: neighbouring rows' data, not padding) are ANDed with
+    # %[pm] (the bit mask 0 in those lanes, ~0 elsewhere) first -- a select: multiplying by 0 would
+    # turn a NaN or an infinity of the neighbouring row into a NaN here.  %[voff] = the lane's byte offset from %[base] (channel m0 of
     # the wave), %[bias] lane g = bias of channel m0 + g, %[gcount] = channels of this wave
     # (1..8).  s[32:37] scratch.
     for tile, base in ((0, ACC_A), (1, ACC_B)):
@@ -384,8 +387,8 @@ def main():
                 C0 = L0 + 4
                 R0 = L0 + 8
                 if r:
-                    lines.append("v_mul_f32 v%d, v%d, %%[pm]" % (R0 + r, R0 + r))
-                    lines.append("v_mul_f32 v%d, v%d, %%[pm]" % (L0 + 3, L0 + 3))
+                    lines.append("v_and_b32 v%d, v%d, %%[pm]" % (R0 + r, R0 + r))
+                    lines.append("v_and_b32 v%d, v%d, %%[pm]" % (L0 + 3, L0 + 3))
                 lines += [
                     "v_add_f32 v%d, v%d, v%d" % (C0 + 0, C0 + 0, R0 + 1),
                     "v_add_f32 v%d, v%d, v%d" % (C0 + 1, C0 + 1, L0 + 0),
@@ -437,7 +440,7 @@ def main():
     # wave): out[e] = sum over kc of class_kc[e + kc - 2], accumulated in place on class 2; positions
     # -2, -1 come from the left neighbour's elements 2, 3 and positions 4, 5 from the right
     # neighbour's 0, 1 through DPP.  In the lanes of a row's partial last quad (r != 0) every class
-    # value at an element >= r is multiplied by %[pm] = 0 first (they hold a neighbouring row's
+    # value at an element >= r is ANDed with %[pm] = 0 first (they hold a neighbouring row's
     # data, and stored outputs two columns away reach them).
     for tile, base in ((0, ACC_A), (1, ACC_B)):
         for r in range(4):
@@ -449,7 +452,7 @@ def main():
                 if r:
                     for kc in (0, 1, 3, 4):
                         for e in range(r, 4):
-                            lines.append("v_mul_f32 v%d, v%d, %%[pm]" % (cls[kc] + e, cls[kc] + e))
+                            lines.append("v_and_b32 v%d, v%d, %%[pm]" % (cls[kc] + e, cls[kc] + e))
                 for e in range(4):
                     for kc in (0, 1, 3, 4):
                         pos = e + kc - 2

@@ -356,7 +356,18 @@ ESCOIN_API const char *escoin_plan_tiling_info(const escoin_plan *plan);
  *   top[n][oc] = sconv(bottom[n], CSR)[oc] (+ bias[oc]) (then ReLU if fuse_relu)
  * bottom: n_images x C x H x W, top: n_images x M x OH x OW, bias: M floats or NULL.
  * bias may be NULL even when has_bias was set (the reference dereferences blobs_[1]
- * unconditionally, base_conv_layer.cpp:648 -- not copied).  n_images <= desc.N. */
+ * unconditionally, base_conv_layer.cpp:648 -- not copied).  n_images <= desc.N.
+ * Non-finite input: the sparse kernels (generic, LDS stream, DMA stream, generated code, csrmm, and the sparse inner
+ * kernels of options "s2d" / "s2b") never multiply by a pruned weight and mask by select, never by multiplication: a NaN
+ * or an infinity in the bottom reaches exactly the top elements that a CSR entry reads it for, an infinity with the sign
+ * of the one entry that reads it; every other element is what it is without it.  The DENSE kernel (KERNEL_DENSE,
+ * LOWERED_GEMM, the dense conv groups of a mixed plan) reads every tap of the element's conv group: pruned positions give
+ * 0 x inf = NaN there.  An element of an image at or past n_images is never read.  Every epilogue's ReLU is
+ * v > 0 ? v : 0 (or max(v, 0), which returns the other operand for a NaN): a NaN and -inf become +0.
+ * Subnormal numbers: bottom elements, weights, the bias and results in the subnormal range are kept -- no kernel of the
+ * forward, the backward or the solver step flushes them to zero (the compiled kernels and the generated code run with
+ * the float denormal mode "preserve"; the matrix-core kernels' A and B operands follow that mode, their accumulators
+ * never flush).  A [top > 0] mask therefore lets the gradient of a positive subnormal top through. */
 ESCOIN_API int escoin_forward(escoin_plan *plan, const float *bottom_dev, const float *bias_dev,
                    float *top_dev, int n_images, void *stream);
 

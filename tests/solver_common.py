@@ -76,6 +76,16 @@ def bits_equal(a, b):
     return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
 
 
+def equal_up_to_nan_payload(a, b):
+    """Same dtype and shape, NaN at the same positions, every other element the same bits (-0.0 != +0.0).  The rule
+    promises one IEEE operation per step, and IEEE leaves a NaN's payload and sign open: bits_equal would compare them."""
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return False
+    na, nb = np.isnan(a), np.isnan(b)
+    bits = np.uint32 if a.dtype == np.float32 else np.uint64
+    return bool(np.array_equal(na, nb) and np.array_equal(a.view(bits)[~na], b.view(bits)[~nb]))
+
+
 def seeded_values(n, seed, dt, zeros=True):
     """n seeded values in (-1, 1); with `zeros` (and n >= 8) a few exactly 0 and one -0.0."""
     rs = np.random.RandomState(seed)
