@@ -64,6 +64,9 @@ API_SYMBOLS = [
     # Space-to-batch (option "s2b")
     "escoin_plan_s2b_pack",
     "escoin_plan_s2b_unpack",
+    # Batch-to-space (option "b2s")
+    "escoin_plan_b2s_pack",
+    "escoin_plan_b2s_unpack",
 ]
 SOLVER_SGD, SOLVER_NESTEROV, SOLVER_ADAM = 0, 1, 2
 REG_NONE, REG_L2, REG_L1 = 0, 1, 2
@@ -86,6 +89,12 @@ class ConvDesc(C.Structure):
         return cls(s.N if N is None else N, s.C, s.H, s.W, s.M, s.KH, s.KW, s.pad_h, s.pad_w,
                    s.stride_h, s.stride_w, s.dil_h, s.dil_w, s.group, int(bool(s.bias)),
                    int(bool(fuse_relu)))
+
+    @classmethod
+    def inner_product(cls, N, K, M, bias=True, relu=False):
+        """An InnerProduct layer of K inputs and M outputs at batch N: N images of K channels and one pixel, a 1x1 kernel
+        (include/escoin.h "Batch-to-space")."""
+        return cls(N, K, 1, 1, M, 1, 1, 0, 0, 1, 1, 1, 1, 1, int(bool(bias)), int(bool(relu)))
 
 
 class SolverDesc(C.Structure):
@@ -246,6 +255,10 @@ def lib():
     L.escoin_plan_s2b_pack.argtypes = [vp, vp, ip, vp]
     L.escoin_plan_s2b_unpack.restype = ip
     L.escoin_plan_s2b_unpack.argtypes = [vp, vp, ip, vp]
+    L.escoin_plan_b2s_pack.restype = ip
+    L.escoin_plan_b2s_pack.argtypes = [vp, vp, vp, vp, ip, ip, vp]
+    L.escoin_plan_b2s_unpack.restype = ip
+    L.escoin_plan_b2s_unpack.argtypes = [vp, vp, vp, ip, ip, ip, vp]
     L.escoin_forward.restype = ip
     L.escoin_forward.argtypes = [vp, vp, vp, vp, ip, vp]
     L.escoin_plan_export_aligned.restype = ip
@@ -785,6 +798,37 @@ class Plan(object):
         assert tuple(top.shape[1:]) == (d.M,) + tuple(self.out_hw), "top shape mismatch"
         stream = C.c_void_p(torch.cuda.current_stream(top.device).cuda_stream)
         check(lib().escoin_plan_s2b_unpack(self._h, C.c_void_p(top.data_ptr()), int(top.shape[0]), stream), "escoin_plan_s2b_unpack")
+
+    def b2s_pack(self, src, dst, mask=None, top_side=False, n_images=None):
+        """One transpose of a "b2s" plan alone, on the caller's tensors and torch's current stream: src (N x CH, CH = M on
+        the top side, C on the bottom side; gated by mask > 0 where mask is given) into dst, the ceil(n_images / B) x CH x B
+        inner blob (at least that many elements; the rest of dst is left alone)."""
+        import torch
+        for t in (src, dst) + (() if mask is None else (mask,)):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        n = int(src.shape[0]) if n_images is None else int(n_images)
+        ch = self.desc.M if top_side else self.desc.C
+        blk = self.stat("b2s_block")
+        assert src.numel() >= n * ch and (mask is None or mask.numel() >= n * ch), "src / mask too small"
+        assert blk <= 0 or dst.numel() >= -(-n // blk) * ch * blk, "dst too small"
+        stream = C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+        check(lib().escoin_plan_b2s_pack(self._h, C.c_void_p(src.data_ptr()), None if mask is None else C.c_void_p(mask.data_ptr()),
+                                         C.c_void_p(dst.data_ptr()), int(bool(top_side)), n, stream), "escoin_plan_b2s_pack")
+
+    def b2s_unpack(self, src, dst, top_side=False, relu=False, n_images=None):
+        """The reverse transpose of a "b2s" plan alone: src, an inner blob as b2s_pack writes it, into the first n_images
+        rows of dst (N x CH), through ReLU if asked."""
+        import torch
+        for t in (src, dst):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        n = int(dst.shape[0]) if n_images is None else int(n_images)
+        ch = self.desc.M if top_side else self.desc.C
+        blk = self.stat("b2s_block")
+        assert dst.numel() >= n * ch, "dst too small"
+        assert blk <= 0 or src.numel() >= -(-n // blk) * ch * blk, "src too small"
+        stream = C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+        check(lib().escoin_plan_b2s_unpack(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), int(bool(top_side)),
+                                           int(bool(relu)), n, stream), "escoin_plan_b2s_unpack")
 
     def forward(self, bottom, bias=None, top=None):
         """Forward_gpu on torch CUDA tensors (float32, or float64 for a double plan), on torch's current stream."""

@@ -11,6 +11,7 @@
 //   caffe::BaseConvolutionLayer  include/caffe/layers/base_conv_layer.hpp:20-202
 //   caffe::ConvolutionLayer      include/caffe/layers/conv_layer.hpp:30-80, conv_layer.cu:8-40
 //   caffe::ConvolutionReLULayer  include/caffe/layers/conv_relu_layer.hpp, conv_relu_layer.cu:8-30
+//   caffe::InnerProductLayer     include/caffe/layers/inner_product_layer.hpp, inner_product_layer.cpp / .cu
 //
 // Backward_gpu / Backward_cpu (conv_layer.cu:42-73, conv_layer.cpp:65-99) call the library's pattern-preserving
 // backward (escoin_backward[_cpu], include/escoin.h): gradients flow through the CSR's nonzeros only and the weight
@@ -107,10 +108,13 @@ class Caffe {
   // the same for dilated stride-1 layers via space-to-batch (include/escoin.h option "s2b")
   static bool s2b() { return Get().s2b_; }
   static void set_s2b(bool on) { Get().s2b_ = on; }
+  // the same for inner-product layers (one pixel, a 1x1 kernel) via batch-to-space (include/escoin.h option "b2s")
+  static bool b2s() { return Get().b2s_; }
+  static void set_b2s(bool on) { Get().b2s_ = on; }
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
@@ -118,6 +122,7 @@ class Caffe {
   int backward_kernel_;
   bool s2d_;
   bool s2b_;
+  bool b2s_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -271,9 +276,17 @@ struct ConvolutionParameter {
   int dilation = 1;
   int group = 1;
 };
+// caffe.proto InnerProductParameter as a POD
+struct InnerProductParameter {
+  int num_output = 0;
+  bool bias_term = true;
+  int axis = 1;             // the first axis of the inner product: K = count from it
+  bool transpose = false;   // not supported: InnerProductLayer aborts
+};
 struct LayerParameter {
   string name, type;
   ConvolutionParameter convolution_param;
+  InnerProductParameter inner_product_param;
 };
 
 template <typename Dtype>
@@ -413,6 +426,12 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
     for (size_t i = 0; i < top.size(); ++i) top[i]->Reshape(num_, num_output_, oh, ow);
     bottom_dim_ = bottom[0]->count(1, 4);
     top_dim_ = top[0]->count(1, 4);
+    plan_for(d);
+  }
+
+ protected:
+  // The plan of descriptor d: the one the layer has where only the batch shrank, a fresh one otherwise.
+  void plan_for(const escoin_conv_desc &d) {
     escoin_conv_desc same_but_n = d;
     same_but_n.N = plan_ ? desc_.N : d.N;
     const bool reusable = plan_ && d.N <= desc_.N && memcmp(&same_but_n, &desc_, sizeof(d)) == 0;
@@ -427,6 +446,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "backward_kernel", Caffe::backward_kernel()));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2d", Caffe::s2d() ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2b", Caffe::s2b() ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "b2s", Caffe::b2s() ? 1 : 0));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;
@@ -436,6 +456,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
     }
   }
 
+ public:
   // base_conv_layer.cpp:46-273: dense blobs_[0] -> CSR (+ the device weight streams), once
   virtual void WeightAlign() {
     ESC_CHECK(plan_ != nullptr);   // SetUp must have run
@@ -823,8 +844,67 @@ class ConvolutionReLULayer : public ConvolutionLayer<Dtype> {   // conv_relu_lay
   virtual inline const char *type() const { return "ConvolutionReLU"; }
 };
 
+// inner_product_layer.hpp / .cpp / .cu: top = bottom (M_ x K_) * blobs_[0]^T (N_ x K_) + bias.  The layer is the 1x1
+// convolution of M_ images of K_ channels and one pixel (include/escoin.h "Batch-to-space"), so it IS a ConvolutionLayer
+// with another SetUp and Reshape: WeightAlign, Forward / Backward in both brews, WeightUpdate, SolverUpdate, Prune, Rewire,
+// DenseWeightDiff and the persisted form are the convolution layer's code on the same C entry points.  With
+// Caffe::set_b2s(true) a float layer in GPU mode runs on the pointwise kernels with the batch as the pixel axis; double
+// and CPU mode run through the unchanged paths.  transpose = true (blobs_[0] as K_ x N_) aborts.
+template <typename Dtype>
+class InnerProductLayer : public ConvolutionLayer<Dtype> {
+ public:
+  explicit InnerProductLayer(const LayerParameter &param) : ConvolutionLayer<Dtype>(param), K_(0) {}
+  virtual inline const char *type() const { return "InnerProduct"; }
+
+  // inner_product_layer.cpp LayerSetUp: K_ is the count from `axis`; blobs_[0] is num_output x K_, blobs_[1] num_output
+  virtual void LayerSetUp(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &) {
+    const InnerProductParameter &ip = this->layer_param_.inner_product_param;
+    if (ip.transpose) {
+      fprintf(stderr, "InnerProductLayer %s: inner_product_param.transpose = true is not supported\n", this->layer_param_.name.c_str());
+      abort();
+    }
+    ESC_CHECK(ip.num_output > 0);
+    axis_ = canonical_axis(bottom[0], ip.axis);
+    K_ = bottom[0]->count(axis_, bottom[0]->num_axes());
+    ESC_CHECK(K_ > 0);
+    this->channels_ = K_;
+    this->num_output_ = ip.num_output;
+    this->group_ = 1;
+    this->bias_term_ = ip.bias_term;
+    this->blobs_.resize(this->bias_term_ ? 2 : 1);
+    vector<int> wshape(2);
+    wshape[0] = this->num_output_; wshape[1] = K_;
+    this->blobs_[0].reset(new Blob<Dtype>(wshape));
+    if (this->bias_term_) this->blobs_[1].reset(new Blob<Dtype>(vector<int>(1, this->num_output_)));
+    this->param_propagate_down_.resize(this->blobs_.size(), true);
+  }
+
+  // inner_product_layer.cpp Reshape: M_ = the count before `axis`; the top is the bottom's axes before `axis`, then num_output
+  virtual void Reshape(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &top) {
+    ESC_CHECK(bottom[0]->count(axis_, bottom[0]->num_axes()) == K_);     // "Input size incompatible with inner product parameters."
+    this->num_ = bottom[0]->count(0, axis_);
+    vector<int> tshape(bottom[0]->shape().begin(), bottom[0]->shape().begin() + axis_);
+    tshape.push_back(this->num_output_);
+    for (size_t i = 0; i < top.size(); ++i) top[i]->Reshape(tshape);
+    this->bottom_dim_ = K_;
+    this->top_dim_ = this->num_output_;
+    escoin_conv_desc d;
+    d.N = this->num_; d.C = K_; d.H = 1; d.W = 1; d.M = this->num_output_; d.KH = 1; d.KW = 1;
+    d.pad_h = 0; d.pad_w = 0; d.stride_h = 1; d.stride_w = 1; d.dil_h = 1; d.dil_w = 1; d.group = 1;
+    d.has_bias = this->bias_term_ ? 1 : 0; d.fuse_relu = 0;
+    this->plan_for(d);
+  }
+
+ private:
+  static int canonical_axis(const Blob<Dtype> *b, int axis) {     // blob.hpp CanonicalAxisIndex
+    ESC_CHECK(axis >= -b->num_axes() && axis < b->num_axes());
+    return axis < 0 ? axis + b->num_axes() : axis;
+  }
+  int K_, axis_ = 1;
+};
+
 // layer_factory.hpp:53-110 / layer_factory.cpp:74: the creator registry `Net::Init` looks layer
-// types up in (LayerRegistry<Dtype>::CreateLayer(param)), with the two creators this path owns.
+// types up in (LayerRegistry<Dtype>::CreateLayer(param)), with the three creators this path owns.
 template <typename Dtype>
 class LayerRegistry {
  public:
@@ -832,13 +912,15 @@ class LayerRegistry {
   static shared_ptr<Layer<Dtype> > CreateLayer(const LayerParameter &param) {
     if (param.type == "Convolution") return shared_ptr<Layer<Dtype> >(new ConvolutionLayer<Dtype>(param));
     if (param.type == "ConvolutionReLU") return shared_ptr<Layer<Dtype> >(new ConvolutionReLULayer<Dtype>(param));
-    fprintf(stderr, "Unknown layer type: %s (known types: Convolution, ConvolutionReLU)\n", param.type.c_str());
+    if (param.type == "InnerProduct") return shared_ptr<Layer<Dtype> >(new InnerProductLayer<Dtype>(param));
+    fprintf(stderr, "Unknown layer type: %s (known types: Convolution, ConvolutionReLU, InnerProduct)\n", param.type.c_str());
     abort();   // LOG(FATAL), layer_factory.hpp:79-80
   }
   static vector<string> LayerTypeList() {
     vector<string> v;
     v.push_back("Convolution");
     v.push_back("ConvolutionReLU");
+    v.push_back("InnerProduct");
     return v;
   }
 };

@@ -28,6 +28,10 @@ import struct
 import numpy as np
 
 V1_CONVOLUTION = 4
+V1_INNER_PRODUCT = 14
+# InnerProduct layers: LayerParameter.inner_product_param = 117, V1LayerParameter.inner_product_param = 17;
+# InnerProductParameter num_output 1, bias_term 2, axis 5 (default 1), transpose 6 (default false).  blobs_[0] is
+# num_output x K; files written before BlobShape carry it as the legacy 1 x 1 x num_output x K.
 
 
 # ---- wire format ---------------------------------------------------------------------------
@@ -177,19 +181,72 @@ def _parse_conv_param(buf):
                 dilation_h=dh, dilation_w=dw)
 
 
-class CaffeLayer(object):
-    """One layer of a .caffemodel: name, type string, blobs (numpy float32) and, for
-    convolutions, the decoded ConvolutionParameter."""
+def _parse_ip_param(buf):
+    one = {fno: v for fno, wt, v in _fields(buf) if wt == 0}
+    axis = one.get(5, 1)
+    if axis >= 1 << 31:                 # (int32 on the wire: a negative axis arrives sign-extended to 64 bits)
+        axis -= 1 << 64
+    return dict(num_output=one.get(1, 0), bias_term=bool(one.get(2, 1)), axis=axis, transpose=bool(one.get(6, 0)))
 
-    def __init__(self, name, type_, blobs, conv_param=None):
+
+class CaffeLayer(object):
+    """One layer of a .caffemodel: name, type string, blobs (numpy float32) and the decoded
+    ConvolutionParameter (convolutions) or InnerProductParameter (inner products)."""
+
+    def __init__(self, name, type_, blobs, conv_param=None, ip_param=None):
         self.name = name
         self.type = type_
         self.blobs = blobs
         self.conv_param = conv_param
+        self.ip_param = ip_param
 
     @property
     def is_convolution(self):
         return self.type in ("Convolution", "ConvolutionReLU", V1_CONVOLUTION)
+
+    @property
+    def is_inner_product(self):
+        return self.type in ("InnerProduct", V1_INNER_PRODUCT)
+
+    def _ip_weight(self):
+        if not self.is_inner_product or not self.blobs:
+            raise ValueError("layer %s is no InnerProduct layer with blobs" % self.name)
+        w = self.blobs[0]
+        if w.ndim == 4 and w.shape[:2] == (1, 1):      # the legacy 1 x 1 x M x K
+            w = w.reshape(w.shape[2:])
+        if w.ndim != 2:
+            raise ValueError("layer %s: InnerProduct weight blob has shape %s" % (self.name, self.blobs[0].shape))
+        if self.ip_param and self.ip_param["transpose"]:
+            raise ValueError("layer %s: InnerProduct transpose = true is not supported" % self.name)
+        if self.ip_param and self.ip_param["num_output"] not in (0, w.shape[0]):
+            raise ValueError("layer %s: num_output %d, weight blob %s" % (self.name, self.ip_param["num_output"], w.shape))
+        return w
+
+    @property
+    def num_output(self):
+        """M of an InnerProduct layer (the weight blob's rows)."""
+        return int(self._ip_weight().shape[0])
+
+    @property
+    def K(self):
+        """Inputs per image of an InnerProduct layer (the weight blob's columns)."""
+        return int(self._ip_weight().shape[1])
+
+    @property
+    def ip_weight(self):
+        """blobs_[0] of an InnerProduct layer as num_output x K, whichever blob shape the file used."""
+        return self._ip_weight()
+
+    @property
+    def ip_bias(self):
+        """blobs_[1] of an InnerProduct layer as a vector, or None (bias_term = false)."""
+        self._ip_weight()
+        return self.blobs[1].reshape(-1) if len(self.blobs) > 1 else None
+
+    def ip_desc(self, N, relu=False):
+        """The 16 ints of escoin_conv_desc for this InnerProduct layer at batch N, in ConvDesc's field order: N images
+        of K channels and one pixel, a 1x1 kernel (ConvDesc(*layer.ip_desc(N)); ConvDesc.inner_product builds the same)."""
+        return (int(N), self.K, 1, 1, self.num_output, 1, 1, 0, 0, 1, 1, 1, 1, 1, int(self.ip_bias is not None), int(bool(relu)))
 
     def __repr__(self):
         return "CaffeLayer(%r, %r, blobs=%s)" % (self.name, self.type, [b.shape for b in self.blobs])
@@ -197,7 +254,8 @@ class CaffeLayer(object):
 
 def _parse_layer(buf, v1):
     f_name, f_type, f_blobs, f_conv = (4, 5, 6, 10) if v1 else (1, 2, 7, 106)
-    name, type_, blobs, conv = "", None, [], None
+    f_ip = 17 if v1 else 117
+    name, type_, blobs, conv, ip = "", None, [], None, None
     for fno, wt, v in _fields(buf):
         if fno == f_name and wt == 2:
             name = bytes(v).decode("utf-8")
@@ -207,7 +265,9 @@ def _parse_layer(buf, v1):
             blobs.append(_parse_blob(v))
         elif fno == f_conv and wt == 2:
             conv = _parse_conv_param(v)
-    return CaffeLayer(name, type_, blobs, conv)
+        elif fno == f_ip and wt == 2:
+            ip = _parse_ip_param(v)
+    return CaffeLayer(name, type_, blobs, conv, ip)
 
 
 def parse_net(buf):
@@ -243,6 +303,11 @@ def conv_weights(layers):
     return out
 
 
+def inner_product_weights(layers):
+    """{layer name: (weight num_output x K, bias or None)} for the InnerProduct layers that carry blobs."""
+    return {l.name: (l.ip_weight, l.ip_bias) for l in layers if l.is_inner_product and l.blobs}
+
+
 # ---- writer (tests / synthetic exports) ------------------------------------------------------
 def _enc_blob(a, legacy_dims=False):
     a = np.ascontiguousarray(a, dtype="<f4")
@@ -269,6 +334,15 @@ def _enc_conv_param(p):
     return out
 
 
+def _enc_ip_param(p):
+    out = _enc_uint(1, p["num_output"]) + _enc_uint(2, int(p.get("bias_term", True)))
+    if p.get("axis", 1) != 1:
+        out += _enc_uint(5, p["axis"])
+    if p.get("transpose", False):
+        out += _enc_uint(6, 1)
+    return out
+
+
 def serialize_net(name, layers, v1=False):
     """layers: iterable of CaffeLayer.  v1=True writes the deprecated V1LayerParameter form
     (with 4-D legacy blob dims), which old pruned model zoo files still use."""
@@ -276,11 +350,13 @@ def serialize_net(name, layers, v1=False):
     for l in layers:
         if v1:
             body = _enc_len(4, l.name.encode("utf-8"))
-            body += _enc_uint(5, V1_CONVOLUTION if l.is_convolution else 0)
+            body += _enc_uint(5, V1_CONVOLUTION if l.is_convolution else V1_INNER_PRODUCT if l.is_inner_product else 0)
             for b in l.blobs:
                 body += _enc_len(6, _enc_blob(b, legacy_dims=True))
             if l.conv_param:
                 body += _enc_len(10, _enc_conv_param(l.conv_param))
+            if l.ip_param:
+                body += _enc_len(17, _enc_ip_param(l.ip_param))
             out += _enc_len(2, body)
         else:
             body = _enc_len(1, l.name.encode("utf-8")) + _enc_len(2, str(l.type).encode("utf-8"))
@@ -288,6 +364,8 @@ def serialize_net(name, layers, v1=False):
                 body += _enc_len(7, _enc_blob(b))
             if l.conv_param:
                 body += _enc_len(106, _enc_conv_param(l.conv_param))
+            if l.ip_param:
+                body += _enc_len(117, _enc_ip_param(l.ip_param))
             out += _enc_len(100, body)
     return out
 

@@ -679,4 +679,36 @@ bool s2b_plan(const Geometry &g, bool is_f64, S2bPlan *sp) {
   return true;
 }
 
+bool b2s_plan(const Geometry &g, bool is_f64, int block, int /*n_cu*/, B2sPlan *bp) {
+  const escoin_conv_desc &d = g.d;
+  if (is_f64) return false;
+  if (d.H != 1 || d.W != 1 || d.KH != 1 || d.KW != 1 || d.pad_h != 0 || d.pad_w != 0) return false;
+  auto inner_images = [&d](int B) { return ((long)d.N + B - 1) / B; };
+  int B = block;
+  if (B == 0) {
+    B = 64;
+    while (B < kB2sMaxBlock && inner_images(B) > kS2bMaxInnerImages) B *= 2;      // (a batch above 4 million)
+  }
+  if (B < kB2sMinBlock || B > kB2sMaxBlock || B % 4 != 0) return false;
+  const long np = inner_images(B);
+  if (np > kS2bMaxInnerImages) return false;
+  const double two31 = 2147483648.0;
+  const double x_floats = (double)np * d.C * B, t_floats = (double)np * d.M * B;
+  if (x_floats >= two31 || t_floats >= two31) return false;      // (the bottom N * C and the top N * M are no larger)
+  B2sPlan p;
+  p.B = B;
+  escoin_conv_desc &in = p.inner;
+  in = d;
+  in.N = (int)np;
+  in.H = 1;
+  in.W = B;
+  in.stride_h = in.stride_w = 1;
+  in.dil_h = in.dil_w = 1;
+  in.fuse_relu = 0;                  // (the unpack kernel applies the outer plan's ReLU)
+  p.x_floats = (long)x_floats;
+  p.t_floats = (long)t_floats;
+  *bp = p;
+  return true;
+}
+
 }  // namespace escoin

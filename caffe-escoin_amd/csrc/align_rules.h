@@ -293,5 +293,26 @@ constexpr long kS2bMaxInnerImages = 65535;
 // N * P is at most kS2bMaxInnerImages.
 bool s2b_plan(const Geometry &g, bool is_f64, S2bPlan *sp);
 
+// ---- inner-product layers on the pointwise kernels via batch-to-space (b2s.hip, plan option "b2s") ------------------
+// An inner product is a 1x1 convolution of N images of one pixel; with the batch as the pixel axis it is a pointwise layer
+// of N' = ceil(N / B) images of 1 x B pixels (include/escoin.h "Batch-to-space"): X'[n'][c][j] = bottom[n' * B + j][c], +0
+// past the batch; pad 0, stride 1, dilation 1, no ReLU; the CSR is the outer one.
+struct B2sPlan {
+  int B = 0;                      // batch positions per inner image: a multiple of 4 in 4..256
+  escoin_conv_desc inner = {};    // the inner plan's descriptor (N' = ceil(N / B) images of 1 x B)
+  long x_floats = 0;              // N' * C * B: the transposed bottom X' (and, in a scratch of its own, its gradient dX')
+  long t_floats = 0;              // N' * M * B: the inner top T' (and the transposed top_diff G')
+};
+constexpr int kB2sMinBlock = 4, kB2sMaxBlock = 256;
+// Whether option "b2s" serves this plan, and the block and the inner descriptor where it does: float plans with H = W = 1,
+// KH = KW = 1 and pad 0 (with one pixel and one tap, stride and dilation are immaterial), whose bottom, top, X' and T' each
+// stay below 2^31 elements (the pack / unpack kernels' 32-bit offsets) and whose N' is at most kS2bMaxInnerImages.
+// `block` forces B (option "b2s_block": a multiple of 4 in 4..256, which the caller has checked); 0 is the rule: B = 64,
+// the block that won or tied the sweep {64, 128, 256} on every benched layer at batch 256 and 32 (profiles/b2s_mi355x.md:
+// of the three it pads the batch least and gives the most inner images, so the most workgroups; at batch 32 a row of 64
+// half full beat a full row of 32) -- and where 64 gives more than kS2bMaxInnerImages, the smaller of 128 and 256 that
+// does not.  n_cu is the device's compute units, which the shipped rule does not weigh.
+bool b2s_plan(const Geometry &g, bool is_f64, int block, int n_cu, B2sPlan *bp);
+
 }  // namespace escoin
 #endif  // ESCOIN_ALIGN_RULES_H_

@@ -124,6 +124,17 @@ static int dense_wgrad_gpu(escoin_plan *p, const float *bottom, const float *top
   if (d.fuse_relu && !top) return fail(ESCOIN_EINVAL, "dense_wgrad: a fuse_relu plan needs the forward's top");
   if (const int rc = check_n_images(p, n_images)) return rc;
   hipStream_t stream = (hipStream_t)stream_v;
+  // option "b2s": the inner plan's own dense weight gradient on (X', G') -- M x Cg on both plans; the padding positions are
+  // +0 in both operands and add exact zeros.  The state and "dwg_count" are the inner plan's and this plan's.
+  if (B2sState *bs = p->b2s_state.get()) {
+    ++p->dwg_count;
+    const int n_inner = (n_images + bs->bp.B - 1) / bs->bp.B;
+    int rc = g_b2s_hooks.pack(p, bottom, nullptr, bs->x.get<float>(), false, n_images, stream);
+    if (rc == ESCOIN_OK) rc = g_b2s_hooks.pack(p, top_diff, d.fuse_relu ? top : nullptr, bs->t.get<float>(), true, n_images, stream);
+    if (rc != ESCOIN_OK) return rc;
+    return escoin_dense_wgrad(bs->inner.plan.get(), bs->x.get<const float>(), nullptr, bs->t.get<const float>(), dense_diff, n_inner,
+                              accumulate, stream_v);
+  }
   if (!p->dwg || p->dwg->device != p->device) {
     const int rc = dwg_build(p, stream);
     if (rc != ESCOIN_OK) {

@@ -20,6 +20,7 @@ static thread_local std::string g_last_error;
 
 S2dHooks g_s2d_hooks = {nullptr, nullptr, nullptr};
 S2bHooks g_s2b_hooks = {nullptr, nullptr, nullptr, nullptr};
+B2sHooks g_b2s_hooks = {nullptr, nullptr, nullptr, nullptr};
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 
@@ -98,10 +99,19 @@ DeviceBytes device_bytes(const escoin_plan *p) {
     b.fwd += sb->x.bytes() + sb->t.bytes() + in.fwd;
     b.bwd += in.bwd;
   }
+  if (const B2sState *bs = p->b2s_state.get()) {
+    // the X', T' / G' and dX' scratches and the inner plan's own owners, as for "s2d"
+    const DeviceBytes in = device_bytes(bs->inner.plan.get());
+    b.fwd += bs->x.bytes() + bs->t.bytes() + bs->dx.bytes() + in.fwd;
+    b.bwd += in.bwd;
+    b.dwg += in.dwg;      // (escoin_dense_wgrad runs on the inner plan)
+  }
   return b;
 }
 
 long bwd_stat(const escoin_plan *p, const char *key) {
+  // option "b2s": the whole backward is the inner plan's, and so are its facts -- but for the bytes, which device_bytes sums
+  if (p->b2s_state && strcmp(key, "bwd_device_bytes") != 0) return bwd_stat(p->b2s_state->inner.plan.get(), key);
   const BwdState *s = p->bwd.get();
   if (!strcmp(key, "bwd_data_kernel")) {
     if (!s) return fail(ESCOIN_ESTATE, "bwd_data_kernel: no backward has run on this alignment");
@@ -138,7 +148,8 @@ long upd_stat(const escoin_plan *p, const char *key) {
 }
 
 long dwg_stat(const escoin_plan *p, const char *key) {
-  const DenseWgradState *w = p->dwg.get();
+  // (option "b2s": the state is the inner plan's)
+  const DenseWgradState *w = p->b2s_state ? p->b2s_state->inner.plan->dwg.get() : p->dwg.get();
   if (!strcmp(key, "dwg_device_bytes")) return (long)device_bytes(p).dwg;
   if (!strcmp(key, "dwg_splits")) return w ? w->splits : 0;
   if (!strcmp(key, "dwg_lds_bytes")) return w ? (long)w->lds_bytes : 0;
@@ -153,6 +164,7 @@ static void free_device(escoin_plan *p) {
   p->bwd.reset();
   p->s2d_state.reset();
   p->s2b_state.reset();
+  p->b2s_state.reset();
   p->gen = GenericArrays();
   tiled_release(p);
   p->col.reset();
@@ -172,12 +184,13 @@ static int upload_generic(escoin_plan *p, hipStream_t stream) {
 }
 
 int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, int kernel, int backward_kernel,
-                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out, int tiling_batch) {
+                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out, int tiling_batch, bool wgrad_options) {
   escoin_plan *q = nullptr;
   int rc = escoin_plan_create(&desc, &q);
   out->plan.reset(q);
   if (rc != ESCOIN_OK) return rc;
-  // what a derived plan inherits, and all of it ("body_variant", "stream_stores" and the "wgrad_*" options are not handed down)
+  // what a derived plan inherits, and all of it ("body_variant" and "stream_stores" are not handed down, the "wgrad_*"
+  // options only where the derived plan computes the weight gradient)
   if ((rc = escoin_plan_set_option(q, "kernel", kernel)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "backward_kernel", backward_kernel)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "tiling_batch", tiling_batch < 0 ? owner->tiling_batch : tiling_batch)) != ESCOIN_OK) return rc;
@@ -185,6 +198,10 @@ int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, i
   if ((rc = escoin_plan_set_option(q, "dense_threshold_pct", owner->dense_threshold_pct)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "dense_gate", owner->dense_gate)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "code_loader", owner->code_loader)) != ESCOIN_OK) return rc;
+  if (wgrad_options) {
+    if ((rc = escoin_plan_set_option(q, "wgrad_kernel", owner->wgrad_kernel)) != ESCOIN_OK) return rc;
+    if ((rc = escoin_plan_set_option(q, "wgrad_channel_block", owner->wgrad_channel_block)) != ESCOIN_OK) return rc;
+  }
   const std::vector<float> flat = flat_entries(owner->values);
   std::vector<float> vals(csr.src.size());
   for (size_t k = 0; k < vals.size(); ++k) vals[k] = flat[(size_t)csr.src[k]];
@@ -246,6 +263,37 @@ static int s2b_build(escoin_plan *p, const S2bPlan &sp, hipStream_t stream) {
   return ESCOIN_OK;
 }
 
+// Option "b2s" (include/escoin.h "Batch-to-space"): the inner pointwise plan of ceil(N / B) images of 1 x B with the plan's
+// kernel, backward and weight-gradient options, aligned on the plan's own CSR (the entry map is the identity), and the X',
+// T' / G' and dX' scratches.  The plan itself keeps the generic arrays alone, as under "s2d".
+static int b2s_build(escoin_plan *p, const B2sPlan &bp, hipStream_t stream) {
+  if (!g_b2s_hooks.pack || !g_b2s_hooks.unpack) return fail(ESCOIN_EINVAL, "option \"b2s\": this build does not carry the batch-to-space kernels");
+  p->b2s_state.reset(new B2sState());
+  B2sState *bs = p->b2s_state.get();
+  bs->bp = bp;
+  DerivedCsr csr;
+  for (int grp = 0; grp < p->g.d.group; ++grp) {
+    csr.rowptr.insert(csr.rowptr.end(), p->rowptr[grp].begin(), p->rowptr[grp].end());
+    csr.colidx.insert(csr.colidx.end(), p->colidx[grp].begin(), p->colidx[grp].end());
+    csr.nnz_g.push_back((int)p->colidx[grp].size());
+  }
+  csr.src.resize(csr.colidx.size());
+  for (size_t k = 0; k < csr.src.size(); ++k) csr.src[k] = (int)k;
+  // "tiling_batch" counts outer images: B of them are one inner image
+  const int tb = (int)(((long)p->tiling_batch + bp.B - 1) / bp.B);
+  const int rc = build_derived_plan(p, bp.inner, p->kernel_choice, p->bwd_kernel, std::move(csr), stream, &bs->inner, tb, true);
+  if (rc != ESCOIN_OK) return rc;
+  ESCOIN_HIP_TRY(bs->x.alloc(sizeof(float) * (size_t)bp.x_floats));
+  ESCOIN_HIP_TRY(bs->t.alloc(sizeof(float) * (size_t)bp.t_floats));
+  ESCOIN_HIP_TRY(bs->dx.alloc(sizeof(float) * (size_t)bp.x_floats));
+  p->n_dense_groups = 0; p->n_sparse_groups = p->g.d.group; p->use_dense = false;
+  p->dense_mask = 0; p->sparse_mask = ~0ull; p->small_rule = 0; p->import_fast = false;
+  p->kernel_name = std::string(g_b2s_hooks.pack_kernel_name) + " + " + escoin_plan_kernel_name(bs->inner.plan.get()) + " + " +
+                   g_b2s_hooks.unpack_kernel_name;
+  p->aligned = true;
+  return ESCOIN_OK;
+}
+
 // Uploads the CSR held in p->rowptr/colidx/values and builds the kernel-specific
 // streams.  Shared tail of escoin_weight_align and escoin_plan_set_csr.
 //   jit_blob: the generated-code section of a persisted aligned form (escoin_plan_import_aligned), tried
@@ -269,6 +317,15 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     p->aligned = true;
     return ESCOIN_OK;
   }
+  const bool direct_mode = p->conv_mode == ESCOIN_CONV_MODE_SCONV || p->conv_mode == ESCOIN_CONV_MODE_SCONV_PAR;
+  // option "b2s": an inner-product layer runs through a pointwise inner plan whose pixel axis is the batch.  Asked first: a
+  // one-pixel layer whose descriptor names a stride or a dilation is this option's, whatever "s2d" / "s2b" say
+  B2sPlan b2p;
+  if (p->b2s && direct_mode && b2s_plan(g, false, p->b2s_block, tiled_device_cus(), &b2p)) {
+    const int rc = b2s_build(p, b2p, stream);
+    if (rc != ESCOIN_OK) p->b2s_state.reset();
+    return rc;
+  }
   // option "s2d": the layer runs through a stride-1 inner plan, which alone decides dense or sparse, tiled or generic,
   // on its own geometry (the 4 % rule of dense_groups() for layers without a fast kernel is what the option removes)
   S2dPlan s2p;
@@ -289,7 +346,8 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
   // without the inner plan, and aligns as under KERNEL_AUTO instead of refusing -- a conv_mode flip left such a plan unaligned.
   int kernel = p->kernel_choice;
   if ((kernel == ESCOIN_KERNEL_TILED || kernel == ESCOIN_KERNEL_JIT) && !tiled_supported(g) &&
-      ((p->s2d && s2d_plan(g, false, &s2p)) || (p->s2b && s2b_plan(g, false, &s2bp))))
+      ((p->s2d && s2d_plan(g, false, &s2p)) || (p->s2b && s2b_plan(g, false, &s2bp)) ||
+       (p->b2s && b2s_plan(g, false, p->b2s_block, tiled_device_cus(), &b2p))))
     kernel = ESCOIN_KERNEL_AUTO;
   // which conv groups go to the dense (fp32 MFMA) kernel (align_rules.h)
   const int G = g.d.group;
@@ -544,6 +602,19 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->s2b = value;
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "b2s")) {
+      if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "b2s must be 0 or 1");
+      if (p->aligned || p->host_aligned) return fail(ESCOIN_ESTATE, "b2s must be set before weight_align / weight_align_cpu / set_csr");
+      p->b2s = value;
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "b2s_block")) {
+      if (value != 0 && (value < kB2sMinBlock || value > kB2sMaxBlock || value % 4 != 0))
+        return fail(ESCOIN_EINVAL, "b2s_block must be 0 (the rule) or a multiple of 4 in 4..256");
+      if (p->aligned || p->host_aligned) return fail(ESCOIN_ESTATE, "b2s_block must be set before weight_align / weight_align_cpu / set_csr");
+      p->b2s_block = value;
+      return ESCOIN_OK;
+    }
     if (p->aligned && strcmp(key, "conv_mode") != 0 && strcmp(key, "cpu_channel_block") != 0 && strcmp(key, "cpu_images_per_job") != 0 &&
         strcmp(key, "wgrad_kernel") != 0)
       return fail(ESCOIN_ESTATE, "this option must be set before weight_align/set_csr");
@@ -586,6 +657,8 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
     if (!strcmp(key, "wgrad_kernel")) {
       if (value < ESCOIN_WGRAD_AUTO || value > ESCOIN_WGRAD_MFMA) return fail(ESCOIN_EINVAL, "wgrad_kernel must be 0 (auto), 1 (entry), 2 (staged) or 3 (mfma)");
       p->wgrad_kernel = value;
+      // (option "b2s": the weight gradient is the inner plan's, which reads the option as this plan would)
+      if (p->b2s_state) return escoin_plan_set_option(p->b2s_state->inner.plan.get(), key, value);
       return ESCOIN_OK;
     }
     if (!strcmp(key, "wgrad_channel_block")) {
@@ -618,7 +691,7 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       // (an "s2d" / "s2b" plan also rebuilds between the lowered modes, which run on the original geometry, and SCONV / SCONV_PAR)
       auto direct = [](int m) { return m == ESCOIN_CONV_MODE_SCONV || m == ESCOIN_CONV_MODE_SCONV_PAR; };
       const bool regroup = p->aligned && ((value == ESCOIN_CONV_MODE_LOWERED_GEMM) != (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_GEMM) ||
-                                          ((p->s2d || p->s2b) && !p->is_f64 && direct(value) != direct(p->conv_mode)));
+                                          ((p->s2d || p->s2b || p->b2s) && !p->is_f64 && direct(value) != direct(p->conv_mode)));
       p->conv_mode = value;
       // to or from LOWERED_GEMM on an aligned plan: the dense / sparse device structures are rebuilt
       // from the CSR the plan holds (the other three modes share theirs).  The plan is not aligned
@@ -784,6 +857,10 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "s2d_scratch_bytes")) return p->s2d_state ? (long)p->s2d_state->x.bytes() : 0;
   if (!strcmp(key, "s2b")) return p->s2b_state ? 1 : 0;
   if (!strcmp(key, "s2b_scratch_bytes")) return p->s2b_state ? (long)(p->s2b_state->x.bytes() + p->s2b_state->t.bytes()) : 0;
+  if (!strcmp(key, "b2s")) return p->b2s_state ? 1 : 0;
+  if (!strcmp(key, "b2s_block")) return p->b2s_state ? p->b2s_state->bp.B : 0;
+  if (!strcmp(key, "b2s_scratch_bytes"))
+    return p->b2s_state ? (long)(p->b2s_state->x.bytes() + p->b2s_state->t.bytes() + p->b2s_state->dx.bytes()) : 0;
   if (p->inner_plan()) {
     // what describes the forward's kernel is the inner plan's
     static const char *const inner_keys[] = {"kernel_choice", "code_bytes", "code_direct", "small_launch_rule", "jit_rows", "jit_records",
@@ -915,6 +992,31 @@ int escoin_plan_s2b_unpack(escoin_plan *p, float *top_dev, int n_images, void *s
   });
 }
 
+int escoin_plan_b2s_pack(escoin_plan *p, const float *src_dev, const float *mask_dev, float *dst_dev, int top_side, int n_images,
+                         void *stream) {
+  return guarded([&]() -> int {
+    if (!p) return fail(ESCOIN_EINVAL, "null argument");
+    if (!p->aligned || !p->b2s_state) return fail(ESCOIN_ESTATE, "b2s_pack: option \"b2s\" is not active on this plan");
+    if (!src_dev || !dst_dev) return fail(ESCOIN_EINVAL, "null argument");
+    if (const int rc = check_n_images(p, n_images)) return rc;
+    if (n_images == 0) return ESCOIN_OK;
+    if (const int rc = check_plan_device(p, "b2s_pack")) return rc;
+    return g_b2s_hooks.pack(p, src_dev, mask_dev, dst_dev, top_side != 0, n_images, (hipStream_t)stream);
+  });
+}
+
+int escoin_plan_b2s_unpack(escoin_plan *p, const float *src_dev, float *dst_dev, int top_side, int relu, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    if (!p) return fail(ESCOIN_EINVAL, "null argument");
+    if (!p->aligned || !p->b2s_state) return fail(ESCOIN_ESTATE, "b2s_unpack: option \"b2s\" is not active on this plan");
+    if (!src_dev || !dst_dev) return fail(ESCOIN_EINVAL, "null argument");
+    if (const int rc = check_n_images(p, n_images)) return rc;
+    if (n_images == 0) return ESCOIN_OK;
+    if (const int rc = check_plan_device(p, "b2s_unpack")) return rc;
+    return g_b2s_hooks.unpack(p, src_dev, dst_dev, top_side != 0, relu != 0, n_images, (hipStream_t)stream);
+  });
+}
+
 int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_dev, float *top_dev,
                    int n_images, void *stream) {
   return guarded([&]() -> int {
@@ -946,6 +1048,16 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
       rc = escoin_forward(sb->inner.plan.get(), sb->x.get<const float>(), bias_dev, sb->t.get<float>(), n_images * P, stream);
       if (rc != ESCOIN_OK) return rc;
       return g_s2b_hooks.unpack(p, sb->t.get<const float>(), top_dev, true, p->g.d.fuse_relu != 0, n_images, s);
+    }
+    // option "b2s": the bottom transposed into X' (the batch becomes the pixel axis), then the inner pointwise plan (bias in
+    // its epilogue) into T', then T' transposed into the top blob (ReLU there)
+    if (B2sState *bs = p->b2s_state.get()) {
+      const int n_inner = (n_images + bs->bp.B - 1) / bs->bp.B;
+      int rc = g_b2s_hooks.pack(p, bottom_dev, nullptr, bs->x.get<float>(), false, n_images, s);
+      if (rc != ESCOIN_OK) return rc;
+      rc = escoin_forward(bs->inner.plan.get(), bs->x.get<const float>(), bias_dev, bs->t.get<float>(), n_inner, stream);
+      if (rc != ESCOIN_OK) return rc;
+      return g_b2s_hooks.unpack(p, bs->t.get<const float>(), top_dev, true, p->g.d.fuse_relu != 0, n_images, s);
     }
     // LOWERED_SPARSE lowers every group, whatever AUTO decided for the direct path
     if (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE && p->kernel_choice != ESCOIN_KERNEL_DENSE)

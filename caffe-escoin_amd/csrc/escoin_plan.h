@@ -178,6 +178,16 @@ struct S2bState {
   DeviceBuffer x, t;           // X' / dX': sp.x_floats floats; T' / G': sp.t_floats floats
 };
 
+// What upload() builds for a plan that option "b2s" serves (escoin_capi.hip; the rule: align_rules.h b2s_plan; the kernels:
+// b2s.hip); reset with the device side.  A plan has at most one of the three states.  The whole backward is the inner
+// plan's: the plan itself builds no BwdState.
+struct B2sState {
+  B2sPlan bp;
+  DerivedPlan inner;           // the pointwise plan of ceil(N / B) images of 1 x B on the outer CSR (src: the identity)
+  DeviceBuffer x, t, dx;       // X': bp.x_floats floats; T' / G': bp.t_floats floats; dX': bp.x_floats floats (X' is the
+                               // weight gradient's operand in the same inner call)
+};
+
 // What the first escoin_dense_wgrad on a plan builds (dense_wgrad.hip).  A function of the descriptor, the device's CU
 // count and option "dense_wgrad_splits" alone -- not of the pattern or the values -- so no align resets it: it lives until
 // the plan is destroyed (or until a call finds the plan aligned on another device, which builds it anew there).
@@ -356,9 +366,12 @@ struct escoin_plan {
   // Space-to-batch (s2b.hip): option "s2b" and what upload() builds where it applies; reset with the device side
   int s2b = 0;
   std::unique_ptr<escoin::S2bState> s2b_state;
-  // the inner plan of whichever of the two options serves this plan (null: neither does)
+  // Batch-to-space (b2s.hip): options "b2s" and "b2s_block" and what upload() builds where they apply; reset with the device side
+  int b2s = 0, b2s_block = 0;
+  std::unique_ptr<escoin::B2sState> b2s_state;
+  // the inner plan of whichever of the three options serves this plan (null: none does)
   const escoin::DerivedPlan *inner_plan() const {
-    return s2d_state ? &s2d_state->inner : s2b_state ? &s2b_state->inner : nullptr;
+    return s2d_state ? &s2d_state->inner : s2b_state ? &s2b_state->inner : b2s_state ? &b2s_state->inner : nullptr;
   }
 
   // Dense weight gradient (dense_wgrad.hip): option "dense_wgrad_splits" (0: the rule decides, n: at most n splits of the
@@ -400,9 +413,10 @@ int realign_from_host_csr(escoin_plan *p, hipStream_t stream);
 // escoin_capi.hip (in the core for the reason S2dHooks gives below): a derived plan of the float plan `owner` into *out --
 // descriptor `desc`, the owner's options and these two kernel options, aligned on `csr` with the owner's values permuted
 // through csr.src, which becomes out->src; tiling_batch >= 0 replaces the owner's "tiling_batch" (option "s2b": the inner
-// plan's images are the owner's times P).  A failure returns the failed call's code; the caller drops *out with its state.
+// plan's images are the owner's times P); wgrad_options hands the owner's "wgrad_kernel" and "wgrad_channel_block" down too
+// (option "b2s": the inner plan computes the weight gradient).  A failure returns the failed call's code; the caller drops *out with its state.
 int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, int kernel, int backward_kernel,
-                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out, int tiling_batch = -1);
+                       DerivedCsr csr, hipStream_t stream, DerivedPlan *out, int tiling_batch = -1, bool wgrad_options = false);
 // escoin_capi.hip: the first half of set_csr -- validates a CSR (flat, as escoin_plan_set_csr takes it) and copies it into
 // the plan's host vectors; a refused CSR leaves the plan as it was.  T = float | double.
 template <typename T>
@@ -495,6 +509,18 @@ struct S2bHooks {
   const char *pack_kernel_name, *unpack_kernel_name;
 };
 extern S2bHooks g_s2b_hooks;   // escoin_capi.hip
+
+// b2s.hip (option "b2s"), registered like S2dHooks.  Each kernel serves both sides; `top_side` names the blob (CH = M) or the
+// bottom side (CH = C), and the buffers are the caller's:
+//   pack    dst[n'][ch][j] = src[n' * B + j][ch] (mask > 0 ? that : 0 where mask, laid out as src, is not null), +0 past
+//           n_images, for the ceil(n_images / B) inner images the first n_images images touch
+//   unpack  dst[n][ch] = src[n / B][ch][n % B] for n < n_images, through ReLU if `relu`
+struct B2sHooks {
+  int (*pack)(const escoin_plan *p, const float *src, const float *mask, float *dst, bool top_side, int n_images, hipStream_t stream);
+  int (*unpack)(const escoin_plan *p, const float *src, float *dst, bool top_side, bool relu, int n_images, hipStream_t stream);
+  const char *pack_kernel_name, *unpack_kernel_name;
+};
+extern B2sHooks g_b2s_hooks;   // escoin_capi.hip
 
 // Index of the k-th set bit of `mask` (k < popcount): blockIdx -> conv group when only some groups
 // of a layer run in a launch.  Wave-uniform scalar code on the device.

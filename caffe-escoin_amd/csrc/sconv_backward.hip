@@ -782,6 +782,32 @@ static int weight_gradient(escoin_plan *p, const T *bottom, const T *top, const 
   return wgrad_entry<T>(p, c);
 }
 
+// option "b2s": the whole backward is the inner plan's, on X' (the bottom transposed: the weight gradient's operand) and G'
+// (top_diff transposed, times [top > 0] on a fuse_relu plan; the inner plan has no ReLU and needs no top).  weight_diff,
+// values_diff and bias_diff have one layout on both plans: the caller's pointers go straight through.  dX' has a scratch of
+// its own (X' is read by the same inner call) and is transposed into bottom_diff.  The plan builds no state of its own.
+static int backward_b2s(escoin_plan *p, const float *bottom, const float *top, const float *top_diff, float *bottom_diff,
+                        float *weight_diff, float *bias_diff, int n_images, hipStream_t stream, bool compact) {
+  B2sState *bs = p->b2s_state.get();
+  escoin_plan *ip = bs->inner.plan.get();
+  // (after device-source updates of THIS plan the inner plan's host CSR, which its backward state is built from, is stale:
+  //  the values come back first, into every host mirror of the walk)
+  if (!ip->bwd)
+    if (const int rcs = sync_host_values(p)) return rcs;
+  if (const int rc = ensure_state<float>(ip, stream)) return rc;
+  if (n_images == 0 || (!bottom_diff && !weight_diff && !bias_diff)) return ESCOIN_OK;
+  const int n_inner = (n_images + bs->bp.B - 1) / bs->bp.B;
+  int rc = ESCOIN_OK;
+  if (weight_diff) rc = g_b2s_hooks.pack(p, bottom, nullptr, bs->x.get<float>(), false, n_images, stream);
+  if (rc == ESCOIN_OK) rc = g_b2s_hooks.pack(p, top_diff, p->g.d.fuse_relu ? top : nullptr, bs->t.get<float>(), true, n_images, stream);
+  if (rc != ESCOIN_OK) return rc;
+  rc = (compact ? escoin_backward_values : escoin_backward)(ip, weight_diff ? bs->x.get<const float>() : nullptr, nullptr,
+                                                            bs->t.get<const float>(), bottom_diff ? bs->dx.get<float>() : nullptr,
+                                                            weight_diff, bias_diff, n_inner, stream);
+  if (rc != ESCOIN_OK || !bottom_diff) return rc;
+  return g_b2s_hooks.unpack(p, bs->dx.get<const float>(), bottom_diff, false, false, n_images, stream);
+}
+
 // The driver: the checks, the state where this alignment has none yet, then the two gradients.  With the state built a
 // call allocates nothing and synchronises nothing.
 template <typename T>
@@ -798,6 +824,8 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
   if (weight_diff && !bottom) return fail(ESCOIN_EINVAL, "backward: the weight gradient needs bottom");
   if (const int rc = check_n_images(p, n_images)) return rc;
   hipStream_t stream = (hipStream_t)stream_v;
+  if constexpr (sizeof(T) == 4)
+    if (p->b2s_state) return backward_b2s(p, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images, stream, compact);
   if (const int rc = ensure_state<T>(p, stream)) return rc;
   if (n_images == 0) return ESCOIN_OK;
   if (bottom_diff) {

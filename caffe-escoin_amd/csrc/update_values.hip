@@ -147,6 +147,10 @@ int for_each_copy(Plan *q, const std::vector<int> *outer, bool with_maps, OnPlan
     if (!through(sb->inner.src, &map)) return mismatch("the inner plan");
     if ((rc = for_each_copy<Plan>(sb->inner.plan.get(), map, with_maps, on_plan, on_array)) != ESCOIN_OK) return rc;
   }
+  if (const B2sState *bs = q->b2s_state.get()) {   // (the identity map; the backward state is the inner plan's alone)
+    if (!through(bs->inner.src, &map)) return mismatch("the inner plan");
+    if ((rc = for_each_copy<Plan>(bs->inner.plan.get(), map, with_maps, on_plan, on_array)) != ESCOIN_OK) return rc;
+  }
   const BwdState *s = q->bwd.get();
   if (!s) return ESCOIN_OK;
   switch (s->data) {
@@ -167,6 +171,9 @@ int for_each_copy(Plan *q, const std::vector<int> *outer, bool with_maps, OnPlan
   }
   return ESCOIN_OK;
 }
+
+// Whether a backward state exists that holds a copy of p's values: p's own, or under option "b2s" the inner plan's.
+bool has_bwd_state(const escoin_plan *p) { return p->bwd || (p->b2s_state && p->b2s_state->inner.plan->bwd); }
 
 const auto skip_arrays = [](const DeviceBuffer &, size_t, const int *, const int *, long) { return ESCOIN_OK; };
 
@@ -199,7 +206,7 @@ int build_state(escoin_plan *p, hipStream_t stream, bool entry_view, bool vals_o
     };
     const int rc = for_each_copy(p, nullptr, true, on_plan, on_array);
     if (rc != ESCOIN_OK) return rc;
-    u->has_bwd = p->bwd != nullptr;
+    u->has_bwd = has_bwd_state(p);
   }
   std::stable_sort(dst.begin(), dst.end(), [](const Dst &a, const Dst &b) { return a.buf != b.buf ? a.buf < b.buf : a.src < b.src; });
   u->n_dst = (long)dst.size();
@@ -307,7 +314,7 @@ int update_t(escoin_plan *p, const T *in, bool from_dense, int on_device, void *
   hipStream_t stream = (hipStream_t)stream_v;
   ++p->upd_count;
   if (!plan_in_place_ok(p)) return update_by_rebuild<T>(p, in, from_dense, on_device != 0, stream);
-  if (!p->upd || p->upd->vals_only || (p->bwd && !p->upd->has_bwd)) {
+  if (!p->upd || p->upd->vals_only || (has_bwd_state(p) && !p->upd->has_bwd)) {
     const bool entry_view = p->upd && p->upd->entry_view && !p->upd->vals_only;
     p->upd.reset();
     const int rc = build_state<T>(p, stream, entry_view);
@@ -370,7 +377,7 @@ int solver_begin(escoin_plan *p, const char *name, hipStream_t stream, SolverTar
   t->nnz = plan_nnz(p);
   if (t->nnz == 0) return ESCOIN_OK;      // (nothing is launched: "update_fast" keeps what the last real update left)
   const UpdState *have = p->upd.get();
-  if (!have || !have->entry_view || have->vals_only != !t->in_place || (t->in_place && p->bwd && !have->has_bwd)) {
+  if (!have || !have->entry_view || have->vals_only != !t->in_place || (t->in_place && has_bwd_state(p) && !have->has_bwd)) {
     p->upd.reset();
     const int rc = build_state<T>(p, stream, true, !t->in_place);
     if (rc != ESCOIN_OK) return rc;

@@ -167,6 +167,10 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *   "s2b"        = 0 (default) / 1: run a dilated stride-1 layer on the stride-1, dilation-1 kernels via space-to-batch
  *                  ("Space-to-batch" below).  1 changes nothing for a layer the option does not serve; KERNEL_AUTO never
  *                  picks it by itself.  May be set together with "s2d": the two serve disjoint geometries.
+ *   "b2s"        = 0 (default) / 1: run an inner-product layer (H = W = 1, a 1x1 kernel, pad 0) on the pointwise kernels
+ *                  with the batch as the pixel axis ("Batch-to-space" below).  1 changes nothing for a layer the option
+ *                  does not serve; KERNEL_AUTO never picks it by itself.  May be set together with "s2d" and "s2b".
+ *   "b2s_block"  = the block B of "b2s": 0 (default) the rule, otherwise a multiple of 4 in 4..256 (a test option).
  * Environment: the product build reads ESCOIN_VERBOSE (diagnostics on stderr) and TMPDIR (temporary file of the
  * code object manager's fallback path) and nothing else -- no environment variable can change a result
  * ("Environment"; csrc/knobs.h for the non-product flavours built by tools/mkabl.sh exp / stamps). */
@@ -319,6 +323,65 @@ ESCOIN_API int escoin_plan_s2d_pack(escoin_plan *plan, const float *bottom_dev, 
  * its last (the T' scratch, whatever it holds, into the top blob), for measuring them; ESCOIN_ESTATE unless stat "s2b" is 1. */
 ESCOIN_API int escoin_plan_s2b_pack(escoin_plan *plan, const float *bottom_dev, int n_images, void *stream);
 ESCOIN_API int escoin_plan_s2b_unpack(escoin_plan *plan, float *top_dev, int n_images, void *stream);
+
+/* ---- Batch-to-space: inner-product layers on the pointwise kernels (option "b2s") ------------------------------------
+ * An InnerProduct layer of K inputs and M outputs is the descriptor {N, C = K, H = W = 1, M, 1x1, stride 1, pad 0}: N
+ * images of one pixel.  Every entry point accepts it, but a row of the fast kernels then holds one pixel.  With the batch
+ * as the pixel axis the same layer is an ordinary pointwise (1x1) layer.  Let B be the block, a multiple of 4 with
+ * 4 <= B <= 256.  The INNER plan has
+ *   N' = ceil(N / B) images of 1 x B pixels (the first n_images outer images are the first ceil(n_images / B) inner ones),
+ *   the outer plan's C, M, group and has_bias, a 1x1 kernel, pad 0, stride 1, dilation 1 (with one pixel and one tap the
+ *   outer stride and dilation are immaterial), fuse_relu = 0;
+ *   weights the outer CSR verbatim: same rows, same columns, same value order;
+ *   input   X'[n'][c][j] = bottom[n' * B + j][c] for n' * B + j < n_images, +0 otherwise;
+ *   T' = inner_forward(X') over ceil(n_images / B) inner images, the bias in the inner epilogue;
+ *   top[n][m] = T'[n / B][m][n % B], then v > 0 ? v : 0 on a fuse_relu plan (the epilogues' expression);
+ *   G'[n'][m][j] = top_diff[n][m] with n = n' * B + j; on a fuse_relu plan top[n][m] > 0 ? top_diff[n][m] : 0; +0 past
+ *           n_images;
+ *   the WHOLE backward is the inner plan's, on (X', G') -- where "b2s" departs from "s2d" / "s2b":
+ *           bottom_diff[n][c] = dX'[n / B][c][n % B] with dX' = inner_data_gradient(G'); the weight, bias and compact
+ *           gradients and escoin_dense_wgrad are the inner plan's own.  weight_diff (M x Cg), values_diff (the same entry
+ *           order) and bias_diff have the same layout on both plans: the caller's pointers go straight through, += included.
+ *           The padding positions are +0 in both operands and add exact zeros.  The outer plan builds no backward state.
+ * Images at or past n_images are neither read nor written on the caller's side, and a padding position is +0 written by the
+ * pack kernel, never a bottom element: image n reaches only image n's outputs, also on the inner DENSE kernel.
+ * With "b2s" = 1 a FLOAT plan in conv_mode SCONV / SCONV_PAR with H = W = 1, KH = KW = 1 and pad 0, of any group, whose
+ * bottom, top, X' and T' each stay below 2^31 elements and whose N' is at most 65535, runs this way: escoin_forward =
+ * escoin_b2s_pack_kernel (an LDS-staged transpose, one pass, zeros included) + the inner plan's forward +
+ * escoin_b2s_unpack_kernel; escoin_backward / escoin_backward_values = escoin_b2s_pack_kernel of the bottom (where a weight
+ * gradient is asked for) and of top_diff + the inner plan's backward + escoin_b2s_unpack_kernel of dX'.  Where both "b2s"
+ * and "s2d" are set on a one-pixel layer whose descriptor names a stride, "b2s" serves it.
+ * The block: B = 64 (the block that won or tied the sweep of profiles/b2s_mi355x.md on every layer, at batch 256 and at
+ * batch 32, where it is half padding); where that gives more than 65535 inner images, the smaller of 128 and 256 that does
+ * not.  "b2s_block" forces it.
+ * The inner plan and three scratches (X', T' / G', and dX', which must not alias X' within one inner call) are built by the
+ * align; the inner plan's backward state by the first backward; after these forward and backward never allocate.  The
+ * inner plan gets the options "kernel", "backward_kernel", "wgrad_kernel", "wgrad_channel_block", "max_launch_bytes",
+ * "dense_threshold_pct", "dense_gate" and "code_loader" as they stand, and "tiling_batch" in inner images (ceil(tiling_batch
+ * / B)), and ALONE decides dense or sparse per group, on its own geometry; forcing TILED / JIT, or a backward or weight-gradient
+ * kernel, fails with ESCOIN_EINVAL where the inner layer does not fit it.  In-place updates (escoin_update_values,
+ * escoin_plan_set_values, escoin_solver_step) reach the inner plan's copies and stay in place wherever the inner plan is
+ * in-place capable; prune, rewire, set_csr and weight_align rebuild the inner plan.  escoin_plan_export_aligned writes the
+ * outer CSR and no code section; escoin_plan_import_aligned aligns from it.  Everywhere else -- H * W > 1, a kernel above 1x1,
+ * a pad, a size limit, a double plan, LOWERED_GEMM / LOWERED_SPARSE (a flip of the conv mode rebuilds) -- the plan behaves
+ * exactly as with "b2s" = 0, with the exception "Space-to-depth" states for a forced "kernel" = TILED / JIT in the lowered modes.
+ * Results: where the inner plan runs a sparse kernel an element's sum order is a function of the pattern, so the results
+ * depend on neither B nor n_images; with the generic kernel inside they equal the plan without the option bit for bit; the
+ * inner DENSE kernel may split K differently per shape and is held to the error bound.
+ * Stats: "b2s" (1 when active), "b2s_block" (the B in use), "b2s_scratch_bytes" (the three scratches); "kernel_choice",
+ * the "bwd_*" / "wgrad_*" / "dgrad_*" facts, escoin_plan_tiling_info and the other facts about the kernels report the inner
+ * plan's; escoin_plan_kernel_name returns "escoin_b2s_pack_kernel + <inner name> + escoin_b2s_unpack_kernel".
+ * "device_bytes" and escoin_plan_workspace_bytes count the scratches and the inner plan.  Ordering across streams is the
+ * caller's, as for any plan: forward and backward share the scratches.
+ * escoin_plan_b2s_pack / escoin_plan_b2s_unpack run one transpose alone on the CALLER's buffers, for measuring and testing:
+ * top_side = 0 is the bottom side (CH = C), 1 the top side (CH = M).  pack reads n_images x CH floats of src_dev (and of
+ * mask_dev, where not NULL: the value is mask > 0 ? src : 0) and writes the ceil(n_images / B) x CH x B first floats of
+ * dst_dev; unpack reads those of src_dev and writes n_images x CH floats of dst_dev, through ReLU if relu != 0.
+ * ESCOIN_ESTATE unless stat "b2s" is 1; ESCOIN_EINVAL for NULL buffers or n_images outside [0, N]. */
+ESCOIN_API int escoin_plan_b2s_pack(escoin_plan *plan, const float *src_dev, const float *mask_dev, float *dst_dev, int top_side,
+                         int n_images, void *stream);
+ESCOIN_API int escoin_plan_b2s_unpack(escoin_plan *plan, const float *src_dev, float *dst_dev, int top_side, int relu, int n_images,
+                         void *stream);
 
 /* Integer facts about an aligned plan (negative = error): "align_us" wall time of the last
  * weight_align / set_csr / import_aligned, "code_bytes" generated machine code on the device,
