@@ -229,6 +229,44 @@ TiledLaunchShape tiled_launch_shape(const Geometry &g, const Tiling &t, int n_im
   return s;
 }
 
+TouchWorkgroup touch_workgroup(const TiledLaunchShape &s, int orig, int T) {
+  TouchWorkgroup w;
+  w.xcd = orig & (kTouchXcds - 1);
+  const int k = orig >> 3;
+  const int wg = s.xcd_q >= 0 ? w.xcd * s.xcd_q + std::min(w.xcd, s.xcd_r) + k : orig;
+  w.by = wg / s.grid_x;
+  w.bx = wg - w.by * s.grid_x;
+  w.toucher = touch_elected((unsigned)touch_rank(s.xcd_q, k, w.bx), (unsigned)T, touch_mul(T));
+  return w;
+}
+
+int touch_election(const TiledLaunchShape &s, bool jit, int n_pref, int n_cu, int option) {
+  // nothing to elect, forced or not: no code or no touches, or ranks the multiplication of touch_elected does not cover
+  if (!jit || n_pref <= 0 || s.grid_x >= (1 << 16) || s.grid_x < 1 || s.grid_y < 1) return 1;
+  if (option >= 1) return std::min(option, kTouchMaxStride);
+  // what the rule cannot describe: a device that is not eight XCDs of whole CUs
+  if (n_cu < 64 || n_cu % kTouchXcds != 0) return 1;
+  // Measured inside the bench step on the four ResNet-50 3x3 shapes at 90 % (profiles/code_touch_election_mi355x.md):
+  // strides 4, 8 and 16 are not separable and 3 % under stride 1 on the step; one toucher per set (its peers then meet
+  // code that is still on its way) puts res2, whose sets are the largest, above stride 1.  8 is the middle of the flat
+  // range.  The sweep separated neither the code's bytes per grid row (0.19-1.44 MB) nor the tiles a workgroup walks
+  // (1-7), so the rule reads neither.  Sets of up to 8 workgroups have their first member alone.
+  return kTouchRuleStride;
+}
+
+long touch_lines(const TiledLaunchShape &s, const Tiling &t, int n_pref, int T, long *touchers) {
+  long lines = 0, nt = 0;
+  if (n_pref > 0 && s.grid_x > 0)
+    for (int orig = 0; orig < s.grid_x * s.grid_y; ++orig) {
+      const TouchWorkgroup w = touch_workgroup(s, orig, T);
+      const long walked = w.bx < s.tiles ? (s.tiles - w.bx + s.grid_x - 1) / s.grid_x : 0;
+      lines += (long)t.waves * n_pref * (1 + walked * t.n_icb) * (w.toucher ? 64 : 1);
+      nt += w.toucher;
+    }
+  if (touchers) *touchers = nt;
+  return lines;
+}
+
 // Generated code: nothing but the planes (and two small tables) lives in LDS -- the first tiling
 // the budget allows is the one.  WeightAlign = tiling, channel deal, code generation, code
 // object (jit_module.h), unit table.

@@ -83,6 +83,45 @@ struct TiledLaunchShape {
 TiledLaunchShape tiled_launch_shape(const Geometry &g, const Tiling &t, int n_images, int groups, bool jit, long code_bytes,
                                     int n_cu);
 
+// ---- which workgroups touch generated code with whole lines (sconv_tiled.hip, plan option "code_touchers") ---------
+// Every unit of generated code starts with n_pref loads that pull the NEXT unit's code towards the wave (jit_codegen.h):
+// 64 lanes x 64 bytes each, so that the code is in the XCD's L2 when the instruction cache asks for it.  One workgroup
+// per L2 achieves that; the others' touches return lines the L2 already holds, through the path the plane DMA uses.  The
+// election leaves the instruction in place and changes the lane offset the compiled body hands it (v63): 64 x lane in a
+// TOUCHER, 0 elsewhere -- all 64 lanes then read one dword, one line request, still counted by vmcnt.
+//
+// The workgroups that share code and L2 are those of one XCD and one grid row (grid y = conv group x workgroup column).
+// Linear workgroup ids go round the eight XCDs, which is what the XCD grouping of tiled_launch_shape relies on too, so a
+// workgroup's RANK in its set follows from its id alone (ids ascending = dispatch order):
+//   grouped launches (xcd_q >= 0): XCD x runs the renumbered ids [start_x, start_x + count_x), k = id / 8 counts from
+//     start_x and bx from the start of the row, so rank = min(k, bx);
+//   launch order (xcd_q < 0): the row's ids of one residue modulo 8 are bx = bx0, bx0 + 8, ..., bx0 < 8: rank = bx / 8.
+// A workgroup is a toucher when rank % T == 0: rank 0 of every set always is, T = 1 makes every workgroup one.
+constexpr int kTouchXcds = 8;
+constexpr int kTouchRuleStride = 8;         // what the rule answers wherever it elects (align_rules.cpp touch_election)
+constexpr int kTouchMaxStride = 65535;      // ranks stay below a launch's grid x, which is below 2^16 workgroups
+// rank % T == 0 without a division: q = floor(rank * mul / 2^32) with mul = floor(2^32 / T) + 1 is floor(rank / T) while
+// rank * T < 2^32 (the multiplier is at most T / 2^32 too large per unit of rank).  T = 1 needs no test; its mul is 0.
+constexpr unsigned touch_mul(int T) { return T >= 2 ? (unsigned)((1ull << 32) / (unsigned)T + 1) : 0u; }
+constexpr int touch_rank(int xcd_q, int k, int bx) { return xcd_q >= 0 ? (k < bx ? k : bx) : bx >> 3; }
+constexpr bool touch_elected(unsigned rank, unsigned T, unsigned mul) {
+  return T <= 1u || rank == (unsigned)(((unsigned long long)rank * mul) >> 32) * T;
+}
+// (grid row, column in the row) of linear workgroup id `orig` -- the renumbering of tiled_body / chained_body -- and
+// whether the workgroup is a toucher at stride T
+struct TouchWorkgroup { int bx, by, xcd; bool toucher; };
+TouchWorkgroup touch_workgroup(const TiledLaunchShape &s, int orig, int T);
+
+// The stride T of a launch: 1 for stream plans, for plans without touches (n_pref = 0) and for grids of 2^16 columns or
+// more, whatever the option says -- there is nothing to elect.  Otherwise option (plan option "code_touchers") k >= 1
+// forces T = k (capped at kTouchMaxStride: then rank 0 alone) and 0 is the rule, a function of the device alone, never
+// of a timing: kTouchRuleStride on eight XCDs, 1 on devices it does not take for that (CU counts below 64 or no multiple
+// of 8).  What it ships and why it reads nothing of the launch: profiles/code_touch_election_mi355x.md.
+int touch_election(const TiledLaunchShape &s, bool jit, int n_pref, int n_cu, int option);
+// Line requests of a launch's code touches at stride T: every wave's first-unit touch plus the touches of each unit of
+// each tile it walks, n_pref instructions each, 64 lines in a toucher and 1 elsewhere.  touchers: the touchers counted.
+long touch_lines(const TiledLaunchShape &s, const Tiling &t, int n_pref, int T, long *touchers = nullptr);
+
 // Generated code: the tiling, the plane buffers and the generator's options.  ok == false: the layer does not fit.
 struct JitLayout {
   bool ok = false;

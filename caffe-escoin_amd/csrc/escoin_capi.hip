@@ -189,7 +189,7 @@ int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, i
   int rc = escoin_plan_create(&desc, &q);
   out->plan.reset(q);
   if (rc != ESCOIN_OK) return rc;
-  // what a derived plan inherits, and all of it ("body_variant" and "stream_stores" are not handed down, the "wgrad_*"
+  // what a derived plan inherits, and all of it ("body_variant", "code_touchers" and "stream_stores" are not handed down, the "wgrad_*"
   // options only where the derived plan computes the weight gradient)
   if ((rc = escoin_plan_set_option(q, "kernel", kernel)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "backward_kernel", backward_kernel)) != ESCOIN_OK) return rc;
@@ -676,6 +676,11 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->body_variant = value;
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "code_touchers")) {
+      if (value < 0) return fail(ESCOIN_EINVAL, "code_touchers must be 0 (the rule) or a stride >= 1");
+      p->code_touchers = value;
+      return ESCOIN_OK;
+    }
     if (!strcmp(key, "stream_stores")) {
       if (value < -1 || value > 1) return fail(ESCOIN_EINVAL, "stream_stores must be -1, 0 or 1");
       p->stream_stores = value;
@@ -865,6 +870,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
     // what describes the forward's kernel is the inner plan's
     static const char *const inner_keys[] = {"kernel_choice", "code_bytes", "code_direct", "small_launch_rule", "jit_rows", "jit_records",
                                              "deal_slowest_over_mean_x1000", "deal_worst_block_x1000", "lds_bytes", "body_variant",
+                                             "code_touchers", "touch_lines_per_launch",
                                              "workgroup_columns", "streamk_gave_up", "streamk", "dense_variant"};
     for (const char *k : inner_keys)
       if (!strcmp(key, k)) return escoin_plan_stat(p->inner_plan()->plan.get(), key);
@@ -885,6 +891,9 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "deal_worst_block_x1000")) return p->tiled.jit ? (long)(p->tiled.deal_worst_block * 1000.f + 0.5f) : 0;
   if (!strcmp(key, "lds_bytes")) return p->tiled.enabled ? (long)p->tiled.lds_bytes : 0;
   if (!strcmp(key, "body_variant")) return p->tiled.enabled ? p->tiled.body_variant_last : 0;
+  if (!strcmp(key, "code_touchers")) return p->tiled.enabled ? p->tiled.touch_stride_last : 1;
+  if (!strcmp(key, "touch_lines_per_launch"))     // (counted on the host from the last launch's shape and stride)
+    return p->tiled.enabled && p->tiled.jit ? touch_lines(p->tiled.launch_shape_last, p->tiled.tiling, p->tiled.jit_pref, p->tiled.touch_stride_last) : 0;
   if (!strcmp(key, "workgroup_columns")) return p->tiled.enabled ? p->tiled.tiling.n_ocblk : 0;
   if (!strcmp(key, "streamk_gave_up")) {
     // dense kernel, stream-K launches: 1 if a workgroup's bounded wait for another one's partial sums ran out in

@@ -74,6 +74,8 @@ struct TiledConfig {
   float deal_slowest_over_mean = 1.f, deal_worst_block = 1.f;   // balance of the channel deal (jit_codegen.h Program)
   std::string info;          // escoin_plan_tiling_info
   mutable int body_variant_last = 0;   // stat "body_variant": the compiled body of the last tiled launch (0 generic, 1 chained)
+  mutable int touch_stride_last = 1;   // stat "code_touchers": the code-touch stride of the last tiled launch (align_rules.h touch_election)
+  mutable TiledLaunchShape launch_shape_last;   // ... and its shape: stat "touch_lines_per_launch" counts from the two
 };
 
 // One host thread's buffers of the CPU mode (sconv_cpu.cpp): the shared-halo padded image and the store scratch.
@@ -325,6 +327,7 @@ struct escoin_plan {
   int n_dense_groups = 0, n_sparse_groups = 0;
   int dense_threshold_pct = -1;   // option "dense_threshold_pct" (-1: the measured default)
   int body_variant = -1;          // option "body_variant": -1 the rule (align_rules.h body_variant), 0 always the generic body
+  int code_touchers = 0;          // option "code_touchers": 0 the rule (align_rules.h touch_election), k >= 1 every k-th workgroup of an XCD and grid row
   int stream_stores = -1;         // option "stream_stores": pointwise layers write the top blob with non-temporal stores (1), never (0), by size (-1)
 
   // LOWERED_SPARSE comparator (sconv_lowered.hip): column buffer, grown on demand by the forward

@@ -162,6 +162,14 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  body_variant), the generic body otherwise; 0: always the generic body.  Both call the same code
  *                  and run the same epilogue: results are bit-identical; tests and same-call A/B runs use 0.  May be
  *                  set on an aligned plan; stat "body_variant" = what the last forward ran (0 generic, 1 chained).
+ *   "code_touchers" = which workgroups of a generated-code launch pull whole lines with their code touches.  0
+ *                  (default): the rule (csrc/align_rules.h touch_election: every 8th workgroup among those that share
+ *                  an XCD and a grid row on a device of eight XCDs, every workgroup elsewhere); k >= 1: every k-th
+ *                  (1: every workgroup; 65535 or more: the first of each set alone).  The other workgroups' touches ask
+ *                  for one line instead of 64.  No instruction and no result changes; stats "code_touchers" (the
+ *                  stride of the last launch) and "touch_lines_per_launch".  Not handed down to derived plans.  Stream
+ *                  plans, code without touches and launches of the chained pointwise body do not elect: their
+ *                  stride is 1 whatever the option says.
  *   "s2d"        = 0 (default) / 1: run a strided layer on the stride-1 kernels via space-to-depth ("Space-to-depth"
  *                  below).  1 changes nothing for a layer the option does not serve; KERNEL_AUTO never picks it by itself.
  *   "s2b"        = 0 (default) / 1: run a dilated stride-1 layer on the stride-1, dilation-1 kernels via space-to-batch
@@ -389,6 +397,9 @@ ESCOIN_API int escoin_plan_b2s_unpack(escoin_plan *plan, const float *src_dev, f
  * filled itself, 0: in a module the HIP loader loaded -- option "code_loader"), "cpu_channel_block" / "cpu_images_per_job"
  * (what the last escoin_forward_cpu used), "jit_rows", "jit_records", "lds_bytes", "workgroup_columns",
  * "body_variant" (the compiled body the last tiled launch ran: 0 generic, 1 chained -- option "body_variant"),
+ * "code_touchers" (the code-touch stride of the last tiled launch -- option "code_touchers") and "touch_lines_per_launch"
+ * (the line requests of that launch's code touches, counted on the host from its grid and stride: every wave's first-unit
+ * touch and the touches of each unit of each tile, 64 lines in an elected workgroup and 1 elsewhere; 0 without touches),
  * "kernel_choice" (the ESCOIN_KERNEL_* id AUTO resolved to for the sparse groups), "small_launch_rule" (KERNEL_AUTO's
  * rule for pointwise launches under 64 MFLOP that fit one round of workgroups -- the reference's SCONV mode runs
  * image by image, conv_layer.cu:16-26 --: 0 not considered, 1 kept generated code, 2 took the generic kernel (decided
