@@ -202,7 +202,7 @@ TiledLaunchShape tiled_launch_shape(const Geometry &g, const Tiling &t, int n_im
                                     int n_cu) {
   TiledLaunchShape s;
   s.tiles = t.band_mode ? n_images * t.bands : (n_images + t.nseg - 1) / t.nseg;
-  s.epi_store = (size_t)n_images * g.d.M * t.OH * t.OW * 4 < ((size_t)1 << 31);
+  s.epi_store = epi_store_fits((unsigned long long)n_images * g.d.M * t.OH * t.OW * 4);
   // persistent workgroups: one 8-wave workgroup per CU is resident (2 waves/SIMD); each walks
   // its share of the pixel tiles so that prologue, first fill and epilogue overlap across tiles
   s.grid_y = groups * t.n_ocblk;
@@ -227,6 +227,72 @@ TiledLaunchShape tiled_launch_shape(const Geometry &g, const Tiling &t, int n_im
   s.xcd_q = on ? nwg / 8 : -1;
   s.xcd_r = on ? nwg % 8 : 0;
   return s;
+}
+
+// ---- the size limits a launch checks ----------------------------------------------------------------------------------
+static LaunchVerdict refuse_launch(int rc, const char *msg) {
+  LaunchVerdict v;
+  v.rc = rc;
+  v.error = msg;
+  return v;
+}
+
+int tiled_chunk(int n_images, unsigned long long in_image_bytes, unsigned long long range) {
+  const unsigned long long fit = range > 16 && in_image_bytes > 0 ? (range - 16) / in_image_bytes : 0;
+  return (int)std::max<unsigned long long>(1, std::min<unsigned long long>((unsigned long long)std::max(n_images, 0), fit));
+}
+
+LaunchVerdict tiled_image_limit(unsigned long long in_image_bytes, unsigned long long range) {
+  if (in_image_bytes >= range) return refuse_launch(ESCOIN_EINVAL, "tiled kernel: one image exceeds the 4 GiB descriptor range");
+  return LaunchVerdict();
+}
+
+LaunchVerdict tiled_strided_top_limit(bool strided, unsigned long long top_bytes) {
+  if (strided && !epi_store_fits(top_bytes))
+    return refuse_launch(ESCOIN_EINVAL, "tiled kernel: strided pointwise layer with a top blob of 2 GiB or more");
+  return LaunchVerdict();
+}
+
+LaunchVerdict tiled_grid_limit(unsigned long grid_y) {
+  if (grid_y > kGridYZMax) return refuse_launch(ESCOIN_EINVAL, "tiled kernel: grid.y exceeds 65535");
+  return LaunchVerdict();
+}
+
+LaunchVerdict tiled_call_limits(const Geometry &g, const Tiling &t, int n_images, int groups, long max_launch_bytes) {
+  const unsigned long long in_image = (unsigned long long)g.d.C * g.d.H * g.d.W * 4;
+  const unsigned long long range = tiled_launch_range(max_launch_bytes);
+  LaunchVerdict v = tiled_image_limit(in_image, range);
+  if (!v.ok()) return v;
+  // the first launch is the largest
+  const int first = std::min(n_images, tiled_chunk(n_images, in_image, range));
+  v = tiled_strided_top_limit(strided_pointwise(g), (unsigned long long)first * g.d.M * g.OH * g.OW * 4);
+  if (!v.ok()) return v;
+  return tiled_grid_limit((unsigned long)groups * (unsigned long)t.n_ocblk);
+}
+
+LaunchVerdict dense_pixels_limit(long pixels) {
+  if (pixels >= (1l << 31)) return refuse_launch(ESCOIN_EINVAL, "dense kernel: N*OH*OW does not fit 31 bits");
+  return LaunchVerdict();
+}
+
+LaunchVerdict dense_bytes_limit(unsigned long long in_bytes, unsigned long long w_bytes) {
+  if (in_bytes >= kDescriptorRange || w_bytes >= kDescriptorRange)
+    return refuse_launch(ESCOIN_EINVAL, "dense kernel: bottom blob or weight matrix exceeds the 4 GiB descriptor range");
+  return LaunchVerdict();
+}
+
+LaunchVerdict grid_yz_limit(GridKernel k, unsigned long grid_y, unsigned long grid_z) {
+  if (grid_y <= kGridYZMax && (grid_z <= kGridYZMax || k == kGridCsrmmF64)) return LaunchVerdict();
+  switch (k) {
+    case kGridGeneric: return refuse_launch(ESCOIN_EINVAL, "generic kernel: grid dimension exceeds 65535");
+    case kGridCsrmm: return refuse_launch(ESCOIN_EINVAL, "csrmm: grid dimension exceeds 65535");
+    case kGridCsrmmF64: return refuse_launch(ESCOIN_EINVAL, "csrmm_f64: more than 65535 rows");
+    default: return refuse_launch(ESCOIN_EINVAL, "im2col: grid dimension exceeds 65535");
+  }
+}
+
+LaunchVerdict generic_call_limits(const Geometry &g, int n_images) {
+  return grid_yz_limit(kGridGeneric, ((unsigned long)g.d.M + 3) / 4, (unsigned long)std::max(n_images, 0));
 }
 
 TouchWorkgroup touch_workgroup(const TiledLaunchShape &s, int orig, int T) {

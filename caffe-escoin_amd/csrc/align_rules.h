@@ -83,6 +83,53 @@ struct TiledLaunchShape {
 TiledLaunchShape tiled_launch_shape(const Geometry &g, const Tiling &t, int n_images, int groups, bool jit, long code_bytes,
                                     int n_cu);
 
+// ---- the size limits a launch checks (include/escoin.h "Size limits") -----------------------------------------------
+// What the .hip files refuse at launch time, as functions of sizes alone: tests/cpp/launch_limits_check.cpp holds each
+// to its edge without a device.  A verdict is the refusal's code and message, ESCOIN_OK and "" where the launch may go.
+struct LaunchVerdict {
+  int rc = ESCOIN_OK;
+  const char *error = "";
+  bool ok() const { return rc == ESCOIN_OK; }
+};
+// A buffer descriptor's 32-bit byte offsets (the plane DMA of the tiled kernels, both operands of the dense kernel): a
+// launch addresses fewer bytes than this.  The last 16 stay out of range: kOOB of sconv_tiled.hip is the offset of a
+// quad that must read as zeros.
+constexpr unsigned long long kDescriptorRange = 0xFFFFFFF0ull;
+// The asm epilogues' 32-bit byte offsets into the top blob (voff + g * ostr): a launch's top lies below this.
+constexpr unsigned long long kEpiStoreRange = 1ull << 31;
+constexpr unsigned kGridYZMax = 65535u;    // a grid's y and z
+
+// the asm epilogues may store this launch's top blob (TiledLaunchShape::epi_store)
+constexpr bool epi_store_fits(unsigned long long top_bytes) { return top_bytes < kEpiStoreRange; }
+// the most bytes of bottom one tiled launch covers: plan option "max_launch_bytes" (> 0) lowers the descriptor's range
+constexpr unsigned long long tiled_launch_range(long max_launch_bytes) {
+  return max_launch_bytes > 0 && (unsigned long long)max_launch_bytes < kDescriptorRange ? (unsigned long long)max_launch_bytes
+                                                                                          : kDescriptorRange;
+}
+// launch_tiled's sub-batch: images per launch of a bottom of n_images x in_image_bytes under `range`, at least one
+int tiled_chunk(int n_images, unsigned long long in_image_bytes, unsigned long long range);
+// ... and the launches that makes
+constexpr long tiled_launches(int n_images, int chunk) { return ((long)n_images + chunk - 1) / chunk; }
+// tiled: one image at or above the range
+LaunchVerdict tiled_image_limit(unsigned long long in_image_bytes, unsigned long long range);
+// tiled: a strided pointwise launch (always the asm epilogue) with a top of kEpiStoreRange bytes or more
+LaunchVerdict tiled_strided_top_limit(bool strided, unsigned long long top_bytes);
+// tiled: grid y
+LaunchVerdict tiled_grid_limit(unsigned long grid_y);
+// Everything launch_tiled refuses for sizes, for a call of n_images, in the order its launches would meet it: what a plan
+// with dense and sparse conv groups asks BEFORE its dense half is launched (escoin_forward).  groups: the conv groups the
+// tiled launches cover.
+LaunchVerdict tiled_call_limits(const Geometry &g, const Tiling &t, int n_images, int groups, long max_launch_bytes);
+// dense: N*OH*OW at or above 2^31
+LaunchVerdict dense_pixels_limit(long pixels);
+// dense: the bottom of the launch or the weight matrix at or above kDescriptorRange bytes
+LaunchVerdict dense_bytes_limit(unsigned long long in_bytes, unsigned long long w_bytes);
+// generic / lowered: grid y or z above kGridYZMax.  The message names the kernel.
+enum GridKernel { kGridGeneric, kGridCsrmm, kGridCsrmmF64, kGridIm2col };
+LaunchVerdict grid_yz_limit(GridKernel k, unsigned long grid_y, unsigned long grid_z);
+// the generic kernel's grid: y = ceil(M / 4) (four waves per workgroup, one output channel each), z = the images
+LaunchVerdict generic_call_limits(const Geometry &g, int n_images);
+
 // ---- which workgroups touch generated code with whole lines (sconv_tiled.hip, plan option "code_touchers") ---------
 // Every unit of generated code starts with n_pref loads that pull the NEXT unit's code towards the wave (jit_codegen.h):
 // 64 lanes x 64 bytes each, so that the code is in the XCD's L2 when the instruction cache asks for it.  One workgroup

@@ -635,15 +635,14 @@ int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, f
   a.pad_h = g.d.pad_h; a.pad_w = g.d.pad_w; a.stride_h = g.d.stride_h; a.stride_w = g.d.stride_w;
   a.Cg = g.Cg; a.Mg = g.Mg; a.K = g.kdim; a.lda = dense_lda(g.kdim); a.relu = g.d.fuse_relu;
   const long P = (long)n_images * g.OH * g.OW;
-  if (P >= (1l << 31)) return fail(ESCOIN_EINVAL, "dense kernel: N*OH*OW does not fit 31 bits");
+  if (const LaunchVerdict v = dense_pixels_limit(P); !v.ok()) return fail(v.rc, v.error);      // (align_rules.h)
   if (g.d.dil_h * (g.d.KH - 1) > 0x7FFE || g.d.dil_w * (g.d.KW - 1) > 0x7FFE)
     return fail(ESCOIN_EINVAL, "dense kernel: dilated kernel extent does not fit 15 bits");
   a.P = (int)P;
   // the operands are addressed through buffer descriptors with 32-bit byte offsets
   const size_t in_bytes = (size_t)n_images * g.d.C * g.d.H * g.d.W * 4;
   const size_t w_bytes = ((size_t)g.d.M + dense_spare_rows()) * a.lda * 4;
-  if (in_bytes >= 0xFFFFFFF0ull || w_bytes >= 0xFFFFFFF0ull)
-    return fail(ESCOIN_EINVAL, "dense kernel: bottom blob or weight matrix exceeds the 4 GiB descriptor range");
+  if (const LaunchVerdict v = dense_bytes_limit(in_bytes, w_bytes); !v.ok()) return fail(v.rc, v.error);
   a.in_bytes = (unsigned)in_bytes;
   a.w_bytes = (unsigned)w_bytes;
   // pointwise (is_1x1_, base_conv_layer.cpp:374-379) with whole quads of pixels per image: the

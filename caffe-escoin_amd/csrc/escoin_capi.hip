@@ -1072,6 +1072,15 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
     if (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE && p->kernel_choice != ESCOIN_KERNEL_DENSE)
       return launch_lowered(p, bottom_dev, bias_dev, top_dev, n_images, s);
     if (p->n_dense_groups > 0) {
+      // dense and sparse groups: what the sparse half's launch refuses for sizes is asked first, so that a refused call
+      // has written nothing (the dense half's own refusals come before its launch anyway)
+      if (!p->use_dense) {
+        if (p->tiled.enabled) {
+          if (const int rc = tiled_precheck(p, n_images)) return rc;
+        } else if (const LaunchVerdict v = generic_call_limits(p->g, n_images); !v.ok()) {
+          return fail(v.rc, v.error);
+        }
+      }
       const int rc = launch_dense(p, bottom_dev, bias_dev, top_dev, n_images, s);
       if (rc != ESCOIN_OK || p->use_dense) return rc;
     }

@@ -459,6 +459,8 @@ int tiled_export(const escoin_plan *p, std::vector<char> *out);
 int tiled_import(escoin_plan *p, const char *blob, size_t bytes, hipStream_t stream);
 int launch_tiled(const escoin_plan *p, const float *bottom, const float *bias, float *top,
                  int n_images, hipStream_t stream);
+// what launch_tiled would refuse for the call's sizes, before anything is launched (a plan that also has dense groups)
+int tiled_precheck(const escoin_plan *p, int n_images);
 const char *tiled_kernel_name(const escoin_plan *p);
 
 // sconv_lowered.hip (conv_mode LOWERED_SPARSE: im2col + CSR x dense, the lowering baseline)

@@ -112,8 +112,7 @@ static int launch_generic_t(const escoin_plan *p, const T *bottom, const T *bias
   const int npix = g.OH * g.OW;
   dim3 block(64, kWavesPerBlock, 1);
   dim3 grid((npix + 63) / 64, (g.d.M + kWavesPerBlock - 1) / kWavesPerBlock, n_images);
-  if (grid.y > 65535u || grid.z > 65535u)
-    return fail(ESCOIN_EINVAL, "generic kernel: grid dimension exceeds 65535");
+  if (const LaunchVerdict v = grid_yz_limit(kGridGeneric, grid.y, grid.z); !v.ok()) return fail(v.rc, v.error);      // (align_rules.h)
   if constexpr (sizeof(T) == 8) {
     if (g.d.fuse_relu)
       hipLaunchKernelGGL(escoin_sconv_generic_f64_kernel<true>, grid, block, 0, stream, a);

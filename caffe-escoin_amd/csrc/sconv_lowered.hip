@@ -105,7 +105,7 @@ const char *lowered_kernel_name() { return "escoin_csrmm_kernel"; }
 
 static int launch_csrmm(const CsrmmArgs &a, int batch, hipStream_t stream) {
   dim3 grid((unsigned)((a.N + 255) / 256), (unsigned)((a.M + 3) / 4), (unsigned)batch);
-  if (grid.y > 65535u || grid.z > 65535u) return fail(ESCOIN_EINVAL, "csrmm: grid dimension exceeds 65535");
+  if (const LaunchVerdict v = grid_yz_limit(kGridCsrmm, grid.y, grid.z); !v.ok()) return fail(v.rc, v.error);      // (align_rules.h)
   hipLaunchKernelGGL(escoin_csrmm_kernel, grid, dim3(256), 0, stream, a);
   ESCOIN_HIP_TRY(hipGetLastError());
   return ESCOIN_OK;
@@ -143,7 +143,7 @@ int csrmm_f64(int M, int N, int K, double alpha, const double *vals, const int *
               const double *B, double beta, double *C, hipStream_t stream) {
   (void)K;
   dim3 grid((unsigned)((N + 255) / 256), (unsigned)M, 1);
-  if (grid.y > 65535u) return fail(ESCOIN_EINVAL, "csrmm_f64: more than 65535 rows");
+  if (const LaunchVerdict v = grid_yz_limit(kGridCsrmmF64, grid.y, 1); !v.ok()) return fail(v.rc, v.error);
   hipLaunchKernelGGL(escoin_csrmm_f64_kernel, grid, dim3(256), 0, stream, M, N, alpha, vals, rowptr, colidx, B, beta, C);
   ESCOIN_HIP_TRY(hipGetLastError());
   return ESCOIN_OK;
@@ -178,7 +178,7 @@ int launch_lowered(escoin_plan *p, const float *bottom, const float *bias, float
         ia.stride_h = g.d.stride_h; ia.stride_w = g.d.stride_w; ia.dil_h = g.d.dil_h; ia.dil_w = g.d.dil_w;
         ia.in_stride = in_image;
         dim3 grid((unsigned)((npix + 255) / 256), (unsigned)g.kdim, (unsigned)nb);
-        if (grid.y > 65535u || grid.z > 65535u) return fail(ESCOIN_EINVAL, "im2col: grid dimension exceeds 65535");
+        if (const LaunchVerdict v = grid_yz_limit(kGridIm2col, grid.y, grid.z); !v.ok()) return fail(v.rc, v.error);
         hipLaunchKernelGGL(escoin_im2col_kernel, grid, dim3(256), 0, stream, ia);
         ESCOIN_HIP_TRY(hipGetLastError());
         B = p->col.get<float>();

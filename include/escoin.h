@@ -60,6 +60,33 @@ extern "C" {
 #define ESCOIN_ESTATE (-4)    /* forward before weight_align / set_csr          */
 #define ESCOIN_ENODEVICE (-5) /* no HIP device visible                          */
 
+/* ---- Size limits --------------------------------------------------------------------------------------------------
+ * Blobs are addressed in 64 bits wherever nothing below says otherwise; every limit is a host-side rule (csrc/align_rules.h,
+ * held to its edge by tests/cpp/launch_limits_check.cpp) and every refusal is ESCOIN_EINVAL with a message, before
+ * anything is launched.  Sizes of one call: n images, bottom n*C*H*W, top n*M*OH*OW floats.
+ *
+ *   what                                     limit                          beyond it
+ *   tiled / generated code: bottom of one    0xFFFFFFF0 bytes (a buffer     the call runs as consecutive launches of
+ *     launch                                 descriptor's 32-bit offsets)   (0xFFFFFFF0 - 16) / image_bytes images
+ *   tiled / generated code: one image        below 0xFFFFFFF0 bytes         refused
+ *   tiled / generated code: top of one       below 2^31 bytes for the asm   the launch stores element-wise from the
+ *     launch                                 epilogues' 32-bit offsets      generic compiled body: same results
+ *   strided pointwise (1x1, stride 2) top    below 2^31 bytes               refused
+ *   tiled: conv groups x workgroup columns   65535 (grid y)                 refused
+ *   dense MFMA kernel: bottom of the call,   below 0xFFFFFFF0 bytes each    refused
+ *     weight matrix
+ *   dense MFMA kernel: n*OH*OW               below 2^31                     refused
+ *   generic kernel: n, ceil(M / 4)           65535 each (grid z, y)         refused
+ *   LOWERED_SPARSE: rows, columns, images    65535 each (grid y, z)         refused
+ *   Backward: N, Mg; C                       65535; 4 x 65535               refused (bwd_choice)
+ *   staged weight gradient                   N*M*OH*OW, N*C*H*W < 2^31      refused when forced, AUTO takes the entry kernel
+ *   MFMA weight / data gradient, dense       N*OH*OW (N*H*W), M*Cg*KH*KW,   refused when forced (wgm_plan, dgm_plan)
+ *     weight gradient                        Cg*H*W (Mg*OH*OW) < 2^31
+ *   options "s2d", "s2b", "b2s"              bottom, top, X', T' < 2^31     the option is not taken: the plan runs as
+ *                                            elements; N*P, N' <= 65535     without it
+ * A plan whose conv groups are split between the dense and the sparse kernels asks the sparse half's limits before it
+ * launches the dense half: a refused call has written nothing. */
+
 /* Caffe::ConvMode, include/caffe/common.hpp:112.  The two direct-sparse modes differ in the
  * reference only by launch granularity (per image vs whole batch, conv_layer.cu:16-26) and produce
  * the same numbers; LOWERED_GEMM is the dense MFMA kernel, LOWERED_SPARSE the lowering comparator. */
