@@ -67,6 +67,10 @@ API_SYMBOLS = [
     # Batch-to-space (option "b2s")
     "escoin_plan_b2s_pack",
     "escoin_plan_b2s_unpack",
+    # Deconvolution (option "deconv")
+    "escoin_deconv_out_shape",
+    "escoin_plan_d2s_pack",
+    "escoin_plan_d2s_unpack",
 ]
 SOLVER_SGD, SOLVER_NESTEROV, SOLVER_ADAM = 0, 1, 2
 REG_NONE, REG_L2, REG_L1 = 0, 1, 2
@@ -95,6 +99,15 @@ class ConvDesc(C.Structure):
         """An InnerProduct layer of K inputs and M outputs at batch N: N images of K channels and one pixel, a 1x1 kernel
         (include/escoin.h "Batch-to-space")."""
         return cls(N, K, 1, 1, M, 1, 1, 0, 0, 1, 1, 1, 1, 1, int(bool(bias)), int(bool(relu)))
+
+    @classmethod
+    def deconvolution(cls, N, C, H, W, M, kernel, stride=1, pad=0, group=1, bias=True, relu=False):
+        """A Deconvolution layer for Plan(..., deconv=1): C bottom channels of H x W, M = num_output; kernel, stride and
+        pad as one int or an (h, w) pair (include/escoin.h "Deconvolution")."""
+        def hw(v):
+            return (int(v), int(v)) if np.isscalar(v) else (int(v[0]), int(v[1]))
+        (kh, kw), (sh, sw), (ph, pw) = hw(kernel), hw(stride), hw(pad)
+        return cls(N, C, H, W, M, kh, kw, ph, pw, sh, sw, 1, 1, group, int(bool(bias)), int(bool(relu)))
 
 
 class SolverDesc(C.Structure):
@@ -259,6 +272,12 @@ def lib():
     L.escoin_plan_b2s_pack.argtypes = [vp, vp, vp, vp, ip, ip, vp]
     L.escoin_plan_b2s_unpack.restype = ip
     L.escoin_plan_b2s_unpack.argtypes = [vp, vp, vp, ip, ip, ip, vp]
+    L.escoin_deconv_out_shape.restype = ip
+    L.escoin_deconv_out_shape.argtypes = [vp, vp, vp]
+    L.escoin_plan_d2s_pack.restype = ip
+    L.escoin_plan_d2s_pack.argtypes = [vp, vp, vp, vp, ip, vp]
+    L.escoin_plan_d2s_unpack.restype = ip
+    L.escoin_plan_d2s_unpack.argtypes = [vp, vp, vp, vp, ip, vp]
     L.escoin_forward.restype = ip
     L.escoin_forward.argtypes = [vp, vp, vp, vp, ip, vp]
     L.escoin_plan_export_aligned.restype = ip
@@ -375,6 +394,13 @@ def out_shape(desc):
     return oh.value, ow.value
 
 
+def deconv_out_shape(desc):
+    """The top image of the Deconvolution layer `desc` describes: stride * (in - 1) + kernel - 2 * pad per axis."""
+    oh, ow = C.c_int(), C.c_int()
+    check(lib().escoin_deconv_out_shape(C.byref(desc), C.byref(oh), C.byref(ow)), "escoin_deconv_out_shape")
+    return oh.value, ow.value
+
+
 def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -392,7 +418,9 @@ class Plan(object):
             self.set_option("conv_mode", conv_mode)
         for k, v in options.items():      # e.g. tiling_batch=256, dense_gate=1, dense_threshold_pct=30
             self.set_option(k, v)
-        self.out_hw = out_shape(desc)
+        # option "deconv": the descriptor is a Deconvolution layer's -- another top image, and blobs_[0] is C x M/g x KH x KW
+        self.deconv = bool(options.get("deconv", 0))
+        self.out_hw = deconv_out_shape(desc) if self.deconv else out_shape(desc)
 
     def close(self):
         if self._h:
@@ -706,7 +734,7 @@ class Plan(object):
 
     def get_csr(self, stretched=False):
         d = self.desc
-        mg = d.M // d.group
+        mg = (d.C if self.deconv else d.M) // d.group      # (a "deconv" plan's rows are the bottom's channels)
         nnz = self.nnz()
         f64 = self.stat("is_f64") == 1
         rp = np.zeros(d.group * (mg + 1), np.int32)
@@ -799,6 +827,31 @@ class Plan(object):
         stream = C.c_void_p(torch.cuda.current_stream(top.device).cuda_stream)
         check(lib().escoin_plan_s2b_unpack(self._h, C.c_void_p(top.data_ptr()), int(top.shape[0]), stream), "escoin_plan_s2b_unpack")
 
+    def d2s_unpack(self, top, bias=None, src=None, n_images=None):
+        """The unpack kernel of a "deconv" plan alone, on torch's current stream: the top blob from T' (src: N x M*P x H' x W';
+        default: the plan's scratch, as the last forward's inner launch left it), + bias, through ReLU on a fuse_relu plan."""
+        import torch
+        for t in (top,) + tuple(x for x in (bias, src) if x is not None):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        n = int(top.shape[0]) if n_images is None else int(n_images)
+        d = self.desc
+        assert top.numel() >= n * d.M * self.out_hw[0] * self.out_hw[1], "top too small"
+        stream = C.c_void_p(torch.cuda.current_stream(top.device).cuda_stream)
+        check(lib().escoin_plan_d2s_unpack(self._h, None if src is None else C.c_void_p(src.data_ptr()),
+                                           None if bias is None else C.c_void_p(bias.data_ptr()), C.c_void_p(top.data_ptr()), n, stream),
+              "escoin_plan_d2s_unpack")
+
+    def d2s_pack(self, top_diff, top=None, dst=None, n_images=None):
+        """The pack kernel of a "deconv" plan alone: G' (dst: N x M*P x H' x W'; default: the plan's scratch) from top_diff,
+        gated by top > 0 on a fuse_relu plan."""
+        import torch
+        for t in (top_diff,) + tuple(x for x in (top, dst) if x is not None):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        n = int(top_diff.shape[0]) if n_images is None else int(n_images)
+        stream = C.c_void_p(torch.cuda.current_stream(top_diff.device).cuda_stream)
+        check(lib().escoin_plan_d2s_pack(self._h, C.c_void_p(top_diff.data_ptr()), None if top is None else C.c_void_p(top.data_ptr()),
+                                         None if dst is None else C.c_void_p(dst.data_ptr()), n, stream), "escoin_plan_d2s_pack")
+
     def b2s_pack(self, src, dst, mask=None, top_side=False, n_images=None):
         """One transpose of a "b2s" plan alone, on the caller's tensors and torch's current stream: src (N x CH, CH = M on
         the top side, C on the bottom side; gated by mask > 0 where mask is given) into dst, the ceil(n_images / B) x CH x B
@@ -858,6 +911,11 @@ class Plan(object):
         d = self.desc
         return (d.C // d.group, d.KH, d.KW)
 
+    def _weight_shape(self):
+        """blobs_[0]: M x C/g x KH x KW, or C x M/g x KH x KW on a "deconv" plan."""
+        d = self.desc
+        return (d.C, d.M // d.group, d.KH, d.KW) if self.deconv else (d.M,) + self._grad_shapes()
+
     def backward(self, top_diff, bottom=None, top=None, bottom_diff=True, weight_diff=None, bias_diff=None,
                  values_diff=None):
         """Backward_gpu on torch CUDA tensors, on torch's current stream.  bottom_diff: True = a new tensor, a tensor =
@@ -886,7 +944,7 @@ class Plan(object):
         if compact and weight_diff is not None and weight_diff is not False:
             raise EscoinError("backward: weight_diff and values_diff are two layouts of one gradient: ask for one")
         bd = _new_or(bottom_diff, (n, d.C, d.H, d.W), False)
-        wd = _new_or(values_diff, (self.nnz(),), True) if compact else _new_or(weight_diff, (d.M,) + self._grad_shapes(), True)
+        wd = _new_or(values_diff, (self.nnz(),), True) if compact else _new_or(weight_diff, self._weight_shape(), True)
         bsd = _new_or(bias_diff, (d.M,), True)
         for t in (bottom, top):
             if t is not None:
@@ -923,7 +981,7 @@ class Plan(object):
         if compact and weight_diff is not None and weight_diff is not False:
             raise EscoinError("backward_cpu: weight_diff and values_diff are two layouts of one gradient: ask for one")
         bd = _new_or(bottom_diff, (n, d.C, d.H, d.W), False)
-        wd = _new_or(values_diff, (self.nnz(),), True) if compact else _new_or(weight_diff, (d.M,) + self._grad_shapes(), True)
+        wd = _new_or(values_diff, (self.nnz(),), True) if compact else _new_or(weight_diff, self._weight_shape(), True)
         bsd = _new_or(bias_diff, (d.M,), True)
         x = None if bottom is None else np.ascontiguousarray(bottom, dt)
         t = None if top is None else np.ascontiguousarray(top, dt)

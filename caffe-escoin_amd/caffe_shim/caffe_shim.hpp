@@ -444,9 +444,11 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_create(&d, &fresh));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_kernel", Caffe::wgrad_kernel()));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "backward_kernel", Caffe::backward_kernel()));
-      ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2d", Caffe::s2d() ? 1 : 0));
-      ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2b", Caffe::s2b() ? 1 : 0));
-      ESCOIN_CHECK(escoin_plan_set_option(fresh, "b2s", Caffe::b2s() ? 1 : 0));
+      // (a Deconvolution layer's plan is option "deconv"'s, which does not combine with the other derived-plan options)
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "deconv", deconv_ ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2d", Caffe::s2d() && !deconv_ ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2b", Caffe::s2b() && !deconv_ ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "b2s", Caffe::b2s() && !deconv_ ? 1 : 0));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;
@@ -772,6 +774,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
   Caffe::ConvMode aligned_mode_ = Caffe::SCONV_PAR;
   int num_, channels_, group_, num_output_;
   bool bias_term_, fuse_relu_;
+  bool deconv_ = false;   // DeconvolutionLayer: the plan reads the descriptor as a Deconvolution layer's (option "deconv")
   int planned_num_;
   int bottom_dim_ = 0, top_dim_ = 0;
 };
@@ -903,8 +906,51 @@ class InnerProductLayer : public ConvolutionLayer<Dtype> {
   int K_, axis_ = 1;
 };
 
+// deconv_layer.hpp / .cpp / .cu: the transposed convolution (forward = the base layer's backward_*_gemm, backward =
+// forward_*_gemm + weight_*_gemm).  blobs_[0] is channels x num_output / group x kernel_h x kernel_w (conv_out_channels_ is
+// the bottom's channel count); the top is stride * (in - 1) + kernel - 2 * pad (compute_output_shape at dilation 1).  The
+// layer runs through plan option "deconv" (include/escoin.h "Deconvolution") in both brews: WeightAlign, Forward, Backward,
+// WeightUpdate and SolverUpdate are the convolution layer's code on the same C entry points; Prune, Rewire and
+// DenseWeightDiff are refused by the library.  Dtype = double aborts in LayerSetUp with the library's message.
+template <typename Dtype>
+class DeconvolutionLayer : public ConvolutionLayer<Dtype> {
+ public:
+  explicit DeconvolutionLayer(const LayerParameter &param) : ConvolutionLayer<Dtype>(param) { this->deconv_ = true; }
+  virtual inline const char *type() const { return "Deconvolution"; }
+
+  virtual void LayerSetUp(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &top) {
+    if (sizeof(Dtype) != 4) {
+      fprintf(stderr, "DeconvolutionLayer %s: option \"deconv\": a double plan has no deconvolution (the inner kernels are fp32)\n",
+              this->layer_param_.name.c_str());
+      abort();
+    }
+    BaseConvolutionLayer<Dtype>::LayerSetUp(bottom, top);
+    const ConvolutionParameter &cp = this->layer_param_.convolution_param;
+    vector<int> wshape(4);      // deconv_layer: conv_out_channels_ = channels_, conv_in_channels_ = num_output_
+    wshape[0] = this->channels_; wshape[1] = this->num_output_ / this->group_; wshape[2] = cp.kernel_h; wshape[3] = cp.kernel_w;
+    this->blobs_[0].reset(new Blob<Dtype>(wshape));
+  }
+
+  virtual void Reshape(const vector<Blob<Dtype> *> &bottom, const vector<Blob<Dtype> *> &top) {
+    const ConvolutionParameter &cp = this->layer_param_.convolution_param;
+    this->num_ = bottom[0]->shape(0);
+    ESC_CHECK(bottom[0]->shape(1) == this->channels_);
+    for (size_t i = 1; i < bottom.size(); ++i) ESC_CHECK(bottom[0]->shape() == bottom[i]->shape());
+    const escoin_conv_desc d = this->desc(bottom[0], cp);
+    int oh = 0, ow = 0;
+    compute_output_shape(d, &oh, &ow);
+    for (size_t i = 0; i < top.size(); ++i) top[i]->Reshape(this->num_, this->num_output_, oh, ow);
+    this->bottom_dim_ = bottom[0]->count(1, 4);
+    this->top_dim_ = top[0]->count(1, 4);
+    this->plan_for(d);
+  }
+
+  // deconv_layer.cpp:7-23
+  static void compute_output_shape(const escoin_conv_desc &d, int *oh, int *ow) { ESCOIN_CHECK(escoin_deconv_out_shape(&d, oh, ow)); }
+};
+
 // layer_factory.hpp:53-110 / layer_factory.cpp:74: the creator registry `Net::Init` looks layer
-// types up in (LayerRegistry<Dtype>::CreateLayer(param)), with the three creators this path owns.
+// types up in (LayerRegistry<Dtype>::CreateLayer(param)), with the four creators this path owns.
 template <typename Dtype>
 class LayerRegistry {
  public:
@@ -913,7 +959,8 @@ class LayerRegistry {
     if (param.type == "Convolution") return shared_ptr<Layer<Dtype> >(new ConvolutionLayer<Dtype>(param));
     if (param.type == "ConvolutionReLU") return shared_ptr<Layer<Dtype> >(new ConvolutionReLULayer<Dtype>(param));
     if (param.type == "InnerProduct") return shared_ptr<Layer<Dtype> >(new InnerProductLayer<Dtype>(param));
-    fprintf(stderr, "Unknown layer type: %s (known types: Convolution, ConvolutionReLU, InnerProduct)\n", param.type.c_str());
+    if (param.type == "Deconvolution") return shared_ptr<Layer<Dtype> >(new DeconvolutionLayer<Dtype>(param));
+    fprintf(stderr, "Unknown layer type: %s (known types: Convolution, ConvolutionReLU, InnerProduct, Deconvolution)\n", param.type.c_str());
     abort();   // LOG(FATAL), layer_factory.hpp:79-80
   }
   static vector<string> LayerTypeList() {
@@ -921,6 +968,7 @@ class LayerRegistry {
     v.push_back("Convolution");
     v.push_back("ConvolutionReLU");
     v.push_back("InnerProduct");
+    v.push_back("Deconvolution");
     return v;
   }
 };

@@ -29,6 +29,9 @@ import numpy as np
 
 V1_CONVOLUTION = 4
 V1_INNER_PRODUCT = 14
+V1_DECONVOLUTION = 39
+# Deconvolution layers (LayerParameter type "Deconvolution", V1LayerParameter type 39) carry the same ConvolutionParameter;
+# blobs_[0] is C x num_output/group x KH x KW: its first axis is the BOTTOM's channel count (deconv_layer.cpp).
 # InnerProduct layers: LayerParameter.inner_product_param = 117, V1LayerParameter.inner_product_param = 17;
 # InnerProductParameter num_output 1, bias_term 2, axis 5 (default 1), transpose 6 (default false).  blobs_[0] is
 # num_output x K; files written before BlobShape carry it as the legacy 1 x 1 x num_output x K.
@@ -208,6 +211,29 @@ class CaffeLayer(object):
     def is_inner_product(self):
         return self.type in ("InnerProduct", V1_INNER_PRODUCT)
 
+    @property
+    def is_deconvolution(self):
+        return self.type in ("Deconvolution", V1_DECONVOLUTION)
+
+    def _deconv_weight(self):
+        if not self.is_deconvolution or not self.blobs or not self.conv_param:
+            raise ValueError("layer %s is no Deconvolution layer with blobs and a convolution_param" % self.name)
+        w, p = self.blobs[0], self.conv_param
+        if w.ndim != 4:
+            raise ValueError("layer %s: weight blob has %d axes" % (self.name, w.ndim))
+        g, m = max(int(p["group"]), 1), int(p["num_output"])
+        if m % g or w.shape[0] % g or tuple(w.shape[1:]) != (m // g, p["kernel_h"], p["kernel_w"]):
+            raise ValueError("layer %s: Deconvolution weight blob %s is not C x %d/%d x %d x %d" %
+                             (self.name, w.shape, m, g, p["kernel_h"], p["kernel_w"]))
+        return w
+
+    def deconv_desc(self, N, H, W, relu=False):
+        """The 16 ints of escoin_conv_desc for this Deconvolution layer at batch N on an H x W bottom, in ConvDesc's field
+        order, for Plan(ConvDesc(*layer.deconv_desc(N, H, W)), deconv=1): C is the weight blob's first axis."""
+        w, p = self._deconv_weight(), self.conv_param
+        return (int(N), int(w.shape[0]), int(H), int(W), int(p["num_output"]), p["kernel_h"], p["kernel_w"], p["pad_h"], p["pad_w"],
+                p["stride_h"], p["stride_w"], p["dilation_h"], p["dilation_w"], p["group"], int(len(self.blobs) > 1), int(bool(relu)))
+
     def _ip_weight(self):
         if not self.is_inner_product or not self.blobs:
             raise ValueError("layer %s is no InnerProduct layer with blobs" % self.name)
@@ -303,6 +329,13 @@ def conv_weights(layers):
     return out
 
 
+def deconv_weights(layers):
+    """{layer name: (weight C x num_output/g x KH x KW, bias or None)} for the Deconvolution layers that carry blobs; the
+    weight blob is checked against the layer's ConvolutionParameter."""
+    return {l.name: (l._deconv_weight(), l.blobs[1].reshape(-1) if len(l.blobs) > 1 else None)
+            for l in layers if l.is_deconvolution and l.blobs}
+
+
 def inner_product_weights(layers):
     """{layer name: (weight num_output x K, bias or None)} for the InnerProduct layers that carry blobs."""
     return {l.name: (l.ip_weight, l.ip_bias) for l in layers if l.is_inner_product and l.blobs}
@@ -350,7 +383,8 @@ def serialize_net(name, layers, v1=False):
     for l in layers:
         if v1:
             body = _enc_len(4, l.name.encode("utf-8"))
-            body += _enc_uint(5, V1_CONVOLUTION if l.is_convolution else V1_INNER_PRODUCT if l.is_inner_product else 0)
+            body += _enc_uint(5, V1_CONVOLUTION if l.is_convolution else V1_INNER_PRODUCT if l.is_inner_product else
+                              V1_DECONVOLUTION if l.is_deconvolution else 0)
             for b in l.blobs:
                 body += _enc_len(6, _enc_blob(b, legacy_dims=True))
             if l.conv_param:

@@ -815,4 +815,46 @@ bool b2s_plan(const Geometry &g, bool is_f64, int block, int /*n_cu*/, B2sPlan *
   return true;
 }
 
+bool d2s_plan(const escoin_conv_desc &d, bool is_f64, D2sPlan *dp) {
+  D2sPlan p;
+  auto refuse = [&](const char *why) { p.error = why; *dp = p; return false; };
+  if (is_f64) return refuse("option \"deconv\": a double plan has no deconvolution (the inner kernels are fp32)");
+  if (d.dil_h != 1 || d.dil_w != 1) return refuse("option \"deconv\": a dilation other than 1 is not served");
+  const long oh = (long)d.stride_h * (d.H - 1) + d.KH - 2L * d.pad_h, ow = (long)d.stride_w * (d.W - 1) + d.KW - 2L * d.pad_w;
+  if (oh < 1 || ow < 1) return refuse("option \"deconv\": empty top (OH or OW < 1: the pad crops the whole image)");
+  if (d.M / d.group > 32767) return refuse("option \"deconv\": more than 32767 output channels per group");
+  const double two31 = 2147483648.0;
+  const double Pd = (double)d.stride_h * d.stride_w;
+  if ((double)d.M * Pd > (double)kD2sMaxInnerChannels)
+    return refuse("option \"deconv\": M * stride_h * stride_w exceeds the inner plan's channel limit (a grid axis)");
+  const int kh = (d.KH + d.stride_h - 1) / d.stride_h, kw = (d.KW + d.stride_w - 1) / d.stride_w;
+  const long hi = (long)d.H + kh - 1, wi = (long)d.W + kw - 1;
+  const double top_floats = (double)d.N * d.M * (double)oh * (double)ow;
+  if (top_floats >= two31) return refuse("option \"deconv\": the top blob reaches 2^31 elements");
+  const double t_floats = (double)d.N * d.M * Pd * (double)hi * (double)wi;
+  if (t_floats >= two31) return refuse("option \"deconv\": the inner top T' reaches 2^31 elements");
+  if ((double)d.M * Pd * (d.C / d.group) * kh * (double)kw >= two31)
+    return refuse("option \"deconv\": the inner weight matrix reaches 2^31 elements");
+  p.OH = (int)oh; p.OW = (int)ow;
+  p.sh = d.stride_h; p.sw = d.stride_w; p.P = d.stride_h * d.stride_w;
+  escoin_conv_desc &in = p.inner;
+  in = d;
+  in.M = d.M * p.P;
+  in.KH = kh; in.KW = kw;
+  in.pad_h = kh - 1; in.pad_w = kw - 1;
+  in.stride_h = in.stride_w = 1;
+  in.dil_h = in.dil_w = 1;
+  in.fuse_relu = 0;                  // (the unpack kernel adds the bias and applies the ReLU; has_bias stays the outer plan's)
+  escoin_conv_desc &mi = p.mirror;
+  mi = d;
+  mi.C = d.M; mi.M = d.C;
+  mi.H = p.OH; mi.W = p.OW;
+  p.t_floats = (long)t_floats;
+  p.top_floats = (long)top_floats;
+  p.unpack_rows = (long)d.N * d.M * oh;
+  p.pack_rows = (long)d.N * d.M * p.P * hi;
+  *dp = p;
+  return true;
+}
+
 }  // namespace escoin

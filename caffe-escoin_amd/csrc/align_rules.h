@@ -400,5 +400,33 @@ constexpr int kB2sMinBlock = 4, kB2sMaxBlock = 256;
 // does not.  n_cu is the device's compute units, which the shipped rule does not weigh.
 bool b2s_plan(const Geometry &g, bool is_f64, int block, int n_cu, B2sPlan *bp);
 
+// ---- Deconvolution layers on the stride-1 kernels via depth-to-space (d2s.hip, plan option "deconv") ----------------
+// A stride-(sh, sw) deconvolution is a stride-1 convolution of the bottom itself with P = sh * sw times the output
+// channels, one per output phase, followed by a depth-to-space interleave (include/escoin.h "Deconvolution"): inner
+// channel m' = (m * sh + ph) * sw + pw, kernel KH' x KW' = ceil(KH / sh) x ceil(KW / sw), pad (KH' - 1, KW' - 1), so the
+// inner top is H' x W' = (H + KH' - 1) x (W + KW' - 1); top[m][oh][ow] = T'[m'(m, hp % sh, wp % sw)][hp / sh][wp / sw]
+// with hp = oh + pad_h, wp = ow + pad_w.  All P phases are inner channels, those without a tap (sh > KH) included.
+inline int deconv_out_dim(int in, int k, int pad, int stride) { return stride * (in - 1) + k - 2 * pad; }
+struct D2sPlan {
+  const char *error = "";         // why the option does not serve the layer ("" where it does)
+  int OH = 0, OW = 0;             // the top image
+  int sh = 0, sw = 0, P = 0;      // the strides and the phases per output channel
+  escoin_conv_desc inner = {};    // the inner plan's descriptor
+  escoin_conv_desc mirror = {};   // the convolution whose backward this layer is (M <-> C, H x W <-> OH x OW): the
+                                  // geometry of the layer's weight matrix, rows = the bottom's channels
+  long t_floats = 0;              // N * M * P * H' * W': the inner top T' (and the rearranged top_diff G', in the same scratch)
+  long top_floats = 0;            // N * M * OH * OW
+  // the launches of the full batch: unpack walks the top's rows (N * M * OH of OW elements), pack the rows of G'
+  // (N * M * P * H' of W' elements); each below 2^31 with the blobs they index
+  long unpack_rows = 0, pack_rows = 0;
+};
+// The most inner output channels M * P: the generic kernel's grid takes four channels per block of an axis of 65535.
+constexpr long kD2sMaxInnerChannels = 4L * 65535;
+// Whether option "deconv" serves the layer `d` describes (read as Caffe's DeconvolutionLayer), and the plan where it does;
+// where not, dp->error names the reason: a double plan, a dilation other than 1, an empty top, top / T' / the inner weight
+// matrix (M * P * Cg * KH' * KW') at or above 2^31 elements, more than kD2sMaxInnerChannels inner channels, more than 32767
+// output channels per group (the mirror convolution's input channels).
+bool d2s_plan(const escoin_conv_desc &d, bool is_f64, D2sPlan *dp);
+
 }  // namespace escoin
 #endif  // ESCOIN_ALIGN_RULES_H_

@@ -248,6 +248,52 @@ DerivedCsr s2d_csr(const CsrView &v, const S2dPlan &sp) {
   return t;
 }
 
+DerivedCsr d2s_csr(const CsrView &v, const D2sPlan &dp) {
+  const Geometry &g = *v.g;      // the mirror convolution's: g.Mg = the bottom's channels per group, g.Cg = the top's
+  const escoin_conv_desc &d = g.d;
+  const int kh = dp.inner.KH, kw = dp.inner.KW, sh = dp.sh, sw = dp.sw;
+  const int rows_g = g.Cg * dp.P;
+  DerivedCsr t;
+  t.rowptr.assign((size_t)d.group * (rows_g + 1), 0);
+  t.nnz_g.assign(d.group, 0);
+  t.colidx.resize((size_t)v.nnz());
+  t.src.resize((size_t)v.nnz());
+  // a counting sort by inner row, then each row by (inner column, outer entry): the columns of a row are distinct, so the
+  // order is a function of the pattern alone
+  std::vector<std::pair<int, int>> row;
+  long base = 0;
+  for (int grp = 0; grp < d.group; ++grp) {
+    const std::vector<int> &rp = (*v.rowptr)[grp], &ci = (*v.colidx)[grp];
+    int *irp = t.rowptr.data() + (size_t)grp * (rows_g + 1);
+    auto inner_row = [&](int col) {
+      const Tap tap = decode_tap(col, d.KH, d.KW);
+      return (tap.ic * sh + tap.kr % sh) * sw + tap.kc % sw;
+    };
+    for (size_t j = 0; j < ci.size(); ++j) ++irp[inner_row(ci[j]) + 1];
+    for (int r = 0; r < rows_g; ++r) irp[r + 1] += irp[r];
+    std::vector<int> at(irp, irp + rows_g);
+    for (int cl = 0; cl < g.Mg; ++cl)
+      for (int j = rp[cl]; j < rp[cl + 1]; ++j) {
+        const Tap tap = decode_tap(ci[j], d.KH, d.KW);
+        const size_t k = (size_t)base + (size_t)at[inner_row(ci[j])]++;
+        t.colidx[k] = (cl * kh + (kh - 1 - tap.kr / sh)) * kw + (kw - 1 - tap.kc / sw);
+        t.src[k] = (int)(base + j);
+      }
+    for (int r = 0; r < rows_g; ++r) {
+      row.clear();
+      for (int k = irp[r]; k < irp[r + 1]; ++k) row.emplace_back(t.colidx[(size_t)base + k], t.src[(size_t)base + k]);
+      std::sort(row.begin(), row.end());
+      for (int k = irp[r]; k < irp[r + 1]; ++k) {
+        t.colidx[(size_t)base + k] = row[(size_t)(k - irp[r])].first;
+        t.src[(size_t)base + k] = row[(size_t)(k - irp[r])].second;
+      }
+    }
+    t.nnz_g[grp] = irp[rows_g];
+    base += (long)ci.size();
+  }
+  return t;
+}
+
 bool compose_maps(const std::vector<int> *outer, const std::vector<int> *inner, long n, std::vector<int> *out) {
   if (n < 0 || (outer && (long)outer->size() != n)) return false;
   std::vector<int> r(inner ? inner->size() : (size_t)n);

@@ -139,6 +139,15 @@ DgmTables dgrad_mfma_tables(const CsrView &v, const DgmPlan &plan);
 struct S2dPlan;
 DerivedCsr s2d_csr(const CsrView &v, const S2dPlan &sp);
 
+// The CSR of the inner stride-1 plan of option "deconv" (align_rules.h d2s_plan), in set_csr's form.  `v` is the layer's own
+// CSR, held in the mirror convolution's geometry (dp.mirror): per group, row = bottom channel cl, column = ml * KH * KW +
+// kr * KW + kc.  Entry (cl, ml, kr, kc) becomes the entry of inner row m' = (ml * sh + kr % sh) * sw + kc % sw (group-local,
+// Mg * P rows per group) at column (cl * KH' + (KH' - 1 - kr / sh)) * KW' + (KW' - 1 - kc / sw), ascending within the row.
+// rowptr [group * (Mg * P + 1)] group-relative, colidx [nnz], nnz_g [group], src [nnz]: inner entry k holds the value of
+// outer entry src[k] (flat index, groups concatenated).  The map is injective; the rows of phases without a tap are empty.
+struct D2sPlan;
+DerivedCsr d2s_csr(const CsrView &v, const D2sPlan &dp);
+
 // Two entry maps in a row, out[k] = outer[inner[k]]: entry k holds the value of entry inner[k] of a plan of n entries, whose
 // entry j holds that of entry outer[j].  A null side is the identity over [0, n).  false, and *out as it was: `outer` has
 // not n elements, or an index of `inner` lies outside [0, n).

@@ -113,6 +113,7 @@ static int dwg_build(escoin_plan *p, hipStream_t stream) {
 static int dense_wgrad_gpu(escoin_plan *p, const float *bottom, const float *top, const float *top_diff, float *dense_diff,
                            int n_images, int accumulate, void *stream_v) {
   if (!p) return fail(ESCOIN_EINVAL, "null plan");
+  if (const int rc = refuse_deconv(p, "escoin_dense_wgrad")) return rc;
   if (!p->aligned) return fail(ESCOIN_ESTATE, "dense_wgrad called before weight_align / set_csr");
   if (p->is_f64) return fail(ESCOIN_EINVAL, kNoDouble);
   if (const int rc = check_plan_device(p, "dense_wgrad")) return rc;

@@ -16,6 +16,7 @@ template <typename T>
 static int dense_wgrad_cpu(escoin_plan *p, const T *bottom, const T *top, const T *top_diff, T *dense_diff, int n_images,
                            int accumulate, int n_threads) {
   if (!p) return fail(ESCOIN_EINVAL, "null plan");
+  if (const int rc = refuse_deconv(p, "escoin_dense_wgrad_cpu")) return rc;
   if (!p->host_aligned) return fail(ESCOIN_ESTATE, "dense_wgrad_cpu called before weight_align / set_csr");
   if (p->is_f64 != (sizeof(T) == 8))
     return fail(ESCOIN_ESTATE, p->is_f64 ? "dense_wgrad_cpu: the plan holds double weights (use the _f64 entry point)"

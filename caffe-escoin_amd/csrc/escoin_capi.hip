@@ -21,6 +21,8 @@ static thread_local std::string g_last_error;
 S2dHooks g_s2d_hooks = {nullptr, nullptr, nullptr};
 S2bHooks g_s2b_hooks = {nullptr, nullptr, nullptr, nullptr};
 B2sHooks g_b2s_hooks = {nullptr, nullptr, nullptr, nullptr};
+D2sHooks g_d2s_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+D2sCpuHooks g_d2s_cpu_hooks = {nullptr, nullptr};
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 
@@ -106,12 +108,19 @@ DeviceBytes device_bytes(const escoin_plan *p) {
     b.bwd += in.bwd;
     b.dwg += in.dwg;      // (escoin_dense_wgrad runs on the inner plan)
   }
+  if (const D2sState *ds = p->d2s_state.get()) {
+    // the T' / G' scratch, the gradients' scratches and maps, and the inner plan's own owners, as for "s2d"
+    const DeviceBytes in = device_bytes(ds->inner.plan.get());
+    b.fwd += ds->scratch_bytes() + in.fwd;
+    b.bwd += in.bwd;
+  }
   return b;
 }
 
 long bwd_stat(const escoin_plan *p, const char *key) {
   // option "b2s": the whole backward is the inner plan's, and so are its facts -- but for the bytes, which device_bytes sums
   if (p->b2s_state && strcmp(key, "bwd_device_bytes") != 0) return bwd_stat(p->b2s_state->inner.plan.get(), key);
+  if (p->d2s_state && strcmp(key, "bwd_device_bytes") != 0) return bwd_stat(p->d2s_state->inner.plan.get(), key);   // (option "deconv": likewise)
   const BwdState *s = p->bwd.get();
   if (!strcmp(key, "bwd_data_kernel")) {
     if (!s) return fail(ESCOIN_ESTATE, "bwd_data_kernel: no backward has run on this alignment");
@@ -165,6 +174,7 @@ static void free_device(escoin_plan *p) {
   p->s2d_state.reset();
   p->s2b_state.reset();
   p->b2s_state.reset();
+  p->d2s_state.reset();
   p->gen = GenericArrays();
   tiled_release(p);
   p->col.reset();
@@ -294,6 +304,47 @@ static int b2s_build(escoin_plan *p, const B2sPlan &bp, hipStream_t stream) {
   return ESCOIN_OK;
 }
 
+// What every align of an option "deconv" plan asks first (the device aligns, and escoin_weight_align_cpu): whether d2s_plan
+// serves the layer for this Dtype, and that no other derived-plan option is set.  ESCOIN_OK on other plans.
+int deconv_precheck(const escoin_plan *p, bool is_f64) {
+  if (!p->deconv) return ESCOIN_OK;
+  D2sPlan dp;
+  if (!d2s_plan(p->user_desc, is_f64, &dp)) return fail(ESCOIN_EINVAL, dp.error);
+  if (p->s2d || p->s2b || p->b2s) return fail(ESCOIN_EINVAL, "option \"deconv\" does not combine with \"s2d\", \"s2b\" or \"b2s\"");
+  return ESCOIN_OK;
+}
+
+// Option "deconv" (include/escoin.h "Deconvolution"): the inner stride-1 plan of M * P output channels with the plan's kernel,
+// backward and weight-gradient options, aligned on d2s_csr of the plan's CSR, the T' / G' scratch, and what the backward's
+// tail needs: the two gradient scratches and the entry map and blobs_[0] positions on the device.  The plan itself keeps the
+// generic arrays alone, as under "s2d" (gen.vals is the value array of the in-place updates); no kernel reads them.
+static int d2s_build(escoin_plan *p, const D2sPlan &dp, hipStream_t stream) {
+  if (!g_d2s_hooks.pack || !g_d2s_hooks.unpack) return fail(ESCOIN_EINVAL, "option \"deconv\": this build does not carry the depth-to-space kernels");
+  p->d2s_state.reset(new D2sState());
+  D2sState *ds = p->d2s_state.get();
+  ds->dp = dp;
+  int rc = build_derived_plan(p, dp.inner, p->kernel_choice, p->bwd_kernel, d2s_csr(csr_view(p), dp), stream, &ds->inner, -1, true);
+  if (rc != ESCOIN_OK) return rc;
+  escoin_plan *ip = ds->inner.plan.get();
+  if (p->conv_mode != ip->conv_mode && (rc = escoin_plan_set_option(ip, "conv_mode", p->conv_mode)) != ESCOIN_OK) return rc;
+  const size_t nz = (size_t)std::max<long>(plan_nnz(p), 1);
+  ESCOIN_HIP_TRY(ds->t.alloc(sizeof(float) * (size_t)dp.t_floats));
+  ESCOIN_HIP_TRY(ds->wv.alloc(sizeof(float) * nz));
+  ESCOIN_HIP_TRY(ds->bv.alloc(sizeof(float) * (size_t)dp.inner.M));
+  std::vector<int> src(ds->inner.src), wpos(nz, 0);
+  const std::vector<int> at = dense_positions(csr_view(p), p->g.kdim);
+  for (size_t k = 0; k < src.size(); ++k) wpos[k] = at[(size_t)src[k]];
+  src.resize(nz, 0);
+  ESCOIN_HIP_TRY(ds->src.upload(src, stream));
+  ESCOIN_HIP_TRY(ds->wpos.upload(wpos, stream));
+  ESCOIN_HIP_TRY(hipStreamSynchronize(stream));  // host vectors die at scope exit
+  p->n_dense_groups = 0; p->n_sparse_groups = p->g.d.group; p->use_dense = false;
+  p->dense_mask = 0; p->sparse_mask = ~0ull; p->small_rule = 0; p->import_fast = false;
+  p->kernel_name = std::string(escoin_plan_kernel_name(ip)) + " + " + g_d2s_hooks.unpack_kernel_name;
+  p->aligned = true;
+  return ESCOIN_OK;
+}
+
 // Uploads the CSR held in p->rowptr/colidx/values and builds the kernel-specific
 // streams.  Shared tail of escoin_weight_align and escoin_plan_set_csr.
 //   jit_blob: the generated-code section of a persisted aligned form (escoin_plan_import_aligned), tried
@@ -304,6 +355,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     return fail(ESCOIN_ENODEVICE, "no HIP device: escoin_weight_align / set_csr / import_aligned prepare the GPU path (Caffe::CPU mode has its own entry points: escoin_weight_align_cpu, escoin_forward_cpu)");
   ESCOIN_HIP_TRY(hipGetDevice(&p->device));
   free_device(p);
+  if (const int rc = deconv_precheck(p, p->is_f64)) return rc;
   const Geometry &g = p->g;
   const int rc_gen = p->is_f64 ? upload_generic<double>(p, stream) : upload_generic<float>(p, stream);
   if (rc_gen != ESCOIN_OK) return rc_gen;
@@ -316,6 +368,15 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     p->kernel_name = generic_kernel_name_f64(g.d.fuse_relu != 0);
     p->aligned = true;
     return ESCOIN_OK;
+  }
+  // option "deconv": the layer runs through the stride-1 inner plan in every conv_mode (the inner plan takes the mode); there
+  // is no kernel of the plan's own to fall back to
+  if (p->deconv) {
+    D2sPlan d2p;
+    d2s_plan(p->user_desc, false, &d2p);      // (deconv_precheck has asked)
+    const int rc = d2s_build(p, d2p, stream);
+    if (rc != ESCOIN_OK) p->d2s_state.reset();
+    return rc;
   }
   const bool direct_mode = p->conv_mode == ESCOIN_CONV_MODE_SCONV || p->conv_mode == ESCOIN_CONV_MODE_SCONV_PAR;
   // option "b2s": an inner-product layer runs through a pointwise inner plan whose pixel axis is the batch.  Asked first: a
@@ -465,6 +526,7 @@ void csr_from_dense(escoin_plan *p, const T *w) {
     }
   }
   p->cpu_off_valid = false;
+  p->cpu_inner.plan.reset();
   p->host_aligned = true;
 }
 template void csr_from_dense<float>(escoin_plan *, const float *);
@@ -473,6 +535,7 @@ template void csr_from_dense<double>(escoin_plan *, const double *);
 template <typename T>
 static int weight_align_t(escoin_plan *p, const T *dense_w, int w_on_device, void *stream) {
   if (!p || !dense_w) return fail(ESCOIN_EINVAL, "null argument");
+  if (const int rc = deconv_precheck(p, sizeof(T) == 8)) return rc;     // (before anything is read through the geometry)
   const auto t_start = std::chrono::steady_clock::now();
   const Geometry &g = p->g;
   const size_t count = (size_t)g.d.M * g.kdim;
@@ -497,6 +560,8 @@ template <typename T>
 static int set_csr_t(escoin_plan *p, const int *rowptr, const int *colidx, const T *values, const int *nnz_per_group,
                      void *stream) {
   const auto t_start = std::chrono::steady_clock::now();
+  if (p)
+    if (const int rc = deconv_precheck(p, sizeof(T) == 8)) return rc;
   const int rc = set_csr_host<T>(p, rowptr, colidx, values, nnz_per_group);
   if (rc != ESCOIN_OK) return rc;
   const int rc2 = upload(p, (hipStream_t)stream);
@@ -551,6 +616,21 @@ int escoin_out_shape(const escoin_conv_desc *desc, int *out_h, int *out_w) {
   return ESCOIN_OK;
 }
 
+int escoin_deconv_out_shape(const escoin_conv_desc *desc, int *out_h, int *out_w) {
+  if (!desc) return fail(ESCOIN_EINVAL, "null descriptor");
+  if (desc->N < 1 || desc->C < 1 || desc->H < 1 || desc->W < 1 || desc->M < 1 || desc->KH < 1 || desc->KW < 1)
+    return fail(ESCOIN_EINVAL, "non-positive dimension");
+  if (desc->pad_h < 0 || desc->pad_w < 0 || desc->stride_h < 1 || desc->stride_w < 1 || desc->dil_h < 1 || desc->dil_w < 1 || desc->group < 1)
+    return fail(ESCOIN_EINVAL, "bad pad/stride/dilation/group");
+  // deconv_layer.cpp compute_output_shape: stride * (in - 1) + dilation * (kernel - 1) + 1 - 2 * pad
+  const long oh = (long)desc->stride_h * (desc->H - 1) + (long)desc->dil_h * (desc->KH - 1) + 1 - 2L * desc->pad_h;
+  const long ow = (long)desc->stride_w * (desc->W - 1) + (long)desc->dil_w * (desc->KW - 1) + 1 - 2L * desc->pad_w;
+  if (oh < 1 || ow < 1 || oh > 0x7fffffffL || ow > 0x7fffffffL) return fail(ESCOIN_EINVAL, "empty or oversized output");
+  if (out_h) *out_h = (int)oh;
+  if (out_w) *out_w = (int)ow;
+  return ESCOIN_OK;
+}
+
 long escoin_padded_len(const escoin_conv_desc *d) {
   if (!d) return fail(ESCOIN_EINVAL, "null descriptor");
   // base_conv_layer.cpp:71, plus the pad_w floats that formula forgets when pad_h == 0 < pad_w: the last row's right
@@ -571,6 +651,7 @@ int escoin_plan_create(const escoin_conv_desc *desc, escoin_plan **plan) {
     escoin_plan *p = new (std::nothrow) escoin_plan();
     if (!p) return fail(ESCOIN_ENOMEM, "out of host memory");
     p->g = g;
+    p->user_desc = *desc;
     p->rowptr.assign(g.d.group, std::vector<int>(g.Mg + 1, 0));
     p->colidx.assign(g.d.group, std::vector<int>());
     p->values.assign(g.d.group, std::vector<float>());
@@ -606,6 +687,20 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "b2s must be 0 or 1");
       if (p->aligned || p->host_aligned) return fail(ESCOIN_ESTATE, "b2s must be set before weight_align / weight_align_cpu / set_csr");
       p->b2s = value;
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "deconv")) {
+      if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "deconv must be 0 or 1");
+      if (p->aligned || p->host_aligned) return fail(ESCOIN_ESTATE, "deconv must be set before weight_align / weight_align_cpu / set_csr");
+      // With the option set the plan's geometry is the mirror convolution's (M <-> C, H x W <-> OH x OW), whose weight matrix
+      // is this layer's C x Mg*KH*KW one.  A layer the rule refuses keeps the descriptor's geometry: every align refuses it.
+      D2sPlan dp;
+      const escoin_conv_desc &want = value && d2s_plan(p->user_desc, false, &dp) ? dp.mirror : p->user_desc;
+      Geometry g;
+      if (const int rc = validate(&want, &g)) return rc;
+      p->deconv = value;
+      p->g = g;
+      p->rowptr.assign(g.d.group, std::vector<int>(g.Mg + 1, 0));
       return ESCOIN_OK;
     }
     if (!strcmp(key, "b2s_block")) {
@@ -657,8 +752,9 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
     if (!strcmp(key, "wgrad_kernel")) {
       if (value < ESCOIN_WGRAD_AUTO || value > ESCOIN_WGRAD_MFMA) return fail(ESCOIN_EINVAL, "wgrad_kernel must be 0 (auto), 1 (entry), 2 (staged) or 3 (mfma)");
       p->wgrad_kernel = value;
-      // (option "b2s": the weight gradient is the inner plan's, which reads the option as this plan would)
+      // (options "b2s" and "deconv": the weight gradient is the inner plan's, which reads the option as this plan would)
       if (p->b2s_state) return escoin_plan_set_option(p->b2s_state->inner.plan.get(), key, value);
+      if (p->d2s_state) return escoin_plan_set_option(p->d2s_state->inner.plan.get(), key, value);
       return ESCOIN_OK;
     }
     if (!strcmp(key, "wgrad_channel_block")) {
@@ -697,6 +793,16 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       auto direct = [](int m) { return m == ESCOIN_CONV_MODE_SCONV || m == ESCOIN_CONV_MODE_SCONV_PAR; };
       const bool regroup = p->aligned && ((value == ESCOIN_CONV_MODE_LOWERED_GEMM) != (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_GEMM) ||
                                           ((p->s2d || p->s2b || p->b2s) && !p->is_f64 && direct(value) != direct(p->conv_mode)));
+      // (option "deconv": the mode is the inner plan's, which rebuilds itself where it has to)
+      if (p->aligned && p->d2s_state) {
+        if (const int rcs = sync_host_values(p)) return rcs;
+        const int rci = escoin_plan_set_option(p->d2s_state->inner.plan.get(), key, value);
+        if (rci != ESCOIN_OK) return rci;
+        p->conv_mode = value;
+        p->upd.reset();      // (the inner plan may have rebuilt its copies)
+        p->kernel_name = std::string(escoin_plan_kernel_name(p->d2s_state->inner.plan.get())) + " + " + g_d2s_hooks.unpack_kernel_name;
+        return ESCOIN_OK;
+      }
       p->conv_mode = value;
       // to or from LOWERED_GEMM on an aligned plan: the dense / sparse device structures are rebuilt
       // from the CSR the plan holds (the other three modes share theirs).  The plan is not aligned
@@ -785,6 +891,7 @@ int set_csr_host(escoin_plan *p, const int *rowptr, const int *colidx, const T *
     base += n_g;
   }
   p->cpu_off_valid = false;
+  p->cpu_inner.plan.reset();
   p->host_aligned = true;
   return ESCOIN_OK;
 }
@@ -817,6 +924,7 @@ int escoin_plan_export_aligned(const escoin_plan *p, void *buf, size_t capacity,
 int escoin_plan_import_aligned(escoin_plan *p, const void *buf, size_t bytes, void *stream) {
   return guarded([&]() -> int {
     if (!p || !buf) return fail(ESCOIN_EINVAL, "null argument");
+    if (const int rc = deconv_precheck(p, false)) return rc;
     const auto t_start = std::chrono::steady_clock::now();
     const AlignedForm f = aligned_parse(buf, bytes, p->g);
     if (f.rc != ESCOIN_OK) return fail(f.rc, f.error);
@@ -862,6 +970,8 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "s2d_scratch_bytes")) return p->s2d_state ? (long)p->s2d_state->x.bytes() : 0;
   if (!strcmp(key, "s2b")) return p->s2b_state ? 1 : 0;
   if (!strcmp(key, "s2b_scratch_bytes")) return p->s2b_state ? (long)(p->s2b_state->x.bytes() + p->s2b_state->t.bytes()) : 0;
+  if (!strcmp(key, "deconv")) return p->d2s_state ? 1 : 0;
+  if (!strcmp(key, "deconv_scratch_bytes")) return p->d2s_state ? (long)p->d2s_state->t.bytes() : 0;
   if (!strcmp(key, "b2s")) return p->b2s_state ? 1 : 0;
   if (!strcmp(key, "b2s_block")) return p->b2s_state ? p->b2s_state->bp.B : 0;
   if (!strcmp(key, "b2s_scratch_bytes"))
@@ -957,6 +1067,7 @@ size_t escoin_plan_workspace_bytes(const escoin_plan *p) {
 }
 
 const char *escoin_plan_kernel_name(const escoin_plan *p) {
+  if (p && p->aligned && p->d2s_state) return p->kernel_name.c_str();      // (option "deconv": the inner plan's name, whatever the mode, + the unpack kernel)
   if (p && p->aligned && !p->is_f64 && p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE &&
       p->kernel_choice != ESCOIN_KERNEL_DENSE)
     return lowered_kernel_name();
@@ -998,6 +1109,31 @@ int escoin_plan_s2b_unpack(escoin_plan *p, float *top_dev, int n_images, void *s
     if (n_images == 0) return ESCOIN_OK;
     if (const int rc = check_plan_device(p, "s2b_unpack")) return rc;
     return g_s2b_hooks.unpack(p, p->s2b_state->t.get<const float>(), top_dev, true, p->g.d.fuse_relu != 0, n_images, (hipStream_t)stream);
+  });
+}
+
+int escoin_plan_d2s_unpack(escoin_plan *p, const float *t_dev, const float *bias_dev, float *top_dev, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    if (!p || !top_dev) return fail(ESCOIN_EINVAL, "null argument");
+    if (!p->aligned || !p->d2s_state) return fail(ESCOIN_ESTATE, "d2s_unpack: option \"deconv\" is not active on this plan");
+    if (const int rc = check_n_images(p, n_images)) return rc;
+    if (n_images == 0) return ESCOIN_OK;
+    if (const int rc = check_plan_device(p, "d2s_unpack")) return rc;
+    return g_d2s_hooks.unpack(p, t_dev ? t_dev : p->d2s_state->t.get<const float>(), bias_dev, top_dev, p->g.d.fuse_relu != 0, n_images,
+                              (hipStream_t)stream);
+  });
+}
+
+int escoin_plan_d2s_pack(escoin_plan *p, const float *top_diff_dev, const float *top_dev, float *g_dev, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    if (!p || !top_diff_dev) return fail(ESCOIN_EINVAL, "null argument");
+    if (!p->aligned || !p->d2s_state) return fail(ESCOIN_ESTATE, "d2s_pack: option \"deconv\" is not active on this plan");
+    if (p->g.d.fuse_relu && !top_dev) return fail(ESCOIN_EINVAL, "d2s_pack: a fuse_relu plan needs the forward's top");
+    if (const int rc = check_n_images(p, n_images)) return rc;
+    if (n_images == 0) return ESCOIN_OK;
+    if (const int rc = check_plan_device(p, "d2s_pack")) return rc;
+    return g_d2s_hooks.pack(p, top_diff_dev, p->g.d.fuse_relu ? top_dev : nullptr, g_dev ? g_dev : p->d2s_state->t.get<float>(), n_images,
+                            (hipStream_t)stream);
   });
 }
 
@@ -1067,6 +1203,14 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
       rc = escoin_forward(bs->inner.plan.get(), bs->x.get<const float>(), bias_dev, bs->t.get<float>(), n_inner, stream);
       if (rc != ESCOIN_OK) return rc;
       return g_b2s_hooks.unpack(p, bs->t.get<const float>(), top_dev, true, p->g.d.fuse_relu != 0, n_images, s);
+    }
+    // option "deconv": the inner stride-1 plan on the caller's bottom itself into T' (no bias: it is not constant over a
+    // phase's crop, and one more rounding in the unpack on the device and in CPU mode alike), then the interleave, the
+    // crop, the bias and the ReLU in the unpack kernel
+    if (D2sState *ds = p->d2s_state.get()) {
+      const int rc = escoin_forward(ds->inner.plan.get(), bottom_dev, nullptr, ds->t.get<float>(), n_images, stream);
+      if (rc != ESCOIN_OK) return rc;
+      return g_d2s_hooks.unpack(p, ds->t.get<const float>(), bias_dev, top_dev, p->g.d.fuse_relu != 0, n_images, s);
     }
     // LOWERED_SPARSE lowers every group, whatever AUTO decided for the direct path
     if (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE && p->kernel_choice != ESCOIN_KERNEL_DENSE)

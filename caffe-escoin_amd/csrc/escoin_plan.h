@@ -190,6 +190,18 @@ struct B2sState {
                                // weight gradient's operand in the same inner call)
 };
 
+// What upload() builds for a plan with option "deconv" (escoin_capi.hip; the rules: align_rules.h d2s_plan, csr_tables.h
+// d2s_csr; the kernels: d2s.hip); reset with the device side.  A plan has at most one of the four states.  The whole
+// backward is the inner plan's, around the pack kernel and the gradients' carry: the plan itself builds no BwdState.
+struct D2sState {
+  D2sPlan dp;
+  DerivedPlan inner;           // the stride-1 plan of M * P output channels on the caller's bottom; holds the only forward copy of the weights
+  DeviceBuffer t;              // T' (forward) / G' (backward): dp.t_floats floats
+  DeviceBuffer wv, bv;         // the inner compact weight gradient [nnz] and the inner bias gradient [M * P], zeroed per call
+  DeviceBuffer src, wpos;      // [nnz] inner entry k -> outer entry (inner.src), -> its position in blobs_[0] (C x Mg x KH x KW)
+  size_t scratch_bytes() const { return t.bytes() + wv.bytes() + bv.bytes() + src.bytes() + wpos.bytes(); }
+};
+
 // What the first escoin_dense_wgrad on a plan builds (dense_wgrad.hip).  A function of the descriptor, the device's CU
 // count and option "dense_wgrad_splits" alone -- not of the pattern or the values -- so no align resets it: it lives until
 // the plan is destroyed (or until a call finds the plan aligned on another device, which builds it anew there).
@@ -372,9 +384,18 @@ struct escoin_plan {
   // Batch-to-space (b2s.hip): options "b2s" and "b2s_block" and what upload() builds where they apply; reset with the device side
   int b2s = 0, b2s_block = 0;
   std::unique_ptr<escoin::B2sState> b2s_state;
-  // the inner plan of whichever of the three options serves this plan (null: none does)
+  // Deconvolution (d2s.hip): option "deconv", the descriptor as the caller gave it (with the option set, g is the mirror
+  // convolution's geometry -- M <-> C, H x W <-> OH x OW -- whose weight matrix, CSR and aligned form are this layer's) and
+  // what upload() builds; reset with the device side.  cpu_inner: the CPU mode's inner plan (sconv_cpu.cpp), host only
+  int deconv = 0;
+  escoin_conv_desc user_desc = {};
+  std::unique_ptr<escoin::D2sState> d2s_state;
+  escoin::DerivedPlan cpu_inner;
+  std::vector<float> cpu_t, cpu_wv, cpu_bv;
+  // the inner plan of whichever of the four options serves this plan (null: none does)
   const escoin::DerivedPlan *inner_plan() const {
-    return s2d_state ? &s2d_state->inner : s2b_state ? &s2b_state->inner : b2s_state ? &b2s_state->inner : nullptr;
+    return s2d_state ? &s2d_state->inner : s2b_state ? &s2b_state->inner : b2s_state ? &b2s_state->inner :
+           d2s_state ? &d2s_state->inner : nullptr;
   }
 
   // Dense weight gradient (dense_wgrad.hip): option "dense_wgrad_splits" (0: the rule decides, n: at most n splits of the
@@ -526,6 +547,38 @@ struct B2sHooks {
   const char *pack_kernel_name, *unpack_kernel_name;
 };
 extern B2sHooks g_b2s_hooks;   // escoin_capi.hip
+
+// d2s.hip (option "deconv"), registered like S2dHooks.  Of the first n_images images:
+//   unpack      top from T' (+ bias[m] where bias is not null, through ReLU if `relu`): one store per top element
+//   pack        G' from top_diff (times [mask > 0] where mask, the top blob, is not null), +0 outside OH x OW
+//   carry       dst[idx[k]] += src[k] for k < n: the inner compact gradient into the outer entry order (idx = D2sState::src)
+//               or into blobs_[0]'s layout (idx = D2sState::wpos); idx is injective
+//   bias_sum    bias_diff[m] += the inner bias gradients of m's P phases, ascending
+struct D2sHooks {
+  int (*unpack)(const escoin_plan *p, const float *t, const float *bias, float *top, bool relu, int n_images, hipStream_t stream);
+  int (*pack)(const escoin_plan *p, const float *top_diff, const float *mask, float *g, int n_images, hipStream_t stream);
+  int (*carry)(const float *src, const int *idx, float *dst, long n, hipStream_t stream);
+  int (*bias_sum)(const float *inner_bias_diff, float *bias_diff, int M, int P, hipStream_t stream);
+  const char *unpack_kernel_name, *pack_kernel_name;
+};
+extern D2sHooks g_d2s_hooks;   // escoin_capi.hip
+// The refusal of an entry point that option "deconv" does not carry yet (`who` names it); ESCOIN_OK on other plans.
+inline int refuse_deconv(const escoin_plan *p, const char *who) {
+  if (!p || !p->deconv) return ESCOIN_OK;
+  return fail(ESCOIN_EINVAL, std::string(who) + ": not carried over to option \"deconv\" plans yet");
+}
+
+// escoin_capi.hip: what every align of an option "deconv" plan asks first -- whether d2s_plan serves the layer for this Dtype
+// (the refusal is ESCOIN_EINVAL with the rule's message) and that no other derived-plan option is set; ESCOIN_OK on other plans
+int deconv_precheck(const escoin_plan *p, bool is_f64);
+// d2s_cpu.cpp: option "deconv" in CPU mode, behind escoin_forward_cpu / escoin_backward_cpu / escoin_backward_values_cpu;
+// registered like S2dHooks, for the same reason (a program that links the core's objects alone refuses the option's CPU mode)
+struct D2sCpuHooks {
+  int (*forward)(escoin_plan *p, const float *bottom, const float *bias, float *top, int n_images, int n_threads);
+  int (*backward)(escoin_plan *p, const float *bottom, const float *top, const float *top_diff, float *bottom_diff,
+                  float *weight_diff, float *bias_diff, int n_images, int n_threads, bool compact);
+};
+extern D2sCpuHooks g_d2s_cpu_hooks;   // escoin_capi.hip
 
 // Index of the k-th set bit of `mask` (k < popcount): blockIdx -> conv group when only some groups
 // of a layer run in a launch.  Wave-uniform scalar code on the device.

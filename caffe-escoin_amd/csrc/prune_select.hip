@@ -234,6 +234,7 @@ int escoin_plan_prune(escoin_plan *p, const escoin_prune_desc *desc, int *entry_
   return guarded([&]() -> int {
     if (!p) return fail(ESCOIN_EINVAL, "prune: null plan");
     if (!desc) return fail(ESCOIN_EINVAL, "prune: null descriptor");
+    if (const int rc = refuse_deconv(p, "escoin_plan_prune")) return rc;
     if (const int rc = prune::check_device_plan(p, "prune")) return rc;
     return p->is_f64 ? prune_device<double>(p, desc, entry_map_dev, new_nnz, (hipStream_t)stream)
                      : prune_device<float>(p, desc, entry_map_dev, new_nnz, (hipStream_t)stream);
@@ -244,6 +245,7 @@ int escoin_plan_prune_cpu(escoin_plan *p, const escoin_prune_desc *desc, int *en
   return guarded([&]() -> int {
     if (!p) return fail(ESCOIN_EINVAL, "prune_cpu: null plan");
     if (!desc) return fail(ESCOIN_EINVAL, "prune: null descriptor");
+    if (const int rc = refuse_deconv(p, "escoin_plan_prune_cpu")) return rc;
     if (!p->host_aligned) return fail(ESCOIN_ESTATE, "prune_cpu called before weight_align_cpu");
     if (p->aligned)
       return fail(ESCOIN_ESTATE, "prune_cpu: the plan has a device side, which this entry point would leave behind; escoin_plan_prune prunes both sides");

@@ -293,6 +293,7 @@ int escoin_plan_rewire(escoin_plan *p, const escoin_rewire_desc *desc, int *entr
                        long *n_grown, void *stream) {
   return guarded([&]() -> int {
     if (const int rc = check_args(p, desc)) return rc;
+    if (const int rc = refuse_deconv(p, "escoin_plan_rewire")) return rc;
     if (const int rc = prune::check_device_plan(p, "rewire")) return rc;
     return p->is_f64 ? rewire_device<double>(p, desc, entry_map_dev, grown_dev, new_nnz, n_grown, (hipStream_t)stream)
                      : rewire_device<float>(p, desc, entry_map_dev, grown_dev, new_nnz, n_grown, (hipStream_t)stream);
@@ -303,6 +304,7 @@ int escoin_plan_rewire_cpu(escoin_plan *p, const escoin_rewire_desc *desc, int *
                            long *n_grown) {
   return guarded([&]() -> int {
     if (const int rc = check_args(p, desc)) return rc;
+    if (const int rc = refuse_deconv(p, "escoin_plan_rewire_cpu")) return rc;
     if (!p->host_aligned) return fail(ESCOIN_ESTATE, "rewire_cpu called before weight_align_cpu");
     if (p->aligned)
       return fail(ESCOIN_ESTATE, "rewire_cpu: the plan has a device side, which this entry point would leave behind; escoin_plan_rewire rewires both sides");

@@ -808,6 +808,38 @@ static int backward_b2s(escoin_plan *p, const float *bottom, const float *top, c
   return g_b2s_hooks.unpack(p, bs->dx.get<const float>(), bottom_diff, false, false, n_images, stream);
 }
 
+// option "deconv": the whole backward is the inner plan's, on the caller's bottom (the weight gradient's operand) and G' (top_diff
+// split into its output phases by the pack kernel, times [top > 0] on a fuse_relu plan, +0 outside the top).  The inner data
+// gradient IS bottom_diff: the caller's pointer goes straight through.  The inner compact weight gradient and the inner
+// bias gradient (M * P phases) land in two scratches, zeroed first (the inner plan accumulates), and are added to the
+// caller's blobs by the carry and bias-sum kernels: through the entry map into values_diff, through the entries' positions
+// in blobs_[0] (C x Mg x KH x KW) into weight_diff.  No atomics, nothing allocated after the inner state is built.
+static int backward_d2s(escoin_plan *p, const float *bottom, const float *top, const float *top_diff, float *bottom_diff,
+                        float *weight_diff, float *bias_diff, int n_images, hipStream_t stream, bool compact) {
+  D2sState *ds = p->d2s_state.get();
+  escoin_plan *ip = ds->inner.plan.get();
+  // (after device-source updates of THIS plan the inner plan's host CSR, which its backward state is built from, is stale)
+  if (!ip->bwd)
+    if (const int rcs = sync_host_values(p)) return rcs;
+  if (const int rc = ensure_state<float>(ip, stream)) return rc;
+  if (n_images == 0 || (!bottom_diff && !weight_diff && !bias_diff)) return ESCOIN_OK;
+  const long nnz = plan_nnz(p);
+  int rc = g_d2s_hooks.pack(p, top_diff, p->g.d.fuse_relu ? top : nullptr, ds->t.get<float>(), n_images, stream);
+  if (rc != ESCOIN_OK) return rc;
+  const bool want_w = weight_diff && nnz > 0;
+  if (want_w) ESCOIN_HIP_TRY(hipMemsetAsync(ds->wv.get<void>(), 0, sizeof(float) * (size_t)nnz, stream));
+  if (bias_diff) ESCOIN_HIP_TRY(hipMemsetAsync(ds->bv.get<void>(), 0, ds->bv.bytes(), stream));
+  rc = escoin_backward_values(ip, want_w ? bottom : nullptr, nullptr, ds->t.get<const float>(), bottom_diff,
+                              want_w ? ds->wv.get<float>() : nullptr, bias_diff ? ds->bv.get<float>() : nullptr, n_images, stream);
+  if (rc != ESCOIN_OK) return rc;
+  if (want_w) {
+    rc = g_d2s_hooks.carry(ds->wv.get<const float>(), compact ? ds->src.get<const int>() : ds->wpos.get<const int>(), weight_diff, nnz, stream);
+    if (rc != ESCOIN_OK) return rc;
+  }
+  if (bias_diff) rc = g_d2s_hooks.bias_sum(ds->bv.get<const float>(), bias_diff, p->user_desc.M, ds->dp.P, stream);
+  return rc;
+}
+
 // The driver: the checks, the state where this alignment has none yet, then the two gradients.  With the state built a
 // call allocates nothing and synchronises nothing.
 template <typename T>
@@ -826,6 +858,8 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
   hipStream_t stream = (hipStream_t)stream_v;
   if constexpr (sizeof(T) == 4)
     if (p->b2s_state) return backward_b2s(p, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images, stream, compact);
+  if constexpr (sizeof(T) == 4)
+    if (p->d2s_state) return backward_d2s(p, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images, stream, compact);
   if (const int rc = ensure_state<T>(p, stream)) return rc;
   if (n_images == 0) return ESCOIN_OK;
   if (bottom_diff) {

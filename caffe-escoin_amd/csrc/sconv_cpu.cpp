@@ -260,6 +260,11 @@ static int forward_cpu(escoin_plan *p, const T *bottom, const T *bias, T *top, i
                                          : "forward_cpu_f64: the plan holds float weights");
   if (n_images < 0) return fail(ESCOIN_EINVAL, "n_images must be >= 0");
   if (n_images == 0) return ESCOIN_OK;
+  if constexpr (sizeof(T) == 4)
+    if (p->deconv) {     // (option "deconv": d2s_cpu.cpp)
+      if (!g_d2s_cpu_hooks.forward) return fail(ESCOIN_EINVAL, "option \"deconv\": this build does not carry its CPU mode");
+      return g_d2s_cpu_hooks.forward(p, bottom, bias, top, n_images, n_threads);
+    }
   if (const int rcs = sync_host_values(p)) return rcs;     // (device-source weight updates: the values come back first)
   if (isa() == kNone) return fail(ESCOIN_ENODEVICE, "the CPU path needs AVX2 + FMA (the reference builds with -mavx2 -mfma too)");
   if (!p->cpu_off_valid) build_offsets(p);
@@ -434,6 +439,7 @@ static int cpu_dense2csr(int M, int N, const T *A, T *A_nonzero_buf, int *A_nonz
 template <typename T>
 static int weight_align_cpu(escoin_plan *p, const T *dense_w) {
   if (!p || !dense_w) return fail(ESCOIN_EINVAL, "null argument");
+  if (const int rc = deconv_precheck(p, sizeof(T) == 8)) return rc;
   csr_from_dense<T>(p, dense_w);     // leaves host_aligned = true, the device side (if any) released
   return ESCOIN_OK;
 }

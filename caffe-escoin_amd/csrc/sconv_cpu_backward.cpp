@@ -35,6 +35,11 @@ static int backward_cpu(escoin_plan *p, const T *bottom, const T *top, const T *
   if (weight_diff && !bottom) return fail(ESCOIN_EINVAL, "backward_cpu: the weight gradient needs bottom");
   if (n_images < 0) return fail(ESCOIN_EINVAL, "n_images must be >= 0");
   if (n_images == 0) return ESCOIN_OK;
+  if constexpr (sizeof(T) == 4)
+    if (p->deconv) {     // (option "deconv": d2s_cpu.cpp)
+      if (!g_d2s_cpu_hooks.backward) return fail(ESCOIN_EINVAL, "option \"deconv\": this build does not carry its CPU mode");
+      return g_d2s_cpu_hooks.backward(p, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images, n_threads, compact);
+    }
   if (const int rcs = sync_host_values(p)) return rcs;     // (device-source weight updates: the values come back first)
   if (n_threads <= 0) {
     const unsigned hc = std::thread::hardware_concurrency();

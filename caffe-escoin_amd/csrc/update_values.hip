@@ -151,6 +151,10 @@ int for_each_copy(Plan *q, const std::vector<int> *outer, bool with_maps, OnPlan
     if (!through(bs->inner.src, &map)) return mismatch("the inner plan");
     if ((rc = for_each_copy<Plan>(bs->inner.plan.get(), map, with_maps, on_plan, on_array)) != ESCOIN_OK) return rc;
   }
+  if (const D2sState *ds = q->d2s_state.get()) {   // (option "deconv": d2s_csr's map; the backward state is the inner plan's alone)
+    if (!through(ds->inner.src, &map)) return mismatch("the inner plan");
+    if ((rc = for_each_copy<Plan>(ds->inner.plan.get(), map, with_maps, on_plan, on_array)) != ESCOIN_OK) return rc;
+  }
   const BwdState *s = q->bwd.get();
   if (!s) return ESCOIN_OK;
   switch (s->data) {
@@ -172,8 +176,10 @@ int for_each_copy(Plan *q, const std::vector<int> *outer, bool with_maps, OnPlan
   return ESCOIN_OK;
 }
 
-// Whether a backward state exists that holds a copy of p's values: p's own, or under option "b2s" the inner plan's.
-bool has_bwd_state(const escoin_plan *p) { return p->bwd || (p->b2s_state && p->b2s_state->inner.plan->bwd); }
+// Whether a backward state exists that holds a copy of p's values: p's own, or under options "b2s" / "deconv" the inner plan's.
+bool has_bwd_state(const escoin_plan *p) {
+  return p->bwd || (p->b2s_state && p->b2s_state->inner.plan->bwd) || (p->d2s_state && p->d2s_state->inner.plan->bwd);
+}
 
 const auto skip_arrays = [](const DeviceBuffer &, size_t, const int *, const int *, long) { return ESCOIN_OK; };
 

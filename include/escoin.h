@@ -418,6 +418,72 @@ ESCOIN_API int escoin_plan_b2s_pack(escoin_plan *plan, const float *src_dev, con
 ESCOIN_API int escoin_plan_b2s_unpack(escoin_plan *plan, const float *src_dev, float *dst_dev, int top_side, int relu, int n_images,
                          void *stream);
 
+/* ---- Deconvolution: Caffe's DeconvolutionLayer on the stride-1 kernels (option "deconv") ---------------------------------
+ *   DeconvolutionLayer<Dtype>   deconv_layer.cpp: forward = the base layer's backward_*_gemm, backward = forward_*_gemm +
+ *                               weight_*_gemm; compute_output_shape at dilation 1
+ * escoin_plan_set_option(plan, "deconv", 1) before the align (default 0; other values ESCOIN_EINVAL; after an align
+ * ESCOIN_ESTATE, as for "s2d").  The descriptor is then read as a Deconvolution layer's: N, C (bottom channels), H x W (the
+ * bottom image), M (num_output), KH x KW, pad, stride, group, has_bias, fuse_relu.  The top is OH = stride_h (H - 1) + KH -
+ * 2 pad_h, OW likewise (escoin_deconv_out_shape).  blobs_[0] is C x Mg x KH x KW with Mg = M / group -- Caffe's shape: its
+ * conv_out_channels_ is the bottom's channel count.  The CSR is per conv group, rows = the group's Cg bottom channels,
+ * column = ml KH KW + kr KW + kc ascending; escoin_plan_get_csr, set_csr, nnz, set_values, values_diff and the compact entry
+ * order all use it (it is the CSR of the MIRROR convolution, M <-> C and H x W <-> OH x OW, whose backward this layer is).
+ * With m = g Mg + ml and c = g Cg + cl:
+ *   top[n][m][oh][ow] = bias[m] + sum over (cl, kr, kc) in the pattern of X[n][c][h][w] * Wd[c][ml][kr][kc]
+ *                       where oh + pad_h = h stride_h + kr and ow + pad_w = w stride_w + kc, (h, w) inside H x W,
+ * then v > 0 ? v : 0 on a fuse_relu plan (the epilogues' expression: a NaN becomes 0).
+ * The decomposition.  Let sh = stride_h, sw = stride_w, P = sh sw, KH' = ceil(KH / sh), KW' = ceil(KW / sw), H' = H + KH' - 1,
+ * W' = W + KW' - 1.  The INNER plan has the outer N, C, H x W and group; M' = M P channels, m' = (m sh + ph) sw + pw (a conv
+ * group's channels stay contiguous); a KH' x KW' kernel, pad (KH' - 1, KW' - 1), stride 1, dilation 1; has_bias as the outer
+ * plan, fuse_relu = 0; its top is H' x W'.  Entry (c, ml, kr, kc) is the entry of row m'(m, kr % sh, kc % sw) at column
+ * cl KH' KW' + (KH' - 1 - kr / sh) KW' + (KW' - 1 - kc / sw): an injective map, so the nonzero count and the FLOPs of the
+ * sparse walk do not change.  All P phases are inner channels, those that own no tap (sh > KH) included, with empty rows.
+ *   forward   T' = inner_forward(X, bias = NULL) on the caller's bottom itself (no pack), then escoin_d2s_unpack_kernel:
+ *             top[n][m][oh][ow] = T'[n][m'(m, hp % sh, wp % sw)][hp / sh][wp / sw] + bias[m], hp = oh + pad_h, wp = ow + pad_w,
+ *             then the ReLU -- one pass, every element of the first n_images images written exactly once, images past
+ *             n_images untouched;
+ *   backward  (escoin_backward, escoin_backward_values) escoin_d2s_pack_kernel: G'[n][m'][i][j] = top_diff[n][m][i sh + ph -
+ *             pad_h][j sw + pw - pad_w] inside OH x OW (top > 0 ? top_diff : 0 there on a fuse_relu plan), +0 outside; then
+ *             the inner plan's backward with bottom = X, top_diff = G' and the caller's bottom_diff pointer.  The inner
+ *             compact weight gradient is carried to the outer entry order through the map (values_diff) or scattered into
+ *             weight_diff in C x Mg x KH x KW layout; bias_diff[m] takes the inner bias gradients of its P phases, added in
+ *             ascending phase order by one lane per m.  No atomics: the bits depend on the geometry, the pattern and
+ *             n_images only; every gradient keeps the accumulate / overwrite contract of a convolution plan.
+ * The inner plan holds the only forward copy of the weights.  escoin_update_values, escoin_plan_set_values and
+ * escoin_solver_step reach its copies in place through the map and stay capturable; weight_align, set_csr and
+ * import_aligned rebuild; escoin_plan_export_aligned writes the outer CSR and no code section.  The inner plan gets the
+ * options "kernel", "backward_kernel", "wgrad_kernel", "wgrad_channel_block", "tiling_batch", "max_launch_bytes",
+ * "dense_threshold_pct", "dense_gate", "code_loader" and "conv_mode" and ALONE decides generated code, stream, dense or
+ * generic per group; forcing TILED / JIT where the inner layer does not fit them fails with ESCOIN_EINVAL.  T' and G' share
+ * one scratch, allocated by the align with the two small gradient scratches: forward and backward never allocate (but for
+ * the inner plan's backward state, at the first backward).
+ * There is no kernel of the plan's own to fall back to: a layer the rule (align_rules.h d2s_plan) does not serve is refused
+ * at the align with ESCOIN_EINVAL and a message naming the reason -- a dilation other than 1; OH or OW < 1; a double plan or
+ * any _f64 entry point; top, T' or the inner weight matrix at or above 2^31 elements; M P above 262140 (a grid axis of the
+ * inner generic kernel); more than 32767 output channels per group; "deconv" together with "s2d", "s2b" or "b2s".
+ * escoin_plan_create itself still reads the descriptor as a convolution's: a layer whose kernel exceeds H + 2 pad (a 1 x 1
+ * bottom under a 4 x 4 kernel) is refused there; lifting that is a later change.
+ * escoin_plan_prune, escoin_plan_rewire, escoin_dense_wgrad and their _cpu twins return ESCOIN_EINVAL on a "deconv" plan,
+ * naming the option: carrying them over is a later change.  The math_functions-level helpers take no plan and know no
+ * Deconvolution layer.
+ * CPU mode: escoin_weight_align_cpu, escoin_forward_cpu, escoin_backward_cpu, escoin_backward_values_cpu (and
+ * escoin_update_values_cpu, escoin_solver_step_cpu) serve a float "deconv" plan by the same decomposition, with host loops
+ * for pack and unpack around the library's own CPU kernels.  With the inner plan forced to the generic kernel the device
+ * forward is array-equal to the CPU mode's: both keep the reference's summation order, and the bias is one more rounding in
+ * the unpack on both sides.
+ * Stats: "deconv" (1 when active), "deconv_scratch_bytes" (the T' / G' scratch); "kernel_choice", the "bwd_*" / "wgrad_*" /
+ * "dgrad_*" facts and escoin_plan_tiling_info report the inner plan's; escoin_plan_kernel_name is "<inner name> +
+ * escoin_d2s_unpack_kernel"; "device_bytes" and escoin_plan_workspace_bytes count the scratches and the inner plan.
+ * escoin_plan_d2s_unpack / escoin_plan_d2s_pack run one kernel alone, for measuring and testing: unpack writes the first
+ * n_images images of top_dev from t_dev (NULL: the plan's scratch) + bias_dev (may be NULL), through ReLU on a fuse_relu
+ * plan; pack writes G' to g_dev (NULL: the plan's scratch) from top_diff_dev, gated by top_dev > 0 on a fuse_relu plan.
+ * ESCOIN_ESTATE unless stat "deconv" is 1. */
+ESCOIN_API int escoin_deconv_out_shape(const escoin_conv_desc *desc, int *out_h, int *out_w);
+ESCOIN_API int escoin_plan_d2s_unpack(escoin_plan *plan, const float *t_dev, const float *bias_dev, float *top_dev, int n_images,
+                           void *stream);
+ESCOIN_API int escoin_plan_d2s_pack(escoin_plan *plan, const float *top_diff_dev, const float *top_dev, float *g_dev, int n_images,
+                         void *stream);
+
 /* Integer facts about an aligned plan (negative = error): "align_us" wall time of the last
  * weight_align / set_csr / import_aligned, "code_bytes" generated machine code on the device,
  * "device_bytes", "import_fast", "code_direct" (1: the plan's generated code sits in executable device memory the library
