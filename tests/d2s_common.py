@@ -1,4 +1,5 @@
-"""Shared by test_d2s_host.py, test_d2s_cpu.py, test_d2s_gpu.py and test_shim_d2s.py: the Deconvolution layers plan option
+"""Shared by test_d2s_host.py, test_d2s_cpu.py, test_d2s_gpu.py and test_shim_d2s.py -- and, through plan_model.DeconvModel,
+d2s_seq_common.py, d2s_edges_common.py and large_common.py, by the sequence, fp32-edge and large-blob suites: the Deconvolution layers plan option
 "deconv" is tested on -- the smallest at which each piece (the inner CSR and its entry map, the pack / unpack kernels' phase
 arithmetic, the crop, the inner kernels) can still go wrong --, a seeded slice of random geometries, the decomposition of
 include/escoin.h "Deconvolution" restated in numpy from the contract's formulas, the torch float64 reference, and the
@@ -184,21 +185,23 @@ def forward_bound(eb, synth, s, w, x, b=None, relu=False):
     return (np.maximum(want, 0.0) if relu else want), B
 
 
-def backward_bound(eb, synth, s, w, x, top_diff, top=None):
+def backward_bound(eb, synth, s, w, x, top_diff, top=None, mask=None):
     """((bottom_diff, weight_diff, bias_diff), (B_bottom, B_weight, B_bias)): errbound.backward_bound of the inner layer on
     G' = pack(top_diff, top), the weight gradient read back through the entry map into C x Mg x KH x KW, the bias gradient
     summed over a channel's P phases.  That sum is P more additions on top of the inner sum's k = N * H' * W' + 4 roundings,
-    so its bound is the inner bounds' sum scaled by gamma(k + P) / gamma(k)."""
+    so its bound is the inner bounds' sum scaled by gamma(k + P) / gamma(k).  `mask`: the plan's pattern in w's shape where
+    it holds explicit zeros (default: w != 0)."""
     P = inner_dims(s)[0]
     wi, at = inner_weights(s, w)
+    own = (np.asarray(w) != 0) if mask is None else np.asarray(mask, bool)
     pattern = np.zeros(wi.size, bool)
-    pattern[at[np.asarray(w) != 0]] = True
+    pattern[at[own]] = True
     g = pack(s, np.asarray(top_diff, np.float64), top)
     bi = np.zeros(s.M * P, np.float32)
     want, Bs = eb.backward_bound(inner_shape(synth, s, x.shape[0]), wi, x, bi, g, mask=pattern.reshape(wi.shape))
     k = float(g.shape[0] * g.shape[2] * g.shape[3] + 4)
     scale = float(eb.gamma(k + P) / eb.gamma(k))
-    wd, Bw = want[1].reshape(-1)[at] * (np.asarray(w) != 0), Bs[1].reshape(-1)[at]
+    wd, Bw = want[1].reshape(-1)[at] * own, Bs[1].reshape(-1)[at]
     bd, Bb = want[2].reshape(s.M, P).sum(axis=1), Bs[2].reshape(s.M, P).sum(axis=1) * scale
     return (want[0], wd, bd), (Bs[0], Bw, Bb)
 

@@ -15,6 +15,7 @@ from collections import namedtuple
 
 import numpy as np
 
+import d2s_common as dc
 import errbound as eb
 
 BASE, SCALES = 4, 7
@@ -370,3 +371,117 @@ def worst_ratio(torch, got, want, B, first_image=0):
             bad_from.append(tuple(int(v) for v in np.unravel_index(n0 * per + at, tuple(got.shape))))
         del g, r
     return float(worst), (bad_from[0] if bad_from else None)
+
+
+# ---- option "deconv": the top and the plan's own scratch T' past 2 and 4 GiB ---------------------------------------------------
+# Deconvolution 16 -> 64 channels, 16 x 16 bottom, k4 s2 p1, 90 % sparse: the top image is 64 x 32 x 32 = 2^16 elements (2^18
+# bytes, so the 7-scale period argument applies to the top as written); the inner layer has 256 channels, a 2 x 2 kernel and
+# pad 1, so a T' image is 256 x 17 x 17 = 73984 elements -- no power of two: test_large_blobs_host.py runs the displacement
+# proof for it.  d2s.hip indexes with 32-bit ELEMENT offsets, which d2s_plan keeps below 2^31; the byte offsets pass 2^31
+# and 2^32 here.
+DC_LAYER = dc.DShape("dc_top", 1, 16, 16, 16, 64, 4, 4, 2, 2, 1, 1, 1)
+DC_DENSITY = 0.1
+DC_TOP_IMAGE, DC_T_IMAGE = 64 * 32 * 32, 256 * 17 * 17
+# (images of the call, the plan's batch, the inner kernel).  8191 / 8192: the top just under and at 2^31 bytes, T' past it
+# (2.26 GiB); 8191 of 8192: the partial batch; 16385: the top one image past 2^32 bytes, T' 4.52 GiB -- every byte offset of
+# d2s.hip passes 2^32 while its element offset stays under 2^31; about 8.8 GiB.  Under an inner GENERIC as far as that kernel
+# accepts the size (the GPU test records which do).
+DcCase = namedtuple("DcCase", "n plan_n kernel")
+DC_FORWARD = [DcCase(n, p, k) for k in ("AUTO", "GENERIC") for n, p in ((8191, 8191), (8192, 8192), (8191, 8192), (16385, 16385))]
+# top_diff past 2 GiB, packed into a G' of 2.26 GiB in the plan's scratch; the inner plan's backward state comes on top
+# (profiles/errbound.md has the measured peak).  The backward is run at this one batch: with top_diff past 4 GiB the blobs,
+# the scratch and what the inner backward keeps of G''s size come too close to the 12 GiB a case may hold.
+DC_BACKWARD_N = 8193
+DC_REFUSED_N = 32768              # the top is exactly 2^31 elements
+DC_TOP_REFUSAL = "option \"deconv\": the top blob reaches 2^31 elements"
+
+
+def dc_case_id(c):
+    return "dc_top-%d%s-%s" % (c.n, "" if c.plan_n == c.n else "of%d" % c.plan_n, c.kernel)
+
+
+def dc_shape(n):
+    return DC_LAYER._replace(N=n)
+
+
+def _dc_scaled(base):
+    idx = np.arange(PERIOD)
+    return np.ascontiguousarray(base[idx % BASE] * np.ldexp(np.float32(1.0), np.array(SCALE_EXP)[idx % SCALES]).astype(np.float32)[:, None, None, None])
+
+
+def dc_pattern():
+    """(shape of PERIOD images, skewed weights C x Mg x KH x KW, bias, base images, the PERIOD pattern images, top_diff base
+    images, the PERIOD top_diff pattern images) of DC_LAYER, as pattern() and bwd_pattern() make a convolution's: the skew
+    per output channel (d2s_seq_common.to_rows), top_diff of one sign."""
+    if "dc" not in _PATTERNS:
+        from wgrad_common import seeded
+        import d2s_seq_common as ds
+        s4 = dc_shape(BASE)
+        k = sum(map(ord, s4.name)) + 77
+        w = dc.weights(s4, k, DC_DENSITY)
+        rs = np.random.RandomState(k + 1)
+        x = rs.uniform(-1, 1, (BASE, s4.C, s4.H, s4.W)).astype(np.float32)
+        b = rs.uniform(-0.5, 0.5, s4.M).astype(np.float32)
+        td = np.abs(seeded((BASE, s4.M) + dc.out_hw(s4), k + 4))
+        sk = eb.skew(s4, ds.to_rows(s4, w), x, b, k + 3, top_diff=td)
+        _PATTERNS["dc"] = (dc_shape(PERIOD), ds.from_rows(s4, sk.w), sk.b, sk.x, _dc_scaled(sk.x), sk.top_diff, _dc_scaled(sk.top_diff))
+    return _PATTERNS["dc"]
+
+
+def dc_reference(synth):
+    """(want, B) of the top: d2s_common.forward_bound with bias and ReLU on the PERIOD pattern images, read-only."""
+    if "dc" not in _REFS:
+        s28, w, b, _, x28 = dc_pattern()[:5]
+        want, B = dc.forward_bound(eb, synth, s28, w, x28, b, relu=True)
+        want.setflags(write=False)
+        B.setflags(write=False)
+        _REFS["dc"] = (want, B)
+    return _REFS["dc"]
+
+
+def dc_inner_top(synth):
+    """T' of the PERIOD pattern images in float64 (the inner forward; the unpack kernel adds the bias)."""
+    s28, w, _, _, x28 = dc_pattern()[:5]
+    return eb.conv64(x28, dc.inner_weights(s28, w)[0], None, dc.inner_shape(synth, s28))
+
+
+def dc_top_of(s, t, b):
+    """The top the unpack rule makes of a T' (float64), with bias and ReLU."""
+    return dc.unpack(s, t, b.astype(np.float64), relu=True)
+
+
+def dc_bwd_reference(synth):
+    """(bottom_diff of the PERIOD pattern images, its bound), without ReLU."""
+    if "dc" not in _BWD_REFS:
+        s28, w, _, _, x28, _, td28 = dc_pattern()
+        want, Bs = dc.backward_bound(eb, synth, s28, w, x28, td28)
+        _BWD_REFS["dc"] = (want[0], Bs[0])
+    return _BWD_REFS["dc"]
+
+
+def dc_pair_gradients():
+    """Per pattern image the float64 weight and bias gradient of that ONE image and the same of the magnitudes (torch's
+    conv_transpose2d autograd): (wd, bd, wmag, bmag), each (PERIOD, ...)."""
+    if "dc" not in _PAIRS:
+        s28, w, b, _, x28, _, td28 = dc_pattern()
+        per = [dc.ref_backward(s28, w, x28[k:k + 1], b, td28[k:k + 1]) for k in range(PERIOD)]
+        mag = [dc.ref_backward(s28, np.abs(w), np.abs(x28[k:k + 1]), np.abs(b), np.abs(td28[k:k + 1])) for k in range(PERIOD)]
+        _PAIRS["dc"] = (np.stack([p[1] for p in per]), np.stack([p[2] for p in per]), np.stack([m[1] for m in mag]), np.stack([m[2] for m in mag]))
+    return _PAIRS["dc"]
+
+
+def dc_weight_reference(n, lost_from=None):
+    """((weight_diff, bias_diff), (their bounds)) of a batch of n images accumulated into zeroed blobs, as weight_reference:
+    the sum of the pattern images' gradients, each as often as it occurs; the bound is the depth of the inner plan's
+    two-stage reduction over its n * H' * W' top pixels (the suite's rule, not the term count), the carry kernel's addition
+    onto the zero prefill as one more term, and for the bias the P phase sums on top (gamma(k + P), as
+    d2s_common.backward_bound)."""
+    counts = _counts(0, n if lost_from is None else min(n, lost_from))
+    wd, bd, wmag, bmag = [(g * counts.reshape((-1,) + (1,) * (g.ndim - 1))).sum(axis=0) for g in dc_pair_gradients()]
+    P, _, _, hi, wi = dc.inner_dims(DC_LAYER)
+    depth = 1024 + -(-n * hi * wi // 1024)
+    bounds = []
+    for m, extra in ((wmag, 0), (bmag, P)):
+        k = float(depth + extra + 4)
+        bounds.append(eb.accumulated_bound(eb.gamma(k) * m + k * eb.TINY, np.zeros_like(m), depth + extra))
+    return (wd, bd), tuple(bounds)

@@ -6,8 +6,11 @@ The state: the layer (a synth shape, or anything with its geometry fields), the 
 blobs_[0], the values in the plan's dtype -- kept BIT-EXACT -- the optional solver histories in CSR order, and the counters
 the stats report.  The model stays exact because it never computes a gradient itself: solver_step takes the gradient's
 bits, rewire the score's, from a caller that has checked them against forward_bound / backward_bound first."""
+from collections import namedtuple
+
 import numpy as np
 
+import d2s_common as dc
 import errbound as eb
 import prune_common as pc
 from prune_common import positions  # noqa: F401  (the tests take it from here)
@@ -73,6 +76,15 @@ class PlanModel(object):
         m = np.zeros(self.dense_size, bool)
         m[self.pos] = True
         return m.reshape(self.w_shape)
+
+    def row_scale(self, row_exp, dt):
+        """2^row_exp of every output channel, shaped to multiply blobs_[0]: its rows are axis 0."""
+        return np.ldexp(1.0, row_exp).astype(dt)[:, None, None, None]
+
+    def wgrad_terms(self, n, td_shape):
+        """The terms of one weight-gradient element over n images (what errbound.accumulated_bound counts): the top's
+        positions."""
+        return n * td_shape[2] * td_shape[3]
 
     # ---- values --------------------------------------------------------------------------------------------------------
     def _updated(self):
@@ -177,3 +189,39 @@ class PlanModel(object):
         """(weight gradient at EVERY position, its bound)."""
         want, Bs = eb.backward_bound(self.desc, self.dense(), x, None, top_diff, top, f64=self.f64, mask=np.ones(self.w_shape, bool))
         return want[1], Bs[1]
+
+
+# ---- option "deconv" ------------------------------------------------------------------------------------------------------
+# The geometry of a Deconvolution layer's blobs_[0] and CSR is its mirror convolution's: C rows of Mg * KH * KW columns per
+# group.  With these five fields the pattern restatements above (prune_common, rewire_common) apply as they stand.
+Mirror = namedtuple("Mirror", "M C group KH KW")
+
+
+class DeconvModel(PlanModel):
+    """A plan of option "deconv": `s` is a d2s_common.DShape; pos are flat positions of the C x Mg x KH x KW blob, so csr()
+    is d2s_common.csr_of's form; the bounds are errbound's on the inner stride-1 layer, through d2s_common."""
+
+    def __init__(self, s, synth, pos, values, relu=False, in_place=True):
+        self.s, self.synth = s, synth
+        PlanModel.__init__(self, Mirror(s.C, s.M, s.group, s.KH, s.KW), pos, values, relu, in_place)
+
+    def row_scale(self, row_exp, dt):
+        """Output channel m = g * Mg + ml is column ml of the rows of group g."""
+        s = self.s
+        e = np.asarray(row_exp).reshape(s.group, 1, s.M // s.group)
+        e = np.broadcast_to(e, (s.group, s.C // s.group, s.M // s.group)).reshape(s.C, s.M // s.group)
+        return np.ldexp(1.0, e).astype(dt)[:, :, None, None]
+
+    def wgrad_terms(self, n, td_shape):
+        """The inner layer's top positions: an entry's gradient is summed over G' = pack(top_diff)."""
+        _, _, _, hi, wi = dc.inner_dims(self.s)
+        return n * hi * wi
+
+    def forward_bound(self, x, b, relu=None):
+        return dc.forward_bound(eb, self.synth, self.s, self.dense(), x, b, self.relu if relu is None else relu)
+
+    def backward_bound(self, x, b, top_diff, top=None):
+        return dc.backward_bound(eb, self.synth, self.s, self.dense(), x, top_diff, top, mask=self.mask())
+
+    def dense_wgrad_bound(self, x, top_diff, top=None):
+        raise NotImplementedError("escoin_dense_wgrad refuses a deconv plan: the op is not in its vocabulary")

@@ -16,8 +16,7 @@ class CpuBackend(object):
 
     def __init__(self, pkg, cfg, inp, csr):
         self.pkg, self.cfg, self.inp, self.dt = pkg, cfg, inp, inp.dt
-        self.desc = pkg.ConvDesc.from_shape(inp.s, fuse_relu=cfg.relu)
-        self.plan = pkg.Plan(self.desc)
+        self.desc, self.plan = self._make()
         self.h = self.h2 = None
         rp, ci, va, ng = csr
         pos = positions(inp.s, rp, ci, ng)
@@ -28,6 +27,11 @@ class CpuBackend(object):
         self.plan.update_values_cpu(w.reshape(self._w_shape()))
         self.update_count0 = 1                           # (the construction's own update)
         assert self.plan.nnz() == pos.size
+
+    def _make(self):
+        """(descriptor, plan): the one point a derived backend overrides (test_d2s_sequence_cpu.py)."""
+        desc = self.pkg.ConvDesc.from_shape(self.inp.s, fuse_relu=self.cfg.relu)
+        return desc, self.pkg.Plan(desc)
 
     def _w_shape(self):
         s = self.inp.s
@@ -141,13 +145,17 @@ class GpuBackend(object):
         import torch
         self.torch, self.pkg, self.dev, self.cfg, self.inp, self.dt = torch, pkg, dev, cfg, inp, inp.dt
         self.tdt = torch.float64 if cfg.f64 else torch.float32
-        self.desc = pkg.ConvDesc.from_shape(inp.s, fuse_relu=cfg.relu)
         self.opts = {k: getattr(pkg, v) if isinstance(v, str) else v for k, v in cfg.options.items()}
+        self.desc = self._describe()
         self.plan = self._new_plan()
         self.plan.set_csr(*csr)
         self.mode = None                 # the conv_mode a flip left (None: the configuration's own, SCONV_PAR)
         self.h = self.h2 = None
         self._const = {}
+
+    def _describe(self):
+        """The descriptor: with _new_plan, the one point a derived backend overrides (test_d2s_sequence_gpu.py)."""
+        return self.pkg.ConvDesc.from_shape(self.inp.s, fuse_relu=self.cfg.relu)
 
     def _new_plan(self):
         return self.pkg.Plan(self.desc, **self.opts)

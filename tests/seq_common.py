@@ -268,7 +268,9 @@ class Driver(object):
                                        read back: exact bits
       set_values, update_values        stat update_fast as the model predicts (backends that report it)
       get_csr, import                  exact bits
-    and after every mutating op a forward (never a host read)."""
+    and after every mutating op a forward (never a host read).  What depends on the layout of blobs_[0] -- which axis a row
+    exponent scales, how many terms a weight-gradient sum has -- the driver asks the model (plan_model.DeconvModel answers
+    for a C x Mg x KH x KW blob)."""
 
     def __init__(self, backend, model, inp, hyper, worst=None):
         self.b, self.m, self.inp, self.hyper = backend, model, inp, hyper
@@ -332,7 +334,7 @@ class Driver(object):
         return got
 
     def _row_scale(self):
-        return np.ldexp(1.0, self.inp.row_exp).astype(self.inp.dt)[:, None, None, None]
+        return self.m.row_scale(self.inp.row_exp, self.inp.dt)
 
     # ---- the ops ---------------------------------------------------------------------------------------------------------
     def op_forward(self, bias, partial):
@@ -358,8 +360,7 @@ class Driver(object):
         if compact:
             wwant, wB = wwant.reshape(-1)[m.pos], wB.reshape(-1)[m.pos]
         if accumulate:
-            oh_ow = inp.td.shape[2] * inp.td.shape[3]
-            wB = eb.accumulated_bound(wB, base, n * oh_ow, f64=m.f64)
+            wB = eb.accumulated_bound(wB, base, m.wgrad_terms(n, inp.td.shape), f64=m.f64)
             wwant = wwant + base.astype(np.float64)
         if not compact:      # outside the pattern nothing is written: the blob keeps what it held
             outside = ~m.mask()

@@ -190,11 +190,19 @@ def test_pack_and_unpack_alone_follow_their_rule(pkg, dev, name):
         gbuf, g = _guarded((s.N, s.M * P, hi, wi), dev, 5.0)
         topv = rs.uniform(-1, 1, td.shape).astype(np.float32)
         tdn = td.copy()
-        tdn[0, 0, 0, 0] = np.nan if relu and topv[0, 0, 0, 0] <= 0 else tdn[0, 0, 0, 0]      # a masked NaN becomes +0: select, not multiply
+        # a masked NaN becomes +0 -- select, not multiply -- under every masking top: 0, -0.0, a negative and NaN, each set
+        # BEFORE top_diff is poisoned there, in the first image's first row, its second row and its last element; without
+        # the mask the NaN passes through with its bits
+        oh, ow = dc.out_hw(s)
+        spots = [(0, 0, 0, 0), (0, 0, 0, 1), (0, 0, 1, 0), (0, s.M - 1, oh - 1, ow - 1)]
+        for spot, value in zip(spots, (0.0, -0.0, -1.0, np.nan)):
+            topv[spot] = value
+            tdn[spot] = np.nan
         plan.d2s_pack(_up(tdn, dev), _up(topv, dev) if relu else None, g, n_images=n)
         torch.cuda.synchronize()
         g_np = g.cpu().numpy()
         assert same_bits(g_np[:n], dc.pack(s, tdn[:n], topv[:n] if relu else None)), (name, relu)
+        assert int(np.isnan(g_np[:n]).sum()) == (0 if relu else len(spots)), (name, relu)
         assert np.all(g_np[n:] == 5.0) and _guards_kept(gbuf, g.numel(), 5.0)
         plan.close()
 

@@ -12,6 +12,7 @@ import edges_common as ec
 import errbound as eb
 import layout_cases as lc
 import solver_common as sc
+from test_b2s_sequence_gpu import LAYER as IP_SPEC
 from test_body_variant_gpu import CASES as BODY_CASES
 from test_fp32_edges_cpu import finite_specials, masked_top_case
 from wgrad_common import csr_positions
@@ -23,6 +24,7 @@ pytestmark = pytest.mark.gpu
 WORST = {}
 S2B_PACK, S2B_UNPACK, S2D_PACK = "escoin_s2b_pack_kernel", "escoin_s2b_unpack_kernel", "escoin_s2d_pack_kernel"
 DENSE_NAME = "escoin_dense_mfma_kernel"
+B2S_PACK = "escoin_b2s_pack_kernel"
 
 
 @pytest.fixture(scope="module")
@@ -63,7 +65,7 @@ class Family(object):
         name = plan.kernel_name
         assert all(t in name for t in self.name) and (self.exact is None or name == self.exact), (self.id, name)
         assert ("f64" in name) == self.f64, (self.id, name)
-        for option in ("s2d", "s2b"):
+        for option in ("s2d", "s2b", "b2s", "deconv"):
             assert plan.stat(option) == self.options.get(option, 0), (self.id, option, name)
         for k, v in self.stats.items():
             assert plan.stat(k) == (getattr(pkg, v) if isinstance(v, str) else v), (self.id, k, plan.stat(k), name)
@@ -91,12 +93,18 @@ SPARSE = [
     Family("s2b_jit_dilated", "DIL", kernel="KERNEL_JIT", s2b=1, name=(S2B_PACK, "jit", S2B_UNPACK)),
     Family("chained_body", "CHAIN", spec=_CHAIN_SPEC, tiling_batch=256, name=("jit",), stats=dict(body_variant=1), **_CHAIN[4]),
     Family("double", "L3X3", f64=True, name=("f64",), stats=dict(is_f64=1)),
+    # option "b2s" on the sequence suite's inner-product layer: 70 images are two inner images, and 58 of the second one's 64
+    # positions are padding
+    Family("b2s_jit", "IP", spec=IP_SPEC, b2s=1, kernel="KERNEL_JIT", tiling_batch=4096, name=(B2S_PACK, "jit"),
+           stats=dict(kernel_choice="KERNEL_JIT")),
+    Family("b2s_generic", "IP", spec=IP_SPEC, b2s=1, kernel="KERNEL_GENERIC", name=(B2S_PACK, "generic")),
 ]
 DENSE = [
     Family("dense_3x3", "L3X3", kernel="KERNEL_DENSE", exact=DENSE_NAME),
     Family("lowered_gemm", "L3X3", conv_mode="CONV_MODE_LOWERED_GEMM", exact=DENSE_NAME),
     Family("dense_stride2", "STR2", kernel="KERNEL_DENSE", exact=DENSE_NAME),
     Family("s2b_dense_dilated", "DIL", kernel="KERNEL_DENSE", s2b=1, name=(S2B_PACK, DENSE_NAME, S2B_UNPACK)),
+    Family("b2s_dense", "IP", spec=IP_SPEC, b2s=1, kernel="KERNEL_DENSE", name=(B2S_PACK, DENSE_NAME)),
 ]
 MIXED = Family("mixed_groups", "MIXED", dense_threshold_pct=30, tiling_batch=256, name=(" + ", DENSE_NAME))
 FORWARD = SPARSE + DENSE + [MIXED]
@@ -182,6 +190,12 @@ BACKWARD = [
            name=(S2B_PACK, "jit", S2B_UNPACK), stats=dict(bwd_data_kernel="KERNEL_JIT")),
     Family("double", "L3X3", f64=True, wgrad_kernel="WGRAD_ENTRY", name=("f64",),
            stats=dict(bwd_data_kernel="KERNEL_GENERIC", wgrad_kernel="WGRAD_ENTRY")),
+    Family("b2s_jit", "IP", spec=IP_SPEC, b2s=1, kernel="KERNEL_JIT", tiling_batch=4096, backward_kernel="KERNEL_JIT", name=(B2S_PACK, "jit"),
+           stats=dict(bwd_data_kernel="KERNEL_JIT")),
+    Family("b2s_dense", "IP", spec=IP_SPEC, b2s=1, kernel="KERNEL_DENSE", backward_kernel="KERNEL_DENSE", wgrad_kernel="WGRAD_MFMA",
+           name=(B2S_PACK, DENSE_NAME), stats=dict(bwd_data_kernel="KERNEL_DENSE", wgrad_kernel="WGRAD_MFMA")),
+    Family("b2s_generic", "IP", spec=IP_SPEC, b2s=1, kernel="KERNEL_GENERIC", backward_kernel="KERNEL_GENERIC", wgrad_kernel="WGRAD_ENTRY",
+           name=(B2S_PACK, "generic"), stats=dict(bwd_data_kernel="KERNEL_GENERIC", wgrad_kernel="WGRAD_ENTRY")),
 ]
 
 
@@ -191,11 +205,11 @@ BACKWARD = [
 def test_backward_at_the_edges_within_the_bound(pkg, synth, dev, fam, kind, relu):
     """Data gradient, dense and compact weight gradient, bias gradient and (float plans) the dense weight gradient.  The
     ReLU runs use the top of the same plan's forward on the sub_out inputs: the mask sees positive subnormal tops."""
-    s, e = ec.edge(synth, fam.layer, kind, backward=True, f64=fam.f64)
+    s, e = ec.edge(synth, fam.layer, kind, backward=True, f64=fam.f64, spec=fam.spec)
     plan = fam.plan(pkg, s, relu)
     topd = top = None
     if relu:
-        so = ec.edge(synth, fam.layer, "sub_out", f64=fam.f64)[1]
+        so = ec.edge(synth, fam.layer, "sub_out", f64=fam.f64, spec=fam.spec)[1]
         plan.weight_align(so.w)
         topd = plan.forward(_up(so.x, dev), _up(so.b, dev)).clone()
         torch.cuda.synchronize()
@@ -282,6 +296,33 @@ def test_nan_in_the_bottom_reaches_exactly_the_outputs_whose_nonzeros_read_it(pk
     _reach_forward(pkg, synth, dev, fam, _sparse_reach)
 
 
+B2S = [f for f in SPARSE + DENSE if f.id.startswith("b2s_")]
+
+
+@pytest.mark.parametrize("fam", B2S, ids=IDS(B2S))
+def test_nan_in_one_image_of_an_inner_product_layer_reaches_only_that_image(pkg, synth, dev, fam):
+    """Option "b2s" lays the batch out as positions of inner images: a NaN in image 37's bottom (an interior position of the
+    first inner image) and in image 69's (the last used position of the second, 58 padding positions behind it) reaches only
+    outputs of those two images -- the ones errbound's reach names -- and nothing of their neighbours in the inner row."""
+    s, sk = ec.skewed(synth, fam.layer, fam.spec)
+    live = int(np.flatnonzero((sk.w != 0).any(axis=(0, 2, 3)))[0])
+    pos = [(37, live, 0, 0), (s.N - 1, live, 0, 0)]
+    bad, _ = ec.poisoned_bottom(sk.x, pos, np.nan)
+    ind = eb.poisoned(bad.shape, pos)
+    reach = eb.reach_forward_dense(s, ind) if fam in DENSE else eb.reach_forward(s, sk.w, ind)
+    assert reach[[37, s.N - 1]].any(axis=(1, 2, 3)).all() and not np.delete(reach, [37, s.N - 1], axis=0).any()
+    plan = fam.plan(pkg, s, False)
+    plan.weight_align(sk.w)
+    got = plan.forward(_up(bad, dev), _up(sk.b, dev))
+    torch.cuda.synchronize()
+    fam.ran(pkg, plan)
+    plan.close()
+    got = got.cpu().numpy()
+    assert np.array_equal(~np.isfinite(got), reach), (fam.id, np.argwhere(~np.isfinite(got) != reach)[:6].tolist())
+    want, B = ec.skewed_forward_ref(synth, fam.layer, False, spec=fam.spec)
+    _within(np.where(reach, 0, got), np.where(reach, 0, want), B, fam.id, "reach", fam.id)
+
+
 @pytest.mark.parametrize("kn", ["AUTO", "TILED"])
 @pytest.mark.parametrize("row", lc.BODY, ids=[r.name for r in lc.BODY])
 def test_nan_in_the_bottom_on_every_tiled_layout_row(pkg, synth, dev, row, kn):
@@ -333,7 +374,7 @@ def test_one_infinity_arrives_with_the_sign_of_the_weight_that_reads_it(pkg, syn
 
 
 PARTIAL = [f for f in FORWARD if f.id in ("generic_3x3", "tiled_3x3", "tiled_3x3_tb256", "jit_3x3", "jit_3x3_tb256", "dense_3x3",
-                                          "jit_pointwise", "s2b_jit_dilated", "s2d_stride2")]
+                                          "jit_pointwise", "s2b_jit_dilated", "s2d_stride2", "b2s_jit", "b2s_dense", "b2s_generic")]
 
 
 @pytest.mark.parametrize("fam", PARTIAL, ids=IDS(PARTIAL))
@@ -402,7 +443,7 @@ def test_nan_in_top_diff_on_the_dense_data_gradient_kernels_stays_inside_the_den
 
 
 MASKED = [f for f in BACKWARD if f.id in ("gather_entry", "tiled_staged", "jit_mfma", "dense_entry", "dgrad_mfma_3x3", "dgrad_mfma_stride2",
-                                          "s2d_inner", "s2b_inner", "s2b_inner_jit", "double")]
+                                          "s2d_inner", "s2b_inner", "s2b_inner_jit", "double", "b2s_jit", "b2s_dense", "b2s_generic")]
 
 
 @pytest.mark.parametrize("fam", MASKED, ids=IDS(MASKED))
@@ -410,7 +451,7 @@ def test_nan_in_top_diff_under_a_masked_top_reaches_nothing(pkg, synth, dev, fam
     """fuse_relu: a top of 0, -1, NaN or -0.0 masks its top_diff element in the gather kernel, the ReLU mask kernel of the
     transposed plans, the s2b pack, the MFMA data gradient, the three weight-gradient kernels and the dense weight
     gradient: every gradient is finite and within the bound of the reference without the poison."""
-    s, sk = ec.skewed(synth, fam.layer)
+    s, sk = ec.skewed(synth, fam.layer, fam.spec)
     dt = np.float64 if fam.f64 else np.float32
     plan = fam.plan(pkg, s, True)
     plan.weight_align(sk.w.astype(dt))

@@ -387,3 +387,132 @@ def test_a_refused_plan_of_dense_and_sparse_groups_has_launched_neither_half(pkg
     def mixed(plan):
         assert plan.kernel_name.endswith(" + escoin_dense_mfma_kernel") and plan.stat("kernel_choice") in (pkg.KERNEL_JIT, pkg.KERNEL_TILED), plan.kernel_name
     assert _refused(pkg, synth, dev, "sp_mixed", n, "AUTO", msg, weights=w, check=mixed) == 0, "the dense half was launched"
+
+
+# ---- option "deconv": the top and the plan's own scratch T' past 2 and 4 GiB -------------------------------------------------
+def _dc_on_device(synth, dev):
+    if "dc" not in _ON_DEVICE:
+        _, w, b, base, _, tdbase, _ = lg.dc_pattern()
+        want, B = lg.dc_reference(synth)
+        bwant, bB = lg.dc_bwd_reference(synth)
+        up = lambda a: torch.tensor(a, device=dev)  # noqa: E731
+        _ON_DEVICE["dc"] = (w, up(b), up(base), up(want), up(B), up(tdbase), up(bwant), up(bB))
+    return _ON_DEVICE["dc"]
+
+
+def _dc_plan(pkg, n, kernel, relu):
+    import d2s_common as dc
+    opts = {} if kernel == "AUTO" else dict(kernel=getattr(pkg, "KERNEL_" + kernel))
+    return pkg.Plan(dc.desc(pkg, lg.dc_shape(n), True, relu), deconv=1, **opts)
+
+
+@pytest.mark.parametrize("c", lg.DC_FORWARD, ids=[lg.dc_case_id(c) for c in lg.DC_FORWARD])
+def test_deconv_forward_every_element_of_a_large_top_with_bias_and_relu(pkg, synth, dev, c):
+    """The top just under, at and (16385 images) past 2^31 / 2^32 bytes with T', the plan's own scratch, past them as well:
+    every top element within d2s_common.forward_bound of the 28 pattern images, the guard zones intact, the images past the
+    call's at the sentinel.  An inner GENERIC that refuses the size at its launch is recorded and must leave the top
+    untouched; under AUTO every size runs."""
+    import d2s_common as dc
+    t0 = time.time()
+    s = lg.dc_shape(c.plan_n)
+    w, bd, base, want, B = _dc_on_device(synth, dev)[:5]
+    scratch = 4 * c.plan_n * lg.DC_T_IMAGE
+    need = lg.need_bytes(c.n * s.C * s.H * s.W, c.plan_n * lg.DC_TOP_IMAGE)
+    assert need + scratch <= lg.MAX_CASE_BYTES, (need, scratch)
+    lg.require_memory(torch, pytest, need + scratch, lg.dc_case_id(c))
+    torch.cuda.reset_peak_memory_stats()
+    x = torch.empty((c.n, s.C, s.H, s.W), device=dev, dtype=torch.float32)
+    lg.fill_pattern(torch, x, base)
+    buf, top = lg.guarded(torch, dev, (c.plan_n, s.M) + dc.out_hw(s))
+    plan = _dc_plan(pkg, c.plan_n, c.kernel, True)
+    try:
+        plan.weight_align(w)
+        name = plan.kernel_name
+        assert plan.stat("deconv") == 1 and plan.stat("deconv_scratch_bytes") == scratch and name.endswith(" + escoin_d2s_unpack_kernel"), name
+        assert c.kernel == "AUTO" or ("generic" in name and plan.stat("kernel_choice") == pkg.KERNEL_GENERIC), name
+        try:
+            plan.forward(x, bd, top[:c.n])
+        except pkg.EscoinError as e:
+            torch.cuda.synchronize()
+            assert c.kernel != "AUTO" and "(-1)" in str(e), (lg.dc_case_id(c), str(e))
+            assert lg.all_sentinel(torch, top) and lg.guards_intact(buf), (lg.dc_case_id(c), "a refused call wrote to the top")
+            print("large forward %-24s %s: the inner kernel refuses the size: %s" % (lg.dc_case_id(c), name, e))
+            REPORT.append("large forward worst %-40s %-48s refused at the launch: %s" % (lg.dc_case_id(c), name[:48], str(e).split("): ")[-1]))
+            return
+        torch.cuda.synchronize()
+        ratio, bad = lg.worst_ratio(torch, top[:c.n], want, B)
+        peak = torch.cuda.max_memory_allocated() + plan.workspace_bytes
+        print("large forward %-24s %s | %s: scratch %.2f GiB, worst err / bound %.3g, first violation %s, peak %.2f GiB, %.1f s" %
+              (lg.dc_case_id(c), name, plan.tiling_info, scratch / 2.0 ** 30, ratio, bad, peak / 2.0 ** 30, time.time() - t0))
+        assert lg.guards_intact(buf), (lg.dc_case_id(c), "a guard zone around the top was written")
+        if c.plan_n > c.n:
+            assert lg.all_sentinel(torch, top[c.n:]), (lg.dc_case_id(c), "images past the call's were written")
+        assert bad is None and ratio <= 1.0, "%s via %s: element %s is off by %.3g x its bound" % (lg.dc_case_id(c), name, bad, ratio)
+        assert peak <= lg.MAX_CASE_BYTES, peak
+        REPORT.append("large forward worst %-40s %-48s %-16s %.3g   peak %.2f GiB" % (lg.dc_case_id(c), name[:48], "", ratio, peak / 2.0 ** 30))
+    finally:
+        plan.close()
+        del x, top, buf
+        _release()
+
+
+def test_deconv_backward_of_a_large_top_diff(pkg, synth, dev):
+    """top_diff past 2^31 bytes, packed into a G' of 2.26 GiB: bottom_diff of every image within
+    d2s_common.backward_bound; the compact weight gradient and the bias gradient of the whole batch against the sum of the
+    28 pattern images' gradients, bounded by the depth of the inner plan's two-stage reduction
+    (large_common.dc_weight_reference)."""
+    t0 = time.time()
+    n = lg.DC_BACKWARD_N
+    s = lg.dc_shape(n)
+    w, _, base, _, _, tdbase, want, B = _dc_on_device(synth, dev)
+    (want_w, want_b), (B_w, B_b) = lg.dc_weight_reference(n)
+    scratch = 4 * n * lg.DC_T_IMAGE
+    need = lg.need_bytes(n * lg.DC_TOP_IMAGE, n * s.C * s.H * s.W, n * s.C * s.H * s.W)
+    lg.require_memory(torch, pytest, need + scratch, ("dc_top", n, "backward"))
+    torch.cuda.reset_peak_memory_stats()
+    td = torch.empty((n, s.M, 32, 32), device=dev, dtype=torch.float32)
+    lg.fill_pattern(torch, td, tdbase)
+    x = torch.empty((n, s.C, s.H, s.W), device=dev, dtype=torch.float32)
+    lg.fill_pattern(torch, x, base)
+    buf, bdiff = lg.guarded(torch, dev, (n, s.C, s.H, s.W))
+    plan = _dc_plan(pkg, n, "AUTO", False)
+    try:
+        plan.weight_align(w)
+        _, vd, bsd = plan.backward(td, bottom=x, bottom_diff=bdiff, values_diff=True, bias_diff=True)
+        torch.cuda.synchronize()
+        kernels = (plan.stat("bwd_data_kernel"), plan.stat("wgrad_kernel"))
+        ratio, bad = lg.worst_ratio(torch, bdiff, want, B)
+        pos = np.flatnonzero(w.reshape(-1))
+        name = "deconv kernels %d / %d" % kernels
+        rv = eb.within(vd.cpu().numpy(), want_w.reshape(-1)[pos], B_w.reshape(-1)[pos], name + " compact", what=(n, "values"))
+        rb = eb.within(bsd.cpu().numpy(), want_b, B_b, name + " bias", what=(n, "bias"))
+        peak = torch.cuda.max_memory_allocated() + plan.workspace_bytes
+        print("large backward dc_top-%d %s, %s: worst err / bound data %.3g (first violation %s), values %.3g, bias %.3g, peak %.2f GiB, %.1f s" %
+              (n, plan.kernel_name, name, ratio, bad, rv, rb, peak / 2.0 ** 30, time.time() - t0))
+        assert lg.guards_intact(buf), "a guard zone around bottom_diff was written"
+        assert bad is None and ratio <= 1.0, "deconv data gradient: element %s is off by %.3g x its bound" % (bad, ratio)
+        assert peak <= lg.MAX_CASE_BYTES, peak
+        REPORT.append("large backward worst dc_top-%d %s   data %.3g  values %.3g  bias %.3g   peak %.2f GiB" % (n, name, ratio, rv, rb, peak / 2.0 ** 30))
+    finally:
+        plan.close()
+        del td, x, bdiff, buf
+        _release()
+
+
+def test_deconv_refuses_a_top_of_2_31_elements_at_the_align_and_leaves_nothing_behind(pkg, synth, dev):
+    """From a descriptor alone: 32768 images of DC_LAYER are a top of exactly 2^31 elements, which d2s_plan refuses by name
+    before anything is allocated; the plan stays unaligned, without a scratch, and the device's free memory is what it was."""
+    w = lg.dc_pattern()[1]
+    _release()
+    plan = _dc_plan(pkg, lg.DC_REFUSED_N, "AUTO", True)
+    free0 = torch.cuda.mem_get_info()[0]
+    try:
+        with pytest.raises(pkg.EscoinError, match=r"\(-1\): " + re.escape(lg.DC_TOP_REFUSAL)):
+            plan.weight_align(w)
+        torch.cuda.synchronize()
+        assert plan.stat("deconv") == 0 and plan.stat("deconv_scratch_bytes") == 0
+        assert torch.cuda.mem_get_info()[0] >= free0 - (64 << 20), (free0, torch.cuda.mem_get_info()[0])      # (a T' would be 9 GiB)
+        with pytest.raises(pkg.EscoinError):
+            plan.forward(torch.zeros((1, 16, 16, 16), device=dev), None)
+    finally:
+        plan.close()

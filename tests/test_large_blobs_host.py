@@ -217,3 +217,85 @@ def test_the_inputs_show_a_displaced_image_and_a_stale_sentinel(synth, layer):
             moved = np.roll(x28.reshape(-1), -sign * (elems % x28.size)).reshape(x28.shape)
             got = np.maximum(eb.conv64(moved, w, b, s28), 0.0)
             assert (np.abs(got - want) > B).reshape(lg.PERIOD, -1).any(axis=1).all(), (layer, sign * elems)
+
+
+# ---- option "deconv": large_common.DC_LAYER ----------------------------------------------------------------------------------------
+def test_the_deconv_cases_are_at_the_edges_they_claim(pkg):
+    """The top of 8191 images is the last under 2^31 bytes and that of 16385 the first past 2^32; T' passes 2^31 bytes in all
+    of them and 2^32 in the last; every ELEMENT offset stays under 2^31.  32768 images, a top of exactly 2^31 elements, are
+    refused at the align by d2s_plan's message for the top -- on the host as on the device, before anything is allocated --
+    and this layer's T' gets there first: 29026 images are the last it serves (test_d2s_host.py holds each limit of
+    d2s_plan to its own edge on layers made for it)."""
+    import d2s_common as dc
+    s = lg.DC_LAYER
+    P, kh, kw, hi, wi = dc.inner_dims(s)
+    assert s.M * dc.out_hw(s)[0] * dc.out_hw(s)[1] == lg.DC_TOP_IMAGE == 2 ** 16 and s.M * P * hi * wi == lg.DC_T_IMAGE == 73984
+    assert (P, kh, kw, hi, wi) == (4, 2, 2, 17, 17)
+    assert 8191 * lg.DC_TOP_IMAGE * 4 < 2 ** 31 == 8192 * lg.DC_TOP_IMAGE * 4 < 8191 * lg.DC_T_IMAGE * 4
+    assert 16384 * lg.DC_TOP_IMAGE * 4 == 2 ** 32 < 16385 * lg.DC_T_IMAGE * 4 and 16385 * lg.DC_T_IMAGE < 2 ** 31
+    assert lg.DC_BACKWARD_N * lg.DC_TOP_IMAGE * 4 > 2 ** 31 and lg.DC_REFUSED_N * lg.DC_TOP_IMAGE == 2 ** 31
+    # what a case holds: bottom, top and the plan's T' / G' scratch (for the backward top_diff and bottom_diff as well)
+    per_in = s.C * s.H * s.W
+    assert all(lg.need_bytes(c.n * per_in, c.plan_n * lg.DC_TOP_IMAGE) + 4 * c.plan_n * lg.DC_T_IMAGE <= lg.MAX_CASE_BYTES for c in lg.DC_FORWARD)
+    n = lg.DC_BACKWARD_N
+    assert lg.need_bytes(n * per_in, n * per_in, n * lg.DC_TOP_IMAGE) + 4 * n * lg.DC_T_IMAGE <= lg.MAX_CASE_BYTES
+    w = lg.dc_pattern()[1]
+    for images, why in ((29026, None), (29027, "the inner top T' reaches 2^31 elements"), (lg.DC_REFUSED_N, lg.DC_TOP_REFUSAL)):
+        plan = pkg.Plan(dc.desc(pkg, lg.dc_shape(images), True, True), deconv=1)
+        if why is None:
+            plan.weight_align_cpu(w)
+            assert plan.stat("host_aligned") == 1
+        else:
+            with pytest.raises(pkg.EscoinError) as e:
+                plan.weight_align_cpu(w)
+            assert "failed (-1)" in str(e.value) and why in str(e.value), str(e.value)
+            assert plan.stat("host_aligned") == 0
+        plan.close()
+
+
+def test_the_deconv_inputs_show_a_displaced_image_a_displaced_inner_image_and_a_stale_sentinel(synth):
+    """For DC_LAYER's pattern: a top image stored 2^31 or 2^32 bytes or elements away from its place (the top image is 2^16
+    elements: whole images, a count that is no multiple of the period), a T' image READ from that far away -- a T' image is
+    73984 elements, no power of two, so the displaced read is a splice of two pattern images and the proof is run, not
+    inferred -- and the sentinel left in place each violate the bound on at least one element of every image."""
+    import d2s_common as dc
+    want, B = lg.dc_reference(synth)
+    s28, _, b = lg.dc_pattern()[:3]
+    assert want.shape == (lg.PERIOD, s28.M) + dc.out_hw(s28) and want[0].size == lg.DC_TOP_IMAGE
+    t = lg.dc_inner_top(synth)
+    assert t[0].size == lg.DC_T_IMAGE
+    honest = lg.dc_top_of(s28, t, b)
+    assert (np.abs(honest - want) <= 1e-6 * B).all()       # (the same float64 sums: the proof below starts from the reference)
+    for elems in (2 ** 29, 2 ** 30, 2 ** 31, 2 ** 32):
+        assert elems % lg.DC_TOP_IMAGE == 0 and (elems // lg.DC_TOP_IMAGE) % lg.PERIOD != 0 and elems % t.size != 0
+        for sign in (1, -1):
+            assert lg.displaced_violates(want, B, sign * elems), (sign * elems, "top")
+            moved = np.roll(t.reshape(-1), -sign * (elems % t.size)).reshape(t.shape)
+            bad = np.abs(lg.dc_top_of(s28, moved, b) - want) > B
+            assert bad.reshape(lg.PERIOD, -1).any(axis=1).all(), (sign * elems, "T'")
+    assert (np.abs(lg.SENTINEL - want) > B).reshape(lg.PERIOD, -1).any(axis=1).all()
+    # the data gradient likewise (bottom_diff images of 2^12 elements)
+    bwant, bB = lg.dc_bwd_reference(synth)
+    for elems in (2 ** 29, 2 ** 31):
+        assert lg.displaced_violates(bwant, bB, elems) and lg.displaced_violates(bwant, bB, -elems), elems
+
+
+def test_the_deconv_weight_and_bias_bounds_show_nothing_written_and_a_lost_tail(synth):
+    """With the bound of the reduction's depth (large_common.dc_weight_reference) at the backward case's batch: a gradient of
+    zeros violates the weight and the bias bound, and so does a batch that lost what lies past 2^31 bytes of top_diff -- one
+    image, so the case's batch has a second size 512 images on for the weights (the suite's rule for an edge)."""
+    import d2s_common as dc
+    n = lg.DC_BACKWARD_N
+    (ww, wb), (Bw, Bb) = lg.dc_weight_reference(n)
+    assert _worst(0 * ww, ww, Bw) > 100 and _worst(0 * wb, wb, Bb) > 100
+    w = lg.dc_pattern()[1]
+    assert ww.shape == w.shape and (ww[w == 0] == 0).all() and np.isfinite(Bw).all()
+    (lw, lb), _ = lg.dc_weight_reference(n + 512, lost_from=8192)
+    (ww2, wb2), (Bw2, Bb2) = lg.dc_weight_reference(n + 512)
+    assert _worst(lw, ww2, Bw2) > 10 and _worst(lb, wb2, Bb2) > 10
+    # ... and the sum of the pattern images' gradients is the gradient of the batch itself
+    s28, w, b, _, x28, _, td28 = lg.dc_pattern()
+    idx = np.arange(61) % lg.PERIOD
+    (w61, b61), (B61, Bb61) = lg.dc_weight_reference(61)
+    _, wd, bsd = dc.ref_backward(s28, w, x28[idx], b, td28[idx])
+    assert (np.abs(wd - w61) <= 1e-6 * B61).all() and (np.abs(bsd - b61) <= 1e-6 * Bb61).all() and np.abs(wd).max() > 0
