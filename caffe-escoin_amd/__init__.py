@@ -24,6 +24,7 @@ LIB_PATH = os.environ.get("ESCOIN_LIB") or os.path.join(_HERE, "libescoin_hip.so
 
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_TILED, KERNEL_DENSE, KERNEL_JIT = 0, 1, 2, 3, 4
 WGRAD_AUTO, WGRAD_ENTRY, WGRAD_STAGED, WGRAD_MFMA = 0, 1, 2, 3   # option / stat "wgrad_kernel"
+WGRAD_POINTWISE = 4    # stat "wgrad_kernel" only: the pointwise kernel of option "wgrad_pointwise" ran
 BWD_MFMA = 5   # option "backward_kernel" / stat "bwd_data_kernel": the fp32-MFMA data-gradient kernel (never "kernel")
 CONV_MODE_LOWERED_GEMM, CONV_MODE_LOWERED_SPARSE, CONV_MODE_SCONV, CONV_MODE_SCONV_PAR = 0, 1, 2, 3
 

@@ -111,10 +111,15 @@ class Caffe {
   // the same for inner-product layers (one pixel, a 1x1 kernel) via batch-to-space (include/escoin.h option "b2s")
   static bool b2s() { return Get().b2s_; }
   static void set_b2s(bool on) { Get().b2s_ = on; }
+  // whether the plans layers create from now on compute the weight gradient of pointwise layers (1x1, pad 0; inner-product
+  // layers through "b2s") by the pointwise kernel (include/escoin.h option "wgrad_pointwise"); a layer the option does not
+  // serve, a forced wgrad_kernel, and CPU mode, run as without it
+  static bool wgrad_pointwise() { return Get().wgrad_pointwise_; }
+  static void set_wgrad_pointwise(bool on) { Get().wgrad_pointwise_ = on; }
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), wgrad_pointwise_(false) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
@@ -123,6 +128,7 @@ class Caffe {
   bool s2d_;
   bool s2b_;
   bool b2s_;
+  bool wgrad_pointwise_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -449,6 +455,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2d", Caffe::s2d() && !deconv_ ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2b", Caffe::s2b() && !deconv_ ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "b2s", Caffe::b2s() && !deconv_ ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_pointwise", Caffe::wgrad_pointwise() ? 1 : 0));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;

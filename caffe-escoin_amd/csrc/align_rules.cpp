@@ -614,6 +614,96 @@ bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp) {
   return true;
 }
 
+// The tiles of one slice height: per (group, c-block) the greedy m-slices.  A row's entries of a c-block are counted with a
+// cursor per row (columns ascend within a row, and a pointwise column IS the group-local channel).
+static void pw_tiles(const Geometry &g, const CsrIndex *rowptr, const CsrIndex *colidx, int cblk, int cap, int height,
+                     std::vector<PwTile> *first, std::vector<PwTile> *rest) {
+  const int nblk = (g.Cg + cblk - 1) / cblk;
+  std::vector<int> cur((size_t)g.Mg);
+  for (int grp = 0; grp < g.d.group; ++grp) {
+    const int *rp = rowptr ? (*rowptr)[grp].data() : nullptr;
+    const int *ci = rowptr && colidx ? (*colidx)[grp].data() : nullptr;
+    for (int m = 0; m < g.Mg; ++m) cur[m] = rp ? rp[m] : 0;
+    for (int b = 0; b < nblk; ++b) {
+      const int c0 = b * cblk, chans = std::min(cblk, g.Cg - c0);
+      std::vector<PwTile> *out = b == 0 ? first : rest;
+      PwTile t;
+      int last = -1;   // the slice's last row with an entry
+      auto close = [&](int end) {
+        if (b > 0) t.rows = last - t.row0 + 1;   // (rows without an entry at the end)
+        else t.rows = end - t.row0;
+        if (t.rows > 0 && (b == 0 || t.items > 0)) out->push_back(t);
+      };
+      bool open = false;
+      for (int m = 0; m < g.Mg; ++m) {
+        int cnt;
+        if (ci) {
+          const int end = rp[m + 1];
+          int j = cur[m];
+          while (j < end && ci[j] < c0 + chans) ++j;
+          cnt = j - cur[m];
+          cur[m] = j;
+        } else {
+          cnt = rp ? std::min(rp[m + 1] - rp[m], chans) : chans;
+        }
+        if (open && (t.items + cnt > cap || m - t.row0 >= height)) {
+          close(m);
+          open = false;
+        }
+        if (!open) {
+          if (b > 0 && cnt == 0) continue;       // (rows without an entry at the start)
+          t = PwTile();
+          t.grp = grp; t.row0 = m; t.c0 = c0; t.chans = chans;
+          open = true;
+          last = m;
+        }
+        t.items += cnt;
+        if (cnt > 0) last = m;
+      }
+      if (open) close(g.Mg);
+    }
+  }
+}
+
+bool pw_plan(const Geometry &g, bool is_f64, long nnz, const CsrIndex *rowptr, const CsrIndex *colidx, int wgrad_channel_block,
+             int tile_entries, int n_cu, PwPlan *pp) {
+  const escoin_conv_desc &d = g.d;
+  if (is_f64 || d.KH != 1 || d.KW != 1 || d.pad_h != 0 || d.pad_w != 0) return false;
+  const double two31 = 2147483648.0;
+  const double pixels = (double)d.N * g.OH * (double)g.OW;
+  if (pixels >= two31 || (double)d.C * d.H * (double)d.W >= two31 || nnz < 0 || (double)nnz >= two31) return false;
+  const long chunks = ((long)pixels + kBwdChunkPixels - 1) / kBwdChunkPixels;
+  if (chunks > (long)kGridYZMax) return false;   // grid y
+  PwPlan p;
+  p.chunks = (int)chunks;
+  p.tile_cap = tile_entries > 0 ? std::min(tile_entries, kPwMaxTileEntries) : kPwMaxTileEntries;
+  p.cblk = std::min(std::min(g.Cg, kPwMaxChannelBlock), p.tile_cap);
+  if (wgrad_channel_block > 0) p.cblk = std::min(p.cblk, wgrad_channel_block);
+  int height = std::min(std::min(g.Mg, kPwMaxSliceRows), kPwMaxLdsRows - p.cblk);
+  const long want = 2L * std::max(n_cu, 1);
+  std::vector<PwTile> first, rest;
+  for (;;) {
+    first.clear();
+    rest.clear();
+    pw_tiles(g, rowptr, colidx, p.cblk, p.tile_cap, height, &first, &rest);
+    if (height <= kPwMinSliceRows || nnz * chunks < kPwSplitWork || chunks * (long)(first.size() + rest.size()) >= want) break;
+    height = std::max(kPwMinSliceRows, height / 2);
+  }
+  p.bias_tiles = (int)first.size();
+  p.tiles = std::move(first);
+  p.tiles.insert(p.tiles.end(), rest.begin(), rest.end());
+  int fullest = 0;
+  for (const PwTile &t : p.tiles) {
+    p.rows_max = std::max(p.rows_max, t.rows);
+    p.chans_max = std::max(p.chans_max, t.chans);
+    fullest = std::max(fullest, t.items);
+  }
+  while (kPwThreads * p.lane_entries < fullest) p.lane_entries *= 2;
+  p.lds_bytes = sizeof(float) * (size_t)p.pitch * (size_t)(p.rows_max + p.chans_max);
+  *pp = std::move(p);
+  return true;
+}
+
 bool dwg_plan(const Geometry &g, bool is_f64, int n_cu, int max_splits, DwgPlan *dp) {
   DwgPlan p;
   if (!wgm_plan(g, is_f64, &p.tile)) return false;
@@ -719,6 +809,10 @@ BwdChoice bwd_choice(const Geometry &g, bool is_f64, long nnz, const BwdOptions 
   else if (staged_ok && (o.wgrad_kernel == ESCOIN_WGRAD_STAGED ||
                          (o.wgrad_kernel == ESCOIN_WGRAD_AUTO && stg_auto_prefers(g, nnz, c.stg, n_cu))))
     c.wgrad = ESCOIN_WGRAD_STAGED;
+  // option "wgrad_pointwise": AUTO's answer gives way on a plan the pointwise kernel serves; a forced kernel does not
+  if (o.wgrad_pointwise && o.wgrad_kernel == ESCOIN_WGRAD_AUTO &&
+      pw_plan(g, is_f64, nnz, nullptr, nullptr, o.wgrad_channel_block, o.pw_tile_entries, n_cu, &c.pw))
+    c.wgrad = ESCOIN_WGRAD_POINTWISE;
   c.chunks_max = (int)(((long)d.N * g.OH * g.OW + kBwdChunkPixels - 1) / kBwdChunkPixels);
   return c;
 }

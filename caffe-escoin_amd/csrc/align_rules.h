@@ -240,6 +240,57 @@ struct WgmPlan {
 // column tiles: the grid).
 bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp);
 
+// ---- the pointwise weight-gradient kernel (wgrad_pointwise.hip, plan option "wgrad_pointwise") ------------------------
+// The sampled product dW[m][c] = sum over pixels of G[m][q] * X[c][q] for the CSR's (m, c) pairs of a 1x1, pad-0 layer.
+// One workgroup of kPwThreads lanes per (tile, chunk).  A tile is rows [row0, row0 + rows) of one conv group crossed with
+// its channels [c0, c0 + chans); the chunk's pixels go through LDS kPwStepPixels at a time, one row of kPwPitch floats per
+// output channel and per input channel of the tile, and a lane owns up to E of the tile's entries, each one fma chain.
+constexpr int kPwThreads = 256;
+constexpr int kPwStepPixels = 32;                    // S: pixels per LDS step
+constexpr int kPwPitch = kPwStepPixels + 4;          // floats per staged row: rows 16-byte aligned, 4 banks apart
+constexpr int kPwMaxLaneEntries = 16;                // E is 1, 2, 4, 8 or 16
+constexpr int kPwMaxTileEntries = kPwThreads * kPwMaxLaneEntries;
+constexpr size_t kPwLdsBudget = 64 * 1024;           // two workgroups per CU
+constexpr int kPwMaxLdsRows = (int)(kPwLdsBudget / (sizeof(float) * kPwPitch));   // G rows + bottom rows of a tile
+constexpr int kPwMaxChannelBlock = 256;              // channels of a tile under the rule
+constexpr int kPwMaxSliceRows = kPwThreads;          // one lane per G row sums the bias
+constexpr int kPwMinSliceRows = 8;                   // the rule splits slices no further than this for more workgroups
+constexpr long kPwSplitWork = 1L << 16;              // ... and not at all below this many (entry, chunk) pairs: such a launch
+                                                     // is a few microseconds of latency, which more workgroups do not shorten
+
+struct PwTile {
+  int grp = 0, row0 = 0, rows = 0;   // conv group, first group-local output channel, output channels
+  int c0 = 0, chans = 0;             // first group-local input channel, input channels
+  int items = 0;                     // entries of the pattern inside (with no pattern: the most any pattern has)
+};
+struct PwPlan {
+  int step = kPwStepPixels, pitch = kPwPitch;
+  int cblk = 0;               // channels per c-block: c-block b of a group covers channels [b * cblk, min(Cg, (b + 1) * cblk))
+  int lane_entries = 1;       // E: the kernel instantiation, 256 * E >= the fullest tile
+  int tile_cap = 0;           // the most entries a tile may hold
+  int chunks = 0;             // chunks of the full batch (grid y)
+  int rows_max = 0, chans_max = 0;   // the tallest m-slice, the widest c-block
+  size_t lds_bytes = 0;       // sizeof(float) * pitch * (rows_max + chans_max)
+  int bias_tiles = 0;         // the tiles of c-block 0, which come first and cover every row of every group once: they sum
+                              // the bias, and a bias-only call launches them alone
+  std::vector<PwTile> tiles;  // c-block-0 tiles (empty ones included), then the other c-blocks' tiles that hold an entry
+};
+// Whether the pointwise kernel serves this plan, and its tiling where it does.  Served: float plans with KH = KW = 1 and
+// pad 0, any stride and group count, with N*OH*OW, C*H*W and nnz below 2^31 and at most 65535 chunks (grid y; the tiles
+// are grid x).  The predicate reads no pattern.  The tiling reads the pattern (rowptr / colidx: the host CSR per conv
+// group; both null: every row is taken as full, which bounds every pattern):
+//   cblk      min(Cg, kPwMaxChannelBlock, the cap), and min(that, wgrad_channel_block) where the option is > 0;
+//   m-slices  per (group, c-block), greedy over the rows: a slice closes before the row that would bring it past the cap
+//             (tile_entries > 0: min(tile_entries, kPwMaxTileEntries); else kPwMaxTileEntries) or past the slice height
+//             min(Mg, kPwMaxSliceRows, kPwMaxLdsRows - cblk).  A row holds at most cblk <= cap entries of a c-block, so
+//             every tile is within the cap.  Past c-block 0, rows without an entry at a slice's ends are left out;
+//   height    halved, down to kPwMinSliceRows, while chunks * tiles stays below two workgroups per CU -- on plans of at
+//             least kPwSplitWork (entry, chunk) pairs.
+// Every entry is in exactly one tile; an empty pattern has its c-block-0 tiles only.  No result's bits depend on the
+// tiling: an entry's sum is one lane's chain over the chunk's pixels.
+bool pw_plan(const Geometry &g, bool is_f64, long nnz, const CsrIndex *rowptr, const CsrIndex *colidx, int wgrad_channel_block,
+             int tile_entries, int n_cu, PwPlan *pp);
+
 // ---- the dense weight gradient on the matrix cores (dense_wgrad.hip) ------------------------------------------------
 // wgm_plan's predicate and tiles; the pixel axis is split over `splits` workgroups per tile, each walking `span` whole
 // chunks with one accumulator set, so that a layer with few tiles still fills the device.  With tiles = group * mtiles *
@@ -308,7 +359,12 @@ bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp);
 bool bwd_transposable(const Geometry &g, bool is_f64);
 // The plan options the backward reads (escoin_plan_set_option), and s2d: the plan has an inner plan (option "s2d" or
 // option "s2b" serves it: it has an S2dState or an S2bState).
-struct BwdOptions { int backward_kernel, wgrad_kernel, wgrad_channel_block; bool s2d; };
+// wgrad_pointwise: option "wgrad_pointwise"; pw_tile_entries: test option "wgrad_pointwise_tile_entries".
+struct BwdOptions {
+  int backward_kernel, wgrad_kernel, wgrad_channel_block;
+  bool s2d;
+  int wgrad_pointwise = 0, pw_tile_entries = 0;
+};
 // Who computes the data gradient: the inner plan of option "s2d" / "s2b" (AUTO, TILED, JIT and DENSE on such a plan; the inner
 // plan refuses what it cannot serve), the transposed forward plan, the gather kernel, the MFMA kernel of dgrad_mfma.hip.
 enum BwdDataPath { kBwdInner, kBwdTransposed, kBwdGather, kBwdMfma };
@@ -318,9 +374,11 @@ struct BwdChoice {
   int rc = ESCOIN_OK;
   const char *error = "";
   BwdDataPath data = kBwdGather;
-  int wgrad = ESCOIN_WGRAD_ENTRY;   // ESCOIN_WGRAD_ENTRY / STAGED / MFMA: what option "wgrad_kernel" resolves to
+  int wgrad = ESCOIN_WGRAD_ENTRY;   // ESCOIN_WGRAD_ENTRY / STAGED / MFMA: what option "wgrad_kernel" resolves to, or
+                                    // ESCOIN_WGRAD_POINTWISE: AUTO with option "wgrad_pointwise" on a plan pw_plan serves
   StgPlan stg;
   WgmPlan wgm;
+  PwPlan pw;                        // (the tiling that bounds every pattern: the state's builder plans again on the CSR)
   DgmPlan dgm;
   int chunks_max = 0;               // chunks of the full batch: the slab's rows
 };

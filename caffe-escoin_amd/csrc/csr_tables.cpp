@@ -114,6 +114,37 @@ StagedTables staged_tables(const CsrView &v, int icb, int nblk, int cs, int Wp) 
   return t;
 }
 
+PwTables pw_tables(const CsrView &v, const PwPlan &plan) {
+  const Geometry &g = *v.g;
+  PwTables t;
+  t.tile.reserve(plan.tiles.size() * kPwTileWords);
+  t.ent.reserve((size_t)v.nnz() + 1);
+  t.pk.reserve((size_t)v.nnz() + 1);
+  std::vector<long> base((size_t)g.d.group);
+  for (int grp = 0; grp < g.d.group; ++grp) base[grp] = v.group_base(grp);
+  for (const PwTile &pt : plan.tiles) {
+    const std::vector<int> &rp = (*v.rowptr)[pt.grp], &ci = (*v.colidx)[pt.grp];
+    const int first = (int)t.ent.size();
+    for (int r = 0; r < pt.rows; ++r) {
+      const int m = pt.row0 + r;
+      // the columns of a row ascend (set_csr checks it), and a pointwise column is the group-local channel
+      const int *lo = std::lower_bound(ci.data() + rp[m], ci.data() + rp[m + 1], pt.c0);
+      for (const int *j = lo; j < ci.data() + rp[m + 1] && *j < pt.c0 + pt.chans; ++j) {
+        t.ent.push_back((int)(base[pt.grp] + (j - ci.data())));
+        t.pk.push_back((r << 16) | (pt.rows + (*j - pt.c0)));
+      }
+    }
+    const int words[kPwTileWords] = {pt.grp, pt.row0, pt.rows, pt.c0, pt.chans, first, (int)t.ent.size() - first, 0};
+    t.tile.insert(t.tile.end(), words, words + kPwTileWords);
+  }
+  if (t.tile.empty()) t.tile.assign(kPwTileWords, 0);
+  if (t.ent.empty()) {
+    t.ent.push_back(0);
+    t.pk.push_back(0);
+  }
+  return t;
+}
+
 WgmTables wgrad_mfma_tables(const CsrView &v, int tile_m, int tile_k) {
   const Geometry &g = *v.g;
   const escoin_conv_desc &d = g.d;

@@ -109,6 +109,17 @@ WgmTables wgrad_mfma_tables(const CsrView &v, int tile_m, int tile_k);
 // That ktab alone: a function of the geometry, no CSR (the dense weight gradient's state, dense_wgrad.hip, needs no more).
 std::vector<int> im2col_ktab(const Geometry &g, int tile_k);
 
+// The pointwise weight-gradient kernel's tables for a tiling of align_rules.h pw_plan made ON THIS PATTERN (its tiles' item
+// counts are then the counts found here).  tile [kPwTileWords * max(tiles, 1)]: per tile, in the plan's order, {group,
+// first row, rows, first channel, channels, first item, items, 0}.  A tile's items are its entries in CSR order -- lane l
+// of the workgroup takes items l, l + 256, ... -- and item i has ent[i] = the entry's flat index and pk[i] = (G row << 16) |
+// bottom row, both rows of the tile's LDS image: G row = m - first row in [0, rows), bottom row = rows + (c - first
+// channel) in [rows, rows + channels).  ent and pk have max(nnz, 1) elements: every entry is an item of exactly one tile.
+constexpr int kPwTileWords = 8;
+struct PwPlan;
+struct PwTables { std::vector<int> tile, ent, pk; };
+PwTables pw_tables(const CsrView &v, const PwPlan &plan);
+
 // The MFMA data-gradient kernel's tables for a tile plan of align_rules.h dgm_plan (P phases, phase index = row residue *
 // stride_w + column residue; ctiles channel tiles of tile_c per conv group; steps of step_k columns):
 //   phase    [8 * P]: {h0, w0, rows, cols, kp, ksteps, col0, ntaps} -- the phase's bottom pixels are (h0 + stride_h * hh,

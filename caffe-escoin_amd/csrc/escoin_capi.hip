@@ -87,7 +87,7 @@ DeviceBytes device_bytes(const escoin_plan *p) {
   if (const UpdState *u = p->upd.get())
     b.upd = u->src.bytes() + u->off.bytes() + u->buf.bytes() + u->wpos.bytes() + u->stage.bytes() + u->e_ptr.bytes() + u->e_off.bytes() + u->e_buf.bytes();
   if (const BwdState *s = p->bwd.get())
-    b.bwd = s->gather.bytes() + s->stg.bytes() + s->wgm.bytes() + s->dgm.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() +
+    b.bwd = s->gather.bytes() + s->stg.bytes() + s->wgm.bytes() + s->pw.bytes() + s->dgm.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() +
             (s->transposed.plan ? device_bytes(s->transposed.plan.get()).fwd : 0);
   if (const S2dState *sd = p->s2d_state.get()) {
     // the X' / dX' scratch and the inner plan's own owners (its update state is never built: the plan's list reaches its copies)
@@ -136,6 +136,7 @@ long bwd_stat(const escoin_plan *p, const char *key) {
   }
   if (!strcmp(key, "wgrad_lds_bytes")) {
     if (s && s->wgrad == ESCOIN_WGRAD_MFMA) return (long)s->wgm.lds_bytes;
+    if (s && s->wgrad == ESCOIN_WGRAD_POINTWISE) return (long)s->pw.lds_bytes;
     return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg.lds_bytes : 0;
   }
   if (!strcmp(key, "dgrad_lds_bytes")) return s && s->data == kBwdMfma ? (long)s->dgm.lds_bytes : 0;
@@ -211,6 +212,8 @@ int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, i
   if (wgrad_options) {
     if ((rc = escoin_plan_set_option(q, "wgrad_kernel", owner->wgrad_kernel)) != ESCOIN_OK) return rc;
     if ((rc = escoin_plan_set_option(q, "wgrad_channel_block", owner->wgrad_channel_block)) != ESCOIN_OK) return rc;
+    if ((rc = escoin_plan_set_option(q, "wgrad_pointwise", owner->wgrad_pointwise)) != ESCOIN_OK) return rc;
+    if ((rc = escoin_plan_set_option(q, "wgrad_pointwise_tile_entries", owner->wgrad_pw_tile_entries)) != ESCOIN_OK) return rc;
   }
   const std::vector<float> flat = flat_entries(owner->values);
   std::vector<float> vals(csr.src.size());
@@ -669,7 +672,7 @@ int escoin_plan_destroy(escoin_plan *plan) {
 int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
   return guarded([&]() -> int {
     if (!p || !key) return fail(ESCOIN_EINVAL, "null argument");
-    // ("wgrad_kernel" on an aligned plan: read when the next backward state is built -- after a refused forced kernel, or
+    // ("wgrad_kernel" and "wgrad_pointwise" on an aligned plan: read when the next backward state is built -- after a refused forced kernel, or
     //  after the next align; a state that exists keeps its kernel)
     if (!strcmp(key, "s2d")) {
       if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "s2d must be 0 or 1");
@@ -711,7 +714,7 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       return ESCOIN_OK;
     }
     if (p->aligned && strcmp(key, "conv_mode") != 0 && strcmp(key, "cpu_channel_block") != 0 && strcmp(key, "cpu_images_per_job") != 0 &&
-        strcmp(key, "wgrad_kernel") != 0)
+        strcmp(key, "wgrad_kernel") != 0 && strcmp(key, "wgrad_pointwise") != 0)
       return fail(ESCOIN_ESTATE, "this option must be set before weight_align/set_csr");
     if (!strcmp(key, "tiling_batch")) {
       if (value < 0) return fail(ESCOIN_EINVAL, "tiling_batch must be >= 0");
@@ -755,6 +758,19 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       // (options "b2s" and "deconv": the weight gradient is the inner plan's, which reads the option as this plan would)
       if (p->b2s_state) return escoin_plan_set_option(p->b2s_state->inner.plan.get(), key, value);
       if (p->d2s_state) return escoin_plan_set_option(p->d2s_state->inner.plan.get(), key, value);
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "wgrad_pointwise")) {
+      if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "wgrad_pointwise must be 0 or 1");
+      p->wgrad_pointwise = value;
+      // (options "b2s" and "deconv": handed on as "wgrad_kernel" is)
+      if (p->b2s_state) return escoin_plan_set_option(p->b2s_state->inner.plan.get(), key, value);
+      if (p->d2s_state) return escoin_plan_set_option(p->d2s_state->inner.plan.get(), key, value);
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "wgrad_pointwise_tile_entries")) {
+      if (value < 0) return fail(ESCOIN_EINVAL, "wgrad_pointwise_tile_entries must be >= 0");
+      p->wgrad_pw_tile_entries = value;
       return ESCOIN_OK;
     }
     if (!strcmp(key, "wgrad_channel_block")) {

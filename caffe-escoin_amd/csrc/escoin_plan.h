@@ -129,6 +129,18 @@ struct WgmState {
   size_t bytes() const { return ent.bytes() + cnt.bytes() + ktab.bytes(); }
 };
 
+// The pointwise weight-gradient kernel (ESCOIN_WGRAD_POINTWISE; wgrad_pointwise.hip; the tiling: align_rules.h pw_plan on
+// the plan's CSR; the tables: csr_tables.h pw_tables)
+struct PwWgrad {
+  int tiles = 0, bias_tiles = 0;   // workgroups per chunk; the leading ones that sum the bias
+  int lane_entries = 1;            // E: the kernel instantiation
+  size_t lds_bytes = 0;
+  DeviceBuffer tile;  // [tiles][kPwTileWords]
+  DeviceBuffer ent;   // per item: the CSR entry
+  DeviceBuffer pk;    // per item: (G row << 16) | bottom row of the tile's LDS image
+  size_t bytes() const { return tile.bytes() + ent.bytes() + pk.bytes(); }
+};
+
 // The fp32-MFMA data-gradient kernel (kBwdMfma; dgrad_mfma.hip; the tables: csr_tables.h dgrad_mfma_tables)
 struct DgmState {
   int phases = 0, ctiles = 0, cols_total = 0;
@@ -161,6 +173,7 @@ struct BwdState {
   int wgrad = ESCOIN_WGRAD_ENTRY, last_wgrad = 0;
   StagedWgrad stg;
   WgmState wgm;
+  PwWgrad pw;
   double align_ms = 0.0;
 };
 
@@ -352,6 +365,8 @@ struct escoin_plan {
   int bwd_kernel = ESCOIN_KERNEL_AUTO;
   int wgrad_kernel = ESCOIN_WGRAD_AUTO;   // option "wgrad_kernel"
   int wgrad_channel_block = 0;            // option "wgrad_channel_block" (0: from the geometry and the LDS budget)
+  int wgrad_pointwise = 0;                // option "wgrad_pointwise": AUTO runs the pointwise kernel where it serves the plan
+  int wgrad_pw_tile_entries = 0;          // option "wgrad_pointwise_tile_entries" (test option; 0: the rule)
   std::unique_ptr<escoin::BwdState> bwd;
 
   // In-place weight updates (update_values.hip): the state the first escoin_update_values builds; reset with the device
@@ -437,7 +452,8 @@ int realign_from_host_csr(escoin_plan *p, hipStream_t stream);
 // escoin_capi.hip (in the core for the reason S2dHooks gives below): a derived plan of the float plan `owner` into *out --
 // descriptor `desc`, the owner's options and these two kernel options, aligned on `csr` with the owner's values permuted
 // through csr.src, which becomes out->src; tiling_batch >= 0 replaces the owner's "tiling_batch" (option "s2b": the inner
-// plan's images are the owner's times P); wgrad_options hands the owner's "wgrad_kernel" and "wgrad_channel_block" down too
+// plan's images are the owner's times P); wgrad_options hands the owner's "wgrad_kernel", "wgrad_channel_block", "wgrad_pointwise" and
+// "wgrad_pointwise_tile_entries" down too
 // (option "b2s": the inner plan computes the weight gradient).  A failure returns the failed call's code; the caller drops *out with its state.
 int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, int kernel, int backward_kernel,
                        DerivedCsr csr, hipStream_t stream, DerivedPlan *out, int tiling_batch = -1, bool wgrad_options = false);
@@ -506,6 +522,13 @@ int dense_spare_rows();       // zero rows after row M - 1
 int wgm_build(const escoin_plan *p, const WgmPlan &wp, WgmState *w, hipStream_t stream);
 int launch_wgrad_mfma(const escoin_plan *p, const WgmState &w, long nnz, const float *bottom, const float *top,
                       const float *top_diff, float *slab_w, int n_images, int chunks, hipStream_t stream);
+
+// wgrad_pointwise.hip (option "wgrad_pointwise"): plans the tiles on the plan's CSR with the options bwd_choice read, and
+// builds the kernel's tables; stage 1 of the weight and / or bias gradient (slab_w null: the bias alone, slab_b likewise)
+// over `chunks` chunks of n_images images into slab_w [chunks][nnz] and slab_b [chunks][M]
+int pw_build(const escoin_plan *p, const BwdOptions &o, PwWgrad *w, hipStream_t stream);
+int launch_wgrad_pointwise(const escoin_plan *p, const PwWgrad &w, long nnz, const float *bottom, const float *top,
+                           const float *top_diff, float *slab_w, float *slab_b, int n_images, int chunks, hipStream_t stream);
 
 // dgrad_mfma.hip (option "backward_kernel" = ESCOIN_BWD_MFMA): builds the phase matrices and the kernel's tables for the
 // tile plan bwd_choice made; the data gradient of n_images images

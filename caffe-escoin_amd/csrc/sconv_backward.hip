@@ -27,16 +27,17 @@
 //     escoin_sconv_wgrad_sum_kernel      one lane per entry (and per bias): its slab column summed in chunk order, the
 //                                        total added into weight_diff / bias_diff.  Every position has one owner.
 //     (option "wgrad_kernel": stage 1 by the LDS-staged kernel below, or by the fp32-MFMA kernel of wgrad_mfma.hip -- same
-//     chunks, same slab; the MFMA kernel's bias gradient is the entry kernel's, launched for the bias alone)
+//     chunks, same slab; the MFMA kernel's bias gradient is the entry kernel's, launched for the bias alone.  option
+//     "wgrad_pointwise": stage 1 of pointwise layers by the kernel of wgrad_pointwise.hip where AUTO would decide)
 //
 // Which of these kernels a plan gets, and what it refuses, is decided by the host-only rule bwd_choice (align_rules.h);
 // bwd_build here calls it once and does the device work.  The backward state (BwdState, escoin_plan.h: one sub-struct per
-// kernel -- GatherDgrad, DgmState, StagedWgrad, WgmState -- next to the transposed plan, the slab and the ReLU scratch) is
+// kernel -- GatherDgrad, DgmState, StagedWgrad, WgmState, PwWgrad -- next to the transposed plan, the slab and the ReLU scratch) is
 // built by the first backward on an aligned plan -- its index tables by the host-only builders of csr_tables.h, this file
 // uploads them -- and dropped with the device side (free_device: weight_align / set_csr / import_aligned; destroy); later
 // calls allocate nothing and synchronise nothing, so they can be captured into a graph.  backward_gpu is the driver:
 // checks, state, then data_gradient (a switch over BwdState::data, one function per path) and weight_gradient
-// (wgrad_entry / wgrad_staged / wgrad_mfma over the shared stage-1 and stage-2 launch helpers).
+// (wgrad_entry / wgrad_staged / wgrad_mfma / wgrad_pointwise over the shared stage-1 and stage-2 launch helpers).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -565,7 +566,8 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   if (const int rcs = sync_host_values(p)) return rcs;
   const Geometry &g = p->g;
   const long nnz = plan_nnz(p);
-  const BwdOptions o{p->bwd_kernel, p->wgrad_kernel, p->wgrad_channel_block, p->inner_plan() != nullptr};
+  const BwdOptions o{p->bwd_kernel, p->wgrad_kernel, p->wgrad_channel_block, p->inner_plan() != nullptr, p->wgrad_pointwise,
+                     p->wgrad_pw_tile_entries};
   const BwdChoice c = bwd_choice(g, p->is_f64, nnz, o, tiled_device_cus());
   if (c.rc != ESCOIN_OK) return fail(c.rc, c.error);
   p->bwd.reset(new BwdState());
@@ -578,6 +580,7 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   ESCOIN_HIP_TRY(s->slab.alloc(sizeof(T) * (size_t)s->chunks_max * (size_t)(nnz + g.d.M)));
   if (c.wgrad == ESCOIN_WGRAD_MFMA) rc = wgm_build(p, c.wgm, &s->wgm, stream);
   else if (c.wgrad == ESCOIN_WGRAD_STAGED) rc = stg_build(p, c.stg, &s->stg, stream);
+  else if (c.wgrad == ESCOIN_WGRAD_POINTWISE) rc = pw_build(p, o, &s->pw, stream);
   if (rc != ESCOIN_OK) return rc;
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
   s->align_ms = ms_since(t0);
@@ -657,7 +660,7 @@ static int data_gradient(escoin_plan *p, const T *top, const T *top_diff, T *bot
   return dgrad_gather<T>(p, top, top_diff, bottom_diff, n_images, stream);
 }
 
-// ---- weight / bias gradient: stage 1 by one of three kernels, stage 2 by one of two sums -----------------------------
+// ---- weight / bias gradient: stage 1 by one of four kernels, stage 2 by one of two sums -----------------------------
 // One call's blobs, outputs (either may be null), slab and chunks.
 template <typename T>
 struct WgradCall {
@@ -765,6 +768,14 @@ static int wgrad_mfma(const escoin_plan *p, const WgradCall<float> &c) {
   return rc;
 }
 
+// option "wgrad_pointwise": weights and bias by the pointwise kernel (wgrad_pointwise.hip), then the tree sum
+static int wgrad_pointwise(const escoin_plan *p, const WgradCall<float> &c) {
+  const BwdState *s = p->bwd.get();
+  const int rc = launch_wgrad_pointwise(p, s->pw, s->nnz, c.bottom, c.top, c.top_diff, c.weight_diff ? c.slab_w : nullptr,
+                                        c.bias_diff ? c.slab_b : nullptr, c.n_images, c.chunks, c.stream);
+  return rc != ESCOIN_OK ? rc : launch_tree_sum(p, c, c.weight_diff, c.bias_diff);
+}
+
 template <typename T>
 static int weight_gradient(escoin_plan *p, const T *bottom, const T *top, const T *top_diff, T *weight_diff, T *bias_diff,
                            int n_images, hipStream_t stream, bool compact) {
@@ -778,6 +789,7 @@ static int weight_gradient(escoin_plan *p, const T *bottom, const T *top, const 
   if constexpr (sizeof(T) == 4) {   // (a double plan's weight gradient is the entry kernel's: bwd_choice)
     if (s->wgrad == ESCOIN_WGRAD_STAGED) return wgrad_staged(p, c);
     if (s->wgrad == ESCOIN_WGRAD_MFMA) return wgrad_mfma(p, c);
+    if (s->wgrad == ESCOIN_WGRAD_POINTWISE) return wgrad_pointwise(p, c);
   }
   return wgrad_entry<T>(p, c);
 }

@@ -751,14 +751,36 @@ ESCOIN_API int escoin_cpu_sparse_dense2csr_f64(int M, int N, const double *A, do
  * geometry and n_images only; its low bits differ from the other two kernels'.  Only CSR positions are written (a NaN
  * elsewhere stays NaN, explicit zeros receive their gradient).  Its bias gradient is the entry kernel's, bit for bit:
  * escoin_sconv_wgrad_partial_kernel launched for the bias alone, then escoin_sconv_wgrad_sum_kernel.
+ * Option "wgrad_pointwise" (0 or 1, default 0; settable whenever "wgrad_kernel" is, and read when the next backward state
+ * is built): with "wgrad_kernel" at ESCOIN_WGRAD_AUTO, a plan the pointwise rule serves runs stage 1 -- weights and bias --
+ * by escoin_sconv_wgrad_pointwise_kernel, then escoin_sconv_wgrad_tree_sum_kernel.  A plan the rule does not serve
+ * behaves exactly as without the option (same kernel, same bits); a forced "wgrad_kernel" wins over it; AUTO never picks
+ * the kernel by itself.  It is not a value of "wgrad_kernel" (4 is refused there).  Served: float plans with KH = KW = 1
+ * and pad 0, any stride and group count, with N*OH*OW, C*H*W and nnz below 2^31 and at most 65535 chunks of 1024 pixels
+ * (N*OH*OW <= 67 107 840); a double plan is not served.  One workgroup per (tile, chunk), a tile being a slice of a conv
+ * group's output channels crossed with a block of its input channels: the tile's G rows and bottom rows go through LDS 32
+ * pixels at a time (the ReLU mask and the stride gather applied on the way in), and each lane owns up to 16 of the
+ * tile's entries, one accumulator register each.  Sum order: per (chunk, entry) ONE fma chain from +0 over the chunk's
+ * pixels in ascending order, in one lane with no cross-lane step (likewise the bias: one lane's chain of additions per
+ * chunk and output channel), then the chunks by the tree sum -- a function of the geometry, the pattern's positions and
+ * n_images only, whatever the tiling; the low bits differ from the other kernels'.  Only CSR positions are written,
+ * explicit zeros receive their gradient, images at or past n_images are not read, a non-finite bottom element reaches the
+ * entries of its channel only, and a bias-only call stages no bottom.  Options "b2s" and "deconv" hand the option to
+ * their inner plan, which is pointwise for every inner-product layer and for deconvolutions whose kernel does not exceed
+ * the stride; "s2d" / "s2b" compute the weight gradient on the outer plan, which the option serves where that plan itself
+ * is pointwise (a 1x1 stride-2 layer under "s2d").  Measurements: profiles/wgrad_pointwise_mi355x.md.
  * Option "wgrad_channel_block" (test option, before the align): 0 = as many input channels per staged block as the
- * LDS budget holds, n = at most n.  Results do not depend on it.
- * Stats: "wgrad_kernel" (ESCOIN_WGRAD_ENTRY / _STAGED / _MFMA: what the last weight / bias gradient ran; ESCOIN_ESTATE
- * before the first one), "wgrad_lds_bytes" (LDS of a staged or an MFMA workgroup; 0 on the entry kernel). */
+ * LDS budget holds, n = at most n; it caps the pointwise kernel's channel block too.  Results do not depend on it.
+ * Option "wgrad_pointwise_tile_entries" (test option, before the align; >= 0): 0 = a pointwise tile holds up to 4096
+ * entries, n = at most min(n, 4096).  Results do not depend on it.
+ * Stats: "wgrad_kernel" (ESCOIN_WGRAD_ENTRY / _STAGED / _MFMA / _POINTWISE: what the last weight / bias gradient ran;
+ * ESCOIN_ESTATE before the first one), "wgrad_lds_bytes" (LDS of a staged, an MFMA or a pointwise workgroup; 0 on the
+ * entry kernel). */
 #define ESCOIN_WGRAD_AUTO 0
 #define ESCOIN_WGRAD_ENTRY 1   /* escoin_sconv_wgrad_partial_kernel: one workgroup per (chunk, output channel) */
 #define ESCOIN_WGRAD_STAGED 2  /* escoin_sconv_wgrad_staged_kernel: the chunk's bottom staged in LDS */
 #define ESCOIN_WGRAD_MFMA 3    /* escoin_sconv_wgrad_mfma_kernel: G x im2col(bottom) on the fp32 matrix cores */
+#define ESCOIN_WGRAD_POINTWISE 4 /* escoin_sconv_wgrad_pointwise_kernel (option "wgrad_pointwise"): a value of the stat only */
 #define ESCOIN_BWD_MFMA 5      /* option "backward_kernel" only: escoin_sconv_dgrad_mfma_kernel, one gather-GEMM per stride phase */
 ESCOIN_API int escoin_backward(escoin_plan *plan, const float *bottom_dev, const float *top_dev, const float *top_diff_dev,
                     float *bottom_diff_dev, float *weight_diff_dev, float *bias_diff_dev, int n_images, void *stream);
