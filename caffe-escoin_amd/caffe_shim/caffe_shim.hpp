@@ -116,10 +116,14 @@ class Caffe {
   // serve, a forced wgrad_kernel, and CPU mode, run as without it
   static bool wgrad_pointwise() { return Get().wgrad_pointwise_; }
   static void set_wgrad_pointwise(bool on) { Get().wgrad_pointwise_ = on; }
+  // whether the plans layers create from now on run depthwise layers (one input channel per group) on the depthwise kernel
+  // pair (include/escoin.h option "depthwise"); a layer the option does not serve, and CPU mode, run as without it
+  static bool depthwise() { return Get().depthwise_; }
+  static void set_depthwise(bool on) { Get().depthwise_ = on; }
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), wgrad_pointwise_(false) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), wgrad_pointwise_(false), depthwise_(false) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
@@ -129,6 +133,7 @@ class Caffe {
   bool s2b_;
   bool b2s_;
   bool wgrad_pointwise_;
+  bool depthwise_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -456,6 +461,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2b", Caffe::s2b() && !deconv_ ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "b2s", Caffe::b2s() && !deconv_ ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_pointwise", Caffe::wgrad_pointwise() ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "depthwise", Caffe::depthwise() ? 1 : 0));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;

@@ -771,6 +771,68 @@ bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp) {
   return true;
 }
 
+bool dw_plan(const Geometry &g, bool is_f64, int band_rows, int n_cu, DwPlan *dp) {
+  const escoin_conv_desc &d = g.d;
+  if (is_f64 || g.Cg != 1) return false;
+  const double two31 = 2147483648.0;
+  if ((double)d.H * d.W >= two31 || (double)g.OH * g.OW >= two31) return false;
+  const long region = kDwWaveLdsBytes / (long)sizeof(float);
+  auto up4 = [](long v) { return (v + 3) / 4 * 4; };
+  DwPlan p;
+  // forward: the window's columns run from image column -padl to the last one the lanes of a row read
+  p.padl = (int)up4(d.pad_w);
+  const long pitch = up4(p.padl - d.pad_w + (up4(g.OW) - 1) * d.stride_w + (long)(d.KW - 1) * d.dil_w + 1);
+  const long row1 = (long)(d.KH - 1) * d.dil_h + 1;             // the window of one output row
+  if (pitch * row1 > region) return false;
+  const long dpitch = up4(g.OW);
+  int t0, t1;
+  long most = 0;                                                 // the most top rows one bottom row reads
+  // (periodic in h with period stride_h away from the edges; the edges only clip)
+  for (int h = 0; h < d.H && h < 2 * d.stride_h + (d.KH - 1) * d.dil_h + 1; ++h) {
+    dw_top_rows(d, g.OH, h, h + 1, &t0, &t1);
+    most = std::max<long>(most, t1);
+  }
+  if (dpitch * most > region) return false;
+  const long want = (long)kDwWaves * 4 * std::max(n_cu, 1);
+  // the tallest band whose rows fit, then enough units
+  auto settle = [&](long fit, int extent, int width, long per_image) {
+    long band = std::min<long>(std::max<long>(fit, 1), extent);
+    band = std::min(band, std::max(1L, (long)kDwLaneItems * 4 * 64 / up4(width)));
+    while (band > 1 && per_image * ((extent + band - 1) / band) < want) band = (band + 1) / 2;
+    if (band_rows > 0) band = std::min<long>(band, band_rows);
+    return (int)band;
+  };
+  p.pitch = (int)pitch;
+  p.band = settle((region / pitch - row1) / d.stride_h + 1, g.OH, g.OW, (long)d.N * d.group);
+  p.nbands = (g.OH + p.band - 1) / p.band;
+  p.rows = (int)((long)(p.band - 1) * d.stride_h + row1);
+  // data gradient: the tallest bottom band whose top rows fit (rows grow by at most one per bottom row)
+  long fit = 1;
+  while (fit < d.H && (fit + (long)(d.KH - 1) * d.dil_h) / d.stride_h + 1 <= region / dpitch) ++fit;
+  p.dpitch = (int)dpitch;
+  p.dband = settle(fit, d.H, d.W, (long)d.N * d.C);
+  p.dnbands = (d.H + p.dband - 1) / p.dband;
+  for (int b = 0; b < p.dnbands; ++b) {
+    dw_top_rows(d, g.OH, b * p.dband, std::min(d.H, (b + 1) * p.dband), &t0, &t1);
+    p.drows = std::max(p.drows, t1);
+  }
+  if ((long)p.drows * dpitch > region || (long)p.rows * pitch > region) return false;   // (the bounds above hold: a guard)
+  auto lane_px = [](int band, int width) {
+    for (int px = 4; px > 1; px /= 2)
+      if ((long)band * ((width + px - 1) / px) >= 64) return px;
+    return 1;
+  };
+  p.px = lane_px(p.band, g.OW);
+  p.dpx = lane_px(p.dband, d.W);
+  p.units = (long)d.N * d.group * p.nbands;
+  p.dunits = (long)d.N * d.C * p.dnbands;
+  if (p.units > kDwMaxUnits || p.dunits > kDwMaxUnits) return false;
+  p.lds_bytes = sizeof(float) * (size_t)kDwWaves * (size_t)p.rows * (size_t)p.pitch;
+  p.dlds_bytes = sizeof(float) * (size_t)kDwWaves * (size_t)std::max(p.drows, 1) * (size_t)p.dpitch;
+  *dp = p;
+  return true;
+}
+
 bool bwd_transposable(const Geometry &g, bool is_f64) {
   const escoin_conv_desc &d = g.d;
   return !is_f64 && d.stride_h == 1 && d.stride_w == 1 && d.pad_h <= d.dil_h * (d.KH - 1) &&
@@ -805,6 +867,9 @@ BwdChoice bwd_choice(const Geometry &g, bool is_f64, long nnz, const BwdOptions 
   c.data = inner ? kBwdInner
            : o.backward_kernel == ESCOIN_BWD_MFMA ? kBwdMfma
            : transposable && o.backward_kernel != ESCOIN_KERNEL_GENERIC ? kBwdTransposed : kBwdGather;
+  // option "depthwise": AUTO's answer gives way on a plan the depthwise kernel serves; a forced kernel and an inner plan do not
+  if (o.depthwise && o.backward_kernel == ESCOIN_KERNEL_AUTO && !o.s2d && dw_plan(g, is_f64, o.dw_band_rows, n_cu, &c.dw))
+    c.data = kBwdDepthwise;
   if (o.wgrad_kernel == ESCOIN_WGRAD_MFMA) c.wgrad = ESCOIN_WGRAD_MFMA;
   else if (staged_ok && (o.wgrad_kernel == ESCOIN_WGRAD_STAGED ||
                          (o.wgrad_kernel == ESCOIN_WGRAD_AUTO && stg_auto_prefers(g, nnz, c.stg, n_cu))))

@@ -353,6 +353,59 @@ struct DgmPlan {
 // 65535 (group, channel tile) pairs: the grid's y and z; fewer than 2^31 (group, phase, channel tile) triples).
 bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp);
 
+// ---- the depthwise kernel pair (depthwise.hip, plan option "depthwise") ----------------------------------------------
+// Layers with one input channel per conv group (Cg == 1; Mg is the channel multiplier).  A workgroup has kDwWaves waves and
+// every wave takes a work unit of its own -- forward: (image, conv group, band of output rows); data gradient: (image,
+// input channel, band of bottom rows) -- with a private LDS region of at most kDwWaveLdsBytes: no workgroup barrier.
+//   forward   the region holds the band's input window, `rows` rows of `pitch` floats: window row r is image row
+//             o0 * stride_h - pad_h + r, window column x is image column x - padl (padl = pad_w rounded up to 4, so that an
+//             aligned quad of the image is an aligned quad of the window); what lies outside the image is written as +0.
+//             pitch (a multiple of 4) reaches the last column a lane's `px` pixels read, dead pixels of a row's last
+//             lane included;
+//   dgrad     the region holds the top_diff rows the bottom band reads, of one output channel at a time: `drows` rows of
+//             `dpitch` floats, column x = ow.
+// Both regions store a row de-interleaved by the lane's pixel count P (1, 2 or 4): column x lies at (x % P) * (pitch / P)
+// + x / P.  A lane owns P consecutive pixels of a row, so for one tap the lanes of a wave read consecutive words (at
+// stride 1) instead of words P apart -- no bank conflicts -- and the staging pass writes a quad as four such runs.
+constexpr int kDwWaves = 4;
+constexpr int kDwWaveLdsBytes = 8 * 1024;            // five workgroups per CU
+constexpr int kDwLaneItems = 4;                      // runs of P pixels a lane holds in registers at once
+constexpr long kDwMaxUnits = 0x7fffffffL - kDwWaves; // grid x = ceil(units / kDwWaves)
+struct DwPlan {
+  int band = 0, nbands = 0;       // output rows per band, bands per image
+  int px = 1;                     // pixels each lane owns along an output row
+  int rows = 0, padl = 0, pitch = 0;   // the window of a full band
+  size_t lds_bytes = 0;           // per workgroup: kDwWaves * sizeof(float) * rows * pitch
+  long units = 0;                 // N * group * nbands
+  int dband = 0, dnbands = 0;     // bottom rows per band, bands per image
+  int dpx = 1;                    // pixels each lane owns along a bottom row
+  int drows = 0, dpitch = 0;      // the top_diff rows of a full band
+  size_t dlds_bytes = 0;
+  long dunits = 0;                // N * C * dnbands
+};
+// The input rows output rows [o0, o1) read, as the window: its first image row (may be negative) and its rows.
+constexpr void dw_window(const escoin_conv_desc &d, int o0, int o1, int *first, int *rows) {
+  *first = o0 * d.stride_h - d.pad_h;
+  *rows = (o1 - 1 - o0) * d.stride_h + (d.KH - 1) * d.dil_h + 1;
+}
+// The top rows bottom rows [h0, h1) receive from: oh with oh * stride_h = h + pad_h - kr * dil_h for an h of the band and a
+// kr < KH, clipped to [0, OH).  rows <= 0: none.  (constexpr: the kernels call both)
+constexpr void dw_top_rows(const escoin_conv_desc &d, int OH, int h0, int h1, int *first, int *rows) {
+  const int lo = h0 + d.pad_h - (d.KH - 1) * d.dil_h, hi = h1 - 1 + d.pad_h;
+  const int a = lo <= 0 ? 0 : (lo + d.stride_h - 1) / d.stride_h;
+  const int b = hi < 0 ? -1 : hi / d.stride_h < OH - 1 ? hi / d.stride_h : OH - 1;
+  *first = a;
+  *rows = b - a + 1;
+}
+// Whether option "depthwise" serves this plan, and the plan where it does: float plans with Cg == 1 -- any Mg, kernel
+// shape, stride, pad and dilation -- whose planes (H * W, OH * OW) and windows stay below 2^31 elements, whose window of ONE
+// output row and whose top_diff rows of ONE bottom row fit kDwWaveLdsBytes, and whose units stay within kDwMaxUnits.
+//   band    the most output rows whose window fits the region (at most OH, and at most kDwLaneItems * 4 * 64 pixels: what a
+//           wave's lanes hold in registers at once), halved while the full batch has fewer than kDwWaves * 4 * n_cu units; band_rows > 0 (test option "depthwise_band_rows") caps it.  dband likewise on bottom rows.
+//   px      the largest of 4, 2, 1 that leaves a full band at least 64 runs (a wave of lanes), else 1.
+// A function of the geometry and n_cu alone; no result's bits depend on it.
+bool dw_plan(const Geometry &g, bool is_f64, int band_rows, int n_cu, DwPlan *dp);
+
 // ---- the backward's kernels (sconv_backward.hip) -------------------------------------------------------------------
 // Whether the data gradient can run as a stride-1 forward of top_diff with the transposed, flipped weights: float plans,
 // stride 1, pad <= dilation * (kernel - 1), at most 32767 output channels per group (a plan's channel limit).
@@ -364,10 +417,13 @@ struct BwdOptions {
   int backward_kernel, wgrad_kernel, wgrad_channel_block;
   bool s2d;
   int wgrad_pointwise = 0, pw_tile_entries = 0;
+  int depthwise = 0, dw_band_rows = 0;   // option "depthwise"; test option "depthwise_band_rows"
 };
 // Who computes the data gradient: the inner plan of option "s2d" / "s2b" (AUTO, TILED, JIT and DENSE on such a plan; the inner
-// plan refuses what it cannot serve), the transposed forward plan, the gather kernel, the MFMA kernel of dgrad_mfma.hip.
-enum BwdDataPath { kBwdInner, kBwdTransposed, kBwdGather, kBwdMfma };
+// plan refuses what it cannot serve), the transposed forward plan, the gather kernel, the MFMA kernel of dgrad_mfma.hip, the
+// depthwise kernel of depthwise.hip (option "depthwise" under AUTO on a plan dw_plan serves and that has no inner plan; a
+// forced backward_kernel wins).
+enum BwdDataPath { kBwdInner, kBwdTransposed, kBwdGather, kBwdMfma, kBwdDepthwise };
 // What the first backward on an alignment builds, or why it builds nothing: rc != ESCOIN_OK is a refusal with its message
 // (the first of the ladder's that applies).  stg / wgm / dgm are filled for the kernel that wgrad / data names.
 struct BwdChoice {
@@ -380,6 +436,7 @@ struct BwdChoice {
   WgmPlan wgm;
   PwPlan pw;                        // (the tiling that bounds every pattern: the state's builder plans again on the CSR)
   DgmPlan dgm;
+  DwPlan dw;                        // (kBwdDepthwise)
   int chunks_max = 0;               // chunks of the full batch: the slab's rows
 };
 BwdChoice bwd_choice(const Geometry &g, bool is_f64, long nnz, const BwdOptions &o, int n_cu);

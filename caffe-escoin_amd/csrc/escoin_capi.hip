@@ -23,6 +23,7 @@ S2bHooks g_s2b_hooks = {nullptr, nullptr, nullptr, nullptr};
 B2sHooks g_b2s_hooks = {nullptr, nullptr, nullptr, nullptr};
 D2sHooks g_d2s_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 D2sCpuHooks g_d2s_cpu_hooks = {nullptr, nullptr};
+DwHooks g_dw_hooks = {nullptr, nullptr, {nullptr, nullptr}};
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 
@@ -126,6 +127,7 @@ long bwd_stat(const escoin_plan *p, const char *key) {
     if (!s) return fail(ESCOIN_ESTATE, "bwd_data_kernel: no backward has run on this alignment");
     if (s->data == kBwdInner) return bwd_stat(p->inner_plan()->plan.get(), key);
     if (s->data == kBwdTransposed) return escoin_plan_stat(s->transposed.plan.get(), "kernel_choice");
+    if (s->data == kBwdDepthwise) return ESCOIN_BWD_DEPTHWISE;
     return s->data == kBwdMfma ? ESCOIN_BWD_MFMA : ESCOIN_KERNEL_GENERIC;
   }
   if (!strcmp(key, "bwd_device_bytes")) return (long)device_bytes(p).bwd;
@@ -139,7 +141,8 @@ long bwd_stat(const escoin_plan *p, const char *key) {
     if (s && s->wgrad == ESCOIN_WGRAD_POINTWISE) return (long)s->pw.lds_bytes;
     return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg.lds_bytes : 0;
   }
-  if (!strcmp(key, "dgrad_lds_bytes")) return s && s->data == kBwdMfma ? (long)s->dgm.lds_bytes : 0;
+  if (!strcmp(key, "dgrad_lds_bytes"))
+    return s && s->data == kBwdMfma ? (long)s->dgm.lds_bytes : s && s->data == kBwdDepthwise ? (long)s->dw.dlds_bytes : 0;
   if (!strcmp(key, "bwd_align_us")) return s ? (long)(s->align_ms * 1e3) : 0;
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
@@ -176,6 +179,7 @@ static void free_device(escoin_plan *p) {
   p->s2b_state.reset();
   p->b2s_state.reset();
   p->d2s_state.reset();
+  p->dw_on = false;
   p->gen = GenericArrays();
   tiled_release(p);
   p->col.reset();
@@ -408,6 +412,17 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
   // A forced TILED / JIT on a layer that "s2d" / "s2b" serves in the direct modes names the INNER plan's kernel: the layer's own
   // geometry (a stride, a dilation) has no tiled kernel.  Here the plan stands in a lowered mode, which runs on that geometry
   // without the inner plan, and aligns as under KERNEL_AUTO instead of refusing -- a conv_mode flip left such a plan unaligned.
+  // option "depthwise" (the derived-plan options have declined): a layer with one input channel per group under KERNEL_AUTO
+  // runs escoin_depthwise_kernel on the generic arrays above -- no dense matrix, no tiled build.  A forced kernel and the
+  // lowered modes behave as without the option.
+  if (p->depthwise && g_dw_hooks.forward && direct_mode && p->kernel_choice == ESCOIN_KERNEL_AUTO && dw_plan(g, false, p->dw_band_rows, tiled_device_cus(), &p->dw)) {
+    p->dw_on = true;
+    p->n_dense_groups = 0; p->n_sparse_groups = g.d.group; p->use_dense = false;
+    p->dense_mask = 0; p->sparse_mask = ~0ull; p->small_rule = 0; p->import_fast = false;
+    p->kernel_name = g_dw_hooks.kernel_name[g.d.fuse_relu != 0];
+    p->aligned = true;
+    return ESCOIN_OK;
+  }
   int kernel = p->kernel_choice;
   if ((kernel == ESCOIN_KERNEL_TILED || kernel == ESCOIN_KERNEL_JIT) && !tiled_supported(g) &&
       ((p->s2d && s2d_plan(g, false, &s2p)) || (p->s2b && s2b_plan(g, false, &s2bp)) ||
@@ -706,6 +721,15 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->rowptr.assign(g.d.group, std::vector<int>(g.Mg + 1, 0));
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "depthwise") || !strcmp(key, "depthwise_band_rows")) {
+      const bool band = key[9] != 0;
+      if (band ? value < 0 : (value < 0 || value > 1))
+        return fail(ESCOIN_EINVAL, band ? "depthwise_band_rows must be >= 0" : "depthwise must be 0 or 1");
+      if (p->aligned || p->host_aligned)
+        return fail(ESCOIN_ESTATE, std::string(key) + " must be set before weight_align / weight_align_cpu / set_csr");
+      (band ? p->dw_band_rows : p->depthwise) = value;
+      return ESCOIN_OK;
+    }
     if (!strcmp(key, "b2s_block")) {
       if (value != 0 && (value < kB2sMinBlock || value > kB2sMaxBlock || value % 4 != 0))
         return fail(ESCOIN_EINVAL, "b2s_block must be 0 (the rule) or a multiple of 4 in 4..256");
@@ -805,10 +829,10 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
     } else if (!strcmp(key, "conv_mode")) {
       if (value < ESCOIN_CONV_MODE_LOWERED_GEMM || value > ESCOIN_CONV_MODE_SCONV_PAR)
         return fail(ESCOIN_EINVAL, "conv_mode must be one of Caffe::ConvMode's four values (0..3)");
-      // (an "s2d" / "s2b" plan also rebuilds between the lowered modes, which run on the original geometry, and SCONV / SCONV_PAR)
+      // (an "s2d" / "s2b" / "b2s" / "depthwise" plan also rebuilds between the lowered modes, which run on the original geometry, and SCONV / SCONV_PAR)
       auto direct = [](int m) { return m == ESCOIN_CONV_MODE_SCONV || m == ESCOIN_CONV_MODE_SCONV_PAR; };
       const bool regroup = p->aligned && ((value == ESCOIN_CONV_MODE_LOWERED_GEMM) != (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_GEMM) ||
-                                          ((p->s2d || p->s2b || p->b2s) && !p->is_f64 && direct(value) != direct(p->conv_mode)));
+                                          ((p->s2d || p->s2b || p->b2s || p->depthwise) && !p->is_f64 && direct(value) != direct(p->conv_mode)));
       // (option "deconv": the mode is the inner plan's, which rebuilds itself where it has to)
       if (p->aligned && p->d2s_state) {
         if (const int rcs = sync_host_values(p)) return rcs;
@@ -988,6 +1012,9 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "s2b_scratch_bytes")) return p->s2b_state ? (long)(p->s2b_state->x.bytes() + p->s2b_state->t.bytes()) : 0;
   if (!strcmp(key, "deconv")) return p->d2s_state ? 1 : 0;
   if (!strcmp(key, "deconv_scratch_bytes")) return p->d2s_state ? (long)p->d2s_state->t.bytes() : 0;
+  if (!strcmp(key, "depthwise")) return p->dw_on ? 1 : 0;
+  if (!strcmp(key, "depthwise_band_rows")) return p->dw_on ? p->dw.band : 0;
+  if (!strcmp(key, "depthwise_lds_bytes")) return p->dw_on ? (long)p->dw.lds_bytes : 0;
   if (!strcmp(key, "b2s")) return p->b2s_state ? 1 : 0;
   if (!strcmp(key, "b2s_block")) return p->b2s_state ? p->b2s_state->bp.B : 0;
   if (!strcmp(key, "b2s_scratch_bytes"))
@@ -1231,6 +1258,7 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
     // LOWERED_SPARSE lowers every group, whatever AUTO decided for the direct path
     if (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_SPARSE && p->kernel_choice != ESCOIN_KERNEL_DENSE)
       return launch_lowered(p, bottom_dev, bias_dev, top_dev, n_images, s);
+    if (p->dw_on) return g_dw_hooks.forward(p, p->dw, bottom_dev, bias_dev, top_dev, n_images, s);     // option "depthwise"
     if (p->n_dense_groups > 0) {
       // dense and sparse groups: what the sparse half's launch refuses for sizes is asked first, so that a refused call
       // has written nothing (the dense half's own refusals come before its launch anyway)

@@ -163,6 +163,7 @@ struct BwdState {
   DerivedPlan transposed;   // kBwdTransposed: the data gradient as a stride-1 forward of top_diff; plan null on the other paths
   GatherDgrad gather;
   DgmState dgm;
+  DwPlan dw;           // kBwdDepthwise: the depthwise kernel's plan (depthwise.hip reads gen.vals: no copy of the values, no tables)
   DeviceBuffer wpos;   // per CSR entry: oc * kdim + colidx (its position in weight_diff)
   DeviceBuffer slab;   // [chunks_max][nnz] weight partials, then [chunks_max][M] bias partials
   DeviceBuffer g;      // fuse_relu + kBwdTransposed: top_diff * [top > 0], desc.N x M x OH x OW
@@ -407,6 +408,11 @@ struct escoin_plan {
   std::unique_ptr<escoin::D2sState> d2s_state;
   escoin::DerivedPlan cpu_inner;
   std::vector<float> cpu_t, cpu_wv, cpu_bv;
+  // Depthwise (depthwise.hip): options "depthwise" and "depthwise_band_rows", and the plan upload() keeps where the forward runs
+  // the depthwise kernel (dw_on; reset with the device side)
+  int depthwise = 0, dw_band_rows = 0;
+  bool dw_on = false;
+  escoin::DwPlan dw;
   // the inner plan of whichever of the four options serves this plan (null: none does)
   const escoin::DerivedPlan *inner_plan() const {
     return s2d_state ? &s2d_state->inner : s2b_state ? &s2b_state->inner : b2s_state ? &b2s_state->inner :
@@ -529,6 +535,17 @@ int launch_wgrad_mfma(const escoin_plan *p, const WgmState &w, long nnz, const f
 int pw_build(const escoin_plan *p, const BwdOptions &o, PwWgrad *w, hipStream_t stream);
 int launch_wgrad_pointwise(const escoin_plan *p, const PwWgrad &w, long nnz, const float *bottom, const float *top,
                            const float *top_diff, float *slab_w, float *slab_b, int n_images, int chunks, hipStream_t stream);
+
+// depthwise.hip (option "depthwise"), registered like S2dHooks below (a program that links the core's objects alone runs the
+// option's layers as without it): the forward and the data gradient of n_images images on the plan's generic arrays, and
+// the forward kernel's name without / with the ReLU
+struct DwHooks {
+  int (*forward)(const escoin_plan *p, const DwPlan &dp, const float *bottom, const float *bias, float *top, int n_images, hipStream_t stream);
+  int (*dgrad)(const escoin_plan *p, const DwPlan &dp, const float *top, const float *top_diff, float *bottom_diff, int n_images,
+               hipStream_t stream);
+  const char *kernel_name[2];
+};
+extern DwHooks g_dw_hooks;   // escoin_capi.hip
 
 // dgrad_mfma.hip (option "backward_kernel" = ESCOIN_BWD_MFMA): builds the phase matrices and the kernel's tables for the
 // tile plan bwd_choice made; the data gradient of n_images images

@@ -14,7 +14,9 @@
 //         row in ascending (ocl, kr, kc) order with one fma per contributing entry from 0 -- the order of the CPU mode's
 //         data gradient (sconv_cpu_backward.cpp), so the two are bit-identical;
 //     (c) option backward_kernel = ESCOIN_BWD_MFMA (never AUTO's choice): escoin_sconv_dgrad_mfma_kernel of dgrad_mfma.hip,
-//         one stride-1 gather-GEMM per stride phase on the fp32 matrix cores, for float plans of any geometry.
+//         one stride-1 gather-GEMM per stride phase on the fp32 matrix cores, for float plans of any geometry;
+//     (d) option "depthwise" under AUTO on a plan with one input channel per group: escoin_depthwise_dgrad_kernel of
+//         depthwise.hip, the bits of (b) with top_diff staged in LDS once per band.
 //   weight gradient weight_diff[oc][colidx] += sum over (n, oh, ow) of G * bottom[...], at the CSR positions only;
 //   bias gradient   bias_diff[oc] += sum over (n, oh, ow) of G.
 //     Two deterministic stages, no float atomics (the order of every sum is a function of the geometry and n_images):
@@ -553,6 +555,7 @@ static int build_data(escoin_plan *p, BwdState *s, const BwdChoice &c, hipStream
     case kBwdInner: return ensure_state<float>(p->inner_plan()->plan.get(), stream);
     case kBwdTransposed: return build_transposed_plan(p, s, stream);
     case kBwdMfma: return dgm_build(p, c.dgm, &s->dgm, stream);
+    case kBwdDepthwise: s->dw = c.dw; return ESCOIN_OK;      // (the kernel walks gen.vals: no transposed plan, no gather tables)
     case kBwdGather: break;
   }
   return build_gather<T>(p, &s->gather, stream);
@@ -567,7 +570,7 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   const Geometry &g = p->g;
   const long nnz = plan_nnz(p);
   const BwdOptions o{p->bwd_kernel, p->wgrad_kernel, p->wgrad_channel_block, p->inner_plan() != nullptr, p->wgrad_pointwise,
-                     p->wgrad_pw_tile_entries};
+                     p->wgrad_pw_tile_entries, g_dw_hooks.dgrad ? p->depthwise : 0, p->dw_band_rows};
   const BwdChoice c = bwd_choice(g, p->is_f64, nnz, o, tiled_device_cus());
   if (c.rc != ESCOIN_OK) return fail(c.rc, c.error);
   p->bwd.reset(new BwdState());
@@ -654,6 +657,7 @@ static int data_gradient(escoin_plan *p, const T *top, const T *top_diff, T *bot
       case kBwdInner: return dgrad_inner(p, top, top_diff, bottom_diff, n_images, stream);
       case kBwdTransposed: return dgrad_transposed(p, top, top_diff, bottom_diff, n_images, stream);
       case kBwdMfma: return launch_dgrad_mfma(p, p->bwd->dgm, top, top_diff, bottom_diff, n_images, stream);
+      case kBwdDepthwise: return g_dw_hooks.dgrad(p, p->bwd->dw, top, top_diff, bottom_diff, n_images, stream);
       case kBwdGather: break;
     }
   }

@@ -159,6 +159,7 @@ int for_each_copy(Plan *q, const std::vector<int> *outer, bool with_maps, OnPlan
   if (!s) return ESCOIN_OK;
   switch (s->data) {
     case kBwdInner:   // the data gradient is the inner plan's, whose backward state the walk has just visited: no copy here
+    case kBwdDepthwise:   // the depthwise kernel reads gen.vals, which on_plan has listed: no copy here
       break;
     case kBwdTransposed:
       if (!through(s->transposed.src, &map)) return mismatch("the backward state");

@@ -229,6 +229,14 @@ def googlenet_1x1(N=256, sparsity=0.95):
     return out
 
 
+def mobilenet_dw(N=64, sparsity=0.0):
+    """The 13 depthwise 3x3 layers of MobileNet-v1 (group = C = M, pad 1), as 9 distinct shapes."""
+    table = [(32, 112, 1, 1), (64, 112, 2, 1), (128, 56, 1, 1), (128, 56, 2, 1), (256, 28, 1, 1), (256, 28, 2, 1), (512, 14, 1, 5),
+             (512, 14, 2, 1), (1024, 7, 1, 1)]
+    return [shape("mbv1_dw%d_%d_s%d" % (c, hw, st), N, c, hw, hw, c, 3, pad=1, stride=st, group=c, sparsity=sparsity, count=cnt)
+            for c, hw, st, cnt in table]
+
+
 def nnz_of(s):
     per_group = (s.M // s.group) * (s.C // s.group) * s.KH * s.KW
     return s.group * (per_group - int(round(s.sparsity * per_group)))

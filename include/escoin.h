@@ -775,7 +775,35 @@ ESCOIN_API int escoin_cpu_sparse_dense2csr_f64(int M, int N, const double *A, do
  * entries, n = at most min(n, 4096).  Results do not depend on it.
  * Stats: "wgrad_kernel" (ESCOIN_WGRAD_ENTRY / _STAGED / _MFMA / _POINTWISE: what the last weight / bias gradient ran;
  * ESCOIN_ESTATE before the first one), "wgrad_lds_bytes" (LDS of a staged, an MFMA or a pointwise workgroup; 0 on the
- * entry kernel). */
+ * entry kernel).
+ *
+ * Depthwise.  Option "depthwise" (0 or 1, default 0; before the align; KERNEL_AUTO never turns it on by itself): a float
+ * plan with ONE input channel per conv group (C / group == 1; M / group is the channel multiplier), any kernel shape,
+ * stride, pad and dilation, in conv_mode SCONV / SCONV_PAR, runs the kernel pair of csrc/depthwise.hip.  Every other plan --
+ * a double plan, more input channels per group, a row too long for one wave's 8 KiB LDS region, H*W or OH*OW at or above
+ * 2^31, more than 2^31 - 5 work units -- behaves exactly as without the option, and so does a plan that "deconv", "b2s",
+ * "s2d" or "s2b" serves, a forced "kernel" and a lowered conv_mode; inner plans are not handed the option.
+ *   forward   with "kernel" at AUTO: escoin_depthwise_kernel.  The plan builds the generic kernel's arrays alone (no dense
+ *             matrix, no tiled build).  A wave takes one (image, conv group, band of output rows), stages the band's input
+ *             rows in its own LDS region once (padding as +0) and walks each output channel's CSR row in order, one fmaf
+ *             per nonzero and pixel from +0, then the bias, then the ReLU.  The top blob is BIT-IDENTICAL to
+ *             ESCOIN_KERNEL_GENERIC's, and so to escoin_forward_cpu's, whatever the banding.
+ *   backward  with "backward_kernel" at AUTO (a forced one wins, as does an inner plan): escoin_depthwise_dgrad_kernel.  A
+ *             wave takes one (image, input channel, band of bottom rows) and stages, per output channel of the group, the
+ *             top_diff rows the band receives from (0 where top <= 0 on a fuse_relu plan); a bottom pixel's sum is one
+ *             fmaf per CONTRIBUTING entry in ascending (output channel, kr, kc) order from +0 -- an entry whose tap does
+ *             not reach the pixel is skipped, not multiplied by a zero.  bottom_diff is BIT-IDENTICAL to "backward_kernel"
+ *             = ESCOIN_KERNEL_GENERIC's and to escoin_backward_cpu's; every element of the first n_images images is
+ *             written exactly once.  The backward state then holds no transposed plan and no gather tables; the weight and
+ *             bias gradients are untouched by the option.
+ * Both kernels read the plan's value array, the destination of every in-place update; images at or past n_images are
+ * neither read nor written; no atomics; nothing is allocated or synchronised after the align (the first backward).
+ * Option "depthwise_band_rows" (test option, before the align; >= 0): 0 = the rule chooses the band, n = at most n output
+ * rows (bottom rows for the data gradient) per band.  Results do not depend on it.
+ * Stats: "depthwise" (1 where the aligned plan's forward runs the kernel), "depthwise_band_rows" (the forward's band),
+ * "depthwise_lds_bytes" (LDS of a forward workgroup of four waves), "bwd_data_kernel" == ESCOIN_BWD_DEPTHWISE, and
+ * "dgrad_lds_bytes".  Measurements: profiles/depthwise_mi355x.md. */
+#define ESCOIN_BWD_DEPTHWISE 6 /* stat "bwd_data_kernel" only: escoin_depthwise_dgrad_kernel (option "depthwise") */
 #define ESCOIN_WGRAD_AUTO 0
 #define ESCOIN_WGRAD_ENTRY 1   /* escoin_sconv_wgrad_partial_kernel: one workgroup per (chunk, output channel) */
 #define ESCOIN_WGRAD_STAGED 2  /* escoin_sconv_wgrad_staged_kernel: the chunk's bottom staged in LDS */
