@@ -120,10 +120,15 @@ class Caffe {
   // pair (include/escoin.h option "depthwise"); a layer the option does not serve, and CPU mode, run as without it
   static bool depthwise() { return Get().depthwise_; }
   static void set_depthwise(bool on) { Get().depthwise_ = on; }
+  // whether the plans layers create from now on compute the weight gradient of depthwise layers by the depthwise kernel
+  // (include/escoin.h option "wgrad_depthwise"; independent of set_depthwise); a layer the option does not serve, a forced
+  // wgrad_kernel, and CPU mode, run as without it
+  static bool wgrad_depthwise() { return Get().wgrad_depthwise_; }
+  static void set_wgrad_depthwise(bool on) { Get().wgrad_depthwise_ = on; }
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), wgrad_pointwise_(false), depthwise_(false) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), wgrad_pointwise_(false), depthwise_(false), wgrad_depthwise_(false) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
@@ -134,6 +139,7 @@ class Caffe {
   bool b2s_;
   bool wgrad_pointwise_;
   bool depthwise_;
+  bool wgrad_depthwise_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -462,6 +468,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "b2s", Caffe::b2s() && !deconv_ ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_pointwise", Caffe::wgrad_pointwise() ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "depthwise", Caffe::depthwise() ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_depthwise", Caffe::wgrad_depthwise() ? 1 : 0));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;

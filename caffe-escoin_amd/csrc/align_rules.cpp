@@ -833,6 +833,23 @@ bool dw_plan(const Geometry &g, bool is_f64, int band_rows, int n_cu, DwPlan *dp
   return true;
 }
 
+bool dww_plan(const Geometry &g, bool is_f64, long nnz, long nseg, int band_rows, int slices, int n_cu, DwwPlan *wp) {
+  DwPlan dp;
+  if (!dw_plan(g, is_f64, band_rows, n_cu, &dp)) return false;
+  if (nnz < 0 || nnz > 0x7fffffffL || nseg < 0 || nseg > 0x7fffffffL) return false;
+  DwwPlan p;
+  p.band = dp.band; p.nbands = dp.nbands; p.px = dp.px;
+  p.rows = dp.rows; p.padl = dp.padl; p.pitch = dp.pitch; p.lds_bytes = dp.lds_bytes;
+  const long pairs = (long)g.d.N * dp.nbands;        // (within kDwMaxUnits: dw_plan)
+  const long want = (long)kDwWaves * 4 * std::max(n_cu, 1);
+  const long S = slices > 0 ? slices : (want + g.d.M - 1) / std::max(g.d.M, 1);
+  p.S = (int)std::min(std::max(S, 1L), std::max(pairs, 1L));
+  p.per = (int)std::max(1L, (pairs + p.S - 1) / p.S);
+  if (std::max(nseg, (long)g.d.M) * p.S > kDwMaxUnits) return false;   // (a bias-only call has M units per slice)
+  *wp = p;
+  return true;
+}
+
 bool bwd_transposable(const Geometry &g, bool is_f64) {
   const escoin_conv_desc &d = g.d;
   return !is_f64 && d.stride_h == 1 && d.stride_w == 1 && d.pad_h <= d.dil_h * (d.KH - 1) &&
@@ -878,7 +895,12 @@ BwdChoice bwd_choice(const Geometry &g, bool is_f64, long nnz, const BwdOptions 
   if (o.wgrad_pointwise && o.wgrad_kernel == ESCOIN_WGRAD_AUTO &&
       pw_plan(g, is_f64, nnz, nullptr, nullptr, o.wgrad_channel_block, o.pw_tile_entries, n_cu, &c.pw))
     c.wgrad = ESCOIN_WGRAD_POINTWISE;
+  // option "wgrad_depthwise": likewise, after the pointwise option (a 1x1 depthwise plan with both on is the pointwise kernel's)
+  else if (o.wgrad_depthwise && o.wgrad_kernel == ESCOIN_WGRAD_AUTO &&
+           dww_plan(g, is_f64, nnz, d.M + nnz / kDwwSegEntries, o.dw_band_rows, o.dww_slices, n_cu, &c.dww))
+    c.wgrad = ESCOIN_WGRAD_DEPTHWISE;
   c.chunks_max = (int)(((long)d.N * g.OH * g.OW + kBwdChunkPixels - 1) / kBwdChunkPixels);
+  if (c.wgrad == ESCOIN_WGRAD_DEPTHWISE) c.chunks_max = std::max(c.chunks_max, c.dww.S);
   return c;
 }
 

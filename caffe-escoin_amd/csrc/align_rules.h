@@ -406,6 +406,31 @@ constexpr void dw_top_rows(const escoin_conv_desc &d, int OH, int h0, int h1, in
 // A function of the geometry and n_cu alone; no result's bits depend on it.
 bool dw_plan(const Geometry &g, bool is_f64, int band_rows, int n_cu, DwPlan *dp);
 
+// ---- the depthwise weight-gradient kernel (depthwise.hip, plan option "wgrad_depthwise") ------------------------------
+// A fifth stage 1 of the weight / bias gradient, for the plans dw_plan serves.  Every wave takes a unit (row segment, slice)
+// with a private LDS region, the forward's: a row segment is up to kDwwSegEntries consecutive CSR entries of one output
+// channel's row (csr_tables.h dww_segments), a slice a contiguous run of `per` of the call's (image, band of output rows)
+// pairs in ascending order, bands being the forward's.  The wave stages each pair's input window as the forward does, keeps
+// one accumulator per entry across the slice and stores one partial per (slice, entry): the slab's rows are slices.
+constexpr int kDwwSegEntries = 16;                   // accumulators of a wave: statically indexed registers
+struct DwwPlan {
+  int band = 0, nbands = 0, px = 1;      // DwPlan's forward band, bands per image, pixels per lane
+  int rows = 0, padl = 0, pitch = 0;     // ... and its window
+  size_t lds_bytes = 0;                  // per workgroup: DwPlan's
+  int S = 0;                             // slices of the full batch the rule aims at (the slab's rows)
+  int per = 0;                           // (image, band) pairs per slice: ceil(N * nbands / S), fixed from the full batch
+  // the slices of a call with n_images images: the last one may be short
+  int slices(int n_images) const { return (int)(((long)n_images * nbands + per - 1) / per); }
+};
+// Whether option "wgrad_depthwise" serves this plan, and the plan where it does: what dw_plan serves (band_rows: its test
+// option), with nnz and nseg -- the row segments, or an upper bound of them (M + nnz / kDwwSegEntries bounds every
+// pattern) -- below 2^31 and nseg * S within kDwMaxUnits (grid x).
+//   S     slices > 0 (test option "wgrad_depthwise_slices"): that; else the fewest slices that give at least kDwWaves * 4 *
+//         n_cu units over the M rows, ceil(kDwWaves * 4 * n_cu / M); clamped to [1, N * nbands];
+//   per   ceil(N * nbands / S).
+// The bits of the result are a function of the geometry, n_images, the band and per.
+bool dww_plan(const Geometry &g, bool is_f64, long nnz, long nseg, int band_rows, int slices, int n_cu, DwwPlan *wp);
+
 // ---- the backward's kernels (sconv_backward.hip) -------------------------------------------------------------------
 // Whether the data gradient can run as a stride-1 forward of top_diff with the transposed, flipped weights: float plans,
 // stride 1, pad <= dilation * (kernel - 1), at most 32767 output channels per group (a plan's channel limit).
@@ -418,6 +443,7 @@ struct BwdOptions {
   bool s2d;
   int wgrad_pointwise = 0, pw_tile_entries = 0;
   int depthwise = 0, dw_band_rows = 0;   // option "depthwise"; test option "depthwise_band_rows"
+  int wgrad_depthwise = 0, dww_slices = 0;   // option "wgrad_depthwise"; test option "wgrad_depthwise_slices"
 };
 // Who computes the data gradient: the inner plan of option "s2d" / "s2b" (AUTO, TILED, JIT and DENSE on such a plan; the inner
 // plan refuses what it cannot serve), the transposed forward plan, the gather kernel, the MFMA kernel of dgrad_mfma.hip, the
@@ -431,13 +457,16 @@ struct BwdChoice {
   const char *error = "";
   BwdDataPath data = kBwdGather;
   int wgrad = ESCOIN_WGRAD_ENTRY;   // ESCOIN_WGRAD_ENTRY / STAGED / MFMA: what option "wgrad_kernel" resolves to, or
-                                    // ESCOIN_WGRAD_POINTWISE: AUTO with option "wgrad_pointwise" on a plan pw_plan serves
+                                    // ESCOIN_WGRAD_POINTWISE: AUTO with option "wgrad_pointwise" on a plan pw_plan serves, or
+                                    // ESCOIN_WGRAD_DEPTHWISE: AUTO with option "wgrad_depthwise" on a plan dww_plan serves
+                                    // (and pw_plan does not, or its option is off)
   StgPlan stg;
   WgmPlan wgm;
   PwPlan pw;                        // (the tiling that bounds every pattern: the state's builder plans again on the CSR)
   DgmPlan dgm;
   DwPlan dw;                        // (kBwdDepthwise)
-  int chunks_max = 0;               // chunks of the full batch: the slab's rows
+  DwwPlan dww;                      // (ESCOIN_WGRAD_DEPTHWISE; nseg bounded: the state's builder plans again on the CSR)
+  int chunks_max = 0;               // the slab's rows: the chunks of the full batch, or dww.S where that is more
 };
 BwdChoice bwd_choice(const Geometry &g, bool is_f64, long nnz, const BwdOptions &o, int n_cu);
 

@@ -145,6 +145,26 @@ PwTables pw_tables(const CsrView &v, const PwPlan &plan) {
   return t;
 }
 
+std::vector<int> dww_segments(const CsrView &v) {
+  const Geometry &g = *v.g;
+  std::vector<int> seg;
+  long base = 0;
+  for (int grp = 0; grp < g.d.group; ++grp) {
+    const std::vector<int> &rp = (*v.rowptr)[grp];
+    for (int m = 0; m < g.Mg; ++m) {
+      int j = rp[m];
+      do {
+        const int n = std::min(rp[m + 1] - j, kDwwSegEntries);
+        const int words[kDwwSegWords] = {grp * g.Mg + m, (int)(base + j), n};
+        seg.insert(seg.end(), words, words + kDwwSegWords);
+        j += n;
+      } while (j < rp[m + 1]);
+    }
+    base += rp[g.Mg];
+  }
+  return seg;
+}
+
 WgmTables wgrad_mfma_tables(const CsrView &v, int tile_m, int tile_k) {
   const Geometry &g = *v.g;
   const escoin_conv_desc &d = g.d;

@@ -120,6 +120,13 @@ struct PwPlan;
 struct PwTables { std::vector<int> tile, ent, pk; };
 PwTables pw_tables(const CsrView &v, const PwPlan &plan);
 
+// The depthwise weight-gradient kernel's row segments (align_rules.h DwwPlan), from rowptr alone: per segment {oc, first
+// entry (flat index), entries}, rows in order and a row's segments in order.  A row of n entries has max(1, ceil(n /
+// kDwwSegEntries)) segments of at most kDwwSegEntries entries: every entry is in exactly one segment, and an empty row keeps
+// one empty segment -- a row's FIRST segment (first entry = the row's first) also sums the row's bias.
+constexpr int kDwwSegWords = 3;
+std::vector<int> dww_segments(const CsrView &v);
+
 // The MFMA data-gradient kernel's tables for a tile plan of align_rules.h dgm_plan (P phases, phase index = row residue *
 // stride_w + column residue; ctiles channel tiles of tile_c per conv group; steps of step_k columns):
 //   phase    [8 * P]: {h0, w0, rows, cols, kp, ksteps, col0, ntaps} -- the phase's bottom pixels are (h0 + stride_h * hh,

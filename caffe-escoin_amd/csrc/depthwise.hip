@@ -23,14 +23,30 @@
 //       the gather kernel's chain -- ascending (ocl, kr, kc), one fmaf per contributing entry from +0 -- so bottom_diff is
 //       bit-identical to backward_kernel = GENERIC's.  S1: stride_w == 1, where a tap's column offset is wave-uniform.
 //
+//   escoin_depthwise_wgrad_kernel<RELU, P>   (plan option "wgrad_depthwise": stage 1 of the weight / bias gradient; align_rules.h
+//       DwwPlan)  unit = (row segment, slice): up to kDwwSegEntries consecutive CSR entries of one output channel's row, and a
+//       contiguous run of the call's (image, band of output rows) pairs, bands being the forward's.  Per pair the wave stages
+//       the band's input window as the forward does, every lane loads top_diff for its runs of P output pixels from global
+//       memory into registers (the forward's item / run mapping; 0 where top <= 0 under fuse_relu), and the segment's entries
+//       are walked: acc[k] = fmaf(g, win[base + at_k], acc[k]) per owned pixel, items and pixels ascending -- one LDS read
+//       per fma, the forward's addresses.  The accumulators are statically indexed registers that live across the slice; the
+//       unit ends with one 64-lane butterfly per entry and lane 0's store of one partial per (slice, entry) into the slab of
+//       sconv_backward.hip, whose tree sum is stage 2 over the slices.  A row's first segment also sums the lane's g: the bias.
+//       A padded tap is multiplied as a zero; a dead lane or a dead pixel of a run is left out by a select, so a non-finite
+//       bottom element reaches only the entries whose tap reads it.  A bias-only call has one unit per (output channel,
+//       slice) and stages nothing.
+//
 // LDS layout (align_rules.h): a row is de-interleaved by P -- column x lies at (x % P) * (pitch / P) + x / P -- so that for
 // one tap the lanes of a wave, whose runs start P columns apart, read consecutive words.  Blob bases are 64-bit; offsets
 // inside a plane fit 32 bits (dw_plan).  No atomics; a launch allocates and synchronises nothing.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
+#include <vector>
 
 #include "align_rules.h"
+#include "csr_tables.h"
 #include "escoin_plan.h"
 
 namespace escoin {
@@ -110,6 +126,18 @@ __device__ inline void dw_store(float *__restrict__ out, const float (&s)[P], in
 #pragma unroll
     for (int q = 0; q < P; ++q)
       if (col + q < width) out[q] = s[q];
+  }
+}
+
+// One run of P values (P = 4 or 2) in a single aligned load
+template <int P>
+__device__ inline void dw_load(const float *__restrict__ in, float (&s)[P]) {
+  if constexpr (P == 4) {
+    const float4 t = *reinterpret_cast<const float4 *>(in);
+    s[0] = t.x; s[1] = t.y; s[2] = t.z; s[3] = t.w;
+  } else {
+    const float2 t = *reinterpret_cast<const float2 *>(in);
+    s[0] = t.x; s[1] = t.y;
   }
 }
 
@@ -269,6 +297,154 @@ escoin_depthwise_dgrad_kernel(DwArgs a) {
   }
 }
 
+struct DwwArgs {
+  const float *__restrict__ bottom;
+  const float *__restrict__ top_diff;
+  const float *__restrict__ top;     // fuse_relu only
+  const int *__restrict__ rowptr;
+  const int *__restrict__ taps;
+  const int *__restrict__ seg;       // [nseg][kDwwSegWords]; unread by a bias-only call
+  float *__restrict__ slab_w;        // [slices][nnz]; null: a bias-only call, whose segments are the output channels
+  float *__restrict__ slab_b;        // [slices][M]; null: no bias
+  escoin_conv_desc d;
+  int OH, OW, Mg;
+  int band, nbands, padl, pitch, region;
+  int nseg, slices, per, pairs;      // units = nseg * slices; pairs = n_images * nbands
+  int nnz;
+  int vec_src, vec_g;                // 16-byte loads of the staging pass / one load per run of top_diff
+};
+
+template <bool RELU, int P>
+__global__ void __launch_bounds__(kDwThreads)
+escoin_depthwise_wgrad_kernel(DwwArgs a) {
+  extern __shared__ float dw_lds[];
+  const escoin_conv_desc &d = a.d;
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int unit = __builtin_amdgcn_readfirstlane(blockIdx.x * kDwWaves + wave);
+  if (unit >= a.nseg * a.slices) return;
+  float *win = dw_lds + wave * a.region;
+  const int slice = unit / a.nseg, sg = unit - slice * a.nseg;
+  const bool bias_only = a.slab_w == nullptr;
+  const int oc = bias_only ? sg : a.seg[kDwwSegWords * sg];
+  const int first = bias_only ? 0 : a.seg[kDwwSegWords * sg + 1];
+  const int cnt = bias_only ? 0 : a.seg[kDwwSegWords * sg + 2];
+  const bool bias = a.slab_b != nullptr && (bias_only || first == a.rowptr[oc]);   // a row's first segment owns its bias
+  const int grp = oc / a.Mg;
+  const int Q = a.pitch / P;
+  const int runs = (a.OW + P - 1) / P;
+  const int col0 = a.padl - d.pad_w;
+  const size_t opix = (size_t)a.OH * a.OW;
+  float acc[kDwwSegEntries];
+#pragma unroll
+  for (int k = 0; k < kDwwSegEntries; ++k) acc[k] = 0.f;
+  float accb = 0.f;
+  const int p0 = slice * a.per, p1 = min(a.pairs, p0 + a.per);
+  for (int pr = p0; pr < p1; ++pr) {
+    const int n = pr / a.nbands, b = pr - n * a.nbands;
+    const int o0 = b * a.band, o1 = min(a.OH, o0 + a.band);
+    const int items = (o1 - o0) * runs;
+    if (cnt > 0) {
+      int wfirst, wrows;
+      dw_window(d, o0, o1, &wfirst, &wrows);
+      dw_stage<P, false>(win, a.bottom + ((size_t)n * d.C + grp) * ((size_t)d.H * d.W), nullptr, wfirst, wrows, d.H, d.W, a.padl, a.pitch,
+                         a.vec_src != 0, lane);
+    }
+    const size_t plane = ((size_t)n * d.M + oc) * opix;
+    const float *__restrict__ gsrc = a.top_diff + plane;
+    const float *__restrict__ msrc = RELU ? a.top + plane : nullptr;
+    for (int it0 = 0; it0 < items; it0 += 64 * kDwLaneItems) {
+      const int ni = min(kDwLaneItems, (items - it0 + 63) >> 6);   // wave-uniform
+      float g[kDwLaneItems][P];
+      int base[kDwLaneItems], nlive[kDwLaneItems];   // nlive: the run's live pixels, 0 on a dead lane
+#pragma unroll
+      for (int i = 0; i < kDwLaneItems; ++i) {
+        const int it = it0 + i * 64 + lane;
+        const bool on = i < ni && it < items;
+        const int itc = on ? it : 0;               // (a dead lane reads item 0's window and contributes nothing)
+        const int row = itc / runs, run = itc - row * runs;
+        base[i] = row * d.stride_h * a.pitch + run * d.stride_w;
+        const int col = run * P, opos = (o0 + row) * a.OW + col;
+        nlive[i] = on ? min(P, a.OW - col) : 0;
+#pragma unroll
+        for (int q = 0; q < P; ++q) g[i][q] = 0.f;
+        bool vec = false;
+        if constexpr (P > 1) {
+          vec = a.vec_g != 0;                      // (OW is a multiple of P: a live run has P live pixels)
+          if (vec && on) {
+            dw_load<P>(gsrc + opos, g[i]);
+            if (RELU) {
+              float m[P];
+              dw_load<P>(msrc + opos, m);
+#pragma unroll
+              for (int q = 0; q < P; ++q) g[i][q] = m[q] > 0.f ? g[i][q] : 0.f;
+            }
+          }
+        }
+        if (!vec) {
+#pragma unroll
+          for (int q = 0; q < P; ++q)
+            if (q < nlive[i]) {
+              g[i][q] = gsrc[opos + q];
+              if (RELU && !(msrc[opos + q] > 0.f)) g[i][q] = 0.f;
+            }
+        }
+      }
+      // every lane's every pixel of this pass is live (wave-uniform): no select
+      const bool full = it0 + ni * 64 <= items && runs * P == a.OW;
+      auto walk = [&](auto sel) __attribute__((always_inline)) {
+        constexpr bool SEL = decltype(sel)::value;
+        if (bias) {
+#pragma unroll
+          for (int i = 0; i < kDwLaneItems; ++i)
+            if (i < ni) {
+#pragma unroll
+              for (int q = 0; q < P; ++q) accb = !SEL || q < nlive[i] ? accb + g[i][q] : accb;
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < kDwwSegEntries; ++k)
+          if (k < cnt) {                           // wave-uniform: acc[k] is a register
+            const int tap = a.taps[first + k];
+            const int kr = (tap >> 8) & 0xff, kc = tap & 0xff;
+            int at[P];
+#pragma unroll
+            for (int q = 0; q < P; ++q) at[q] = kr * d.dil_h * a.pitch + dw_pos<P>(q * d.stride_w + kc * d.dil_w + col0, Q);
+#pragma unroll
+            for (int i = 0; i < kDwLaneItems; ++i)
+              if (i < ni) {
+#pragma unroll
+                for (int q = 0; q < P; ++q) {
+                  const float x = win[base[i] + at[q]];
+                  acc[k] = !SEL || q < nlive[i] ? fmaf(g[i][q], x, acc[k]) : acc[k];
+                }
+              }
+          }
+      };
+      if (full) walk(std::false_type());
+      else walk(std::true_type());
+    }
+    // the next pair's window overwrites the region: the reads above were issued before those writes
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  // the pairing of sconv_backward.hip's wave_sum: the same tree on every call
+#pragma unroll
+  for (int k = 0; k < kDwwSegEntries; ++k)
+    if (k < cnt) {
+      float v = acc[k];
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+      if (lane == 0) a.slab_w[(size_t)slice * a.nnz + first + k] = v;
+    }
+  if (bias) {
+    float v = accb;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) a.slab_b[(size_t)slice * d.M + oc] = v;
+  }
+}
+
 namespace {
 
 bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -340,10 +516,61 @@ static int launch_depthwise_dgrad(const escoin_plan *p, const DwPlan &dp, const 
   return ESCOIN_OK;
 }
 
+// option "wgrad_depthwise": the segments of the plan's CSR, the rule on their count with the options bwd_choice read
+static int dww_build(const escoin_plan *p, const BwdOptions &o, DwWgrad *w, hipStream_t stream) {
+  w->host_seg = dww_segments(csr_view(p));
+  const long nseg = (long)(w->host_seg.size() / kDwwSegWords);
+  if (!dww_plan(p->g, p->is_f64, plan_nnz(p), nseg, o.dw_band_rows, o.dww_slices, tiled_device_cus(), &w->plan))
+    return fail(ESCOIN_ESTATE, "depthwise weight-gradient kernel: the rule does not serve this plan");
+  w->nseg = (int)nseg;
+  ESCOIN_HIP_TRY(w->seg.upload(w->host_seg, stream));   // (bwd_build synchronises)
+  return ESCOIN_OK;
+}
+
+template <bool RELU>
+static void launch_dww(int px, dim3 grid, size_t lds, hipStream_t stream, const DwwArgs &a) {
+  if (px == 4) hipLaunchKernelGGL((escoin_depthwise_wgrad_kernel<RELU, 4>), grid, dim3(kDwThreads), lds, stream, a);
+  else if (px == 2) hipLaunchKernelGGL((escoin_depthwise_wgrad_kernel<RELU, 2>), grid, dim3(kDwThreads), lds, stream, a);
+  else hipLaunchKernelGGL((escoin_depthwise_wgrad_kernel<RELU, 1>), grid, dim3(kDwThreads), lds, stream, a);
+}
+
+static int launch_depthwise_wgrad(const escoin_plan *p, DwWgrad *w, long nnz, const float *bottom, const float *top, const float *top_diff,
+                                  float *slab_w, float *slab_b, int n_images, int *slices, hipStream_t stream) {
+  const Geometry &g = p->g;
+  const DwwPlan &wp = w->plan;
+  *slices = w->last_slices = 0;
+  const bool want_w = slab_w != nullptr && nnz > 0, want_b = slab_b != nullptr;
+  if ((!want_w && !want_b) || n_images <= 0) return ESCOIN_OK;     // nothing to produce: no launch
+  if (!w->seg.get<void>() || wp.per <= 0) return fail(ESCOIN_ESTATE, "depthwise weight-gradient kernel: the backward state has no segments for it");
+  DwwArgs a = {};
+  a.bottom = bottom; a.top_diff = top_diff; a.top = top;
+  a.rowptr = p->gen.rowptr.get<int>(); a.taps = p->gen.taps.get<int>(); a.seg = w->seg.get<const int>();
+  a.slab_w = want_w ? slab_w : nullptr; a.slab_b = slab_b;
+  a.d = g.d;
+  a.OH = g.OH; a.OW = g.OW; a.Mg = g.Mg;
+  a.band = wp.band; a.nbands = wp.nbands; a.padl = wp.padl; a.pitch = wp.pitch; a.region = wp.rows * wp.pitch;
+  a.pairs = n_images * wp.nbands;                       // (n_images <= N: within kDwMaxUnits, dw_plan)
+  a.slices = wp.slices(n_images);                       // (<= S: the slab's rows)
+  a.per = wp.per;
+  a.nseg = want_w ? w->nseg : g.d.M;                    // the bias alone: one unit per (output channel, slice), nothing staged
+  a.nnz = (int)nnz;
+  a.vec_src = aligned16(bottom) && g.d.W % 4 == 0;
+  a.vec_g = aligned16(top_diff) && (!g.d.fuse_relu || aligned16(top)) && g.OW % wp.px == 0;
+  const long units = (long)a.nseg * a.slices;           // (within kDwMaxUnits: dww_plan)
+  const dim3 grid((unsigned)((units + kDwWaves - 1) / kDwWaves));
+  const size_t lds = want_w ? wp.lds_bytes : 0;
+  if (g.d.fuse_relu) launch_dww<true>(wp.px, grid, lds, stream, a);
+  else launch_dww<false>(wp.px, grid, lds, stream, a);
+  ESCOIN_HIP_TRY(hipGetLastError());
+  *slices = w->last_slices = a.slices;
+  return ESCOIN_OK;
+}
+
 // (the plan's core -- escoin_capi.hip, sconv_backward.hip -- reaches these through g_dw_hooks: escoin_plan.h)
 namespace {
 __attribute__((used)) const bool g_registered =
-    (g_dw_hooks = DwHooks{launch_depthwise, launch_depthwise_dgrad, {"escoin_depthwise_kernel<false>", "escoin_depthwise_kernel<true>"}}, true);
+    (g_dw_hooks = DwHooks{launch_depthwise, launch_depthwise_dgrad, {"escoin_depthwise_kernel<false>", "escoin_depthwise_kernel<true>"},
+                          dww_build, launch_depthwise_wgrad}, true);
 }  // namespace
 
 }  // namespace escoin

@@ -23,7 +23,7 @@ S2bHooks g_s2b_hooks = {nullptr, nullptr, nullptr, nullptr};
 B2sHooks g_b2s_hooks = {nullptr, nullptr, nullptr, nullptr};
 D2sHooks g_d2s_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 D2sCpuHooks g_d2s_cpu_hooks = {nullptr, nullptr};
-DwHooks g_dw_hooks = {nullptr, nullptr, {nullptr, nullptr}};
+DwHooks g_dw_hooks = {nullptr, nullptr, {nullptr, nullptr}, nullptr, nullptr};
 
 void set_error(const std::string &msg) { g_last_error = msg; }
 
@@ -88,7 +88,7 @@ DeviceBytes device_bytes(const escoin_plan *p) {
   if (const UpdState *u = p->upd.get())
     b.upd = u->src.bytes() + u->off.bytes() + u->buf.bytes() + u->wpos.bytes() + u->stage.bytes() + u->e_ptr.bytes() + u->e_off.bytes() + u->e_buf.bytes();
   if (const BwdState *s = p->bwd.get())
-    b.bwd = s->gather.bytes() + s->stg.bytes() + s->wgm.bytes() + s->pw.bytes() + s->dgm.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() +
+    b.bwd = s->gather.bytes() + s->stg.bytes() + s->wgm.bytes() + s->pw.bytes() + s->dww.bytes() + s->dgm.bytes() + s->wpos.bytes() + s->slab.bytes() + s->g.bytes() +
             (s->transposed.plan ? device_bytes(s->transposed.plan.get()).fwd : 0);
   if (const S2dState *sd = p->s2d_state.get()) {
     // the X' / dX' scratch and the inner plan's own owners (its update state is never built: the plan's list reaches its copies)
@@ -139,8 +139,11 @@ long bwd_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "wgrad_lds_bytes")) {
     if (s && s->wgrad == ESCOIN_WGRAD_MFMA) return (long)s->wgm.lds_bytes;
     if (s && s->wgrad == ESCOIN_WGRAD_POINTWISE) return (long)s->pw.lds_bytes;
+    if (s && s->wgrad == ESCOIN_WGRAD_DEPTHWISE) return (long)s->dww.plan.lds_bytes;
     return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg.lds_bytes : 0;
   }
+  if (!strcmp(key, "wgrad_depthwise_slices")) return s && s->last_wgrad == ESCOIN_WGRAD_DEPTHWISE ? s->dww.last_slices : 0;
+  if (!strcmp(key, "wgrad_depthwise_px")) return s && s->wgrad == ESCOIN_WGRAD_DEPTHWISE ? s->dww.plan.px : 0;
   if (!strcmp(key, "dgrad_lds_bytes"))
     return s && s->data == kBwdMfma ? (long)s->dgm.lds_bytes : s && s->data == kBwdDepthwise ? (long)s->dw.dlds_bytes : 0;
   if (!strcmp(key, "bwd_align_us")) return s ? (long)(s->align_ms * 1e3) : 0;
@@ -738,7 +741,8 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       return ESCOIN_OK;
     }
     if (p->aligned && strcmp(key, "conv_mode") != 0 && strcmp(key, "cpu_channel_block") != 0 && strcmp(key, "cpu_images_per_job") != 0 &&
-        strcmp(key, "wgrad_kernel") != 0 && strcmp(key, "wgrad_pointwise") != 0)
+        strcmp(key, "wgrad_kernel") != 0 && strcmp(key, "wgrad_pointwise") != 0 && strcmp(key, "wgrad_depthwise") != 0 &&
+        strcmp(key, "wgrad_depthwise_slices") != 0)
       return fail(ESCOIN_ESTATE, "this option must be set before weight_align/set_csr");
     if (!strcmp(key, "tiling_batch")) {
       if (value < 0) return fail(ESCOIN_EINVAL, "tiling_batch must be >= 0");
@@ -790,6 +794,17 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       // (options "b2s" and "deconv": handed on as "wgrad_kernel" is)
       if (p->b2s_state) return escoin_plan_set_option(p->b2s_state->inner.plan.get(), key, value);
       if (p->d2s_state) return escoin_plan_set_option(p->d2s_state->inner.plan.get(), key, value);
+      return ESCOIN_OK;
+    }
+    // ("b2s" and "deconv": not handed on -- their inner plans are not depthwise)
+    if (!strcmp(key, "wgrad_depthwise")) {
+      if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "wgrad_depthwise must be 0 or 1");
+      p->wgrad_depthwise = value;
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "wgrad_depthwise_slices")) {
+      if (value < 0) return fail(ESCOIN_EINVAL, "wgrad_depthwise_slices must be >= 0");
+      p->wgrad_dw_slices = value;
       return ESCOIN_OK;
     }
     if (!strcmp(key, "wgrad_pointwise_tile_entries")) {

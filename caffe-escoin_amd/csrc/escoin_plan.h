@@ -141,6 +141,17 @@ struct PwWgrad {
   size_t bytes() const { return tile.bytes() + ent.bytes() + pk.bytes(); }
 };
 
+// The depthwise weight-gradient kernel (ESCOIN_WGRAD_DEPTHWISE; depthwise.hip; the plan: align_rules.h dww_plan on the plan's
+// segment count; the segments: csr_tables.h dww_segments)
+struct DwWgrad {
+  DwwPlan plan;
+  int nseg = 0;        // row segments: the units of one slice
+  int last_slices = 0; // stat "wgrad_depthwise_slices"
+  std::vector<int> host_seg;   // the upload's source: alive until the builder's caller has synchronised
+  DeviceBuffer seg;    // [nseg][kDwwSegWords]
+  size_t bytes() const { return seg.bytes(); }
+};
+
 // The fp32-MFMA data-gradient kernel (kBwdMfma; dgrad_mfma.hip; the tables: csr_tables.h dgrad_mfma_tables)
 struct DgmState {
   int phases = 0, ctiles = 0, cols_total = 0;
@@ -175,6 +186,7 @@ struct BwdState {
   StagedWgrad stg;
   WgmState wgm;
   PwWgrad pw;
+  DwWgrad dww;
   double align_ms = 0.0;
 };
 
@@ -368,6 +380,8 @@ struct escoin_plan {
   int wgrad_channel_block = 0;            // option "wgrad_channel_block" (0: from the geometry and the LDS budget)
   int wgrad_pointwise = 0;                // option "wgrad_pointwise": AUTO runs the pointwise kernel where it serves the plan
   int wgrad_pw_tile_entries = 0;          // option "wgrad_pointwise_tile_entries" (test option; 0: the rule)
+  int wgrad_depthwise = 0;                // option "wgrad_depthwise": AUTO runs the depthwise weight-gradient kernel where it serves the plan
+  int wgrad_dw_slices = 0;                // option "wgrad_depthwise_slices" (test option; 0: the rule)
   std::unique_ptr<escoin::BwdState> bwd;
 
   // In-place weight updates (update_values.hip): the state the first escoin_update_values builds; reset with the device
@@ -538,12 +552,18 @@ int launch_wgrad_pointwise(const escoin_plan *p, const PwWgrad &w, long nnz, con
 
 // depthwise.hip (option "depthwise"), registered like S2dHooks below (a program that links the core's objects alone runs the
 // option's layers as without it): the forward and the data gradient of n_images images on the plan's generic arrays, and
-// the forward kernel's name without / with the ReLU
+// the forward kernel's name without / with the ReLU; option "wgrad_depthwise": wgrad_build plans on the plan's segments with
+// the options bwd_choice read and uploads them, wgrad is stage 1 of the weight and / or bias gradient (slab_w null: the bias
+// alone, slab_b likewise) of n_images images into slab_w [slices][nnz] and slab_b [slices][M], and returns the slices in
+// *slices (0: nothing launched)
 struct DwHooks {
   int (*forward)(const escoin_plan *p, const DwPlan &dp, const float *bottom, const float *bias, float *top, int n_images, hipStream_t stream);
   int (*dgrad)(const escoin_plan *p, const DwPlan &dp, const float *top, const float *top_diff, float *bottom_diff, int n_images,
                hipStream_t stream);
   const char *kernel_name[2];
+  int (*wgrad_build)(const escoin_plan *p, const BwdOptions &o, DwWgrad *w, hipStream_t stream);
+  int (*wgrad)(const escoin_plan *p, DwWgrad *w, long nnz, const float *bottom, const float *top, const float *top_diff, float *slab_w,
+               float *slab_b, int n_images, int *slices, hipStream_t stream);
 };
 extern DwHooks g_dw_hooks;   // escoin_capi.hip
 

@@ -30,7 +30,9 @@
 //                                        total added into weight_diff / bias_diff.  Every position has one owner.
 //     (option "wgrad_kernel": stage 1 by the LDS-staged kernel below, or by the fp32-MFMA kernel of wgrad_mfma.hip -- same
 //     chunks, same slab; the MFMA kernel's bias gradient is the entry kernel's, launched for the bias alone.  option
-//     "wgrad_pointwise": stage 1 of pointwise layers by the kernel of wgrad_pointwise.hip where AUTO would decide)
+//     "wgrad_pointwise": stage 1 of pointwise layers by the kernel of wgrad_pointwise.hip where AUTO would decide; option
+//     "wgrad_depthwise": likewise for layers with one input channel per group, by escoin_depthwise_wgrad_kernel of
+//     depthwise.hip, whose slab rows are slices of (image, band) pairs instead of chunks)
 //
 // Which of these kernels a plan gets, and what it refuses, is decided by the host-only rule bwd_choice (align_rules.h);
 // bwd_build here calls it once and does the device work.  The backward state (BwdState, escoin_plan.h: one sub-struct per
@@ -39,7 +41,7 @@
 // uploads them -- and dropped with the device side (free_device: weight_align / set_csr / import_aligned; destroy); later
 // calls allocate nothing and synchronise nothing, so they can be captured into a graph.  backward_gpu is the driver:
 // checks, state, then data_gradient (a switch over BwdState::data, one function per path) and weight_gradient
-// (wgrad_entry / wgrad_staged / wgrad_mfma / wgrad_pointwise over the shared stage-1 and stage-2 launch helpers).
+// (wgrad_entry / wgrad_staged / wgrad_mfma / wgrad_pointwise / wgrad_depthwise over the shared stage-1 and stage-2 launch helpers).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -570,7 +572,8 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   const Geometry &g = p->g;
   const long nnz = plan_nnz(p);
   const BwdOptions o{p->bwd_kernel, p->wgrad_kernel, p->wgrad_channel_block, p->inner_plan() != nullptr, p->wgrad_pointwise,
-                     p->wgrad_pw_tile_entries, g_dw_hooks.dgrad ? p->depthwise : 0, p->dw_band_rows};
+                     p->wgrad_pw_tile_entries, g_dw_hooks.dgrad ? p->depthwise : 0, p->dw_band_rows,
+                     g_dw_hooks.wgrad ? p->wgrad_depthwise : 0, p->wgrad_dw_slices};
   const BwdChoice c = bwd_choice(g, p->is_f64, nnz, o, tiled_device_cus());
   if (c.rc != ESCOIN_OK) return fail(c.rc, c.error);
   p->bwd.reset(new BwdState());
@@ -584,6 +587,7 @@ static int bwd_build(escoin_plan *p, hipStream_t stream) {
   if (c.wgrad == ESCOIN_WGRAD_MFMA) rc = wgm_build(p, c.wgm, &s->wgm, stream);
   else if (c.wgrad == ESCOIN_WGRAD_STAGED) rc = stg_build(p, c.stg, &s->stg, stream);
   else if (c.wgrad == ESCOIN_WGRAD_POINTWISE) rc = pw_build(p, o, &s->pw, stream);
+  else if (c.wgrad == ESCOIN_WGRAD_DEPTHWISE) rc = g_dw_hooks.wgrad_build(p, o, &s->dww, stream);
   if (rc != ESCOIN_OK) return rc;
   ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
   s->align_ms = ms_since(t0);
@@ -664,7 +668,7 @@ static int data_gradient(escoin_plan *p, const T *top, const T *top_diff, T *bot
   return dgrad_gather<T>(p, top, top_diff, bottom_diff, n_images, stream);
 }
 
-// ---- weight / bias gradient: stage 1 by one of four kernels, stage 2 by one of two sums -----------------------------
+// ---- weight / bias gradient: stage 1 by one of five kernels, stage 2 by one of two sums -----------------------------
 // One call's blobs, outputs (either may be null), slab and chunks.
 template <typename T>
 struct WgradCall {
@@ -780,6 +784,16 @@ static int wgrad_pointwise(const escoin_plan *p, const WgradCall<float> &c) {
   return rc != ESCOIN_OK ? rc : launch_tree_sum(p, c, c.weight_diff, c.bias_diff);
 }
 
+// option "wgrad_depthwise": weights and bias by the depthwise kernel (depthwise.hip) -- the slab's rows are its slices --,
+// then the tree sum over them
+static int wgrad_depthwise(const escoin_plan *p, const WgradCall<float> &c) {
+  BwdState *s = p->bwd.get();
+  WgradCall<float> cs = c;
+  const int rc = g_dw_hooks.wgrad(p, &s->dww, s->nnz, c.bottom, c.top, c.top_diff, c.weight_diff ? c.slab_w : nullptr,
+                                  c.bias_diff ? c.slab_b : nullptr, c.n_images, &cs.chunks, c.stream);
+  return rc != ESCOIN_OK || cs.chunks == 0 ? rc : launch_tree_sum(p, cs, c.weight_diff, c.bias_diff);
+}
+
 template <typename T>
 static int weight_gradient(escoin_plan *p, const T *bottom, const T *top, const T *top_diff, T *weight_diff, T *bias_diff,
                            int n_images, hipStream_t stream, bool compact) {
@@ -794,6 +808,7 @@ static int weight_gradient(escoin_plan *p, const T *bottom, const T *top, const 
     if (s->wgrad == ESCOIN_WGRAD_STAGED) return wgrad_staged(p, c);
     if (s->wgrad == ESCOIN_WGRAD_MFMA) return wgrad_mfma(p, c);
     if (s->wgrad == ESCOIN_WGRAD_POINTWISE) return wgrad_pointwise(p, c);
+    if (s->wgrad == ESCOIN_WGRAD_DEPTHWISE) return wgrad_depthwise(p, c);
   }
   return wgrad_entry<T>(p, c);
 }

@@ -773,7 +773,7 @@ ESCOIN_API int escoin_cpu_sparse_dense2csr_f64(int M, int N, const double *A, do
  * LDS budget holds, n = at most n; it caps the pointwise kernel's channel block too.  Results do not depend on it.
  * Option "wgrad_pointwise_tile_entries" (test option, before the align; >= 0): 0 = a pointwise tile holds up to 4096
  * entries, n = at most min(n, 4096).  Results do not depend on it.
- * Stats: "wgrad_kernel" (ESCOIN_WGRAD_ENTRY / _STAGED / _MFMA / _POINTWISE: what the last weight / bias gradient ran;
+ * Stats: "wgrad_kernel" (ESCOIN_WGRAD_ENTRY / _STAGED / _MFMA / _POINTWISE / _DEPTHWISE: what the last weight / bias gradient ran;
  * ESCOIN_ESTATE before the first one), "wgrad_lds_bytes" (LDS of a staged, an MFMA or a pointwise workgroup; 0 on the
  * entry kernel).
  *
@@ -802,7 +802,32 @@ ESCOIN_API int escoin_cpu_sparse_dense2csr_f64(int M, int N, const double *A, do
  * rows (bottom rows for the data gradient) per band.  Results do not depend on it.
  * Stats: "depthwise" (1 where the aligned plan's forward runs the kernel), "depthwise_band_rows" (the forward's band),
  * "depthwise_lds_bytes" (LDS of a forward workgroup of four waves), "bwd_data_kernel" == ESCOIN_BWD_DEPTHWISE, and
- * "dgrad_lds_bytes".  Measurements: profiles/depthwise_mi355x.md. */
+ * "dgrad_lds_bytes".  Measurements: profiles/depthwise_mi355x.md.
+ * Option "wgrad_depthwise" (0 or 1, default 0; settable whenever "wgrad_kernel" is, and read when the next backward state
+ * is built; independent of "depthwise"): with "wgrad_kernel" at ESCOIN_WGRAD_AUTO, a plan the depthwise rule serves (the
+ * plans above: float, one input channel per group; nnz and the row segments below 2^31) runs stage 1 of the weight / bias
+ * gradient by escoin_depthwise_wgrad_kernel, then escoin_sconv_wgrad_tree_sum_kernel.  A plan the rule does not serve
+ * behaves exactly as without the option (same kernel, same bits); a forced "wgrad_kernel" wins over it, and so does
+ * "wgrad_pointwise" on a plan that option serves; AUTO never picks the kernel by itself; it is not a value of
+ * "wgrad_kernel" (5 is refused there).  "s2d" / "s2b" compute the weight gradient on the outer plan, which the option
+ * serves as any plan; "b2s" and "deconv" do not hand it to their inner plans (they are not depthwise); CPU mode ignores
+ * it.  A wave takes one (row segment, slice): up to 16 consecutive CSR entries of one output channel's row, and a
+ * contiguous run of the call's (image, band of output rows) pairs, the bands being the forward's.  Per pair it stages the
+ * band's input window in its LDS region as the forward does (padding as +0), loads its lanes' top_diff pixels (0 where top
+ * <= 0 on a fuse_relu plan) into registers and adds acc[k] = fmaf(g, x, acc[k]) per entry k and owned pixel, pixels in
+ * ascending order; a padded tap is multiplied as a zero, a lane or pixel past the band's end is left out by a select.  The
+ * accumulators live across the slice; the unit ends with one fixed 64-lane butterfly per entry and one store per (slice,
+ * entry).  The bias is one more accumulator, summed by each row's first segment (an empty row keeps one); a bias-only call
+ * stages nothing.  Sum order: a function of the geometry, n_images, the band and the slice length -- deterministic from run
+ * to run, not the other kernels' bits.  Only CSR positions are written, explicit zeros receive their gradient, images at or
+ * past n_images are not read, a non-finite bottom element reaches only the entries whose tap reads it, no atomics,
+ * nothing allocated or synchronised after the first backward.  Measurements: profiles/depthwise_wgrad_mi355x.md.
+ * Option "wgrad_depthwise_slices" (test option, settable as "wgrad_depthwise" is; >= 0): 0 = the rule chooses the slices of
+ * the full batch (the fewest that give 16 units per CU over the M rows), n = n, both clamped to the batch's (image, band)
+ * pairs.  "depthwise_band_rows" caps this kernel's band too.
+ * Stats: "wgrad_depthwise_slices" (the slices of the last weight / bias gradient the kernel ran; 0: it has not run),
+ * "wgrad_depthwise_px" (4, 2 or 1: the output pixels a lane owns per run, the kernel's instantiation; 0: another kernel). */
+#define ESCOIN_WGRAD_DEPTHWISE 5 /* escoin_depthwise_wgrad_kernel (option "wgrad_depthwise"): a value of stat "wgrad_kernel" only */
 #define ESCOIN_BWD_DEPTHWISE 6 /* stat "bwd_data_kernel" only: escoin_depthwise_dgrad_kernel (option "depthwise") */
 #define ESCOIN_WGRAD_AUTO 0
 #define ESCOIN_WGRAD_ENTRY 1   /* escoin_sconv_wgrad_partial_kernel: one workgroup per (chunk, output channel) */

@@ -14,7 +14,16 @@ roofline: synth.algorithmic_bytes over HBM_PEAK over the time.  The outputs of "
 at the timed size.  Prints one JSON line (progress on stderr); --markdown FILE also writes the tables of
 profiles/depthwise_mi355x.md.
 
-    python tools/depthwise_bench.py [--batch 64] [--only a,b] [--regions 7] [--reps 5] [--markdown FILE]
+--sets wgrad times the weight + bias gradient instead (plan option "wgrad_depthwise"; the tables of
+profiles/depthwise_wgrad_mi355x.md), by the same method, three routes:
+
+  on       option "wgrad_depthwise" = 1: escoin_depthwise_wgrad_kernel, then the tree sum (stat "wgrad_kernel" asserted to read 5)
+  off      the same plan on the same build with the option off: the kernel AUTO picks (named per layer) -- the baseline
+  torch    aten.convolution_backward's weight and bias gradient of conv2d(groups=C)
+
+"on" and "off" sum in different orders: their largest difference, relative to the largest gradient, is reported.
+
+    python tools/depthwise_bench.py [--sets forward,wgrad] [--batch 64] [--only a,b] [--regions 7] [--reps 5] [--markdown FILE]
 """
 import argparse
 import json
@@ -100,6 +109,61 @@ def bench_layer(pkg, synth, s, regions, reps):
     return row
 
 
+WGRAD_NAMES = {1: "entry", 2: "staged", 3: "mfma", 4: "pointwise", 5: "depthwise"}
+
+
+def bench_wgrad(pkg, synth, s, regions, reps):
+    import torch
+    dev = torch.device("cuda:0")
+    w = synth.pruned_weights(s, 11)
+    x = torch.from_numpy(synth.activations(s, 12)).to(dev)
+    oh, ow = synth.out_hw(s)
+    td = torch.from_numpy(synth.uniform(21, s.N * s.M * oh * ow).reshape(s.N, s.M, oh, ow)).to(dev)
+    wd = torch.from_numpy(w).to(dev)
+    desc = pkg.ConvDesc.from_shape(s)
+    plans = dict(on=pkg.Plan(desc, wgrad_depthwise=1), off=pkg.Plan(desc))
+    for p in plans.values():
+        p.weight_align(w)
+    # (the gradients accumulate: the blobs are zeroed once, and compared after one call each on fresh ones)
+    gw = {k: torch.zeros_like(wd) for k in plans}
+    gb = {k: torch.zeros(s.M, device=dev) for k in plans}
+    fns = {k: (lambda p=p, k=k: p.backward(td, bottom=x, bottom_diff=None, weight_diff=gw[k], bias_diff=gb[k])) for k, p in plans.items()}
+    fns["torch"] = lambda: torch.ops.aten.convolution_backward(td, x, wd, [s.M], (s.stride_h, s.stride_w), (s.pad_h, s.pad_w), (1, 1), False,
+                                                               (0, 0), s.group, (False, True, True))
+    t = alternating(fns, regions, reps)
+    torch.cuda.synchronize()
+    on, off = plans["on"], plans["off"]
+    assert on.stat("wgrad_kernel") == pkg.WGRAD_DEPTHWISE == 5 and off.stat("wgrad_kernel") != 5
+    one = {k: p.backward(td, bottom=x, bottom_diff=None, weight_diff=True, bias_diff=True)[1:] for k, p in plans.items()}
+    diff = max(float((a - b).abs().max() / b.abs().max()) for a, b in zip(one["on"], one["off"]))
+    floor_ms = synth.algorithmic_bytes(s) / HBM_PEAK * 1e3
+    row = dict(layer=s.name, count=s.count, N=s.N, C=s.C, HW=s.H, stride=s.stride_h, nnz=on.nnz(), alg_mbytes=round(synth.algorithmic_bytes(s) / 1e6, 1),
+               slices=on.stat("wgrad_depthwise_slices"), lds_bytes=on.stat("wgrad_lds_bytes"), off_kernel=WGRAD_NAMES[off.stat("wgrad_kernel")],
+               off_chunks=off.stat("bwd_chunks"), wgrad={k: summary(v) for k, v in t.items()},
+               roofline=round(floor_ms / float(np.median(t["on"])), 3), max_rel_diff=diff)
+    for p in plans.values():
+        p.close()
+    return row
+
+
+def markdown_wgrad(results, dev_name, regions, reps):
+    out = ["Box: %s.  Median of %d regions of %d back-to-back calls per route, routes alternating (min .. max in brackets), ms."
+           % (dev_name, regions, reps), ""]
+    for sparsity, rows in results:
+        out += ["### Weight + bias gradient, %d %% of the taps pruned" % round(sparsity * 100), "",
+                "| layer | x | alg. MB | slices | on | off | off: AUTO's kernel (chunks) | torch | off / on | torch / on | on: of the HBM roofline | max rel. on - off |",
+                "|---|---|---|---|---|---|---|---|---|---|---|---|"]
+        for r in rows:
+            c = r["wgrad"]
+            cell = lambda k: "%.3f (%.3f .. %.3f)" % (c[k]["median_ms"], c[k]["min_ms"], c[k]["max_ms"])  # noqa: E731
+            m = lambda k: c[k]["median_ms"] / c["on"]["median_ms"]  # noqa: E731
+            out.append("| %s | %d | %.1f | %d | %s | %s | %s (%d) | %s | %.2fx | %.2fx | %.0f %% | %.1e |" % (
+                r["layer"], r["count"], r["alg_mbytes"], r["slices"], cell("on"), cell("off"), r["off_kernel"], r["off_chunks"], cell("torch"),
+                m("off"), m("torch"), 100 * r["roofline"], r["max_rel_diff"]))
+        out.append("")
+    return "\n".join(out)
+
+
 def markdown(results, dev_name, regions, reps):
     out = ["Box: %s.  Median of %d regions of %d back-to-back calls per route, routes alternating (min .. max in brackets), ms."
            % (dev_name, regions, reps), ""]
@@ -123,6 +187,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--only", default="")
+    ap.add_argument("--sets", default="forward", help="forward (and data gradient), wgrad, or both: forward,wgrad")
     ap.add_argument("--regions", type=int, default=7)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--markdown", default="")
@@ -134,8 +199,17 @@ def main():
     synth = pkg.synth
     keep = [k for k in args.only.split(",") if k]
     regions = max(args.regions, 5)
-    results = []
-    for sparsity in (0.0, 0.5):
+    sets = [k for k in args.sets.split(",") if k]
+    results, wresults = [], []
+    for sparsity in (0.0, 0.5) if "wgrad" in sets else ():
+        rows = []
+        for s in synth.mobilenet_dw(args.batch, sparsity):
+            if keep and not any(k in s.name for k in keep):
+                continue
+            print("[depthwise_bench] wgrad %s @ %.1f" % (s.name, sparsity), file=sys.stderr, flush=True)
+            rows.append(bench_wgrad(pkg, synth, s, regions, args.reps))
+        wresults.append((sparsity, rows))
+    for sparsity in (0.0, 0.5) if "forward" in sets else ():
         rows = []
         for s in synth.mobilenet_dw(args.batch, sparsity):
             if keep and not any(k in s.name for k in keep):
@@ -146,9 +220,11 @@ def main():
     dev_name = torch.cuda.get_device_name(0)
     if args.markdown:
         with open(args.markdown, "w") as f:
-            f.write(markdown(results, dev_name, regions, args.reps))
+            f.write("\n".join(([markdown(results, dev_name, regions, args.reps)] if results else []) +
+                              ([markdown_wgrad(wresults, dev_name, regions, args.reps)] if wresults else [])))
     print(json.dumps(dict(tool="depthwise_bench", device=dev_name, batch=args.batch, regions=regions, reps=args.reps, hbm_peak=HBM_PEAK,
-                          results=[dict(sparsity=sp, layers=rows) for sp, rows in results])))
+                          results=[dict(sparsity=sp, layers=rows) for sp, rows in results],
+                          wgrad=[dict(sparsity=sp, layers=rows) for sp, rows in wresults])))
 
 
 if __name__ == "__main__":
