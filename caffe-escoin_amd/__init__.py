@@ -70,6 +70,10 @@ API_SYMBOLS = [
     # Batch-to-space (option "b2s")
     "escoin_plan_b2s_pack",
     "escoin_plan_b2s_unpack",
+    # Width-to-batch (option "w2b")
+    "escoin_plan_w2b_pack",
+    "escoin_plan_w2b_unpack",
+    "escoin_plan_w2b_unpack_sum",
     # Deconvolution (option "deconv")
     "escoin_deconv_out_shape",
     "escoin_plan_d2s_pack",
@@ -275,6 +279,12 @@ def lib():
     L.escoin_plan_b2s_pack.argtypes = [vp, vp, vp, vp, ip, ip, vp]
     L.escoin_plan_b2s_unpack.restype = ip
     L.escoin_plan_b2s_unpack.argtypes = [vp, vp, vp, ip, ip, ip, vp]
+    L.escoin_plan_w2b_pack.restype = ip
+    L.escoin_plan_w2b_pack.argtypes = [vp, vp, vp, vp, ip, ip, vp]
+    L.escoin_plan_w2b_unpack.restype = ip
+    L.escoin_plan_w2b_unpack.argtypes = [vp, vp, vp, ip, ip, vp]
+    L.escoin_plan_w2b_unpack_sum.restype = ip
+    L.escoin_plan_w2b_unpack_sum.argtypes = [vp, vp, vp, ip, vp]
     L.escoin_deconv_out_shape.restype = ip
     L.escoin_deconv_out_shape.argtypes = [vp, vp, vp]
     L.escoin_plan_d2s_pack.restype = ip
@@ -885,6 +895,45 @@ class Plan(object):
         stream = C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
         check(lib().escoin_plan_b2s_unpack(self._h, C.c_void_p(src.data_ptr()), C.c_void_p(dst.data_ptr()), int(bool(top_side)),
                                            int(bool(relu)), n, stream), "escoin_plan_b2s_unpack")
+
+    def _w2b_call(self, name, src, dst, n_images, src_rows, dst_rows, *mid, mask=None):
+        """One rearrangement of a "w2b" plan alone on the caller's tensors and torch's current stream; src_rows / dst_rows:
+        the floats per outer image each side must hold."""
+        import torch
+        for t in (src, dst) + (() if mask is None else (mask,)):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        n = int(n_images)
+        assert src.numel() >= n * src_rows and dst.numel() >= n * dst_rows, "src / dst too small"
+        stream = C.c_void_p(torch.cuda.current_stream(src.device).cuda_stream)
+        args = (C.c_void_p(src.data_ptr()),) + (() if name != "pack" else (None if mask is None else C.c_void_p(mask.data_ptr()),))
+        check(getattr(lib(), "escoin_plan_w2b_" + name)(self._h, *args, C.c_void_p(dst.data_ptr()), *mid, n, stream),
+              "escoin_plan_w2b_" + name)
+
+    def _w2b_floats(self, top_side):
+        """(floats per image of the spread blob, of its S strips) on the bottom or the top side."""
+        d, S, SW = self.desc, self.stat("w2b_strips"), self.stat("w2b_strip")
+        oh, ow = self.out_hw
+        return (d.M * oh * ow, S * d.M * oh * SW) if top_side else (d.C * d.H * d.W, S * d.C * d.H * (SW + d.KW - 1))
+
+    def w2b_pack(self, src, dst, mask=None, top_side=False, n_images=None):
+        """The strips of a "w2b" plan alone: src (the bottom: N x C x H x W, or on the top side top_diff: N x M x OH x OW,
+        gated by mask > 0 where mask is given) into dst, the n_images * S strip images (H x Wi, or OH x SW on the top side)."""
+        n = int(src.shape[0]) if n_images is None else n_images
+        if mask is not None:
+            assert mask.numel() >= src.numel()
+        self._w2b_call("pack", src, dst, n, *self._w2b_floats(top_side), int(bool(top_side)), mask=mask)
+
+    def w2b_unpack(self, src, dst, relu=False, n_images=None):
+        """The reverse on the top side: src, n_images * S strip images of OH x SW, into dst (N x M x OH x OW), through ReLU
+        if asked."""
+        spread, strips = self._w2b_floats(True)
+        self._w2b_call("unpack", src, dst, int(dst.shape[0]) if n_images is None else n_images, strips, spread, int(bool(relu)))
+
+    def w2b_unpack_sum(self, src, dst, n_images=None):
+        """The data gradient's gather: src, n_images * S strip images of H x Wi, into dst (N x C x H x W), every element the
+        sum over the one or two strips that hold its column."""
+        spread, strips = self._w2b_floats(False)
+        self._w2b_call("unpack_sum", src, dst, int(dst.shape[0]) if n_images is None else n_images, strips, spread)
 
     def forward(self, bottom, bias=None, top=None):
         """Forward_gpu on torch CUDA tensors (float32, or float64 for a double plan), on torch's current stream."""

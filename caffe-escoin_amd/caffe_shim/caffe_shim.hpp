@@ -111,6 +111,9 @@ class Caffe {
   // the same for inner-product layers (one pixel, a 1x1 kernel) via batch-to-space (include/escoin.h option "b2s")
   static bool b2s() { return Get().b2s_; }
   static void set_b2s(bool on) { Get().b2s_ = on; }
+  // the same for stride-1, dilation-1 layers wider than 256 columns via width-to-batch (include/escoin.h option "w2b")
+  static bool w2b() { return Get().w2b_; }
+  static void set_w2b(bool on) { Get().w2b_ = on; }
   // whether the plans layers create from now on compute the weight gradient of pointwise layers (1x1, pad 0; inner-product
   // layers through "b2s") by the pointwise kernel (include/escoin.h option "wgrad_pointwise"); a layer the option does not
   // serve, a forced wgrad_kernel, and CPU mode, run as without it
@@ -128,7 +131,7 @@ class Caffe {
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), wgrad_pointwise_(false), depthwise_(false), wgrad_depthwise_(false) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), w2b_(false), wgrad_pointwise_(false), depthwise_(false), wgrad_depthwise_(false) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
@@ -137,6 +140,7 @@ class Caffe {
   bool s2d_;
   bool s2b_;
   bool b2s_;
+  bool w2b_;
   bool wgrad_pointwise_;
   bool depthwise_;
   bool wgrad_depthwise_;
@@ -466,6 +470,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2d", Caffe::s2d() && !deconv_ ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "s2b", Caffe::s2b() && !deconv_ ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "b2s", Caffe::b2s() && !deconv_ ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "w2b", Caffe::w2b() && !deconv_ ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_pointwise", Caffe::wgrad_pointwise() ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "depthwise", Caffe::depthwise() ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_depthwise", Caffe::wgrad_depthwise() ? 1 : 0));

@@ -996,6 +996,42 @@ bool b2s_plan(const Geometry &g, bool is_f64, int block, int /*n_cu*/, B2sPlan *
   return true;
 }
 
+bool w2b_plan(const Geometry &g, bool is_f64, int strip, W2bPlan *wp) {
+  const escoin_conv_desc &d = g.d;
+  if (is_f64) return false;
+  if (d.stride_h != 1 || d.stride_w != 1 || d.dil_h != 1 || d.dil_w != 1) return false;
+  const int halo = d.KW - 1;
+  if (!w2b_strip_ok(strip, d.KW)) return false;
+  if (strip == 0 && d.W <= kW2bMaxWidth && g.OW <= kW2bMaxWidth) return false;      // (a row the tiled kernels take as it is)
+  W2bPlan p;
+  if (strip > 0) {
+    p.SW = strip;
+    p.S = (g.OW + p.SW - 1) / p.SW;
+  } else {
+    const int cap = (kW2bMaxWidth - halo) / 4 * 4;
+    if (cap < 4) return false;
+    p.S = (g.OW + cap - 1) / cap;
+    p.SW = ((g.OW + p.S - 1) / p.S + 3) / 4 * 4;
+  }
+  p.Wi = p.SW + halo;
+  if (p.SW < halo || p.Wi > kW2bMaxWidth) return false;
+  if ((long)d.N * p.S > kS2bMaxInnerImages) return false;
+  escoin_conv_desc &in = p.inner;
+  in = d;
+  in.N = d.N * p.S;
+  in.W = p.Wi;
+  in.pad_w = 0;
+  in.fuse_relu = 0;                  // (the unpack kernel applies the outer plan's ReLU)
+  const double two31 = 2147483648.0;
+  const double x_floats = (double)in.N * d.C * d.H * (double)p.Wi, t_floats = (double)in.N * d.M * g.OH * (double)p.SW;
+  if (x_floats >= two31 || t_floats >= two31) return false;
+  if ((double)d.N * d.C * d.H * (double)d.W >= two31 || (double)d.N * d.M * g.OH * (double)g.OW >= two31) return false;
+  p.x_floats = (long)x_floats;
+  p.t_floats = (long)t_floats;
+  *wp = p;
+  return true;
+}
+
 bool d2s_plan(const escoin_conv_desc &d, bool is_f64, D2sPlan *dp) {
   D2sPlan p;
   auto refuse = [&](const char *why) { p.error = why; *dp = p; return false; };

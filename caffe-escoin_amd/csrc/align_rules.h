@@ -544,6 +544,33 @@ constexpr int kB2sMinBlock = 4, kB2sMaxBlock = 256;
 // does not.  n_cu is the device's compute units, which the shipped rule does not weigh.
 bool b2s_plan(const Geometry &g, bool is_f64, int block, int n_cu, B2sPlan *bp);
 
+// ---- wide layers on the tiled kernels via width-to-batch (w2b.hip, plan option "w2b") --------------------------------
+// A stride-1, dilation-1 convolution of a wide image is S independent convolutions of column strips with a halo
+// (include/escoin.h "Width-to-batch"): strip s of image n is image n' = n * S + s of the inner plan, an H x Wi image with
+// Wi = SW + KW - 1 whose column x is column s * SW - pad_w + x of the bottom (+0 outside it); pad_h as the layer's, pad_w 0,
+// no ReLU; the CSR is the outer one.  The inner top is OH x SW, and top[n][m][oh][ow] = T'[n * S + ow / SW][m][oh][ow % SW].
+struct W2bPlan {
+  int S = 0, SW = 0, Wi = 0;      // strips per image, a strip's output width (a multiple of 4), its input width
+  escoin_conv_desc inner = {};    // the inner plan's descriptor (N' = N * S images of H x Wi)
+  long x_floats = 0;              // N' * C * H * Wi: the strips of the bottom X' (and, in a scratch of its own, dX')
+  long t_floats = 0;              // N' * M * OH * SW: the inner top T' (and the strips of top_diff G')
+};
+constexpr int kW2bMaxWidth = 256;       // the widest row the tiled kernels take (stream_builder.cpp tile_with, aligned_form.cpp)
+// what option "w2b_strip" accepts for a kernel of KW columns: 0 (the rule), or a multiple of 4 with KW - 1 <= SW and
+// SW + KW - 1 <= kW2bMaxWidth
+constexpr bool w2b_strip_ok(int strip, int KW) {
+  return strip == 0 || (strip > 0 && strip % 4 == 0 && KW - 1 <= strip && strip + KW - 1 <= kW2bMaxWidth);
+}
+// Whether option "w2b" serves this plan, and the strips and the inner descriptor where it does: float plans with stride 1
+// and dilation 1 in both axes whose input or output row is wider than kW2bMaxWidth -- or any width where `strip` (test option
+// "w2b_strip", which the caller has checked with w2b_strip_ok) forces SW -- with SW >= KW - 1 (a bottom column lies in at
+// most two strips), N * S at most kS2bMaxInnerImages and bottom, top, X' and T' each below 2^31 elements (the kernels' 32-bit
+// offsets).  strip = 0 is the rule, the fewest strips: with cap = the largest multiple of 4 that leaves SW + KW - 1 <=
+// kW2bMaxWidth, S = ceil(OW / cap) and SW = the smallest multiple of 4 at or above ceil(OW / S), which is at most cap.
+// Narrower strips (Wi <= 128, two rows per slab of the tiled walk) were measured against the fewest on four layers
+// (profiles/w2b_mi355x.md): they won some and lost some, no rule followed, so the simple rule ships.
+bool w2b_plan(const Geometry &g, bool is_f64, int strip, W2bPlan *wp);
+
 // ---- Deconvolution layers on the stride-1 kernels via depth-to-space (d2s.hip, plan option "deconv") ----------------
 // A stride-(sh, sw) deconvolution is a stride-1 convolution of the bottom itself with P = sh * sw times the output
 // channels, one per output phase, followed by a depth-to-space interleave (include/escoin.h "Deconvolution"): inner

@@ -136,6 +136,15 @@ static int dense_wgrad_gpu(escoin_plan *p, const float *bottom, const float *top
     return escoin_dense_wgrad(bs->inner.plan.get(), bs->x.get<const float>(), nullptr, bs->t.get<const float>(), dense_diff, n_inner,
                               accumulate, stream_v);
   }
+  // option "w2b": likewise on the strips -- M x Cg x KH x KW on both plans; the last strip's tail is +0 in G'
+  if (W2bState *ws = p->w2b_state.get()) {
+    ++p->dwg_count;
+    int rc = g_w2b_hooks.pack(p, bottom, nullptr, ws->x.get<float>(), false, n_images, stream);
+    if (rc == ESCOIN_OK) rc = g_w2b_hooks.pack(p, top_diff, d.fuse_relu ? top : nullptr, ws->t.get<float>(), true, n_images, stream);
+    if (rc != ESCOIN_OK) return rc;
+    return escoin_dense_wgrad(ws->inner.plan.get(), ws->x.get<const float>(), nullptr, ws->t.get<const float>(), dense_diff,
+                              n_images * ws->wp.S, accumulate, stream_v);
+  }
   if (!p->dwg || p->dwg->device != p->device) {
     const int rc = dwg_build(p, stream);
     if (rc != ESCOIN_OK) {

@@ -21,6 +21,7 @@ static thread_local std::string g_last_error;
 S2dHooks g_s2d_hooks = {nullptr, nullptr, nullptr};
 S2bHooks g_s2b_hooks = {nullptr, nullptr, nullptr, nullptr};
 B2sHooks g_b2s_hooks = {nullptr, nullptr, nullptr, nullptr};
+W2bHooks g_w2b_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 D2sHooks g_d2s_hooks = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 D2sCpuHooks g_d2s_cpu_hooks = {nullptr, nullptr};
 DwHooks g_dw_hooks = {nullptr, nullptr, {nullptr, nullptr}, nullptr, nullptr};
@@ -109,6 +110,13 @@ DeviceBytes device_bytes(const escoin_plan *p) {
     b.bwd += in.bwd;
     b.dwg += in.dwg;      // (escoin_dense_wgrad runs on the inner plan)
   }
+  if (const W2bState *ws = p->w2b_state.get()) {
+    // the X', T' / G' and dX' scratches and the inner plan's own owners, as for "b2s"
+    const DeviceBytes in = device_bytes(ws->inner.plan.get());
+    b.fwd += ws->x.bytes() + ws->t.bytes() + ws->dx.bytes() + in.fwd;
+    b.bwd += in.bwd;
+    b.dwg += in.dwg;      // (escoin_dense_wgrad runs on the inner plan)
+  }
   if (const D2sState *ds = p->d2s_state.get()) {
     // the T' / G' scratch, the gradients' scratches and maps, and the inner plan's own owners, as for "s2d"
     const DeviceBytes in = device_bytes(ds->inner.plan.get());
@@ -121,6 +129,7 @@ DeviceBytes device_bytes(const escoin_plan *p) {
 long bwd_stat(const escoin_plan *p, const char *key) {
   // option "b2s": the whole backward is the inner plan's, and so are its facts -- but for the bytes, which device_bytes sums
   if (p->b2s_state && strcmp(key, "bwd_device_bytes") != 0) return bwd_stat(p->b2s_state->inner.plan.get(), key);
+  if (p->w2b_state && strcmp(key, "bwd_device_bytes") != 0) return bwd_stat(p->w2b_state->inner.plan.get(), key);   // (option "w2b": likewise)
   if (p->d2s_state && strcmp(key, "bwd_device_bytes") != 0) return bwd_stat(p->d2s_state->inner.plan.get(), key);   // (option "deconv": likewise)
   const BwdState *s = p->bwd.get();
   if (!strcmp(key, "bwd_data_kernel")) {
@@ -164,8 +173,8 @@ long upd_stat(const escoin_plan *p, const char *key) {
 }
 
 long dwg_stat(const escoin_plan *p, const char *key) {
-  // (option "b2s": the state is the inner plan's)
-  const DenseWgradState *w = p->b2s_state ? p->b2s_state->inner.plan->dwg.get() : p->dwg.get();
+  // (options "b2s" and "w2b": the state is the inner plan's)
+  const DenseWgradState *w = p->b2s_state ? p->b2s_state->inner.plan->dwg.get() : p->w2b_state ? p->w2b_state->inner.plan->dwg.get() : p->dwg.get();
   if (!strcmp(key, "dwg_device_bytes")) return (long)device_bytes(p).dwg;
   if (!strcmp(key, "dwg_splits")) return w ? w->splits : 0;
   if (!strcmp(key, "dwg_lds_bytes")) return w ? (long)w->lds_bytes : 0;
@@ -181,6 +190,7 @@ static void free_device(escoin_plan *p) {
   p->s2d_state.reset();
   p->s2b_state.reset();
   p->b2s_state.reset();
+  p->w2b_state.reset();
   p->d2s_state.reset();
   p->dw_on = false;
   p->gen = GenericArrays();
@@ -314,6 +324,39 @@ static int b2s_build(escoin_plan *p, const B2sPlan &bp, hipStream_t stream) {
   return ESCOIN_OK;
 }
 
+// Option "w2b" (include/escoin.h "Width-to-batch"): the inner plan of N * S strip images of H x Wi with the plan's kernel,
+// backward and weight-gradient options, aligned on the plan's own CSR (the entry map is the identity) and deciding its kernel
+// on its own geometry, and the X', T' / G' and dX' scratches.  The plan itself keeps the generic arrays alone, as under "s2d".
+static int w2b_build(escoin_plan *p, const W2bPlan &wp, hipStream_t stream) {
+  if (!g_w2b_hooks.pack || !g_w2b_hooks.unpack || !g_w2b_hooks.unpack_sum)
+    return fail(ESCOIN_EINVAL, "option \"w2b\": this build does not carry the width-to-batch kernels");
+  p->w2b_state.reset(new W2bState());
+  W2bState *ws = p->w2b_state.get();
+  ws->wp = wp;
+  DerivedCsr csr;
+  for (int grp = 0; grp < p->g.d.group; ++grp) {
+    csr.rowptr.insert(csr.rowptr.end(), p->rowptr[grp].begin(), p->rowptr[grp].end());
+    csr.colidx.insert(csr.colidx.end(), p->colidx[grp].begin(), p->colidx[grp].end());
+    csr.nnz_g.push_back((int)p->colidx[grp].size());
+  }
+  csr.src.resize(csr.colidx.size());
+  for (size_t k = 0; k < csr.src.size(); ++k) csr.src[k] = (int)k;
+  // "tiling_batch" counts outer images: an outer image is S inner ones
+  const long tb = (long)p->tiling_batch * wp.S;
+  if (tb > 0x7fffffffL) return fail(ESCOIN_EINVAL, "option \"w2b\": tiling_batch times the strips exceeds 2^31");
+  const int rc = build_derived_plan(p, wp.inner, p->kernel_choice, p->bwd_kernel, std::move(csr), stream, &ws->inner, (int)tb, true);
+  if (rc != ESCOIN_OK) return rc;
+  ESCOIN_HIP_TRY(ws->x.alloc(sizeof(float) * (size_t)wp.x_floats));
+  ESCOIN_HIP_TRY(ws->t.alloc(sizeof(float) * (size_t)wp.t_floats));
+  ESCOIN_HIP_TRY(ws->dx.alloc(sizeof(float) * (size_t)wp.x_floats));
+  p->n_dense_groups = 0; p->n_sparse_groups = p->g.d.group; p->use_dense = false;
+  p->dense_mask = 0; p->sparse_mask = ~0ull; p->small_rule = 0; p->import_fast = false;
+  p->kernel_name = std::string(g_w2b_hooks.pack_kernel_name) + " + " + escoin_plan_kernel_name(ws->inner.plan.get()) + " + " +
+                   g_w2b_hooks.unpack_kernel_name;
+  p->aligned = true;
+  return ESCOIN_OK;
+}
+
 // What every align of an option "deconv" plan asks first (the device aligns, and escoin_weight_align_cpu): whether d2s_plan
 // serves the layer for this Dtype, and that no other derived-plan option is set.  ESCOIN_OK on other plans.
 int deconv_precheck(const escoin_plan *p, bool is_f64) {
@@ -412,6 +455,15 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     if (rc != ESCOIN_OK) p->s2b_state.reset();
     return rc;
   }
+  // option "w2b": likewise for a stride-1, dilation-1 layer wider than the tiled kernels take, through an inner plan of N * S
+  // column strips (the options above serve other geometries; "b2s" or "depthwise" set on the same plan keep the layer)
+  W2bPlan w2p;
+  const bool w2b_asked = p->w2b && !p->b2s && !p->depthwise;
+  if (w2b_asked && direct_mode && w2b_plan(g, false, p->w2b_strip, &w2p)) {
+    const int rc = w2b_build(p, w2p, stream);
+    if (rc != ESCOIN_OK) p->w2b_state.reset();
+    return rc;
+  }
   // A forced TILED / JIT on a layer that "s2d" / "s2b" serves in the direct modes names the INNER plan's kernel: the layer's own
   // geometry (a stride, a dilation) has no tiled kernel.  Here the plan stands in a lowered mode, which runs on that geometry
   // without the inner plan, and aligns as under KERNEL_AUTO instead of refusing -- a conv_mode flip left such a plan unaligned.
@@ -429,7 +481,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
   int kernel = p->kernel_choice;
   if ((kernel == ESCOIN_KERNEL_TILED || kernel == ESCOIN_KERNEL_JIT) && !tiled_supported(g) &&
       ((p->s2d && s2d_plan(g, false, &s2p)) || (p->s2b && s2b_plan(g, false, &s2bp)) ||
-       (p->b2s && b2s_plan(g, false, p->b2s_block, tiled_device_cus(), &b2p))))
+       (p->b2s && b2s_plan(g, false, p->b2s_block, tiled_device_cus(), &b2p)) || (w2b_asked && w2b_plan(g, false, p->w2b_strip, &w2p))))
     kernel = ESCOIN_KERNEL_AUTO;
   // which conv groups go to the dense (fp32 MFMA) kernel (align_rules.h)
   const int G = g.d.group;
@@ -710,6 +762,19 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->b2s = value;
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "w2b")) {
+      if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "w2b must be 0 or 1");
+      if (p->aligned || p->host_aligned) return fail(ESCOIN_ESTATE, "w2b must be set before weight_align / weight_align_cpu / set_csr");
+      p->w2b = value;
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "w2b_strip")) {
+      if (!w2b_strip_ok(value, p->g.d.KW))
+        return fail(ESCOIN_EINVAL, "w2b_strip must be 0 (the rule) or a multiple of 4 with KW - 1 <= w2b_strip and w2b_strip + KW - 1 <= 256");
+      if (p->aligned || p->host_aligned) return fail(ESCOIN_ESTATE, "w2b_strip must be set before weight_align / weight_align_cpu / set_csr");
+      p->w2b_strip = value;
+      return ESCOIN_OK;
+    }
     if (!strcmp(key, "deconv")) {
       if (value < 0 || value > 1) return fail(ESCOIN_EINVAL, "deconv must be 0 or 1");
       if (p->aligned || p->host_aligned) return fail(ESCOIN_ESTATE, "deconv must be set before weight_align / weight_align_cpu / set_csr");
@@ -785,6 +850,7 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->wgrad_kernel = value;
       // (options "b2s" and "deconv": the weight gradient is the inner plan's, which reads the option as this plan would)
       if (p->b2s_state) return escoin_plan_set_option(p->b2s_state->inner.plan.get(), key, value);
+      if (p->w2b_state) return escoin_plan_set_option(p->w2b_state->inner.plan.get(), key, value);      // (option "w2b": likewise)
       if (p->d2s_state) return escoin_plan_set_option(p->d2s_state->inner.plan.get(), key, value);
       return ESCOIN_OK;
     }
@@ -793,6 +859,7 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       p->wgrad_pointwise = value;
       // (options "b2s" and "deconv": handed on as "wgrad_kernel" is)
       if (p->b2s_state) return escoin_plan_set_option(p->b2s_state->inner.plan.get(), key, value);
+      if (p->w2b_state) return escoin_plan_set_option(p->w2b_state->inner.plan.get(), key, value);      // (option "w2b": likewise)
       if (p->d2s_state) return escoin_plan_set_option(p->d2s_state->inner.plan.get(), key, value);
       return ESCOIN_OK;
     }
@@ -847,7 +914,7 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       // (an "s2d" / "s2b" / "b2s" / "depthwise" plan also rebuilds between the lowered modes, which run on the original geometry, and SCONV / SCONV_PAR)
       auto direct = [](int m) { return m == ESCOIN_CONV_MODE_SCONV || m == ESCOIN_CONV_MODE_SCONV_PAR; };
       const bool regroup = p->aligned && ((value == ESCOIN_CONV_MODE_LOWERED_GEMM) != (p->conv_mode == ESCOIN_CONV_MODE_LOWERED_GEMM) ||
-                                          ((p->s2d || p->s2b || p->b2s || p->depthwise) && !p->is_f64 && direct(value) != direct(p->conv_mode)));
+                                          ((p->s2d || p->s2b || p->b2s || p->w2b || p->depthwise) && !p->is_f64 && direct(value) != direct(p->conv_mode)));
       // (option "deconv": the mode is the inner plan's, which rebuilds itself where it has to)
       if (p->aligned && p->d2s_state) {
         if (const int rcs = sync_host_values(p)) return rcs;
@@ -1034,6 +1101,11 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "b2s_block")) return p->b2s_state ? p->b2s_state->bp.B : 0;
   if (!strcmp(key, "b2s_scratch_bytes"))
     return p->b2s_state ? (long)(p->b2s_state->x.bytes() + p->b2s_state->t.bytes() + p->b2s_state->dx.bytes()) : 0;
+  if (!strcmp(key, "w2b")) return p->w2b_state ? 1 : 0;
+  if (!strcmp(key, "w2b_strips")) return p->w2b_state ? p->w2b_state->wp.S : 0;
+  if (!strcmp(key, "w2b_strip")) return p->w2b_state ? p->w2b_state->wp.SW : 0;
+  if (!strcmp(key, "w2b_scratch_bytes"))
+    return p->w2b_state ? (long)(p->w2b_state->x.bytes() + p->w2b_state->t.bytes() + p->w2b_state->dx.bytes()) : 0;
   if (p->inner_plan()) {
     // what describes the forward's kernel is the inner plan's
     static const char *const inner_keys[] = {"kernel_choice", "code_bytes", "code_direct", "small_launch_rule", "jit_rows", "jit_records",
@@ -1220,6 +1292,37 @@ int escoin_plan_b2s_unpack(escoin_plan *p, const float *src_dev, float *dst_dev,
   });
 }
 
+// the checks the three "w2b" entry points share
+static int w2b_entry(const escoin_plan *p, const void *src_dev, const void *dst_dev, int n_images, const char *who) {
+  if (!p) return fail(ESCOIN_EINVAL, "null argument");
+  if (!p->aligned || !p->w2b_state) return fail(ESCOIN_ESTATE, std::string(who) + ": option \"w2b\" is not active on this plan");
+  if (!src_dev || !dst_dev) return fail(ESCOIN_EINVAL, "null argument");
+  if (const int rc = check_n_images(p, n_images)) return rc;
+  return n_images == 0 ? ESCOIN_OK : check_plan_device(p, who);
+}
+
+int escoin_plan_w2b_pack(escoin_plan *p, const float *src_dev, const float *mask_dev, float *dst_dev, int top_side, int n_images,
+                         void *stream) {
+  return guarded([&]() -> int {
+    if (const int rc = w2b_entry(p, src_dev, dst_dev, n_images, "w2b_pack")) return rc;
+    return g_w2b_hooks.pack(p, src_dev, mask_dev, dst_dev, top_side != 0, n_images, (hipStream_t)stream);
+  });
+}
+
+int escoin_plan_w2b_unpack(escoin_plan *p, const float *src_dev, float *dst_dev, int relu, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    if (const int rc = w2b_entry(p, src_dev, dst_dev, n_images, "w2b_unpack")) return rc;
+    return g_w2b_hooks.unpack(p, src_dev, dst_dev, relu != 0, n_images, (hipStream_t)stream);
+  });
+}
+
+int escoin_plan_w2b_unpack_sum(escoin_plan *p, const float *src_dev, float *dst_dev, int n_images, void *stream) {
+  return guarded([&]() -> int {
+    if (const int rc = w2b_entry(p, src_dev, dst_dev, n_images, "w2b_unpack_sum")) return rc;
+    return g_w2b_hooks.unpack_sum(p, src_dev, dst_dev, n_images, (hipStream_t)stream);
+  });
+}
+
 int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_dev, float *top_dev,
                    int n_images, void *stream) {
   return guarded([&]() -> int {
@@ -1261,6 +1364,15 @@ int escoin_forward(escoin_plan *p, const float *bottom_dev, const float *bias_de
       rc = escoin_forward(bs->inner.plan.get(), bs->x.get<const float>(), bias_dev, bs->t.get<float>(), n_inner, stream);
       if (rc != ESCOIN_OK) return rc;
       return g_b2s_hooks.unpack(p, bs->t.get<const float>(), top_dev, true, p->g.d.fuse_relu != 0, n_images, s);
+    }
+    // option "w2b": the bottom's column strips become images of X', then the inner plan (bias in its epilogue) into T', then
+    // the strips' tops side by side into the top blob (ReLU there)
+    if (W2bState *ws = p->w2b_state.get()) {
+      int rc = g_w2b_hooks.pack(p, bottom_dev, nullptr, ws->x.get<float>(), false, n_images, s);
+      if (rc != ESCOIN_OK) return rc;
+      rc = escoin_forward(ws->inner.plan.get(), ws->x.get<const float>(), bias_dev, ws->t.get<float>(), n_images * ws->wp.S, stream);
+      if (rc != ESCOIN_OK) return rc;
+      return g_w2b_hooks.unpack(p, ws->t.get<const float>(), top_dev, p->g.d.fuse_relu != 0, n_images, s);
     }
     // option "deconv": the inner stride-1 plan on the caller's bottom itself into T' (no bias: it is not constant over a
     // phase's crop, and one more rounding in the unpack on the device and in CPU mode alike), then the interleave, the

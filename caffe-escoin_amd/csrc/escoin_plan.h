@@ -216,6 +216,16 @@ struct B2sState {
                                // weight gradient's operand in the same inner call)
 };
 
+// What upload() builds for a plan that option "w2b" serves (escoin_capi.hip; the rule: align_rules.h w2b_plan; the kernels:
+// w2b.hip); reset with the device side.  The whole backward is the inner plan's, as under "b2s": the plan itself builds no
+// BwdState.
+struct W2bState {
+  W2bPlan wp;
+  DerivedPlan inner;           // the plan of N * S strip images of H x Wi on the outer CSR (src: the identity)
+  DeviceBuffer x, t, dx;       // X': wp.x_floats floats; T' / G': wp.t_floats floats; dX': wp.x_floats floats (X' is the
+                               // weight gradient's operand in the same inner call)
+};
+
 // What upload() builds for a plan with option "deconv" (escoin_capi.hip; the rules: align_rules.h d2s_plan, csr_tables.h
 // d2s_csr; the kernels: d2s.hip); reset with the device side.  A plan has at most one of the four states.  The whole
 // backward is the inner plan's, around the pack kernel and the gradients' carry: the plan itself builds no BwdState.
@@ -414,6 +424,9 @@ struct escoin_plan {
   // Batch-to-space (b2s.hip): options "b2s" and "b2s_block" and what upload() builds where they apply; reset with the device side
   int b2s = 0, b2s_block = 0;
   std::unique_ptr<escoin::B2sState> b2s_state;
+  // Width-to-batch (w2b.hip): options "w2b" and "w2b_strip" and what upload() builds where they apply; reset with the device side
+  int w2b = 0, w2b_strip = 0;
+  std::unique_ptr<escoin::W2bState> w2b_state;
   // Deconvolution (d2s.hip): option "deconv", the descriptor as the caller gave it (with the option set, g is the mirror
   // convolution's geometry -- M <-> C, H x W <-> OH x OW -- whose weight matrix, CSR and aligned form are this layer's) and
   // what upload() builds; reset with the device side.  cpu_inner: the CPU mode's inner plan (sconv_cpu.cpp), host only
@@ -427,10 +440,10 @@ struct escoin_plan {
   int depthwise = 0, dw_band_rows = 0;
   bool dw_on = false;
   escoin::DwPlan dw;
-  // the inner plan of whichever of the four options serves this plan (null: none does)
+  // the inner plan of whichever of the five options serves this plan (null: none does)
   const escoin::DerivedPlan *inner_plan() const {
     return s2d_state ? &s2d_state->inner : s2b_state ? &s2b_state->inner : b2s_state ? &b2s_state->inner :
-           d2s_state ? &d2s_state->inner : nullptr;
+           w2b_state ? &w2b_state->inner : d2s_state ? &d2s_state->inner : nullptr;
   }
 
   // Dense weight gradient (dense_wgrad.hip): option "dense_wgrad_splits" (0: the rule decides, n: at most n splits of the
@@ -607,6 +620,19 @@ struct B2sHooks {
   const char *pack_kernel_name, *unpack_kernel_name;
 };
 extern B2sHooks g_b2s_hooks;   // escoin_capi.hip
+
+// w2b.hip (option "w2b"), registered like S2dHooks.  The buffers are the caller's; always of the first n_images images:
+//   pack        top_side false: X' from the bottom blob (a strip's column 0 is column s * SW - pad_w); true: G' from top_diff
+//               (column s * SW), times [mask > 0] where mask (the top blob) is not null; +0 outside the row
+//   unpack      the top blob from T', through ReLU if `relu`
+//   unpack_sum  bottom_diff from dX': per element the sum over the one or two strips that hold its column
+struct W2bHooks {
+  int (*pack)(const escoin_plan *p, const float *src, const float *mask, float *dst, bool top_side, int n_images, hipStream_t stream);
+  int (*unpack)(const escoin_plan *p, const float *src, float *dst, bool relu, int n_images, hipStream_t stream);
+  int (*unpack_sum)(const escoin_plan *p, const float *src, float *dst, int n_images, hipStream_t stream);
+  const char *pack_kernel_name, *unpack_kernel_name, *unpack_sum_kernel_name;
+};
+extern W2bHooks g_w2b_hooks;   // escoin_capi.hip
 
 // d2s.hip (option "deconv"), registered like S2dHooks.  Of the first n_images images:
 //   unpack      top from T' (+ bias[m] where bias is not null, through ReLU if `relu`): one store per top element

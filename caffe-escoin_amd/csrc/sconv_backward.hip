@@ -839,6 +839,30 @@ static int backward_b2s(escoin_plan *p, const float *bottom, const float *top, c
   return g_b2s_hooks.unpack(p, bs->dx.get<const float>(), bottom_diff, false, false, n_images, stream);
 }
 
+// option "w2b": the whole backward is the inner plan's, "b2s"'s route: on X' (the bottom's strips, packed again from the
+// caller's bottom: the weight gradient's operand) and G' (top_diff's strips, times [top > 0] on a fuse_relu plan, +0 in the last
+// strip's tail -- those pixels add nothing to any gradient).  The CSR is the same, so weight_diff, values_diff and bias_diff
+// go straight through.  dX' has a scratch of its own and unpack_sum gathers bottom_diff from it: the halo columns' two terms.
+static int backward_w2b(escoin_plan *p, const float *bottom, const float *top, const float *top_diff, float *bottom_diff,
+                        float *weight_diff, float *bias_diff, int n_images, hipStream_t stream, bool compact) {
+  W2bState *ws = p->w2b_state.get();
+  escoin_plan *ip = ws->inner.plan.get();
+  // (after device-source updates of THIS plan the inner plan's host CSR, which its backward state is built from, is stale)
+  if (!ip->bwd)
+    if (const int rcs = sync_host_values(p)) return rcs;
+  if (const int rc = ensure_state<float>(ip, stream)) return rc;
+  if (n_images == 0 || (!bottom_diff && !weight_diff && !bias_diff)) return ESCOIN_OK;
+  int rc = ESCOIN_OK;
+  if (weight_diff) rc = g_w2b_hooks.pack(p, bottom, nullptr, ws->x.get<float>(), false, n_images, stream);
+  if (rc == ESCOIN_OK) rc = g_w2b_hooks.pack(p, top_diff, p->g.d.fuse_relu ? top : nullptr, ws->t.get<float>(), true, n_images, stream);
+  if (rc != ESCOIN_OK) return rc;
+  rc = (compact ? escoin_backward_values : escoin_backward)(ip, weight_diff ? ws->x.get<const float>() : nullptr, nullptr,
+                                                            ws->t.get<const float>(), bottom_diff ? ws->dx.get<float>() : nullptr,
+                                                            weight_diff, bias_diff, n_images * ws->wp.S, stream);
+  if (rc != ESCOIN_OK || !bottom_diff) return rc;
+  return g_w2b_hooks.unpack_sum(p, ws->dx.get<const float>(), bottom_diff, n_images, stream);
+}
+
 // option "deconv": the whole backward is the inner plan's, on the caller's bottom (the weight gradient's operand) and G' (top_diff
 // split into its output phases by the pack kernel, times [top > 0] on a fuse_relu plan, +0 outside the top).  The inner data
 // gradient IS bottom_diff: the caller's pointer goes straight through.  The inner compact weight gradient and the inner
@@ -889,6 +913,8 @@ static int backward_gpu(escoin_plan *p, const T *bottom, const T *top, const T *
   hipStream_t stream = (hipStream_t)stream_v;
   if constexpr (sizeof(T) == 4)
     if (p->b2s_state) return backward_b2s(p, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images, stream, compact);
+  if constexpr (sizeof(T) == 4)
+    if (p->w2b_state) return backward_w2b(p, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images, stream, compact);
   if constexpr (sizeof(T) == 4)
     if (p->d2s_state) return backward_d2s(p, bottom, top, top_diff, bottom_diff, weight_diff, bias_diff, n_images, stream, compact);
   if (const int rc = ensure_state<T>(p, stream)) return rc;

@@ -82,8 +82,8 @@ extern "C" {
  *   staged weight gradient                   N*M*OH*OW, N*C*H*W < 2^31      refused when forced, AUTO takes the entry kernel
  *   MFMA weight / data gradient, dense       N*OH*OW (N*H*W), M*Cg*KH*KW,   refused when forced (wgm_plan, dgm_plan)
  *     weight gradient                        Cg*H*W (Mg*OH*OW) < 2^31
- *   options "s2d", "s2b", "b2s"              bottom, top, X', T' < 2^31     the option is not taken: the plan runs as
- *                                            elements; N*P, N' <= 65535     without it
+ *   options "s2d", "s2b", "b2s", "w2b"       bottom, top, X', T' < 2^31     the option is not taken: the plan runs as
+ *                                            elements; N*P, N', N*S <= 65535  without it
  * A plan whose conv groups are split between the dense and the sparse kernels asks the sparse half's limits before it
  * launches the dense half: a refused call has written nothing. */
 
@@ -206,6 +206,13 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  with the batch as the pixel axis ("Batch-to-space" below).  1 changes nothing for a layer the option
  *                  does not serve; KERNEL_AUTO never picks it by itself.  May be set together with "s2d" and "s2b".
  *   "b2s_block"  = the block B of "b2s": 0 (default) the rule, otherwise a multiple of 4 in 4..256 (a test option).
+ *   "w2b"        = 0 (default) / 1: run a stride-1, dilation-1 layer whose input or output row is wider than 256 columns
+ *                  on the tiled kernels as column strips ("Width-to-batch" below).  1 changes nothing for a layer the
+ *                  option does not serve; KERNEL_AUTO never picks it by itself.  May be set together with "s2d" and "s2b",
+ *                  which serve other geometries; a plan with "b2s", "depthwise" or "deconv" set runs as without "w2b".
+ *   "w2b_strip"  = the strip width SW of "w2b": 0 (default) the rule, otherwise a multiple of 4 with KW - 1 <= SW and
+ *                  SW + KW - 1 <= 256, which also serves rows of 256 columns and fewer (a test option); other values
+ *                  ESCOIN_EINVAL.  Both are refused after an align with ESCOIN_ESTATE.
  * Environment: the product build reads ESCOIN_VERBOSE (diagnostics on stderr) and TMPDIR (temporary file of the
  * code object manager's fallback path) and nothing else -- no environment variable can change a result
  * ("Environment"; csrc/knobs.h for the non-product flavours built by tools/mkabl.sh exp / stamps). */
@@ -417,6 +424,65 @@ ESCOIN_API int escoin_plan_b2s_pack(escoin_plan *plan, const float *src_dev, con
                          int n_images, void *stream);
 ESCOIN_API int escoin_plan_b2s_unpack(escoin_plan *plan, const float *src_dev, float *dst_dev, int top_side, int relu, int n_images,
                          void *stream);
+
+/* ---- Width-to-batch: wide layers on the tiled kernels by column strips (option "w2b") ----------------------------------
+ * The tiled kernels (generated code, the LDS stream kernel) take rows of at most 256 columns, input and output.  A
+ * stride-1, dilation-1 convolution of a wider image is S independent convolutions of column strips with a halo.  Let SW be a
+ * strip's output width, a multiple of 4 with SW >= KW - 1, S = ceil(OW / SW) and Wi = SW + KW - 1 <= 256.  The INNER plan has
+ *   N' = N * S images, strip s of image n being image n' = n * S + s (the first n_images outer images are the first
+ *   n_images * S inner ones), of H x Wi pixels;
+ *   the outer plan's C, M, group, kernel, pad_h and has_bias, pad_w = 0, stride 1, dilation 1, fuse_relu = 0;
+ *   weights the outer CSR verbatim: same rows, same columns, same value order;
+ *   input   X'[n'][c][h][x] = bottom[n][c][h][s * SW - pad_w + x] where that column is inside the bottom, +0 outside (the
+ *           pad, and the tail of the last strip);
+ *   T' = inner_forward(X') over n_images * S inner images, OH x SW each, the bias in the inner epilogue;
+ *   top[n][m][oh][ow] = T'[n * S + ow / SW][m][oh][ow % SW], then v > 0 ? v : 0 on a fuse_relu plan;
+ *   G'[n'][m][oh][j] = top_diff[n][m][oh][s * SW + j] for s * SW + j < OW (on a fuse_relu plan gated by top > 0), +0 past OW;
+ *   the WHOLE backward is the inner plan's, on (X', G'), as under "b2s": the weight, bias and compact gradients and
+ *           escoin_dense_wgrad are the inner plan's own, the caller's pointers going straight through (the CSR is the same,
+ *           and the zero-filled tails add exact zeros); bottom_diff[n][c][h][w] = the sum, in ascending s, of
+ *           dX'[n * S + s][c][h][w + pad_w - s * SW] over the strips whose [0, Wi) holds that column -- one term, or two in
+ *           the KW - 1 halo columns (SW >= KW - 1: never three) -- with dX' = inner_data_gradient(G').  Columns of the padded
+ *           frame outside the bottom are dropped.  The outer plan builds no backward state.
+ * A strip row is one contiguous run of the bottom's (top's) row: both sides of every copy are unit-stride, and only the halo
+ * columns are read twice.  Images at or past n_images are neither read nor written on the caller's side.
+ * With "w2b" = 1 a FLOAT plan in conv_mode SCONV / SCONV_PAR with stride 1 and dilation 1 in both axes and W > 256 or
+ * OW > 256, of any kernel shape, pad and group, whose bottom, top, X' and T' each stay below 2^31 elements and whose N * S is
+ * at most 65535, runs this way: escoin_forward = escoin_w2b_pack_kernel + the inner plan's forward +
+ * escoin_w2b_unpack_kernel; escoin_backward / escoin_backward_values = escoin_w2b_pack_kernel of the bottom (where a weight
+ * gradient is asked for) and of top_diff + the inner plan's backward + escoin_w2b_unpack_sum_kernel of dX'.  All three
+ * kernels are one pass with one store per destination element, zeros included: no memset, no atomics.
+ * The strips: the fewest.  With cap the largest multiple of 4 with cap + KW - 1 <= 256, S = ceil(OW / cap) and SW = the
+ * smallest multiple of 4 at or above ceil(OW / S) (W = OW = 300, 3x3: S = 2, SW = 152, Wi = 154).  "w2b_strip" forces SW, on
+ * a row of any width.  Strips of Wi <= 128 were measured against the fewest (profiles/w2b_mi355x.md): mixed, no rule followed.
+ * The inner plan and three scratches (X', T' / G', and dX') are built by the align; the inner plan's backward state by the
+ * first backward; after these forward and backward never allocate.  The inner plan gets the options "b2s" hands down, and
+ * "tiling_batch" in inner images (tiling_batch * S), and ALONE decides its kernel on its own geometry -- generated code, the
+ * stream kernel, dense or generic; forcing TILED / JIT, or a backward or weight-gradient kernel, fails with ESCOIN_EINVAL
+ * where the inner layer does not fit it.  In-place updates (escoin_update_values, escoin_plan_set_values,
+ * escoin_solver_step) reach the inner plan's copies; prune, rewire, set_csr and weight_align rebuild the inner plan.
+ * escoin_plan_export_aligned writes the outer CSR and no code section.  Everywhere else -- a narrow row, a stride or a
+ * dilation above 1, a size limit, a double plan, the lowered modes (a flip of the conv mode rebuilds), "b2s", "depthwise" or
+ * "deconv" on the same plan -- the plan behaves exactly as with "w2b" = 0, with the exception "Space-to-depth" states for a
+ * forced "kernel" = TILED / JIT in the lowered modes.  Not served: a wide INNER layer of "s2d", "s2b" or "deconv" (their inner
+ * plans do not get the option), double plans, and CPU mode, which has no width limit.
+ * Results: an element's sum order on the inner sparse kernels is a function of the pattern, so a top element does not
+ * depend on the strips; the inner DENSE kernel and the weight gradient (whose chunks are cut on the strips' pixels) are held
+ * to the error bound.
+ * Stats: "w2b" (1 when active), "w2b_strips" (S), "w2b_strip" (SW), "w2b_scratch_bytes" (the three scratches);
+ * "kernel_choice", the "bwd_*" / "wgrad_*" / "dgrad_*" facts, escoin_plan_tiling_info and the other facts about the kernels
+ * report the inner plan's; escoin_plan_kernel_name returns "escoin_w2b_pack_kernel + <inner name> + escoin_w2b_unpack_kernel".
+ * "device_bytes" and escoin_plan_workspace_bytes count the scratches and the inner plan.
+ * escoin_plan_w2b_pack / _unpack / _unpack_sum run one rearrangement alone on the CALLER's buffers, for measuring and
+ * testing.  pack: top_side = 0 reads n_images x C x H x W floats of src_dev and writes n_images * S x C x H x Wi of dst_dev;
+ * top_side = 1 reads n_images x M x OH x OW (and mask_dev, where not NULL: the value is mask > 0 ? src : 0) and writes
+ * n_images * S x M x OH x SW.  unpack reads the latter and writes the former, through ReLU if relu != 0.  unpack_sum reads
+ * n_images * S x C x H x Wi floats and writes n_images x C x H x W.  ESCOIN_ESTATE unless stat "w2b" is 1; ESCOIN_EINVAL for
+ * NULL buffers or n_images outside [0, N]. */
+ESCOIN_API int escoin_plan_w2b_pack(escoin_plan *plan, const float *src_dev, const float *mask_dev, float *dst_dev, int top_side,
+                         int n_images, void *stream);
+ESCOIN_API int escoin_plan_w2b_unpack(escoin_plan *plan, const float *src_dev, float *dst_dev, int relu, int n_images, void *stream);
+ESCOIN_API int escoin_plan_w2b_unpack_sum(escoin_plan *plan, const float *src_dev, float *dst_dev, int n_images, void *stream);
 
 /* ---- Deconvolution: Caffe's DeconvolutionLayer on the stride-1 kernels (option "deconv") ---------------------------------
  *   DeconvolutionLayer<Dtype>   deconv_layer.cpp: forward = the base layer's backward_*_gemm, backward = forward_*_gemm +
