@@ -281,6 +281,26 @@ LaunchVerdict dense_bytes_limit(unsigned long long in_bytes, unsigned long long 
   return LaunchVerdict();
 }
 
+LaunchVerdict db16_plan(const Geometry &g, bool is_f64, int n_images, int groups, int n_cu, Db16Plan *dp) {
+  if (is_f64) return refuse_launch(ESCOIN_ESTATE, "dense_math = 1 (bf16): the plan holds double weights");
+  const long P = (long)n_images * g.OH * g.OW;
+  if (const LaunchVerdict v = dense_pixels_limit(P); !v.ok()) return v;
+  Db16Plan p;
+  // (the weight matrix is the fp32 kernel's: rows of K rounded up to 32 floats, 128 spare rows)
+  const unsigned long long lda = (unsigned long long)(g.kdim + 31) / 32 * 32;
+  p.in_bytes = (unsigned long long)n_images * g.d.C * g.d.H * g.d.W * 4;
+  p.w_bytes = ((unsigned long long)g.d.M + 128) * lda * 4;
+  if (const LaunchVerdict v = dense_bytes_limit(p.in_bytes, p.w_bytes); !v.ok()) return v;
+  p.bm = g.Mg <= 64 ? 64 : 128;
+  p.n_ptiles = (int)((P + kDb16TileP - 1) / kDb16TileP);
+  p.n_mtiles = (g.Mg + p.bm - 1) / p.bm;
+  p.ksteps = (g.kdim + kDb16StepK - 1) / kDb16StepK;
+  p.tiles = (long)p.n_ptiles * p.n_mtiles * groups;
+  p.workgroups = std::min(p.tiles, 2l * std::max(n_cu, 1));
+  *dp = p;
+  return LaunchVerdict();
+}
+
 LaunchVerdict grid_yz_limit(GridKernel k, unsigned long grid_y, unsigned long grid_z) {
   if (grid_y <= kGridYZMax && (grid_z <= kGridYZMax || k == kGridCsrmmF64)) return LaunchVerdict();
   switch (k) {

@@ -124,6 +124,19 @@ LaunchVerdict tiled_call_limits(const Geometry &g, const Tiling &t, int n_images
 LaunchVerdict dense_pixels_limit(long pixels);
 // dense: the bottom of the launch or the weight matrix at or above kDescriptorRange bytes
 LaunchVerdict dense_bytes_limit(unsigned long long in_bytes, unsigned long long w_bytes);
+// ---- the dense forward kernel's bf16 math mode (dense_bf16.hip, plan option "dense_math" = ESCOIN_MATH_BF16) ---------
+// What launch_dense_bf16 launches for the first n_images images of `groups` conv groups on n_cu compute units, or why it
+// refuses: float plans only, and the fp32 kernel's limits (dense_pixels_limit, dense_bytes_limit: the operands are addressed
+// through the same 32-bit buffer descriptors).  The GEMM view is the fp32 kernel's -- per group C[Mg x P] = A[Mg x K] *
+// B[K x P] -- in tiles of bm x kDb16TileP outputs (bm = 64 where Mg <= 64, else 128) walked in k-steps of kDb16StepK by
+// min(tiles, 2 * n_cu) persistent workgroups; whole tiles always (no stream-K).
+constexpr int kDb16TileP = 128, kDb16StepK = 64;
+struct Db16Plan {
+  int bm = 0, n_ptiles = 0, n_mtiles = 0, ksteps = 0;
+  long tiles = 0, workgroups = 0;
+  unsigned long long in_bytes = 0, w_bytes = 0;     // the descriptors' ranges: the launch's bottom, the padded weight matrix
+};
+LaunchVerdict db16_plan(const Geometry &g, bool is_f64, int n_images, int groups, int n_cu, Db16Plan *dp);
 // generic / lowered: grid y or z above kGridYZMax.  The message names the kernel.
 enum GridKernel { kGridGeneric, kGridCsrmm, kGridCsrmmF64, kGridIm2col };
 LaunchVerdict grid_yz_limit(GridKernel k, unsigned long grid_y, unsigned long grid_z);

@@ -32,6 +32,7 @@
 #include <cstdlib>
 #include <vector>
 
+#include "dense_common.h"
 #include "escoin_plan.h"
 #include "knobs.h"
 
@@ -66,33 +67,7 @@
 
 namespace escoin {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4d __attribute__((ext_vector_type(4)));
-
-constexpr int kBN = 128, kBK = 32;
-
-struct DenseArgs {
-  const float *__restrict__ in;
-  const float *__restrict__ w;     // dense (M + 128) x lda, zero-padded: rows of lda = K rounded up to 32
-  const float *__restrict__ bias;
-  const int2 *__restrict__ ktab;   // [K rounded up to 32]: {element offset of tap k in the image, dy | dx << 16}
-  float *__restrict__ out;
-  int n_images, C, H, W, M, OH, OW;
-  int pad_h, pad_w, stride_h, stride_w;
-  int Cg, Mg, K, lda, P, relu;
-  int n_ptiles, n_mtiles, n_groups;        // tiles: pixel x channel x conv group (of this launch)
-  unsigned in_bytes, w_bytes;              // buffer descriptor ranges
-  int vec_out;                             // OH*OW % 4 == 0 and top 16-byte aligned: 16-byte stores through LDS
-  unsigned long long group_mask;           // conv groups this launch covers (all ones: every group)
-  unsigned long long *prof;                // ESCOIN_STAMPS builds: stamp profile [workgroup][wave][8] (ESC_DPROF)
-  // stream-K (STREAMK instantiations): every workgroup takes an equal, contiguous run of (tile, k-step) units;
-  // a tile cut by a run boundary is finished by the workgroup holding its last k-steps, which adds the others'
-  // partial accumulators from `sk_ws` ([workgroup][wave][16 quads][64 lanes] floats x 4) once their `sk_flag`
-  // words (zeroed by the launch function before every launch) carry 1
-  float *sk_ws;
-  unsigned *sk_flag;     // [0 .. gridDim.x): published flags; [gridDim.x]: set when a bounded spin gave up
-  unsigned *sk_fail;     // the same give-up, sticky, in pinned HOST memory: the next escoin_forward on the plan fails loudly
-};
+constexpr int kBK = 32;
 
 __device__ __forceinline__ int a_swizzle(int row, int chunk) { return row * kBK + ((chunk ^ ((row >> 1) & 7)) << 2); }
 
@@ -623,8 +598,15 @@ int dense_build_ktab(escoin_plan *p, hipStream_t stream) {
   return ESCOIN_OK;
 }
 
+DenseBf16Launch g_dense_bf16_launch = nullptr;
+
 int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, float *top,
                  int n_images, hipStream_t stream) {
+  // option "dense_math": every launch of a plan that asks for bf16 products is dense_bf16.hip's
+  if (p->dense_math == ESCOIN_MATH_BF16) {
+    if (!g_dense_bf16_launch) return fail(ESCOIN_EINVAL, "option \"dense_math\": this build does not carry the bf16 dense kernel");
+    return g_dense_bf16_launch(p, bottom, bias, top, n_images, stream);
+  }
   const Geometry &g = p->g;
   const DenseArrays &dn = p->dense;
   if (!dn.ktab.get<void>() || !dn.w.get<void>()) return fail(ESCOIN_ESTATE, "dense kernel: plan has no dense weights");
@@ -707,6 +689,7 @@ int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, f
                        (int)(flag_bytes / 4));
   }
   dn.sk_used = streamk;
+  dn.math_last = ESCOIN_MATH_FP32;
   dn.variant_last = (bm == 64 ? 1 : 2) + 4 * (vec_b ? 1 : 0) + 8 * (a.vec_out ? 1 : 0) + 16 * (streamk ? 1 : 0);
   dim3 grid((unsigned)n_wg, 1, 1);
 #define ESC_DENSE_LAUNCH(WR, MODE)                                                                                 \

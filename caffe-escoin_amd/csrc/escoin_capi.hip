@@ -226,6 +226,7 @@ int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, i
   if ((rc = escoin_plan_set_option(q, "dense_threshold_pct", owner->dense_threshold_pct)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "dense_gate", owner->dense_gate)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "code_loader", owner->code_loader)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "dense_math", owner->dense_math)) != ESCOIN_OK) return rc;
   if (wgrad_options) {
     if ((rc = escoin_plan_set_option(q, "wgrad_kernel", owner->wgrad_kernel)) != ESCOIN_OK) return rc;
     if ((rc = escoin_plan_set_option(q, "wgrad_channel_block", owner->wgrad_channel_block)) != ESCOIN_OK) return rc;
@@ -360,6 +361,9 @@ static int w2b_build(escoin_plan *p, const W2bPlan &wp, hipStream_t stream) {
 // What every align of an option "deconv" plan asks first (the device aligns, and escoin_weight_align_cpu): whether d2s_plan
 // serves the layer for this Dtype, and that no other derived-plan option is set.  ESCOIN_OK on other plans.
 int deconv_precheck(const escoin_plan *p, bool is_f64) {
+  // (every align of either Dtype passes here first: option "dense_math" = bf16 set before a double align is refused by name too)
+  if (is_f64 && p->dense_math == ESCOIN_MATH_BF16)
+    return fail(ESCOIN_EINVAL, "dense_math = 1 (bf16) is for float plans: these weights are double");
   if (!p->deconv) return ESCOIN_OK;
   D2sPlan dp;
   if (!d2s_plan(p->user_desc, is_f64, &dp)) return fail(ESCOIN_EINVAL, dp.error);
@@ -798,6 +802,16 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       (band ? p->dw_band_rows : p->depthwise) = value;
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "dense_math")) {
+      // (no state of its own: read by every dense launch, so it may change between forwards; an inner plan's launches are
+      //  the ones that run, so it is handed on like "kernel" at the align and at once where the inner plan exists)
+      if (value != ESCOIN_MATH_FP32 && value != ESCOIN_MATH_BF16) return fail(ESCOIN_EINVAL, "dense_math must be 0 (fp32) or 1 (bf16)");
+      if (value == ESCOIN_MATH_BF16 && p->is_f64 && (p->aligned || p->host_aligned))
+        return fail(ESCOIN_EINVAL, "dense_math = 1 (bf16) is for float plans: this plan holds double weights");
+      p->dense_math = value;
+      if (p->inner_plan()) return escoin_plan_set_option(p->inner_plan()->plan.get(), key, value);
+      return ESCOIN_OK;
+    }
     if (!strcmp(key, "b2s_block")) {
       if (value != 0 && (value < kB2sMinBlock || value > kB2sMaxBlock || value % 4 != 0))
         return fail(ESCOIN_EINVAL, "b2s_block must be 0 (the rule) or a multiple of 4 in 4..256");
@@ -1111,7 +1125,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
     static const char *const inner_keys[] = {"kernel_choice", "code_bytes", "code_direct", "small_launch_rule", "jit_rows", "jit_records",
                                              "deal_slowest_over_mean_x1000", "deal_worst_block_x1000", "lds_bytes", "body_variant",
                                              "code_touchers", "touch_lines_per_launch",
-                                             "workgroup_columns", "streamk_gave_up", "streamk", "dense_variant"};
+                                             "workgroup_columns", "streamk_gave_up", "streamk", "dense_variant", "dense_math"};
     for (const char *k : inner_keys)
       if (!strcmp(key, k)) return escoin_plan_stat(p->inner_plan()->plan.get(), key);
   }
@@ -1148,6 +1162,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   }
   if (!strcmp(key, "streamk")) return p->dense.sk_used ? 1 : 0;
   if (!strcmp(key, "dense_variant")) return p->dense.variant_last;
+  if (!strcmp(key, "dense_math")) return p->dense.math_last;
   if (!strncmp(key, "bwd_", 4) || !strncmp(key, "wgrad_", 6) || !strncmp(key, "dgrad_", 6)) return bwd_stat(p, key);
   if (!strncmp(key, "upd", 3)) return upd_stat(p, key);
   if (!strncmp(key, "dwg_", 4)) return dwg_stat(p, key);

@@ -316,7 +316,9 @@ struct DenseArrays {
   mutable bool sk_used = false;   // the last dense launch of this plan split K (escoin_plan_stat "streamk")
   // the instantiation and store path of the last dense launch: WROWS + 4 * BMODE + 8 * vec_out + 16 * STREAMK, 0 before
   // the first one (escoin_plan_stat "dense_variant")
+  // (+ 32 where dense_bf16.hip's kernel ran: its WROWS, operand path and store path under the same terms, never stream-K)
   mutable int variant_last = 0;
+  mutable int math_last = 0;      // ESCOIN_MATH_* of the last dense launch (escoin_plan_stat "dense_math")
 };
 
 }  // namespace escoin
@@ -374,6 +376,7 @@ struct escoin_plan {
   unsigned long long dense_mask = 0, sparse_mask = ~0ull;
   int n_dense_groups = 0, n_sparse_groups = 0;
   int dense_threshold_pct = -1;   // option "dense_threshold_pct" (-1: the measured default)
+  int dense_math = ESCOIN_MATH_FP32;   // option "dense_math": ESCOIN_MATH_BF16 = every dense launch runs dense_bf16.hip's kernel
   int body_variant = -1;          // option "body_variant": -1 the rule (align_rules.h body_variant), 0 always the generic body
   int code_touchers = 0;          // option "code_touchers": 0 the rule (align_rules.h touch_election), k >= 1 every k-th workgroup of an XCD and grid row
   int stream_stores = -1;         // option "stream_stores": pointwise layers write the top blob with non-temporal stores (1), never (0), by size (-1)
@@ -549,6 +552,11 @@ const char *dense_kernel_name();
 int dense_build_ktab(escoin_plan *p, hipStream_t stream);
 int dense_lda(int K);          // floats per row of d_dense_w (K rounded up to whole k-steps)
 int dense_spare_rows();       // zero rows after row M - 1
+// dense_bf16.hip (option "dense_math" = ESCOIN_MATH_BF16): the launch launch_dense hands over to, registered when the library
+// is loaded like S2dHooks below -- null in a program that links the core's objects alone, where the option is refused
+typedef int (*DenseBf16Launch)(const escoin_plan *p, const float *bottom, const float *bias, float *top, int n_images,
+                               hipStream_t stream);
+extern DenseBf16Launch g_dense_bf16_launch;   // dense_mfma.hip
 
 // wgrad_mfma.hip (option "wgrad_kernel" = MFMA): builds the kernel's tables for the tile plan bwd_choice made; stage 1 of
 // the weight gradient of the plan's nnz entries over `chunks` chunks of n_images images into slab_w [chunks][nnz]

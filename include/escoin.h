@@ -100,6 +100,9 @@ extern "C" {
 #define ESCOIN_KERNEL_GENERIC 1 /* one lane = one output pixel, CSR order kept    */
 #define ESCOIN_KERNEL_TILED 2   /* LDS-staged tiles, row-grouped weight stream    */
 #define ESCOIN_KERNEL_DENSE 3   /* implicit-GEMM on the fp32 matrix cores (MFMA)  */
+/* option / stat "dense_math": how the dense forward kernel multiplies */
+#define ESCOIN_MATH_FP32 0 /* exact fp32 products (v_mfma_f32_32x32x2_f32): the default */
+#define ESCOIN_MATH_BF16 1 /* operands rounded to bf16 inside the kernel, fp32 sums (v_mfma_f32_32x32x16_bf16) */
 #define ESCOIN_KERNEL_JIT 4     /* LDS-staged tiles; the weight walk is machine code
                                    WeightAlign generated from the sparsity pattern
                                    (what AUTO runs on every stride-1 layer -- and on
@@ -161,6 +164,23 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  sends the whole layer to the dense path (base_conv_layer.cpp:750-755,805-811);
  *   "dense_threshold_pct" = density in percent above which AUTO picks the dense kernel
  *                  (-1 = the built-in measured crossover; 100 = never);
+ *   "dense_math" = ESCOIN_MATH_FP32 (0, default) / ESCOIN_MATH_BF16 (1); any other value is ESCOIN_EINVAL.  With 1, every
+ *                  launch of the dense forward kernel on this float plan -- KERNEL_DENSE, the dense groups AUTO or
+ *                  "dense_gate" choose, LOWERED_GEMM, and the dense launches of the inner plans of "s2d" / "s2b" / "b2s" /
+ *                  "w2b" / "deconv", to which the option is handed on like "kernel" -- runs escoin_dense_bf16_kernel
+ *                  instead (tensor-op math with conversion; the blobs and the weights stay fp32).  The contract: the top
+ *                  blob is the fp32-accumulated convolution of bf16_rne(w) and bf16_rne(x) (products of two bf16 values
+ *                  are exact in fp32; the order of the sum is unspecified); the bias is added in fp32, unrounded, and the
+ *                  ReLU applied as always.  Element-wise, the distance to the exact result of the UNROUNDED operands is at
+ *                  most (2^-8 + 2^-18) * sum |w| |x| plus the fp32 accumulation bound.  An fp32 operand above bf16's
+ *                  largest finite value (about 3.39e38) rounds to infinity; a non-finite operand that meets a pruned zero
+ *                  weight gives NaN, as in the fp32 dense kernel.  Nothing turns the option on by itself, and it changes
+ *                  no decision: KERNEL_AUTO, its crossover and every other rule are as without it.  It holds no state
+ *                  (the kernel reads the plan's one fp32 weight matrix, so update_values / set_values / the solver step /
+ *                  prune / rewire need nothing more) and may be set at any time, also between forwards of an aligned
+ *                  plan.  Launches run whole tiles: stat "streamk" reads 0 under it.  A double plan refuses value 1 by
+ *                  name (at set_option when it is aligned, else at the double align); CPU mode, the sparse kernels and the
+ *                  backward's MFMA kernels ignore it.  Measured against the fp32 kernel in profiles/dense_bf16_mi355x.md;
  *   "tiling_batch" = choose the tiled kernel's tiling as for a batch of this many images
  *                  (0 = desc.N).  Results do not depend on it; tests use it to run small inputs
  *                  through the weight stream / tile shapes of the full-size configurations;
@@ -572,7 +592,10 @@ ESCOIN_API int escoin_plan_d2s_pack(escoin_plan *plan, const float *top_diff_dev
  * (dense kernel; a give-up also makes the next escoin_forward on the plan fail with ESCOIN_EHIP),
  * "dense_variant" (which instantiation and store path the plan's last dense launch took: output-channel rows per wave
  * (1: 64-row tiles, 2: 128-row tiles) + 4 if the pointwise operand was staged 16 bytes at a time + 8 if the top was
- * stored 16 bytes at a time + 16 if K was split across workgroups; 0 before the first dense launch). */
+ * stored 16 bytes at a time + 16 if K was split across workgroups + 32 if escoin_dense_bf16_kernel ran (option "dense_math";
+ * the other terms keep their meaning -- + 4: the pointwise operand's predicate held and it was addressed directly -- and the
+ * 16 is never set with it); 0 before the first dense launch),
+ * "dense_math" (ESCOIN_MATH_*: what the plan's last dense launch ran; 0 before the first one). */
 ESCOIN_API long escoin_plan_stat(const escoin_plan *plan, const char *key);
 
 /* Name of the device kernel the plan launches (the symbol rocprofv3 reports). */
