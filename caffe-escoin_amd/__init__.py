@@ -28,7 +28,9 @@ WGRAD_POINTWISE = 4    # stat "wgrad_kernel" only: the pointwise kernel of optio
 WGRAD_DEPTHWISE = 5    # stat "wgrad_kernel" only: the depthwise kernel of Plan(..., wgrad_depthwise=1) ran
 BWD_MFMA = 5   # option "backward_kernel" / stat "bwd_data_kernel": the fp32-MFMA data-gradient kernel (never "kernel")
 BWD_DEPTHWISE = 6   # stat "bwd_data_kernel" only: the depthwise data-gradient kernel of Plan(..., depthwise=1)
-MATH_FP32, MATH_BF16 = 0, 1   # option / stat "dense_math": Plan(..., dense_math=MATH_BF16) runs dense launches on the bf16 matrix cores
+MATH_FP32, MATH_BF16 = 0, 1   # option / stat "dense_math": Plan(..., dense_math=MATH_BF16) runs dense launches on the bf16 matrix cores;
+#                               option / stats "wgrad_math", "dwg_math": Plan(..., wgrad_math=MATH_BF16) does so for the MFMA weight gradient
+#                               (wgrad_kernel=WGRAD_MFMA) and for dense_wgrad
 CONV_MODE_LOWERED_GEMM, CONV_MODE_LOWERED_SPARSE, CONV_MODE_SCONV, CONV_MODE_SCONV_PAR = 0, 1, 2, 3
 
 # every symbol include/escoin.h declares (tests check the library exports all of them)

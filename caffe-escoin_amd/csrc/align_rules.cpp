@@ -634,6 +634,17 @@ bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp) {
   return true;
 }
 
+bool wgb_plan(const Geometry &g, bool is_f64, WgbPlan *bp) {
+  const escoin_conv_desc &d = g.d;
+  WgbPlan p;
+  if (!wgm_plan(g, is_f64, &p.tile)) return false;
+  p.tile.lds_bytes = kWgbLdsBytes;
+  p.vec_g = ((long)g.OH * g.OW) % 4 == 0;
+  p.vec_x = p.vec_g && d.KH == 1 && d.KW == 1 && d.stride_h == 1 && d.stride_w == 1 && d.pad_h == 0 && d.pad_w == 0;
+  *bp = p;
+  return true;
+}
+
 // The tiles of one slice height: per (group, c-block) the greedy m-slices.  A row's entries of a c-block are counted with a
 // cursor per row (columns ascend within a row, and a pointwise column IS the group-local channel).
 static void pw_tiles(const Geometry &g, const CsrIndex *rowptr, const CsrIndex *colidx, int cblk, int cap, int height,

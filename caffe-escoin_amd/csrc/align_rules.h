@@ -253,6 +253,23 @@ struct WgmPlan {
 // column tiles: the grid).
 bool wgm_plan(const Geometry &g, bool is_f64, WgmPlan *wp);
 
+// ---- the bf16 math mode of the MFMA weight-gradient kernels (wgrad_bf16.hip, plan option "wgrad_math" = ESCOIN_MATH_BF16)
+// The fp32 kernels' tiles, tables, chunks and grid (wgm_plan's predicate is this mode's); the chunk's pixels go through LDS
+// kWgbStepPixels at a time as bf16, k-contiguous: 2 buffers x (G tile, bottom tile) x 64 rows x 64 pixels x 2 bytes, no
+// padding (the rows are swizzled, wgrad_bf16_step.h).
+constexpr int kWgbStepPixels = 64;                   // pixels per LDS step: 4 k-steps of v_mfma_f32_32x32x16_bf16
+constexpr size_t kWgbLdsBytes = 2 * 2 * 2 * (size_t)kWgmTileM * kWgbStepPixels;
+static_assert(kWgbLdsBytes <= kWgmLdsBudget, "the bf16 weight-gradient tiles exceed their LDS budget");
+struct WgbPlan {
+  WgmPlan tile;              // wgm_plan's, with lds_bytes = kWgbLdsBytes
+  // Which operand's quads of 4 consecutive pixels MAY be staged by one 16-byte load (the launch also asks that the call's
+  // blob pointers are 16-byte aligned): G where OH*OW % 4 == 0 -- chunks start at multiples of 1024, so a quad then lies
+  // inside one image, wholly live or wholly dead --, the bottom where the layer is 1x1, stride 1, pad 0 on top of that (a
+  // column of the weight matrix is then a channel, contiguous along the pixels).
+  bool vec_g = false, vec_x = false;
+};
+bool wgb_plan(const Geometry &g, bool is_f64, WgbPlan *bp);
+
 // ---- the pointwise weight-gradient kernel (wgrad_pointwise.hip, plan option "wgrad_pointwise") ------------------------
 // The sampled product dW[m][c] = sum over pixels of G[m][q] * X[c][q] for the CSR's (m, c) pairs of a 1x1, pad-0 layer.
 // One workgroup of kPwThreads lanes per (tile, chunk).  A tile is rows [row0, row0 + rows) of one conv group crossed with

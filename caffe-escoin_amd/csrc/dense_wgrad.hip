@@ -34,14 +34,6 @@
 
 namespace escoin {
 
-struct DwgArgs {
-  WgmIn in;
-  float *__restrict__ part;             // [splits][D]
-  long positions;                       // D
-  int span_pixels;                      // span * kBwdChunkPixels
-  int Kd, mtiles;
-};
-
 template <bool RELU>
 __global__ void __launch_bounds__(kWgmThreads)
 escoin_dense_wgrad_mfma_kernel(DwgArgs a) {
@@ -170,9 +162,20 @@ static int dense_wgrad_gpu(escoin_plan *p, const float *bottom, const float *top
     a.span_pixels = (int)std::min<long>((long)w->span * kBwdChunkPixels, 0x7fffffffL);   // (never below a span's live pixels)
     a.Kd = g.kdim; a.mtiles = w->mtiles;
     const dim3 grid((unsigned)live_splits, (unsigned)(d.group * w->mtiles), (unsigned)w->ktiles), block(kWgmThreads);
-    if (d.fuse_relu) hipLaunchKernelGGL(escoin_dense_wgrad_mfma_kernel<true>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(escoin_dense_wgrad_mfma_kernel<false>, grid, block, 0, stream, a);
-    ESCOIN_HIP_TRY(hipGetLastError());
+    // option "wgrad_math": a plan that asks for bf16 products runs wgrad_bf16.hip's kernel on these arguments
+    if (p->wgrad_math == ESCOIN_MATH_BF16) {
+      if (!g_wgb_hooks.dense) return fail(ESCOIN_EINVAL, "option \"wgrad_math\": this build does not carry the bf16 weight-gradient kernels");
+      w->math_last = ESCOIN_MATH_BF16;
+      w->lds_bytes = kWgbLdsBytes;
+      if (const int rc = g_wgb_hooks.dense(g, a, grid, stream, &w->variant_last)) return rc;
+    } else {
+      w->math_last = ESCOIN_MATH_FP32;
+      w->variant_last = 0;
+      w->lds_bytes = kWgmLdsBytes;
+      if (d.fuse_relu) hipLaunchKernelGGL(escoin_dense_wgrad_mfma_kernel<true>, grid, block, 0, stream, a);
+      else hipLaunchKernelGGL(escoin_dense_wgrad_mfma_kernel<false>, grid, block, 0, stream, a);
+      ESCOIN_HIP_TRY(hipGetLastError());
+    }
   }
   const unsigned blocks = (unsigned)((w->positions + kDwgSumThreads - 1) / kDwgSumThreads);
   hipLaunchKernelGGL(escoin_dense_wgrad_sum_kernel, dim3(blocks), dim3(kDwgSumThreads), 0, stream, w->part.get<const float>(), dense_diff,

@@ -151,6 +151,9 @@ long bwd_stat(const escoin_plan *p, const char *key) {
     if (s && s->wgrad == ESCOIN_WGRAD_DEPTHWISE) return (long)s->dww.plan.lds_bytes;
     return s && s->wgrad == ESCOIN_WGRAD_STAGED ? (long)s->stg.lds_bytes : 0;
   }
+  // (option "wgrad_math": what the last launch of the MFMA stage 1 ran, 0 before the first one)
+  if (!strcmp(key, "wgrad_math")) return s ? s->wgm.math_last : 0;
+  if (!strcmp(key, "wgrad_math_variant")) return s ? s->wgm.variant_last : 0;
   if (!strcmp(key, "wgrad_depthwise_slices")) return s && s->last_wgrad == ESCOIN_WGRAD_DEPTHWISE ? s->dww.last_slices : 0;
   if (!strcmp(key, "wgrad_depthwise_px")) return s && s->wgrad == ESCOIN_WGRAD_DEPTHWISE ? s->dww.plan.px : 0;
   if (!strcmp(key, "dgrad_lds_bytes"))
@@ -178,6 +181,8 @@ long dwg_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "dwg_device_bytes")) return (long)device_bytes(p).dwg;
   if (!strcmp(key, "dwg_splits")) return w ? w->splits : 0;
   if (!strcmp(key, "dwg_lds_bytes")) return w ? (long)w->lds_bytes : 0;
+  if (!strcmp(key, "dwg_math")) return w ? w->math_last : 0;
+  if (!strcmp(key, "dwg_math_variant")) return w ? w->variant_last : 0;
   if (!strcmp(key, "dwg_count")) return p->dwg_count;
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
@@ -229,6 +234,7 @@ int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, i
   if ((rc = escoin_plan_set_option(q, "dense_math", owner->dense_math)) != ESCOIN_OK) return rc;
   if (wgrad_options) {
     if ((rc = escoin_plan_set_option(q, "wgrad_kernel", owner->wgrad_kernel)) != ESCOIN_OK) return rc;
+    if ((rc = escoin_plan_set_option(q, "wgrad_math", owner->wgrad_math)) != ESCOIN_OK) return rc;
     if ((rc = escoin_plan_set_option(q, "wgrad_channel_block", owner->wgrad_channel_block)) != ESCOIN_OK) return rc;
     if ((rc = escoin_plan_set_option(q, "wgrad_pointwise", owner->wgrad_pointwise)) != ESCOIN_OK) return rc;
     if ((rc = escoin_plan_set_option(q, "wgrad_pointwise_tile_entries", owner->wgrad_pw_tile_entries)) != ESCOIN_OK) return rc;
@@ -364,6 +370,8 @@ int deconv_precheck(const escoin_plan *p, bool is_f64) {
   // (every align of either Dtype passes here first: option "dense_math" = bf16 set before a double align is refused by name too)
   if (is_f64 && p->dense_math == ESCOIN_MATH_BF16)
     return fail(ESCOIN_EINVAL, "dense_math = 1 (bf16) is for float plans: these weights are double");
+  if (is_f64 && p->wgrad_math == ESCOIN_MATH_BF16)     // (option "wgrad_math": likewise)
+    return fail(ESCOIN_EINVAL, "wgrad_math = 1 (bf16) is for float plans: these weights are double");
   if (!p->deconv) return ESCOIN_OK;
   D2sPlan dp;
   if (!d2s_plan(p->user_desc, is_f64, &dp)) return fail(ESCOIN_EINVAL, dp.error);
@@ -810,6 +818,18 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
         return fail(ESCOIN_EINVAL, "dense_math = 1 (bf16) is for float plans: this plan holds double weights");
       p->dense_math = value;
       if (p->inner_plan()) return escoin_plan_set_option(p->inner_plan()->plan.get(), key, value);
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "wgrad_math")) {
+      // (no state of its own either: read by every launch of the MFMA weight-gradient stage 1 and by every device call of
+      //  escoin_dense_wgrad, so it may change between backwards; handed on where "wgrad_kernel" is)
+      if (value != ESCOIN_MATH_FP32 && value != ESCOIN_MATH_BF16) return fail(ESCOIN_EINVAL, "wgrad_math must be 0 (fp32) or 1 (bf16)");
+      if (value == ESCOIN_MATH_BF16 && p->is_f64 && (p->aligned || p->host_aligned))
+        return fail(ESCOIN_EINVAL, "wgrad_math = 1 (bf16) is for float plans: this plan holds double weights");
+      p->wgrad_math = value;
+      if (p->b2s_state) return escoin_plan_set_option(p->b2s_state->inner.plan.get(), key, value);
+      if (p->w2b_state) return escoin_plan_set_option(p->w2b_state->inner.plan.get(), key, value);
+      if (p->d2s_state) return escoin_plan_set_option(p->d2s_state->inner.plan.get(), key, value);
       return ESCOIN_OK;
     }
     if (!strcmp(key, "b2s_block")) {

@@ -122,8 +122,11 @@ struct StagedWgrad {
 // The fp32-MFMA weight-gradient kernel (ESCOIN_WGRAD_MFMA; wgrad_mfma.hip; the tables: csr_tables.h wgrad_mfma_tables)
 struct WgmState {
   int mtiles = 0, ktiles = 0;  // tiles per conv group along the output channels / the columns
-  size_t lds_bytes = 0;
-  DeviceBuffer ent;   // [M * kdim] (row, column) -> CSR entry, -1: none
+  // what the last launch ran (option "wgrad_math"; stats "wgrad_lds_bytes", "wgrad_math", "wgrad_math_variant"): the LDS of
+  // its workgroup (before the first launch: the fp32 kernel's), ESCOIN_MATH_*, and the bf16 kernel's staging variant
+  mutable size_t lds_bytes = 0;
+  mutable int math_last = 0, variant_last = 0;
+  DeviceBuffer ent;  // [M * kdim] (row, column) -> CSR entry, -1: none
   DeviceBuffer cnt;   // [group * mtiles * ktiles] entries per tile
   DeviceBuffer ktab;  // [4 * ktiles * tile_k] the im2col decode of a column
   size_t bytes() const { return ent.bytes() + cnt.bytes() + ktab.bytes(); }
@@ -246,7 +249,9 @@ struct DenseWgradState {
   int mtiles = 0, ktiles = 0;          // tiles per conv group along the output channels / the columns
   int span = 0, splits = 0;            // chunks per split, splits of the full batch (align_rules.h dwg_plan)
   long positions = 0;                  // D = M * Cg * KH * KW
-  size_t lds_bytes = 0;
+  // what the last launch ran (option "wgrad_math"; stats "dwg_lds_bytes", "dwg_math", "dwg_math_variant"), as in WgmState
+  mutable size_t lds_bytes = 0;
+  mutable int math_last = 0, variant_last = 0;
   DeviceBuffer ktab;                   // [4 * ktiles * tile_k] the im2col decode of a column (csr_tables.h im2col_ktab)
   DeviceBuffer part;                   // [splits][D] partial sums
 };
@@ -390,6 +395,7 @@ struct escoin_plan {
   // the device side (free_device), so weight_align / set_csr / import_aligned drop it
   int bwd_kernel = ESCOIN_KERNEL_AUTO;
   int wgrad_kernel = ESCOIN_WGRAD_AUTO;   // option "wgrad_kernel"
+  int wgrad_math = ESCOIN_MATH_FP32;      // option "wgrad_math": ESCOIN_MATH_BF16 = the MFMA weight-gradient stage 1 and escoin_dense_wgrad run wgrad_bf16.hip's kernels
   int wgrad_channel_block = 0;            // option "wgrad_channel_block" (0: from the geometry and the LDS budget)
   int wgrad_pointwise = 0;                // option "wgrad_pointwise": AUTO runs the pointwise kernel where it serves the plan
   int wgrad_pw_tile_entries = 0;          // option "wgrad_pointwise_tile_entries" (test option; 0: the rule)

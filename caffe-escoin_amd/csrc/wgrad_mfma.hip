@@ -20,14 +20,7 @@
 
 namespace escoin {
 
-struct WgmArgs {
-  WgmIn in;                             // the blobs, the column decode, the geometry (wgrad_mfma_step.h)
-  const int *__restrict__ ent;          // [M][Kd]: CSR entry or -1
-  const int *__restrict__ tile_cnt;     // [group][mtiles][ktiles]
-  float *__restrict__ slab_w;           // [chunks][nnz]
-  int nnz;
-  int Kd, mtiles, ktiles;
-};
+WgbHooks g_wgb_hooks = {nullptr, nullptr};
 
 template <bool RELU>
 __global__ void __launch_bounds__(kWgmThreads)
@@ -84,6 +77,16 @@ int launch_wgrad_mfma(const escoin_plan *p, const WgmState &w, long nnz, const f
   a.in.pad_h = d.pad_h; a.in.pad_w = d.pad_w; a.in.stride_h = d.stride_h; a.in.stride_w = d.stride_w;
   a.in.Cg = g.Cg; a.in.Mg = g.Mg; a.Kd = g.kdim; a.mtiles = w.mtiles; a.ktiles = w.ktiles;
   const dim3 grid((unsigned)chunks, (unsigned)(d.group * w.mtiles), (unsigned)w.ktiles), block(kWgmThreads);
+  // option "wgrad_math": every stage-1 launch of a plan that asks for bf16 products is wgrad_bf16.hip's, on these arguments
+  if (p->wgrad_math == ESCOIN_MATH_BF16) {
+    if (!g_wgb_hooks.sparse) return fail(ESCOIN_EINVAL, "option \"wgrad_math\": this build does not carry the bf16 weight-gradient kernels");
+    w.math_last = ESCOIN_MATH_BF16;
+    w.lds_bytes = kWgbLdsBytes;
+    return g_wgb_hooks.sparse(g, a, grid, stream, &w.variant_last);
+  }
+  w.math_last = ESCOIN_MATH_FP32;
+  w.variant_last = 0;
+  w.lds_bytes = kWgmLdsBytes;
   if (d.fuse_relu) hipLaunchKernelGGL(escoin_sconv_wgrad_mfma_kernel<true>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(escoin_sconv_wgrad_mfma_kernel<false>, grid, block, 0, stream, a);
   ESCOIN_HIP_TRY(hipGetLastError());

@@ -49,6 +49,34 @@ struct WgmIn {
   int Cg, Mg;
 };
 
+// The argument blocks of the two kernels around the loop -- and of their bf16 twins (wgrad_bf16.hip), which read the same
+// tables, slabs and grids.
+struct WgmArgs {                        // wgrad_mfma.hip: grid (chunk, group * mtiles, ktiles)
+  WgmIn in;
+  const int *__restrict__ ent;          // [M][Kd]: CSR entry or -1
+  const int *__restrict__ tile_cnt;     // [group][mtiles][ktiles]
+  float *__restrict__ slab_w;           // [chunks][nnz]
+  int nnz;
+  int Kd, mtiles, ktiles;
+};
+struct DwgArgs {                        // dense_wgrad.hip: grid (split, group * mtiles, ktiles)
+  WgmIn in;
+  float *__restrict__ part;             // [splits][D]
+  long positions;                       // D
+  int span_pixels;                      // span * kBwdChunkPixels
+  int Kd, mtiles;
+};
+
+// wgrad_bf16.hip (plan option "wgrad_math" = ESCOIN_MATH_BF16): the launches the two fp32 launches hand over to, registered
+// when the library is loaded -- null in a program that links the core's objects alone, where the option is refused.  Each
+// picks its staging variant from the geometry's rule (align_rules.h wgb_plan) and the blob pointers' alignment, and
+// returns it in *variant: 1 (G by 16-byte loads) + 2 (the bottom by 16-byte loads).
+struct WgbHooks {
+  int (*sparse)(const Geometry &g, const WgmArgs &a, dim3 grid, hipStream_t stream, int *variant);
+  int (*dense)(const Geometry &g, const DwgArgs &a, dim3 grid, hipStream_t stream, int *variant);
+};
+extern WgbHooks g_wgb_hooks;            // wgrad_mfma.hip
+
 template <bool RELU>
 __device__ __forceinline__ wgm_f32x16 wgm_tile_sum(const WgmIn &a, float (*sG)[kWgmTileFloats], float (*sX)[kWgmTileFloats],
                                                    int grp, int m0, int k0, long q0, int live) {

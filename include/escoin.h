@@ -180,7 +180,39 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  prune / rewire need nothing more) and may be set at any time, also between forwards of an aligned
  *                  plan.  Launches run whole tiles: stat "streamk" reads 0 under it.  A double plan refuses value 1 by
  *                  name (at set_option when it is aligned, else at the double align); CPU mode, the sparse kernels and the
- *                  backward's MFMA kernels ignore it.  Measured against the fp32 kernel in profiles/dense_bf16_mi355x.md;
+ *                  backward's MFMA kernels ignore it (the weight gradient has an option of its own, "wgrad_math" below; the MFMA
+ *                  data gradient has none).  Measured against the fp32 kernel in profiles/dense_bf16_mi355x.md;
+ *   "wgrad_math" = ESCOIN_MATH_FP32 (0, default) / ESCOIN_MATH_BF16 (1); any other value is ESCOIN_EINVAL.  With 1 on a float
+ *                  plan, every launch of the MFMA weight-gradient stage 1 ("wgrad_kernel" = ESCOIN_WGRAD_MFMA, also on the
+ *                  inner plans of "b2s" / "w2b" / "deconv", to which the option is handed on wherever "wgrad_kernel" is) runs
+ *                  escoin_sconv_wgrad_bf16_kernel, and every device call of escoin_dense_wgrad runs
+ *                  escoin_dense_wgrad_bf16_kernel (csrc/wgrad_bf16.hip; the blobs stay fp32).  The contract:
+ *                  - every written element is the fp32-accumulated sum over the pixels of bf16_rne(G) * bf16_rne(X), G =
+ *                    top_diff masked by top > 0 BEFORE the rounding on fuse_relu plans (products of two bf16 values are
+ *                    exact in fp32);
+ *                  - the order of the sum -- steps of 64 pixels ascending from the chunk's (span's) start, within a step
+ *                    the matrix instructions' own fixed order -- is a function of the geometry and n_images only (for
+ *                    escoin_dense_wgrad also of the CU count and "dense_wgrad_splits"): deterministic, no atomics, one
+ *                    writer per slab element; independent of "tiling_batch", the stream and of whether the operands were
+ *                    staged by 16-byte or by 4-byte loads (16-byte loads need OH*OW % 4 == 0 and 16-byte aligned blob
+ *                    pointers; for the bottom also a 1x1, stride-1, pad-0 layer); the compact form equals the dense form
+ *                    gathered, bit for bit;
+ *                  - element-wise, the distance to the exact result of the UNROUNDED operands is at most (2^-8 + 2^-18) *
+ *                    sum |g| |x| plus the fp32 accumulation bound; an operand above bf16's largest finite value rounds to
+ *                    infinity, a NaN stays a NaN;
+ *                  - the bias gradient does not pass through these kernels and keeps its bits;
+ *                  - zeros are staged by select: a non-finite bottom element reaches only the entries whose tap reads it, a
+ *                    non-finite G only its own row.
+ *                  Nothing turns the option on by itself and it changes no decision: ESCOIN_WGRAD_AUTO, "wgrad_pointwise",
+ *                  "wgrad_depthwise", the data gradient, the forward and CPU mode are as without it, and a plan whose weight
+ *                  gradient runs another kernel ignores it.  It holds no state (the kernels read the fp32 kernels' tables,
+ *                  slab, chunks and grid) and may be set at any time, also between backwards of an aligned plan.  A double
+ *                  plan refuses value 1 by name (at set_option when it is aligned, else at the double align).  Stats:
+ *                  "wgrad_math" / "dwg_math" (what the last MFMA stage-1 launch / the last escoin_dense_wgrad ran; 0 before
+ *                  the first), "wgrad_math_variant" / "dwg_math_variant" (the bf16 launch's staging: 1 = G by 16-byte loads,
+ *                  + 2 = the bottom too; 0 under fp32), and "wgrad_lds_bytes" / "dwg_lds_bytes" report the kernel that ran.
+ *                  Faster than the fp32 kernel on stride-1 pointwise and 3x3 layers whose OH*OW is a multiple of 4, SLOWER
+ *                  on stride-2 pointwise layers: profiles/wgrad_bf16_mi355x.md;
  *   "tiling_batch" = choose the tiled kernel's tiling as for a batch of this many images
  *                  (0 = desc.N).  Results do not depend on it; tests use it to run small inputs
  *                  through the weight stream / tile shapes of the full-size configurations;

@@ -90,6 +90,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--prev-pkg", default="", help="another checkout's caffe-escoin_amd directory (built): route B on its library too")
     ap.add_argument("--splits", type=int, default=0, help="option dense_wgrad_splits of route A's plan (0: the rule)")
+    ap.add_argument("--wgrad-math", action="store_true", help="route A also with plan option wgrad_math = 1 (bf16), in the same rounds")
     ap.add_argument("--markdown", default="")
     a = ap.parse_args()
     if a.regions < 5:
@@ -128,6 +129,14 @@ def main():
         diff = float((score - wd).abs().max() / wd.abs().max().clamp_min(1e-30))
         fns = {"A": lambda: plan.dense_wgrad(td, x, out=score),
                "B": lambda: shadow.backward(td, bottom=x, bottom_diff=None, weight_diff=wd)}
+        if a.wgrad_math:
+            # route A again with plan option "wgrad_math" = bf16 on the same plan (escoin_dense_wgrad_bf16_kernel): a member of
+            # every round; the option is back at 0 when route A's next region starts
+            def a16():
+                plan.set_option("wgrad_math", 1)
+                plan.dense_wgrad(td, x, out=score)
+                plan.set_option("wgrad_math", 0)
+            fns["A16"] = a16
         shadow_prev = None
         if prev is not None:
             shadow_prev = shadow_plan(prev, s)
@@ -144,6 +153,12 @@ def main():
                  a_dense_tflops=round(2.0 * s.N * oh * ow * s.M * kdim / (med["A"] * 1e-6) / 1e12, 2),
                  dwg_device_bytes=plan.stat("dwg_device_bytes"), shadow_workspace_bytes=shadow.workspace_bytes,
                  plan_workspace_growth=plan.workspace_bytes - ws_before, max_rel_diff=diff)
+        if a.wgrad_math:
+            r.update(a16_us=med["A16"], a16_spread_us=[t["A16"][0], t["A16"][-1]], a16_over_a=round(med["A16"] / med["A"], 3),
+                     a16_variant=plan.stat("dwg_math_variant"),
+                     a16_dense_tflops=round(2.0 * s.N * oh * ow * s.M * kdim / (med["A16"] * 1e-6) / 1e12, 2))
+            print("%-26s A bf16 %8.1f us (%.1f .. %.1f)  x%.3f of A  variant %d  %.1f TFLOP/s" % (
+                s.name, r["a16_us"], t["A16"][0], t["A16"][-1], r["a16_over_a"], r["a16_variant"], r["a16_dense_tflops"]), file=sys.stderr, flush=True)
         if shadow_prev is not None:
             r.update(b_prev_us=med["B_prev"], b_prev_spread_us=[t["B_prev"][0], t["B_prev"][-1]],
                      a_over_b_prev=round(med["A"] / med["B_prev"], 3), b_over_b_prev=round(med["B"] / med["B_prev"], 3))
