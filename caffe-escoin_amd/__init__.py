@@ -30,7 +30,8 @@ BWD_MFMA = 5   # option "backward_kernel" / stat "bwd_data_kernel": the fp32-MFM
 BWD_DEPTHWISE = 6   # stat "bwd_data_kernel" only: the depthwise data-gradient kernel of Plan(..., depthwise=1)
 MATH_FP32, MATH_BF16 = 0, 1   # option / stat "dense_math": Plan(..., dense_math=MATH_BF16) runs dense launches on the bf16 matrix cores;
 #                               option / stats "wgrad_math", "dwg_math": Plan(..., wgrad_math=MATH_BF16) does so for the MFMA weight gradient
-#                               (wgrad_kernel=WGRAD_MFMA) and for dense_wgrad
+#                               (wgrad_kernel=WGRAD_MFMA) and for dense_wgrad; option / stat "dgrad_math": Plan(..., dgrad_math=MATH_BF16)
+#                               does so for the MFMA data gradient (backward_kernel=BWD_MFMA)
 CONV_MODE_LOWERED_GEMM, CONV_MODE_LOWERED_SPARSE, CONV_MODE_SCONV, CONV_MODE_SCONV_PAR = 0, 1, 2, 3
 
 # every symbol include/escoin.h declares (tests check the library exports all of them)

@@ -137,10 +137,14 @@ class Caffe {
   // multiply (include/escoin.h option "wgrad_math")
   static int wgrad_math() { return Get().wgrad_math_; }
   static void set_wgrad_math(int math) { Get().wgrad_math_ = math; }
+  // likewise how the MFMA data-gradient kernel (backward_kernel = ESCOIN_BWD_MFMA) multiplies (include/escoin.h option
+  // "dgrad_math")
+  static int dgrad_math() { return Get().dgrad_math_; }
+  static void set_dgrad_math(int math) { Get().dgrad_math_ = math; }
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), w2b_(false), wgrad_pointwise_(false), depthwise_(false), wgrad_depthwise_(false), dense_math_(ESCOIN_MATH_FP32), wgrad_math_(ESCOIN_MATH_FP32) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), w2b_(false), wgrad_pointwise_(false), depthwise_(false), wgrad_depthwise_(false), dense_math_(ESCOIN_MATH_FP32), wgrad_math_(ESCOIN_MATH_FP32), dgrad_math_(ESCOIN_MATH_FP32) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
@@ -155,6 +159,7 @@ class Caffe {
   bool wgrad_depthwise_;
   int dense_math_;
   int wgrad_math_;
+  int dgrad_math_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -487,6 +492,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_depthwise", Caffe::wgrad_depthwise() ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "dense_math", sizeof(Dtype) == 4 ? Caffe::dense_math() : ESCOIN_MATH_FP32));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_math", sizeof(Dtype) == 4 ? Caffe::wgrad_math() : ESCOIN_MATH_FP32));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "dgrad_math", sizeof(Dtype) == 4 ? Caffe::dgrad_math() : ESCOIN_MATH_FP32));
       if (plan_) escoin_plan_destroy(plan_);
       plan_ = fresh;
       desc_ = d;

@@ -802,6 +802,14 @@ bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp) {
   return true;
 }
 
+bool dgb_plan(const Geometry &g, bool is_f64, DgmPlan *dp) {
+  DgmPlan p;
+  if (!dgm_plan(g, is_f64, &p)) return false;
+  p.lds_bytes = kDgbLdsBytes;
+  *dp = p;
+  return true;
+}
+
 bool dw_plan(const Geometry &g, bool is_f64, int band_rows, int n_cu, DwPlan *dp) {
   const escoin_conv_desc &d = g.d;
   if (is_f64 || g.Cg != 1) return false;

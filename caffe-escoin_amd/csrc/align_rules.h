@@ -383,6 +383,16 @@ struct DgmPlan {
 // 65535 (group, channel tile) pairs: the grid's y and z; fewer than 2^31 (group, phase, channel tile) triples).
 bool dgm_plan(const Geometry &g, bool is_f64, DgmPlan *dp);
 
+// ---- the bf16 math mode of the MFMA data-gradient kernel (dgrad_bf16.hip, plan option "dgrad_math" = ESCOIN_MATH_BF16) --
+// The fp32 kernel's phases, tiles, tables, live steps and grid (dgm_plan's predicate is this mode's: float plans only); two
+// live steps go through LDS per barrier as bf16, k-contiguous: 2 buffers x (weight tile, G tile) x 64 rows x kDgbStepK
+// columns x 2 bytes, no padding (the rows are swizzled, dgrad_bf16.hip).
+constexpr int kDgbStepK = 2 * kDgmStepK;             // columns per barrier: 4 k-steps of v_mfma_f32_32x32x16_bf16
+constexpr size_t kDgbLdsBytes = 2 * 2 * 2 * (size_t)kDgmTileC * kDgbStepK;
+static_assert(kDgbLdsBytes <= kDgmLdsBudget, "the bf16 data-gradient tiles exceed their LDS budget");
+// dgm_plan's tile plan with lds_bytes = kDgbLdsBytes.
+bool dgb_plan(const Geometry &g, bool is_f64, DgmPlan *dp);
+
 // ---- the depthwise kernel pair (depthwise.hip, plan option "depthwise") ----------------------------------------------
 // Layers with one input channel per conv group (Cg == 1; Mg is the channel multiplier).  A workgroup has kDwWaves waves and
 // every wave takes a work unit of its own -- forward: (image, conv group, band of output rows); data gradient: (image,

@@ -50,20 +50,7 @@ constexpr int kDgmTileFloats = kDgmStepK * kDgmLdsRow;
 static_assert(kDgmTileC == 64 && kDgmTileP == 64 && kDgmStepK == 32, "the wave layout below is 2 x 2 blocks of 32 x 32");
 static_assert(sizeof(float) * 4 * kDgmTileFloats == kDgmLdsBytes, "align_rules.h reports this kernel's LDS");
 
-struct DgmArgs {
-  const float *__restrict__ top_diff;
-  const float *__restrict__ top;        // fuse_relu only
-  float *__restrict__ bottom_diff;
-  const float *__restrict__ mat;        // the phase matrices
-  const int4 *__restrict__ col;         // [cols_total]: {G offset of ocl, dh, dw, valid}
-  const int *__restrict__ phase;        // [phases][8]: {h0, w0, rows, cols, kp, ksteps, col0, ntaps}
-  const int *__restrict__ live_ptr;     // [group * phases * ctiles + 1]
-  const int *__restrict__ live;
-  int n_images;
-  int C, H, W, M, OH, OW;
-  int stride_h, stride_w;
-  int Cg, Mg, ctiles, phases, cols_total;
-};
+DgradBf16Launch g_dgrad_bf16_launch = nullptr;
 
 template <bool RELU>
 __global__ void __launch_bounds__(kDgmThreads)
@@ -196,6 +183,15 @@ int launch_dgrad_mfma(const escoin_plan *p, const DgmState &m, const float *top,
   a.stride_h = d.stride_h; a.stride_w = d.stride_w;
   a.Cg = g.Cg; a.Mg = g.Mg; a.ctiles = m.ctiles; a.phases = m.phases; a.cols_total = m.cols_total;
   const dim3 grid((unsigned)tiles, (unsigned)m.phases, (unsigned)(d.group * m.ctiles)), block(kDgmThreads);
+  // option "dgrad_math": every launch of a plan that asks for bf16 products is dgrad_bf16.hip's, on these arguments
+  if (p->dgrad_math == ESCOIN_MATH_BF16) {
+    if (!g_dgrad_bf16_launch) return fail(ESCOIN_EINVAL, "option \"dgrad_math\": this build does not carry the bf16 data-gradient kernel");
+    m.math_last = ESCOIN_MATH_BF16;
+    m.lds_bytes = kDgbLdsBytes;
+    return g_dgrad_bf16_launch(a, grid, d.fuse_relu != 0, stream);
+  }
+  m.math_last = ESCOIN_MATH_FP32;
+  m.lds_bytes = kDgmLdsBytes;
   if (d.fuse_relu) hipLaunchKernelGGL(escoin_sconv_dgrad_mfma_kernel<true>, grid, block, 0, stream, a);
   else hipLaunchKernelGGL(escoin_sconv_dgrad_mfma_kernel<false>, grid, block, 0, stream, a);
   ESCOIN_HIP_TRY(hipGetLastError());

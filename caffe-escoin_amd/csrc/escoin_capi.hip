@@ -158,6 +158,11 @@ long bwd_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "wgrad_depthwise_px")) return s && s->wgrad == ESCOIN_WGRAD_DEPTHWISE ? s->dww.plan.px : 0;
   if (!strcmp(key, "dgrad_lds_bytes"))
     return s && s->data == kBwdMfma ? (long)s->dgm.lds_bytes : s && s->data == kBwdDepthwise ? (long)s->dw.dlds_bytes : 0;
+  // (option "dgrad_math": what the last launch of the MFMA data-gradient kernel ran, 0 before the first one)
+  if (!strcmp(key, "dgrad_math")) {
+    if (s && s->data == kBwdInner) return bwd_stat(p->inner_plan()->plan.get(), key);
+    return s && s->data == kBwdMfma ? s->dgm.math_last : 0;
+  }
   if (!strcmp(key, "bwd_align_us")) return s ? (long)(s->align_ms * 1e3) : 0;
   return fail(ESCOIN_EINVAL, std::string("unknown stat: ") + key);
 }
@@ -232,6 +237,7 @@ int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, i
   if ((rc = escoin_plan_set_option(q, "dense_gate", owner->dense_gate)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "code_loader", owner->code_loader)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "dense_math", owner->dense_math)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "dgrad_math", owner->dgrad_math)) != ESCOIN_OK) return rc;
   if (wgrad_options) {
     if ((rc = escoin_plan_set_option(q, "wgrad_kernel", owner->wgrad_kernel)) != ESCOIN_OK) return rc;
     if ((rc = escoin_plan_set_option(q, "wgrad_math", owner->wgrad_math)) != ESCOIN_OK) return rc;
@@ -372,6 +378,8 @@ int deconv_precheck(const escoin_plan *p, bool is_f64) {
     return fail(ESCOIN_EINVAL, "dense_math = 1 (bf16) is for float plans: these weights are double");
   if (is_f64 && p->wgrad_math == ESCOIN_MATH_BF16)     // (option "wgrad_math": likewise)
     return fail(ESCOIN_EINVAL, "wgrad_math = 1 (bf16) is for float plans: these weights are double");
+  if (is_f64 && p->dgrad_math == ESCOIN_MATH_BF16)     // (option "dgrad_math": likewise)
+    return fail(ESCOIN_EINVAL, "dgrad_math = 1 (bf16) is for float plans: these weights are double");
   if (!p->deconv) return ESCOIN_OK;
   D2sPlan dp;
   if (!d2s_plan(p->user_desc, is_f64, &dp)) return fail(ESCOIN_EINVAL, dp.error);
@@ -817,6 +825,16 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       if (value == ESCOIN_MATH_BF16 && p->is_f64 && (p->aligned || p->host_aligned))
         return fail(ESCOIN_EINVAL, "dense_math = 1 (bf16) is for float plans: this plan holds double weights");
       p->dense_math = value;
+      if (p->inner_plan()) return escoin_plan_set_option(p->inner_plan()->plan.get(), key, value);
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "dgrad_math")) {
+      // (no state of its own either: read by every launch of the MFMA data-gradient kernel, so it may change between
+      //  backwards; handed on like "dense_math")
+      if (value != ESCOIN_MATH_FP32 && value != ESCOIN_MATH_BF16) return fail(ESCOIN_EINVAL, "dgrad_math must be 0 (fp32) or 1 (bf16)");
+      if (value == ESCOIN_MATH_BF16 && p->is_f64 && (p->aligned || p->host_aligned))
+        return fail(ESCOIN_EINVAL, "dgrad_math = 1 (bf16) is for float plans: this plan holds double weights");
+      p->dgrad_math = value;
       if (p->inner_plan()) return escoin_plan_set_option(p->inner_plan()->plan.get(), key, value);
       return ESCOIN_OK;
     }

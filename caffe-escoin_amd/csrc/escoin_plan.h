@@ -158,7 +158,10 @@ struct DwWgrad {
 // The fp32-MFMA data-gradient kernel (kBwdMfma; dgrad_mfma.hip; the tables: csr_tables.h dgrad_mfma_tables)
 struct DgmState {
   int phases = 0, ctiles = 0, cols_total = 0;
-  size_t lds_bytes = 0;
+  // what the last launch ran (option "dgrad_math"; stats "dgrad_lds_bytes", "dgrad_math"): the LDS of its workgroup (before
+  // the first launch: the fp32 kernel's) and ESCOIN_MATH_*
+  mutable size_t lds_bytes = 0;
+  mutable int math_last = 0;
   DeviceBuffer mat;    // the phase matrices: the weights transposed, columns permuted by phase, zero outside the pattern
   DeviceBuffer phase;  // [phases][8] a phase's pixels, columns and place in col / mat
   DeviceBuffer col;    // [4 * cols_total] the decode of a column: {G offset of ocl, dh, dw, valid}
@@ -394,6 +397,7 @@ struct escoin_plan {
   // Backward (sconv_backward.hip): option "backward_kernel" and the state the first escoin_backward builds; reset with
   // the device side (free_device), so weight_align / set_csr / import_aligned drop it
   int bwd_kernel = ESCOIN_KERNEL_AUTO;
+  int dgrad_math = ESCOIN_MATH_FP32;      // option "dgrad_math": ESCOIN_MATH_BF16 = every launch of the MFMA data-gradient kernel runs dgrad_bf16.hip's kernel
   int wgrad_kernel = ESCOIN_WGRAD_AUTO;   // option "wgrad_kernel"
   int wgrad_math = ESCOIN_MATH_FP32;      // option "wgrad_math": ESCOIN_MATH_BF16 = the MFMA weight-gradient stage 1 and escoin_dense_wgrad run wgrad_bf16.hip's kernels
   int wgrad_channel_block = 0;            // option "wgrad_channel_block" (0: from the geometry and the LDS budget)
@@ -599,6 +603,27 @@ extern DwHooks g_dw_hooks;   // escoin_capi.hip
 int dgm_build(const escoin_plan *p, const DgmPlan &dp, DgmState *m, hipStream_t stream);
 int launch_dgrad_mfma(const escoin_plan *p, const DgmState &m, const float *top, const float *top_diff,
                       float *bottom_diff, int n_images, hipStream_t stream);
+// The argument block of the kernel -- and of its bf16 twin (dgrad_bf16.hip), which reads the same tables on the same grid
+// (longest phase's pixel tiles, phases, group * ctiles).
+struct DgmArgs {
+  const float *__restrict__ top_diff;
+  const float *__restrict__ top;        // fuse_relu only
+  float *__restrict__ bottom_diff;
+  const float *__restrict__ mat;        // the phase matrices
+  const int4 *__restrict__ col;         // [cols_total]: {G offset of ocl, dh, dw, valid}
+  const int *__restrict__ phase;        // [phases][8]: {h0, w0, rows, cols, kp, ksteps, col0, ntaps}
+  const int *__restrict__ live_ptr;     // [group * phases * ctiles + 1]
+  const int *__restrict__ live;
+  int n_images;
+  int C, H, W, M, OH, OW;
+  int stride_h, stride_w;
+  int Cg, Mg, ctiles, phases, cols_total;
+};
+// dgrad_bf16.hip (option "dgrad_math" = ESCOIN_MATH_BF16): the launch launch_dgrad_mfma hands its filled arguments and grid
+// to, registered when the library is loaded like g_dense_bf16_launch above -- null in a program that links the core's
+// objects alone, where the option is refused
+typedef int (*DgradBf16Launch)(const DgmArgs &a, dim3 grid, bool relu, hipStream_t stream);
+extern DgradBf16Launch g_dgrad_bf16_launch;   // dgrad_mfma.hip
 
 // s2d.hip (option "s2d"): X' of the first n_images images from the bottom blob (pack), bottom_diff of the first n_images
 // images from dX' (unpack), and the pack kernel's name.  s2d.hip registers them when the library is loaded; the plan's core

@@ -180,8 +180,8 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  prune / rewire need nothing more) and may be set at any time, also between forwards of an aligned
  *                  plan.  Launches run whole tiles: stat "streamk" reads 0 under it.  A double plan refuses value 1 by
  *                  name (at set_option when it is aligned, else at the double align); CPU mode, the sparse kernels and the
- *                  backward's MFMA kernels ignore it (the weight gradient has an option of its own, "wgrad_math" below; the MFMA
- *                  data gradient has none).  Measured against the fp32 kernel in profiles/dense_bf16_mi355x.md;
+ *                  backward's MFMA kernels ignore it (the weight gradient and the MFMA data gradient have options of their
+ *                  own, "wgrad_math" and "dgrad_math" below).  Measured against the fp32 kernel in profiles/dense_bf16_mi355x.md;
  *   "wgrad_math" = ESCOIN_MATH_FP32 (0, default) / ESCOIN_MATH_BF16 (1); any other value is ESCOIN_EINVAL.  With 1 on a float
  *                  plan, every launch of the MFMA weight-gradient stage 1 ("wgrad_kernel" = ESCOIN_WGRAD_MFMA, also on the
  *                  inner plans of "b2s" / "w2b" / "deconv", to which the option is handed on wherever "wgrad_kernel" is) runs
@@ -213,6 +213,35 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  + 2 = the bottom too; 0 under fp32), and "wgrad_lds_bytes" / "dwg_lds_bytes" report the kernel that ran.
  *                  Faster than the fp32 kernel on stride-1 pointwise and 3x3 layers whose OH*OW is a multiple of 4, SLOWER
  *                  on stride-2 pointwise layers: profiles/wgrad_bf16_mi355x.md;
+ *   "dgrad_math" = ESCOIN_MATH_FP32 (0, default) / ESCOIN_MATH_BF16 (1); any other value is ESCOIN_EINVAL.  With 1 on a float
+ *                  plan, every launch that would run escoin_sconv_dgrad_mfma_kernel ("backward_kernel" = ESCOIN_BWD_MFMA:
+ *                  the layers without a transposed plan, the outer data gradient of "s2d" / "s2b" plans, and inner plans
+ *                  that receive ESCOIN_BWD_MFMA, to which the option is handed on like "dense_math") runs
+ *                  escoin_sconv_dgrad_bf16_kernel (csrc/dgrad_bf16.hip; the blobs stay fp32).  The contract:
+ *                  - every bottom_diff element is the fp32-accumulated sum over the columns (ocl, tap) of its phase's live
+ *                    steps of bf16_rne(W) * bf16_rne(G), G = top_diff masked by top > 0 BEFORE the rounding on fuse_relu
+ *                    plans (products of two bf16 values are exact in fp32);
+ *                  - the order of the sum -- live steps of 32 columns ascending, within a step its two matrix
+ *                    instructions ascending, within an instruction its own fixed order over its 16 columns -- is a
+ *                    function of the geometry and the pattern only: not of n_images, of the image's place in the batch, of
+ *                    the stream or of the blobs' alignment;
+ *                  - element-wise, the distance to the exact gradient of the UNROUNDED operands is at most (2^-8 + 2^-18) *
+ *                    sum |w| |g| plus the fp32 accumulation bound; an operand above bf16's largest finite value rounds to
+ *                    infinity, a NaN stays a NaN;
+ *                  - the fp32 kernel's non-finite property carries over: a pruned position inside a live step contributes
+ *                    0 x bf16(G), so a non-finite G gives NaN there; zeros are staged by select otherwise;
+ *                  - images at or past n_images are not touched.
+ *                  Nothing turns the option on by itself and it changes no decision: ESCOIN_KERNEL_AUTO, the backward's
+ *                  rules, the weight gradient, the forward and CPU mode are as without it, and a plan whose data gradient
+ *                  runs another kernel ignores it.  It holds no state (the kernel reads the fp32 kernel's phase matrix and
+ *                  tables on its grid, so updates, the solver step, prune, rewire and set_csr need nothing more) and may be
+ *                  set at any time, also between backwards of an aligned plan.  A double plan refuses value 1 by name (at
+ *                  set_option when it is aligned, else at the double align).  Stats: "dgrad_math" (what the last launch of
+ *                  the MFMA data gradient ran; 0 before the first) and "dgrad_lds_bytes" (the LDS of the kernel that ran).
+ *                  Measured against the fp32 kernel in same-call pairs (profiles/dgrad_bf16_mi355x.md, batch 256): 0.45-0.57x
+ *                  its time on 3x3 stride-2 layers, 0.42x on the two conv1 layers, 0.60-0.96x on stride-2 pointwise layers
+ *                  with 256 or more output channels, and a TIE (0.99x) on the store-bound 256 @ 56 x 56 -> 128 one; no layer of
+ *                  that set loses, but the rounding is not free either: choose it per layer;
  *   "tiling_batch" = choose the tiled kernel's tiling as for a batch of this many images
  *                  (0 = desc.N).  Results do not depend on it; tests use it to run small inputs
  *                  through the weight stream / tile shapes of the full-size configurations;

@@ -16,9 +16,11 @@ stride-2 pad-1 shapes 128 @ 56, 256 @ 28 and 512 @ 14 (ResNet-50 v1.5) @90 % (ba
 name contains one of the given substrings.  Times are device
 events around `--reps` back-to-back calls after a warm-up, the median of `--regions` regions, per call.  Prints one JSON line (and progress on stderr).
 --wgrad-math measures one thing instead: the MFMA weight gradient with plan option "wgrad_math" at 0 and at 1 (bf16) in
-alternating regions of one plan per layer (profiles/wgrad_bf16_mi355x.md).
+alternating regions of one plan per layer (profiles/wgrad_bf16_mi355x.md).  --dgrad-math likewise: the MFMA data gradient
+(backward_kernel = BWD_MFMA) of the chosen sets' layers that have no transposed plan, with plan option "dgrad_math" at 0 and
+at 1 (profiles/dgrad_bf16_mi355x.md).
 
-    python tools/backward_bench.py [--sets resnet,googlenet,alexnet,chain,sweep,strided] [--only a,b] [--regions 7] [--reps 5] [--no-torch] [--wgrad-math]
+    python tools/backward_bench.py [--sets resnet,googlenet,alexnet,chain,sweep,strided] [--only a,b] [--regions 7] [--reps 5] [--no-torch] [--wgrad-math | --dgrad-math]
 """
 import argparse
 import json
@@ -154,8 +156,66 @@ def wgrad_math_row(pkg, synth, s, i, a, dev):
     return r
 
 
+def dgrad_math_row(pkg, synth, s, i, a, dev):
+    """--dgrad-math: the data gradient of ONE plan forced to backward_kernel = BWD_MFMA with option "dgrad_math" at 0 (the
+    fp32 kernel, untouched) and 1 (bf16) in alternating regions of `--reps` calls: per side the median and min .. max of
+    `--regions` regions and the LDS bytes of its workgroup, and torch's dense data gradient beside them."""
+    import torch
+    w = synth.pruned_weights(s, 1000 + i)
+    plan = pkg.Plan(pkg.ConvDesc.from_shape(s), backward_kernel=pkg.BWD_MFMA)
+    plan.weight_align(w)
+    oh, ow = plan.out_hw
+    td = torch.empty((s.N, s.M, oh, ow), device=dev).uniform_(-1, 1)
+    bd = torch.empty((s.N, s.C, s.H, s.W), device=dev)
+
+    def call():
+        plan.backward(td, bottom_diff=bd)
+    times, lds = {0: [], 1: []}, {}
+    for math in (0, 1):                                    # warm-up of both kernels
+        plan.set_option("dgrad_math", math)
+        call()
+        assert plan.stat("bwd_data_kernel") == pkg.BWD_MFMA and plan.stat("dgrad_math") == math
+        lds[math] = plan.stat("dgrad_lds_bytes")
+    torch.cuda.synchronize()
+    for _ in range(a.regions):
+        for math in (0, 1):
+            plan.set_option("dgrad_math", math)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.reps):
+                call()
+            e1.record()
+            e1.synchronize()
+            times[math].append(e0.elapsed_time(e1) * 1e3 / a.reps)
+    flop = 2.0 * s.N * oh * ow * s.M * (s.C // s.group) * s.KH * s.KW
+    r = dict(layer=s.name, N=s.N, density=round(float((w != 0).mean()), 4))
+    for math, key in ((0, "fp32"), (1, "bf16")):
+        t = sorted(times[math])
+        r[key + "_us"], r[key + "_spread_us"], r[key + "_lds_bytes"] = t[len(t) // 2], [t[0], t[-1]], lds[math]
+        r[key + "_dense_tflops"] = round(flop / (r[key + "_us"] * 1e-6) / 1e12, 2)
+    r["bf16_over_fp32"] = round(r["bf16_us"] / r["fp32_us"], 3)
+    # beyond the same-call spread: the slower side's fastest region against the faster side's slowest
+    r["verdict"] = ("bf16 faster" if r["bf16_spread_us"][1] < r["fp32_spread_us"][0] else
+                    "bf16 SLOWER" if r["bf16_spread_us"][0] > r["fp32_spread_us"][1] else "within spread")
+    if not a.no_torch:
+        wdense = torch.from_numpy(w).to(dev)
+        x = torch.empty((s.N, s.C, s.H, s.W), device=dev)
+        args = ([s.stride_h, s.stride_w], [s.pad_h, s.pad_w], [s.dil_h, s.dil_w], False, [0, 0], s.group)
+        r["torch_data_us"] = timed(lambda: torch.ops.aten.convolution_backward(td, x, wdense, None, *args, [True, False, False]),
+                                   a.regions, a.reps)
+    plan.close()
+    print("%-28s dgrad fp32 %8.1f (%.1f .. %.1f)  bf16 %8.1f (%.1f .. %.1f) us  x%.3f  %5.1f -> %5.1f TFLOP/s  %s%s" % (
+        s.name, r["fp32_us"], r["fp32_spread_us"][0], r["fp32_spread_us"][1], r["bf16_us"], r["bf16_spread_us"][0],
+        r["bf16_spread_us"][1], r["bf16_over_fp32"], r["fp32_dense_tflops"], r["bf16_dense_tflops"], r["verdict"],
+        "" if a.no_torch else "  torch %8.1f" % r["torch_data_us"]), file=sys.stderr, flush=True)
+    return r
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dgrad-math", action="store_true",
+                    help="only the MFMA data gradient of the layers without a transposed plan, option dgrad_math 0 against 1 in "
+                         "alternating regions of one plan")
     ap.add_argument("--wgrad-math", action="store_true",
                     help="only the MFMA weight gradient, option wgrad_math 0 against 1 in alternating regions of one plan")
     ap.add_argument("--sets", default="resnet,googlenet,alexnet")
@@ -188,6 +248,11 @@ def main():
     if a.wgrad_math:
         rows = [wgrad_math_row(pkg, synth, s, i, a, dev) for i, s in enumerate(layers)]
         print(json.dumps(dict(tool="backward_bench --wgrad-math", device=torch.cuda.get_device_name(0), layers=rows)))
+        return
+    if a.dgrad_math:
+        layers = [s for s in layers if max(s.stride_h, s.stride_w) > 1 or s.pad_h > s.dil_h * (s.KH - 1) or s.pad_w > s.dil_w * (s.KW - 1)]
+        rows = [dgrad_math_row(pkg, synth, s, i, a, dev) for i, s in enumerate(layers)]
+        print(json.dumps(dict(tool="backward_bench --dgrad-math", device=torch.cuda.get_device_name(0), layers=rows)))
         return
     for i, s in enumerate(layers):
         w = synth.pruned_weights(s, 1000 + i)
