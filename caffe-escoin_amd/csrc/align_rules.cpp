@@ -301,6 +301,17 @@ LaunchVerdict db16_plan(const Geometry &g, bool is_f64, int n_images, int groups
   return LaunchVerdict();
 }
 
+LaunchVerdict sp24_plan(const Geometry &g, bool is_f64, int n_images, int groups, int n_cu, Sp24Plan *sp) {
+  if (is_f64) return refuse_launch(ESCOIN_ESTATE, "sp24 = 1: the plan holds double weights");
+  Sp24Plan p;
+  if (const LaunchVerdict v = db16_plan(g, false, n_images, groups, n_cu, &p.t); !v.ok()) return v;
+  p.idx_rows = g.d.M + 128;
+  p.idx_row_words = (g.kdim + 31) / 32 * 2;
+  p.idx_bytes = (unsigned long long)p.idx_rows * p.idx_row_words * 2;
+  *sp = p;
+  return LaunchVerdict();
+}
+
 LaunchVerdict grid_yz_limit(GridKernel k, unsigned long grid_y, unsigned long grid_z) {
   if (grid_y <= kGridYZMax && (grid_z <= kGridYZMax || k == kGridCsrmmF64)) return LaunchVerdict();
   switch (k) {

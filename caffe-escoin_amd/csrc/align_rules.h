@@ -137,6 +137,18 @@ struct Db16Plan {
   unsigned long long in_bytes = 0, w_bytes = 0;     // the descriptors' ranges: the launch's bottom, the padded weight matrix
 };
 LaunchVerdict db16_plan(const Geometry &g, bool is_f64, int n_images, int groups, int n_cu, Db16Plan *dp);
+// ---- the 2:4 structured-sparse dense forward kernel (dense_sp24.hip, plan option "sp24") ------------------------------
+// What launch_dense_sp24 launches, or why it refuses: the bf16 kernel's limits and tile plan (db16_plan: float plans, the
+// same descriptors, tiles and persistent workgroups).  A k-step covers kDb16StepK dense k = kSp24StepKept kept values per
+// row, in kSp24StepInstr matrix instructions per 32 x 32 block; idx_bytes is the index table's descriptor range: one
+// 16-bit word per (row of the padded matrix, 16 columns of its lda) -- csr_tables.h sp24_index.
+constexpr int kSp24StepKept = kDb16StepK / 2, kSp24StepInstr = 2;
+struct Sp24Plan {
+  Db16Plan t;                         // the tile plan: bm, tiles, k-steps, workgroups, the operand descriptors' ranges
+  int idx_rows = 0, idx_row_words = 0;
+  unsigned long long idx_bytes = 0;
+};
+LaunchVerdict sp24_plan(const Geometry &g, bool is_f64, int n_images, int groups, int n_cu, Sp24Plan *sp);
 // generic / lowered: grid y or z above kGridYZMax.  The message names the kernel.
 enum GridKernel { kGridGeneric, kGridCsrmm, kGridCsrmmF64, kGridIm2col };
 LaunchVerdict grid_yz_limit(GridKernel k, unsigned long grid_y, unsigned long grid_z);

@@ -34,6 +34,32 @@ std::vector<int> dense_positions(const CsrView &v, int row_stride) {
   return pos;
 }
 
+Sp24Index sp24_index(const CsrView &v, int rows, int row_stride) {
+  const Geometry &g = *v.g;
+  const int runs = row_stride / 16;
+  // per (row, group of 4): the positions that hold an entry, as a 4-bit mask
+  std::vector<unsigned char> mask((size_t)g.d.M * runs * 4, 0);
+  Sp24Index t;
+  t.ok = rows >= g.d.M && row_stride % 16 == 0 && row_stride >= g.kdim;
+  if (!t.ok) return t;
+  for_each_entry(v, [&](const CsrEntry &c) {
+    unsigned char &m = mask[((size_t)c.grp * g.Mg + c.m) * runs * 4 + c.col / 4];
+    m |= (unsigned char)(1u << (c.col % 4));
+    if (__builtin_popcount(m) > 2) t.ok = false;
+  });
+  if (!t.ok) return t;
+  t.idx.assign((size_t)rows * runs, kSp24EmptyWord);
+  for (size_t q = 0; q < mask.size(); ++q) {
+    unsigned m = mask[q];
+    for (int pos = 0; __builtin_popcount(m) < 2; ++pos) m |= 1u << pos;     // fillers: the lowest positions without an entry
+    const int lo = __builtin_ctz(m), hi = 31 - __builtin_clz(m);
+    unsigned short &w = t.idx[q / 4];
+    const int shift = 4 * (int)(q % 4);
+    w = (unsigned short)((w & ~(0xFu << shift)) | ((unsigned)(lo | hi << 2) << shift));
+  }
+  return t;
+}
+
 GatherTables gather_transpose(const CsrView &v) {
   const Geometry &g = *v.g;
   const escoin_conv_desc &d = g.d;

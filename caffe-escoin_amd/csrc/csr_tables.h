@@ -74,6 +74,23 @@ GenericTables generic_tables(const CsrView &v);
 // row_stride = kdim: its position in blobs_[0] (wpos); row_stride = dense_lda(kdim): in the MFMA kernel's matrix.
 std::vector<int> dense_positions(const CsrView &v, int row_stride);
 
+// The 2:4 kernel's index table (dense_sp24.hip, plan option "sp24").  `ok`: the pattern qualifies -- every row of every conv
+// group has at most 2 CSR positions (entries, explicit zeros included) in each aligned group of 4 columns 4j .. 4j + 3; a
+// last group cut short by kdim counts like any other.  idx (only when ok): one 16-bit word per (row, run of 16 columns) of
+// the dense matrix, [rows][row_stride / 16] with rows >= M (the matrix's zero rows included) and row_stride =
+// dense_lda(kdim): word (r, t) covers columns 16 t .. 16 t + 15 of row r = grp * Mg + m.  Bit order, as
+// v_smfmac_f32_32x32x32_bf16 reads it (tools/probes/probe_smfmac.hip): field i = bits 2 i + 1 .. 2 i, i = 0 .. 7, is the
+// position inside group i / 2 of the run (columns 16 t + 4 (i / 2) ..) of the i-th value the lane hands over; the two fields
+// of a group ascend.  A group with fewer than 2 entries is filled up with the lowest positions that hold no entry (they may
+// lie at or past kdim: the matrix is zero there as well), so every word names 8 distinct columns and the kernel has no
+// special case; a run without entries is kSp24EmptyWord.
+constexpr unsigned short kSp24EmptyWord = 0x4444;   // positions 0 and 1 of each group
+struct Sp24Index {
+  bool ok = false;
+  std::vector<unsigned short> idx;
+};
+Sp24Index sp24_index(const CsrView &v, int rows, int row_stride);
+
 // The gather kernel's transposed CSR: per global input channel c the entries of rows trow[c] .. trow[c + 1], in
 // ascending (ocl, kr, kc) -- the order the original rows visit them in when they are walked oc by oc.
 // trow [C + 1], ttap [max(nnz, 1)] = pack_tap(ocl, kr, kc), tsrc [nnz] = the flat index of the entry at that place

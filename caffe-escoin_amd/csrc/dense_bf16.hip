@@ -27,6 +27,7 @@
 //     rows (8 lanes = the 8 slots of a row in some order): contiguous, conflict-free as well.
 // Rows past K: B stages zeros there (ktab entries past K fail the border test; the pointwise path compares k with K; past
 // ktab's end -- K rounded up to 32 -- nothing is read), and so does A past lda (up to lda the matrix's own zero padding).
+// The tile walk, the B staging, the swizzle and the epilogue live in dense_common.h: dense_sp24.hip shares them.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -37,26 +38,11 @@
 
 namespace escoin {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4b __attribute__((ext_vector_type(4)));
-
 constexpr int kBK16 = kDb16StepK;                 // k per step
-constexpr int kRowChunks = kBK16 / 8;             // 16-byte chunks per LDS row
-static_assert(kBN == kDb16TileP && kRowChunks == 8, "the swizzle and the staging maps are written for 128 x 64 tiles");
+constexpr int kRowChunks = kB16RowChunks;         // 16-byte chunks per LDS row
+static_assert(kBN == kDb16TileP && kBK16 == kB16StepK && kRowChunks == 8, "the swizzle and the staging maps are written for 128 x 64 tiles");
 
-// index (in chunks of 8 bf16) of logical chunk `chunk` of row `row` of a tile
-__device__ __forceinline__ int chunk_at(int row, int chunk) { return row * kRowChunks + (chunk ^ ((row >> 1) & 7)); }
-
-__device__ __forceinline__ bf16x8 pack8(const float (&v)[8]) {
-  const f32x8 f = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
-  return __builtin_convertvector(f, bf16x8);      // four v_cvt_pk_bf16_f32: round to nearest even, overflow to infinity
-}
-
-// BMODE: how the B tile's elements are addressed --
-//   0  gathered through ktab with the border test (any kernel / stride / padding / dilation)
-//   1  pointwise (the fp32 kernel's predicate: 1x1, stride 1, no padding, H*W % 4 == 0, bottom 16-byte aligned): row k of
-//      the column matrix is channel k of the bottom blob
+// BMODE: how the B tile's elements are addressed (dense_common.h DenseB16Stage)
 template <int WROWS, int BMODE>
 __global__ void __launch_bounds__(256, 2) escoin_dense_bf16_kernel(DenseArgs a) {
   constexpr int BM = 64 * WROWS;
@@ -64,7 +50,6 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_bf16_kernel(DenseArgs a) 
   constexpr int WN = kBN / WCOLS;            // columns per wave: 64 or 32
   constexpr int NB = WN / 32;                // 32-column blocks per wave
   constexpr int AQ = BM / 32;                // A chunks a lane stages per k-step: rows 32 q + tid / 8, chunk tid % 8
-  constexpr unsigned kOOB = 0xFFFFFFF0u;     // a byte offset no descriptor of this kernel covers: the load delivers zero
   // one array per buffer: A tile then B tile, in bf16 (the epilogue reuses a whole buffer as its fp32 staging area:
   // 4 waves x 32 x WN floats = 32 KiB of the 32 KiB buffer at BM = 128, 16 of 24 KiB at BM = 64)
   constexpr int kBufChunks = (BM + kBN) * kRowChunks;
@@ -85,43 +70,21 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_bf16_kernel(DenseArgs a) 
   const __amdgpu_buffer_rsrc_t rA = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.w), 0, a.w_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rB = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.in), 0, a.in_bytes, 0x00020000);
 
-  auto tile_coords = [&](long tile, int &cg, int &m0, int &p0) {
-    const int mt = (int)(tile % a.n_mtiles);
-    const long r = tile / a.n_mtiles;
-    const int pt = (int)(r % a.n_ptiles);
-    const int gsel = (int)(r / a.n_ptiles);
-    cg = a.group_mask == ~0ull ? gsel : nth_set_bit(a.group_mask, gsel);
-    m0 = mt * BM;
-    p0 = pt * kBN;
-  };
+  auto tile_coords = [&](long tile, int &cg, int &m0, int &p0) { dense_tile_coords(a, BM, tile, cg, m0, p0); };
 
   // ---- addressing of the tile being FETCHED (recomputed when the fetch moves to a new tile) ----
   //  A: rows 32 q + tid / 8 of the tile, chunk tid % 8
-  //  B: pixels p0 + 64 half + lane, half = 0, 1; chunks 2 wave + cc, cc = 0, 1 (k-group 16 wave .. + 15 of the step: wave-uniform)
+  //  B: dense_common.h DenseB16Stage
   unsigned fa_row = 0u;              // byte offset of the lane's first A row, column 0
-  unsigned fb_pix[2] = {0u, 0u};     // byte offset of the lane's pixel (window origin) in the blob
-  int fb_ih0[2] = {0, 0}, fb_iw0[2] = {0, 0};
+  DenseB16Stage<BMODE> bs;
   int f_cg = 0, f_m0 = 0, f_p0 = 0;
   auto fetch_setup = [&](long tile) {
     tile_coords(tile, f_cg, f_m0, f_p0);
     fa_row = (unsigned)(((size_t)f_cg * a.Mg + f_m0 + (tid >> 3)) * a.lda * 4);
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const int p = min(f_p0 + 64 * half + lane, a.P - 1);
-      const int n = p / ohw, rem = p - n * ohw;
-      if (BMODE == 1) {
-        fb_pix[half] = (unsigned)((((size_t)n * a.C + (size_t)f_cg * a.Cg) * hw + rem) * 4);
-      } else {
-        const int oh = rem / a.OW, ow = rem - oh * a.OW;
-        fb_ih0[half] = oh * a.stride_h - a.pad_h;
-        fb_iw0[half] = ow * a.stride_w - a.pad_w;
-        fb_pix[half] = (unsigned)((((long)n * a.C + (long)f_cg * a.Cg) * hw + (long)fb_ih0[half] * a.W + fb_iw0[half]) * 4);
-      }
-    }
+    bs.setup(a, f_cg, f_p0, lane, ohw, hw);
   };
   // the staging registers: one k-step of this lane's share of both tiles, fp32 as loaded
   f32x4b ra[AQ][2];
-  float rb[2][2][8];               // [half][cc][k]
   auto fetch = [&](int kstep) {
     const int k0 = kstep * kBK16;
     // A: 8 floats at column k0 + 8 (tid % 8); columns at or past lda are other rows' (or nothing): zeros
@@ -130,46 +93,10 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_bf16_kernel(DenseArgs a) 
 #pragma unroll
     for (int q = 0; q < AQ; ++q) {
       const unsigned vq = fa_row + (unsigned)((32 * q * a.lda + ka) * 4);
-      ra[q][0] = __builtin_bit_cast(f32x4b, __builtin_amdgcn_raw_buffer_load_b128(rA, (int)(a_in ? vq : kOOB), 0, 0));
-      ra[q][1] = __builtin_bit_cast(f32x4b, __builtin_amdgcn_raw_buffer_load_b128(rA, (int)(a_in ? vq + 16u : kOOB), 0, 0));
+      ra[q][0] = __builtin_bit_cast(f32x4b, __builtin_amdgcn_raw_buffer_load_b128(rA, (int)(a_in ? vq : kB16OOB), 0, 0));
+      ra[q][1] = __builtin_bit_cast(f32x4b, __builtin_amdgcn_raw_buffer_load_b128(rA, (int)(a_in ? vq + 16u : kB16OOB), 0, 0));
     }
-    const int kw = k0 + 16 * wave;
-    if (BMODE == 1) {
-#pragma unroll
-      for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const int k = kw + 8 * cc + e;
-          // rows past K are channels of the next conv group, of the next image or memory past the blob: zeros
-          const unsigned ko = (unsigned)k * (unsigned)hw * 4u;
-#pragma unroll
-          for (int half = 0; half < 2; ++half)
-            rb[half][cc][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rB, (int)(k < a.K ? fb_pix[half] + ko : kOOB), 0, 0));
-        }
-    } else {
-      // this wave's 16 taps of the step: 128 contiguous bytes at a wave-uniform address; the table ends at lda (= K rounded
-      // up to 32, a multiple of 16: a wave's taps are all inside it or all past it)
-      const bool in_tab = kw < a.lda;
-      const int4 *tp = reinterpret_cast<const int4 *>(a.ktab + (in_tab ? kw : 0));
-#pragma unroll
-      for (int cc = 0; cc < 2; ++cc)
-#pragma unroll
-        for (int e2 = 0; e2 < 4; ++e2) {
-          int4 t = {0, 0x7FFF7FFF, 0, 0x7FFF7FFF};
-          if (in_tab) t = tp[4 * cc + e2];
-#pragma unroll
-          for (int o = 0; o < 2; ++o) {
-            const int toff = o ? t.z : t.x, tdyx = o ? t.w : t.y;
-#pragma unroll
-            for (int half = 0; half < 2; ++half) {
-              const int ih = fb_ih0[half] + (tdyx & 0xFFFF), iw = fb_iw0[half] + (tdyx >> 16);
-              const bool ok = (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
-              rb[half][cc][2 * e2 + o] =
-                  __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rB, (int)(ok ? fb_pix[half] + (unsigned)(toff * 4) : kOOB), 0, 0));
-            }
-          }
-        }
-    }
+    bs.fetch(a, rB, k0, wave, hw);
   };
   // ... converted and written to buffer `buf`: one chunk per (row, 8 k)
   auto stage = [&](int buf) {
@@ -178,10 +105,7 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_bf16_kernel(DenseArgs a) 
       const float v[8] = {ra[q][0][0], ra[q][0][1], ra[q][0][2], ra[q][0][3], ra[q][1][0], ra[q][1][1], ra[q][1][2], ra[q][1][3]};
       sA(buf)[chunk_at(32 * q + (tid >> 3), tid & 7)] = pack8(v);
     }
-#pragma unroll
-    for (int half = 0; half < 2; ++half)
-#pragma unroll
-      for (int cc = 0; cc < 2; ++cc) sB(buf)[chunk_at(64 * half + lane, 2 * wave + cc)] = pack8(rb[half][cc]);
+    bs.stage(sB(buf), lane, wave);
   };
 
   f32x16 acc[2][NB];
@@ -246,81 +170,8 @@ __global__ void __launch_bounds__(256, 2) escoin_dense_bf16_kernel(DenseArgs a) 
       }
     }
 
-    // ---- epilogue (the fp32 kernel's): C/D layout col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5) ----
-    // The bias of the lane's 32 rows is fetched in one go and pinned down: a load still pending when the stores start
-    // makes the compiler wait for the previous store in front of every one of them.
-    float bv[2][16];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) {
-        const int m = m0 + wm * 64 + 32 * i + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-        bv[i][reg] = (a.bias && m < a.Mg) ? a.bias[cg * a.Mg + m] : 0.f;
-      }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int reg = 0; reg < 16; ++reg) asm volatile("" : "+v"(bv[i][reg]));
-    if (a.vec_out) {
-      // Output rows of whole pixel quads (OH*OW % 4 == 0): transposed through LDS and stored 16 bytes per lane.  Staging
-      // area: the buffer the tile's last k-step was read from (the other one holds the next tile's first step); a barrier
-      // says everybody is done reading it, the barrier at the next k-step's top that everybody is done with the staging.
-      // A wave transposes its own 32 x WN half-tiles: no cross-wave traffic.
-      __syncthreads();
-      float *stg = &sAB[buf ^ 1][wave * 32 * WN];
-      constexpr int kQPR = WN / 4;                     // quads per staged row
-      constexpr int kRowsPerIt = 64 / kQPR;            // rows one 64-lane read covers
-      const int c4 = lane % kQPR, r0 = lane / kQPR;
-      const int pq = p0 + wn * WN + 4 * c4;
-      const int nq = pq / ohw, rq = pq - nq * ohw;
-      float *oq = a.out + ((size_t)nq * a.M + (size_t)cg * a.Mg) * ohw + rq;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int row = (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-#pragma unroll
-          for (int j = 0; j < NB; ++j) {
-            float v = acc[i][j][reg] + bv[i][reg];
-            if (a.relu) v = fmaxf(v, 0.f);
-            stg[row * WN + 32 * j + li] = v;
-          }
-        }
-        // (the wave reads back what it wrote itself: LDS operations of a wave complete in order; the compiler must keep
-        // the order too)
-        asm volatile("" ::: "memory");
-        float4 vq[32 / kRowsPerIt];
-#pragma unroll
-        for (int it = 0; it < 32 / kRowsPerIt; ++it)
-          vq[it] = *reinterpret_cast<const float4 *>(&stg[(it * kRowsPerIt + r0) * WN + 4 * c4]);
-#pragma unroll
-        for (int it = 0; it < 32 / kRowsPerIt; ++it) {
-          const int m = m0 + wm * 64 + 32 * i + it * kRowsPerIt + r0;
-          if (m < a.Mg && pq < a.P) *reinterpret_cast<float4 *>(oq + (size_t)m * ohw) = vq[it];
-        }
-        asm volatile("" ::: "memory");
-      }
-      continue;
-    }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const int pj = p0 + wn * WN + 32 * j + li;
-      if (pj >= a.P) continue;
-      const int nn = pj / ohw;
-      const int rr = pj - nn * ohw;
-      float *obase = a.out + ((size_t)nn * a.M + (size_t)cg * a.Mg) * ohw + rr;
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-#pragma unroll
-        for (int reg = 0; reg < 16; ++reg) {
-          const int m = m0 + wm * 64 + 32 * i + (reg & 3) + 8 * (reg >> 2) + 4 * lh;
-          if (m >= a.Mg) continue;
-          float v = acc[i][j][reg] + bv[i][reg];
-          if (a.relu) v = fmaxf(v, 0.f);
-          obase[(size_t)m * ohw] = v;
-        }
-      }
-    }
+    // ---- epilogue (dense_common.h): staged through the buffer the tile's last k-step was read from ----
+    dense_b16_epilogue<NB>(a, acc, cg, m0, p0, wm, wn, lane, ohw, &sAB[buf ^ 1][wave * 32 * WN]);
   }
 }
 

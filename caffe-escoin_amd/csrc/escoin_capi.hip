@@ -83,7 +83,7 @@ DeviceBytes device_bytes(const escoin_plan *p) {
   const TiledArrays &t = p->tiled_dev;
   const DenseArrays &dn = p->dense;
   DeviceBytes b{p->gen.rowptr.bytes() + p->gen.taps.bytes() + p->gen.vals.bytes() + t.stream.bytes() + t.unit_hdr.bytes() +
-                    t.chan.bytes() + t.jit.code_bytes + dn.w.bytes() + dn.ktab.bytes() + dn.sk_ws.bytes() + p->col.bytes(),
+                    t.chan.bytes() + t.jit.code_bytes + dn.w.bytes() + dn.ktab.bytes() + dn.sk_ws.bytes() + dn.sp_idx.bytes() + p->col.bytes(),
                 0, 0, 0};
   if (const DenseWgradState *w = p->dwg.get()) b.dwg = w->ktab.bytes() + w->part.bytes();
   if (const UpdState *u = p->upd.get())
@@ -237,6 +237,7 @@ int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, i
   if ((rc = escoin_plan_set_option(q, "dense_gate", owner->dense_gate)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "code_loader", owner->code_loader)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "dense_math", owner->dense_math)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "sp24", owner->sp24)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "dgrad_math", owner->dgrad_math)) != ESCOIN_OK) return rc;
   if (wgrad_options) {
     if ((rc = escoin_plan_set_option(q, "wgrad_kernel", owner->wgrad_kernel)) != ESCOIN_OK) return rc;
@@ -376,6 +377,7 @@ int deconv_precheck(const escoin_plan *p, bool is_f64) {
   // (every align of either Dtype passes here first: option "dense_math" = bf16 set before a double align is refused by name too)
   if (is_f64 && p->dense_math == ESCOIN_MATH_BF16)
     return fail(ESCOIN_EINVAL, "dense_math = 1 (bf16) is for float plans: these weights are double");
+  if (is_f64 && p->sp24) return fail(ESCOIN_EINVAL, "sp24 = 1 is for float plans: these weights are double");
   if (is_f64 && p->wgrad_math == ESCOIN_MATH_BF16)     // (option "wgrad_math": likewise)
     return fail(ESCOIN_EINVAL, "wgrad_math = 1 (bf16) is for float plans: these weights are double");
   if (is_f64 && p->dgrad_math == ESCOIN_MATH_BF16)     // (option "dgrad_math": likewise)
@@ -429,6 +431,7 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
   ESCOIN_HIP_TRY(hipGetDevice(&p->device));
   free_device(p);
   if (const int rc = deconv_precheck(p, p->is_f64)) return rc;
+  p->sp24_at_align = p->sp24 != 0;
   const Geometry &g = p->g;
   const int rc_gen = p->is_f64 ? upload_generic<double>(p, stream) : upload_generic<float>(p, stream);
   if (rc_gen != ESCOIN_OK) return rc_gen;
@@ -525,6 +528,15 @@ static int upload(escoin_plan *p, hipStream_t stream, const char *jit_blob = nul
     ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
     const int rc = dense_build_ktab(p, stream);
     if (rc != ESCOIN_OK) return rc;
+    // option "sp24": the index table, where the pattern of every conv group is 2:4 (a plan aligned without the option
+    // allocates nothing)
+    if (p->sp24) {
+      const Sp24Index si = sp24_index(csr_view(p), g.d.M + dense_spare_rows(), (int)lda);
+      if (si.ok) {
+        ESCOIN_HIP_TRY(p->dense.sp_idx.upload(si.idx, stream));
+        ESCOIN_HIP_TRY(hipStreamSynchronize(stream));
+      }
+    }
   }
   if (p->use_dense) {
     p->kernel_name = dense_kernel_name();
@@ -621,6 +633,7 @@ void csr_from_dense(escoin_plan *p, const T *w) {
   p->cpu_off_valid = false;
   p->cpu_inner.plan.reset();
   p->host_aligned = true;
+  p->sp24_at_align = p->sp24 != 0;
 }
 template void csr_from_dense<float>(escoin_plan *, const float *);
 template void csr_from_dense<double>(escoin_plan *, const double *);
@@ -825,6 +838,18 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       if (value == ESCOIN_MATH_BF16 && p->is_f64 && (p->aligned || p->host_aligned))
         return fail(ESCOIN_EINVAL, "dense_math = 1 (bf16) is for float plans: this plan holds double weights");
       p->dense_math = value;
+      if (p->inner_plan()) return escoin_plan_set_option(p->inner_plan()->plan.get(), key, value);
+      return ESCOIN_OK;
+    }
+    if (!strcmp(key, "sp24")) {
+      // (read by every dense launch, so it may change between forwards -- but the index table is built by the align: a plan
+      //  aligned without the option has none; handed on like "dense_math")
+      if (value != 0 && value != 1) return fail(ESCOIN_EINVAL, "sp24 must be 0 or 1");
+      if (value && p->is_f64 && (p->aligned || p->host_aligned))
+        return fail(ESCOIN_EINVAL, "sp24 = 1 is for float plans: this plan holds double weights");
+      if (value && (p->aligned || p->host_aligned) && !p->sp24_at_align)
+        return fail(ESCOIN_ESTATE, "sp24 = 1 on a plan aligned without it: set sp24 before weight_align / weight_align_cpu / set_csr (the align builds its index table)");
+      p->sp24 = value;
       if (p->inner_plan()) return escoin_plan_set_option(p->inner_plan()->plan.get(), key, value);
       return ESCOIN_OK;
     }
@@ -1067,6 +1092,7 @@ int set_csr_host(escoin_plan *p, const int *rowptr, const int *colidx, const T *
   p->cpu_off_valid = false;
   p->cpu_inner.plan.reset();
   p->host_aligned = true;
+  p->sp24_at_align = p->sp24 != 0;
   return ESCOIN_OK;
 }
 template int set_csr_host<float>(escoin_plan *, const int *, const int *, const float *, const int *);
@@ -1163,7 +1189,8 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
     static const char *const inner_keys[] = {"kernel_choice", "code_bytes", "code_direct", "small_launch_rule", "jit_rows", "jit_records",
                                              "deal_slowest_over_mean_x1000", "deal_worst_block_x1000", "lds_bytes", "body_variant",
                                              "code_touchers", "touch_lines_per_launch",
-                                             "workgroup_columns", "streamk_gave_up", "streamk", "dense_variant", "dense_math"};
+                                             "workgroup_columns", "streamk_gave_up", "streamk", "dense_variant", "dense_math",
+                                             "sp24_pattern", "dense_sp24"};
     for (const char *k : inner_keys)
       if (!strcmp(key, k)) return escoin_plan_stat(p->inner_plan()->plan.get(), key);
   }
@@ -1201,6 +1228,8 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "streamk")) return p->dense.sk_used ? 1 : 0;
   if (!strcmp(key, "dense_variant")) return p->dense.variant_last;
   if (!strcmp(key, "dense_math")) return p->dense.math_last;
+  if (!strcmp(key, "sp24_pattern")) return p->dense.sp_idx.get<void>() ? 1 : 0;
+  if (!strcmp(key, "dense_sp24")) return p->dense.sp24_last ? 1 : 0;
   if (!strncmp(key, "bwd_", 4) || !strncmp(key, "wgrad_", 6) || !strncmp(key, "dgrad_", 6)) return bwd_stat(p, key);
   if (!strncmp(key, "upd", 3)) return upd_stat(p, key);
   if (!strncmp(key, "dwg_", 4)) return dwg_stat(p, key);

@@ -164,6 +164,19 @@ def pruned_weights(s, seed, dist="uniform"):
     return w.reshape(s.M, cg, s.KH, s.KW)
 
 
+def pattern_2of4(w):
+    """A copy of w (M, C/g, KH, KW) on a 2:4 pattern: of every aligned group of 4 along a row's flattened C/g*KH*KW axis only
+    the two largest |values| stay (ties go to the lower position); a last group of fewer than 4 keeps at most 2 as well."""
+    m, k = w.shape[0], int(np.prod(w.shape[1:]))
+    pad = np.zeros((m, (k + 3) // 4 * 4), w.dtype)
+    pad[:, :k] = w.reshape(m, k)
+    g = pad.reshape(m, -1, 4)
+    order = np.argsort(-np.abs(g), axis=2, kind="stable")      # descending |value|, equal ones in position order
+    keep = np.zeros(g.shape, bool)
+    np.put_along_axis(keep, order[:, :, :2], True, axis=2)
+    return np.where(keep, g, 0).reshape(m, -1)[:, :k].reshape(w.shape).astype(w.dtype)
+
+
 def bias_vector(s, seed):
     return uniform(seed ^ 0xB1A5, s.M, -0.1, 0.1) if s.bias else None
 

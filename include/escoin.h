@@ -182,6 +182,27 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  name (at set_option when it is aligned, else at the double align); CPU mode, the sparse kernels and the
  *                  backward's MFMA kernels ignore it (the weight gradient and the MFMA data gradient have options of their
  *                  own, "wgrad_math" and "dgrad_math" below).  Measured against the fp32 kernel in profiles/dense_bf16_mi355x.md;
+ *   "sp24" = 0 (default) / 1; any other value is ESCOIN_EINVAL.  With 1 on a float plan, every launch of the dense forward
+ *                  kernel (the launches "dense_math" names, inner plans included: the option is handed on the same way)
+ *                  runs escoin_dense_sp24_kernel on the 2:4 structured-sparse matrix instruction
+ *                  v_smfmac_f32_32x32x32_bf16 WHILE THE ALIGNED PATTERN QUALIFIES: every row of every conv group has at most
+ *                  2 CSR positions (explicit zeros count) in each aligned group of 4 columns 4j .. 4j + 3 of its Cg*KH*KW
+ *                  columns, a last group cut short by the row's end included.  A pattern that does not qualify -- at the
+ *                  align, or after a set_csr / prune / rewire / import -- runs exactly what the plan runs without the option
+ *                  (fp32 or bf16 by "dense_math", the same bits, no error).  The index table the kernel needs (about 1/32
+ *                  of the fp32 weight matrix, counted in "device_bytes") is built by the align, so the option is set before
+ *                  weight_align / set_csr / import_aligned; set to 1 on a plan aligned without it, it is refused with
+ *                  ESCOIN_ESTATE.  Between forwards it may be set to 0 and back to 1.  A plan aligned without it allocates
+ *                  nothing new.  The contract is "dense_math" = bf16's over the pattern's positions: each top element is
+ *                  the fp32 sum, in a fixed but unspecified order, of bf16_rne(w) * bf16_rne(x), plus bias and ReLU in fp32;
+ *                  deterministic, and the same bits for every n_images, stream and blob alignment.  Positions outside the
+ *                  pattern are never multiplied: a non-finite activation there does not reach the top -- except under a
+ *                  position the table uses as filler (a group with fewer than 2 entries is filled up with its lowest free
+ *                  positions), which is multiplied by the matrix's 0 and gives NaN.  The values stay in the plan's one fp32
+ *                  weight matrix (update_values / set_values / the solver step need nothing more).  Nothing turns the
+ *                  option on by itself and KERNEL_AUTO is as without it.  A double plan refuses value 1 by name (at
+ *                  set_option when it is aligned, else at the double align); CPU mode and the backward ignore it.  Measured
+ *                  in profiles/sp24_mi355x.md;
  *   "wgrad_math" = ESCOIN_MATH_FP32 (0, default) / ESCOIN_MATH_BF16 (1); any other value is ESCOIN_EINVAL.  With 1 on a float
  *                  plan, every launch of the MFMA weight-gradient stage 1 ("wgrad_kernel" = ESCOIN_WGRAD_MFMA, also on the
  *                  inner plans of "b2s" / "w2b" / "deconv", to which the option is handed on wherever "wgrad_kernel" is) runs
@@ -656,7 +677,11 @@ ESCOIN_API int escoin_plan_d2s_pack(escoin_plan *plan, const float *top_diff_dev
  * stored 16 bytes at a time + 16 if K was split across workgroups + 32 if escoin_dense_bf16_kernel ran (option "dense_math";
  * the other terms keep their meaning -- + 4: the pointwise operand's predicate held and it was addressed directly -- and the
  * 16 is never set with it); 0 before the first dense launch),
- * "dense_math" (ESCOIN_MATH_*: what the plan's last dense launch ran; 0 before the first one). */
+ * "dense_math" (ESCOIN_MATH_*: what the plan's last dense launch ran; 0 before the first one; ESCOIN_MATH_BF16 after a
+ * launch of escoin_dense_sp24_kernel, whose products are bf16 products),
+ * "sp24_pattern" (1: the aligned pattern is 2:4 and option "sp24"'s index table exists), "dense_sp24" (1: the plan's last
+ * dense launch ran escoin_dense_sp24_kernel; "dense_variant" then carries + 64 on top of its row, operand-path and
+ * store-path terms). */
 ESCOIN_API long escoin_plan_stat(const escoin_plan *plan, const char *key);
 
 /* Name of the device kernel the plan launches (the symbol rocprofv3 reports). */
