@@ -34,6 +34,8 @@ MATH_FP32, MATH_BF16 = 0, 1   # option / stat "dense_math": Plan(..., dense_math
 #                               does so for the MFMA data gradient (backward_kernel=BWD_MFMA)
 # option "sp24": Plan(..., sp24=1), set before the align, runs dense launches on the 2:4 sparse matrix instructions while the
 # aligned pattern has at most 2 entries in every aligned group of 4 columns (stats "sp24_pattern", "dense_sp24"); synth.pattern_2of4
+# option "dense_split": Plan(..., dense_split=1) runs dense launches with split-bf16 products (hi + lo terms, three products per
+# tap: fp32's order of error on the bf16 matrix cores; stat "dense_split"); ahead of dense_math, may be set between forwards
 CONV_MODE_LOWERED_GEMM, CONV_MODE_LOWERED_SPARSE, CONV_MODE_SCONV, CONV_MODE_SCONV_PAR = 0, 1, 2, 3
 
 # every symbol include/escoin.h declares (tests check the library exports all of them)

@@ -137,6 +137,11 @@ class Caffe {
   // the aligned pattern is 2:4 (include/escoin.h option "sp24").  Double layers and CPU mode run as without it
   static bool sp24() { return Get().sp24_; }
   static void set_sp24(bool on) { Get().sp24_ = on; }
+  // whether the plans float layers create from now on run their dense launches with split-bf16 products (hi + lo terms,
+  // three products: fp32's order of error on the bf16 matrix cores; include/escoin.h option "dense_split").  Ahead of
+  // dense_math; double layers and CPU mode run as without it
+  static bool dense_split() { return Get().dense_split_; }
+  static void set_dense_split(bool on) { Get().dense_split_ = on; }
   // likewise how the MFMA weight-gradient kernels (wgrad_kernel = ESCOIN_WGRAD_MFMA) and escoin_dense_wgrad of those plans
   // multiply (include/escoin.h option "wgrad_math")
   static int wgrad_math() { return Get().wgrad_math_; }
@@ -148,7 +153,7 @@ class Caffe {
 
  private:
   // the reference leaves conv_mode_ uninitialised; here it defaults to SCONV_PAR
-  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), w2b_(false), wgrad_pointwise_(false), depthwise_(false), wgrad_depthwise_(false), dense_math_(ESCOIN_MATH_FP32), wgrad_math_(ESCOIN_MATH_FP32), dgrad_math_(ESCOIN_MATH_FP32), sp24_(false) {}
+  Caffe() : mode_(CPU), conv_mode_(SCONV_PAR), cpu_threads_(0), wgrad_kernel_(ESCOIN_WGRAD_AUTO), backward_kernel_(ESCOIN_KERNEL_AUTO), s2d_(false), s2b_(false), b2s_(false), w2b_(false), wgrad_pointwise_(false), depthwise_(false), wgrad_depthwise_(false), dense_math_(ESCOIN_MATH_FP32), wgrad_math_(ESCOIN_MATH_FP32), dgrad_math_(ESCOIN_MATH_FP32), sp24_(false), dense_split_(false) {}
   Brew mode_;
   ConvMode conv_mode_;
   int cpu_threads_;
@@ -165,6 +170,7 @@ class Caffe {
   int wgrad_math_;
   int dgrad_math_;
   bool sp24_;
+  bool dense_split_;
 };
 
 // Dtype -> C ABI.  The float entry points are the unsuffixed ones, double the _f64 twins (include/escoin.h).
@@ -497,6 +503,7 @@ class BaseConvolutionLayer : public Layer<Dtype> {   // base_conv_layer.hpp:20-2
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_depthwise", Caffe::wgrad_depthwise() ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "dense_math", sizeof(Dtype) == 4 ? Caffe::dense_math() : ESCOIN_MATH_FP32));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "sp24", sizeof(Dtype) == 4 && Caffe::sp24() ? 1 : 0));
+      ESCOIN_CHECK(escoin_plan_set_option(fresh, "dense_split", sizeof(Dtype) == 4 && Caffe::dense_split() ? 1 : 0));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "wgrad_math", sizeof(Dtype) == 4 ? Caffe::wgrad_math() : ESCOIN_MATH_FP32));
       ESCOIN_CHECK(escoin_plan_set_option(fresh, "dgrad_math", sizeof(Dtype) == 4 ? Caffe::dgrad_math() : ESCOIN_MATH_FP32));
       if (plan_) escoin_plan_destroy(plan_);

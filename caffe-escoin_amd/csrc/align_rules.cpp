@@ -301,6 +301,15 @@ LaunchVerdict db16_plan(const Geometry &g, bool is_f64, int n_images, int groups
   return LaunchVerdict();
 }
 
+LaunchVerdict db3_plan(const Geometry &g, bool is_f64, int n_images, int groups, int n_cu, Db16Plan *dp) {
+  if (is_f64) return refuse_launch(ESCOIN_ESTATE, "dense_split = 1: the plan holds double weights");
+  Db16Plan p;
+  if (const LaunchVerdict v = db16_plan(g, false, n_images, groups, n_cu, &p); !v.ok()) return v;
+  p.ksteps = (g.kdim + kDb3StepK - 1) / kDb3StepK;
+  *dp = p;
+  return LaunchVerdict();
+}
+
 LaunchVerdict sp24_plan(const Geometry &g, bool is_f64, int n_images, int groups, int n_cu, Sp24Plan *sp) {
   if (is_f64) return refuse_launch(ESCOIN_ESTATE, "sp24 = 1: the plan holds double weights");
   Sp24Plan p;

@@ -149,6 +149,12 @@ struct Sp24Plan {
   unsigned long long idx_bytes = 0;
 };
 LaunchVerdict sp24_plan(const Geometry &g, bool is_f64, int n_images, int groups, int n_cu, Sp24Plan *sp);
+// ---- the dense forward kernel's split-bf16 math mode (dense_bf16x3.hip, plan option "dense_split") --------------------
+// What launch_dense_bf16x3 launches, or why it refuses: db16_plan's refusals (by this option's name), descriptors, tiles
+// and persistent workgroups, walked in k-steps of kDb3StepK: each operand takes two bf16 terms of LDS, so a 128-byte LDS
+// row holds half the k.
+constexpr int kDb3StepK = kDb16StepK / 2;
+LaunchVerdict db3_plan(const Geometry &g, bool is_f64, int n_images, int groups, int n_cu, Db16Plan *dp);
 // generic / lowered: grid y or z above kGridYZMax.  The message names the kernel.
 enum GridKernel { kGridGeneric, kGridCsrmm, kGridCsrmmF64, kGridIm2col };
 LaunchVerdict grid_yz_limit(GridKernel k, unsigned long grid_y, unsigned long grid_z);

@@ -1,6 +1,7 @@
 // dense_common.h -- what the dense forward kernels (dense_mfma.hip: fp32 products; dense_bf16.hip: plan option
-// "dense_math" = ESCOIN_MATH_BF16; dense_sp24.hip: plan option "sp24") share: the GEMM view's pixel tile, the launch's
-// argument block, and -- between the two kernels that multiply bf16 -- the tile walk, the B tile's staging and the epilogue.
+// "dense_math" = ESCOIN_MATH_BF16; dense_sp24.hip: plan option "sp24"; dense_bf16x3.hip: plan option "dense_split") share:
+// the GEMM view's pixel tile, the launch's argument block, and -- between the kernels that multiply bf16 -- the tile walk, the
+// B tile's staging and the epilogue.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -141,6 +142,75 @@ struct DenseB16Stage {
     for (int half = 0; half < 2; ++half)
 #pragma unroll
       for (int cc = 0; cc < 2; ++cc) sB[chunk_at(64 * half + lane, 2 * wave + cc)] = pack8(rb[half][cc]);
+  }
+};
+
+// ---- dense_bf16x3.hip (plan option "dense_split"): every fp32 operand as two bf16 terms ----------------------------------
+// hi = rne(v), lo = rne(v - float(hi)): the subtraction is exact (hi is v's leading 8 bits), so |v - hi - lo| <= 2^-18 |v|
+// while lo does not underflow.  A zero gives two zeros; a value past bf16's largest finite one gives hi = +-inf and a lo of
+// the other sign (NaN where v itself is infinite).
+__device__ __forceinline__ void split8(const float (&v)[8], bf16x8 &hi, bf16x8 &lo) {
+  const f32x8 f = {v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]};
+  hi = __builtin_convertvector(f, bf16x8);       // four v_cvt_pk_bf16_f32, as pack8
+  // float(hi) from the packed pairs -- a shift for the low half, a mask for the high one -- so that hi stays packed
+  const u32x4d hu = __builtin_bit_cast(u32x4d, hi);
+  f32x8 d;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    d[2 * p] = v[2 * p] - __builtin_bit_cast(float, hu[p] << 16);
+    d[2 * p + 1] = v[2 * p + 1] - __builtin_bit_cast(float, hu[p] & 0xFFFF0000u);
+  }
+  lo = __builtin_convertvector(d, bf16x8);
+}
+
+// The B tile's staging in k-steps of 32, [p][32 k hi and lo]: the pixels and their addressing are DenseB16Stage's (setup);
+// a lane owns the same two pixels and the 8 k of the step that its wave covers (k-chunk `wave`) -- eight 4-byte loads per
+// half -- and writes two chunks per pixel: the hi terms at logical chunk 2 wave, the lo terms at 2 wave + 1.  A step never
+// reaches past ktab's end (K rounded up to 32 is a whole number of steps).
+template <int BMODE>
+struct DenseSplitStage : DenseB16Stage<BMODE> {
+  float rs[2][8];                  // [half][k]: one k-step of the lane's share, fp32 as loaded
+
+  __device__ __forceinline__ void fetch32(const DenseArgs &a, __amdgpu_buffer_rsrc_t rB, int k0, int wave, int hw) {
+    const int kw = k0 + 8 * wave;
+    if (BMODE == 1) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        // rows past K are channels of the next conv group, of the next image or memory past the blob: zeros
+        const unsigned ko = (unsigned)(kw + e) * (unsigned)hw * 4u;
+#pragma unroll
+        for (int half = 0; half < 2; ++half)
+          rs[half][e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rB, (int)(kw + e < a.K ? this->pix[half] + ko : kB16OOB), 0, 0));
+      }
+    } else {
+      // this wave's 8 taps of the step: 64 contiguous bytes at a wave-uniform address, inside the table (kw < lda)
+      const int4 *tp = reinterpret_cast<const int4 *>(a.ktab + kw);
+#pragma unroll
+      for (int e2 = 0; e2 < 4; ++e2) {
+        const int4 t = tp[e2];
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+          const int toff = o ? t.z : t.x, tdyx = o ? t.w : t.y;
+#pragma unroll
+          for (int half = 0; half < 2; ++half) {
+            const int ih = this->ih0[half] + (tdyx & 0xFFFF), iw = this->iw0[half] + (tdyx >> 16);
+            const bool ok = (unsigned)ih < (unsigned)a.H && (unsigned)iw < (unsigned)a.W;
+            rs[half][2 * e2 + o] =
+                __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rB, (int)(ok ? this->pix[half] + (unsigned)(toff * 4) : kB16OOB), 0, 0));
+          }
+        }
+      }
+    }
+  }
+  // ... split and written to the B tile at sB: two chunks per (pixel, 8 k)
+  __device__ __forceinline__ void stage_split(bf16x8 *sB, int lane, int wave) const {
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+      bf16x8 hi, lo;
+      split8(rs[half], hi, lo);
+      sB[chunk_at(64 * half + lane, 2 * wave)] = hi;
+      sB[chunk_at(64 * half + lane, 2 * wave + 1)] = lo;
+    }
   }
 };
 

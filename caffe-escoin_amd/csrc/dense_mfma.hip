@@ -600,15 +600,22 @@ int dense_build_ktab(escoin_plan *p, hipStream_t stream) {
 
 DenseBf16Launch g_dense_bf16_launch = nullptr;
 DenseBf16Launch g_dense_sp24_launch = nullptr;
+DenseBf16Launch g_dense_split_launch = nullptr;
 
 int launch_dense(const escoin_plan *p, const float *bottom, const float *bias, float *top,
                  int n_images, hipStream_t stream) {
   // option "sp24": while the aligned pattern is 2:4 (the index table exists) every launch is dense_sp24.hip's; a pattern
   // that does not qualify runs as without the option
   p->dense.sp24_last = false;
+  p->dense.split_last = false;
   if (p->sp24 && p->dense.sp_idx.get<void>()) {
     if (!g_dense_sp24_launch) return fail(ESCOIN_EINVAL, "option \"sp24\": this build does not carry the 2:4 dense kernel");
     return g_dense_sp24_launch(p, bottom, bias, top, n_images, stream);
+  }
+  // option "dense_split": every launch of a plan that asks for split-bf16 products is dense_bf16x3.hip's, ahead of "dense_math"
+  if (p->dense_split) {
+    if (!g_dense_split_launch) return fail(ESCOIN_EINVAL, "option \"dense_split\": this build does not carry the split-bf16 dense kernel");
+    return g_dense_split_launch(p, bottom, bias, top, n_images, stream);
   }
   // option "dense_math": every launch of a plan that asks for bf16 products is dense_bf16.hip's
   if (p->dense_math == ESCOIN_MATH_BF16) {

@@ -238,6 +238,7 @@ int build_derived_plan(const escoin_plan *owner, const escoin_conv_desc &desc, i
   if ((rc = escoin_plan_set_option(q, "code_loader", owner->code_loader)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "dense_math", owner->dense_math)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "sp24", owner->sp24)) != ESCOIN_OK) return rc;
+  if ((rc = escoin_plan_set_option(q, "dense_split", owner->dense_split)) != ESCOIN_OK) return rc;
   if ((rc = escoin_plan_set_option(q, "dgrad_math", owner->dgrad_math)) != ESCOIN_OK) return rc;
   if (wgrad_options) {
     if ((rc = escoin_plan_set_option(q, "wgrad_kernel", owner->wgrad_kernel)) != ESCOIN_OK) return rc;
@@ -378,6 +379,7 @@ int deconv_precheck(const escoin_plan *p, bool is_f64) {
   if (is_f64 && p->dense_math == ESCOIN_MATH_BF16)
     return fail(ESCOIN_EINVAL, "dense_math = 1 (bf16) is for float plans: these weights are double");
   if (is_f64 && p->sp24) return fail(ESCOIN_EINVAL, "sp24 = 1 is for float plans: these weights are double");
+  if (is_f64 && p->dense_split) return fail(ESCOIN_EINVAL, "dense_split = 1 is for float plans: these weights are double");
   if (is_f64 && p->wgrad_math == ESCOIN_MATH_BF16)     // (option "wgrad_math": likewise)
     return fail(ESCOIN_EINVAL, "wgrad_math = 1 (bf16) is for float plans: these weights are double");
   if (is_f64 && p->dgrad_math == ESCOIN_MATH_BF16)     // (option "dgrad_math": likewise)
@@ -853,6 +855,15 @@ int escoin_plan_set_option(escoin_plan *p, const char *key, int value) {
       if (p->inner_plan()) return escoin_plan_set_option(p->inner_plan()->plan.get(), key, value);
       return ESCOIN_OK;
     }
+    if (!strcmp(key, "dense_split")) {
+      // (no state of its own, like "dense_math": read by every dense launch, handed on the same way)
+      if (value != 0 && value != 1) return fail(ESCOIN_EINVAL, "dense_split must be 0 or 1");
+      if (value && p->is_f64 && (p->aligned || p->host_aligned))
+        return fail(ESCOIN_EINVAL, "dense_split = 1 is for float plans: this plan holds double weights");
+      p->dense_split = value;
+      if (p->inner_plan()) return escoin_plan_set_option(p->inner_plan()->plan.get(), key, value);
+      return ESCOIN_OK;
+    }
     if (!strcmp(key, "dgrad_math")) {
       // (no state of its own either: read by every launch of the MFMA data-gradient kernel, so it may change between
       //  backwards; handed on like "dense_math")
@@ -1190,7 +1201,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
                                              "deal_slowest_over_mean_x1000", "deal_worst_block_x1000", "lds_bytes", "body_variant",
                                              "code_touchers", "touch_lines_per_launch",
                                              "workgroup_columns", "streamk_gave_up", "streamk", "dense_variant", "dense_math",
-                                             "sp24_pattern", "dense_sp24"};
+                                             "sp24_pattern", "dense_sp24", "dense_split"};
     for (const char *k : inner_keys)
       if (!strcmp(key, k)) return escoin_plan_stat(p->inner_plan()->plan.get(), key);
   }
@@ -1230,6 +1241,7 @@ long escoin_plan_stat(const escoin_plan *p, const char *key) {
   if (!strcmp(key, "dense_math")) return p->dense.math_last;
   if (!strcmp(key, "sp24_pattern")) return p->dense.sp_idx.get<void>() ? 1 : 0;
   if (!strcmp(key, "dense_sp24")) return p->dense.sp24_last ? 1 : 0;
+  if (!strcmp(key, "dense_split")) return p->dense.split_last ? 1 : 0;
   if (!strncmp(key, "bwd_", 4) || !strncmp(key, "wgrad_", 6) || !strncmp(key, "dgrad_", 6)) return bwd_stat(p, key);
   if (!strncmp(key, "upd", 3)) return upd_stat(p, key);
   if (!strncmp(key, "dwg_", 4)) return dwg_stat(p, key);

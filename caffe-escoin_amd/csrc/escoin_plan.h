@@ -332,6 +332,9 @@ struct DenseArrays {
   // kernel (escoin_plan_stat "dense_sp24"; "dense_variant" + 64)
   DeviceBuffer sp_idx;
   mutable bool sp24_last = false;
+  // option "dense_split": the last dense launch ran dense_bf16x3.hip's kernel (escoin_plan_stat "dense_split";
+  // "dense_variant" + 128, "dense_math" reads bf16)
+  mutable bool split_last = false;
 };
 
 }  // namespace escoin
@@ -391,7 +394,8 @@ struct escoin_plan {
   int dense_threshold_pct = -1;   // option "dense_threshold_pct" (-1: the measured default)
   int dense_math = ESCOIN_MATH_FP32;   // option "dense_math": ESCOIN_MATH_BF16 = every dense launch runs dense_bf16.hip's kernel
   int sp24 = 0;                   // option "sp24": 1 = dense launches run dense_sp24.hip's kernel while the aligned pattern is 2:4
-  bool sp24_at_align = false;     // ... and its value at the last align: only then was the index table looked for
+  int dense_split = 0;            // option "dense_split": 1 = every dense launch runs dense_bf16x3.hip's kernel (ahead of dense_math)
+  bool sp24_at_align = false;    // ... and its value at the last align: only then was the index table looked for
   int body_variant = -1;          // option "body_variant": -1 the rule (align_rules.h body_variant), 0 always the generic body
   int code_touchers = 0;          // option "code_touchers": 0 the rule (align_rules.h touch_election), k >= 1 every k-th workgroup of an XCD and grid row
   int stream_stores = -1;         // option "stream_stores": pointwise layers write the top blob with non-temporal stores (1), never (0), by size (-1)
@@ -576,6 +580,8 @@ typedef int (*DenseBf16Launch)(const escoin_plan *p, const float *bottom, const 
 extern DenseBf16Launch g_dense_bf16_launch;   // dense_mfma.hip
 // dense_sp24.hip (option "sp24"): likewise, for the launches of a plan whose option is on and whose index table exists
 extern DenseBf16Launch g_dense_sp24_launch;   // dense_mfma.hip
+// dense_bf16x3.hip (option "dense_split"): likewise, for every launch of a plan whose option is on
+extern DenseBf16Launch g_dense_split_launch;  // dense_mfma.hip
 
 // wgrad_mfma.hip (option "wgrad_kernel" = MFMA): builds the kernel's tables for the tile plan bwd_choice made; stage 1 of
 // the weight gradient of the plan's nnz entries over `chunks` chunks of n_images images into slab_w [chunks][nnz]

@@ -182,6 +182,28 @@ ESCOIN_API int escoin_plan_destroy(escoin_plan *plan);
  *                  name (at set_option when it is aligned, else at the double align); CPU mode, the sparse kernels and the
  *                  backward's MFMA kernels ignore it (the weight gradient and the MFMA data gradient have options of their
  *                  own, "wgrad_math" and "dgrad_math" below).  Measured against the fp32 kernel in profiles/dense_bf16_mi355x.md;
+ *   "dense_split" = 0 (default) / 1; any other value is ESCOIN_EINVAL.  With 1 on a float plan, every launch of the dense
+ *                  forward kernel (the launches "dense_math" names, inner plans included: the option is handed on the same
+ *                  way) runs escoin_dense_bf16x3_kernel: split-bf16 products on the bf16 matrix cores (BF16x3), fp32's order
+ *                  of error.  The staging lane splits every fp32 operand v into two bf16 terms, hi(v) = bf16_rne(v) and
+ *                  lo(v) = bf16_rne(v - hi(v)) (the subtraction is exact); each top element is the fp32 sum, in a fixed but
+ *                  unspecified order, of the exact products hi(w) hi(x), hi(w) lo(x) and lo(w) hi(x) over the taps; bias and
+ *                  ReLU are applied in fp32.  Deterministic: the same bits for every n_images, stream and blob alignment.
+ *                  The bound, for operands that are zero or of magnitude at least 2^-100: |v - hi| <= 2^-9 |v|, so
+ *                  |lo| <= 2^-9 |v| and e(v) = v - hi - lo has |e| <= 2^-9 |v - hi| <= 2^-18 |v|.  Then
+ *                      w x = [hi(w) hi(x) + hi(w) lo(x) + lo(w) hi(x)] + lo(w) lo(x) + e(w) x + (w - e(w)) e(x),
+ *                  and the three dropped terms are at most 2^-18, 2^-18 and (1 + 2^-18) 2^-18 times |w||x|: together less
+ *                  than 4 * 2^-18 |w||x|.  Element-wise, the distance to the exact result of the unsplit operands is at most
+ *                  2^-16 * sum |w||x| plus the fp32 accumulation bound of the 3 K products summed.  Below 2^-100 lo(v)
+ *                  underflows (it may be flushed to zero), and the contract falls back to "dense_math" = bf16's bound.  An
+ *                  operand above bf16's largest finite value gives a non-finite result (hi is infinite, lo is infinite of
+ *                  the other sign, or NaN where the operand itself is infinite); a non-finite operand that meets a pruned
+ *                  zero weight gives NaN, as in the other dense kernels.  Precedence in a dense launch: a qualifying "sp24"
+ *                  launch, then "dense_split", then "dense_math", then fp32.  It holds no state (the kernel reads the plan's
+ *                  one fp32 weight matrix) and may be set at any time, also between forwards of an aligned plan; nothing
+ *                  turns it on by itself and KERNEL_AUTO is as without it.  Launches run whole tiles ("streamk" reads 0).  A
+ *                  double plan refuses value 1 by name (at set_option when it is aligned, else at the double align); CPU
+ *                  mode, the sparse kernels and the backward ignore it.  Measured in profiles/dense_split_mi355x.md;
  *   "sp24" = 0 (default) / 1; any other value is ESCOIN_EINVAL.  With 1 on a float plan, every launch of the dense forward
  *                  kernel (the launches "dense_math" names, inner plans included: the option is handed on the same way)
  *                  runs escoin_dense_sp24_kernel on the 2:4 structured-sparse matrix instruction
@@ -681,7 +703,9 @@ ESCOIN_API int escoin_plan_d2s_pack(escoin_plan *plan, const float *top_diff_dev
  * launch of escoin_dense_sp24_kernel, whose products are bf16 products),
  * "sp24_pattern" (1: the aligned pattern is 2:4 and option "sp24"'s index table exists), "dense_sp24" (1: the plan's last
  * dense launch ran escoin_dense_sp24_kernel; "dense_variant" then carries + 64 on top of its row, operand-path and
- * store-path terms). */
+ * store-path terms), "dense_split" (1: the plan's last dense launch ran escoin_dense_bf16x3_kernel, option "dense_split";
+ * "dense_variant" then carries + 128 on top of those terms, "dense_math" reads ESCOIN_MATH_BF16 -- the operands of the
+ * matrix instructions are bf16 -- and "streamk" 0). */
 ESCOIN_API long escoin_plan_stat(const escoin_plan *plan, const char *key);
 
 /* Name of the device kernel the plan launches (the symbol rocprofv3 reports). */
